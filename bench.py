@@ -12,6 +12,8 @@ synthetic 7-DOF, 2000-sample joint-space paths already resident in HBM.
   ... --workload configs2                 BASELINE.json configs[2]: 8192 paths per GPU
                                           (65536 over 8 GPUs)
   ... --gather full                       gather q(t) as well (t, sd, sdd, q), in chunks
+  ... --dump-outputs DIR                  after the timed steps, write the last timed step's outputs
+                                          (rank 0's shard) as DIR/<name>.npy, see dump_outputs()
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
 """
@@ -35,6 +37,11 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 # every 4 cycles.
 VALU_PEAK_LANE_OPS = 256 * 4 * 16 * 2.4e9
 WORKLOADS = {"configs1": 1024, "configs2": 8192}
+DUMP_BUDGET_BYTES = 64 * 10**6       # --dump-outputs on disk: arrays plus DUMP_HEADER_BYTES
+DUMP_HEADER_BYTES = 4096             # the .npy headers of the 11 files (128 bytes each)
+DUMP_SUBSET_SEED = 20240601
+DUMP_PER_PATH_KEYS = ("status", "last_extremal_index", "max_time_increment")
+DUMP_PER_SAMPLE_KEYS = ("time", "s", "sd", "sdd", "q", "qd", "qdd")
 
 
 def baseline_metric():
@@ -63,6 +70,42 @@ def gather_bytes_per_path(mode, D, N):
     if mode == "compact":
         return 8 * N * 2 + 16
     return 8 * N * 3 + (8 * N * D if mode == "full" else 0)
+
+
+def dump_path_subset(B, D, N):
+    """Sorted indices (into the B-path batch) of the paths whose per-sample outputs --dump-outputs
+    writes: every path if all of them fit the 64 MB budget, else a fixed seeded subset, so that two
+    runs with the same arguments write the same paths. Per-path scalars and the index list are
+    always written in full and count against the budget as well."""
+    per_path = 8 * N * (4 + 3 * D) + 8      # time, s, sd, sdd [N]; q, qd, qdd [N][D]; path_index
+    k = min(B, (DUMP_BUDGET_BYTES - DUMP_HEADER_BYTES - 8 * B * len(DUMP_PER_PATH_KEYS)) // per_path)
+    if k < 1:
+        raise SystemExit("bench.py: one path's outputs (%d bytes) exceed the --dump-outputs budget of "
+                         "%d bytes" % (per_path, DUMP_BUDGET_BYTES))
+    import numpy as np
+    if k == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SUBSET_SEED).choice(B, size=k, replace=False))
+
+
+def dump_outputs(out, subset, first_path_index, dirname):
+    """Write the outputs `out` (time_joint_paths' dict of tensors) as float64 DIR/<name>.npy:
+    status, last_extremal_index, max_time_increment [B] for every path; time, s, sd, sdd [k][N]
+    and q, qd, qdd [k][N][D] for the k paths of `subset`, whose global indices go to
+    path_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    idx = torch.as_tensor(subset, dtype=torch.int64, device=out["time"].device)
+    arrays = {"path_index": np.asarray(subset, dtype=np.float64) + first_path_index}
+    for k in DUMP_PER_PATH_KEYS:
+        arrays[k] = out[k].to(torch.float64).cpu().numpy()
+    for k in DUMP_PER_SAMPLE_KEYS:
+        arrays[k] = out[k].index_select(0, idx).to(torch.float64).cpu().numpy()
+    paths = [os.path.join(dirname, k + ".npy") for k in arrays]
+    for p, a in zip(paths, arrays.values()):
+        np.save(p, a)
+    return sum(os.path.getsize(p) for p in paths)
 
 
 def kernel_source_hash():
@@ -226,7 +269,13 @@ def main():
                     help="untimed solves of the same batch before the W warm-up steps, until this much "
                          "wall time has passed: the GPU's clocks need a few hundred ms of load to settle "
                          "(0.56 -> 0.52 ms per step measured); 0 = off. Reported in config.")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's "
+                         "shard) as float64 DIR/<name>.npy, at most 64 MB: the per-path scalars of "
+                         "every path and the per-sample arrays of a fixed seeded subset of paths")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     import numpy as np  # noqa: F401
     import torch
@@ -266,6 +315,7 @@ def main():
     total_paths = B * world
     lo, hi = shd.shard_bounds(total_paths, world, rank)
     assert hi - lo == B
+    subset = dump_path_subset(B, D, N) if args.dump_outputs else None
     batch = syn.make_joint_batch(B, D, N, first_path_index=lo)
     P = batch["control_points"].shape[1]
     E = eng.Engine(dev_index)
@@ -443,6 +493,10 @@ def main():
                   file=sys.stderr)
     # every path of the LAST timed step must have been solved (status is rewritten by each step)
     ok = int((outs[(counter[0] - 1) % 2]["status"] == 0).sum()) if counter[0] else 0
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(outs[(counter[0] - 1) % 2], subset, lo, args.dump_outputs)
+        print("bench.py: last timed step's outputs (per-sample arrays of %d of %d paths, %.1f MB) in %s"
+              % (len(subset), B, nbytes / 1e6, args.dump_outputs), file=sys.stderr)
     dominant_ms = E.profile_mean_ms(eng.KERNEL_SWEEP)[0] if timing else 0.0
     if timing and rank == 0:
         # the other kernels' durations, outside the timed region (events around every kernel

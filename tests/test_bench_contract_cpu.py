@@ -67,3 +67,34 @@ def test_gather_payload_bytes_and_counter_file_binding(tmp_path, monkeypatch):
     r = bench.roofline_block({"k_sweep": (0.4, 20)}, 0.4, 1024, 7, 2000, 28, 0.7)
     assert r["traffic"] == 5 and r["step_traffic"] == 5 and r["valu"]["busy_pct"] == 40.0
     assert "instruction issue" in r["limiter"]
+
+
+def test_dump_outputs_sample_budget_and_files(tmp_path):
+    """--dump-outputs: a fixed subset of paths within 64 MB on disk at the benchmarked shapes, every
+    array a float64 .npy holding the rows of the chosen paths."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    for B, D, N in ((1024, 7, 2000), (8192, 7, 2000), (1024, 14, 2000)):
+        s = bench.dump_path_subset(B, D, N)
+        assert len(s) < B and (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < B
+        assert (s == bench.dump_path_subset(B, D, N)).all()                  # same paths on every run
+        assert 8 * 3 * B + len(s) * (8 * N * (4 + 3 * D) + 8) + 11 * 128 <= 64 * 10**6
+    assert (bench.dump_path_subset(5, 7, 300) == np.arange(5)).all()         # small batches: every path
+    B, D, N = 6, 3, 10
+    g = torch.Generator().manual_seed(1)
+    out = {k: torch.rand(B, N, dtype=torch.float64, generator=g) for k in ("time", "s", "sd", "sdd")}
+    out.update({k: torch.rand(B, N, D, dtype=torch.float64, generator=g) for k in ("q", "qd", "qdd")})
+    out["status"] = torch.arange(B, dtype=torch.int32)
+    out["last_extremal_index"] = torch.arange(B, dtype=torch.int32) * 3
+    out["max_time_increment"] = torch.rand(B, dtype=torch.float64, generator=g)
+    sample = np.array([1, 4])
+    nbytes = bench.dump_outputs(out, sample, 100, str(tmp_path / "d"))
+    files = {p.stem: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert set(files) == set(out) | {"path_index"}
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(p.stat().st_size for p in (tmp_path / "d").iterdir()) == nbytes
+    assert nbytes == sum(a.nbytes for a in files.values()) + 11 * 128     # .npy headers
+    assert (files["path_index"] == [101, 104]).all()
+    assert (files["status"] == np.arange(B)).all() and files["max_time_increment"].shape == (B,)
+    assert (files["q"] == out["q"].numpy()[sample]).all() and files["time"].shape == (2, N)
