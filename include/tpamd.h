@@ -488,6 +488,54 @@ int tpamd_resample_skip_device(tpamd_engine *engine, const tpamd_resample_args *
 int tpamd_resample_skip_host(tpamd_engine *engine, const tpamd_resample_args *args);
 
 /* ------------------------------------------------------------------------
+ * Fastest stop: PathTimingTrajectory::GetPathStopParameter (path_timing_trajectory.cc:235-287)
+ * with ComputeFastestStop (:75-172) on a batch of timed paths. For path b and query_time[b]:
+ * the start index is the lower_bound of query_time[b] in time[b][0 .. count[b]); from there the
+ * path is time-scaled to rest as fast as max_acceleration[b] allows. Outputs the path parameter
+ * s[b][stop_index] of the sample the robot could be at rest at, stop_index (absolute, within
+ * the row), the stopping duration and a TPAMD_PLAN_* status: TPAMD_PLAN_INVALID_ARGUMENT if no
+ * sample is at or after the query time ("not in timed path range"; stop_parameter 0, stop_index
+ * -1). A query on the last sample gives s[b][count-1], duration 0.
+ * Rows are the outputs of tpamd_time_joint_paths_* (count = num_samples_per_path) or of
+ * tpamd_resample_* (out_*, count) as they are. count [B] may be NULL (every row has `stride`
+ * samples); counts are clamped to [0, stride]. profile_time / profile_rate2 / profile_drate2
+ * [B][stride] (all three or none) receive ComputeFastestStop's append_time /
+ * append_rate_squared / append_diff_rate_squared samples, stop_index - start + 1 per path
+ * (nothing for an invalid query); the braking velocities are qd * sqrt(rate2). Results are
+ * bit-identical to the scalar restatement in host/fastest_stop.cc. Non-finite inputs are
+ * outside the contract. Device pointers.
+ * ------------------------------------------------------------------------ */
+typedef struct tpamd_fastest_stop_args {
+  int32_t num_paths, stride, num_dofs; /* num_dofs 1..16 */
+  int32_t reserved;
+  const double *time, *s;              /* [B][stride] */
+  const double *qd, *qdd;              /* [B][stride][D] */
+  const int32_t *count;                /* [B] samples per row; NULL: stride */
+  const double *max_acceleration;      /* [B][D] */
+  const double *query_time;            /* [B] seconds */
+  double *stop_parameter;              /* [B] */
+  int32_t *stop_index;                 /* [B] */
+  double *duration;                    /* [B] */
+  int32_t *status;                     /* [B] TPAMD_PLAN_* */
+  double *profile_time, *profile_rate2, *profile_drate2; /* [B][stride], NULL: not written */
+} tpamd_fastest_stop_args;
+
+int tpamd_fastest_stop_device(tpamd_engine *engine, const tpamd_fastest_stop_args *args,
+                              void *hip_stream);
+/* Same with HOST pointers in args (copies in, runs, copies out, synchronises). */
+int tpamd_fastest_stop_host(tpamd_engine *engine, const tpamd_fastest_stop_args *args);
+
+/* GetPathStopParameter(time) for `count` planners of a set (ids[count], or planners
+ * 0..count-1 if ids is NULL) on their resident trajectories after the last Plan: time_ns [count]
+ * (TimeToSec: ns / 1e9), stop_parameter, duration (may be NULL), status [count] TPAMD_PLAN_*.
+ * A planner without a plan yet gives 0.0 with TPAMD_PLAN_OK (:239-242). Every id is checked
+ * before anything runs. One launch; 8 bytes per planner up (12 with ids) and 20 down; no planner
+ * state changes. Host pointers; synchronises. */
+int tpamd_planner_set_stop_parameters(tpamd_planner_set *set, int count, const int32_t *ids,
+                                      const int64_t *time_ns, double *stop_parameter,
+                                      double *duration, int32_t *status);
+
+/* ------------------------------------------------------------------------
  * Debug/inspection: copy the boundary curve of the LAST solve to host arrays
  * [B][N] (Boundary::sd2_max, sdd_max_for_sd2_max, sdd_min_for_sd2_max,
  * sd2_max_for_sdd0, type; time_optimal_path_timing.h:225-255) and the squared

@@ -15,6 +15,7 @@
 #include "tpamd_kernels.h"
 #include "tpamd_launch.h"
 #include "tpamd_planner_set.h"
+#include "tpamd_stop.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 
 using namespace tpamd;
@@ -1741,6 +1742,83 @@ int tpamd_resample_skip_host(tpamd_engine *e, const tpamd_resample_args *a) {
   return resample_host(e, a, true);
 }
 
+int tpamd_fastest_stop_device(tpamd_engine *e, const tpamd_fastest_stop_args *a, void *hip_stream) {
+  if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
+  if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (a->stride < 1 || a->num_dofs < 1 || a->num_dofs > 16) return TPAMD_E_INVALID_ARGUMENT;
+  if (!a->time || !a->s || !a->qd || !a->qdd || !a->max_acceleration || !a->query_time ||
+      !a->stop_parameter || !a->stop_index || !a->duration || !a->status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  const int np = (a->profile_time != nullptr) + (a->profile_rate2 != nullptr) + (a->profile_drate2 != nullptr);
+  if (np != 0 && np != 3) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  FastestStopParams p{};
+  p.Q = a->num_paths; p.stride = a->stride;
+  p.time = a->time; p.s = a->s; p.qd = a->qd; p.qdd = a->qdd; p.count = a->count;
+  p.amax = a->max_acceleration; p.query_sec = a->query_time;
+  p.stop_s = a->stop_parameter; p.stop_index = a->stop_index; p.duration = a->duration; p.status = a->status;
+  p.p_time = a->profile_time; p.p_rate2 = a->profile_rate2; p.p_drate2 = a->profile_drate2;
+  if (!launch_fastest_stop(a->num_dofs, p, (hipStream_t)hip_stream)) return TPAMD_E_INVALID_ARGUMENT;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_fastest_stop_host(tpamd_engine *e, const tpamd_fastest_stop_args *a) {
+  if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
+  if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (a->stride < 1 || a->num_dofs < 1 || a->num_dofs > 16) return TPAMD_E_INVALID_ARGUMENT;
+  if (!a->time || !a->s || !a->qd || !a->qdd || !a->max_acceleration || !a->query_time ||
+      !a->stop_parameter || !a->stop_index || !a->duration || !a->status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  const bool prof = a->profile_time != nullptr;
+  const int np = prof + (a->profile_rate2 != nullptr) + (a->profile_drate2 != nullptr);
+  if (np != 0 && np != 3) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = a->num_paths, M = a->stride, D = a->num_dofs;
+  TPAMD_ON_DEVICE(e);
+  for (int pass = 0; pass < 2; pass++) {
+    Stage s(pass ? e->stage_base : nullptr);
+    double *d_t = s.take<double>(B * M), *d_s = s.take<double>(B * M);
+    double *d_qd = s.take<double>(B * M * D), *d_qdd = s.take<double>(B * M * D);
+    int32_t *d_cnt = a->count ? s.take<int32_t>(B) : nullptr;
+    double *d_am = s.take<double>(B * D), *d_q = s.take<double>(B);
+    double *o_s = s.take<double>(B), *o_dur = s.take<double>(B);
+    int32_t *o_idx = s.take<int32_t>(B), *o_st = s.take<int32_t>(B);
+    double *o_pt = prof ? s.take<double>(B * M) : nullptr, *o_pr = prof ? s.take<double>(B * M) : nullptr,
+           *o_pd = prof ? s.take<double>(B * M) : nullptr;
+    if (!pass) {
+      int rc = ensure_stage(e, s.off);
+      if (rc) return rc;
+      continue;
+    }
+    hipStream_t st = nullptr;
+    HIPCHK(hipMemcpyAsync(d_t, a->time, B * M * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_s, a->s, B * M * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qd, a->qd, B * M * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qdd, a->qdd, B * M * D * 8, hipMemcpyHostToDevice, st));
+    if (d_cnt) HIPCHK(hipMemcpyAsync(d_cnt, a->count, B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_am, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_q, a->query_time, B * 8, hipMemcpyHostToDevice, st));
+    tpamd_fastest_stop_args da = *a;
+    da.time = d_t; da.s = d_s; da.qd = d_qd; da.qdd = d_qdd; da.count = d_cnt;
+    da.max_acceleration = d_am; da.query_time = d_q;
+    da.stop_parameter = o_s; da.stop_index = o_idx; da.duration = o_dur; da.status = o_st;
+    da.profile_time = o_pt; da.profile_rate2 = o_pr; da.profile_drate2 = o_pd;
+    int rc = tpamd_fastest_stop_device(e, &da, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(a->stop_parameter, o_s, B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a->stop_index, o_idx, B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a->duration, o_dur, B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a->status, o_st, B * 4, hipMemcpyDeviceToHost, st));
+    if (prof) {
+      HIPCHK(hipMemcpyAsync(a->profile_time, o_pt, B * M * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(a->profile_rate2, o_pr, B * M * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(a->profile_drate2, o_pd, B * M * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return 0;
+}
+
 int tpamd_debug_copy_boundary(tpamd_engine *e, int B, int N, double *sd2_max, double *sdd_max,
                               double *sdd_min, double *sd2_zero, uint8_t *type, double *sd2) {
   if (!e || B != e->last_B || N != e->last_N) return TPAMD_E_INVALID_ARGUMENT;
@@ -1826,6 +1904,7 @@ struct tpamd_planner_set {
   int *d_windows = nullptr;
   long long *d_start = nullptr, *d_horizon = nullptr, *d_loop_start = nullptr;
   PlannerSummaryDev *d_summary = nullptr;
+  char *d_stop_in = nullptr, *d_stop_out = nullptr;   // stop queries: [time_ns][ids], [s][duration][status]
   size_t last_h2d = 0, last_d2h = 0;
 };
 
@@ -1945,6 +2024,7 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
     ps->d_windows = s.take<int>(B);
     ps->P.old_state = s.take<int>(B); ps->P.offset = s.take<int>(B); ps->P.loop = s.take<int>(B); ps->P.append = s.take<int>(B);
     ps->d_summary = s.take<PlannerSummaryDev>(B);
+    ps->d_stop_in = s.take<char>(B * 12); ps->d_stop_out = s.take<char>(B * 20);
     if (!pass) {
       ps->fixed_bytes = s.off;
       if (hipMalloc(&ps->fixed, s.off) != hipSuccess) { delete ps; return TPAMD_E_HIP; }
@@ -2161,6 +2241,41 @@ int tpamd_planner_set_download_trajectory(tpamd_planner_set *ps, int planner, in
   if (q) HIPCHK(hipMemcpy(q, S.t_q + o * D, n * D * 8, hipMemcpyDeviceToHost));
   if (qd) HIPCHK(hipMemcpy(qd, S.t_qd + o * D, n * D * 8, hipMemcpyDeviceToHost));
   if (qdd) HIPCHK(hipMemcpy(qdd, S.t_qdd + o * D, n * D * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tpamd_planner_set_stop_parameters(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                                      double *stop_parameter, double *duration, int32_t *status) {
+  if (!ps || count < 0 || !time_ns || !stop_parameter || !status) return TPAMD_E_INVALID_ARGUMENT;
+  const PlannerSetState &S = ps->S;
+  if (count > S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (ids)
+    for (int k = 0; k < count; k++)
+      if (ids[k] < 0 || ids[k] >= S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  const size_t n = (size_t)count;
+  // one copy up ([time_ns][ids]), one launch, one copy down ([s][duration][status])
+  std::vector<char> in(n * (ids ? 12 : 8)), out(n * 20);
+  std::memcpy(in.data(), time_ns, n * 8);
+  if (ids) std::memcpy(in.data() + n * 8, ids, n * 4);
+  hipStream_t st = nullptr;
+  HIPCHK(hipMemcpyAsync(ps->d_stop_in, in.data(), in.size(), hipMemcpyHostToDevice, st));
+  FastestStopParams p{};
+  p.Q = count; p.stride = ps->tcap;
+  p.time = S.t_time; p.s = S.t_s; p.qd = S.t_qd; p.qdd = S.t_qdd;
+  p.count = S.t_count; p.first = S.t_first; p.initial_plan = S.initial_plan;
+  p.ids = ids ? (const int *)(ps->d_stop_in + n * 8) : nullptr;
+  p.amax = S.amax; p.query_ns = (const long long *)ps->d_stop_in;
+  p.stop_s = (double *)ps->d_stop_out; p.duration = (double *)(ps->d_stop_out + n * 8);
+  p.status = (int *)(ps->d_stop_out + n * 16);
+  if (!launch_fastest_stop(S.D, p, st)) return TPAMD_E_UNSUPPORTED;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out.data(), ps->d_stop_out, out.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(stop_parameter, out.data(), n * 8);
+  if (duration) std::memcpy(duration, out.data() + n * 8, n * 8);
+  std::memcpy(status, out.data() + n * 16, n * 4);
   return 0;
 }
 

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
-            "tpamd_sweep_joint.h", "tpamd_planner_set.h"]
+            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -163,6 +163,15 @@ class _ResampleArgs(C.Structure):
                                            "out_qd", "out_qdd", "count")])
 
 
+class _FastestStopArgs(C.Structure):
+    _fields_ = ([("num_paths", C.c_int32), ("stride", C.c_int32), ("num_dofs", C.c_int32),
+                 ("reserved", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("time", "s", "qd", "qdd", "count", "max_acceleration",
+                                           "query_time", "stop_parameter", "stop_index", "duration",
+                                           "status", "profile_time", "profile_rate2",
+                                           "profile_drate2")])
+
+
 _LIB = None
 
 # every symbol include/tpamd.h declares
@@ -181,6 +190,7 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
     "tpamd_planner_set_reset", "tpamd_planner_set_plan", "tpamd_planner_set_download_trajectory",
     "tpamd_planner_set_last_plan_bytes", "tpamd_planner_set_device_bytes",
+    "tpamd_planner_set_stop_parameters", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
     "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
     "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
     "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_kernel_vgprs",
@@ -270,6 +280,12 @@ def load_library():
     L.tpamd_resample_skip_device.argtypes = [vp, C.POINTER(_ResampleArgs), vp]
     L.tpamd_resample_skip_host.restype = i
     L.tpamd_resample_skip_host.argtypes = [vp, C.POINTER(_ResampleArgs)]
+    L.tpamd_fastest_stop_device.restype = i
+    L.tpamd_fastest_stop_device.argtypes = [vp, C.POINTER(_FastestStopArgs), vp]
+    L.tpamd_fastest_stop_host.restype = i
+    L.tpamd_fastest_stop_host.argtypes = [vp, C.POINTER(_FastestStopArgs)]
+    L.tpamd_planner_set_stop_parameters.restype = i
+    L.tpamd_planner_set_stop_parameters.argtypes = [vp, i] + [vp] * 5
     L.tpamd_debug_copy_boundary.restype = i
     L.tpamd_debug_copy_boundary.argtypes = [vp, i, i] + [vp] * 6
     L.tpamd_debug_keep_boundary.argtypes = [vp, i]
@@ -506,6 +522,47 @@ class Engine:
         fn = self._lib.tpamd_resample_skip_device if skip else self._lib.tpamd_resample_uniform_device
         _check(fn(self._h, C.byref(args), _stream_ptr(stream)),
                "tpamd_resample_skip_device" if skip else "tpamd_resample_uniform_device")
+
+    def fastest_stop(self, time, s, qd, qdd, max_acceleration, query_time, count=None,
+                     profile=False, stream=None, host=False):
+        """GetPathStopParameter for a batch (tpamd_fastest_stop_*): time, s [B][stride], qd, qdd
+        [B][stride][D], max_acceleration [B][D], query_time [B] seconds, count [B] int32 or None
+        (every row has stride samples) -- e.g. a solve's outputs or resample_uniform's out_* and
+        count as they are. Returns a dict stop_parameter, duration [B] float64, stop_index,
+        status [B] int32 (TPAMD_PLAN_*), and with profile=True profile_time, profile_rate2,
+        profile_drate2 [B][stride] (entries 0 .. stop_index - start of each row are written).
+        host=False: CUDA tensors, outputs on their device, enqueued on `stream`; host=True: CPU
+        arrays (numpy or torch), numpy outputs, synchronous."""
+        B, M, D = qd.shape
+        if host:
+            cv = lambda x, dt: None if x is None else np.ascontiguousarray(
+                x.numpy() if hasattr(x, "numpy") else x, dtype=dt)
+            time, s, qd, qdd, max_acceleration, query_time = (
+                cv(x, np.float64) for x in (time, s, qd, qdd, max_acceleration, query_time))
+            count = cv(count, np.int32)
+            new = lambda shape, dt: np.zeros(shape, dtype=dt)
+            f64, i32 = np.float64, np.int32
+        else:
+            import torch
+            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=qd.device)
+            f64, i32 = torch.float64, torch.int32
+        out = dict(stop_parameter=new((B,), f64), stop_index=new((B,), i32),
+                   duration=new((B,), f64), status=new((B,), i32))
+        if profile:
+            for k in ("profile_time", "profile_rate2", "profile_drate2"):
+                out[k] = new((B, M), f64)
+        args = _FastestStopArgs(
+            B, M, D, 0, _ptr(time), _ptr(s), _ptr(qd), _ptr(qdd), _ptr(count),
+            _ptr(max_acceleration), _ptr(query_time),
+            *[_ptr(out.get(k)) for k in ("stop_parameter", "stop_index", "duration", "status",
+                                         "profile_time", "profile_rate2", "profile_drate2")])
+        if host:
+            _check(self._lib.tpamd_fastest_stop_host(self._h, C.byref(args)),
+                   "tpamd_fastest_stop_host")
+        else:
+            _check(self._lib.tpamd_fastest_stop_device(self._h, C.byref(args), _stream_ptr(stream)),
+                   "tpamd_fastest_stop_device")
+        return out
 
     def debug_boundary(self, B, N):
         arr = {k: np.zeros((B, N)) for k in ("sd2_max", "sdd_max", "sdd_min", "sd2_zero", "sd2")}

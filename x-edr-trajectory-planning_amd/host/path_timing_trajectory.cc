@@ -1,12 +1,15 @@
 #include "path_timing_trajectory.h"
 
 #include <algorithm>
+#include <cstdio>
+#include <iterator>
 #include <cmath>
 #include <limits>
 #include <map>
 #include <tuple>
 
 #include "engine_handle.h"
+#include "fastest_stop.h"
 #include "timeable_path_cartesian_spline.h"
 #include "timeable_path_joint_spline.h"
 
@@ -69,6 +72,32 @@ Status PathTimingTrajectory::SetPath(std::shared_ptr<TimeablePath> path) {
 
 Time PathTimingTrajectory::GetNextPlanStartTime(Time target_time) {
   return std::min(end_time_, std::max(target_time, start_time_));
+}
+
+// path_timing_trajectory.cc:235-287
+StatusOr<double> PathTimingTrajectory::GetPathStopParameter(Time time) const {
+  const double double_time = TimeToSec(time);
+  if (!initial_plan_) return 0.0;    // no plan yet: the beginning of the path
+  const auto time_it = std::lower_bound(time_.begin(), time_.end(), double_time);
+  if (time_it == time_.end()) {
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "Time %g not in timed path range", double_time);
+    return InvalidArgumentError(msg);
+  }
+  if (time_it == std::prev(time_.end())) return path_parameter_.back();
+  const int offset = (int)(time_it - time_.begin());
+  const int n = (int)time_.size() - offset;
+  std::vector<const double *> vel(n), acc(n);
+  for (int i = 0; i < n; i++) {
+    vel[i] = velocities_[offset + i].data();
+    acc[i] = accelerations_[offset + i].data();
+  }
+  double duration = 0.0;
+  const int stop = offset + ComputeFastestStop(n, (int)path_->GetMaxJointAcceleration().size(), time_.data() + offset, vel.data(),
+                                               acc.data(), path_->GetMaxJointAcceleration().data(), &duration,
+                                               nullptr);
+  if (stop < 0 || stop >= (int)time_.size()) return InternalError("stop index out of range");
+  return path_parameter_[stop];
 }
 
 StatusOr<int> PathTimingTrajectory::GetTimeOffsetAfter(Time time) const {

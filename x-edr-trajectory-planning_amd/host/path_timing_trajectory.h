@@ -54,6 +54,11 @@ class PathTimingTrajectory : public TrajectoryPlanner {
   Time GetFinalDecelStart() const { return final_decel_start_; }
   Time GetNextPlanStartTime(Time target_time);
   Status SetPath(std::shared_ptr<TimeablePath> path) override;
+  // path_timing_trajectory.h:116-118: the path parameter at which the robot could be at rest if
+  // it started braking at `time` with the path's joint acceleration limits (ComputeFastestStop,
+  // host/fastest_stop.h, on this planner's trajectory). 0.0 before the first plan; an
+  // InvalidArgument status if `time` lies after the last sample.
+  ::tpamd::compat::StatusOr<double> GetPathStopParameter(Time time) const;
   void SetProfileDebugVerbosity(int level) { TimeOptimalPathProfile::SetDebugVerbosity(level); }
   const PathTimingTrajectoryOptions &GetOptions() const { return options_; }
   const TimeOptimalPathProfile &GetProfile() const { return profile_; }

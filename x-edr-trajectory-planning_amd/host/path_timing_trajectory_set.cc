@@ -1,6 +1,7 @@
 #include "path_timing_trajectory_set.h"
 
 #include <algorithm>
+#include <cstdio>
 
 namespace trajectory_planning {
 
@@ -10,6 +11,7 @@ using ::tpamd::compat::InternalError;
 using ::tpamd::compat::InvalidArgumentError;
 using ::tpamd::compat::OkStatus;
 using ::tpamd::compat::OutOfRangeError;
+using ::tpamd::compat::StatusOr;
 
 PathTimingTrajectorySet::PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
                                                  size_t num_control_points, double constraint_safety, int device)
@@ -137,6 +139,48 @@ std::vector<Status> PathTimingTrajectorySet::Plan(const std::vector<Time> &start
     }
   }
   return result;
+}
+
+namespace {
+StatusOr<double> StopResult(int32_t status, double stop_parameter, int64_t time_ns) {
+  if (status == TPAMD_PLAN_OK) return stop_parameter;
+  if (status == TPAMD_PLAN_INVALID_ARGUMENT) {      // path_timing_trajectory.cc:245-249
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "Time %g not in timed path range", (double)time_ns / 1e9);
+    return InvalidArgumentError(msg);
+  }
+  return InternalError("stop parameter query failed");
+}
+}  // namespace
+
+StatusOr<double> PathTimingTrajectorySet::GetPathStopParameter(size_t planner, Time time) const {
+  if (!init_status_.ok()) return init_status_;
+  if (planner >= num_planners_) return InvalidArgumentError("no such planner");
+  const int32_t id = (int32_t)planner;
+  const int64_t t = ::tpamd::compat::ToUnixNanos(time);
+  double s = 0.0;
+  int32_t st = 0;
+  const int rc = tpamd_planner_set_stop_parameters(set_, 1, &id, &t, &s, nullptr, &st);
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  return StopResult(st, s, t);
+}
+
+std::vector<StatusOr<double>> PathTimingTrajectorySet::GetPathStopParameters(const std::vector<Time> &time) const {
+  if (!init_status_.ok() || time.size() != num_planners_) {
+    const Status st = init_status_.ok() ? InvalidArgumentError("one time per planner") : init_status_;
+    return std::vector<StatusOr<double>>(num_planners_, st);
+  }
+  const size_t n = num_planners_;
+  std::vector<int64_t> t(n);
+  for (size_t b = 0; b < n; b++) t[b] = ::tpamd::compat::ToUnixNanos(time[b]);
+  std::vector<double> s(n);
+  std::vector<int32_t> st(n);
+  const int rc = tpamd_planner_set_stop_parameters(set_, (int)n, nullptr, t.data(), s.data(), nullptr, st.data());
+  if (rc != 0) return std::vector<StatusOr<double>>(n, InternalError(tpamd_error_string(rc)));
+  std::vector<StatusOr<double>> out;
+  out.reserve(n);
+  for (size_t b = 0; b < n; b++) out.push_back(StopResult(st[b], s[b], t[b]));
+  return out;
 }
 
 Status PathTimingTrajectorySet::GetTrajectory(size_t planner, PlannedTrajectory *out) const {

@@ -65,6 +65,11 @@ class PathTimingTrajectorySet {
     return st != 1 && st != 2 && summary_[planner].target_reached != 0;
   }
   int WindowsOfLastPlan(size_t planner) const { return summary_[planner].windows; }
+  // PathTimingTrajectory::GetPathStopParameter(time) on the resident trajectories after the last
+  // Plan (tpamd_planner_set_stop_parameters): one planner, or every planner with one time each
+  // (one launch, no trajectory download). No planner state changes.
+  ::tpamd::compat::StatusOr<double> GetPathStopParameter(size_t planner, Time time) const;
+  std::vector<::tpamd::compat::StatusOr<double>> GetPathStopParameters(const std::vector<Time> &time) const;
   // The planner's trajectory (GetTime, GetPositions, ...): one download of its samples.
   Status GetTrajectory(size_t planner, PlannedTrajectory *out) const;
   // Bytes the last Plan call moved over PCIe, both directions.
