@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import hp_reference
 import scenarios
 from conftest import PKG_NAME
 
@@ -663,6 +664,15 @@ def test_config2_full_size_properties(env):
     # joint limits with the 0.8 safety factor (timeable_path.h:80): |qd| <= 0.8 vmax, |qdd| <= amax
     assert (np.abs(qd) <= 0.8 * b["vmax"][:, None, :] * (1 + 1e-9) + 1e-12).all()
     assert (np.abs(qdd) <= b["amax"][:, None, :]).all()
+    # qdd is clipped to +-amax, so the line above cannot fail: the bound the solver enforces is
+    # safety * amax on q' sdd + q'' sd^2, with the exact spline (hp_reference.check_profile)
+    for lo in range(0, B, 256):
+        q12 = [hp_reference.sample_path(b["knots"][i], b["control_points"][i], 0.0, b["delta"][i], N)
+               for i in range(lo, lo + 256)]
+        bad = hp_reference.accel_rule_violations(np.stack([x[1] for x in q12]),
+                                                 np.stack([x[2] for x in q12]), sd[lo:lo + 256],
+                                                 sdd[lo:lo + 256], b["amax"][lo:lo + 256])
+        assert not bad.any(), np.argwhere(bad)[:8] + [lo, 0]
     np.testing.assert_allclose(q[:, 0], b["control_points"][:, 0], atol=1e-12)
     np.testing.assert_allclose(q[:, -1], b["control_points"][:, -1], atol=1e-9)
     # a time-optimal profile rides a velocity limit on a sizeable share of the samples

@@ -973,7 +973,10 @@ struct JointSweep {
     const double chain_next = y_out;                     // what the chain fed to step k+1
     const bool bits_equal = __double_as_longlong(chain_next) == __double_as_longlong(my_new);
     int guess = -1;
-    const bool bad = chain_step_bad<FWD>(ops, wl / L::PARTS, hi_r, arow, my_cur, my_sdd, guess);
+    // FindSdd skips a row with |q'| < kTiny: where the speculated row becomes one, its candidate
+    // does not exist there (a stationary stretch of the path) and the step falls to the scalar code
+    const bool bad = chain_step_bad<FWD>(ops, wl / L::PARTS, hi_r, arow, my_cur, my_sdd, guess) |
+                     is_tiny(arow.x);
     const int t_j = __double2loint(mt_j.y), t_n = __double2loint(mt_n.y);
     const double m_j = mt_j.x, m_n = mt_n.x;
     const bool riding = is_tiny(my_cur - m_j) & ((t_j & kBndTrajectory) != 0) & ((t_n & kBndTrajectory) != 0);
