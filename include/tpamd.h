@@ -380,6 +380,45 @@ int tpamd_planner_set_upload_paths(tpamd_planner_set *set, int count, const int3
                                    const double *max_velocity, const double *max_acceleration,
                                    const double *delta, const double *initial_velocity,
                                    const int32_t *path_state);
+/* Paths of any size: planner k's path has num_points[k] >= 3 control points, its knots
+ * (num_points[k] + 3) and control points (num_points[k] x D) packed behind those of planner k - 1
+ * in `knots` / `control_points`; the other arrays as in tpamd_planner_set_upload_paths. The set's
+ * per-planner capacity grows (by doubling) before anything changes; every id, state and size is
+ * checked before the first copy. The fixed-size entry above takes paths of the config's
+ * num_points. Host pointers; synchronises. */
+int tpamd_planner_set_upload_paths_ragged(tpamd_planner_set *set, int count, const int32_t *ids,
+                                          const int32_t *num_points, const double *knots,
+                                          const double *control_points, const double *max_velocity,
+                                          const double *max_acceleration, const double *delta,
+                                          const double *initial_velocity, const int32_t *path_state);
+/* The resident path of one planner: *num_points (0: no path) and, if the arrays are not NULL, its
+ * knots [num_points + 3] and control points [num_points][D]. `capacity` is the number of control
+ * points the arrays can hold; a larger path gives TPAMD_E_INVALID_ARGUMENT (*num_points is still
+ * written). With both arrays NULL nothing crosses PCIe. */
+int tpamd_planner_set_download_path(tpamd_planner_set *set, int planner, int32_t *num_points,
+                                    double *knots, double *control_points, int capacity);
+/* The online path switch (path_timing_trajectory_test.cc:298-420) for `count` planners of a set
+ * (ids[count], each listed once, or planners 0..count-1 if ids is NULL), on the device:
+ *   1. stop parameter: keep_path_until[k], or if keep_path_until is NULL the fastest-stop
+ *      parameter GetPathStopParameter(time_ns[k]) (as tpamd_planner_set_stop_parameters);
+ *   2. the velocity at time_ns[k] on the resident trajectory (TrajectoryBuffer::GetVelocityAtTime:
+ *      TPAMD_PLAN_FAILED_PRECONDITION without a plan, TPAMD_PLAN_OUT_OF_RANGE outside it);
+ *   3. TimeableJointSplinePath::SwitchToWaypointPath(stop, waypoints) with the new waypoints
+ *      waypoints[waypoint_offsets[k] .. waypoint_offsets[k + 1])[D] (rounding radius 0.2, the
+ *      PathOptions default), bit-identical to the host mirror;
+ *   4. on success the new spline, the velocity as initial velocity and path_state 2
+ *      (kModifiedPath) replace the planner's; the next tpamd_planner_set_plan plans it as
+ *      PathTimingTrajectory::Plan plans a modified path. On failure the planner is unchanged.
+ * Per planner: stop_parameter[k] (the one used), num_points[k] (the planner's control points after
+ * the call) and status[k] TPAMD_PLAN_* (the first step that failed). Call-level errors (a bad or
+ * repeated id, NULL arrays, waypoint_offsets[0] != 0 or decreasing) change nothing. The set's
+ * per-planner capacity grows first if P + 3 + 3 (W + 1) - 2 does not fit. About 16 bytes per
+ * planner plus the waypoints go up, 16 come down; no trajectory is downloaded. Host pointers;
+ * synchronises. */
+int tpamd_planner_set_switch_paths(tpamd_planner_set *set, int count, const int32_t *ids,
+                                   const int64_t *time_ns, const double *keep_path_until,
+                                   const int32_t *waypoint_offsets, const double *waypoints,
+                                   double *stop_parameter, int32_t *num_points, int32_t *status);
 /* TrajectoryPlanner::Reset for the listed planners (ids NULL: all): no path, no plan. */
 int tpamd_planner_set_reset(tpamd_planner_set *set, int count, const int32_t *ids);
 /* Plan(start, time_horizon) for every planner: start_ns / horizon_ns [B] host arrays;

@@ -1,0 +1,248 @@
+// CPU test of the planner-set switch's edit routines (run by tests/test_set_switch_cpu.py): the
+// host/device functions of csrc/tpamd_switch.h, compiled here for the host, against the mirror's
+// TimeableJointSplinePath::SwitchToWaypointPath bit for bit, and the velocity bracket
+// (sw_velocity_at_time) against TrajectoryPlanner::GetVelocityAtTime.
+//
+// Seeded cases for D = 1, 3, 7, 16 and W = 1..8 new waypoints, with stop parameters inside a span,
+// on a knot, at or before the first knot, at or after the last knot, new waypoints whose
+// projection lies within 1e-3 of the switch point, projections before the first new waypoint
+// (line parameter < 0), and three switches in a row on one spline. Prints one line per category
+// and "ALL OK".
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../x-edr-trajectory-planning_amd/csrc/tpamd_switch.h"
+#include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
+#include "../../x-edr-trajectory-planning_amd/host/trajectory_planner.h"
+
+using namespace trajectory_planning;
+using tpamd::compat::StatusCode;
+
+static int g_fail = 0;
+#define CHECK(cond)                                                                          \
+  do {                                                                                       \
+    if (!(cond)) {                                                                           \
+      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
+      g_fail++;                                                                              \
+    }                                                                                        \
+  } while (0)
+
+static unsigned long long g_seed = 20261015ULL;
+static double Rnd() {
+  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
+  return (double)(g_seed >> 11) / 9007199254740992.0;
+}
+static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
+
+static int PlanCode(const tpamd::compat::Status &s) {
+  switch (s.code()) {
+    case StatusCode::kOk: return tpamd::kSwOk;
+    case StatusCode::kFailedPrecondition: return tpamd::kSwFailedPrecondition;
+    case StatusCode::kOutOfRange: return tpamd::kSwOutOfRange;
+    case StatusCode::kInvalidArgument: return tpamd::kSwInvalidArgument;
+    default: return tpamd::kSwInternal;
+  }
+}
+
+static bool SameBits(const std::vector<double> &a, const double *b, size_t n) {
+  return a.size() == n && (n == 0 || std::memcmp(a.data(), b, n * sizeof(double)) == 0);
+}
+
+static std::vector<VectorXd> RandomWaypoints(int W, int D, double scale) {
+  std::vector<VectorXd> w;
+  for (int i = 0; i < W; i++) {
+    VectorXd v(D);
+    for (int d = 0; d < D; d++) v[d] = scale * (2.0 * Rnd() - 1.0);
+    w.push_back(v);
+  }
+  return w;
+}
+
+// The device-side state of one planner's path: what the set holds between calls.
+struct HdPath {
+  std::vector<double> knots, pts;
+  int np = 0;
+};
+
+static std::map<std::string, int> g_seen;
+
+// One switch on the mirror and through the host/device routines; compares status and result.
+static void SwitchBoth(TimeableJointSplinePath *mirror, HdPath *hd, int D, double keep,
+                       const std::vector<VectorXd> &wps, const char *category) {
+  const int W = (int)wps.size();
+  const int bound = tpamd::sw_points_bound(hd->np, W);
+  std::vector<double> k(bound + 3, 0.0), p((size_t)bound * D, 0.0), work((size_t)(W + 2) * D, 0.0);
+  std::copy(hd->knots.begin(), hd->knots.end(), k.begin());
+  std::copy(hd->pts.begin(), hd->pts.end(), p.begin());
+  std::vector<double> flat;
+  for (const auto &w : wps) flat.insert(flat.end(), w.begin(), w.end());
+  int nk = 0, np = 0;
+  const int st = tpamd::sw_switch_to_waypoint_path(k.data(), p.data(), hd->np + 3, hd->np, D, keep, flat.data(), W,
+                                                   tpamd::kSwitchRounding, work.data(), &nk, &np);
+  const auto want = mirror->SwitchToWaypointPath(keep, {wps.data(), wps.size()});
+  CHECK(st == PlanCode(want));
+  if (st != PlanCode(want)) {
+    std::printf("  %s: status %d vs %d (%s) D %d W %d keep %.17g\n", category, st, PlanCode(want),
+                want.message().c_str(), D, W, keep);
+    return;
+  }
+  g_seen[std::string(category) + (st == 0 ? "/ok" : "/status " + std::to_string(st))]++;
+  if (st != tpamd::kSwOk) return;
+  CHECK(np <= bound);
+  CHECK(np == mirror->num_control_points() && nk == np + 3);
+  const bool same = SameBits(mirror->knots(), k.data(), (size_t)nk) &&
+                    SameBits(mirror->packed_control_points(), p.data(), (size_t)np * D);
+  CHECK(same);
+  if (!same) std::printf("  %s: result differs (D %d W %d keep %.17g)\n", category, D, W, keep);
+  hd->knots.assign(k.begin(), k.begin() + nk);
+  hd->pts.assign(p.begin(), p.begin() + (size_t)np * D);
+  hd->np = np;
+}
+
+static std::shared_ptr<TimeableJointSplinePath> NewPath(int D, const std::vector<VectorXd> &wps, HdPath *hd) {
+  auto path = std::make_shared<TimeableJointSplinePath>(JointPathOptions().set_num_dofs(D).set_num_path_samples(8));
+  CHECK(path->SetWaypoints({wps.data(), wps.size()}).ok());
+  hd->knots = path->knots();
+  hd->pts = path->packed_control_points();
+  hd->np = path->num_control_points();
+  return path;
+}
+
+static void TestEdits() {
+  const int dofs[] = {1, 3, 7, 16};
+  int cases = 0;
+  for (int D : dofs) {
+    for (int rep = 0; rep < 160; rep++) {
+      for (int W = 1; W <= 8; W++) {
+        const int kind = (rep + W) % 8;
+        HdPath hd;
+        auto path = NewPath(D, RandomWaypoints(RndInt(2, 7), D, 2.5), &hd);
+        const std::vector<double> &kn = path->knots();
+        const double umin = kn.front(), umax = kn.back();
+        std::vector<VectorXd> wps = RandomWaypoints(W, D, 2.5);
+        double keep = umin + (0.05 + 0.9 * Rnd()) * (umax - umin);
+        const char *cat = "inside a span";
+        if (kind == 1) {                     // on an interior knot
+          const int nk = (int)kn.size();
+          keep = kn[RndInt(3, nk - 4)];
+          cat = "on a knot";
+        } else if (kind == 2) {
+          keep = (rep & 1) ? umin : umin - 0.1 * Rnd();
+          cat = "keep <= umin";
+        } else if (kind == 3) {
+          keep = (rep & 1) ? umax : umax + 0.1 * Rnd();
+          cat = "keep >= umax";
+        } else if (kind == 4) {              // the first new waypoint within 1e-3 of the switch point
+          VectorXd at(D);             // the switch point: the spline truncated at keep, evaluated there
+          std::vector<double> k(hd.np + 8, 0.0), p((size_t)(hd.np + 8) * D, 0.0);
+          std::copy(hd.knots.begin(), hd.knots.end(), k.begin());
+          std::copy(hd.pts.begin(), hd.pts.end(), p.begin());
+          tpamd::SwSpline s{k.data(), p.data(), hd.np + 3, hd.np, D, 1000, umin, umax, false};
+          tpamd::sw_truncate(s, keep);
+          tpamd::sw_eval(s, keep, at.data());
+          for (int d = 0; d < D; d++) wps[0][d] = at[d] + ((d & 1) ? 4e-4 : -4e-4) * Rnd();
+          cat = "projection within 1e-3";
+        } else if (kind == 5) {              // the switch point lies before the first new segment
+          VectorXd at(D);
+          std::vector<double> k(hd.np + 8, 0.0), p((size_t)(hd.np + 8) * D, 0.0);
+          std::copy(hd.knots.begin(), hd.knots.end(), k.begin());
+          std::copy(hd.pts.begin(), hd.pts.end(), p.begin());
+          tpamd::SwSpline s{k.data(), p.data(), hd.np + 3, hd.np, D, 1000, umin, umax, false};
+          tpamd::sw_truncate(s, keep);
+          tpamd::sw_eval(s, keep, at.data());
+          if (W >= 2) {
+            for (int d = 0; d < D; d++) {
+              wps[0][d] = at[d] + 1.0 + 0.1 * d;      // the segment points away from the switch point
+              wps[1][d] = wps[0][d] + 2.0;
+            }
+            for (int i = 2; i < W; i++)
+              for (int d = 0; d < D; d++) wps[i][d] = wps[1][d] + 5.0 * i;
+          }
+          cat = "line parameter < 0";
+        } else if (kind == 6) {              // three switches in a row
+          SwitchBoth(path.get(), &hd, D, keep, wps, "three in a row (1)");
+          for (int r = 2; r <= 3; r++) {
+            const double lo = path->knots().front(), hi = path->knots().back();
+            const double k2 = lo + (0.3 + 0.6 * Rnd()) * (hi - lo);
+            const char *c = r == 2 ? "three in a row (2)" : "three in a row (3)";
+            SwitchBoth(path.get(), &hd, D, k2, RandomWaypoints(RndInt(1, 8), D, 2.5), c);
+          }
+          cases += 3;
+          continue;
+        } else if (kind == 7) {              // repeated or coincident new waypoints
+          for (int i = 1; i < W; i += 2) wps[i] = wps[i - 1];
+          cat = "repeated waypoints";
+        }
+        SwitchBoth(path.get(), &hd, D, keep, wps, cat);
+        cases++;
+      }
+    }
+  }
+  std::printf("edit cases: %d\n", cases);
+}
+
+// TrajectoryPlanner::GetVelocityAtTime on a filled buffer
+struct BufferProbe : TrajectoryPlanner {
+  Status Plan(Time, tpamd::compat::Duration) override { return Status(); }
+  Status SetPath(std::shared_ptr<TimeablePath>) override { return Status(); }
+  void ResetDerived() override {}
+  void Fill(const std::vector<double> &t, const std::vector<VectorXd> &v) { time_ = t; velocities_ = v; }
+};
+
+static void TestVelocityBracket() {
+  int seen[6] = {0, 0, 0, 0, 0, 0};
+  for (int c = 0; c < 2000; c++) {
+    const int D = (int[]){1, 3, 7, 16}[c % 4];
+    const int n = c % 97 == 0 ? 0 : RndInt(1, 60);
+    std::vector<double> t(n), flat;
+    std::vector<VectorXd> v(n, VectorXd(D));
+    double now = 2.0 + 3.0 * Rnd();
+    for (int i = 0; i < n; i++) {
+      now += (c % 5 == 0) ? 0.004 : 0.001 + 0.01 * Rnd();
+      t[i] = (double)(long long)(now * 1e9) / 1e9;   // on the nanosecond grid, as resampled times are
+      for (int d = 0; d < D; d++) v[i][d] = 3.0 * Rnd() - 1.5;
+      flat.insert(flat.end(), v[i].begin(), v[i].end());
+    }
+    BufferProbe probe;
+    probe.Fill(t, v);
+    const int kind = c % 6;
+    long long ns = 1000000000LL;
+    if (n > 0) {
+      const int i = RndInt(0, n - 1);
+      if (kind == 0) ns = (long long)llround(t[i] * 1e9);                               // on a sample
+      else if (kind == 1 && i + 1 < n) ns = (long long)((0.5 * (t[i] + t[i + 1])) * 1e9); // between
+      else if (kind == 2) ns = (long long)llround(t[n - 1] * 1e9);                      // the last sample
+      else if (kind == 3) ns = (long long)llround(t[n - 1] * 1e9) + 1000;                 // after the end
+      else if (kind == 4) ns = (long long)llround(t[0] * 1e9) - 1000;                     // before the start
+      else ns = (long long)((t[0] + Rnd() * (t[n - 1] - t[0])) * 1e9);
+    }
+    const auto want = probe.GetVelocityAtTime(tpamd::compat::FromUnixNanos(ns));
+    std::vector<double> got(D, -7.0);
+    const int st = tpamd::sw_velocity_at_time(t.data(), flat.data(), n, D, (double)ns / 1e9, got.data());
+    CHECK(st == PlanCode(want.status()));
+    if (st == 0 && want.ok()) {
+      CHECK(std::memcmp(got.data(), (*want).data(), D * sizeof(double)) == 0);
+      seen[kind]++;
+    }
+    if (n == 0) CHECK(st == tpamd::kSwFailedPrecondition);
+    if (n > 0 && kind == 3) CHECK(st == tpamd::kSwOutOfRange);
+    if (n > 0 && kind == 2 && st == 0)
+      CHECK(std::memcmp(got.data(), v[n - 1].data(), D * sizeof(double)) == 0);
+  }
+  std::printf("velocity bracket: on a sample %d, between %d, last sample %d, inside %d\n", seen[0], seen[1], seen[2],
+              seen[5]);
+  CHECK(seen[0] > 0 && seen[1] > 0 && seen[2] > 0 && seen[5] > 0);
+}
+
+int main() {
+  TestEdits();
+  TestVelocityBracket();
+  for (const auto &kv : g_seen) std::printf("category %s: %d\n", kv.first.c_str(), kv.second);
+  if (g_fail == 0) std::printf("ALL OK\n");
+  else std::printf("%d CHECKS FAILED\n", g_fail);
+  return g_fail == 0 ? 0 : 1;
+}

@@ -16,6 +16,7 @@
 #include "tpamd_launch.h"
 #include "tpamd_planner_set.h"
 #include "tpamd_stop.h"
+#include "tpamd_switch.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 
 using namespace tpamd;
@@ -640,6 +641,9 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
   e->last_B = B; e->last_N = N; e->last_time = out->time;
   e->ws.ns = in->num_samples_per_path;
   e->ws.amax = in->max_acceleration;
+  // planner sets: paths of their own sizes in arrays of stride P_cap; P is the largest in use
+  e->ws.np = plan ? plan->np : nullptr;
+  e->ws.p_stride = (plan && plan->np) ? plan->K - 3 : P;
   // ragged batches: sweep workgroups take the paths longest first (k_order_paths, below)
   int32_t *order = const_cast<int32_t *>(e->ws.order);
   const bool ordered = in->num_samples_per_path != nullptr && B > 1 && e->order_ragged && plan == nullptr;
@@ -1891,9 +1895,15 @@ struct tpamd_planner_set {
   tpamd_engine *e = nullptr;
   tpamd_planner_set_config cfg{};
   int cap = 0, tcap = 0;
-  // fixed-size state (one allocation), history and trajectory (one allocation each: they grow)
-  void *fixed = nullptr, *hist = nullptr, *traj = nullptr;
-  size_t fixed_bytes = 0, hist_bytes = 0, traj_bytes = 0;
+  int pcap = 0;                         // control points per planner the path arrays hold (P_cap)
+  // fixed-size state (one allocation); paths, history and trajectory (one allocation each: they grow)
+  void *fixed = nullptr, *hist = nullptr, *traj = nullptr, *path = nullptr;
+  size_t fixed_bytes = 0, hist_bytes = 0, traj_bytes = 0, path_bytes = 0;
+  // host copies of S.np and S.has_path: they change only through uploads, switches and resets
+  std::vector<int> h_np;
+  std::vector<char> h_has;
+  void *sw_buf = nullptr;               // switch calls: inputs, outputs and the edit's scratch
+  size_t sw_bytes = 0;
   PlannerSetState S{};
   PlanParams P{};
   // device arrays that are not part of S / P
@@ -1910,6 +1920,14 @@ struct tpamd_planner_set {
 
 namespace {
 
+// knots [B][pcap + 3] | control points [B][pcap][D]
+size_t carve_paths(char *base, size_t B, size_t pcap, size_t D, tpamd_planner_set *ps) {
+  size_t off = 0;
+  auto take = [&](size_t n) { double *p = base ? (double *)(base + off) : nullptr; off = align_up(off + n * 8, 256); return p; };
+  double *k = take(B * (pcap + 3)), *cp = take(B * pcap * D);
+  if (ps) { ps->S.knots = k; ps->d_cp = cp; ps->S.K = (int)pcap + 3; }
+  return off;
+}
 size_t carve_history(char *base, size_t B, size_t cap, size_t D, tpamd_planner_set *ps) {
   size_t off = 0;
   auto take = [&](size_t n) { double *p = base ? (double *)(base + off) : nullptr; off = align_up(off + n * 8, 256); return p; };
@@ -1935,7 +1953,7 @@ size_t carve_trajectory(char *base, size_t B, size_t tcap, size_t D, tpamd_plann
 void refresh_plan_params(tpamd_planner_set *ps) {
   PlannerSetState &S = ps->S;
   PlanParams &p = ps->P;
-  p.B = S.B; p.N = S.N; p.D = S.D; p.K = S.K; p.cap = ps->cap;
+  p.B = S.B; p.N = S.N; p.D = S.D; p.K = S.K; p.cap = ps->cap; p.np = S.np;
   p.max_iterations = ps->cfg.max_planning_iterations;
   p.max_initial_velocity_error = ps->cfg.max_initial_velocity_error;
   p.knots = S.knots; p.delta = ps->d_delta; p.initial_velocity = ps->d_iv;
@@ -1982,6 +2000,109 @@ int grow_rows(tpamd_planner_set *ps, bool history, int new_cap, hipStream_t st) 
   return 0;
 }
 
+// Move the paths to arrays of a larger per-planner capacity (P_cap); contents unchanged.
+int grow_paths(tpamd_planner_set *ps, int new_pcap, hipStream_t st) {
+  const size_t B = ps->S.B, D = ps->S.D, old_p = ps->pcap, new_p = new_pcap;
+  const double *old_k = ps->S.knots, *old_cp = ps->d_cp;
+  void *old_base = ps->path;
+  const size_t need = carve_paths(nullptr, B, new_p, D, nullptr);
+  void *fresh = nullptr;
+  HIPCHK(hipMalloc(&fresh, need));
+  carve_paths((char *)fresh, B, new_p, D, ps);
+  ps->path = fresh; ps->path_bytes = need; ps->pcap = new_pcap;
+  HIPCHK(hipMemcpy2DAsync((double *)ps->S.knots, (new_p + 3) * 8, old_k, (old_p + 3) * 8, (old_p + 3) * 8, B,
+                          hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpy2DAsync(ps->d_cp, new_p * D * 8, old_cp, old_p * D * 8, old_p * D * 8, B,
+                          hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipFree(old_base));
+  refresh_plan_params(ps);
+  return 0;
+}
+
+// P_cap by doubling until `need` points fit
+int ensure_pcap(tpamd_planner_set *ps, int need, hipStream_t st) {
+  if (need <= ps->pcap) return 0;
+  int p = ps->pcap;
+  while (p < need) p *= 2;
+  return grow_paths(ps, p, st);
+}
+
+int largest_points(const tpamd_planner_set *ps) {
+  int m = 3;
+  for (int v : ps->h_np) m = std::max(m, v);
+  return m;
+}
+
+// tpamd_planner_set_upload_paths(_ragged): num_points null = every path has the config's P
+int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *num_points,
+                        const double *knots, const double *cps, const double *vmax, const double *amax,
+                        const double *delta, const double *iv, const int32_t *path_state) {
+  if (!ps || count < 0 || !knots || !cps || !vmax || !amax || !delta || !path_state) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = ps->S.B, D = ps->S.D, P0 = ps->cfg.num_points;
+  if ((size_t)count > B) return TPAMD_E_INVALID_ARGUMENT;
+  // every id, state and size is checked before the first copy
+  int need = 0;
+  for (int k = 0; k < count; k++) {
+    const long long b = ids ? (long long)ids[k] : (long long)k;
+    if (b < 0 || b >= (long long)B || (path_state[k] != 1 && path_state[k] != 2)) return TPAMD_E_INVALID_ARGUMENT;
+    const int P = num_points ? num_points[k] : (int)P0;
+    if (P < 3) return TPAMD_E_INVALID_ARGUMENT;
+    need = std::max(need, P);
+  }
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const int grc = ensure_pcap(ps, need, st);
+  if (grc) return grc;
+  const size_t Pc = ps->pcap, Kc = Pc + 3, n = (size_t)count;
+  std::vector<double> zeros(iv ? 0 : n * D, 0.0);
+  const double *ivp = iv ? iv : zeros.data();
+  std::vector<int> ones(n, 1), np(n);
+  for (size_t k = 0; k < n; k++) np[k] = num_points ? num_points[k] : (int)P0;
+  if (!ids) {     // planners 0 .. count-1: the paths staged at the device stride, one copy per array
+    std::vector<double> hk(n * Kc, 0.0), hc(n * Pc * D, 0.0);
+    size_t ok = 0, oc = 0;
+    for (size_t k = 0; k < n; k++) {
+      const size_t P = np[k];
+      std::memcpy(hk.data() + k * Kc, knots + ok, (P + 3) * 8);
+      std::memcpy(hc.data() + k * Pc * D, cps + oc, P * D * 8);
+      ok += P + 3; oc += P * D;
+    }
+    HIPCHK(hipMemcpyAsync((double *)ps->S.knots, hk.data(), n * Kc * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->d_cp, hc.data(), n * Pc * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->d_vmax, vmax, n * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((double *)ps->S.amax, amax, n * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->d_delta, delta, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->d_iv, ivp, n * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->S.path_state, path_state, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->S.has_path, ones.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->S.np, np.data(), n * 4, hipMemcpyHostToDevice, st));
+  } else {
+    size_t ok = 0, oc = 0;
+    for (size_t k = 0; k < n; k++) {
+      const size_t b = (size_t)ids[k], P = np[k];
+      HIPCHK(hipMemcpyAsync((double *)ps->S.knots + b * Kc, knots + ok, (P + 3) * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->d_cp + b * Pc * D, cps + oc, P * D * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->d_vmax + b * D, vmax + k * D, D * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync((double *)ps->S.amax + b * D, amax + k * D, D * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->d_delta + b, delta + k, 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->d_iv + b * D, ivp + k * D, D * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->S.path_state + b, path_state + k, 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->S.has_path + b, &ones[k], 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ps->S.np + b, &np[k], 4, hipMemcpyHostToDevice, st));
+      ok += P + 3; oc += P * D;
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t k = 0; k < n; k++) {
+    const size_t b = ids ? (size_t)ids[k] : k;
+    ps->h_np[b] = np[k];
+    ps->h_has[b] = 1;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2000,11 +2121,13 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
   ps->cfg = *cfg;
   ps->cap = cfg->history_capacity > 0 ? std::max<int>(cfg->history_capacity, 2 * (int)N) : 8 * (int)N;
   ps->tcap = cfg->trajectory_capacity > 0 ? cfg->trajectory_capacity : 4096;
-  const size_t K = P + 3;
+  ps->pcap = (int)P;
+  ps->h_np.assign(B, (int)P);
+  ps->h_has.assign(B, 0);
   PlannerSetState &S = ps->S;
   for (int pass = 0; pass < 2; pass++) {
     Stage s(pass ? ps->fixed : nullptr);
-    S.knots = s.take<double>(B * K); ps->d_cp = s.take<double>(B * P * D);
+    S.np = s.take<int>(B);
     ps->d_vmax = s.take<double>(B * D); S.amax = s.take<double>(B * D);
     ps->d_delta = s.take<double>(B); ps->d_iv = s.take<double>(B * D); ps->d_sdd0 = s.take<double>(B);
     S.path_state = s.take<int>(B); S.has_path = s.take<int>(B); S.count = s.take<int>(B);
@@ -2032,19 +2155,30 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
   }
   S.w_time = ps->w_time; S.w_lei = ps->w_lei;
   S.start_ns = ps->d_start; S.horizon_ns = ps->d_horizon;
-  S.B = (int)B; S.N = (int)N; S.D = (int)D; S.K = (int)K;
+  S.B = (int)B; S.N = (int)N; S.D = (int)D;
   S.method = cfg->sampling_method; S.max_iterations = cfg->max_planning_iterations;
   S.time_step_sec = (double)cfg->time_step_ns / 1e9;                    // path_timing_trajectory.cc:206-211
   S.time_step_duration_ns = (long long)llround(S.time_step_sec * 1e9);  // absl::Seconds(time_step_sec_)
   ps->hist_bytes = carve_history(nullptr, B, ps->cap, D, nullptr);
   ps->traj_bytes = carve_trajectory(nullptr, B, ps->tcap, D, nullptr);
-  if (hipMalloc(&ps->hist, ps->hist_bytes) != hipSuccess || hipMalloc(&ps->traj, ps->traj_bytes) != hipSuccess) {
+  ps->path_bytes = carve_paths(nullptr, B, ps->pcap, D, nullptr);
+  if (hipMalloc(&ps->hist, ps->hist_bytes) != hipSuccess || hipMalloc(&ps->traj, ps->traj_bytes) != hipSuccess ||
+      hipMalloc(&ps->path, ps->path_bytes) != hipSuccess) {
     tpamd_planner_set_destroy(ps);
     return TPAMD_E_HIP;
   }
   carve_history((char *)ps->hist, B, ps->cap, D, ps);
   carve_trajectory((char *)ps->traj, B, ps->tcap, D, ps);
-  if (hipMemset(ps->fixed, 0, ps->fixed_bytes) != hipSuccess) { tpamd_planner_set_destroy(ps); return TPAMD_E_HIP; }
+  carve_paths((char *)ps->path, B, ps->pcap, D, ps);
+  if (hipMemset(ps->fixed, 0, ps->fixed_bytes) != hipSuccess || hipMemset(ps->path, 0, ps->path_bytes) != hipSuccess) {
+    tpamd_planner_set_destroy(ps);
+    return TPAMD_E_HIP;
+  }
+  // a planner without a path still has a count the sampling kernel can read (its knots are zero)
+  if (hipMemcpy(S.np, ps->h_np.data(), B * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    tpamd_planner_set_destroy(ps);
+    return TPAMD_E_HIP;
+  }
   refresh_plan_params(ps);
   // ResetDerived :213-227: planned_to_end_ = true (all other scalars zero)
   std::vector<int> ones(B, 1);
@@ -2062,11 +2196,13 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (ps->fixed) (void)hipFree(ps->fixed);
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
+  if (ps->path) (void)hipFree(ps->path);
+  if (ps->sw_buf) (void)hipFree(ps->sw_buf);
   delete ps;
 }
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
-  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes : 0;
+  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_bytes : 0;
 }
 
 void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *ps, size_t *h2d, size_t *d2h) {
@@ -2077,42 +2213,28 @@ void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *ps, size_t *h2d,
 int tpamd_planner_set_upload_paths(tpamd_planner_set *ps, int count, const int32_t *ids, const double *knots,
                                    const double *cps, const double *vmax, const double *amax, const double *delta,
                                    const double *iv, const int32_t *path_state) {
-  if (!ps || count < 0 || !knots || !cps || !vmax || !amax || !delta || !path_state) return TPAMD_E_INVALID_ARGUMENT;
-  const size_t B = ps->S.B, D = ps->S.D, K = ps->S.K, P = K - 3;
-  if ((size_t)count > B) return TPAMD_E_INVALID_ARGUMENT;
+  return upload_paths_common(ps, count, ids, nullptr, knots, cps, vmax, amax, delta, iv, path_state);
+}
+
+int tpamd_planner_set_upload_paths_ragged(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                          const int32_t *num_points, const double *knots, const double *cps,
+                                          const double *vmax, const double *amax, const double *delta,
+                                          const double *iv, const int32_t *path_state) {
+  if (!num_points) return TPAMD_E_INVALID_ARGUMENT;
+  return upload_paths_common(ps, count, ids, num_points, knots, cps, vmax, amax, delta, iv, path_state);
+}
+
+int tpamd_planner_set_download_path(tpamd_planner_set *ps, int planner, int32_t *num_points, double *knots,
+                                    double *cps, int capacity) {
+  if (!ps || !num_points || planner < 0 || planner >= ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  const int P = ps->h_has[planner] ? ps->h_np[planner] : 0;
+  *num_points = P;
+  if (P == 0 || (!knots && !cps)) return 0;
+  if (P > capacity) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(ps->e);
-  const int one = 1;
-  std::vector<double> zero(D, 0.0);
-  if (!ids && count > 0) {     // planners 0 .. count-1: one copy per array
-    for (int k = 0; k < count; k++)
-      if (path_state[k] != 1 && path_state[k] != 2) return TPAMD_E_INVALID_ARGUMENT;
-    const size_t n = (size_t)count;
-    std::vector<int> ones(n, 1);
-    std::vector<double> zeros(iv ? 0 : n * D, 0.0);
-    HIPCHK(hipMemcpyAsync((double *)ps->S.knots, knots, n * K * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_cp, cps, n * P * D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_vmax, vmax, n * D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync((double *)ps->S.amax, amax, n * D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_delta, delta, n * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_iv, iv ? iv : zeros.data(), n * D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->S.path_state, path_state, n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->S.has_path, ones.data(), n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return 0;
-  }
-  for (int k = 0; k < count; k++) {
-    const size_t b = ids ? (size_t)ids[k] : (size_t)k;
-    if (b >= B || (path_state[k] != 1 && path_state[k] != 2)) return TPAMD_E_INVALID_ARGUMENT;
-    HIPCHK(hipMemcpyAsync((double *)ps->S.knots + b * K, knots + (size_t)k * K, K * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_cp + b * P * D, cps + (size_t)k * P * D, P * D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_vmax + b * D, vmax + (size_t)k * D, D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync((double *)ps->S.amax + b * D, amax + (size_t)k * D, D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_delta + b, delta + k, 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->d_iv + b * D, iv ? iv + (size_t)k * D : zero.data(), D * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->S.path_state + b, path_state + k, 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(ps->S.has_path + b, &one, 4, hipMemcpyHostToDevice, nullptr));
-  }
-  HIPCHK(hipStreamSynchronize(nullptr));
+  const size_t D = ps->S.D, b = planner;
+  if (knots) HIPCHK(hipMemcpy(knots, ps->S.knots + b * ps->S.K, (size_t)(P + 3) * 8, hipMemcpyDeviceToHost));
+  if (cps) HIPCHK(hipMemcpy(cps, ps->d_cp + b * ps->pcap * D, (size_t)P * D * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2123,9 +2245,10 @@ int tpamd_planner_set_reset(tpamd_planner_set *ps, int count, const int32_t *ids
   PlannerSetState &S = ps->S;
   const int one = 1;
   const int n = ids ? count : (int)B;
+  for (int k = 0; k < n; k++)
+    if (ids && (ids[k] < 0 || (size_t)ids[k] >= B)) return TPAMD_E_INVALID_ARGUMENT;
   for (int k = 0; k < n; k++) {
     const size_t b = ids ? (size_t)ids[k] : (size_t)k;
-    if (b >= B) return TPAMD_E_INVALID_ARGUMENT;
     for (int *a : {S.path_state, S.has_path, S.count, S.initial_plan, S.target_reached, S.t_first, S.t_count})
       HIPCHK(hipMemsetAsync(a + b, 0, 4, nullptr));
     for (double *a : {S.path_horizon, S.path_start, S.path_start_velocity, S.path_time_start})
@@ -2135,6 +2258,7 @@ int tpamd_planner_set_reset(tpamd_planner_set *ps, int count, const int32_t *ids
     HIPCHK(hipMemcpyAsync(S.planned_to_end + b, &one, 4, hipMemcpyHostToDevice, nullptr));
   }
   HIPCHK(hipStreamSynchronize(nullptr));
+  for (int k = 0; k < n; k++) ps->h_has[ids ? (size_t)ids[k] : (size_t)k] = 0;
   return 0;
 }
 
@@ -2145,7 +2269,8 @@ int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const
   tpamd_engine *e = ps->e;
   TPAMD_ON_DEVICE(e);
   PlannerSetState &S = ps->S;
-  const size_t B = S.B, N = S.N, D = S.D, P = S.K - 3;
+  // the sampling kernel's LDS layout holds the largest path in use; each planner reads its own
+  const size_t B = S.B, N = S.N, D = S.D, P = largest_points(ps);
   hipStream_t st = nullptr;
   ps->last_h2d = ps->last_d2h = 0;
   HIPCHK(hipMemcpyAsync(ps->d_start, start_ns, B * 8, hipMemcpyHostToDevice, st));
@@ -2276,6 +2401,105 @@ int tpamd_planner_set_stop_parameters(tpamd_planner_set *ps, int count, const in
   std::memcpy(stop_parameter, out.data(), n * 8);
   if (duration) std::memcpy(duration, out.data() + n * 8, n * 8);
   std::memcpy(status, out.data() + n * 16, n * 4);
+  return 0;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                                   const double *keep_path_until, const int32_t *waypoint_offsets,
+                                   const double *waypoints, double *stop_parameter, int32_t *num_points,
+                                   int32_t *status) {
+  if (!ps || count < 0 || !time_ns || !waypoint_offsets || !waypoints || !stop_parameter || !num_points || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  const PlannerSetState &S = ps->S;
+  const size_t B = S.B, D = S.D;
+  if ((size_t)count > B) return TPAMD_E_INVALID_ARGUMENT;
+  // every id (in range, listed once) and the waypoint offsets are checked before anything changes
+  std::vector<char> seen(B, 0);
+  std::vector<int32_t> id(count);
+  for (int k = 0; k < count; k++) {
+    const long long b = ids ? (long long)ids[k] : (long long)k;
+    if (b < 0 || b >= (long long)B || seen[b]) return TPAMD_E_INVALID_ARGUMENT;
+    seen[b] = 1;
+    id[k] = (int32_t)b;
+  }
+  if (waypoint_offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  for (int k = 0; k < count; k++)
+    if (waypoint_offsets[k + 1] < waypoint_offsets[k]) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  // the new P of every listed planner is bounded by its current P and W; P_cap grows first
+  int need = 0, wmax = 0;
+  for (int k = 0; k < count; k++) {
+    const int W = waypoint_offsets[k + 1] - waypoint_offsets[k];
+    need = std::max(need, sw_points_bound(ps->h_np[id[k]], W));
+    wmax = std::max(wmax, W);
+  }
+  int rc = ensure_pcap(ps, need, st);
+  if (rc) return rc;
+  const size_t n = (size_t)count, rows = (size_t)waypoint_offsets[count];
+  const int scr_points = need, scr_work = (wmax + 3) * (int)D;
+  const size_t per_query = (size_t)scr_points + 3 + (size_t)scr_points * D + scr_work;
+  // device buffer: in [time_ns][keep][ids][offsets][waypoints] | out [stop][num_points][status] |
+  // stop status | scratch
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+  const size_t o_time = take(n * 8), o_keep = take(keep_path_until ? n * 8 : 0), o_ids = take(n * 4),
+               o_off = take((n + 1) * 4), o_wps = take(rows * D * 8);
+  const size_t in_end = off;
+  const size_t o_stop = take(n * 8), o_np = take(n * 4), o_status = take(n * 4);
+  const size_t out_begin = o_stop, out_end = off;
+  const size_t o_stop_status = take(n * 4), o_scr = take(n * per_query * 8);
+  if (off > ps->sw_bytes) {
+    if (ps->sw_buf) HIPCHK(hipFree(ps->sw_buf));
+    ps->sw_buf = nullptr;
+    ps->sw_bytes = 0;
+    HIPCHK(hipMalloc(&ps->sw_buf, off));
+    ps->sw_bytes = off;
+  }
+  char *base = (char *)ps->sw_buf;
+  std::vector<char> in(in_end, 0), out(out_end - out_begin);
+  std::memcpy(in.data() + o_time, time_ns, n * 8);
+  if (keep_path_until) std::memcpy(in.data() + o_keep, keep_path_until, n * 8);
+  std::memcpy(in.data() + o_ids, id.data(), n * 4);
+  std::memcpy(in.data() + o_off, waypoint_offsets, (n + 1) * 4);
+  if (rows) std::memcpy(in.data() + o_wps, waypoints, rows * D * 8);
+  HIPCHK(hipMemcpyAsync(base, in.data(), in_end, hipMemcpyHostToDevice, st));
+  if (!keep_path_until) {       // GetPathStopParameter(time) on the resident trajectories
+    FastestStopParams f{};
+    f.Q = count; f.stride = ps->tcap;
+    f.time = S.t_time; f.s = S.t_s; f.qd = S.t_qd; f.qdd = S.t_qdd;
+    f.count = S.t_count; f.first = S.t_first; f.initial_plan = S.initial_plan;
+    f.ids = (const int *)(base + o_ids);
+    f.amax = S.amax; f.query_ns = (const long long *)(base + o_time);
+    f.stop_s = (double *)(base + o_stop); f.status = (int *)(base + o_stop_status);
+    if (!launch_fastest_stop((int)D, f, st)) return TPAMD_E_UNSUPPORTED;
+  }
+  SwitchParams p{};
+  p.Q = count; p.D = (int)D; p.K = S.K; p.pcap = ps->pcap; p.tcap = ps->tcap;
+  p.scr_points = scr_points; p.scr_work = scr_work;
+  p.ids = (const int *)(base + o_ids); p.time_ns = (const long long *)(base + o_time);
+  p.keep = keep_path_until ? (const double *)(base + o_keep) : nullptr;
+  p.stop_in = (const double *)(base + o_stop); p.stop_status = (const int *)(base + o_stop_status);
+  p.offsets = (const int *)(base + o_off); p.wps = (const double *)(base + o_wps);
+  p.knots = (double *)S.knots; p.cps = ps->d_cp; p.iv = ps->d_iv; p.np = S.np; p.path_state = S.path_state;
+  p.has_path = S.has_path; p.initial_plan = S.initial_plan; p.t_first = S.t_first; p.t_count = S.t_count;
+  p.t_time = S.t_time; p.t_qd = S.t_qd;
+  p.scr = (double *)(base + o_scr);
+  p.stop_out = (double *)(base + o_stop); p.np_out = (int *)(base + o_np); p.status_out = (int *)(base + o_status);
+  hipLaunchKernelGGL(k_pset_switch, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out.data(), base + out_begin, out.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(stop_parameter, out.data() + (o_stop - out_begin), n * 8);
+  std::memcpy(num_points, out.data() + (o_np - out_begin), n * 4);
+  std::memcpy(status, out.data() + (o_status - out_begin), n * 4);
+  for (size_t k = 0; k < n; k++)
+    if (status[k] == TPAMD_PLAN_OK) ps->h_np[id[k]] = num_points[k];
   return 0;
 }
 

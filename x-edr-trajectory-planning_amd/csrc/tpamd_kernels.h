@@ -47,6 +47,10 @@ struct Workspace {
   long long *diag;  // [B][64] cycle counters; filled only by -DTPAMD_DIAG builds
   double *sd2_out;  // optional caller copy of sd2 ([B][N]); may be null
   int keep_boundary;  // the fused boundary passes also store sdd_max/sdd_min/type (debug copy)
+  // Planner sets with paths of different sizes: control points of each path (null: every path
+  // has the launch's P) and the per-path stride of the knot / control-point arrays (P_cap).
+  const int32_t *np;
+  int p_stride;
 };
 
 __device__ __forceinline__ int path_samples(const Workspace &ws, int b, int N) {
@@ -268,11 +272,14 @@ __device__ __forceinline__ void sample_lp_joint_body(int N, int D_rt, int P, con
   const int TPB = blockDim.x;
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
-  const int K = P + 3;
+  const int K = P + 3;                        // LDS layout: the largest P of the launch
   const int D = DT ? DT : D_rt;
   const int C = 2 * D;
   // a block that lies wholly behind the end of a (ragged) path has nothing to do
   if ((int)(blockIdx.x * TPB) >= path_samples(ws, b, N)) return;
+  const int Ps = ws.np ? ws.p_stride : P;     // stride of the path arrays
+  const int Pb = ws.np ? ws.np[b] : P;        // this path's control points
+  const int Kb = Pb + 3;
   double q1r[DT ? DT : 1], q2r[DT ? DT : 1];
   double *s_knots = lds;
   double *s_cp = s_knots + K;
@@ -280,8 +287,8 @@ __device__ __forceinline__ void sample_lp_joint_body(int N, int D_rt, int P, con
   double *s_hi = s_lo + C;
   double *s_Q1 = s_hi + C;
   double *s_Q2 = s_Q1 + (size_t)D * TPB;
-  for (int k = tid; k < K; k += TPB) s_knots[k] = knots_g[(size_t)b * K + k];
-  for (int k = tid; k < P * D; k += TPB) s_cp[k] = cps_g[(size_t)b * P * D + k];
+  for (int k = tid; k < Kb; k += TPB) s_knots[k] = knots_g[(size_t)b * (Ps + 3) + k];
+  for (int k = tid; k < Pb * D; k += TPB) s_cp[k] = cps_g[(size_t)b * Ps * D + k];
   for (int k = tid; k < 2 * C; k += TPB) s_lo[k] = ws.lim[(size_t)b * 2 * C + k];
   __syncthreads();
   const int i0 = blockIdx.x * TPB;
@@ -292,7 +299,7 @@ __device__ __forceinline__ void sample_lp_joint_body(int N, int D_rt, int P, con
 
   const double path_start = ws.s_start[b];
   const double delta = ws.delta[b];
-  const double k0 = s_knots[0], kend = s_knots[K - 1];
+  const double k0 = s_knots[0], kend = s_knots[Kb - 1];
   const double parameter = path_start + i * delta;
   double *Q1 = s_Q1 + tid, *Q2 = s_Q2 + tid;
   if (!live) {
@@ -301,7 +308,7 @@ __device__ __forceinline__ void sample_lp_joint_body(int N, int D_rt, int P, con
     double u = parameter;
     if (u < k0) u = k0;
     if (kend < u) u = kend;
-    const int span = knot_span_deg2(s_knots, K, u);
+    const int span = knot_span_deg2(s_knots, Kb, u);
     double ders[3][3];
     basis_ders_deg2(s_knots, span, u, ders);
     const double *p0 = s_cp + (size_t)(span - 2) * D, *p1 = p0 + D, *p2 = p1 + D;
@@ -317,7 +324,7 @@ __device__ __forceinline__ void sample_lp_joint_body(int N, int D_rt, int P, con
       if (DT) { q1r[d] = v1; q2r[d] = v2; }
     }
   } else {
-    const double *pl = s_cp + (size_t)(P - 1) * D;
+    const double *pl = s_cp + (size_t)(Pb - 1) * D;
 #pragma unroll
     for (int d = 0; d < D; d++) {
       if (q_out) q_out[o * D + d] = pl[d];
@@ -1646,6 +1653,7 @@ struct PlanParams {
   int B, N, D, K, cap, max_iterations;
   double max_initial_velocity_error;
   const double *knots;             // [B][K]
+  const int *np;                   // [B] control points of each path (planner sets), null: K - 3
   const double *delta;             // [B]
   const double *initial_velocity;  // [B][D]
   const long long *start_ns, *horizon_ns;   // [B] arguments of Plan
@@ -1761,7 +1769,8 @@ static __global__ void k_plan_end(PlanParams p) {
   const int lei = p.w_lei[b];
   const int decel_start = max(lei, N / 2);
   p.final_decel_start_ns[b] = (long long)(t[decel_start] * 1e9);
-  const double kend = p.knots[(size_t)b * p.K + p.K - 1];
+  const int kb = p.np ? p.np[b] + 3 : p.K;
+  const double kend = p.knots[(size_t)b * p.K + kb - 1];
   const int planned_to_end = p.path_horizon[b] >= kend - 1e-4;     // CloseToEnd, kSmall
   p.planned_to_end[b] = planned_to_end;
   const bool reached = (t[N - 1] - (double)p.start_ns[b] / 1e9) > (double)p.horizon_ns[b] / 1e9;

@@ -29,7 +29,8 @@ struct PlannerSetState {
   double time_step_sec;
   long long time_step_duration_ns;      // absl::Seconds(time_step_sec_): llround(s * 1e9)
   // path
-  const double *knots;                  // [B][K]
+  const double *knots;                  // [B][K]: K = P_cap + 3, the stride
+  int *np;                              // [B] control points of each planner's path (<= P_cap)
   const double *amax;                   // [B][D]
   int *path_state;                      // [B]
   int *has_path;                        // [B]
@@ -97,7 +98,7 @@ static __global__ void k_pset_prologue(PlannerSetState S) {
     S.path_horizon[b] = 0.0;
     S.path_start[b] = 0.0;
   } else {
-    const double kend = S.knots[(size_t)b * S.K + S.K - 1];
+    const double kend = S.knots[(size_t)b * S.K + S.np[b] + 2];
     planned_to_end = S.path_horizon[b] >= kend - 1e-4;    // CloseToEnd
     if (planned_to_end) {
       if (!fresh) {

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
-            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h"]
+            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h", "tpamd_switch.h"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -190,7 +190,8 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
     "tpamd_planner_set_reset", "tpamd_planner_set_plan", "tpamd_planner_set_download_trajectory",
     "tpamd_planner_set_last_plan_bytes", "tpamd_planner_set_device_bytes",
-    "tpamd_planner_set_stop_parameters", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
+    "tpamd_planner_set_stop_parameters", "tpamd_planner_set_upload_paths_ragged",
+    "tpamd_planner_set_download_path", "tpamd_planner_set_switch_paths", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
     "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
     "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
     "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_kernel_vgprs",

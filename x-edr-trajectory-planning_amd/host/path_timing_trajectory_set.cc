@@ -54,16 +54,15 @@ Status PathTimingTrajectorySet::SetPath(size_t planner, const TimeableJointSplin
   if (path.NumDofs() != options_.GetNumDofs()) return InvalidArgumentError("Path and planner disagree on the number of dofs");
   if (path.NumPathSamples() != options_.GetNumPathSamples())
     return InvalidArgumentError("Path and planner disagree on the number of path samples");
-  if ((size_t)path.num_control_points() != num_control_points_)
-    return InvalidArgumentError("the set holds splines of one size (control points)");
+  if (path.num_control_points() < 3) return FailedPreconditionError("SetWaypoints / SwitchToWaypointPath first");
   if (path.options().constraint_safety() != constraint_safety_) return InvalidArgumentError("constraint safety differs");
   const int state = StateCode(path.GetState());
   if (state != 1 && state != 2) return FailedPreconditionError("SetWaypoints / SwitchToWaypointPath first");
-  const int32_t id = (int32_t)planner, st = state;
+  const int32_t id = (int32_t)planner, st = state, np = path.num_control_points();
   const double delta = path.GetPathSamplingDistance();
-  const int rc = tpamd_planner_set_upload_paths(set_, 1, &id, path.knots().data(), path.packed_control_points().data(),
-                                                path.GetMaxJointVelocity().data(), path.GetMaxJointAcceleration().data(),
-                                                &delta, path.GetInitialVelocity().data(), &st);
+  const int rc = tpamd_planner_set_upload_paths_ragged(
+      set_, 1, &id, &np, path.knots().data(), path.packed_control_points().data(), path.GetMaxJointVelocity().data(),
+      path.GetMaxJointAcceleration().data(), &delta, path.GetInitialVelocity().data(), &st);
   if (rc != 0) return InternalError(tpamd_error_string(rc));
   summary_[planner].path_state = state;
   return OkStatus();
@@ -72,18 +71,20 @@ Status PathTimingTrajectorySet::SetPath(size_t planner, const TimeableJointSplin
 Status PathTimingTrajectorySet::SetPaths(const std::vector<std::shared_ptr<TimeableJointSplinePath>> &paths) {
   if (!init_status_.ok()) return init_status_;
   if (paths.size() > num_planners_) return InvalidArgumentError("more paths than planners");
-  const size_t n = paths.size(), D = options_.GetNumDofs(), P = num_control_points_;
-  std::vector<double> knots(n * (P + 3)), cps(n * P * D), vmax(n * D), amax(n * D), dl(n), iv(n * D);
-  std::vector<int32_t> st(n);
+  const size_t n = paths.size(), D = options_.GetNumDofs();
+  std::vector<double> knots, cps, vmax(n * D), amax(n * D), dl(n), iv(n * D);
+  std::vector<int32_t> st(n), np(n);
   for (size_t k = 0; k < n; k++) {
     const TimeableJointSplinePath &p = *paths[k];
     if (p.NumDofs() != D || p.NumPathSamples() != options_.GetNumPathSamples() ||
-        (size_t)p.num_control_points() != P || p.options().constraint_safety() != constraint_safety_)
+        p.options().constraint_safety() != constraint_safety_)
       return InvalidArgumentError("path does not have the shape of the set");
     st[k] = StateCode(p.GetState());
     if (st[k] != 1 && st[k] != 2) return FailedPreconditionError("SetWaypoints / SwitchToWaypointPath first");
-    std::copy(p.knots().begin(), p.knots().end(), knots.begin() + k * (P + 3));
-    std::copy(p.packed_control_points().begin(), p.packed_control_points().end(), cps.begin() + k * P * D);
+    np[k] = p.num_control_points();
+    if (np[k] < 3) return FailedPreconditionError("SetWaypoints / SwitchToWaypointPath first");
+    knots.insert(knots.end(), p.knots().begin(), p.knots().end());       // packed back to back
+    cps.insert(cps.end(), p.packed_control_points().begin(), p.packed_control_points().end());
     for (size_t d = 0; d < D; d++) {
       vmax[k * D + d] = p.GetMaxJointVelocity()[d];
       amax[k * D + d] = p.GetMaxJointAcceleration()[d];
@@ -91,8 +92,8 @@ Status PathTimingTrajectorySet::SetPaths(const std::vector<std::shared_ptr<Timea
     }
     dl[k] = p.GetPathSamplingDistance();
   }
-  const int rc = tpamd_planner_set_upload_paths(set_, (int)n, nullptr, knots.data(), cps.data(), vmax.data(), amax.data(),
-                                                dl.data(), iv.data(), st.data());
+  const int rc = tpamd_planner_set_upload_paths_ragged(set_, (int)n, nullptr, np.data(), knots.data(), cps.data(),
+                                                       vmax.data(), amax.data(), dl.data(), iv.data(), st.data());
   if (rc != 0) return InternalError(tpamd_error_string(rc));
   for (size_t k = 0; k < n; k++) summary_[k].path_state = st[k];
   return OkStatus();
@@ -181,6 +182,64 @@ std::vector<StatusOr<double>> PathTimingTrajectorySet::GetPathStopParameters(con
   out.reserve(n);
   for (size_t b = 0; b < n; b++) out.push_back(StopResult(st[b], s[b], t[b]));
   return out;
+}
+
+std::vector<Status> PathTimingTrajectorySet::SwitchToWaypointPaths(const std::vector<size_t> &planners,
+                                                                  const std::vector<Time> &time,
+                                                                  const std::vector<std::vector<VectorXd>> &waypoints) {
+  const size_t n = planners.size(), D = options_.GetNumDofs();
+  if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
+  if (time.size() != n || waypoints.size() != n)
+    return std::vector<Status>(n, InvalidArgumentError("one time and one waypoint list per planner"));
+  std::vector<int32_t> ids(n), offsets(n + 1, 0), np(n), st(n);
+  std::vector<int64_t> t(n);
+  std::vector<double> wps, stop(n);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_) return std::vector<Status>(n, InvalidArgumentError("no such planner"));
+    ids[k] = (int32_t)planners[k];
+    t[k] = ::tpamd::compat::ToUnixNanos(time[k]);
+    for (const VectorXd &w : waypoints[k]) {
+      if (w.size() != D) return std::vector<Status>(n, InvalidArgumentError("waypoint has the wrong dimension"));
+      wps.insert(wps.end(), w.begin(), w.end());
+    }
+    offsets[k + 1] = offsets[k] + (int32_t)waypoints[k].size();
+  }
+  if (wps.empty()) wps.push_back(0.0);      // the entry takes a non-NULL array even without rows
+  const int rc = tpamd_planner_set_switch_paths(set_, (int)n, ids.data(), t.data(), nullptr, offsets.data(),
+                                                wps.data(), stop.data(), np.data(), st.data());
+  if (rc != 0) return std::vector<Status>(n, rc == TPAMD_E_INVALID_ARGUMENT ? InvalidArgumentError(tpamd_error_string(rc))
+                                                                           : InternalError(tpamd_error_string(rc)));
+  std::vector<Status> result(n, OkStatus());
+  for (size_t k = 0; k < n; k++) {
+    switch (st[k]) {
+      case TPAMD_PLAN_OK: summary_[planners[k]].path_state = 2; break;     // kModifiedPath
+      case TPAMD_PLAN_FAILED_PRECONDITION: result[k] = FailedPreconditionError("no path or no plan to switch from"); break;
+      case TPAMD_PLAN_OUT_OF_RANGE: result[k] = OutOfRangeError("switch time or parameter outside the path"); break;
+      case TPAMD_PLAN_INVALID_ARGUMENT: result[k] = InvalidArgumentError("Time not in timed path range / no waypoints left"); break;
+      default: result[k] = InternalError("path switch failed"); break;
+    }
+  }
+  return result;
+}
+
+Status PathTimingTrajectorySet::GetPath(size_t planner, std::vector<double> *knots,
+                                        std::vector<double> *control_points) const {
+  if (!init_status_.ok()) return init_status_;
+  if (planner >= num_planners_ || !knots || !control_points) return InvalidArgumentError("no such planner");
+  const size_t P = NumControlPoints(planner), D = options_.GetNumDofs();
+  knots->assign(P ? P + 3 : 0, 0.0);
+  control_points->assign(P * D, 0.0);
+  if (P == 0) return OkStatus();
+  int32_t got = 0;
+  const int rc = tpamd_planner_set_download_path(set_, (int)planner, &got, knots->data(), control_points->data(), (int)P);
+  return rc == 0 && (size_t)got == P ? OkStatus() : InternalError(tpamd_error_string(rc));
+}
+
+size_t PathTimingTrajectorySet::NumControlPoints(size_t planner) const {
+  if (!init_status_.ok() || planner >= num_planners_) return 0;
+  int32_t np = 0;
+  tpamd_planner_set_download_path(set_, (int)planner, &np, nullptr, nullptr, 0);   // host copy: no transfer
+  return (size_t)np;
 }
 
 Status PathTimingTrajectorySet::GetTrajectory(size_t planner, PlannedTrajectory *out) const {

@@ -1,5 +1,5 @@
 // PathTimingTrajectorySet -- B PathTimingTrajectory planners (path_timing_trajectory.h:91-186) with
-// TimeableJointSplinePath paths of one shape whose state stays ON THE DEVICE between Plan calls
+// TimeableJointSplinePath paths (any number of control points) whose state stays ON THE DEVICE between Plan calls
 // (include/tpamd.h tpamd_planner_set_*). Where PathTimingTrajectory::PlanBatch ships every
 // planner's window history up and down on each call (about 200 MB each way for 1024 planners),
 // a Plan call here moves 24 bytes per planner up and one 56-byte record down; the histories, the
@@ -7,9 +7,11 @@
 // path_timing_trajectory.cc:540-577, :660-684 run on the device. Every planner ends in exactly the
 // state Plan(start, time_horizon) would have left a PathTimingTrajectory in.
 //
-// The waypoint fit and online path edits stay on the host (TimeableJointSplinePath::SetWaypoints,
-// SwitchToWaypointPath: O(waypoints)); SetPath uploads the resulting spline and its state.
-// Trajectories come down only when asked for (GetTrajectory).
+// The waypoint fit stays on the host (TimeableJointSplinePath::SetWaypoints); SetPath uploads the
+// resulting spline and its state. The online switch to new waypoints runs on the device
+// (SwitchToWaypointPaths): stop parameter, velocity at the switch time and the spline edit, with
+// no trajectory download. Splines of different sizes share a set. Trajectories come down only when
+// asked for (GetTrajectory).
 #ifndef TPAMD_HOST_PATH_TIMING_TRAJECTORY_SET_H_
 #define TPAMD_HOST_PATH_TIMING_TRAJECTORY_SET_H_
 
@@ -30,8 +32,9 @@ struct PlannedTrajectory {
 
 class PathTimingTrajectorySet {
  public:
-  // All planners share the planner options, the path options (dofs, samples, delta may differ per
-  // path: it is taken from each path) and the number of control points of their splines.
+  // All planners share the planner options and the path options (dofs, samples; delta may differ
+  // per path: it is taken from each path). num_control_points is the per-planner capacity the
+  // set starts with; paths of any size are accepted and the capacity grows as needed.
   PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
                           size_t num_control_points, double constraint_safety = 0.8, int device = -1);
   ~PathTimingTrajectorySet();
@@ -41,8 +44,8 @@ class PathTimingTrajectorySet {
   Status status() const { return init_status_; }      // construction outcome (no GPU: not ok)
   size_t size() const { return num_planners_; }
   // SetPath for one planner / for planners 0..paths.size()-1: the path must be kNewPath (after
-  // SetWaypoints) or kModifiedPath (after SwitchToWaypointPath); its spline, limits, sampling
-  // distance and initial velocity go to the device.
+  // SetWaypoints) or kModifiedPath (after SwitchToWaypointPath); its spline (any number of
+  // control points >= 3), limits, sampling distance and initial velocity go to the device.
   Status SetPath(size_t planner, const TimeableJointSplinePath &path);
   Status SetPaths(const std::vector<std::shared_ptr<TimeableJointSplinePath>> &paths);
   void Reset(size_t planner);
@@ -70,6 +73,17 @@ class PathTimingTrajectorySet {
   // (one launch, no trajectory download). No planner state changes.
   ::tpamd::compat::StatusOr<double> GetPathStopParameter(size_t planner, Time time) const;
   std::vector<::tpamd::compat::StatusOr<double>> GetPathStopParameters(const std::vector<Time> &time) const;
+  // The online path switch of path_timing_trajectory_test.cc:298-420 for the listed planners, on
+  // the device (tpamd_planner_set_switch_paths): stop = GetPathStopParameter(time[k]);
+  // path->SwitchToWaypointPath(stop, waypoints[k]); path->SetInitialVelocity(the trajectory's
+  // GetVelocityAtTime(time[k])). The next Plan plans the modified path. One status per listed
+  // planner; a planner whose switch failed keeps its state. The new control polygon is rounded
+  // with the PathOptions default radius (0.2).
+  std::vector<Status> SwitchToWaypointPaths(const std::vector<size_t> &planners, const std::vector<Time> &time,
+                                            const std::vector<std::vector<VectorXd>> &waypoints);
+  // The planner's resident spline (no path: empty) and its number of control points.
+  Status GetPath(size_t planner, std::vector<double> *knots, std::vector<double> *control_points) const;
+  size_t NumControlPoints(size_t planner) const;
   // The planner's trajectory (GetTime, GetPositions, ...): one download of its samples.
   Status GetTrajectory(size_t planner, PlannedTrajectory *out) const;
   // Bytes the last Plan call moved over PCIe, both directions.

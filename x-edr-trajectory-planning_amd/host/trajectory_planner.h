@@ -3,6 +3,7 @@
 #ifndef TPAMD_HOST_TRAJECTORY_PLANNER_H_
 #define TPAMD_HOST_TRAJECTORY_PLANNER_H_
 
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -48,6 +49,22 @@ class TrajectoryPlanner {
   const std::vector<double> &GetPathParameterDerivatives() const { return path_parameter_derivative_; }
   const std::vector<double> &GetSecondPathParameterDerivatives() const {
     return second_path_parameter_derivative_;
+  }
+  // TrajectoryBuffer::GetVelocityAtTime (trajectory_buffer.cc:233-275): the bracket of `time`
+  // by upper_bound over GetTime(), then InterpolateLinear (a + t (b - a) with t the time fraction)
+  // between its velocities; a time on the last sample gives that sample's velocity.
+  ::tpamd::compat::StatusOr<VectorXd> GetVelocityAtTime(Time time) const {
+    if (time_.empty()) return ::tpamd::compat::FailedPreconditionError("No samples.");
+    const double time_sec = (double)::tpamd::compat::ToUnixNanos(time) / 1e9;
+    if (time_sec < time_.front() || time_sec > time_.back())
+      return ::tpamd::compat::OutOfRangeError("Time outside the trajectory");
+    const auto upper = std::upper_bound(time_.begin(), time_.end(), time_sec);
+    if (upper == time_.end()) return velocities_.back();
+    const size_t u = upper - time_.begin(), l = u - 1;
+    const double t = (time_sec - time_[l]) / (time_[u] - time_[l]);
+    VectorXd v(velocities_[l].size());
+    for (size_t d = 0; d < v.size(); d++) v[d] = velocities_[l][d] + t * (velocities_[u][d] - velocities_[l][d]);
+    return v;
   }
   virtual bool IsTrajectoryAtEnd() const {
     const bool path_unchanged = path_ == nullptr ||
