@@ -431,9 +431,66 @@ int tpamd_planner_set_plan(tpamd_planner_set *set, const int64_t *start_ns, cons
 int tpamd_planner_set_download_trajectory(tpamd_planner_set *set, int planner, int first, int count,
                                           double *time, double *s, double *sd, double *sdd,
                                           double *q, double *qd, double *qdd);
+/* Setpoints at control ticks. For listed planner k (ids[k], or k if ids is NULL; repeats allowed)
+ * and tick j < num_ticks, time_ns = start_ns[k] + j * step_ns (converted as (double)ns / 1e9 like
+ * the rest of the set). Outputs are TrajectoryBuffer::Get{Position,Velocity,Acceleration}AtTime
+ * (trajectory_buffer.cc:228-294: the upper_bound bracket, then InterpolateLinear; at the last
+ * sample that sample) on the planner's resident trajectory, in q / qd / qdd [count][num_ticks][D]
+ * (any of them may be NULL), and status [count][num_ticks]: TPAMD_PLAN_OK,
+ * TPAMD_PLAN_FAILED_PRECONDITION (no samples: never planned, or reset) or TPAMD_PLAN_OUT_OF_RANGE
+ * (before the first or after the last sample, or a tick time that overflows int64). The values of
+ * a tick that is not OK are left untouched. No planner state changes.
+ * Call-level errors change nothing: a NULL set / start_ns / status, count < 0, count > B with a
+ * NULL ids, step_ns <= 0, num_ticks < 1, and in this host variant an id out of range (every id is
+ * checked before the first copy). One copy up, one launch, one copy down per requested array.
+ * Host pointers; synchronises. */
+int tpamd_planner_set_sample_at_ticks(tpamd_planner_set *set, int count, const int32_t *ids,
+                                      const int64_t *start_ns, int64_t step_ns, int num_ticks,
+                                      double *q, double *qd, double *qdd, int32_t *status);
+/* The same with every array (ids, start_ns, q, qd, qdd, status) a device pointer. Only enqueues on
+ * hip_stream (NULL: the null stream) and does not synchronise. ids are checked in the kernel: an
+ * id out of range gives TPAMD_PLAN_INVALID_ARGUMENT for each of its ticks. Stream ordering: see
+ * tpamd_planner_set_download_trajectories_device. */
+int tpamd_planner_set_sample_at_ticks_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                             const int64_t *start_ns, int64_t step_ns, int num_ticks,
+                                             double *q, double *qd, double *qdd, int32_t *status,
+                                             void *hip_stream);
+/* The trajectories of the listed planners (ids[count], repeats allowed, or planners 0..count-1 if
+ * ids is NULL), packed: planner k's samples fill rows offsets[k] .. offsets[k+1) of time / s / sd /
+ * sdd [rows] and q / qd / qdd [rows][D] (any may be NULL), as tpamd_planner_set_download_trajectory
+ * gives them one planner at a time. offsets [count + 1] is always written. If offsets[count] >
+ * capacity (rows the arrays hold), no row is written and this host variant returns
+ * TPAMD_E_INVALID_ARGUMENT: the caller grows its arrays to offsets[count] and calls again.
+ * Call-level errors as for tpamd_planner_set_sample_at_ticks (NULL offsets, capacity < 0).
+ * ids up, one scan, offsets down, one pack, one copy down per requested array. Host pointers;
+ * synchronises. No planner state changes. */
+int tpamd_planner_set_download_trajectories(tpamd_planner_set *set, int count, const int32_t *ids,
+                                            int64_t *offsets, int64_t capacity, double *time,
+                                            double *s, double *sd, double *sdd, double *q,
+                                            double *qd, double *qdd);
+/* The same with ids, offsets and the arrays on the device; enqueues on hip_stream and does not
+ * synchronise. It cannot know the total when it returns: if offsets[count] > capacity the rows stay
+ * unwritten, and the caller reads offsets[count] before using them. An id out of range gets an
+ * empty row range.
+ * Stream ordering of the two _device readouts with the set's other calls, whatever hip_stream is
+ * (a non-blocking stream included): a readout sees the set's last change (the changing calls
+ * enqueue on the null stream and synchronise before they return; the readout's stream also waits
+ * on an event recorded on the null stream when it is enqueued). The calls that change planner
+ * state (upload_paths*, switch_paths, reset, plan) make the null stream wait on an event recorded
+ * after the last device readout before their first copy or launch, so they never overwrite a
+ * trajectory a readout is still reading; successive device readouts on different streams are
+ * chained the same way. The set must outlive the readouts' use of its trajectories until then
+ * (tpamd_planner_set_destroy waits for them). */
+int tpamd_planner_set_download_trajectories_device(tpamd_planner_set *set, int count,
+                                                   const int32_t *ids, int64_t *offsets,
+                                                   int64_t capacity, double *time, double *s,
+                                                   double *sd, double *sdd, double *q, double *qd,
+                                                   double *qdd, void *hip_stream);
 /* Bytes the last tpamd_planner_set_plan call moved over PCIe (host to device, device to host). */
 void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *set, size_t *host_to_device,
                                        size_t *device_to_host);
+/* Device memory the set holds: its state, and the staging of the switch and the host readouts,
+ * which grows as calls need it. */
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *set);
 
 /* Batched TimeOptimalPathProfile::FindMaxSd2Simplex (time_optimal_path_timing.cc:1149-1363)

@@ -1,0 +1,48 @@
+"""The planner-set readout's bracket and interpolation on the CPU: csrc/tpamd_readout.h (host/device
+functions) compiled for the host and compared bit for bit with the mirror's
+TrajectoryPlanner::Get{Position,Velocity,Acceleration}AtTime, and the switch's sw_velocity_at_time,
+which takes the same bracket, with GetVelocityAtTime (tests/cpp/test_readout_interp.cc). No GPU
+needed."""
+import os
+import subprocess
+
+from conftest import ROOT, PKG_NAME
+
+
+def _build_driver(tmp_path):
+    exe = str(tmp_path / "test_readout_interp")
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
+           os.path.join(ROOT, "tests", "cpp", "test_readout_interp.cc")]
+    subprocess.check_call(cmd)
+    return exe
+
+
+def test_readout_interpolation_matches_mirror_bit_for_bit(tmp_path):
+    exe = _build_driver(tmp_path)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    print(out.stdout[-3000:])
+    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+    counts = {}
+    for line in out.stdout.splitlines():
+        if line.startswith("category "):
+            name, n = line[len("category "):].rsplit(":", 1)
+            counts[name.strip()] = int(n)
+        if line.startswith("interpolation cases:"):
+            assert int(line.split(":")[1]) >= 20000
+    # every edge of the bracket is reached
+    for cat in ("on a sample/ok", "between samples/ok", "first sample/ok", "last sample/ok", "inside/ok",
+                "1 ns before the first/status 2", "1 ns after the last/status 2", "on a repeated stamp/ok",
+                "one sample/ok", "one sample/status 2", "empty/status 1"):
+        assert counts.get(cat, 0) > 0, (cat, counts)
+    assert "tick times: ok" in out.stdout
+
+
+def test_readout_exports_are_declared():
+    """The four readout entry points are in the header and registered with the binding."""
+    hdr = open(os.path.join(ROOT, "include", "tpamd.h")).read()
+    src = open(os.path.join(ROOT, PKG_NAME, "engine.py")).read()
+    for name in ("tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
+                 "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device"):
+        assert "int %s(" % name in hdr, name
+        assert '"%s"' % name in src, name
+    assert '"tpamd_readout.h"' in src

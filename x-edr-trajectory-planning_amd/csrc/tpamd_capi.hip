@@ -15,6 +15,7 @@
 #include "tpamd_kernels.h"
 #include "tpamd_launch.h"
 #include "tpamd_planner_set.h"
+#include "tpamd_readout.h"
 #include "tpamd_stop.h"
 #include "tpamd_switch.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
@@ -1916,6 +1917,13 @@ struct tpamd_planner_set {
   PlannerSummaryDev *d_summary = nullptr;
   char *d_stop_in = nullptr, *d_stop_out = nullptr;   // stop queries: [time_ns][ids], [s][duration][status]
   size_t last_h2d = 0, last_d2h = 0;
+  // staging of the host readouts (inputs and offsets | packed rows or tick values); they grow
+  void *rd_in = nullptr, *rd_out = nullptr;
+  size_t rd_in_bytes = 0, rd_out_bytes = 0;
+  // device readouts run on the caller's stream: ev_set orders them after the set's last change,
+  // ev_read (recorded after each of them) orders the next change after them
+  hipEvent_t ev_set = nullptr, ev_read = nullptr;
+  bool read_pending = false;
 };
 
 namespace {
@@ -2034,6 +2042,72 @@ int largest_points(const tpamd_planner_set *ps) {
   return m;
 }
 
+// Called by every call that changes planner state, before its first copy or launch (all of them
+// run on the null stream): the device readouts still in flight on other streams finish first.
+int order_after_readouts(tpamd_planner_set *ps) {
+  if (!ps->read_pending) return 0;
+  HIPCHK(hipStreamWaitEvent(nullptr, ps->ev_read, 0));
+  ps->read_pending = false;
+  return 0;
+}
+
+// A device readout on `st`: it starts after everything enqueued on the null stream so far (the
+// set's changes; they also synchronise before they return, except on an error path) and after the
+// previous device readout (so that ev_read, recorded after this one, covers both).
+int readout_begin(tpamd_planner_set *ps, hipStream_t st) {
+  HIPCHK(hipEventRecord(ps->ev_set, nullptr));
+  HIPCHK(hipStreamWaitEvent(st, ps->ev_set, 0));
+  if (ps->read_pending) HIPCHK(hipStreamWaitEvent(st, ps->ev_read, 0));
+  return 0;
+}
+int readout_end(tpamd_planner_set *ps, hipStream_t st) {
+  HIPCHK(hipEventRecord(ps->ev_read, st));
+  ps->read_pending = true;
+  return 0;
+}
+
+// Grow a staging buffer of the host readouts to at least `bytes` (contents are not kept).
+int ensure_staging(void **buf, size_t *have, size_t bytes) {
+  if (bytes <= *have) return 0;
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  HIPCHK(hipMalloc(buf, bytes));
+  *have = bytes;
+  return 0;
+}
+
+// ReadoutParams view of the set's resident trajectories
+ReadoutParams readout_params(const tpamd_planner_set *ps) {
+  const PlannerSetState &S = ps->S;
+  ReadoutParams p{};
+  p.B = S.B; p.D = S.D; p.tcap = ps->tcap;
+  p.t_first = S.t_first; p.t_count = S.t_count;
+  p.t_time = S.t_time; p.t_s = S.t_s; p.t_sd = S.t_sd; p.t_sdd = S.t_sdd;
+  p.t_q = S.t_q; p.t_qd = S.t_qd; p.t_qdd = S.t_qdd;
+  return p;
+}
+
+// The call-level checks of the four readouts; host_ids: every id is checked here too.
+bool sample_args_ok(const tpamd_planner_set *ps, int count, const int32_t *ids, bool host_ids, const int64_t *start_ns,
+                    int64_t step_ns, int num_ticks, const int32_t *status) {
+  if (!ps || count < 0 || !start_ns || !status || step_ns <= 0 || num_ticks < 1) return false;
+  if (!ids && count > ps->S.B) return false;
+  if (ids && host_ids)
+    for (int k = 0; k < count; k++)
+      if (ids[k] < 0 || ids[k] >= ps->S.B) return false;
+  return true;
+}
+bool pack_args_ok(const tpamd_planner_set *ps, int count, const int32_t *ids, bool host_ids, const int64_t *offsets,
+                  int64_t capacity) {
+  if (!ps || count < 0 || !offsets || capacity < 0) return false;
+  if (!ids && count > ps->S.B) return false;
+  if (ids && host_ids)
+    for (int k = 0; k < count; k++)
+      if (ids[k] < 0 || ids[k] >= ps->S.B) return false;
+  return true;
+}
+
 // tpamd_planner_set_upload_paths(_ragged): num_points null = every path has the config's P
 int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *num_points,
                         const double *knots, const double *cps, const double *vmax, const double *amax,
@@ -2053,6 +2127,7 @@ int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, co
   if (count == 0) return 0;
   TPAMD_ON_DEVICE(ps->e);
   hipStream_t st = nullptr;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
   const int grc = ensure_pcap(ps, need, st);
   if (grc) return grc;
   const size_t Pc = ps->pcap, Kc = Pc + 3, n = (size_t)count;
@@ -2180,6 +2255,11 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
     return TPAMD_E_HIP;
   }
   refresh_plan_params(ps);
+  if (hipEventCreateWithFlags(&ps->ev_set, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&ps->ev_read, hipEventDisableTiming) != hipSuccess) {
+    tpamd_planner_set_destroy(ps);
+    return TPAMD_E_HIP;
+  }
   // ResetDerived :213-227: planned_to_end_ = true (all other scalars zero)
   std::vector<int> ones(B, 1);
   if (hipMemcpy(S.planned_to_end, ones.data(), B * 4, hipMemcpyHostToDevice) != hipSuccess) {
@@ -2193,6 +2273,11 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
 void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (!ps) return;
   DeviceScope scope(ps->e->device);
+  if (ps->read_pending) (void)hipEventSynchronize(ps->ev_read);   // a device readout may still read the set
+  if (ps->ev_set) (void)hipEventDestroy(ps->ev_set);
+  if (ps->ev_read) (void)hipEventDestroy(ps->ev_read);
+  if (ps->rd_in) (void)hipFree(ps->rd_in);
+  if (ps->rd_out) (void)hipFree(ps->rd_out);
   if (ps->fixed) (void)hipFree(ps->fixed);
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
@@ -2202,7 +2287,9 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
 }
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
-  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_bytes : 0;
+  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_bytes + ps->rd_in_bytes +
+                   ps->rd_out_bytes
+            : 0;
 }
 
 void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *ps, size_t *h2d, size_t *d2h) {
@@ -2247,6 +2334,7 @@ int tpamd_planner_set_reset(tpamd_planner_set *ps, int count, const int32_t *ids
   const int n = ids ? count : (int)B;
   for (int k = 0; k < n; k++)
     if (ids && (ids[k] < 0 || (size_t)ids[k] >= B)) return TPAMD_E_INVALID_ARGUMENT;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
   for (int k = 0; k < n; k++) {
     const size_t b = ids ? (size_t)ids[k] : (size_t)k;
     for (int *a : {S.path_state, S.has_path, S.count, S.initial_plan, S.target_reached, S.t_first, S.t_count})
@@ -2272,6 +2360,7 @@ int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const
   // the sampling kernel's LDS layout holds the largest path in use; each planner reads its own
   const size_t B = S.B, N = S.N, D = S.D, P = largest_points(ps);
   hipStream_t st = nullptr;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
   ps->last_h2d = ps->last_d2h = 0;
   HIPCHK(hipMemcpyAsync(ps->d_start, start_ns, B * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ps->d_horizon, horizon_ns, B * 8, hipMemcpyHostToDevice, st));
@@ -2432,6 +2521,7 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
   if (count == 0) return 0;
   TPAMD_ON_DEVICE(ps->e);
   hipStream_t st = nullptr;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
   // the new P of every listed planner is bounded by its current P and W; P_cap grows first
   int need = 0, wmax = 0;
   for (int k = 0; k < count; k++) {
@@ -2501,6 +2591,149 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
   for (size_t k = 0; k < n; k++)
     if (status[k] == TPAMD_PLAN_OK) ps->h_np[id[k]] = num_points[k];
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- planner-set readouts
+extern "C" {
+
+int tpamd_planner_set_sample_at_ticks(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *start_ns,
+                                      int64_t step_ns, int num_ticks, double *q, double *qd, double *qdd,
+                                      int32_t *status) {
+  if (!sample_args_ok(ps, count, ids, /*host_ids=*/true, start_ns, step_ns, num_ticks, status))
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  const size_t n = count, T = num_ticks, D = ps->S.D, ticks = n * T;
+  if ((ticks + 255) / 256 > 0x7fffffff) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  // one copy up [start_ns][ids], one launch, one copy down per requested array
+  const size_t o_ids = align_up(n * 8, 256), in_bytes = o_ids + (ids ? n * 4 : 0);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+  const size_t o_st = take(ticks * 4), o_q = take(q ? ticks * D * 8 : 0), o_qd = take(qd ? ticks * D * 8 : 0),
+               o_qdd = take(qdd ? ticks * D * 8 : 0);
+  if (ensure_staging(&ps->rd_in, &ps->rd_in_bytes, in_bytes) || ensure_staging(&ps->rd_out, &ps->rd_out_bytes, off))
+    return TPAMD_E_HIP;
+  std::vector<char> in(in_bytes);
+  std::memcpy(in.data(), start_ns, n * 8);
+  if (ids) std::memcpy(in.data() + o_ids, ids, n * 4);
+  char *din = (char *)ps->rd_in, *dout = (char *)ps->rd_out;
+  HIPCHK(hipMemcpyAsync(din, in.data(), in_bytes, hipMemcpyHostToDevice, st));
+  ReadoutParams p = readout_params(ps);
+  p.count = count; p.num_ticks = num_ticks;
+  p.ids = ids ? (const int *)(din + o_ids) : nullptr;
+  p.start_ns = (const long long *)din; p.step_ns = step_ns;
+  p.status = (int *)(dout + o_st);
+  p.q = q ? (double *)(dout + o_q) : nullptr;
+  p.qd = qd ? (double *)(dout + o_qd) : nullptr;
+  p.qdd = qdd ? (double *)(dout + o_qdd) : nullptr;
+  hipLaunchKernelGGL(k_pset_sample_at_ticks, dim3((unsigned)((ticks + 255) / 256)), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  // the values come down whole; only the OK ticks reach the caller's arrays
+  std::vector<char> out(off);
+  HIPCHK(hipMemcpyAsync(status, dout + o_st, ticks * 4, hipMemcpyDeviceToHost, st));
+  for (size_t o : {q ? o_q : SIZE_MAX, qd ? o_qd : SIZE_MAX, qdd ? o_qdd : SIZE_MAX})
+    if (o != SIZE_MAX) HIPCHK(hipMemcpyAsync(out.data() + o, dout + o, ticks * D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const double *src[3] = {(const double *)(out.data() + o_q), (const double *)(out.data() + o_qd),
+                          (const double *)(out.data() + o_qdd)};
+  double *dst[3] = {q, qd, qdd};
+  for (int a = 0; a < 3; a++) {
+    if (!dst[a]) continue;
+    for (size_t i = 0; i < ticks; i++)
+      if (status[i] == TPAMD_PLAN_OK) std::memcpy(dst[a] + i * D, src[a] + i * D, D * 8);
+  }
+  return 0;
+}
+
+int tpamd_planner_set_sample_at_ticks_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                             const int64_t *start_ns, int64_t step_ns, int num_ticks, double *q,
+                                             double *qd, double *qdd, int32_t *status, void *hip_stream) {
+  if (!sample_args_ok(ps, count, ids, /*host_ids=*/false, start_ns, step_ns, num_ticks, status))
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  const size_t ticks = (size_t)count * num_ticks;
+  if ((ticks + 255) / 256 > 0x7fffffff) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  ReadoutParams p = readout_params(ps);
+  p.count = count; p.num_ticks = num_ticks; p.ids = ids;
+  p.start_ns = (const long long *)start_ns; p.step_ns = step_ns;
+  p.q = q; p.qd = qd; p.qdd = qdd; p.status = status;
+  hipLaunchKernelGGL(k_pset_sample_at_ticks, dim3((unsigned)((ticks + 255) / 256)), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+int tpamd_planner_set_download_trajectories(tpamd_planner_set *ps, int count, const int32_t *ids, int64_t *offsets,
+                                            int64_t capacity, double *time, double *s, double *sd, double *sdd,
+                                            double *q, double *qd, double *qdd) {
+  if (!pack_args_ok(ps, count, ids, /*host_ids=*/true, offsets, capacity)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) {
+    offsets[0] = 0;
+    return 0;
+  }
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const size_t n = count, D = ps->S.D;
+  // [offsets][ids] up (ids only), the scan, offsets down; then the pack and one copy per array
+  const size_t o_ids = align_up((n + 1) * 8, 256), in_bytes = o_ids + (ids ? n * 4 : 0);
+  if (ensure_staging(&ps->rd_in, &ps->rd_in_bytes, in_bytes)) return TPAMD_E_HIP;
+  char *din = (char *)ps->rd_in;
+  if (ids) HIPCHK(hipMemcpyAsync(din + o_ids, ids, n * 4, hipMemcpyHostToDevice, st));
+  ReadoutParams p = readout_params(ps);
+  p.count = count;
+  p.ids = ids ? (const int *)(din + o_ids) : nullptr;
+  p.offsets = (long long *)din;
+  hipLaunchKernelGGL(k_pset_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(offsets, din, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const size_t rows = (size_t)offsets[count];
+  if ((int64_t)rows > capacity) return TPAMD_E_INVALID_ARGUMENT;
+  double *dst1[4] = {time, s, sd, sdd}, *dstD[3] = {q, qd, qdd};
+  size_t off = 0, o1[4], oD[3];
+  for (int a = 0; a < 4; a++) { o1[a] = off; if (dst1[a]) off = align_up(off + rows * 8, 256); }
+  for (int a = 0; a < 3; a++) { oD[a] = off; if (dstD[a]) off = align_up(off + rows * D * 8, 256); }
+  if (rows == 0 || off == 0) return 0;
+  if (ensure_staging(&ps->rd_out, &ps->rd_out_bytes, off)) return TPAMD_E_HIP;
+  char *dout = (char *)ps->rd_out;
+  p.capacity = (long long)rows;
+  p.o_time = time ? (double *)(dout + o1[0]) : nullptr;
+  p.o_s = s ? (double *)(dout + o1[1]) : nullptr;
+  p.o_sd = sd ? (double *)(dout + o1[2]) : nullptr;
+  p.o_sdd = sdd ? (double *)(dout + o1[3]) : nullptr;
+  p.o_q = q ? (double *)(dout + oD[0]) : nullptr;
+  p.o_qd = qd ? (double *)(dout + oD[1]) : nullptr;
+  p.o_qdd = qdd ? (double *)(dout + oD[2]) : nullptr;
+  hipLaunchKernelGGL(k_pset_pack_trajectories, dim3((unsigned)n), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  for (int a = 0; a < 4; a++)
+    if (dst1[a]) HIPCHK(hipMemcpyAsync(dst1[a], dout + o1[a], rows * 8, hipMemcpyDeviceToHost, st));
+  for (int a = 0; a < 3; a++)
+    if (dstD[a]) HIPCHK(hipMemcpyAsync(dstD[a], dout + oD[a], rows * D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int tpamd_planner_set_download_trajectories_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                                   int64_t *offsets, int64_t capacity, double *time, double *s,
+                                                   double *sd, double *sdd, double *q, double *qd, double *qdd,
+                                                   void *hip_stream) {
+  if (!pack_args_ok(ps, count, ids, /*host_ids=*/false, offsets, capacity)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  ReadoutParams p = readout_params(ps);
+  p.count = count; p.ids = ids; p.offsets = (long long *)offsets; p.capacity = capacity;
+  p.o_time = time; p.o_s = s; p.o_sd = sd; p.o_sdd = sdd; p.o_q = q; p.o_qd = qd; p.o_qdd = qdd;
+  hipLaunchKernelGGL(k_pset_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, p);      // offsets[0] = 0 for none
+  if (count > 0) hipLaunchKernelGGL(k_pset_pack_trajectories, dim3((unsigned)count), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
 }
 
 }  // extern "C"

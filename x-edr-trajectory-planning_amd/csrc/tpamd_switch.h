@@ -27,11 +27,7 @@
 #include "tpamd_planner_set.h"   // pset_time_to_sec
 #endif
 
-#if defined(__HIPCC__) || defined(__HIP__)
-#define TPAMD_HD __host__ __device__
-#else
-#define TPAMD_HD
-#endif
+#include "tpamd_readout.h"     // TPAMD_HD, the trajectory bracket
 
 namespace tpamd {
 
@@ -312,28 +308,15 @@ TPAMD_HD inline int sw_switch_to_waypoint_path(double *knots, double *pts, int n
   return kSwOk;
 }
 
-// TrajectoryBuffer::GetVelocityAtTime (trajectory_buffer.cc:233-275): GetOffsetBracket by
-// upper_bound over time [n], then InterpolateLinear (restated as lerp a + t (b - a), as
-// lerp_ref in tpamd_kernels.h) between the bracket's velocities [n][D]; one sample: its velocity.
+// TrajectoryBuffer::GetVelocityAtTime (trajectory_buffer.cc:233-275): the bracket of tb_bracket
+// (upper_bound over time [n]), then InterpolateLinear (lerp a + t (b - a), as lerp_ref in
+// tpamd_kernels.h) between the bracket's velocities [n][D]; at the last sample: its velocity.
 TPAMD_HD inline int sw_velocity_at_time(const double *time, const double *vel, int n, int D, double time_sec,
                                         double *out) {
-  if (n <= 0) return kSwFailedPrecondition;      // "No samples."
-  if (time_sec < time[0] || time_sec > time[n - 1]) return kSwOutOfRange;
-  int lo = 0, hi = n;                            // upper_bound
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (time[mid] <= time_sec) lo = mid + 1; else hi = mid;
-  }
-  if (lo == n) {
-    for (int d = 0; d < D; d++) out[d] = vel[(size_t)(n - 1) * D + d];
-    return kSwOk;
-  }
-  const int l = lo - 1, u = lo;
-  const double at = (time_sec - time[l]) / (time[u] - time[l]);
-  for (int d = 0; d < D; d++) {
-    const double a = vel[(size_t)l * D + d], b = vel[(size_t)u * D + d];
-    out[d] = a + at * (b - a);
-  }
+  int l = 0, u = 0;
+  const int st = tb_bracket(time, n, time_sec, &l, &u);   // "No samples." / out of range
+  if (st != kRdOk) return st;
+  tb_interpolate(vel, l, u, D, tb_fraction(time, l, u, time_sec), out);
   return kSwOk;
 }
 

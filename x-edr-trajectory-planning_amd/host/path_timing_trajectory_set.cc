@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <limits>
 
 namespace trajectory_planning {
 
@@ -255,6 +256,83 @@ Status PathTimingTrajectorySet::GetTrajectory(size_t planner, PlannedTrajectory 
       out->second_path_parameter_derivative.data(), out->positions.data(), out->velocities.data(),
       out->accelerations.data());
   return rc == 0 ? OkStatus() : InternalError(tpamd_error_string(rc));
+}
+
+Status PathTimingTrajectorySet::GetTrajectories(const std::vector<size_t> &planners,
+                                                std::vector<PlannedTrajectory> *out) const {
+  if (!init_status_.ok()) return init_status_;
+  if (!out) return InvalidArgumentError("no output");
+  const size_t n = planners.size(), D = options_.GetNumDofs();
+  std::vector<int32_t> ids(n);
+  size_t rows = 0;      // the summaries' sample counts: the packed size, unless the set changed since
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_) return InvalidArgumentError("no such planner");
+    ids[k] = (int32_t)planners[k];
+    rows += (size_t)summary_[planners[k]].num_samples;
+  }
+  std::vector<int64_t> offsets(n + 1);
+  std::vector<double> t, s, sd, sdd, q, qd, qdd;
+  for (int attempt = 0;; attempt++) {
+    const size_t r = std::max<size_t>(rows, 1);
+    t.resize(r); s.resize(r); sd.resize(r); sdd.resize(r); q.resize(r * D); qd.resize(r * D); qdd.resize(r * D);
+    const int rc = tpamd_planner_set_download_trajectories(set_, (int)n, ids.data(), offsets.data(), (int64_t)rows,
+                                                           t.data(), s.data(), sd.data(), sdd.data(), q.data(),
+                                                           qd.data(), qdd.data());
+    if (rc == 0) break;
+    if (rc != TPAMD_E_INVALID_ARGUMENT || attempt > 0 || (size_t)offsets[n] <= rows)
+      return InternalError(tpamd_error_string(rc));
+    rows = (size_t)offsets[n];           // grow to the total and go again
+  }
+  out->assign(n, PlannedTrajectory());
+  for (size_t k = 0; k < n; k++) {
+    const size_t a = (size_t)offsets[k], b = (size_t)offsets[k + 1];
+    PlannedTrajectory &o = (*out)[k];
+    o.time.assign(t.begin() + a, t.begin() + b);
+    o.path_parameter.assign(s.begin() + a, s.begin() + b);
+    o.path_parameter_derivative.assign(sd.begin() + a, sd.begin() + b);
+    o.second_path_parameter_derivative.assign(sdd.begin() + a, sdd.begin() + b);
+    o.positions.assign(q.begin() + a * D, q.begin() + b * D);
+    o.velocities.assign(qd.begin() + a * D, qd.begin() + b * D);
+    o.accelerations.assign(qdd.begin() + a * D, qdd.begin() + b * D);
+  }
+  return OkStatus();
+}
+
+Status PathTimingTrajectorySet::GetSetpoints(const std::vector<size_t> &planners, const std::vector<Time> &start,
+                                             Duration step, int ticks, TrajectorySetpoints *out) const {
+  if (!init_status_.ok()) return init_status_;
+  if (!out || start.size() != planners.size()) return InvalidArgumentError("one start time per planner");
+  if (step.nanos() <= 0 || ticks < 1) return InvalidArgumentError("step and ticks must be positive");
+  const size_t n = planners.size(), D = options_.GetNumDofs(), T = (size_t)ticks;
+  std::vector<int32_t> ids(n);
+  std::vector<int64_t> s(n);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_) return InvalidArgumentError("no such planner");
+    ids[k] = (int32_t)planners[k];
+    s[k] = ::tpamd::compat::ToUnixNanos(start[k]);
+  }
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  out->num_planners = n; out->num_ticks = T; out->num_dofs = D;
+  out->positions.assign(n * T * D, nan);
+  out->velocities.assign(n * T * D, nan);
+  out->accelerations.assign(n * T * D, nan);
+  out->status.assign(n * T, OkStatus());
+  if (n == 0) return OkStatus();
+  std::vector<int32_t> st(n * T);
+  const int rc = tpamd_planner_set_sample_at_ticks(set_, (int)n, ids.data(), s.data(), step.nanos(), ticks,
+                                                   out->positions.data(), out->velocities.data(),
+                                                   out->accelerations.data(), st.data());
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  for (size_t i = 0; i < n * T; i++) {
+    switch (st[i]) {
+      case TPAMD_PLAN_OK: break;
+      case TPAMD_PLAN_FAILED_PRECONDITION: out->status[i] = FailedPreconditionError("No samples."); break;
+      case TPAMD_PLAN_OUT_OF_RANGE: out->status[i] = OutOfRangeError("Time outside the trajectory"); break;
+      case TPAMD_PLAN_INVALID_ARGUMENT: out->status[i] = InvalidArgumentError("no such planner"); break;
+      default: out->status[i] = InternalError("setpoint query failed"); break;
+    }
+  }
+  return OkStatus();
 }
 
 size_t PathTimingTrajectorySet::LastPlanBytesOverPcie() const {

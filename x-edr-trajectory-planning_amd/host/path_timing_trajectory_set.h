@@ -11,7 +11,8 @@
 // resulting spline and its state. The online switch to new waypoints runs on the device
 // (SwitchToWaypointPaths): stop parameter, velocity at the switch time and the spline edit, with
 // no trajectory download. Splines of different sizes share a set. Trajectories come down only when
-// asked for (GetTrajectory).
+// asked for: one planner (GetTrajectory), several in one packed download (GetTrajectories), or only
+// the setpoints at control ticks (GetSetpoints).
 #ifndef TPAMD_HOST_PATH_TIMING_TRAJECTORY_SET_H_
 #define TPAMD_HOST_PATH_TIMING_TRAJECTORY_SET_H_
 
@@ -28,6 +29,15 @@ namespace trajectory_planning {
 struct PlannedTrajectory {
   std::vector<double> time, path_parameter, path_parameter_derivative, second_path_parameter_derivative;
   std::vector<double> positions, velocities, accelerations;   // [samples][dofs], packed
+};
+
+// Setpoints of several planners at a grid of control ticks (GetSetpoints): positions, velocities
+// and accelerations [planners][ticks][dofs], packed, and one status per (planner, tick). The
+// values of a tick whose status is not ok are NaN.
+struct TrajectorySetpoints {
+  size_t num_planners = 0, num_ticks = 0, num_dofs = 0;
+  std::vector<double> positions, velocities, accelerations;
+  std::vector<Status> status;
 };
 
 class PathTimingTrajectorySet {
@@ -86,6 +96,15 @@ class PathTimingTrajectorySet {
   size_t NumControlPoints(size_t planner) const;
   // The planner's trajectory (GetTime, GetPositions, ...): one download of its samples.
   Status GetTrajectory(size_t planner, PlannedTrajectory *out) const;
+  // GetTrajectory for each listed planner (repeats allowed) in one call: one packed download
+  // (tpamd_planner_set_download_trajectories). out->at(k) is planner planners[k]'s trajectory.
+  Status GetTrajectories(const std::vector<size_t> &planners, std::vector<PlannedTrajectory> *out) const;
+  // TrajectoryBuffer::Get{Position,Velocity,Acceleration}AtTime(start[k] + j step) of each listed
+  // planner k for ticks j < ticks, on the device (tpamd_planner_set_sample_at_ticks): the same
+  // values and statuses as the per-planner getters. A planner out of range, step <= 0 or ticks < 1
+  // fails the call.
+  Status GetSetpoints(const std::vector<size_t> &planners, const std::vector<Time> &start, Duration step, int ticks,
+                      TrajectorySetpoints *out) const;
   // Bytes the last Plan call moved over PCIe, both directions.
   size_t LastPlanBytesOverPcie() const;
   size_t DeviceBytes() const;

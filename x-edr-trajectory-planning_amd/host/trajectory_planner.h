@@ -50,21 +50,14 @@ class TrajectoryPlanner {
   const std::vector<double> &GetSecondPathParameterDerivatives() const {
     return second_path_parameter_derivative_;
   }
-  // TrajectoryBuffer::GetVelocityAtTime (trajectory_buffer.cc:233-275): the bracket of `time`
-  // by upper_bound over GetTime(), then InterpolateLinear (a + t (b - a) with t the time fraction)
-  // between its velocities; a time on the last sample gives that sample's velocity.
-  ::tpamd::compat::StatusOr<VectorXd> GetVelocityAtTime(Time time) const {
-    if (time_.empty()) return ::tpamd::compat::FailedPreconditionError("No samples.");
-    const double time_sec = (double)::tpamd::compat::ToUnixNanos(time) / 1e9;
-    if (time_sec < time_.front() || time_sec > time_.back())
-      return ::tpamd::compat::OutOfRangeError("Time outside the trajectory");
-    const auto upper = std::upper_bound(time_.begin(), time_.end(), time_sec);
-    if (upper == time_.end()) return velocities_.back();
-    const size_t u = upper - time_.begin(), l = u - 1;
-    const double t = (time_sec - time_[l]) / (time_[u] - time_[l]);
-    VectorXd v(velocities_[l].size());
-    for (size_t d = 0; d < v.size(); d++) v[d] = velocities_[l][d] + t * (velocities_[u][d] - velocities_[l][d]);
-    return v;
+  // TrajectoryBuffer::Get{Position,Velocity,Acceleration}AtTime (trajectory_buffer.cc:228-294):
+  // the bracket of `time` by upper_bound over GetTime(), then InterpolateLinear (a + t (b - a)
+  // with t the time fraction) between its rows; a time on the last sample gives that sample.
+  // FailedPrecondition without samples, OutOfRange outside [first, last] time stamp.
+  ::tpamd::compat::StatusOr<VectorXd> GetPositionAtTime(Time time) const { return ValueAtTime(positions_, time); }
+  ::tpamd::compat::StatusOr<VectorXd> GetVelocityAtTime(Time time) const { return ValueAtTime(velocities_, time); }
+  ::tpamd::compat::StatusOr<VectorXd> GetAccelerationAtTime(Time time) const {
+    return ValueAtTime(accelerations_, time);
   }
   virtual bool IsTrajectoryAtEnd() const {
     const bool path_unchanged = path_ == nullptr ||
@@ -96,6 +89,22 @@ class TrajectoryPlanner {
       second_path_parameter_derivative_;
   std::vector<VectorXd> positions_, velocities_, accelerations_;
   bool target_reached_ = false;
+
+ private:
+  // GetOffsetBracket (:233-251) and InterpolateLinear on one of the sample arrays
+  ::tpamd::compat::StatusOr<VectorXd> ValueAtTime(const std::vector<VectorXd> &values, Time time) const {
+    if (time_.empty()) return ::tpamd::compat::FailedPreconditionError("No samples.");
+    const double time_sec = (double)::tpamd::compat::ToUnixNanos(time) / 1e9;
+    if (time_sec < time_.front() || time_sec > time_.back())
+      return ::tpamd::compat::OutOfRangeError("Time outside the trajectory");
+    const auto upper = std::upper_bound(time_.begin(), time_.end(), time_sec);
+    if (upper == time_.end()) return values.back();
+    const size_t u = upper - time_.begin(), l = u - 1;
+    const double t = (time_sec - time_[l]) / (time_[u] - time_[l]);
+    VectorXd v(values[l].size());
+    for (size_t d = 0; d < v.size(); d++) v[d] = values[l][d] + t * (values[u][d] - values[l][d]);
+    return v;
+  }
 };
 
 }  // namespace trajectory_planning
