@@ -1803,6 +1803,13 @@ int tpamd_fastest_stop_host(tpamd_engine *e, const tpamd_fastest_stop_args *a) {
     if (d_cnt) HIPCHK(hipMemcpyAsync(d_cnt, a->count, B * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_am, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_q, a->query_time, B * 8, hipMemcpyHostToDevice, st));
+    if (prof) {
+      // the kernel writes a prefix of each profile row; the rest must come back as the caller
+      // had it (as with the device entry), not as an earlier host call left the staging buffer
+      HIPCHK(hipMemcpyAsync(o_pt, a->profile_time, B * M * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(o_pr, a->profile_rate2, B * M * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(o_pd, a->profile_drate2, B * M * 8, hipMemcpyHostToDevice, st));
+    }
     tpamd_fastest_stop_args da = *a;
     da.time = d_t; da.s = d_s; da.qd = d_qd; da.qdd = d_qdd; da.count = d_cnt;
     da.max_acceleration = d_am; da.query_time = d_q;
