@@ -287,6 +287,7 @@ int tpamd_sample_pose_splines_host(tpamd_engine *engine, int num_paths, int num_
 #define TPAMD_PLAN_INVALID_ARGUMENT 3    /* non-positive duration (:313-317), start velocity (:387-392) */
 #define TPAMD_PLAN_INTERNAL 4            /* solver set-up / optimisation failed (:394-417) */
 #define TPAMD_PLAN_DEADLINE_EXCEEDED 5   /* planning-loop limit (:655-658) */
+#define TPAMD_PLAN_NOT_FOUND 6           /* stopping trajectories: no safe stop (trajectory_buffer.cc:333-349) */
 #define TPAMD_PLAN_MORE 100              /* history_capacity exhausted: call again with more room */
 
 typedef struct tpamd_plan_args {
@@ -486,6 +487,34 @@ int tpamd_planner_set_download_trajectories_device(tpamd_planner_set *set, int c
                                                    int64_t capacity, double *time, double *s,
                                                    double *sd, double *sdd, double *q, double *qd,
                                                    double *qdd, void *hip_stream);
+/* TrajectoryBuffer::StopBeforeTime(TimeToSec(time_ns[k]), max_acceleration[k], time_step)
+ * (trajectory_buffer.cc:296-385, as tpamd_stop_trajectories_*) on the resident trajectory of each
+ * listed planner (ids[count], repeats allowed, or planners 0..count-1 if ids is NULL), as if it
+ * were loaded into a TrajectoryBuffer (default timestep_tolerance 1e-6): status[k] TPAMD_PLAN_*,
+ * keep[k] (samples of the trajectory kept before the segment) and the segment, packed: planner k's
+ * rows fill offsets[k] .. offsets[k+1) of time [rows] and q / qd / qdd [rows][D] (any may be NULL).
+ * The stopped trajectory is the planner's first keep[k] samples followed by those rows. A planner
+ * without samples gives TPAMD_PLAN_OK, keep 0 and no rows; a stop that fails gives keep = its
+ * sample count and no rows. max_acceleration [count][D]. offsets [count + 1], status and keep are
+ * always written; if offsets[count] > capacity no row is written and this host variant returns
+ * TPAMD_E_INVALID_ARGUMENT (grow to offsets[count] and call again). Call-level errors (NULL set /
+ * time_ns / max_acceleration / status / keep / offsets, count < 0, count > B with a NULL ids,
+ * capacity < 0, an id out of range) change nothing. No planner state changes: the next Plan is
+ * the one it would have been without this call. Host pointers; synchronises. */
+int tpamd_planner_set_stop_trajectories(tpamd_planner_set *set, int count, const int32_t *ids,
+                                        const int64_t *time_ns, const double *max_acceleration,
+                                        double time_step, int32_t *status, int32_t *keep,
+                                        int64_t *offsets, int64_t capacity, double *time, double *q,
+                                        double *qd, double *qdd);
+/* The same with every array a device pointer; enqueues on hip_stream and does not synchronise.
+ * An id out of range gives TPAMD_PLAN_INVALID_ARGUMENT, keep 0 and no rows. If offsets[count] >
+ * capacity the rows stay unwritten. Stream ordering as for the _device readouts
+ * (tpamd_planner_set_download_trajectories_device). */
+int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                               const int64_t *time_ns, const double *max_acceleration,
+                                               double time_step, int32_t *status, int32_t *keep,
+                                               int64_t *offsets, int64_t capacity, double *time,
+                                               double *q, double *qd, double *qdd, void *hip_stream);
 /* Bytes the last tpamd_planner_set_plan call moved over PCIe (host to device, device to host). */
 void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *set, size_t *host_to_device,
                                        size_t *device_to_host);
@@ -620,6 +649,48 @@ int tpamd_fastest_stop_device(tpamd_engine *engine, const tpamd_fastest_stop_arg
                               void *hip_stream);
 /* Same with HOST pointers in args (copies in, runs, copies out, synchronises). */
 int tpamd_fastest_stop_host(tpamd_engine *engine, const tpamd_fastest_stop_args *args);
+
+/* ------------------------------------------------------------------------
+ * Stopping trajectories: TrajectoryBuffer::StopBeforeTime / StopAtIndex (trajectory_buffer.cc:
+ * 296-385) with RescaleTrajectoryBackwardToStop (rescale_to_stop.cc) for B sampled trajectories:
+ * row b (time [stride], qd / qdd [stride][D], count[b] samples) is cut after sample index and the
+ * samples up to it are time-scaled so that the robot comes to rest at q[index] along the same
+ * positions within max_acceleration[b]. index = min(lower_bound(stop_time[b]) + 1, count - 1)
+ * (StopBeforeTime), or stop_index[b] if stop_index is not NULL (StopAtIndex).
+ * Per row: status[b] TPAMD_PLAN_* -- OUT_OF_RANGE (index outside [1, count - 1], a stop time
+ * before the first sample), INVALID_ARGUMENT (max_acceleration <= 0, time_step <= 0, times not
+ * strictly increasing up to index), NOT_FOUND (the stop needs every sample and still misses the
+ * velocity there by more than 1e-2), INTERNAL (sample index < count - 1 already at rest: the
+ * reference aborts there), OK; keep[b], the samples of the row kept before the segment; first[b],
+ * last[b], the segment's rows within the row. out_time [B][stride] and out_qd / out_qdd
+ * [B][stride][D] are written at rows [first, last] only; the segment's positions are the input's
+ * q[first .. last], unchanged. The trajectory after the stop is input[0, keep) ++ segment. No
+ * samples: OK, keep 0 and an empty segment (first 0, last -1); a failed stop: keep = count and an
+ * empty segment (first = count, last = count - 1). On the last sample with |v| < 1e-4 the segment
+ * is that sample with zero velocity and acceleration. time_step is checked, not used (as in the
+ * reference). count [B] may be NULL (stride samples each); counts are clamped to [0, stride].
+ * Bit-identical to the mirror's TrajectoryBuffer (host/trajectory_buffer.cc). Non-finite inputs
+ * are outside the contract. Device pointers.
+ * ------------------------------------------------------------------------ */
+typedef struct tpamd_stop_trajectory_args {
+  int32_t num_paths, stride, num_dofs; /* num_dofs 1..16 */
+  int32_t reserved;
+  const double *time;                  /* [B][stride] */
+  const double *qd, *qdd;              /* [B][stride][D] */
+  const int32_t *count;                /* [B] samples per row; NULL: stride */
+  const double *max_acceleration;      /* [B][D] */
+  double time_step;
+  const double *stop_time;             /* [B] seconds (StopBeforeTime) */
+  const int32_t *stop_index;           /* [B] (StopAtIndex); not NULL: used instead of stop_time */
+  int32_t *status, *keep, *first, *last; /* [B] */
+  double *out_time;                    /* [B][stride] */
+  double *out_qd, *out_qdd;            /* [B][stride][D] */
+} tpamd_stop_trajectory_args;
+
+int tpamd_stop_trajectories_device(tpamd_engine *engine, const tpamd_stop_trajectory_args *args,
+                                   void *hip_stream);
+/* Same with HOST pointers in args (copies in, runs, copies out, synchronises). */
+int tpamd_stop_trajectories_host(tpamd_engine *engine, const tpamd_stop_trajectory_args *args);
 
 /* GetPathStopParameter(time) for `count` planners of a set (ids[count], or planners
  * 0..count-1 if ids is NULL) on their resident trajectories after the last Plan: time_ns [count]

@@ -16,6 +16,7 @@
 #include "tpamd_launch.h"
 #include "tpamd_planner_set.h"
 #include "tpamd_readout.h"
+#include "tpamd_rescale.h"
 #include "tpamd_stop.h"
 #include "tpamd_switch.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
@@ -1898,6 +1899,83 @@ int tpamd_profile_num_kernels(void) { return KI_COUNT; }
 
 }  // extern "C"
 
+static bool stop_batch_args_ok(const tpamd_stop_trajectory_args *a) {
+  if (a->stride < 1 || a->num_dofs < 1 || a->num_dofs > 16) return false;
+  return a->time && a->qd && a->qdd && a->max_acceleration && (a->stop_time || a->stop_index) && a->status &&
+         a->keep && a->first && a->last && a->out_time && a->out_qd && a->out_qdd;
+}
+
+int tpamd_stop_trajectories_device(tpamd_engine *e, const tpamd_stop_trajectory_args *a, void *hip_stream) {
+  if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
+  if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (!stop_batch_args_ok(a)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  StopTrajParams p{};
+  p.Q = p.B = a->num_paths; p.stride = a->stride; p.mode = kRsBatch;
+  p.time = a->time; p.qd = a->qd; p.qdd = a->qdd; p.count = a->count;
+  p.amax = a->max_acceleration; p.time_step = a->time_step;
+  p.stop_sec = a->stop_time; p.stop_index = a->stop_index;
+  p.status = a->status; p.keep = a->keep; p.seg_first = a->first; p.seg_last = a->last;
+  p.o_time = a->out_time; p.o_qd = a->out_qd; p.o_qdd = a->out_qdd;
+  if (!launch_stop_trajectories(a->num_dofs, p, (hipStream_t)hip_stream)) return TPAMD_E_INVALID_ARGUMENT;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_stop_trajectories_host(tpamd_engine *e, const tpamd_stop_trajectory_args *a) {
+  if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
+  if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (!stop_batch_args_ok(a)) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = a->num_paths, M = a->stride, D = a->num_dofs;
+  TPAMD_ON_DEVICE(e);
+  for (int pass = 0; pass < 2; pass++) {
+    Stage s(pass ? e->stage_base : nullptr);
+    double *d_t = s.take<double>(B * M), *d_qd = s.take<double>(B * M * D), *d_qdd = s.take<double>(B * M * D);
+    int32_t *d_cnt = a->count ? s.take<int32_t>(B) : nullptr;
+    double *d_am = s.take<double>(B * D);
+    double *d_st = a->stop_index ? nullptr : s.take<double>(B);
+    int32_t *d_si = a->stop_index ? s.take<int32_t>(B) : nullptr;
+    int32_t *o_res = s.take<int32_t>(4 * B);
+    double *o_t = s.take<double>(B * M), *o_qd = s.take<double>(B * M * D), *o_qdd = s.take<double>(B * M * D);
+    if (!pass) {
+      int rc = ensure_stage(e, s.off);
+      if (rc) return rc;
+      continue;
+    }
+    hipStream_t st = nullptr;
+    HIPCHK(hipMemcpyAsync(d_t, a->time, B * M * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qd, a->qd, B * M * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qdd, a->qdd, B * M * D * 8, hipMemcpyHostToDevice, st));
+    if (d_cnt) HIPCHK(hipMemcpyAsync(d_cnt, a->count, B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_am, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
+    if (d_st) HIPCHK(hipMemcpyAsync(d_st, a->stop_time, B * 8, hipMemcpyHostToDevice, st));
+    if (d_si) HIPCHK(hipMemcpyAsync(d_si, a->stop_index, B * 4, hipMemcpyHostToDevice, st));
+    // only the segments' rows are written; the rest must come back as the caller had it
+    HIPCHK(hipMemcpyAsync(o_t, a->out_time, B * M * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o_qd, a->out_qd, B * M * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o_qdd, a->out_qdd, B * M * D * 8, hipMemcpyHostToDevice, st));
+    tpamd_stop_trajectory_args da = *a;
+    da.time = d_t; da.qd = d_qd; da.qdd = d_qdd; da.count = d_cnt; da.max_acceleration = d_am;
+    da.stop_time = d_st; da.stop_index = d_si;
+    da.status = o_res; da.keep = o_res + B; da.first = o_res + 2 * B; da.last = o_res + 3 * B;
+    da.out_time = o_t; da.out_qd = o_qd; da.out_qdd = o_qdd;
+    int rc = tpamd_stop_trajectories_device(e, &da, st);
+    if (rc) return rc;
+    std::vector<int32_t> res(4 * B);
+    HIPCHK(hipMemcpyAsync(res.data(), o_res, 16 * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a->out_time, o_t, B * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a->out_qd, o_qd, B * M * D * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a->out_qdd, o_qdd, B * M * D * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(a->status, res.data(), 4 * B);
+    std::memcpy(a->keep, res.data() + B, 4 * B);
+    std::memcpy(a->first, res.data() + 2 * B, 4 * B);
+    std::memcpy(a->last, res.data() + 3 * B, 4 * B);
+  }
+  return 0;
+}
+
+
 // ---------------------------------------------------------------- planner sets
 struct tpamd_planner_set {
   tpamd_engine *e = nullptr;
@@ -1931,6 +2009,10 @@ struct tpamd_planner_set {
   // ev_read (recorded after each of them) orders the next change after them
   hipEvent_t ev_set = nullptr, ev_read = nullptr;
   bool read_pending = false;
+  // stopping trajectories: per-listed-planner scratch (segment rows, shift, length; host variant:
+  // status, keep, offsets as well)
+  void *stop_buf = nullptr;
+  size_t stop_bytes = 0;
 };
 
 namespace {
@@ -2115,6 +2197,30 @@ bool pack_args_ok(const tpamd_planner_set *ps, int count, const int32_t *ids, bo
   return true;
 }
 
+bool stop_args_ok(const tpamd_planner_set *ps, int count, const int32_t *ids, bool host_ids, const int64_t *time_ns,
+                  const double *amax, const int32_t *status, const int32_t *keep, const int64_t *offsets,
+                  int64_t capacity) {
+  if (!time_ns || !amax || !status || !keep) return false;
+  return pack_args_ok(ps, count, ids, host_ids, offsets, capacity);
+}
+
+// Grow the stop scratch; a device stop still in flight may be using the old one.
+int ensure_stop_buf(tpamd_planner_set *ps, size_t bytes) {
+  if (bytes <= ps->stop_bytes) return 0;
+  if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
+  return ensure_staging(&ps->stop_buf, &ps->stop_bytes, bytes);
+}
+
+// StopTrajParams view of the set's resident trajectories
+StopTrajParams stop_params(const tpamd_planner_set *ps) {
+  const PlannerSetState &S = ps->S;
+  StopTrajParams p{};
+  p.B = S.B; p.stride = ps->tcap;
+  p.time = S.t_time; p.q = S.t_q; p.qd = S.t_qd; p.qdd = S.t_qdd;
+  p.count = S.t_count; p.first = S.t_first;
+  return p;
+}
+
 // tpamd_planner_set_upload_paths(_ragged): num_points null = every path has the config's P
 int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *num_points,
                         const double *knots, const double *cps, const double *vmax, const double *amax,
@@ -2285,6 +2391,7 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (ps->ev_read) (void)hipEventDestroy(ps->ev_read);
   if (ps->rd_in) (void)hipFree(ps->rd_in);
   if (ps->rd_out) (void)hipFree(ps->rd_out);
+  if (ps->stop_buf) (void)hipFree(ps->stop_buf);
   if (ps->fixed) (void)hipFree(ps->fixed);
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
@@ -2295,7 +2402,7 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
   return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_bytes + ps->rd_in_bytes +
-                   ps->rd_out_bytes
+                   ps->rd_out_bytes + ps->stop_bytes
             : 0;
 }
 
@@ -2739,6 +2846,112 @@ int tpamd_planner_set_download_trajectories_device(tpamd_planner_set *ps, int co
   p.o_time = time; p.o_s = s; p.o_sd = sd; p.o_sdd = sdd; p.o_q = q; p.o_qd = qd; p.o_qdd = qdd;
   hipLaunchKernelGGL(k_pset_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, p);      // offsets[0] = 0 for none
   if (count > 0) hipLaunchKernelGGL(k_pset_pack_trajectories, dim3((unsigned)count), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+// Stopping trajectories: the find pass (status, keep, segment rows and shift per listed planner),
+// the scan of the segment lengths into offsets, the write pass (rows at offsets[k], if they fit).
+int tpamd_planner_set_stop_trajectories(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                                        const double *max_acceleration, double time_step, int32_t *status,
+                                        int32_t *keep, int64_t *offsets, int64_t capacity, double *time, double *q,
+                                        double *qd, double *qdd) {
+  if (!stop_args_ok(ps, count, ids, /*host_ids=*/true, time_ns, max_acceleration, status, keep, offsets, capacity))
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) {
+    offsets[0] = 0;
+    return 0;
+  }
+  if (ps->S.D > 16) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const size_t n = count, D = ps->S.D;
+  // up: [time_ns][max_acceleration][ids]; scratch: [first][last][status][keep][shift][length][offsets]
+  const size_t o_am = align_up(n * 8, 256), o_ids = align_up(o_am + n * D * 8, 256),
+               in_bytes = o_ids + (ids ? n * 4 : 0);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+  const size_t o_fi = take(n * 4), o_la = take(n * 4), o_st = take(n * 4), o_kp = take(n * 4), o_sh = take(n * 8),
+               o_len = take(n * 8), o_off = take((n + 1) * 8);
+  if (ensure_stop_buf(ps, off) || ensure_staging(&ps->rd_in, &ps->rd_in_bytes, in_bytes)) return TPAMD_E_HIP;
+  // a device stop in flight on another stream may still use the scratch
+  if (ps->read_pending) HIPCHK(hipStreamWaitEvent(st, ps->ev_read, 0));
+  std::vector<char> in(in_bytes);
+  std::memcpy(in.data(), time_ns, n * 8);
+  std::memcpy(in.data() + o_am, max_acceleration, n * D * 8);
+  if (ids) std::memcpy(in.data() + o_ids, ids, n * 4);
+  char *din = (char *)ps->rd_in, *sb = (char *)ps->stop_buf;
+  HIPCHK(hipMemcpyAsync(din, in.data(), in_bytes, hipMemcpyHostToDevice, st));
+  StopTrajParams p = stop_params(ps);
+  p.Q = count; p.mode = kRsSetFind;
+  p.ids = ids ? (const int *)(din + o_ids) : nullptr;
+  p.stop_ns = (const long long *)din; p.amax = (const double *)(din + o_am); p.time_step = time_step;
+  p.seg_first = (int *)(sb + o_fi); p.seg_last = (int *)(sb + o_la); p.status = (int *)(sb + o_st);
+  p.keep = (int *)(sb + o_kp); p.seg_offset = (double *)(sb + o_sh); p.seg_len = (long long *)(sb + o_len);
+  if (!launch_stop_trajectories((int)D, p, st)) return TPAMD_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k_stop_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, count, p.seg_len,
+                     (long long *)(sb + o_off));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(status, sb + o_st, n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(keep, sb + o_kp, n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(offsets, sb + o_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const size_t rows = (size_t)offsets[count];
+  if ((int64_t)rows > capacity) return TPAMD_E_INVALID_ARGUMENT;
+  double *dst[4] = {time, q, qd, qdd};
+  const size_t width[4] = {1, D, D, D};
+  size_t o_out[4], out_bytes = 0;
+  for (int a = 0; a < 4; a++) {
+    o_out[a] = out_bytes;
+    if (dst[a]) out_bytes = align_up(out_bytes + rows * width[a] * 8, 256);
+  }
+  if (rows == 0 || out_bytes == 0) return 0;
+  if (ensure_staging(&ps->rd_out, &ps->rd_out_bytes, out_bytes)) return TPAMD_E_HIP;
+  char *dout = (char *)ps->rd_out;
+  p.mode = kRsSetWrite;
+  p.offsets = (const long long *)(sb + o_off); p.capacity = (long long)rows;
+  p.o_time = time ? (double *)(dout + o_out[0]) : nullptr;
+  p.o_q = q ? (double *)(dout + o_out[1]) : nullptr;
+  p.o_qd = qd ? (double *)(dout + o_out[2]) : nullptr;
+  p.o_qdd = qdd ? (double *)(dout + o_out[3]) : nullptr;
+  launch_stop_trajectories((int)D, p, st);
+  HIPCHK(hipGetLastError());
+  for (int a = 0; a < 4; a++)
+    if (dst[a]) HIPCHK(hipMemcpyAsync(dst[a], dout + o_out[a], rows * width[a] * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                               const int64_t *time_ns, const double *max_acceleration,
+                                               double time_step, int32_t *status, int32_t *keep, int64_t *offsets,
+                                               int64_t capacity, double *time, double *q, double *qd, double *qdd,
+                                               void *hip_stream) {
+  if (!stop_args_ok(ps, count, ids, /*host_ids=*/false, time_ns, max_acceleration, status, keep, offsets, capacity))
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (ps->S.D > 16) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t n = count;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+  const size_t o_fi = take(n * 4), o_la = take(n * 4), o_sh = take(n * 8), o_len = take(n * 8);
+  if (off > 0 && ensure_stop_buf(ps, off)) return TPAMD_E_HIP;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  char *sb = (char *)ps->stop_buf;
+  StopTrajParams p = stop_params(ps);
+  p.Q = count; p.mode = kRsSetFind;
+  p.ids = ids; p.stop_ns = (const long long *)time_ns; p.amax = max_acceleration; p.time_step = time_step;
+  p.status = status; p.keep = keep;
+  p.seg_first = (int *)(sb + o_fi); p.seg_last = (int *)(sb + o_la);
+  p.seg_offset = (double *)(sb + o_sh); p.seg_len = (long long *)(sb + o_len);
+  launch_stop_trajectories(ps->S.D, p, st);
+  hipLaunchKernelGGL(k_stop_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, count, p.seg_len,
+                     (long long *)offsets);                                               // offsets[0] = 0 for none
+  p.mode = kRsSetWrite;
+  p.offsets = (const long long *)offsets; p.capacity = capacity;
+  p.o_time = time; p.o_q = q; p.o_qd = qd; p.o_qdd = qdd;
+  launch_stop_trajectories(ps->S.D, p, st);
   HIPCHK(hipGetLastError());
   return readout_end(ps, st) ? TPAMD_E_HIP : 0;
 }

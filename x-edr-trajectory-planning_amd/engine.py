@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
-            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h"]
+            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
+            "tpamd_rescale.h"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -194,6 +195,8 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_download_path", "tpamd_planner_set_switch_paths", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
     "tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
     "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device",
+    "tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
+    "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
     "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
     "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
     "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_kernel_vgprs",
@@ -297,6 +300,14 @@ def load_library():
     L.tpamd_planner_set_sample_at_ticks_device.argtypes = [vp, i, vp, vp, i64, i] + [vp] * 4 + [vp]
     L.tpamd_planner_set_download_trajectories.argtypes = [vp, i, vp, vp, i64] + [vp] * 7
     L.tpamd_planner_set_download_trajectories_device.argtypes = [vp, i, vp, vp, i64] + [vp] * 7 + [vp]
+    for name in ("tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
+                 "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_stop_trajectories.argtypes = [vp, i, vp, vp, vp, C.c_double, vp, vp, vp, i64] + [vp] * 4
+    L.tpamd_planner_set_stop_trajectories_device.argtypes = (
+        [vp, i, vp, vp, vp, C.c_double, vp, vp, vp, i64] + [vp] * 4 + [vp])
+    L.tpamd_stop_trajectories_device.argtypes = [vp, vp, vp]
+    L.tpamd_stop_trajectories_host.argtypes = [vp, vp]
     L.tpamd_debug_copy_boundary.restype = i
     L.tpamd_debug_copy_boundary.argtypes = [vp, i, i] + [vp] * 6
     L.tpamd_debug_keep_boundary.argtypes = [vp, i]

@@ -10,6 +10,7 @@ using ::tpamd::compat::DeadlineExceededError;
 using ::tpamd::compat::FailedPreconditionError;
 using ::tpamd::compat::InternalError;
 using ::tpamd::compat::InvalidArgumentError;
+using ::tpamd::compat::NotFoundError;
 using ::tpamd::compat::OkStatus;
 using ::tpamd::compat::OutOfRangeError;
 using ::tpamd::compat::StatusOr;
@@ -331,6 +332,63 @@ Status PathTimingTrajectorySet::GetSetpoints(const std::vector<size_t> &planners
       case TPAMD_PLAN_INVALID_ARGUMENT: out->status[i] = InvalidArgumentError("no such planner"); break;
       default: out->status[i] = InternalError("setpoint query failed"); break;
     }
+  }
+  return OkStatus();
+}
+
+Status PathTimingTrajectorySet::StopTrajectoriesBeforeTime(const std::vector<size_t> &planners,
+                                                           const std::vector<Time> &time,
+                                                           const std::vector<VectorXd> &max_acceleration,
+                                                           double time_step, std::vector<StoppingSegment> *out) const {
+  if (!init_status_.ok()) return init_status_;
+  const size_t n = planners.size(), D = options_.GetNumDofs();
+  if (!out || time.size() != n || max_acceleration.size() != n)
+    return InvalidArgumentError("one time and one max_acceleration per planner");
+  std::vector<int32_t> ids(n), st(n), keep(n);
+  std::vector<int64_t> t(n), offsets(n + 1);
+  std::vector<double> amax(n * D);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_) return InvalidArgumentError("no such planner");
+    if (max_acceleration[k].size() != D) return InvalidArgumentError("max_acceleration has the wrong dimension");
+    ids[k] = (int32_t)planners[k];
+    t[k] = ::tpamd::compat::ToUnixNanos(time[k]);
+    std::copy(max_acceleration[k].begin(), max_acceleration[k].end(), amax.begin() + k * D);
+  }
+  out->assign(n, StoppingSegment());
+  if (n == 0) return OkStatus();
+  // The segments' total is known only after the stop: a first call without room reports it (and
+  // the statuses), the second writes the rows. Segments are short next to the trajectories, so
+  // sizing the arrays exactly beats a generous first guess.
+  std::vector<double> tm, q, qd, qdd;
+  size_t rows = 0;
+  for (int attempt = 0;; attempt++) {
+    const size_t r = std::max<size_t>(rows, 1);
+    tm.resize(r); q.resize(r * D); qd.resize(r * D); qdd.resize(r * D);
+    const int rc = tpamd_planner_set_stop_trajectories(set_, (int)n, ids.data(), t.data(), amax.data(), time_step,
+                                                       st.data(), keep.data(), offsets.data(), (int64_t)rows,
+                                                       tm.data(), q.data(), qd.data(), qdd.data());
+    if (rc == 0) break;
+    if (rc != TPAMD_E_INVALID_ARGUMENT || attempt > 0 || (size_t)offsets[n] <= rows)
+      return InternalError(tpamd_error_string(rc));
+    rows = (size_t)offsets[n];           // grow to the total and go again
+  }
+  for (size_t k = 0; k < n; k++) {
+    StoppingSegment &o = (*out)[k];
+    switch (st[k]) {
+      case TPAMD_PLAN_OK: o.status = OkStatus(); break;
+      case TPAMD_PLAN_OUT_OF_RANGE: o.status = OutOfRangeError("stop index or time out of range"); break;
+      case TPAMD_PLAN_INVALID_ARGUMENT: o.status = InvalidArgumentError("invalid stop arguments or samples"); break;
+      case TPAMD_PLAN_NOT_FOUND:
+        o.status = NotFoundError("No safe stopping trajectory found (likely not enough time).");
+        break;
+      default: o.status = InternalError("no stopping trajectory"); break;
+    }
+    o.keep = (size_t)keep[k];
+    const size_t a = (size_t)offsets[k], b = (size_t)offsets[k + 1];
+    o.time.assign(tm.begin() + a, tm.begin() + b);
+    o.positions.assign(q.begin() + a * D, q.begin() + b * D);
+    o.velocities.assign(qd.begin() + a * D, qd.begin() + b * D);
+    o.accelerations.assign(qdd.begin() + a * D, qdd.begin() + b * D);
   }
   return OkStatus();
 }

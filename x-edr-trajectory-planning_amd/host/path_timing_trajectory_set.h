@@ -40,6 +40,15 @@ struct TrajectorySetpoints {
   std::vector<Status> status;
 };
 
+// One planner's stop (StopTrajectoriesBeforeTime): the stopped trajectory is the planner's first
+// `keep` samples followed by the segment's rows (time [rows], positions / velocities /
+// accelerations [rows][dofs], packed). A failed stop keeps every sample and has no rows.
+struct StoppingSegment {
+  Status status;
+  size_t keep = 0;
+  std::vector<double> time, positions, velocities, accelerations;
+};
+
 class PathTimingTrajectorySet {
  public:
   // All planners share the planner options and the path options (dofs, samples; delta may differ
@@ -105,6 +114,14 @@ class PathTimingTrajectorySet {
   // fails the call.
   Status GetSetpoints(const std::vector<size_t> &planners, const std::vector<Time> &start, Duration step, int ticks,
                       TrajectorySetpoints *out) const;
+  // TrajectoryBuffer::StopBeforeTime(time[k], max_acceleration[k], time_step) on each listed
+  // planner's trajectory as GetTrajectory gives it, loaded into a TrajectoryBuffer
+  // (host/trajectory_buffer.h), on the device (tpamd_planner_set_stop_trajectories): per planner the
+  // status, keep and the segment. No planner state changes; the next Plan is unaffected. A planner
+  // out of range or a max_acceleration of the wrong size fails the call.
+  Status StopTrajectoriesBeforeTime(const std::vector<size_t> &planners, const std::vector<Time> &time,
+                                    const std::vector<VectorXd> &max_acceleration, double time_step,
+                                    std::vector<StoppingSegment> *out) const;
   // Bytes the last Plan call moved over PCIe, both directions.
   size_t LastPlanBytesOverPcie() const;
   size_t DeviceBytes() const;

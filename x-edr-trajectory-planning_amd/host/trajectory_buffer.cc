@@ -1,0 +1,157 @@
+// TrajectoryBuffer (trajectory_buffer.cc), the part that stopping needs, restated on the compat
+// types. Quirks of the reference are kept on purpose: InsertSegment's upper_bound with a <= b and
+// its step back by one within the tolerance, and StopAtIndex validating time_step without using it.
+#include "trajectory_buffer.h"
+
+#include <algorithm>
+#include <string>
+
+#include "rescale_to_stop.h"
+
+namespace trajectory_planning {
+
+using ::tpamd::compat::StatusOr;
+
+StatusOr<std::shared_ptr<TrajectoryBuffer>> TrajectoryBuffer::Create(TrajectoryBufferOptions options) {
+  if (!(options.timestep_tolerance > 0))
+    return ::tpamd::compat::FailedPreconditionError("timestep_tolerance (" +
+                                                    std::to_string(options.timestep_tolerance) + ") not positive");
+  return std::shared_ptr<TrajectoryBuffer>(new TrajectoryBuffer(options));
+}
+
+void TrajectoryBuffer::Clear() {
+  times_.clear();
+  positions_.clear();
+  velocities_.clear();
+  accelerations_.clear();
+}
+
+Status TrajectoryBuffer::InsertSegment(Span<const double> times, Span<const VectorXd> positions,
+                                       Span<const VectorXd> velocities, Span<const VectorXd> accelerations) {
+  if (positions.size() != velocities.size())
+    return ::tpamd::compat::InvalidArgumentError("positions and velocity arguments have different size.");
+  if (positions.size() != accelerations.size())
+    return ::tpamd::compat::InvalidArgumentError("positions and accelerations arguments have different size.");
+  if (positions.size() != times.size())
+    return ::tpamd::compat::InvalidArgumentError("positions and times arguments have different size.");
+  if (positions.empty()) return ::tpamd::compat::OkStatus();
+
+  // the first sample later than times.front()
+  auto it_upper = std::upper_bound(times_.begin(), times_.end(), times[0],
+                                   [](const double a, const double b) { return a <= b; });
+  if (positions_.empty() || it_upper == times_.begin()) {
+    times_.assign(times.begin(), times.end());
+    positions_.assign(positions.begin(), positions.end());
+    velocities_.assign(velocities.begin(), velocities.end());
+    accelerations_.assign(accelerations.begin(), accelerations.end());
+    return ::tpamd::compat::OkStatus();
+  }
+  // the new first sample is just after an existing one: replace that one
+  if (times[0] - *std::prev(it_upper) < options_.timestep_tolerance) --it_upper;
+  const size_t samples_to_keep = (size_t)(it_upper - times_.begin());
+  times_.resize(samples_to_keep);
+  positions_.resize(samples_to_keep);
+  velocities_.resize(samples_to_keep);
+  accelerations_.resize(samples_to_keep);
+  times_.insert(times_.end(), times.begin(), times.end());
+  positions_.insert(positions_.end(), positions.begin(), positions.end());
+  velocities_.insert(velocities_.end(), velocities.begin(), velocities.end());
+  accelerations_.insert(accelerations_.end(), accelerations.begin(), accelerations.end());
+  return ::tpamd::compat::OkStatus();
+}
+
+StatusOr<VectorXd> TrajectoryBuffer::ValueAtTime(const std::vector<VectorXd> &values, double time_sec) const {
+  if (times_.empty()) return ::tpamd::compat::FailedPreconditionError("No samples.");
+  if (time_sec < times_.front() || time_sec > times_.back())
+    return ::tpamd::compat::OutOfRangeError("Time outside the trajectory");
+  const auto upper = std::upper_bound(times_.begin(), times_.end(), time_sec);
+  if (upper == times_.end()) return values.back();
+  const size_t u = upper - times_.begin(), l = u - 1;
+  const double t = (time_sec - times_[l]) / (times_[u] - times_[l]);
+  VectorXd v(values[l].size());
+  for (size_t d = 0; d < v.size(); d++) v[d] = values[l][d] + t * (values[u][d] - values[l][d]);
+  return v;
+}
+
+static double TimeToSec(Time time) { return (double)::tpamd::compat::ToUnixNanos(time) / 1e9; }
+
+StatusOr<VectorXd> TrajectoryBuffer::GetPositionAtTime(double time_sec) const {
+  return ValueAtTime(positions_, time_sec);
+}
+StatusOr<VectorXd> TrajectoryBuffer::GetVelocityAtTime(double time_sec) const {
+  return ValueAtTime(velocities_, time_sec);
+}
+StatusOr<VectorXd> TrajectoryBuffer::GetAccelerationAtTime(double time_sec) const {
+  return ValueAtTime(accelerations_, time_sec);
+}
+StatusOr<VectorXd> TrajectoryBuffer::GetPositionAtTime(Time time) const { return GetPositionAtTime(TimeToSec(time)); }
+StatusOr<VectorXd> TrajectoryBuffer::GetVelocityAtTime(Time time) const { return GetVelocityAtTime(TimeToSec(time)); }
+StatusOr<VectorXd> TrajectoryBuffer::GetAccelerationAtTime(Time time) const {
+  return GetAccelerationAtTime(TimeToSec(time));
+}
+
+Status TrajectoryBuffer::StopAtIndex(int index, const VectorXd &max_acceleration, double time_step) {
+  const int n = (int)GetNumSamples();
+  if (index <= 0 || index > n - 1)
+    return ::tpamd::compat::OutOfRangeError("index (" + std::to_string(index) + ")  out of range (0, " +
+                                            std::to_string(n - 1) + "].");
+  double min_acceleration = max_acceleration.size() ? max_acceleration[0] : 0.0;
+  for (size_t j = 1; j < max_acceleration.size(); j++)
+    min_acceleration = max_acceleration[j] < min_acceleration ? max_acceleration[j] : min_acceleration;
+  if (min_acceleration <= 0.0)
+    return ::tpamd::compat::InvalidArgumentError("max_acceleration has non-positive minimum coefficient " +
+                                                 std::to_string(min_acceleration));
+  if (time_step <= 0.0)
+    return ::tpamd::compat::InvalidArgumentError("`time_step` should be positive but is " +
+                                                 std::to_string(time_step) + ".");
+
+  constexpr double kVerySmall = 1e-4;
+  if (index == n - 1 && velocities_.back().maxAbs() < kVerySmall) {
+    velocities_.back().setZero();
+    accelerations_.back().setZero();
+    return ::tpamd::compat::OkStatus();
+  }
+
+  const size_t samples_for_stop = (size_t)index + 1;
+  const auto rescaled = RescaleTrajectoryBackwardToStop(
+      max_acceleration, Span<const double>(times_.data(), samples_for_stop),
+      Span<const VectorXd>(positions_.data(), samples_for_stop),
+      Span<const VectorXd>(velocities_.data(), samples_for_stop),
+      Span<const VectorXd>(accelerations_.data(), samples_for_stop));
+  if (!rescaled.ok()) return rescaled.status();
+  const SampledTrajectory &stop = *rescaled;
+  // The reference aborts here (CHECK); this happens when sample `index` is already at rest.
+  if (stop.times.empty())
+    return ::tpamd::compat::InternalError("sample " + std::to_string(index) +
+                                          " is at rest before the end: no stopping trajectory");
+
+  // A stop that needs every sample must match the original velocity where it starts.
+  if (stop.times.size() == (size_t)index) {
+    const auto velocity_at_start = GetVelocityAtTime(stop.times.front());
+    if (!velocity_at_start.ok()) return velocity_at_start.status();
+    double err = 0.0;
+    for (size_t j = 0; j < stop.velocities.front().size(); j++) {
+      const double e = std::fabs((*velocity_at_start)[j] - stop.velocities.front()[j]);
+      err = e > err ? e : err;
+    }
+    constexpr double kAcceptableMatchError = 1e-2;
+    if (err > kAcceptableMatchError)
+      return ::tpamd::compat::NotFoundError("No safe stopping trajectory found (likely not enough time).");
+  }
+  return InsertSegment(stop.times, stop.positions, stop.velocities, stop.accelerations);
+}
+
+Status TrajectoryBuffer::StopBeforeTime(Time time, const VectorXd &max_acceleration, double time_step) {
+  return StopBeforeTime(TimeToSec(time), max_acceleration, time_step);
+}
+
+Status TrajectoryBuffer::StopBeforeTime(double time_sec, const VectorXd &max_acceleration, double time_step) {
+  if (times_.empty()) return ::tpamd::compat::OkStatus();
+  if (time_sec < times_.front()) return ::tpamd::compat::OutOfRangeError("time < times_.front().");
+  // the sample after the first one at or after time_sec, or the last
+  const int lower = (int)(std::lower_bound(times_.begin(), times_.end(), time_sec) - times_.begin());
+  const int index = std::min<int>(lower + 1, (int)times_.size() - 1);
+  return StopAtIndex(index, max_acceleration, time_step);
+}
+
+}  // namespace trajectory_planning
