@@ -420,6 +420,42 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *set, int count, const int3
                                    const int64_t *time_ns, const double *keep_path_until,
                                    const int32_t *waypoint_offsets, const double *waypoints,
                                    double *stop_parameter, int32_t *num_points, int32_t *status);
+/* New waypoint paths for `count` planners of a set (ids[count], each listed once, or planners
+ * 0..count-1 if ids is NULL), fitted on the device: TimeableJointSplinePath::SetWaypoints
+ * (FitSplineToWaypoints, timeable_path_joint_spline.cc:199-206, :252-292) on planner k's waypoints
+ * waypoints[waypoint_offsets[k] .. waypoint_offsets[k + 1])[D] with the PathOptions::rounding radius
+ * `rounding` (0.2 is the default; any value passes through unchanged, 0 included), bit-identical to
+ * the host mirror. Planner k then holds what tpamd_planner_set_upload_paths_ragged with path_state
+ * 1 (kNewPath) leaves: the spline (max(3 W - 2, 4) control points), max_velocity[k] /
+ * max_acceleration[k] / initial_velocity[k] [count][D] (initial_velocity NULL: zero) and delta[k];
+ * the next tpamd_planner_set_plan plans it as a new path. Per planner: num_points[k] (may be NULL;
+ * the planner's control points after the call, 0 for no path) and status[k] TPAMD_PLAN_*: a planner
+ * with no waypoints gets TPAMD_PLAN_INVALID_ARGUMENT ("Control point vector empty.") and keeps its
+ * state. Call-level errors change nothing: NULL set / waypoint_offsets / max_velocity /
+ * max_acceleration / delta / status, NULL waypoints with rows, count < 0 or > B, a bad or repeated
+ * id, waypoint_offsets[0] != 0 or decreasing. The set's per-planner capacity grows (by doubling)
+ * before anything changes. Host pointers; synchronises. */
+int tpamd_planner_set_set_waypoints(tpamd_planner_set *set, int count, const int32_t *ids,
+                                    const int32_t *waypoint_offsets, const double *waypoints,
+                                    double rounding, const double *max_velocity,
+                                    const double *max_acceleration, const double *delta,
+                                    const double *initial_velocity, int32_t *num_points,
+                                    int32_t *status);
+/* The same with waypoints, max_velocity, max_acceleration, delta, initial_velocity, num_points and
+ * status device pointers; ids and waypoint_offsets stay HOST arrays: the id checks, the planners'
+ * control-point counts and the capacity growth need them on the host before the launch (they go
+ * up through pinned staging on hip_stream). Enqueues on hip_stream (NULL: the null stream) and does
+ * not synchronise, except when the capacity grows (on the null stream, first) or the staging of
+ * the previous call of this entry is still in use. Stream ordering as for the _device readouts
+ * (tpamd_planner_set_download_trajectories_device): the fit starts after the set's last change and
+ * the last device readout; the calls that change or read planner state on the null stream wait for
+ * it, and so do later device readouts. */
+int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                           const int32_t *waypoint_offsets, const double *waypoints,
+                                           double rounding, const double *max_velocity,
+                                           const double *max_acceleration, const double *delta,
+                                           const double *initial_velocity, int32_t *num_points,
+                                           int32_t *status, void *hip_stream);
 /* TrajectoryPlanner::Reset for the listed planners (ids NULL: all): no path, no plan. */
 int tpamd_planner_set_reset(tpamd_planner_set *set, int count, const int32_t *ids);
 /* Plan(start, time_horizon) for every planner: start_ns / horizon_ns [B] host arrays;

@@ -19,6 +19,7 @@
 #include "tpamd_rescale.h"
 #include "tpamd_stop.h"
 #include "tpamd_switch.h"
+#include "tpamd_fit.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 
 using namespace tpamd;
@@ -2013,6 +2014,12 @@ struct tpamd_planner_set {
   // status, keep, offsets as well)
   void *stop_buf = nullptr;
   size_t stop_bytes = 0;
+  // set_waypoints calls: device inputs and outputs; the _device variant stages ids and offsets in
+  // pinned memory, which ev_wp (recorded after their copy) guards against the next call
+  void *wp_buf = nullptr, *wp_pin = nullptr;
+  size_t wp_bytes = 0, wp_pin_bytes = 0;
+  hipEvent_t ev_wp = nullptr;
+  bool wp_pin_busy = false;
 };
 
 namespace {
@@ -2369,7 +2376,8 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
   }
   refresh_plan_params(ps);
   if (hipEventCreateWithFlags(&ps->ev_set, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ps->ev_read, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&ps->ev_read, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&ps->ev_wp, hipEventDisableTiming) != hipSuccess) {
     tpamd_planner_set_destroy(ps);
     return TPAMD_E_HIP;
   }
@@ -2397,12 +2405,15 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (ps->traj) (void)hipFree(ps->traj);
   if (ps->path) (void)hipFree(ps->path);
   if (ps->sw_buf) (void)hipFree(ps->sw_buf);
+  if (ps->wp_buf) (void)hipFree(ps->wp_buf);
+  if (ps->wp_pin) (void)hipHostFree(ps->wp_pin);
+  if (ps->ev_wp) (void)hipEventDestroy(ps->ev_wp);
   delete ps;
 }
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
   return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_bytes + ps->rd_in_bytes +
-                   ps->rd_out_bytes + ps->stop_bytes
+                   ps->rd_out_bytes + ps->stop_bytes + ps->wp_bytes
             : 0;
 }
 
@@ -2433,6 +2444,7 @@ int tpamd_planner_set_download_path(tpamd_planner_set *ps, int planner, int32_t 
   if (P == 0 || (!knots && !cps)) return 0;
   if (P > capacity) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(ps->e);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // a device set_waypoints may still be writing
   const size_t D = ps->S.D, b = planner;
   if (knots) HIPCHK(hipMemcpy(knots, ps->S.knots + b * ps->S.K, (size_t)(P + 3) * 8, hipMemcpyDeviceToHost));
   if (cps) HIPCHK(hipMemcpy(cps, ps->d_cp + b * ps->pcap * D, (size_t)P * D * 8, hipMemcpyDeviceToHost));
@@ -2588,6 +2600,7 @@ int tpamd_planner_set_stop_parameters(tpamd_planner_set *ps, int count, const in
   std::memcpy(in.data(), time_ns, n * 8);
   if (ids) std::memcpy(in.data() + n * 8, ids, n * 4);
   hipStream_t st = nullptr;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // the limits of a device set_waypoints
   HIPCHK(hipMemcpyAsync(ps->d_stop_in, in.data(), in.size(), hipMemcpyHostToDevice, st));
   FastestStopParams p{};
   p.Q = count; p.stride = ps->tcap;
@@ -2705,6 +2718,168 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
   for (size_t k = 0; k < n; k++)
     if (status[k] == TPAMD_PLAN_OK) ps->h_np[id[k]] = num_points[k];
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- planner-set waypoint fits
+namespace {
+
+// The call-level checks of the two set_waypoints entries (before anything changes): the arrays,
+// every id in range and listed once (ids NULL: 0..count-1), offsets from 0 and non-decreasing.
+// Fills id[count] and *need, the largest control-point count of a fit.
+int waypoint_args(const tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *offsets,
+                  const double *waypoints, const double *vmax, const double *amax, const double *delta,
+                  const int32_t *status, std::vector<int32_t> *id, int *need) {
+  if (!ps || count < 0 || !offsets || !vmax || !amax || !delta || !status) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = ps->S.B;
+  if ((size_t)count > B || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<char> seen(B, 0);
+  id->resize(count);
+  long long most = 0;
+  for (int k = 0; k < count; k++) {
+    const long long b = ids ? (long long)ids[k] : (long long)k;
+    if (b < 0 || b >= (long long)B || seen[b]) return TPAMD_E_INVALID_ARGUMENT;
+    seen[b] = 1;
+    (*id)[k] = (int32_t)b;
+    if (offsets[k + 1] < offsets[k]) return TPAMD_E_INVALID_ARGUMENT;
+    const long long W = (long long)offsets[k + 1] - offsets[k];
+    if (W > 0) most = std::max(most, W == 1 ? 4 : 3 * W - 2);
+  }
+  if (offsets[count] > 0 && !waypoints) return TPAMD_E_INVALID_ARGUMENT;
+  if (most > (1 << 24)) return TPAMD_E_UNSUPPORTED;
+  *need = (int)most;
+  return 0;
+}
+
+// Grow the set_waypoints device buffer (contents are not kept); a device call in flight may use it.
+int ensure_wp_buf(tpamd_planner_set *ps, size_t bytes) {
+  if (bytes <= ps->wp_bytes) return 0;
+  if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
+  return ensure_staging(&ps->wp_buf, &ps->wp_bytes, bytes);
+}
+
+FitParams fit_params(const tpamd_planner_set *ps, int count, double rounding) {
+  const PlannerSetState &S = ps->S;
+  FitParams p{};
+  p.Q = count; p.D = S.D; p.K = S.K; p.pcap = ps->pcap; p.rounding = rounding;
+  p.knots = (double *)S.knots; p.cps = ps->d_cp;
+  p.s_vmax = ps->d_vmax; p.s_amax = (double *)S.amax; p.s_delta = ps->d_delta; p.s_iv = ps->d_iv;
+  p.np = S.np; p.path_state = S.path_state; p.has_path = S.has_path;
+  return p;
+}
+
+// the host copies of np / has_path after a fit (its outcome follows from W alone)
+void fit_bookkeeping(tpamd_planner_set *ps, int count, const std::vector<int32_t> &id, const int32_t *offsets) {
+  for (int k = 0; k < count; k++) {
+    const int W = offsets[k + 1] - offsets[k];
+    if (W < 1) continue;
+    ps->h_np[id[k]] = fit_points(W);
+    ps->h_has[id[k]] = 1;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_planner_set_set_waypoints(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                    const int32_t *waypoint_offsets, const double *waypoints, double rounding,
+                                    const double *max_velocity, const double *max_acceleration, const double *delta,
+                                    const double *initial_velocity, int32_t *num_points, int32_t *status) {
+  std::vector<int32_t> id;
+  int need = 0;
+  int rc = waypoint_args(ps, count, ids, waypoint_offsets, waypoints, max_velocity, max_acceleration, delta, status,
+                         &id, &need);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)count, D = ps->S.D, rows = (size_t)waypoint_offsets[count];
+  // device buffer: in [ids][offsets][waypoints][vmax][amax][delta][iv] | out [num_points][status]
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+  const size_t o_ids = take(n * 4), o_off = take((n + 1) * 4), o_wps = take(rows * D * 8), o_vmax = take(n * D * 8),
+               o_amax = take(n * D * 8), o_delta = take(n * 8), o_iv = take(initial_velocity ? n * D * 8 : 0);
+  const size_t in_end = off;
+  const size_t o_np = take(n * 4), o_status = take(n * 4);
+  if (ensure_wp_buf(ps, off)) return TPAMD_E_HIP;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  rc = ensure_pcap(ps, need, st);
+  if (rc) return rc;
+  std::vector<char> in(in_end, 0), out(off - o_np);
+  std::memcpy(in.data() + o_ids, id.data(), n * 4);
+  std::memcpy(in.data() + o_off, waypoint_offsets, (n + 1) * 4);
+  if (rows) std::memcpy(in.data() + o_wps, waypoints, rows * D * 8);
+  std::memcpy(in.data() + o_vmax, max_velocity, n * D * 8);
+  std::memcpy(in.data() + o_amax, max_acceleration, n * D * 8);
+  std::memcpy(in.data() + o_delta, delta, n * 8);
+  if (initial_velocity) std::memcpy(in.data() + o_iv, initial_velocity, n * D * 8);
+  char *base = (char *)ps->wp_buf;
+  HIPCHK(hipMemcpyAsync(base, in.data(), in_end, hipMemcpyHostToDevice, st));
+  FitParams p = fit_params(ps, count, rounding);
+  p.ids = (const int *)(base + o_ids); p.offsets = (const int *)(base + o_off);
+  p.wps = (const double *)(base + o_wps); p.vmax = (const double *)(base + o_vmax);
+  p.amax = (const double *)(base + o_amax); p.delta = (const double *)(base + o_delta);
+  p.iv = initial_velocity ? (const double *)(base + o_iv) : nullptr;
+  p.np_out = (int *)(base + o_np); p.status_out = (int *)(base + o_status);
+  launch_set_waypoints(p, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out.data(), base + o_np, out.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (num_points) std::memcpy(num_points, out.data(), n * 4);
+  std::memcpy(status, out.data() + (o_status - o_np), n * 4);
+  fit_bookkeeping(ps, count, id, waypoint_offsets);
+  return 0;
+}
+
+int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                           const int32_t *waypoint_offsets, const double *waypoints, double rounding,
+                                           const double *max_velocity, const double *max_acceleration,
+                                           const double *delta, const double *initial_velocity, int32_t *num_points,
+                                           int32_t *status, void *hip_stream) {
+  std::vector<int32_t> id;
+  int need = 0;
+  int rc = waypoint_args(ps, count, ids, waypoint_offsets, waypoints, max_velocity, max_acceleration, delta, status,
+                         &id, &need);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t n = (size_t)count, bytes = align_up(n * 4, 256) + (n + 1) * 4;
+  if (ensure_wp_buf(ps, bytes)) return TPAMD_E_HIP;
+  if (need > ps->pcap) {         // the growth runs on the null stream, after the device calls in flight
+    if (order_after_readouts(ps)) return TPAMD_E_HIP;
+    rc = ensure_pcap(ps, need, nullptr);
+    if (rc) return rc;
+  }
+  // ids and offsets through pinned staging; the previous call's copy out of it has to be done
+  if (ps->wp_pin_busy) {
+    HIPCHK(hipEventSynchronize(ps->ev_wp));
+    ps->wp_pin_busy = false;
+  }
+  if (bytes > ps->wp_pin_bytes) {
+    if (ps->wp_pin) HIPCHK(hipHostFree(ps->wp_pin));
+    ps->wp_pin = nullptr;
+    ps->wp_pin_bytes = 0;
+    HIPCHK(hipHostMalloc(&ps->wp_pin, bytes, hipHostMallocDefault));
+    ps->wp_pin_bytes = bytes;
+  }
+  char *pin = (char *)ps->wp_pin, *base = (char *)ps->wp_buf;
+  std::memcpy(pin, id.data(), n * 4);
+  std::memcpy(pin + align_up(n * 4, 256), waypoint_offsets, (n + 1) * 4);
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  HIPCHK(hipMemcpyAsync(base, pin, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ps->ev_wp, st));
+  ps->wp_pin_busy = true;
+  FitParams p = fit_params(ps, count, rounding);
+  p.ids = (const int *)base; p.offsets = (const int *)(base + align_up(n * 4, 256));
+  p.wps = waypoints; p.vmax = max_velocity; p.amax = max_acceleration; p.delta = delta; p.iv = initial_velocity;
+  p.np_out = num_points; p.status_out = status;
+  launch_set_waypoints(p, st);
+  HIPCHK(hipGetLastError());
+  fit_bookkeeping(ps, count, id, waypoint_offsets);
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
 }
 
 }  // extern "C"

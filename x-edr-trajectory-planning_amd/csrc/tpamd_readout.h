@@ -73,7 +73,7 @@ TPAMD_HD inline bool tb_tick_time(int64_t start_ns, int64_t step_ns, int64_t j, 
   return !__builtin_add_overflow(start_ns, off, out);
 }
 
-#if defined(__HIPCC__) || defined(__HIP__)
+#if (defined(__HIPCC__) || defined(__HIP__)) && !defined(TPAMD_HD_ROUTINES_ONLY)
 // ------------------------------------------------------------------ the readout kernels
 struct ReadoutParams {
   int B, D, tcap;                      // planners, joints, trajectory row stride of the set

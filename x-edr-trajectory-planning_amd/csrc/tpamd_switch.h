@@ -23,7 +23,8 @@
 #include <math.h>
 #include <float.h>
 
-#if defined(__HIPCC__) || defined(__HIP__)
+// TPAMD_HD_ROUTINES_ONLY: the routines without the kernels (tpamd_fit.hip)
+#if (defined(__HIPCC__) || defined(__HIP__)) && !defined(TPAMD_HD_ROUTINES_ONLY)
 #include "tpamd_planner_set.h"   // pset_time_to_sec
 #endif
 
@@ -320,7 +321,7 @@ TPAMD_HD inline int sw_velocity_at_time(const double *time, const double *vel, i
   return kSwOk;
 }
 
-#if defined(__HIPCC__) || defined(__HIP__)
+#if (defined(__HIPCC__) || defined(__HIP__)) && !defined(TPAMD_HD_ROUTINES_ONLY)
 // ------------------------------------------------------------------ the switch kernel
 struct SwitchParams {
   int Q, D, K, pcap, tcap;             // queries; joints; knot / point strides of the set (K = pcap + 3)

@@ -16,7 +16,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
-            "tpamd_rescale.h"]
+            "tpamd_rescale.h", "tpamd_fit.h", "tpamd_fit.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -54,7 +54,8 @@ def _compile(target, extra_flags, force, verbose):
                           "obj_" + os.path.splitext(os.path.basename(target))[0])
     os.makedirs(objdir, exist_ok=True)
     flags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags)
-    units = [(os.path.join(objdir, "capi.o"), ["tpamd_capi.hip"])]
+    units = [(os.path.join(objdir, "capi.o"), ["tpamd_capi.hip"]),
+             (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"])]
     for d, e in SWEEP_INSTANCES:
         units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
                       ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
@@ -173,6 +174,21 @@ class _FastestStopArgs(C.Structure):
                                            "profile_drate2")])
 
 
+class _PlannerSetConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in (
+        "num_planners", "num_dofs", "num_samples", "num_points", "history_capacity",
+        "trajectory_capacity", "sampling_method", "max_planning_iterations")] +
+                [("constraint_safety", C.c_double), ("max_initial_velocity_error", C.c_double),
+                 ("time_step_ns", C.c_int64)])
+
+
+# tpamd_planner_summary
+PLANNER_SUMMARY_DTYPE = np.dtype([
+    ("end_time_ns", np.int64), ("final_decel_start_ns", np.int64), ("start_time_ns", np.int64),
+    ("num_samples", np.int32), ("target_reached", np.int32), ("planned_to_end", np.int32),
+    ("windows", np.int32), ("path_state", np.int32), ("history_count", np.int32),
+    ("status", np.int32), ("reserved", np.int32)])
+
 _LIB = None
 
 # every symbol include/tpamd.h declares
@@ -196,6 +212,7 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
     "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device",
     "tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
+    "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
     "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
     "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
     "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
@@ -308,6 +325,29 @@ def load_library():
         [vp, i, vp, vp, vp, C.c_double, vp, vp, vp, i64] + [vp] * 4 + [vp])
     L.tpamd_stop_trajectories_device.argtypes = [vp, vp, vp]
     L.tpamd_stop_trajectories_host.argtypes = [vp, vp]
+    # planner sets (PlannerSet)
+    for name in ("tpamd_planner_set_create", "tpamd_planner_set_upload_paths",
+                 "tpamd_planner_set_upload_paths_ragged", "tpamd_planner_set_download_path",
+                 "tpamd_planner_set_reset", "tpamd_planner_set_plan",
+                 "tpamd_planner_set_download_trajectory", "tpamd_planner_set_switch_paths",
+                 "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_create.argtypes = [vp, C.POINTER(_PlannerSetConfig), C.POINTER(vp)]
+    L.tpamd_planner_set_destroy.restype = None
+    L.tpamd_planner_set_destroy.argtypes = [vp]
+    L.tpamd_planner_set_upload_paths.argtypes = [vp, i] + [vp] * 8
+    L.tpamd_planner_set_upload_paths_ragged.argtypes = [vp, i] + [vp] * 9
+    L.tpamd_planner_set_download_path.argtypes = [vp, i, vp, vp, vp, i]
+    L.tpamd_planner_set_reset.argtypes = [vp, i, vp]
+    L.tpamd_planner_set_plan.argtypes = [vp, vp, vp, vp]
+    L.tpamd_planner_set_download_trajectory.argtypes = [vp, i, i, i] + [vp] * 7
+    L.tpamd_planner_set_switch_paths.argtypes = [vp, i] + [vp] * 8
+    L.tpamd_planner_set_set_waypoints.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6
+    L.tpamd_planner_set_set_waypoints_device.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6 + [vp]
+    L.tpamd_planner_set_last_plan_bytes.restype = None
+    L.tpamd_planner_set_last_plan_bytes.argtypes = [vp, vp, vp]
+    L.tpamd_planner_set_device_bytes.restype = C.c_size_t
+    L.tpamd_planner_set_device_bytes.argtypes = [vp]
     L.tpamd_debug_copy_boundary.restype = i
     L.tpamd_debug_copy_boundary.argtypes = [vp, i, i] + [vp] * 6
     L.tpamd_debug_keep_boundary.argtypes = [vp, i]
@@ -638,6 +678,341 @@ class Engine:
         for k in range(self._lib.tpamd_profile_num_kernels()):
             ms, n = self.profile_mean_ms(k)
             out[self._lib.tpamd_profile_kernel_name(k).decode()] = (ms, n)
+        return out
+
+
+def _is_cuda(t):
+    return hasattr(t, "is_cuda") and t.is_cuda
+
+
+def _host(x, dtype, shape=None, what="argument"):
+    """A C-contiguous numpy copy of a host (or CUDA) array-like; None stays None."""
+    if x is None:
+        return None
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(x, dtype=dtype))
+    if shape is not None and a.shape != tuple(shape):
+        raise TpamdError("%s has shape %s, expected %s" % (what, a.shape, tuple(shape)))
+    return a
+
+
+class PlannerSet:
+    """B receding-horizon planners with joint-space spline paths whose whole state stays on the
+    device between calls (include/tpamd.h tpamd_planner_set_*). The typical loop keeps its goals,
+    limits and setpoints in CUDA tensors:
+
+        with PlannerSet(engine, B, D, N) as ps:
+            ps.set_waypoints(wps, offsets, vmax, amax, delta)     # wps: CUDA [rows][D]
+            summary = ps.plan(start_ns, horizon_ns)
+            ps.sample_at_ticks(t0_ns, step_ns, T, q=q, qd=qd)     # CUDA [B][T][D]
+
+    CUDA tensors go through the _device entries on torch's current stream (or `stream`); CPU
+    tensors and numpy arrays through the host entries, which synchronise. ids (int32, each listed
+    once where a call changes planners; None: planners 0..count-1) and waypoint offsets are host
+    arrays in every call (a CUDA tensor is copied to the host first). Errors raise TpamdError."""
+
+    def __init__(self, engine, num_planners, num_dofs, num_samples, num_points=16, time_step_ns=4_000_000,
+                 sampling_method=0, max_planning_iterations=200, constraint_safety=0.8,
+                 max_initial_velocity_error=1e-2, history_capacity=0, trajectory_capacity=0):
+        self._lib = load_library()
+        self.B, self.D, self.N = int(num_planners), int(num_dofs), int(num_samples)
+        self.device = engine.device
+        cfg = _PlannerSetConfig(self.B, self.D, self.N, int(num_points), int(history_capacity),
+                                int(trajectory_capacity), int(sampling_method), int(max_planning_iterations),
+                                float(constraint_safety), float(max_initial_velocity_error), int(time_step_ns))
+        h = C.c_void_p()
+        _check(self._lib.tpamd_planner_set_create(engine._h, C.byref(cfg), C.byref(h)), "tpamd_planner_set_create")
+        self._engine = engine          # the set must not outlive its engine
+        self._h = h
+        self._num_samples = np.zeros(self.B, dtype=np.int64)    # GetNumTimeSamples after the last plan
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tpamd_planner_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise TpamdError("the planner set is closed")
+        return self._h
+
+    def _ids(self, ids, count=None):
+        if ids is None:
+            return None, (self.B if count is None else int(count))
+        a = _host(ids, np.int32, what="ids").reshape(-1)
+        return a, a.shape[0]
+
+    @property
+    def device_bytes(self):
+        return self._lib.tpamd_planner_set_device_bytes(self._handle())
+
+    # ------------------------------------------------------------ paths
+    def set_waypoints(self, waypoints, offsets, max_velocity, max_acceleration, delta, initial_velocity=None,
+                      ids=None, rounding=0.2, stream=None):
+        """New waypoint paths, fitted on the device (tpamd_planner_set_set_waypoints*):
+        listed planner k (ids[k], or k) gets waypoints[offsets[k]:offsets[k + 1]] ([rows][D]
+        float64), max_velocity / max_acceleration / initial_velocity [count][D] (initial_velocity
+        None: zero), delta [count] (or one number) and the PathOptions rounding radius `rounding`.
+        Returns (status, num_points) int32 [count]: TPAMD_PLAN_* per planner (no waypoints:
+        INVALID_ARGUMENT, the planner keeps its state) and the control points after the call. With
+        a CUDA `waypoints` every array is taken on its device and the call only enqueues on
+        `stream` (default: torch's current stream); results are CUDA tensors. Otherwise the host
+        entry runs and synchronises; results are CPU tensors."""
+        import torch
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("waypoint offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        D = self.D
+        if _is_cuda(waypoints):
+            dev = waypoints.device
+            f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
+            w = f(waypoints, None, "waypoints").reshape(-1, D) if waypoints.numel() else \
+                torch.zeros((0, D), dtype=torch.float64, device=dev)
+            if n and w.shape[0] != off[-1]:
+                raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+            vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
+            dl = f(delta if hasattr(delta, "shape") else torch.full((n,), float(delta), dtype=torch.float64),
+                   (n,), "delta")
+            iv = None if initial_velocity is None else f(initial_velocity, (n, D), "initial_velocity")
+            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            num_points = torch.zeros((n,), dtype=torch.int32, device=dev)
+            _check(self._lib.tpamd_planner_set_set_waypoints_device(
+                self._handle(), n, _ptr(ida), _ptr(off), w.data_ptr() if w.numel() else None, float(rounding),
+                _ptr(vm), _ptr(am), _ptr(dl), _ptr(iv), _ptr(num_points), _ptr(status),
+                _stream_ptr(stream)), "tpamd_planner_set_set_waypoints_device")
+            return status, num_points
+        w = _host(waypoints, np.float64, what="waypoints").reshape(-1, D)
+        if w.shape[0] != off[-1]:
+            raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
+        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
+        dl = _host(np.broadcast_to(_host(delta, np.float64), (n,)), np.float64, (n,), "delta")
+        iv = _host(initial_velocity, np.float64, (n, D), "initial_velocity")
+        status = np.full(n, -1, dtype=np.int32)
+        num_points = np.zeros(n, dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_set_waypoints(
+            self._handle(), n, _ptr(ida), _ptr(off), _ptr(w) if w.size else None, float(rounding), _ptr(vm),
+            _ptr(am), _ptr(dl), _ptr(iv), _ptr(num_points), _ptr(status)), "tpamd_planner_set_set_waypoints")
+        return torch.from_numpy(status), torch.from_numpy(num_points)
+
+    @staticmethod
+    def _cuda(x, dtype, device, shape, what):
+        import torch
+        t = torch.as_tensor(x, dtype=dtype, device=device).contiguous()
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise TpamdError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
+        return t
+
+    def set_paths(self, knots, control_points, num_points, max_velocity, max_acceleration, delta,
+                  initial_velocity=None, ids=None, path_state=None):
+        """Fitted splines of any size (tpamd_planner_set_upload_paths_ragged): planner k's
+        num_points[k] control points [P][D] and P + 3 knots packed behind planner k - 1's in
+        control_points / knots; limits [count][D], delta [count], path_state [count] (1 kNewPath,
+        default, or 2 kModifiedPath). Host arrays; synchronises."""
+        npts = _host(num_points, np.int32, what="num_points").reshape(-1)
+        ida, n = self._ids(ids, npts.shape[0])
+        if npts.shape[0] != n:
+            raise TpamdError("one num_points per listed planner")
+        D = self.D
+        k = _host(knots, np.float64, what="knots").reshape(-1)
+        c = _host(control_points, np.float64, what="control_points").reshape(-1)
+        if k.shape[0] != int(npts.sum()) + 3 * n or c.shape[0] != int(npts.sum()) * D:
+            raise TpamdError("knots / control_points do not hold the listed paths")
+        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
+        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
+        dl = _host(np.broadcast_to(_host(delta, np.float64), (n,)), np.float64, (n,), "delta")
+        iv = _host(initial_velocity, np.float64, (n, D), "initial_velocity")
+        ps = np.ones(n, dtype=np.int32) if path_state is None else _host(path_state, np.int32, (n,), "path_state")
+        _check(self._lib.tpamd_planner_set_upload_paths_ragged(
+            self._handle(), n, _ptr(ida), _ptr(npts), _ptr(k), _ptr(c), _ptr(vm), _ptr(am), _ptr(dl), _ptr(iv),
+            _ptr(ps)), "tpamd_planner_set_upload_paths_ragged")
+
+    def download_path(self, planner):
+        """The resident spline of one planner: (knots [P + 3], control_points [P][D]) numpy; P = 0:
+        no path."""
+        P = C.c_int32(0)
+        _check(self._lib.tpamd_planner_set_download_path(self._handle(), int(planner), C.byref(P), None, None, 0),
+               "tpamd_planner_set_download_path")
+        k, c = np.zeros(P.value + 3 if P.value else 0), np.zeros((P.value, self.D))
+        if P.value:
+            _check(self._lib.tpamd_planner_set_download_path(self._handle(), int(planner), C.byref(P), _ptr(k),
+                                                             _ptr(c), P.value), "tpamd_planner_set_download_path")
+        return k, c
+
+    def reset(self, ids=None):
+        """TrajectoryPlanner::Reset for the listed planners (None: all)."""
+        ida, n = self._ids(ids)
+        _check(self._lib.tpamd_planner_set_reset(self._handle(), n, _ptr(ida)), "tpamd_planner_set_reset")
+        if ida is None:
+            self._num_samples[:] = 0
+        else:
+            self._num_samples[ida] = 0
+
+    # ------------------------------------------------------------ planning
+    def plan(self, start_ns, horizon_ns):
+        """Plan(start, time_horizon) for every planner (one number or [B] int64 nanoseconds each).
+        Returns the summary records as a dict of CPU tensors [B] (status, num_samples, end_time_ns,
+        final_decel_start_ns, start_time_ns, target_reached, planned_to_end, windows, path_state,
+        history_count)."""
+        import torch
+        s = _host(np.broadcast_to(_host(start_ns, np.int64), (self.B,)), np.int64)
+        h = _host(np.broadcast_to(_host(horizon_ns, np.int64), (self.B,)), np.int64)
+        out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
+        _check(self._lib.tpamd_planner_set_plan(self._handle(), _ptr(s), _ptr(h), out.ctypes.data),
+               "tpamd_planner_set_plan")
+        self._num_samples[:] = out["num_samples"]
+        return {name: torch.from_numpy(np.ascontiguousarray(out[name]))
+                for name in PLANNER_SUMMARY_DTYPE.names if name != "reserved"}
+
+    def stop_parameters(self, time_ns, ids=None):
+        """GetPathStopParameter(time) on the resident trajectories (tpamd_planner_set_stop_parameters):
+        dict stop_parameter, duration [count] float64 and status [count] int32, CPU tensors."""
+        import torch
+        t = _host(time_ns, np.int64).reshape(-1)
+        ida, n = self._ids(ids, t.shape[0])
+        if t.shape[0] != n:
+            raise TpamdError("one time per listed planner")
+        s, dur, st = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_stop_parameters(self._handle(), n, _ptr(ida), _ptr(t), _ptr(s), _ptr(dur),
+                                                           _ptr(st)), "tpamd_planner_set_stop_parameters")
+        return dict(stop_parameter=torch.from_numpy(s), duration=torch.from_numpy(dur), status=torch.from_numpy(st))
+
+    def switch_paths(self, time_ns, waypoints, offsets, ids=None, keep_path_until=None):
+        """The online path switch (tpamd_planner_set_switch_paths) at time_ns [count] onto
+        waypoints[offsets[k]:offsets[k + 1]]: dict stop_parameter, num_points, status (CPU tensors)."""
+        import torch
+        off = _host(offsets, np.int32).reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        t = _host(time_ns, np.int64).reshape(-1)
+        if off.shape[0] != n + 1 or t.shape[0] != n:
+            raise TpamdError("one time and count + 1 offsets for the listed planners")
+        w = _host(waypoints, np.float64).reshape(-1, self.D)
+        if w.shape[0] != off[-1]:
+            raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+        if not w.size:
+            w = np.zeros((1, self.D))    # the entry takes a non-NULL array even without rows
+        keep = _host(keep_path_until, np.float64, (n,), "keep_path_until")
+        s, npts, st = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_switch_paths(self._handle(), n, _ptr(ida), _ptr(t), _ptr(keep), _ptr(off),
+                                                        _ptr(w), _ptr(s), _ptr(npts), _ptr(st)),
+               "tpamd_planner_set_switch_paths")
+        return dict(stop_parameter=torch.from_numpy(s), num_points=torch.from_numpy(npts), status=torch.from_numpy(st))
+
+    # ------------------------------------------------------------ readouts
+    def sample_at_ticks(self, start_ns, step_ns, num_ticks, ids=None, q=None, qd=None, qdd=None, status=None,
+                        stream=None, host=False):
+        """Setpoints at control ticks start_ns[k] + j step_ns (tpamd_planner_set_sample_at_ticks*):
+        q / qd / qdd [count][num_ticks][D] float64 and status [count][num_ticks] int32. Device
+        variant (host=False): start_ns, ids and the outputs are CUDA tensors (outputs given or
+        allocated; None for q / qd / qdd means not wanted unless none is given: then all three),
+        enqueued on `stream`; ticks that are not OK keep their values. host=True: host arrays,
+        synchronises. Returns dict q, qd, qdd, status."""
+        import torch
+        T = int(num_ticks)
+        if not host:
+            dev = torch.device("cuda", self.device)
+            st0 = self._cuda(start_ns, torch.int64, dev, None, "start_ns").reshape(-1)
+            n = st0.shape[0]
+            idt = None if ids is None else self._cuda(ids, torch.int32, dev, (n,), "ids")
+            if ids is None and n > self.B:
+                raise TpamdError("more start times than planners")
+            if q is None and qd is None and qdd is None:
+                q, qd, qdd = (torch.full((n, T, self.D), float("nan"), dtype=torch.float64, device=dev)
+                              for _ in range(3))
+            for name, a in (("q", q), ("qd", qd), ("qdd", qdd)):
+                if a is not None and (not _is_cuda(a) or tuple(a.shape) != (n, T, self.D) or
+                                      a.dtype != torch.float64 or not a.is_contiguous()):
+                    raise TpamdError("%s must be a contiguous CUDA float64 tensor [%d][%d][%d]" % (name, n, T, self.D))
+            if status is None:
+                status = torch.full((n, T), -1, dtype=torch.int32, device=dev)
+            _check(self._lib.tpamd_planner_set_sample_at_ticks_device(
+                self._handle(), n, _ptr(idt), _ptr(st0), int(step_ns), T, _ptr(q), _ptr(qd), _ptr(qdd),
+                _ptr(status), _stream_ptr(stream)), "tpamd_planner_set_sample_at_ticks_device")
+            return dict(q=q, qd=qd, qdd=qdd, status=status)
+        st0 = _host(start_ns, np.int64).reshape(-1)
+        ida, n = self._ids(ids, st0.shape[0])
+        if st0.shape[0] != n:
+            raise TpamdError("one start time per listed planner")
+        out = {k: np.full((n, T, self.D), np.nan) for k in ("q", "qd", "qdd")}
+        out["status"] = np.full((n, T), -1, dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_sample_at_ticks(
+            self._handle(), n, _ptr(ida), _ptr(st0), int(step_ns), T, _ptr(out["q"]), _ptr(out["qd"]),
+            _ptr(out["qdd"]), _ptr(out["status"])), "tpamd_planner_set_sample_at_ticks")
+        return {k: torch.from_numpy(v) for k, v in out.items()}
+
+    def download_trajectories(self, ids=None, stream=None):
+        """The trajectories of the listed planners packed into CUDA tensors
+        (tpamd_planner_set_download_trajectories_device, on `stream`): dict offsets [count + 1]
+        int64 and time, s, sd, sdd [rows], q, qd, qdd [rows][D]; planner k's rows are
+        offsets[k]:offsets[k + 1]. The rows are sized from the last plan's sample counts."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ida, n = self._ids(ids)
+        rows = int(self._num_samples[ida].sum() if ida is not None else self._num_samples[:n].sum())
+        f = dict(dtype=torch.float64, device=dev)
+        out = dict(offsets=torch.zeros(n + 1, dtype=torch.int64, device=dev))
+        for k in ("time", "s", "sd", "sdd"):
+            out[k] = torch.empty(rows, **f)
+        for k in ("q", "qd", "qdd"):
+            out[k] = torch.empty(rows, self.D, **f)
+        idt = None if ida is None else torch.from_numpy(ida).to(dev)
+        _check(self._lib.tpamd_planner_set_download_trajectories_device(
+            self._handle(), n, _ptr(idt), _ptr(out["offsets"]), rows,
+            *[_ptr(out[k]) if rows else None for k in ("time", "s", "sd", "sdd", "q", "qd", "qdd")],
+            _stream_ptr(stream)), "tpamd_planner_set_download_trajectories_device")
+        out["_ids"] = idt          # kept alive with the result until the stream has used it
+        return out
+
+    def stop_trajectories(self, time_ns, max_acceleration, time_step, ids=None, capacity=None, stream=None):
+        """TrajectoryBuffer::StopBeforeTime on the resident trajectories
+        (tpamd_planner_set_stop_trajectories_device, on `stream`), CUDA tensors: time_ns [count]
+        int64, max_acceleration [count][D]. Returns dict status, keep [count] int32, offsets
+        [count + 1] int64 and the segments' time [rows], q, qd, qdd [rows][D]. The rows are sized by
+        `capacity` (default: the planners' sample counts plus 64 each); if the segments need more,
+        the call is repeated with room for them (it changes no state)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        t = self._cuda(time_ns, torch.int64, dev, None, "time_ns").reshape(-1)
+        n = t.shape[0]
+        idt = None if ids is None else self._cuda(ids, torch.int32, dev, (n,), "ids")
+        if ids is None and n > self.B:
+            raise TpamdError("more stop times than planners")
+        am = self._cuda(max_acceleration, torch.float64, dev, (n, self.D), "max_acceleration")
+        if capacity is None:
+            sel = self._num_samples[:n] if ids is None else self._num_samples[_host(ids, np.int64).reshape(-1)]
+            capacity = int(sel.sum()) + 64 * n
+        for _ in range(2):
+            out = dict(status=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                       keep=torch.zeros(n, dtype=torch.int32, device=dev),
+                       offsets=torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                       time=torch.empty(capacity, dtype=torch.float64, device=dev))
+            for k in ("q", "qd", "qdd"):
+                out[k] = torch.empty(capacity, self.D, dtype=torch.float64, device=dev)
+            _check(self._lib.tpamd_planner_set_stop_trajectories_device(
+                self._handle(), n, _ptr(idt), _ptr(t), _ptr(am), float(time_step), _ptr(out["status"]),
+                _ptr(out["keep"]), _ptr(out["offsets"]), int(capacity),
+                *[_ptr(out[k]) if capacity else None for k in ("time", "q", "qd", "qdd")],
+                _stream_ptr(stream)), "tpamd_planner_set_stop_trajectories_device")
+            rows = int(out["offsets"][-1].item()) if n else 0
+            if rows <= capacity:
+                break
+            capacity = rows
+        for k in ("time", "q", "qd", "qdd"):
+            out[k] = out[k][:rows]
         return out
 
 

@@ -224,6 +224,63 @@ std::vector<Status> PathTimingTrajectorySet::SwitchToWaypointPaths(const std::ve
   return result;
 }
 
+std::vector<Status> PathTimingTrajectorySet::SetWaypointPaths(const std::vector<size_t> &planners,
+                                                             const std::vector<std::vector<VectorXd>> &waypoints,
+                                                             const std::vector<VectorXd> &max_velocity,
+                                                             const std::vector<VectorXd> &max_acceleration,
+                                                             const std::vector<VectorXd> &initial_velocity,
+                                                             double rounding, double delta_parameter) {
+  const size_t n = planners.size(), D = options_.GetNumDofs();
+  if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
+  if (waypoints.size() != n || max_velocity.size() != n || max_acceleration.size() != n ||
+      (!initial_velocity.empty() && initial_velocity.size() != n))
+    return std::vector<Status>(n, InvalidArgumentError("one waypoint list and one set of limits per planner"));
+  std::vector<int32_t> ids(n), offsets(n + 1, 0), np(n), st(n);
+  std::vector<double> wps, vmax(n * D, 0.0), amax(n * D, 0.0), iv(n * D, 0.0), dl(n, delta_parameter);
+  std::vector<Status> result(n, OkStatus());
+  std::vector<char> seen(num_planners_, 0);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_ || seen[planners[k]])
+      return std::vector<Status>(n, InvalidArgumentError("no such planner, or listed twice"));
+    seen[planners[k]] = 1;
+    ids[k] = (int32_t)planners[k];
+    // SetWaypoints' dimension check, then the limits' and the initial velocity's: a planner that
+    // fails one of them goes to the device without waypoints (it keeps its state)
+    bool ok = true;
+    for (const VectorXd &w : waypoints[k])
+      if (w.size() != D) ok = false;
+    if (!ok) result[k] = InvalidArgumentError("waypoint has the wrong dimension");
+    if (ok && (max_velocity[k].size() != D || max_acceleration[k].size() != D)) {
+      result[k] = InvalidArgumentError("max_velocity / max_acceleration has the wrong dimension");
+      ok = false;
+    }
+    if (ok && !initial_velocity.empty() && initial_velocity[k].size() != D) {
+      result[k] = InvalidArgumentError("Velocity dimension doesn't match number of dofs.");
+      ok = false;
+    }
+    if (ok) {
+      for (const VectorXd &w : waypoints[k]) wps.insert(wps.end(), w.begin(), w.end());
+      for (size_t d = 0; d < D; d++) {
+        vmax[k * D + d] = max_velocity[k][d];
+        amax[k * D + d] = max_acceleration[k][d];
+        if (!initial_velocity.empty()) iv[k * D + d] = initial_velocity[k][d];
+      }
+    }
+    offsets[k + 1] = offsets[k] + (ok ? (int32_t)waypoints[k].size() : 0);
+  }
+  if (n == 0) return result;
+  const int rc = tpamd_planner_set_set_waypoints(set_, (int)n, ids.data(), offsets.data(), wps.data(), rounding,
+                                                 vmax.data(), amax.data(), dl.data(), iv.data(), np.data(), st.data());
+  if (rc != 0) return std::vector<Status>(n, rc == TPAMD_E_INVALID_ARGUMENT ? InvalidArgumentError(tpamd_error_string(rc))
+                                                                           : InternalError(tpamd_error_string(rc)));
+  for (size_t k = 0; k < n; k++) {
+    if (!result[k].ok()) continue;
+    if (st[k] == TPAMD_PLAN_OK) summary_[planners[k]].path_state = 1;      // kNewPath
+    else result[k] = InvalidArgumentError("Control point vector empty.");
+  }
+  return result;
+}
+
 Status PathTimingTrajectorySet::GetPath(size_t planner, std::vector<double> *knots,
                                         std::vector<double> *control_points) const {
   if (!init_status_.ok()) return init_status_;

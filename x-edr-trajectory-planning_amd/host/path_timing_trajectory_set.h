@@ -7,8 +7,8 @@
 // path_timing_trajectory.cc:540-577, :660-684 run on the device. Every planner ends in exactly the
 // state Plan(start, time_horizon) would have left a PathTimingTrajectory in.
 //
-// The waypoint fit stays on the host (TimeableJointSplinePath::SetWaypoints); SetPath uploads the
-// resulting spline and its state. The online switch to new waypoints runs on the device
+// New goals: SetPath uploads a spline fitted on the host (TimeableJointSplinePath::SetWaypoints), or
+// SetWaypointPaths fits the waypoints on the device, bit-identically. The online switch to new waypoints runs on the device
 // (SwitchToWaypointPaths): stop parameter, velocity at the switch time and the spline edit, with
 // no trajectory download. Splines of different sizes share a set. Trajectories come down only when
 // asked for: one planner (GetTrajectory), several in one packed download (GetTrajectories), or only
@@ -100,6 +100,22 @@ class PathTimingTrajectorySet {
   // with the PathOptions default radius (0.2).
   std::vector<Status> SwitchToWaypointPaths(const std::vector<size_t> &planners, const std::vector<Time> &time,
                                             const std::vector<std::vector<VectorXd>> &waypoints);
+  // New waypoint paths for the listed planners (each listed once), fitted on the device
+  // (tpamd_planner_set_set_waypoints): planner planners[k] ends in the state that
+  //   path->SetWaypoints(waypoints[k]) (with PathOptions rounding `rounding` and delta_parameter
+  //   `delta_parameter`); path->SetMaxJointVelocity(max_velocity[k]);
+  //   path->SetMaxJointAcceleration(max_acceleration[k]); path->SetInitialVelocity(initial_velocity[k]);
+  //   SetPath(planners[k], *path)
+  // leaves, bit for bit. initial_velocity may be empty (zero for all). One status per listed
+  // planner: a waypoint or a limit of the wrong dimension or an empty waypoint list gives
+  // InvalidArgument and leaves that planner unchanged. A planner out of range or listed twice, or
+  // vectors of the wrong length, fail the call and change nothing.
+  std::vector<Status> SetWaypointPaths(const std::vector<size_t> &planners,
+                                       const std::vector<std::vector<VectorXd>> &waypoints,
+                                       const std::vector<VectorXd> &max_velocity,
+                                       const std::vector<VectorXd> &max_acceleration,
+                                       const std::vector<VectorXd> &initial_velocity, double rounding = 0.2,
+                                       double delta_parameter = 0.005);
   // The planner's resident spline (no path: empty) and its number of control points.
   Status GetPath(size_t planner, std::vector<double> *knots, std::vector<double> *control_points) const;
   size_t NumControlPoints(size_t planner) const;
