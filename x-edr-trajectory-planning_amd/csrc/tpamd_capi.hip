@@ -47,29 +47,154 @@ struct EventPair {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// bump allocator over the staging buffer (first pass with base == null only sizes)
+// bump allocator over a device layout (with base == null it only sizes)
 struct Stage {
   char *base;
   size_t off = 0;
-  explicit Stage(void *b) : base((char *)b) {}
+  size_t align;
+  explicit Stage(void *b, size_t a = 256) : base((char *)b), align(a) {}
   template <typename T>
   T *take(size_t count) {
     T *p = base ? (T *)(base + off) : nullptr;
-    off = align_up(off + count * sizeof(T), 256);
+    off = align_up(off + count * sizeof(T), align);
     return p;
   }
+};
+
+// A device allocation that grows (free, then malloc) and does not keep its contents.
+struct DeviceBuffer {
+  void *p = nullptr;
+  size_t bytes = 0;
+  int reserve(size_t need) {
+    if (need <= bytes) return 0;
+    if (p) HIPCHK(hipFree(p));
+    p = nullptr;
+    bytes = 0;
+    HIPCHK(hipMalloc(&p, need));
+    bytes = need;
+    return 0;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// The host arrays of one call, staged in one device buffer. Each array is declared once: the
+// pointer that receives its device address, the host memory it comes from and/or goes back to,
+// its element count. upload() patches every declared pointer and queues the copies up (and the
+// zero fills) in declaration order; download() queues the copies down in order and synchronises.
+// up / down / both with a null host pointer stage nothing and yield a null device pointer; the
+// other forms always stage the array.
+// Packed: the arrays declared to go up travel in one copy of a host image of [0, end of the last of
+// them), the arrays declared to come back in one copy of their span. Tight: those spans, and
+// bytes(), end at the last array's last byte instead of the next alignment boundary.
+class HostStage {
+ public:
+  explicit HostStage(bool packed = false, bool tight = false, size_t align = 256)
+      : packed_(packed), tight_(tight), layout_(nullptr, align) {}
+
+  template <typename T> void up(T **dev, const void *host, size_t n) { add(dev, sizeof(T) * n, host, nullptr, kUp, host, false); }
+  template <typename T> void down(T **dev, void *host, size_t n) { add(dev, sizeof(T) * n, nullptr, host, kDown, host, false); }
+  template <typename T> void both(T **dev, void *host, size_t n) { add(dev, sizeof(T) * n, host, host, kUp | kDown, host, false); }
+  template <typename T> void scratch(T **dev, size_t n) { add(dev, sizeof(T) * n, nullptr, nullptr, 0, true, false); }
+  // an input the device needs either way: zero-filled when the caller passes none
+  template <typename T> void up_or_zero(T **dev, const void *host, size_t n) {
+    add(dev, sizeof(T) * n, host, nullptr, kUp, true, true);
+  }
+  // an output the kernel writes either way: copied back only if the caller asked for it
+  template <typename T> void down_or_scratch(T **dev, void *host, size_t n) {
+    add(dev, sizeof(T) * n, nullptr, host, kDown, true, false);
+  }
+  // up from `from` (or zero-filled if `from` is null and `zero`), back to `to` if that is not null
+  template <typename T> void up_down(T **dev, const void *from, void *to, size_t n, bool zero = false) {
+    add(dev, sizeof(T) * n, from, to, kUp | kDown, true, zero);
+  }
+
+  size_t bytes() const { return tight_ ? tight_end_ : layout_.off; }
+
+  int upload(DeviceBuffer &buf, hipStream_t st) {
+    if (buf.reserve(bytes())) return TPAMD_E_HIP;
+    return upload(buf.p, st);
+  }
+  int upload(void *base, hipStream_t st) {
+    base_ = (char *)base;
+    for (const Item &a : items_) {
+      char *p = a.staged ? base_ + a.off : nullptr;
+      std::memcpy(a.dev, &p, sizeof p);   // dev is the address of a T* of any T
+    }
+    if (packed_) {
+      const size_t end = span_end(up_end_);
+      if (end == 0) return 0;
+      std::vector<char> image(end, 0);
+      for (const Item &a : items_)
+        if (a.from && a.bytes) std::memcpy(image.data() + a.off, a.from, a.bytes);
+      HIPCHK(hipMemcpyAsync(base_, image.data(), end, hipMemcpyHostToDevice, st));
+      return 0;
+    }
+    for (const Item &a : items_) {
+      if (!a.bytes) continue;
+      if (a.from) HIPCHK(hipMemcpyAsync(base_ + a.off, a.from, a.bytes, hipMemcpyHostToDevice, st));
+      else if (a.zero) HIPCHK(hipMemsetAsync(base_ + a.off, 0, a.bytes, st));
+    }
+    return 0;
+  }
+  int download(hipStream_t st) {
+    if (packed_ && down_begin_ != SIZE_MAX) {
+      std::vector<char> image(span_end(down_end_) - down_begin_);
+      HIPCHK(hipMemcpyAsync(image.data(), base_ + down_begin_, image.size(), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (const Item &a : items_)
+        if (a.to && a.bytes) std::memcpy(a.to, image.data() + (a.off - down_begin_), a.bytes);
+      return 0;
+    }
+    if (!packed_)
+      for (const Item &a : items_)
+        if (a.to && a.bytes) HIPCHK(hipMemcpyAsync(a.to, base_ + a.off, a.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+
+ private:
+  struct Item {
+    void *dev;
+    const void *from;
+    void *to;
+    size_t off, bytes;
+    bool staged, zero;
+  };
+  enum { kUp = 1, kDown = 2 };
+  // An array that is not staged takes no bytes but keeps its place: a packed span that it ends,
+  // ends at its (aligned) offset.
+  void add(void *dev, size_t size, const void *from, void *to, int dir, bool staged, bool zero) {
+    const size_t bytes = staged ? size : 0;
+    const size_t off = layout_.off;
+    layout_.take<char>(bytes);
+    items_.push_back(Item{dev, from, to, off, bytes, staged, zero});
+    tight_end_ = off + bytes;
+    if (dir & kUp) up_end_ = off + bytes;
+    if (dir & kDown) {
+      down_begin_ = std::min(down_begin_, off);
+      down_end_ = off + bytes;
+    }
+  }
+  size_t span_end(size_t end) const { return tight_ ? end : align_up(end, layout_.align); }
+
+  bool packed_, tight_;
+  Stage layout_;
+  std::vector<Item> items_;
+  char *base_ = nullptr;
+  size_t tight_end_ = 0, up_end_ = 0, down_begin_ = SIZE_MAX, down_end_ = 0;
 };
 
 }  // namespace
 
 struct tpamd_engine {
   int device = 0;
-  void *ws_base = nullptr;
-  size_t ws_bytes = 0;
-  void *stage_base = nullptr;  // staging for the _host entry points
-  size_t stage_bytes = 0;
-  void *rows_base = nullptr;   // assembled constraint rows of Cartesian batches
-  size_t rows_bytes = 0;
+  DeviceBuffer ws_buf;         // the current workspace
+  DeviceBuffer stage;          // staging for the _host entry points
+  DeviceBuffer rows;           // assembled constraint rows of Cartesian batches
   Workspace ws{};
   int last_B = 0, last_N = 0;
   const double *last_time = nullptr;   // out->time of the last solve (tpamd_query_device's check)
@@ -84,17 +209,15 @@ struct tpamd_engine {
   hipStream_t sweep_stream[2] = {nullptr, nullptr};
   hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_sweep[2] = {nullptr, nullptr},
              ev_call[2] = {nullptr, nullptr};
-  void *slot_base[2] = {nullptr, nullptr};   // ws_base / ws_bytes of the slot not in use
-  size_t slot_bytes[2] = {0, 0};
-  int slot = 0;                // workspace slot e->ws_base currently refers to
+  DeviceBuffer ws_spare;       // the workspace of the slot not in use
+  int slot = 0;                // workspace slot e->ws_buf currently refers to
   // Concurrent groups (tpamd_time_joint_groups_*): each lane is a stream of the engine with a
   // workspace of its own; the groups of one call are spread over the lanes and run side by side.
   struct Lane {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     hipEvent_t front = nullptr;   // this lane's sampling/LP kernel has finished
-    void *base = nullptr;
-    size_t bytes = 0;
+    DeviceBuffer ws;
   };
   static constexpr int kMaxLanes = 8;
   Lane lanes[kMaxLanes];
@@ -127,59 +250,50 @@ namespace {
 
 // Carve the workspace for (B, N, C). Returns the bytes needed; fills ws when base != null.
 size_t carve_workspace(char *base, int B, int N, int C, Workspace *ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) -> char * {
-    char *p = base ? base + off : nullptr;
-    off = align_up(off + bytes, 256);
-    return p;
-  };
+  Stage s(base);
   const size_t nb = (size_t)B, ns = (size_t)B * N;
   Workspace w{};
-  w.ds = (double *)take(nb * 8);
-  w.s_start = (double *)take(nb * 8);
-  w.s_end = (double *)take(nb * 8);
-  w.sd_start = (double *)take(nb * 8);
-  w.sdd_start = (double *)take(nb * 8);
-  w.t_start = (double *)take(nb * 8);
-  w.delta = (double *)take(nb * 8);
-  w.err_bits = (uint32_t *)take(nb * 4);
-  w.lim = (double *)take(nb * 2 * C * 8);
+  w.ds = s.take<double>(nb);
+  w.s_start = s.take<double>(nb);
+  w.s_end = s.take<double>(nb);
+  w.sd_start = s.take<double>(nb);
+  w.sdd_start = s.take<double>(nb);
+  w.t_start = s.take<double>(nb);
+  w.delta = s.take<double>(nb);
+  w.err_bits = s.take<uint32_t>(nb);
+  w.lim = s.take<double>(nb * 2 * C);
   // + one tile of records: the sweep's tile prefetch always loads 32 whole records, so the
   // last path's partial tile reads up to 31 records past its end (tpamd_sweep_joint.h)
-  w.q12 = (double *)take((ns + kTileSamples) * (C + 2) * 8);
-  w.m0 = (double *)take(ns * 8);
-  w.z0 = (double *)take(ns * 8);
-  w.X0 = (double *)take(ns * 8);
-  w.Y0 = (double *)take(ns * 8);
-  w.Xz = (double *)take(ns * 8);
-  w.Yz = (double *)take(ns * 8);
-  w.at0 = (uint8_t *)take(ns);
-  w.fix_flag = (uint8_t *)take(ns);
-  w.fix_val = (double *)take(ns * 8);
-  w.m = (double *)take(ns * 8);
-  w.X = (double *)take(ns * 8);
-  w.Y = (double *)take(ns * 8);
-  w.type = (uint8_t *)take(ns);
-  w.sd2 = (double *)take(ns * 8);
-  w.diag = (long long *)take(nb * 64 * 8);
-  w.order = (const int32_t *)take(nb * 4);
+  w.q12 = s.take<double>((ns + kTileSamples) * (C + 2));
+  w.m0 = s.take<double>(ns);
+  w.z0 = s.take<double>(ns);
+  w.X0 = s.take<double>(ns);
+  w.Y0 = s.take<double>(ns);
+  w.Xz = s.take<double>(ns);
+  w.Yz = s.take<double>(ns);
+  w.at0 = s.take<uint8_t>(ns);
+  w.fix_flag = s.take<uint8_t>(ns);
+  w.fix_val = s.take<double>(ns);
+  w.m = s.take<double>(ns);
+  w.X = s.take<double>(ns);
+  w.Y = s.take<double>(ns);
+  w.type = s.take<uint8_t>(ns);
+  w.sd2 = s.take<double>(ns);
+  w.diag = s.take<long long>(nb * 64);
+  w.order = s.take<int32_t>(nb);
   if (ws) *ws = w;
-  return off;
+  return s.off;
 }
 
 int ensure_workspace(tpamd_engine *e, int B, int N, int C) {
   const size_t need = carve_workspace(nullptr, B, N, C, nullptr);
-  if (need > e->ws_bytes) {
-    if (e->ws_base) HIPCHK(hipFree(e->ws_base));
-    e->ws_base = nullptr;
-    e->ws_bytes = 0;
-    HIPCHK(hipMalloc(&e->ws_base, need));
-    e->ws_bytes = need;
+  if (need > e->ws_buf.bytes) {
+    if (e->ws_buf.reserve(need)) return TPAMD_E_HIP;
 #ifdef TPAMD_K1_STUDY
-    HIPCHK(hipMemset(e->ws_base, 0, need));
+    HIPCHK(hipMemset(e->ws_buf.p, 0, need));
 #endif
   }
-  carve_workspace((char *)e->ws_base, B, N, C, &e->ws);
+  carve_workspace((char *)e->ws_buf.p, B, N, C, &e->ws);
   e->ws.keep_boundary = e->keep_boundary ? 1 : 0;
 #ifdef TPAMD_K1_STUDY
   {   // study build: both workspace slots share one timestamp buffer; the slot goes along in bit 1
@@ -192,13 +306,10 @@ int ensure_workspace(tpamd_engine *e, int B, int N, int C) {
   return 0;
 }
 
-// Pipelined mode: make workspace slot `slot` the current one (e->ws_base / e->ws_bytes).
+// Pipelined mode: make workspace slot `slot` the current one (e->ws_buf).
 void select_slot(tpamd_engine *e, int slot) {
   if (slot == e->slot) return;
-  e->slot_base[e->slot] = e->ws_base;
-  e->slot_bytes[e->slot] = e->ws_bytes;
-  e->ws_base = e->slot_base[slot];
-  e->ws_bytes = e->slot_bytes[slot];
+  std::swap(e->ws_buf, e->ws_spare);
   e->slot = slot;
 }
 
@@ -231,28 +342,6 @@ struct SlotGuard {
     if (on) (void)hipEventRecord(e->ev_sweep[slot], st);
   }
 };
-
-int ensure_stage(tpamd_engine *e, size_t need) {
-  if (need > e->stage_bytes) {
-    if (e->stage_base) HIPCHK(hipFree(e->stage_base));
-    e->stage_base = nullptr;
-    e->stage_bytes = 0;
-    HIPCHK(hipMalloc(&e->stage_base, need));
-    e->stage_bytes = need;
-  }
-  return 0;
-}
-
-int ensure_rows(tpamd_engine *e, size_t need) {
-  if (need > e->rows_bytes) {
-    if (e->rows_base) HIPCHK(hipFree(e->rows_base));
-    e->rows_base = nullptr;
-    e->rows_bytes = 0;
-    HIPCHK(hipMalloc(&e->rows_base, need));
-    e->rows_bytes = need;
-  }
-  return 0;
-}
 
 constexpr size_t kMaxPendingEvents = 512;
 
@@ -569,8 +658,8 @@ void tpamd_engine_destroy(tpamd_engine *e) {
   DeviceScope scope(e->device);
   for (auto *v : {&e->events, &e->pool})
     for (auto &ev : *v) { (void)hipEventDestroy(ev.start); (void)hipEventDestroy(ev.stop); }
-  if (e->ws_base) (void)hipFree(e->ws_base);
-  if (e->slot_base[1 - e->slot]) (void)hipFree(e->slot_base[1 - e->slot]);
+  e->ws_buf.release();
+  e->ws_spare.release();
   for (int k = 0; k < 2; k++) {
     if (e->ev_front[k]) (void)hipEventDestroy(e->ev_front[k]);
     if (e->ev_sweep[k]) (void)hipEventDestroy(e->ev_sweep[k]);
@@ -582,11 +671,11 @@ void tpamd_engine_destroy(tpamd_engine *e) {
     if (ln.stream) (void)hipStreamDestroy(ln.stream);
     if (ln.done) (void)hipEventDestroy(ln.done);
     if (ln.front) (void)hipEventDestroy(ln.front);
-    if (ln.base) (void)hipFree(ln.base);
+    ln.ws.release();
   }
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->stage_base) (void)hipFree(e->stage_base);
-  if (e->rows_base) (void)hipFree(e->rows_base);
+  e->stage.release();
+  e->rows.release();
   delete e;
 }
 
@@ -601,11 +690,22 @@ int tpamd_engine_reserve(tpamd_engine *e, int B, int N, int C) {
   return rc;
 }
 
-size_t tpamd_engine_workspace_bytes(const tpamd_engine *e) { return e ? e->ws_bytes : 0; }
+size_t tpamd_engine_workspace_bytes(const tpamd_engine *e) { return e ? e->ws_buf.bytes : 0; }
 
 }  // extern "C"
 
 namespace {
+// The checks of a joint batch (after the null structs and B <= 0), shared with the _host entries.
+int joint_args(const tpamd_joint_batch *bt, const tpamd_joint_inputs *in, const tpamd_path_outputs *out) {
+  const int D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
+  if (D < 1 || D > 16 || N < 3 || N > 8192 || P < 3) return TPAMD_E_UNSUPPORTED;
+  if (!in->knots || !in->control_points || !in->max_velocity || !in->max_acceleration ||
+      !in->path_start || !in->delta || !in->sd_start || !in->time_start || !out->time ||
+      !out->s || !out->sd || !out->sdd || !out->status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+
 // The joint-space solve; `plan` (window chaining, tpamd_plan_joint_windows_host) adds two small
 // kernels: skip marks after the set-up kernel, the start-velocity projection after K1.
 int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
@@ -614,11 +714,7 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (D < 1 || D > 16 || N < 3 || N > 8192 || P < 3) return TPAMD_E_UNSUPPORTED;
-  if (!in->knots || !in->control_points || !in->max_velocity || !in->max_acceleration ||
-      !in->path_start || !in->delta || !in->sd_start || !in->time_start || !out->time ||
-      !out->s || !out->sd || !out->sdd || !out->status)
-    return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = joint_args(bt, in, out)) return rc;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = (hipStream_t)hip_stream;
   const int C = 2 * D;
@@ -767,162 +863,122 @@ int tpamd_plan_joint_windows_host(tpamd_engine *e, const tpamd_plan_args *a) {
     if (a->history_count[b] < 0 || (size_t)a->history_count[b] > cap) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_knots = s.take<double>(B * (P + 3)), *d_cp = s.take<double>(B * P * D);
-    double *d_vmax = s.take<double>(B * D), *d_amax = s.take<double>(B * D), *d_dl = s.take<double>(B);
-    double *d_iv = s.take<double>(B * D);
-    long long *d_start = s.take<long long>(B), *d_hor = s.take<long long>(B), *d_loop_start = s.take<long long>(B),
-              *d_fds = s.take<long long>(B);
-    int *d_state = s.take<int>(B), *d_count = s.take<int>(B), *d_pte = s.take<int>(B), *d_active = s.take<int>(B),
-        *d_old = s.take<int>(B), *d_off = s.take<int>(B), *d_loop = s.take<int>(B), *d_app = s.take<int>(B),
-        *d_win = s.take<int>(B), *d_status = s.take<int>(B), *d_nact = s.take<int>(1);
-    double *h_t = s.take<double>(B * cap), *h_s = s.take<double>(B * cap), *h_sd = s.take<double>(B * cap),
-           *h_sdd = s.take<double>(B * cap);
-    double *h_q = s.take<double>(B * cap * D), *h_qd = s.take<double>(B * cap * D), *h_qdd = s.take<double>(B * cap * D);
-    double *d_ph = s.take<double>(B), *d_ps = s.take<double>(B), *d_sd0 = s.take<double>(B), *d_t0 = s.take<double>(B),
-           *d_sdd0 = s.take<double>(B);
-    double *w_t = s.take<double>(B * N), *w_s = s.take<double>(B * N), *w_sd = s.take<double>(B * N),
-           *w_sdd = s.take<double>(B * N), *w_sd2 = s.take<double>(B * N);
-    double *w_q = s.take<double>(B * N * D), *w_qd = s.take<double>(B * N * D), *w_qdd = s.take<double>(B * N * D);
-    double *w_q1 = s.take<double>(B * N * D), *w_q2 = s.take<double>(B * N * D), *w_dtm = s.take<double>(B);
-    int32_t *w_lei = s.take<int32_t>(B), *w_st = s.take<int32_t>(B);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    HIPCHK(hipMemcpyAsync(d_knots, a->knots, B * (P + 3) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_cp, a->control_points, B * P * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_vmax, a->max_velocity, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_amax, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_dl, a->delta, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_iv, a->initial_velocity, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_start, a->start_ns, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_loop_start, a->resume ? a->loop_start_ns : a->start_ns, B * 8,
-                          hipMemcpyHostToDevice, st));   // :630
-    HIPCHK(hipMemcpyAsync(d_hor, a->horizon_ns, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_state, a->path_state, B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_count, a->history_count, B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pte, a->planned_to_end, B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ph, a->path_horizon, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_fds, a->final_decel_start_ns, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_t, a->history_time, B * cap * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_s, a->history_s, B * cap * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_sd, a->history_sd, B * cap * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_sdd, a->history_sdd, B * cap * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_q, a->history_q, B * cap * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_qd, a->history_qd, B * cap * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h_qdd, a->history_qdd, B * cap * D * 8, hipMemcpyHostToDevice, st));
-    // loop state: a planner loops while it has not planned to the end (:632); nothing solved yet
-    std::vector<int> act(B), zero(B, 0);
-    int n_active = 0;
-    for (size_t b = 0; b < B; b++) {
-      act[b] = a->resume ? (a->looping[b] != 0) : (a->planned_to_end[b] ? 0 : 1);
-      n_active += act[b];
-    }
-    HIPCHK(hipMemcpyAsync(d_active, act.data(), B * 4, hipMemcpyHostToDevice, st));
-    for (int *z : {d_old, d_off, d_loop, d_app, d_win, d_status})
-      HIPCHK(hipMemcpyAsync(z, zero.data(), B * 4, hipMemcpyHostToDevice, st));
-    if (a->resume) HIPCHK(hipMemcpyAsync(d_loop, a->loop_count, B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_sdd0, 0, B * 8, st));
-    HIPCHK(hipMemsetAsync(w_t, 0, B * N * 8, st));
-    HIPCHK(hipMemsetAsync(d_ps, 0, B * 8, st));
-    HIPCHK(hipMemsetAsync(d_sd0, 0, B * 8, st));
-    HIPCHK(hipMemsetAsync(d_t0, 0, B * 8, st));
-    HIPCHK(hipMemsetAsync(w_lei, 0, B * 4, st));
-    HIPCHK(hipMemsetAsync(w_dtm, 0, B * 8, st));
-    PlanParams p{};
-    p.B = (int)B; p.N = (int)N; p.D = (int)D; p.K = (int)P + 3; p.cap = (int)cap;
-    p.max_iterations = a->max_planning_iterations;
-    p.max_initial_velocity_error = a->max_initial_velocity_error;
-    p.knots = d_knots; p.delta = d_dl; p.initial_velocity = d_iv; p.start_ns = d_start; p.horizon_ns = d_hor;
-    p.path_state = d_state; p.count = d_count; p.h_time = h_t; p.h_s = h_s; p.h_sd = h_sd; p.h_sdd = h_sdd;
-    p.h_q = h_q; p.h_qd = h_qd; p.h_qdd = h_qdd; p.planned_to_end = d_pte; p.path_horizon = d_ph;
-    p.final_decel_start_ns = d_fds; p.active = d_active; p.old_state = d_old; p.offset = d_off; p.loop = d_loop;
-    p.append = d_app; p.windows = d_win; p.status = d_status; p.loop_start_ns = d_loop_start; p.num_active = d_nact;
-    p.path_start = d_ps; p.sd_start = d_sd0; p.time_start = d_t0;
-    p.w_time = w_t; p.w_s = w_s; p.w_sd = w_sd; p.w_sdd = w_sdd; p.w_q = w_q; p.w_qd = w_qd; p.w_qdd = w_qdd;
-    p.w_status = w_st; p.w_lei = w_lei;
-    tpamd_joint_batch bt{(int)B, (int)D, (int)N, (int)P, 0, 0, a->constraint_safety};
-    tpamd_joint_inputs din{d_knots, d_cp, d_vmax, d_amax, d_ps, d_dl, d_sd0, d_sdd0, d_t0, nullptr};
-    tpamd_path_outputs dout{w_t, w_s, w_sd, w_sdd, w_q, w_qd, w_qdd, w_lei, w_dtm, w_st, w_sd2};
-    const unsigned gb = (unsigned)((B + 127) / 128);
-    bool any_window = false;
-    {
+  // loop state: a planner loops while it has not planned to the end (:632); nothing solved yet
+  std::vector<int> act(B), zero(B, 0);
+  int n_active = 0;
+  for (size_t b = 0; b < B; b++) {
+    act[b] = a->resume ? (a->looping[b] != 0) : (a->planned_to_end[b] ? 0 : 1);
+    n_active += act[b];
+  }
+  PlanParams p{};
+  tpamd_joint_inputs din{};
+  tpamd_path_outputs dout{};
+  double *w_q1 = nullptr, *w_q2 = nullptr;
+  HostStage s;
+  s.up(&p.knots, a->knots, B * (P + 3));
+  s.up(&din.control_points, a->control_points, B * P * D);
+  s.up(&din.max_velocity, a->max_velocity, B * D);
+  s.up(&din.max_acceleration, a->max_acceleration, B * D);
+  s.up(&p.delta, a->delta, B);
+  s.up(&p.initial_velocity, a->initial_velocity, B * D);
+  s.up(&p.start_ns, a->start_ns, B);
+  s.up(&p.horizon_ns, a->horizon_ns, B);
+  s.up_down(&p.loop_start_ns, a->resume ? a->loop_start_ns : a->start_ns, a->loop_start_ns, B);   // :630
+  s.both(&p.final_decel_start_ns, a->final_decel_start_ns, B);
+  s.both(&p.path_state, a->path_state, B);
+  s.both(&p.count, a->history_count, B);
+  s.both(&p.planned_to_end, a->planned_to_end, B);
+  s.both(&p.path_horizon, a->path_horizon, B);
+  s.both(&p.h_time, a->history_time, B * cap);
+  s.both(&p.h_s, a->history_s, B * cap);
+  s.both(&p.h_sd, a->history_sd, B * cap);
+  s.both(&p.h_sdd, a->history_sdd, B * cap);
+  s.both(&p.h_q, a->history_q, B * cap * D);
+  s.both(&p.h_qd, a->history_qd, B * cap * D);
+  s.both(&p.h_qdd, a->history_qdd, B * cap * D);
+  s.up_down(&p.active, act.data(), act.data(), B);
+  s.up(&p.old_state, zero.data(), B);
+  s.up(&p.offset, zero.data(), B);
+  s.up_down(&p.loop, zero.data(), a->loop_count, B);
+  s.up(&p.append, zero.data(), B);
+  s.up_down(&p.windows, zero.data(), a->windows, B);
+  s.up_down(&p.status, zero.data(), a->status, B);
+  s.scratch(&p.num_active, 1);
+  s.up_down(&p.path_start, nullptr, a->window_path_start, B, /*zero=*/true);
+  s.up_down(&p.sd_start, nullptr, a->window_sd_start, B, /*zero=*/true);
+  s.up_down(&p.time_start, nullptr, a->window_time_start, B, /*zero=*/true);
+  s.up_or_zero(&din.sdd_start, nullptr, B);
+  s.up_down(&dout.time, nullptr, a->window_time, B * N, /*zero=*/true);
+  s.down(&dout.s, a->window_s, B * N);
+  s.down(&dout.sd, a->window_sd, B * N);
+  s.down(&dout.sdd, a->window_sdd, B * N);
+  s.down(&dout.sd2, a->window_sd2, B * N);
+  s.down(&dout.q, a->window_q, B * N * D);
+  s.scratch(&dout.qd, B * N * D);
+  s.scratch(&dout.qdd, B * N * D);
+  s.down(&w_q1, a->window_q1, B * N * D);
+  s.down(&w_q2, a->window_q2, B * N * D);
+  s.up_down(&dout.last_extremal_index, nullptr, a->window_last_extremal_index, B, /*zero=*/true);
+  s.up_down(&dout.max_time_increment, nullptr, a->window_max_time_increment, B, /*zero=*/true);
+  s.scratch(&dout.status, B);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  // resuming: the caller's loop counts replace the zeros
+  if (a->resume) HIPCHK(hipMemcpyAsync(p.loop, a->loop_count, B * 4, hipMemcpyHostToDevice, st));
+  p.B = (int)B; p.N = (int)N; p.D = (int)D; p.K = (int)P + 3; p.cap = (int)cap;
+  p.max_iterations = a->max_planning_iterations;
+  p.max_initial_velocity_error = a->max_initial_velocity_error;
+  p.w_time = dout.time; p.w_s = dout.s; p.w_sd = dout.sd; p.w_sdd = dout.sdd; p.w_q = dout.q; p.w_qd = dout.qd;
+  p.w_qdd = dout.qdd; p.w_status = dout.status; p.w_lei = dout.last_extremal_index;
+  din.knots = p.knots; din.path_start = p.path_start; din.delta = p.delta; din.sd_start = p.sd_start;
+  din.time_start = p.time_start;
+  tpamd_joint_batch bt{(int)B, (int)D, (int)N, (int)P, 0, 0, a->constraint_safety};
+  const unsigned gb = (unsigned)((B + 127) / 128);
+  bool any_window = false;
+  {
+    bool full = false;
+    for (size_t b = 0; b < B; b++)
+      if (act[b] && (size_t)a->history_count[b] + N > cap) full = true;
+    if (full) n_active = 0;           // reported as TPAMD_PLAN_MORE below (p.active is untouched)
+  }
+  while (n_active > 0) {
+    // every planner's history must be able to take one more window wherever it connects
+    hipLaunchKernelGGL(k_plan_begin, dim3(gb), dim3(128), 0, st, p, e->ws);
+    rc = solve_joint(e, &bt, &din, &dout, st, &p);
+    if (rc) return rc;
+    any_window = true;
+    HIPCHK(hipMemsetAsync(p.num_active, 0, 4, st));
+    hipLaunchKernelGGL(k_plan_end, dim3(gb), dim3(128), 0, st, p);
+    hipLaunchKernelGGL(k_plan_append, dim3((unsigned)((N + 127) / 128), (unsigned)B), dim3(128), 0, st, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&n_active, p.num_active, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_active > 0) {
+      // capacity for the next round: count + N must fit for every looping planner
+      std::vector<int> cnt(B), actv(B);
+      HIPCHK(hipMemcpy(cnt.data(), p.count, B * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(actv.data(), p.active, B * 4, hipMemcpyDeviceToHost));
       bool full = false;
       for (size_t b = 0; b < B; b++)
-        if (act[b] && (size_t)a->history_count[b] + N > cap) full = true;
-      if (full) n_active = 0;           // reported as TPAMD_PLAN_MORE below (d_active is untouched)
+        if (actv[b] && (size_t)cnt[b] + N > cap) full = true;
+      if (full) break;      // the caller continues with a larger history (status stays 0, planners stay looping)
     }
-    while (n_active > 0) {
-      // every planner's history must be able to take one more window wherever it connects
-      hipLaunchKernelGGL(k_plan_begin, dim3(gb), dim3(128), 0, st, p, e->ws);
-      int rc = solve_joint(e, &bt, &din, &dout, st, &p);
-      if (rc) return rc;
-      any_window = true;
-      HIPCHK(hipMemsetAsync(d_nact, 0, 4, st));
-      hipLaunchKernelGGL(k_plan_end, dim3(gb), dim3(128), 0, st, p);
-      hipLaunchKernelGGL(k_plan_append, dim3((unsigned)((N + 127) / 128), (unsigned)B), dim3(128), 0, st, p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&n_active, d_nact, 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if (n_active > 0) {
-        // capacity for the next round: count + N must fit for every looping planner
-        std::vector<int> cnt(B), actv(B);
-        HIPCHK(hipMemcpy(cnt.data(), d_count, B * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(actv.data(), d_active, B * 4, hipMemcpyDeviceToHost));
-        bool full = false;
-        for (size_t b = 0; b < B; b++)
-          if (actv[b] && (size_t)cnt[b] + N > cap) full = true;
-        if (full) break;      // the caller continues with a larger history (status stays 0, planners stay looping)
-      }
-    }
-    if (any_window) {
-      const size_t total = B * N * D;
-      hipLaunchKernelGGL(k_unpack_records, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)B, (int)N,
-                         (int)D, e->ws.q12, w_q1, w_q2);
-      HIPCHK(hipGetLastError());
-    } else {
-      HIPCHK(hipMemsetAsync(w_q1, 0, B * N * D * 8, st));
-      HIPCHK(hipMemsetAsync(w_q2, 0, B * N * D * 8, st));
-    }
-    HIPCHK(hipMemcpyAsync(a->path_state, d_state, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->planned_to_end, d_pte, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_count, d_count, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_time, h_t, B * cap * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_s, h_s, B * cap * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_sd, h_sd, B * cap * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_sdd, h_sdd, B * cap * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_q, h_q, B * cap * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_qd, h_qd, B * cap * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->history_qdd, h_qdd, B * cap * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->path_horizon, d_ph, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->final_decel_start_ns, d_fds, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_time, w_t, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_s, w_s, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_sd, w_sd, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_sdd, w_sdd, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_sd2, w_sd2, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_q, w_q, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_q1, w_q1, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_q2, w_q2, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_path_start, d_ps, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_sd_start, d_sd0, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_time_start, d_t0, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_last_extremal_index, w_lei, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->window_max_time_increment, w_dtm, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->status, d_status, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->windows, d_win, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(act.data(), d_active, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->loop_start_ns, d_loop_start, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->loop_count, d_loop, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    // planners that are still looping stopped because a history is full
-    for (size_t b = 0; b < B; b++) {
-      a->looping[b] = act[b];
-      if (a->status[b] == 0 && act[b]) a->status[b] = TPAMD_PLAN_MORE;
-    }
+  }
+  if (any_window) {
+    const size_t total = B * N * D;
+    hipLaunchKernelGGL(k_unpack_records, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)B, (int)N,
+                       (int)D, e->ws.q12, w_q1, w_q2);
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(hipMemsetAsync(w_q1, 0, B * N * D * 8, st));
+    HIPCHK(hipMemsetAsync(w_q2, 0, B * N * D * 8, st));
+  }
+  rc = s.download(st);
+  if (rc) return rc;
+  // planners that are still looping stopped because a history is full
+  for (size_t b = 0; b < B; b++) {
+    a->looping[b] = act[b];
+    if (a->status[b] == 0 && act[b]) a->status[b] = TPAMD_PLAN_MORE;
   }
   return 0;
 }
@@ -969,17 +1025,60 @@ int tpamd_engine_set_pipelining(tpamd_engine *e, int on) {
   return 0;
 }
 
+}  // extern "C"
+
+namespace {
+// The outputs of one solve in `s`; dout receives their device addresses. Every _host solve
+// entry stages its outputs this way.
+void stage_path_outputs(HostStage &s, size_t B, size_t N, size_t D, const tpamd_path_outputs *out,
+                        tpamd_path_outputs *dout) {
+  s.down(&dout->time, out->time, B * N);
+  s.down(&dout->s, out->s, B * N);
+  s.down(&dout->sd, out->sd, B * N);
+  s.down(&dout->sdd, out->sdd, B * N);
+  s.down(&dout->q, out->q, B * N * D);
+  s.down(&dout->qd, out->qd, B * N * D);
+  s.down(&dout->qdd, out->qdd, B * N * D);
+  s.down_or_scratch(&dout->last_extremal_index, out->last_extremal_index, B);
+  s.down_or_scratch(&dout->max_time_increment, out->max_time_increment, B);
+  s.down(&dout->status, out->status, B);
+  s.down(&dout->sd2, out->sd2, B * N);
+}
+
+// The checks of a rows batch after the null structs and B <= 0 (both entries).
+int rows_args(const tpamd_rows_batch *bt, const tpamd_rows_inputs *in, const tpamd_path_outputs *out) {
+  const int N = bt->num_samples, C = bt->num_rows;
+  if (C < 1 || C > 64 || N < 3 || N > 8192) return TPAMD_E_UNSUPPORTED;
+  if (!in->a || !in->b || !in->lower || !in->upper || !in->s_start || !in->s_end ||
+      !in->sd_start || !in->time_start || !out->time || !out->s || !out->sd || !out->sdd ||
+      !out->status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+
+// The checks of a Cartesian batch after the null structs and B <= 0 (both entries).
+int cartesian_args(const tpamd_cartesian_batch *bt, const tpamd_cartesian_inputs *in,
+                   const tpamd_path_outputs *out) {
+  const int D = bt->num_dofs, N = bt->num_samples;
+  if (D < 1 || D > 16 || N < 3 || N > 8192) return TPAMD_E_UNSUPPORTED;
+  if (!in->ik_positions || !in->jacobians || !in->max_velocity || !in->max_acceleration ||
+      !in->max_translational_velocity || !in->max_rotational_velocity || !in->path_start ||
+      !in->delta || !in->sd_start || !in->time_start || !out->time || !out->s || !out->sd ||
+      !out->sdd || !out->status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
 int tpamd_optimize_rows_device(tpamd_engine *e, const tpamd_rows_batch *bt,
                                const tpamd_rows_inputs *in, const tpamd_path_outputs *out,
                                void *hip_stream) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, N = bt->num_samples, C = bt->num_rows;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (C < 1 || C > 64 || N < 3 || N > 8192) return TPAMD_E_UNSUPPORTED;
-  if (!in->a || !in->b || !in->lower || !in->upper || !in->s_start || !in->s_end ||
-      !in->sd_start || !in->time_start || !out->time || !out->s || !out->sd || !out->sdd ||
-      !out->status)
-    return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = rows_args(bt, in, out)) return rc;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = (hipStream_t)hip_stream;
   SlotGuard slot_guard(e, st);
@@ -1004,12 +1103,7 @@ int tpamd_time_cartesian_paths_device(tpamd_engine *e, const tpamd_cartesian_bat
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (D < 1 || D > 16 || N < 3 || N > 8192) return TPAMD_E_UNSUPPORTED;
-  if (!in->ik_positions || !in->jacobians || !in->max_velocity || !in->max_acceleration ||
-      !in->max_translational_velocity || !in->max_rotational_velocity || !in->path_start ||
-      !in->delta || !in->sd_start || !in->time_start || !out->time || !out->s || !out->sd ||
-      !out->sdd || !out->status)
-    return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = cartesian_args(bt, in, out)) return rc;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = (hipStream_t)hip_stream;
   const int C = 2 * D + 2;
@@ -1060,12 +1154,11 @@ int tpamd_time_cartesian_paths_device(tpamd_engine *e, const tpamd_cartesian_bat
     return 0;
   }
   const size_t nrow = align_up((size_t)B * N * C * 8, 256);
-  rc = ensure_rows(e, 4 * nrow);
-  if (rc) return rc;
+  if (e->rows.reserve(4 * nrow)) return TPAMD_E_HIP;
   const Workspace &ws = e->ws;
-  double *A = (double *)e->rows_base, *Bm = (double *)((char *)e->rows_base + nrow),
-         *LO = (double *)((char *)e->rows_base + 2 * nrow),
-         *HI = (double *)((char *)e->rows_base + 3 * nrow);
+  double *A = (double *)e->rows.p, *Bm = (double *)((char *)e->rows.p + nrow),
+         *LO = (double *)((char *)e->rows.p + 2 * nrow),
+         *HI = (double *)((char *)e->rows.p + 3 * nrow);
   {
     Timer t(e, st, KI_SETUP);
     hipLaunchKernelGGL(k_cartesian_rows, dim3((N + 127) / 128, B), dim3(128), 0, st, N, D,
@@ -1094,66 +1187,32 @@ int tpamd_time_cartesian_paths_host(tpamd_engine *e, const tpamd_cartesian_batch
                                     const tpamd_path_outputs *out) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (!in->ik_positions || !in->jacobians || !in->max_velocity || !in->max_acceleration ||
-      !in->max_translational_velocity || !in->max_rotational_velocity || !in->path_start ||
-      !in->delta || !in->sd_start || !in->time_start || !out->time || !out->s || !out->sd ||
-      !out->sdd || !out->status)
-    return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = cartesian_args(bt, in, out)) return rc;
   const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_q = s.take<double>(B * N * D), *d_J = s.take<double>(B * N * 6 * D);
-    double *d_vmax = s.take<double>(B * D), *d_amax = s.take<double>(B * D);
-    double *d_vt = s.take<double>(B), *d_vr = s.take<double>(B);
-    double *d_ps = s.take<double>(B), *d_dl = s.take<double>(B), *d_sd0 = s.take<double>(B);
-    double *d_sdd0 = s.take<double>(B), *d_t0 = s.take<double>(B);
-    double *d_t = s.take<double>(B * N), *d_s = s.take<double>(B * N);
-    double *d_sd = s.take<double>(B * N), *d_sdd = s.take<double>(B * N);
-    double *d_qd = out->qd ? s.take<double>(B * N * D) : nullptr;
-    double *d_qdd = out->qdd ? s.take<double>(B * N * D) : nullptr;
-    int32_t *d_lei = s.take<int32_t>(B), *d_st = s.take<int32_t>(B);
-    double *d_dtm = s.take<double>(B);
-    double *d_sd2 = out->sd2 ? s.take<double>(B * N) : nullptr;
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_q, in->ik_positions, B * N * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_J, in->jacobians, B * N * 6 * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_vmax, in->max_velocity, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_amax, in->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_vt, in->max_translational_velocity, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_vr, in->max_rotational_velocity, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ps, in->path_start, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_dl, in->delta, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sd0, in->sd_start, B * 8, hipMemcpyHostToDevice, st));
-    if (in->sdd_start)
-      HIPCHK(hipMemcpyAsync(d_sdd0, in->sdd_start, B * 8, hipMemcpyHostToDevice, st));
-    else
-      HIPCHK(hipMemsetAsync(d_sdd0, 0, B * 8, st));
-    HIPCHK(hipMemcpyAsync(d_t0, in->time_start, B * 8, hipMemcpyHostToDevice, st));
-    tpamd_cartesian_inputs din{d_q, d_J, d_vmax, d_amax, d_vt, d_vr, d_ps, d_dl, d_sd0, d_sdd0, d_t0};
-    tpamd_path_outputs dout{d_t, d_s, d_sd, d_sdd, nullptr, d_qd, d_qdd, d_lei, d_dtm, d_st, d_sd2};
-    int rc = tpamd_time_cartesian_paths_device(e, bt, &din, &dout, st);
-    if (rc) return rc;
-    if (out->sd2) HIPCHK(hipMemcpyAsync(out->sd2, d_sd2, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->time, d_t, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->s, d_s, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->sd, d_sd, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->sdd, d_sdd, B * N * 8, hipMemcpyDeviceToHost, st));
-    if (out->qd) HIPCHK(hipMemcpyAsync(out->qd, d_qd, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    if (out->qdd) HIPCHK(hipMemcpyAsync(out->qdd, d_qdd, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    if (out->last_extremal_index)
-      HIPCHK(hipMemcpyAsync(out->last_extremal_index, d_lei, B * 4, hipMemcpyDeviceToHost, st));
-    if (out->max_time_increment)
-      HIPCHK(hipMemcpyAsync(out->max_time_increment, d_dtm, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->status, d_st, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (out->q && out->q != in->ik_positions) std::memcpy(out->q, in->ik_positions, B * N * D * 8);
-  }
+  hipStream_t st = nullptr;
+  tpamd_cartesian_inputs din{};
+  tpamd_path_outputs dout{}, staged = *out;
+  staged.q = nullptr;   // q is the caller's ik_positions: copied on the host below
+  HostStage s;
+  s.up(&din.ik_positions, in->ik_positions, B * N * D);
+  s.up(&din.jacobians, in->jacobians, B * N * 6 * D);
+  s.up(&din.max_velocity, in->max_velocity, B * D);
+  s.up(&din.max_acceleration, in->max_acceleration, B * D);
+  s.up(&din.max_translational_velocity, in->max_translational_velocity, B);
+  s.up(&din.max_rotational_velocity, in->max_rotational_velocity, B);
+  s.up(&din.path_start, in->path_start, B);
+  s.up(&din.delta, in->delta, B);
+  s.up(&din.sd_start, in->sd_start, B);
+  s.up_or_zero(&din.sdd_start, in->sdd_start, B);
+  s.up(&din.time_start, in->time_start, B);
+  stage_path_outputs(s, B, N, D, &staged, &dout);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = tpamd_time_cartesian_paths_device(e, bt, &din, &dout, st);
+  if (!rc) rc = s.download(st);
+  if (rc) return rc;
+  if (out->q && out->q != in->ik_positions) std::memcpy(out->q, in->ik_positions, B * N * D * 8);
   return 0;
 }
 
@@ -1162,74 +1221,27 @@ int tpamd_time_cartesian_paths_host(tpamd_engine *e, const tpamd_cartesian_batch
 }  // extern "C"
 
 namespace {
-// Device copies of one joint batch's host arrays inside the staging buffer.
-struct JointStage {
-  double *knots, *cp, *vmax, *amax, *ps, *dl, *sd0, *sdd0, *t0;
-  double *t, *s, *sd, *sdd, *q, *qd, *qdd, *dtm, *sd2;
-  int32_t *lei, *st, *ns;
-};
-
-void carve_joint_stage(Stage &s, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
-                       const tpamd_path_outputs *out, JointStage *j) {
+// One joint batch's host arrays in `s`.
+void stage_joint(HostStage &s, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
+                 const tpamd_path_outputs *out, tpamd_joint_inputs *din, tpamd_path_outputs *dout) {
   const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
-  j->knots = s.take<double>(B * (P + 3)); j->cp = s.take<double>(B * P * D);
-  j->vmax = s.take<double>(B * D); j->amax = s.take<double>(B * D);
-  j->ps = s.take<double>(B); j->dl = s.take<double>(B); j->sd0 = s.take<double>(B);
-  j->sdd0 = s.take<double>(B); j->t0 = s.take<double>(B);
-  j->t = s.take<double>(B * N); j->s = s.take<double>(B * N);
-  j->sd = s.take<double>(B * N); j->sdd = s.take<double>(B * N);
-  j->q = out->q ? s.take<double>(B * N * D) : nullptr;
-  j->qd = out->qd ? s.take<double>(B * N * D) : nullptr;
-  j->qdd = out->qdd ? s.take<double>(B * N * D) : nullptr;
-  j->lei = s.take<int32_t>(B); j->st = s.take<int32_t>(B);
-  j->dtm = s.take<double>(B);
-  j->sd2 = out->sd2 ? s.take<double>(B * N) : nullptr;
-  j->ns = in->num_samples_per_path ? s.take<int32_t>(B) : nullptr;
+  s.up(&din->knots, in->knots, B * (P + 3));
+  s.up(&din->control_points, in->control_points, B * P * D);
+  s.up(&din->max_velocity, in->max_velocity, B * D);
+  s.up(&din->max_acceleration, in->max_acceleration, B * D);
+  s.up(&din->path_start, in->path_start, B);
+  s.up(&din->delta, in->delta, B);
+  s.up(&din->sd_start, in->sd_start, B);
+  s.up_or_zero(&din->sdd_start, in->sdd_start, B);
+  s.up(&din->time_start, in->time_start, B);
+  s.up(&din->num_samples_per_path, in->num_samples_per_path, B);
+  stage_path_outputs(s, B, N, D, out, dout);
 }
 
-int upload_joint_stage(const JointStage &j, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
-                       hipStream_t st) {
-  const size_t B = bt->num_paths, D = bt->num_dofs, P = bt->num_points;
-  if (j.ns) HIPCHK(hipMemcpyAsync(j.ns, in->num_samples_per_path, B * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.knots, in->knots, B * (P + 3) * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.cp, in->control_points, B * P * D * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.vmax, in->max_velocity, B * D * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.amax, in->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.ps, in->path_start, B * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.dl, in->delta, B * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(j.sd0, in->sd_start, B * 8, hipMemcpyHostToDevice, st));
-  if (in->sdd_start)
-    HIPCHK(hipMemcpyAsync(j.sdd0, in->sdd_start, B * 8, hipMemcpyHostToDevice, st));
-  else
-    HIPCHK(hipMemsetAsync(j.sdd0, 0, B * 8, st));
-  HIPCHK(hipMemcpyAsync(j.t0, in->time_start, B * 8, hipMemcpyHostToDevice, st));
-  return 0;
-}
-
-int download_joint_stage(const JointStage &j, const tpamd_joint_batch *bt, const tpamd_path_outputs *out,
-                         hipStream_t st) {
-  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
-  if (out->sd2) HIPCHK(hipMemcpyAsync(out->sd2, j.sd2, B * N * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out->time, j.t, B * N * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out->s, j.s, B * N * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out->sd, j.sd, B * N * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out->sdd, j.sdd, B * N * 8, hipMemcpyDeviceToHost, st));
-  if (out->q) HIPCHK(hipMemcpyAsync(out->q, j.q, B * N * D * 8, hipMemcpyDeviceToHost, st));
-  if (out->qd) HIPCHK(hipMemcpyAsync(out->qd, j.qd, B * N * D * 8, hipMemcpyDeviceToHost, st));
-  if (out->qdd) HIPCHK(hipMemcpyAsync(out->qdd, j.qdd, B * N * D * 8, hipMemcpyDeviceToHost, st));
-  if (out->last_extremal_index)
-    HIPCHK(hipMemcpyAsync(out->last_extremal_index, j.lei, B * 4, hipMemcpyDeviceToHost, st));
-  if (out->max_time_increment)
-    HIPCHK(hipMemcpyAsync(out->max_time_increment, j.dtm, B * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out->status, j.st, B * 4, hipMemcpyDeviceToHost, st));
-  return 0;
-}
-
-bool joint_host_args_ok(const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
-                        const tpamd_path_outputs *out) {
-  return bt->num_dofs >= 1 && bt->num_samples >= 1 && bt->num_points >= 1 && in->knots &&
-         in->control_points && in->max_velocity && in->max_acceleration && in->path_start && in->delta &&
-         in->sd_start && in->time_start && out->time && out->s && out->sd && out->sdd && out->status;
+// The _host joint entries: sizes below 1 are invalid arguments, then the checks of solve_joint.
+int joint_host_args(const tpamd_joint_batch *bt, const tpamd_joint_inputs *in, const tpamd_path_outputs *out) {
+  if (bt->num_dofs < 1 || bt->num_samples < 1 || bt->num_points < 1) return TPAMD_E_INVALID_ARGUMENT;
+  return joint_args(bt, in, out);
 }
 
 // Lane k of the engine: created on first use. Lane 0 gets the highest stream priority (it is
@@ -1252,15 +1264,13 @@ int ensure_lane(tpamd_engine *e, int k) {
 template <class F>
 int with_lane_workspace(tpamd_engine *e, int k, F fn) {
   tpamd_engine::Lane &ln = e->lanes[k];
-  std::swap(e->ws_base, ln.base);
-  std::swap(e->ws_bytes, ln.bytes);
+  std::swap(e->ws_buf, ln.ws);
   const Workspace saved = e->ws;
   e->in_lane = true;
   const int rc = fn(ln.stream);
   e->in_lane = false;
   e->ws = saved;
-  std::swap(e->ws_base, ln.base);
-  std::swap(e->ws_bytes, ln.bytes);
+  std::swap(e->ws_buf, ln.ws);
   return rc;
 }
 }  // namespace
@@ -1354,71 +1364,44 @@ int tpamd_time_joint_groups_host(tpamd_engine *e, int num_groups, const tpamd_jo
   for (int g = 0; g < num_groups; g++) {
     if (batches[g].num_paths < 0) return TPAMD_E_INVALID_ARGUMENT;
     if (batches[g].num_paths == 0) continue;
-    if (!joint_host_args_ok(&batches[g], &inputs[g], &outputs[g])) return TPAMD_E_INVALID_ARGUMENT;
+    if (int rc = joint_host_args(&batches[g], &inputs[g], &outputs[g])) return rc;
     live.push_back(g);
   }
   if (live.empty()) return 0;
   TPAMD_ON_DEVICE(e);
   const size_t G = live.size();
-  std::vector<JointStage> js(G);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    for (size_t k = 0; k < G; k++) carve_joint_stage(s, &batches[live[k]], &inputs[live[k]], &outputs[live[k]], &js[k]);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-    }
-  }
   hipStream_t st = nullptr;
   std::vector<tpamd_joint_batch> bts(G);
   std::vector<tpamd_joint_inputs> dins(G);
   std::vector<tpamd_path_outputs> douts(G);
+  HostStage s;
   for (size_t k = 0; k < G; k++) {
-    const JointStage &j = js[k];
-    int rc = upload_joint_stage(j, &batches[live[k]], &inputs[live[k]], st);
-    if (rc) return rc;
     bts[k] = batches[live[k]];
-    dins[k] = tpamd_joint_inputs{j.knots, j.cp, j.vmax, j.amax, j.ps, j.dl, j.sd0, j.sdd0, j.t0, j.ns};
-    douts[k] = tpamd_path_outputs{j.t, j.s, j.sd, j.sdd, j.q, j.qd, j.qdd, j.lei, j.dtm, j.st, j.sd2};
+    stage_joint(s, &bts[k], &inputs[live[k]], &outputs[live[k]], &dins[k], &douts[k]);
   }
-  int rc = tpamd_time_joint_groups_device(e, (int)G, bts.data(), dins.data(), douts.data(), st);
+  int rc = s.upload(e->stage, st);
   if (rc) return rc;
-  for (size_t k = 0; k < G; k++) {
-    rc = download_joint_stage(js[k], &batches[live[k]], &outputs[live[k]], st);
-    if (rc) return rc;
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  rc = tpamd_time_joint_groups_device(e, (int)G, bts.data(), dins.data(), douts.data(), st);
+  return rc ? rc : s.download(st);
 }
 
 int tpamd_time_joint_paths_host(tpamd_engine *e, const tpamd_joint_batch *bt,
                                 const tpamd_joint_inputs *in, const tpamd_path_outputs *out) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (!joint_host_args_ok(bt, in, out)) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = joint_host_args(bt, in, out)) return rc;
   TPAMD_ON_DEVICE(e);
-  JointStage j{};
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    carve_joint_stage(s, bt, in, out, &j);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-    }
-  }
   hipStream_t st = nullptr;
-  int rc = upload_joint_stage(j, bt, in, st);
+  tpamd_joint_inputs din{};
+  tpamd_path_outputs dout{};
+  HostStage s;
+  stage_joint(s, bt, in, out, &din, &dout);
+  int rc = s.upload(e->stage, st);
   if (rc) return rc;
-  tpamd_joint_inputs din{j.knots, j.cp, j.vmax, j.amax, j.ps, j.dl, j.sd0, j.sdd0, j.t0, j.ns};
-  tpamd_path_outputs dout{j.t, j.s, j.sd, j.sdd, j.q, j.qd, j.qdd, j.lei, j.dtm, j.st, j.sd2};
   // never pipelined: the inputs were just queued on this stream, the outputs are copied back
   // right behind the solve, and the staging buffer is reused by the next _host call
   rc = solve_joint(e, bt, &din, &dout, st, nullptr, /*allow_pipelining=*/false);
-  if (rc) return rc;
-  rc = download_joint_stage(j, bt, out, st);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  return rc ? rc : s.download(st);
 }
 
 int tpamd_sample_joint_paths_host(tpamd_engine *e, int num_paths, int num_dofs, int num_samples,
@@ -1431,33 +1414,37 @@ int tpamd_sample_joint_paths_host(tpamd_engine *e, int num_paths, int num_dofs, 
   if (num_dofs < 1 || num_samples < 1 || num_points < 3) return TPAMD_E_UNSUPPORTED;
   const size_t B = num_paths, D = num_dofs, N = num_samples, P = num_points;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_knots = s.take<double>(B * (P + 3)), *d_cp = s.take<double>(B * P * D);
-    double *d_ps = s.take<double>(B), *d_dl = s.take<double>(B);
-    double *d_q = s.take<double>(B * N * D), *d_q1 = s.take<double>(B * N * D),
-           *d_q2 = s.take<double>(B * N * D);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_knots, knots, B * (P + 3) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_cp, control_points, B * P * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ps, path_start, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_dl, delta, B * 8, hipMemcpyHostToDevice, st));
-    const size_t lds = (P + 3 + P * D) * 8;
-    hipLaunchKernelGGL(k_sample_only, dim3((unsigned)((N + 255) / 256), (unsigned)B), dim3(256),
-                       lds, st, (int)N, (int)D, (int)P, d_knots, d_cp, d_ps, d_dl, d_q, d_q1, d_q2);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(q, d_q, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(q1, d_q1, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(q2, d_q2, B * N * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+  hipStream_t st = nullptr;
+  const double *d_knots, *d_cp, *d_ps, *d_dl;
+  double *d_q, *d_q1, *d_q2;
+  HostStage s;
+  s.up(&d_knots, knots, B * (P + 3));
+  s.up(&d_cp, control_points, B * P * D);
+  s.up(&d_ps, path_start, B);
+  s.up(&d_dl, delta, B);
+  s.down(&d_q, q, B * N * D);
+  s.down(&d_q1, q1, B * N * D);
+  s.down(&d_q2, q2, B * N * D);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  const size_t lds = (P + 3 + P * D) * 8;
+  hipLaunchKernelGGL(k_sample_only, dim3((unsigned)((N + 255) / 256), (unsigned)B), dim3(256),
+                     lds, st, (int)N, (int)D, (int)P, d_knots, d_cp, d_ps, d_dl, d_q, d_q1, d_q2);
+  HIPCHK(hipGetLastError());
+  return s.download(st);
 }
+
+}  // extern "C"
+
+namespace {
+// The sizes both pose-spline entries refuse (after their null and num_paths checks).
+int pose_spline_sizes(int num_samples, int num_points) {
+  if (num_samples < 1 || num_points < 3) return TPAMD_E_UNSUPPORTED;
+  const size_t lds = ((size_t)(num_points + 3) + 7 * (size_t)num_points) * 8;
+  return lds > 64 * 1024 ? TPAMD_E_UNSUPPORTED : 0;
+}
+}  // namespace
+
+extern "C" {
 
 int tpamd_sample_pose_splines_device(tpamd_engine *e, int num_paths, int num_samples, int num_points,
                                      const double *knots, const double *translation_points,
@@ -1466,9 +1453,8 @@ int tpamd_sample_pose_splines_device(tpamd_engine *e, int num_paths, int num_sam
   if (!e || !knots || !translation_points || !rotation_points || !path_start || !delta || !poses)
     return TPAMD_E_INVALID_ARGUMENT;
   if (num_paths <= 0) return num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (num_samples < 1 || num_points < 3) return TPAMD_E_UNSUPPORTED;
+  if (int rc = pose_spline_sizes(num_samples, num_points)) return rc;
   const size_t lds = ((size_t)(num_points + 3) + 7 * (size_t)num_points) * 8;
-  if (lds > 64 * 1024) return TPAMD_E_UNSUPPORTED;
   TPAMD_ON_DEVICE(e);
   hipLaunchKernelGGL(k_sample_pose_splines, dim3((num_samples + 255) / 256, num_paths), dim3(256), lds,
                      (hipStream_t)hip_stream, num_samples, num_points, knots, translation_points,
@@ -1484,85 +1470,51 @@ int tpamd_sample_pose_splines_host(tpamd_engine *e, int num_paths, int num_sampl
   if (!e || !knots || !translation_points || !rotation_points || !path_start || !delta || !poses)
     return TPAMD_E_INVALID_ARGUMENT;
   if (num_paths <= 0) return num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = pose_spline_sizes(num_samples, num_points)) return rc;
   const size_t B = num_paths, N = num_samples, P = num_points;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_k = s.take<double>(B * (P + 3)), *d_t = s.take<double>(B * P * 3), *d_r = s.take<double>(B * P * 4);
-    double *d_ps = s.take<double>(B), *d_dl = s.take<double>(B), *d_out = s.take<double>(B * N * 7);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_k, knots, B * (P + 3) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_t, translation_points, B * P * 3 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_r, rotation_points, B * P * 4 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ps, path_start, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_dl, delta, B * 8, hipMemcpyHostToDevice, st));
-    int rc = tpamd_sample_pose_splines_device(e, num_paths, num_samples, num_points, d_k, d_t, d_r, d_ps,
-                                              d_dl, d_out, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(poses, d_out, B * N * 7 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+  hipStream_t st = nullptr;
+  const double *d_k, *d_t, *d_r, *d_ps, *d_dl;
+  double *d_out;
+  HostStage s;
+  s.up(&d_k, knots, B * (P + 3));
+  s.up(&d_t, translation_points, B * P * 3);
+  s.up(&d_r, rotation_points, B * P * 4);
+  s.up(&d_ps, path_start, B);
+  s.up(&d_dl, delta, B);
+  s.down(&d_out, poses, B * N * 7);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = tpamd_sample_pose_splines_device(e, num_paths, num_samples, num_points, d_k, d_t, d_r, d_ps, d_dl, d_out, st);
+  return rc ? rc : s.download(st);
 }
 
 int tpamd_optimize_rows_host(tpamd_engine *e, const tpamd_rows_batch *bt,
                              const tpamd_rows_inputs *in, const tpamd_path_outputs *out) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
-  const size_t B = bt->num_paths, N = bt->num_samples, C = bt->num_rows;
   if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = rows_args(bt, in, out)) return rc;
+  const size_t B = bt->num_paths, N = bt->num_samples, C = bt->num_rows;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_a = s.take<double>(B * N * C), *d_b = s.take<double>(B * N * C);
-    double *d_lo = s.take<double>(B * N * C), *d_hi = s.take<double>(B * N * C);
-    double *d_s0 = s.take<double>(B), *d_s1 = s.take<double>(B), *d_sd0 = s.take<double>(B);
-    double *d_sdd0 = s.take<double>(B), *d_t0 = s.take<double>(B);
-    double *d_t = s.take<double>(B * N), *d_s = s.take<double>(B * N);
-    double *d_sd = s.take<double>(B * N), *d_sdd = s.take<double>(B * N);
-    int32_t *d_lei = s.take<int32_t>(B), *d_st = s.take<int32_t>(B);
-    double *d_dtm = s.take<double>(B);
-    double *d_sd2 = out->sd2 ? s.take<double>(B * N) : nullptr;
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_a, in->a, B * N * C * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_b, in->b, B * N * C * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_lo, in->lower, B * N * C * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_hi, in->upper, B * N * C * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_s0, in->s_start, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_s1, in->s_end, B * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sd0, in->sd_start, B * 8, hipMemcpyHostToDevice, st));
-    if (in->sdd_start)
-      HIPCHK(hipMemcpyAsync(d_sdd0, in->sdd_start, B * 8, hipMemcpyHostToDevice, st));
-    else
-      HIPCHK(hipMemsetAsync(d_sdd0, 0, B * 8, st));
-    HIPCHK(hipMemcpyAsync(d_t0, in->time_start, B * 8, hipMemcpyHostToDevice, st));
-    tpamd_rows_inputs din{d_a, d_b, d_lo, d_hi, d_s0, d_s1, d_sd0, d_sdd0, d_t0};
-    tpamd_path_outputs dout{d_t, d_s, d_sd, d_sdd, nullptr, nullptr, nullptr, d_lei, d_dtm, d_st,
-                            d_sd2};
-    int rc = tpamd_optimize_rows_device(e, bt, &din, &dout, st);
-    if (rc) return rc;
-    if (out->sd2) HIPCHK(hipMemcpyAsync(out->sd2, d_sd2, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->time, d_t, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->s, d_s, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->sd, d_sd, B * N * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->sdd, d_sdd, B * N * 8, hipMemcpyDeviceToHost, st));
-    if (out->last_extremal_index)
-      HIPCHK(hipMemcpyAsync(out->last_extremal_index, d_lei, B * 4, hipMemcpyDeviceToHost, st));
-    if (out->max_time_increment)
-      HIPCHK(hipMemcpyAsync(out->max_time_increment, d_dtm, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out->status, d_st, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+  hipStream_t st = nullptr;
+  tpamd_rows_inputs din{};
+  tpamd_path_outputs dout{}, staged = *out;
+  staged.q = staged.qd = staged.qdd = nullptr;   // a rows solve has no joint values
+  HostStage s;
+  s.up(&din.a, in->a, B * N * C);
+  s.up(&din.b, in->b, B * N * C);
+  s.up(&din.lower, in->lower, B * N * C);
+  s.up(&din.upper, in->upper, B * N * C);
+  s.up(&din.s_start, in->s_start, B);
+  s.up(&din.s_end, in->s_end, B);
+  s.up(&din.sd_start, in->sd_start, B);
+  s.up_or_zero(&din.sdd_start, in->sdd_start, B);
+  s.up(&din.time_start, in->time_start, B);
+  stage_path_outputs(s, B, N, 0, &staged, &dout);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = tpamd_optimize_rows_device(e, bt, &din, &dout, st);
+  return rc ? rc : s.download(st);
 }
 
 int tpamd_find_max_sd2_host(tpamd_engine *e, int num, int C, const double *a, const double *b,
@@ -1574,35 +1526,27 @@ int tpamd_find_max_sd2_host(tpamd_engine *e, int num, int C, const double *a, co
   if (C < 1 || C > 64) return TPAMD_E_UNSUPPORTED;
   TPAMD_ON_DEVICE(e);
   const size_t n = (size_t)num, nc = n * C;
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_a = s.take<double>(nc), *d_b = s.take<double>(nc), *d_lo = s.take<double>(nc),
-           *d_hi = s.take<double>(nc);
-    double *d_o0 = s.take<double>(n), *d_o1 = s.take<double>(n), *d_o2 = s.take<double>(n);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_a, a, nc * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_b, b, nc * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_lo, lower, nc * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_hi, upper, nc * 8, hipMemcpyHostToDevice, st));
-    const dim3 grid((num + 63) / 64);
-    if (C <= 32)
-      hipLaunchKernelGGL((k_lp_only<1>), grid, dim3(64), 0, st, num, C, d_a, d_b, d_lo, d_hi, d_o0,
-                         d_o1, d_o2);
-    else
-      hipLaunchKernelGGL((k_lp_only<2>), grid, dim3(64), 0, st, num, C, d_a, d_b, d_lo, d_hi, d_o0,
-                         d_o1, d_o2);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(sd2max, d_o0, n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(sddmax, d_o1, n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(sd2zero, d_o2, n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+  hipStream_t st = nullptr;
+  const double *d_a, *d_b, *d_lo, *d_hi;
+  double *d_o0, *d_o1, *d_o2;
+  HostStage s;
+  s.up(&d_a, a, nc);
+  s.up(&d_b, b, nc);
+  s.up(&d_lo, lower, nc);
+  s.up(&d_hi, upper, nc);
+  s.down(&d_o0, sd2max, n);
+  s.down(&d_o1, sddmax, n);
+  s.down(&d_o2, sd2zero, n);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  const dim3 grid((num + 63) / 64);
+  if (C <= 32)
+    hipLaunchKernelGGL((k_lp_only<1>), grid, dim3(64), 0, st, num, C, d_a, d_b, d_lo, d_hi, d_o0,
+                       d_o1, d_o2);
+  else
+    hipLaunchKernelGGL((k_lp_only<2>), grid, dim3(64), 0, st, num, C, d_a, d_b, d_lo, d_hi, d_o0,
+                       d_o1, d_o2);
+  HIPCHK(hipGetLastError());
+  return s.download(st);
 }
 
 int tpamd_rebuild_time_device(tpamd_engine *e, int num_shards, int paths_per_shard, int N,
@@ -1649,15 +1593,21 @@ int tpamd_query_device(tpamd_engine *e, int B, int N, int K, const double *time,
 }  // extern "C"
 
 namespace {
-int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_stream, bool skip_mode) {
-  if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
-  if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+// The checks of both resample entries after the null structs and num_paths <= 0.
+int resample_args(const tpamd_resample_args *a, bool skip_mode) {
   if (a->num_samples < 2 || a->num_dofs < 1 || a->max_out < 1 || !(a->time_step > 0))
     return TPAMD_E_INVALID_ARGUMENT;
   if (!a->time || !a->s || !a->sd || !a->sdd || !a->q || !a->qd || !a->qdd ||
       !a->max_acceleration || !a->start_sec || !a->out_time || !a->out_s || !a->out_sd ||
       !a->out_sdd || !a->out_q || !a->out_qd || !a->out_qdd || !a->count)
     return TPAMD_E_INVALID_ARGUMENT;
+  return skip_mode && a->num_samples > 32768 ? TPAMD_E_UNSUPPORTED : 0;
+}
+
+int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_stream, bool skip_mode) {
+  if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
+  if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = resample_args(a, skip_mode)) return rc;
   TPAMD_ON_DEVICE(e);
   ResampleParams p;
   p.B = a->num_paths; p.N = a->num_samples; p.D = a->num_dofs; p.max_out = a->max_out;
@@ -1667,7 +1617,6 @@ int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_str
   p.ot = a->out_time; p.os = a->out_s; p.osd = a->out_sd; p.osdd = a->out_sdd;
   p.oq = a->out_q; p.oqd = a->out_qd; p.oqdd = a->out_qdd; p.count = a->count;
   if (skip_mode) {
-    if (a->num_samples > 32768) return TPAMD_E_UNSUPPORTED;
     p.time_step = 0.95 * a->time_step;   // GetMinTimeDeltaToKeep, path_timing_trajectory.cc:893-900
     hipLaunchKernelGGL(k_resample_skip, dim3(a->num_paths), dim3(64), (size_t)a->num_samples * 4,
                        (hipStream_t)hip_stream, p);
@@ -1682,55 +1631,34 @@ int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_str
 int resample_host(tpamd_engine *e, const tpamd_resample_args *a, bool skip_mode) {
   if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
   if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = resample_args(a, skip_mode)) return rc;
   const size_t B = a->num_paths, N = a->num_samples, D = a->num_dofs, M = a->max_out;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_t = s.take<double>(B * N), *d_s = s.take<double>(B * N), *d_sd = s.take<double>(B * N),
-           *d_sdd = s.take<double>(B * N);
-    double *d_q = s.take<double>(B * N * D), *d_qd = s.take<double>(B * N * D),
-           *d_qdd = s.take<double>(B * N * D);
-    double *d_am = s.take<double>(B * D), *d_st = s.take<double>(B);
-    int32_t *d_status = a->status ? s.take<int32_t>(B) : nullptr;
-    double *o_t = s.take<double>(B * M), *o_s = s.take<double>(B * M), *o_sd = s.take<double>(B * M),
-           *o_sdd = s.take<double>(B * M);
-    double *o_q = s.take<double>(B * M * D), *o_qd = s.take<double>(B * M * D),
-           *o_qdd = s.take<double>(B * M * D);
-    int32_t *o_cnt = s.take<int32_t>(B);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_t, a->time, B * N * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_s, a->s, B * N * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sd, a->sd, B * N * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sdd, a->sdd, B * N * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_q, a->q, B * N * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_qd, a->qd, B * N * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_qdd, a->qdd, B * N * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_am, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_st, a->start_sec, B * 8, hipMemcpyHostToDevice, st));
-    if (d_status) HIPCHK(hipMemcpyAsync(d_status, a->status, B * 4, hipMemcpyHostToDevice, st));
-    tpamd_resample_args da = *a;
-    da.time = d_t; da.s = d_s; da.sd = d_sd; da.sdd = d_sdd; da.q = d_q; da.qd = d_qd; da.qdd = d_qdd;
-    da.max_acceleration = d_am; da.start_sec = d_st; da.status = d_status;
-    da.out_time = o_t; da.out_s = o_s; da.out_sd = o_sd; da.out_sdd = o_sdd;
-    da.out_q = o_q; da.out_qd = o_qd; da.out_qdd = o_qdd; da.count = o_cnt;
-    int rc = resample_device(e, &da, st, skip_mode);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(a->out_time, o_t, B * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_s, o_s, B * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_sd, o_sd, B * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_sdd, o_sdd, B * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_q, o_q, B * M * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_qd, o_qd, B * M * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_qdd, o_qdd, B * M * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->count, o_cnt, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+  hipStream_t st = nullptr;
+  tpamd_resample_args da = *a;
+  HostStage s;
+  s.up(&da.time, a->time, B * N);
+  s.up(&da.s, a->s, B * N);
+  s.up(&da.sd, a->sd, B * N);
+  s.up(&da.sdd, a->sdd, B * N);
+  s.up(&da.q, a->q, B * N * D);
+  s.up(&da.qd, a->qd, B * N * D);
+  s.up(&da.qdd, a->qdd, B * N * D);
+  s.up(&da.max_acceleration, a->max_acceleration, B * D);
+  s.up(&da.start_sec, a->start_sec, B);
+  s.up(&da.status, a->status, B);
+  s.down(&da.out_time, a->out_time, B * M);
+  s.down(&da.out_s, a->out_s, B * M);
+  s.down(&da.out_sd, a->out_sd, B * M);
+  s.down(&da.out_sdd, a->out_sdd, B * M);
+  s.down(&da.out_q, a->out_q, B * M * D);
+  s.down(&da.out_qd, a->out_qd, B * M * D);
+  s.down(&da.out_qdd, a->out_qdd, B * M * D);
+  s.down(&da.count, a->count, B);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = resample_device(e, &da, st, skip_mode);
+  return rc ? rc : s.download(st);
 }
 }  // namespace
 
@@ -1749,15 +1677,24 @@ int tpamd_resample_skip_host(tpamd_engine *e, const tpamd_resample_args *a) {
   return resample_host(e, a, true);
 }
 
+}  // extern "C"
+
+// The checks of both fastest-stop entries after the null structs and num_paths <= 0.
+static bool fastest_stop_args_ok(const tpamd_fastest_stop_args *a) {
+  if (a->stride < 1 || a->num_dofs < 1 || a->num_dofs > 16) return false;
+  if (!a->time || !a->s || !a->qd || !a->qdd || !a->max_acceleration || !a->query_time ||
+      !a->stop_parameter || !a->stop_index || !a->duration || !a->status)
+    return false;
+  const int np = (a->profile_time != nullptr) + (a->profile_rate2 != nullptr) + (a->profile_drate2 != nullptr);
+  return np == 0 || np == 3;
+}
+
+extern "C" {
+
 int tpamd_fastest_stop_device(tpamd_engine *e, const tpamd_fastest_stop_args *a, void *hip_stream) {
   if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
   if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (a->stride < 1 || a->num_dofs < 1 || a->num_dofs > 16) return TPAMD_E_INVALID_ARGUMENT;
-  if (!a->time || !a->s || !a->qd || !a->qdd || !a->max_acceleration || !a->query_time ||
-      !a->stop_parameter || !a->stop_index || !a->duration || !a->status)
-    return TPAMD_E_INVALID_ARGUMENT;
-  const int np = (a->profile_time != nullptr) + (a->profile_rate2 != nullptr) + (a->profile_drate2 != nullptr);
-  if (np != 0 && np != 3) return TPAMD_E_INVALID_ARGUMENT;
+  if (!fastest_stop_args_ok(a)) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(e);
   FastestStopParams p{};
   p.Q = a->num_paths; p.stride = a->stride;
@@ -1773,64 +1710,32 @@ int tpamd_fastest_stop_device(tpamd_engine *e, const tpamd_fastest_stop_args *a,
 int tpamd_fastest_stop_host(tpamd_engine *e, const tpamd_fastest_stop_args *a) {
   if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
   if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (a->stride < 1 || a->num_dofs < 1 || a->num_dofs > 16) return TPAMD_E_INVALID_ARGUMENT;
-  if (!a->time || !a->s || !a->qd || !a->qdd || !a->max_acceleration || !a->query_time ||
-      !a->stop_parameter || !a->stop_index || !a->duration || !a->status)
-    return TPAMD_E_INVALID_ARGUMENT;
-  const bool prof = a->profile_time != nullptr;
-  const int np = prof + (a->profile_rate2 != nullptr) + (a->profile_drate2 != nullptr);
-  if (np != 0 && np != 3) return TPAMD_E_INVALID_ARGUMENT;
+  if (!fastest_stop_args_ok(a)) return TPAMD_E_INVALID_ARGUMENT;
   const size_t B = a->num_paths, M = a->stride, D = a->num_dofs;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_t = s.take<double>(B * M), *d_s = s.take<double>(B * M);
-    double *d_qd = s.take<double>(B * M * D), *d_qdd = s.take<double>(B * M * D);
-    int32_t *d_cnt = a->count ? s.take<int32_t>(B) : nullptr;
-    double *d_am = s.take<double>(B * D), *d_q = s.take<double>(B);
-    double *o_s = s.take<double>(B), *o_dur = s.take<double>(B);
-    int32_t *o_idx = s.take<int32_t>(B), *o_st = s.take<int32_t>(B);
-    double *o_pt = prof ? s.take<double>(B * M) : nullptr, *o_pr = prof ? s.take<double>(B * M) : nullptr,
-           *o_pd = prof ? s.take<double>(B * M) : nullptr;
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_t, a->time, B * M * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_s, a->s, B * M * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_qd, a->qd, B * M * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_qdd, a->qdd, B * M * D * 8, hipMemcpyHostToDevice, st));
-    if (d_cnt) HIPCHK(hipMemcpyAsync(d_cnt, a->count, B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_am, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_q, a->query_time, B * 8, hipMemcpyHostToDevice, st));
-    if (prof) {
-      // the kernel writes a prefix of each profile row; the rest must come back as the caller
-      // had it (as with the device entry), not as an earlier host call left the staging buffer
-      HIPCHK(hipMemcpyAsync(o_pt, a->profile_time, B * M * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(o_pr, a->profile_rate2, B * M * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(o_pd, a->profile_drate2, B * M * 8, hipMemcpyHostToDevice, st));
-    }
-    tpamd_fastest_stop_args da = *a;
-    da.time = d_t; da.s = d_s; da.qd = d_qd; da.qdd = d_qdd; da.count = d_cnt;
-    da.max_acceleration = d_am; da.query_time = d_q;
-    da.stop_parameter = o_s; da.stop_index = o_idx; da.duration = o_dur; da.status = o_st;
-    da.profile_time = o_pt; da.profile_rate2 = o_pr; da.profile_drate2 = o_pd;
-    int rc = tpamd_fastest_stop_device(e, &da, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(a->stop_parameter, o_s, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->stop_index, o_idx, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->duration, o_dur, B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->status, o_st, B * 4, hipMemcpyDeviceToHost, st));
-    if (prof) {
-      HIPCHK(hipMemcpyAsync(a->profile_time, o_pt, B * M * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(a->profile_rate2, o_pr, B * M * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(a->profile_drate2, o_pd, B * M * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+  hipStream_t st = nullptr;
+  tpamd_fastest_stop_args da = *a;
+  HostStage s;
+  s.up(&da.time, a->time, B * M);
+  s.up(&da.s, a->s, B * M);
+  s.up(&da.qd, a->qd, B * M * D);
+  s.up(&da.qdd, a->qdd, B * M * D);
+  s.up(&da.count, a->count, B);
+  s.up(&da.max_acceleration, a->max_acceleration, B * D);
+  s.up(&da.query_time, a->query_time, B);
+  s.down(&da.stop_parameter, a->stop_parameter, B);
+  s.down(&da.stop_index, a->stop_index, B);
+  s.down(&da.duration, a->duration, B);
+  s.down(&da.status, a->status, B);
+  // the kernel writes a prefix of each profile row; the rest must come back as the caller
+  // had it (as with the device entry), not as an earlier host call left the staging buffer
+  s.both(&da.profile_time, a->profile_time, B * M);
+  s.both(&da.profile_rate2, a->profile_rate2, B * M);
+  s.both(&da.profile_drate2, a->profile_drate2, B * M);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = tpamd_fastest_stop_device(e, &da, st);
+  return rc ? rc : s.download(st);
 }
 
 int tpamd_debug_copy_boundary(tpamd_engine *e, int B, int N, double *sd2_max, double *sdd_max,
@@ -1929,50 +1834,33 @@ int tpamd_stop_trajectories_host(tpamd_engine *e, const tpamd_stop_trajectory_ar
   if (!stop_batch_args_ok(a)) return TPAMD_E_INVALID_ARGUMENT;
   const size_t B = a->num_paths, M = a->stride, D = a->num_dofs;
   TPAMD_ON_DEVICE(e);
-  for (int pass = 0; pass < 2; pass++) {
-    Stage s(pass ? e->stage_base : nullptr);
-    double *d_t = s.take<double>(B * M), *d_qd = s.take<double>(B * M * D), *d_qdd = s.take<double>(B * M * D);
-    int32_t *d_cnt = a->count ? s.take<int32_t>(B) : nullptr;
-    double *d_am = s.take<double>(B * D);
-    double *d_st = a->stop_index ? nullptr : s.take<double>(B);
-    int32_t *d_si = a->stop_index ? s.take<int32_t>(B) : nullptr;
-    int32_t *o_res = s.take<int32_t>(4 * B);
-    double *o_t = s.take<double>(B * M), *o_qd = s.take<double>(B * M * D), *o_qdd = s.take<double>(B * M * D);
-    if (!pass) {
-      int rc = ensure_stage(e, s.off);
-      if (rc) return rc;
-      continue;
-    }
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_t, a->time, B * M * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_qd, a->qd, B * M * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_qdd, a->qdd, B * M * D * 8, hipMemcpyHostToDevice, st));
-    if (d_cnt) HIPCHK(hipMemcpyAsync(d_cnt, a->count, B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_am, a->max_acceleration, B * D * 8, hipMemcpyHostToDevice, st));
-    if (d_st) HIPCHK(hipMemcpyAsync(d_st, a->stop_time, B * 8, hipMemcpyHostToDevice, st));
-    if (d_si) HIPCHK(hipMemcpyAsync(d_si, a->stop_index, B * 4, hipMemcpyHostToDevice, st));
-    // only the segments' rows are written; the rest must come back as the caller had it
-    HIPCHK(hipMemcpyAsync(o_t, a->out_time, B * M * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(o_qd, a->out_qd, B * M * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(o_qdd, a->out_qdd, B * M * D * 8, hipMemcpyHostToDevice, st));
-    tpamd_stop_trajectory_args da = *a;
-    da.time = d_t; da.qd = d_qd; da.qdd = d_qdd; da.count = d_cnt; da.max_acceleration = d_am;
-    da.stop_time = d_st; da.stop_index = d_si;
-    da.status = o_res; da.keep = o_res + B; da.first = o_res + 2 * B; da.last = o_res + 3 * B;
-    da.out_time = o_t; da.out_qd = o_qd; da.out_qdd = o_qdd;
-    int rc = tpamd_stop_trajectories_device(e, &da, st);
-    if (rc) return rc;
-    std::vector<int32_t> res(4 * B);
-    HIPCHK(hipMemcpyAsync(res.data(), o_res, 16 * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_time, o_t, B * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_qd, o_qd, B * M * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(a->out_qdd, o_qdd, B * M * D * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::memcpy(a->status, res.data(), 4 * B);
-    std::memcpy(a->keep, res.data() + B, 4 * B);
-    std::memcpy(a->first, res.data() + 2 * B, 4 * B);
-    std::memcpy(a->last, res.data() + 3 * B, 4 * B);
-  }
+  hipStream_t st = nullptr;
+  tpamd_stop_trajectory_args da = *a;
+  std::vector<int32_t> res(4 * B);   // status, keep, first, last: one copy down
+  int32_t *d_res = nullptr;
+  HostStage s;
+  s.up(&da.time, a->time, B * M);
+  s.up(&da.qd, a->qd, B * M * D);
+  s.up(&da.qdd, a->qdd, B * M * D);
+  s.up(&da.count, a->count, B);
+  s.up(&da.max_acceleration, a->max_acceleration, B * D);
+  s.up(&da.stop_time, a->stop_index ? nullptr : a->stop_time, B);
+  s.up(&da.stop_index, a->stop_index, B);
+  s.down(&d_res, res.data(), 4 * B);
+  // only the segments' rows are written; the rest must come back as the caller had it
+  s.both(&da.out_time, a->out_time, B * M);
+  s.both(&da.out_qd, a->out_qd, B * M * D);
+  s.both(&da.out_qdd, a->out_qdd, B * M * D);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  da.status = d_res; da.keep = d_res + B; da.first = d_res + 2 * B; da.last = d_res + 3 * B;
+  rc = tpamd_stop_trajectories_device(e, &da, st);
+  if (!rc) rc = s.download(st);
+  if (rc) return rc;
+  std::memcpy(a->status, res.data(), 4 * B);
+  std::memcpy(a->keep, res.data() + B, 4 * B);
+  std::memcpy(a->first, res.data() + 2 * B, 4 * B);
+  std::memcpy(a->last, res.data() + 3 * B, 4 * B);
   return 0;
 }
 
@@ -1989,8 +1877,7 @@ struct tpamd_planner_set {
   // host copies of S.np and S.has_path: they change only through uploads, switches and resets
   std::vector<int> h_np;
   std::vector<char> h_has;
-  void *sw_buf = nullptr;               // switch calls: inputs, outputs and the edit's scratch
-  size_t sw_bytes = 0;
+  DeviceBuffer sw_buf;                  // switch calls: inputs, outputs and the edit's scratch
   PlannerSetState S{};
   PlanParams P{};
   // device arrays that are not part of S / P
@@ -2004,20 +1891,19 @@ struct tpamd_planner_set {
   char *d_stop_in = nullptr, *d_stop_out = nullptr;   // stop queries: [time_ns][ids], [s][duration][status]
   size_t last_h2d = 0, last_d2h = 0;
   // staging of the host readouts (inputs and offsets | packed rows or tick values); they grow
-  void *rd_in = nullptr, *rd_out = nullptr;
-  size_t rd_in_bytes = 0, rd_out_bytes = 0;
+  DeviceBuffer rd_in, rd_out;
   // device readouts run on the caller's stream: ev_set orders them after the set's last change,
   // ev_read (recorded after each of them) orders the next change after them
   hipEvent_t ev_set = nullptr, ev_read = nullptr;
   bool read_pending = false;
   // stopping trajectories: per-listed-planner scratch (segment rows, shift, length; host variant:
   // status, keep, offsets as well)
-  void *stop_buf = nullptr;
-  size_t stop_bytes = 0;
+  DeviceBuffer stop_buf;
   // set_waypoints calls: device inputs and outputs; the _device variant stages ids and offsets in
   // pinned memory, which ev_wp (recorded after their copy) guards against the next call
-  void *wp_buf = nullptr, *wp_pin = nullptr;
-  size_t wp_bytes = 0, wp_pin_bytes = 0;
+  DeviceBuffer wp_buf;
+  void *wp_pin = nullptr;
+  size_t wp_pin_bytes = 0;
   hipEvent_t ev_wp = nullptr;
   bool wp_pin_busy = false;
 };
@@ -2026,31 +1912,30 @@ namespace {
 
 // knots [B][pcap + 3] | control points [B][pcap][D]
 size_t carve_paths(char *base, size_t B, size_t pcap, size_t D, tpamd_planner_set *ps) {
-  size_t off = 0;
-  auto take = [&](size_t n) { double *p = base ? (double *)(base + off) : nullptr; off = align_up(off + n * 8, 256); return p; };
-  double *k = take(B * (pcap + 3)), *cp = take(B * pcap * D);
+  Stage st(base);
+  double *k = st.take<double>(B * (pcap + 3)), *cp = st.take<double>(B * pcap * D);
   if (ps) { ps->S.knots = k; ps->d_cp = cp; ps->S.K = (int)pcap + 3; }
-  return off;
+  return st.off;
 }
 size_t carve_history(char *base, size_t B, size_t cap, size_t D, tpamd_planner_set *ps) {
-  size_t off = 0;
-  auto take = [&](size_t n) { double *p = base ? (double *)(base + off) : nullptr; off = align_up(off + n * 8, 256); return p; };
-  double *t = take(B * cap), *s = take(B * cap), *sd = take(B * cap), *sdd = take(B * cap);
-  double *q = take(B * cap * D), *qd = take(B * cap * D), *qdd = take(B * cap * D);
+  Stage st(base);
+  double *t = st.take<double>(B * cap), *s = st.take<double>(B * cap), *sd = st.take<double>(B * cap),
+         *sdd = st.take<double>(B * cap);
+  double *q = st.take<double>(B * cap * D), *qd = st.take<double>(B * cap * D), *qdd = st.take<double>(B * cap * D);
   if (ps) {
     ps->S.h_time = t; ps->S.h_s = s; ps->S.h_sd = sd; ps->S.h_sdd = sdd; ps->S.h_q = q; ps->S.h_qd = qd; ps->S.h_qdd = qdd;
   }
-  return off;
+  return st.off;
 }
 size_t carve_trajectory(char *base, size_t B, size_t tcap, size_t D, tpamd_planner_set *ps) {
-  size_t off = 0;
-  auto take = [&](size_t n) { double *p = base ? (double *)(base + off) : nullptr; off = align_up(off + n * 8, 256); return p; };
-  double *t = take(B * tcap), *s = take(B * tcap), *sd = take(B * tcap), *sdd = take(B * tcap);
-  double *q = take(B * tcap * D), *qd = take(B * tcap * D), *qdd = take(B * tcap * D);
+  Stage st(base);
+  double *t = st.take<double>(B * tcap), *s = st.take<double>(B * tcap), *sd = st.take<double>(B * tcap),
+         *sdd = st.take<double>(B * tcap);
+  double *q = st.take<double>(B * tcap * D), *qd = st.take<double>(B * tcap * D), *qdd = st.take<double>(B * tcap * D);
   if (ps) {
     ps->S.t_time = t; ps->S.t_s = s; ps->S.t_sd = sd; ps->S.t_sdd = sdd; ps->S.t_q = q; ps->S.t_qd = qd; ps->S.t_qdd = qdd;
   }
-  return off;
+  return st.off;
 }
 
 // PlanParams view of the set (the window-loop kernels of tpamd_kernels.h)
@@ -2162,17 +2047,6 @@ int readout_end(tpamd_planner_set *ps, hipStream_t st) {
   return 0;
 }
 
-// Grow a staging buffer of the host readouts to at least `bytes` (contents are not kept).
-int ensure_staging(void **buf, size_t *have, size_t bytes) {
-  if (bytes <= *have) return 0;
-  if (*buf) HIPCHK(hipFree(*buf));
-  *buf = nullptr;
-  *have = 0;
-  HIPCHK(hipMalloc(buf, bytes));
-  *have = bytes;
-  return 0;
-}
-
 // ReadoutParams view of the set's resident trajectories
 ReadoutParams readout_params(const tpamd_planner_set *ps) {
   const PlannerSetState &S = ps->S;
@@ -2213,9 +2087,9 @@ bool stop_args_ok(const tpamd_planner_set *ps, int count, const int32_t *ids, bo
 
 // Grow the stop scratch; a device stop still in flight may be using the old one.
 int ensure_stop_buf(tpamd_planner_set *ps, size_t bytes) {
-  if (bytes <= ps->stop_bytes) return 0;
+  if (bytes <= ps->stop_buf.bytes) return 0;
   if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
-  return ensure_staging(&ps->stop_buf, &ps->stop_bytes, bytes);
+  return ps->stop_buf.reserve(bytes);
 }
 
 // StopTrajParams view of the set's resident trajectories
@@ -2397,23 +2271,23 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (ps->read_pending) (void)hipEventSynchronize(ps->ev_read);   // a device readout may still read the set
   if (ps->ev_set) (void)hipEventDestroy(ps->ev_set);
   if (ps->ev_read) (void)hipEventDestroy(ps->ev_read);
-  if (ps->rd_in) (void)hipFree(ps->rd_in);
-  if (ps->rd_out) (void)hipFree(ps->rd_out);
-  if (ps->stop_buf) (void)hipFree(ps->stop_buf);
+  ps->rd_in.release();
+  ps->rd_out.release();
+  ps->stop_buf.release();
   if (ps->fixed) (void)hipFree(ps->fixed);
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
   if (ps->path) (void)hipFree(ps->path);
-  if (ps->sw_buf) (void)hipFree(ps->sw_buf);
-  if (ps->wp_buf) (void)hipFree(ps->wp_buf);
+  ps->sw_buf.release();
+  ps->wp_buf.release();
   if (ps->wp_pin) (void)hipHostFree(ps->wp_pin);
   if (ps->ev_wp) (void)hipEventDestroy(ps->ev_wp);
   delete ps;
 }
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
-  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_bytes + ps->rd_in_bytes +
-                   ps->rd_out_bytes + ps->stop_bytes + ps->wp_bytes
+  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_buf.bytes +
+                   ps->rd_in.bytes + ps->rd_out.bytes + ps->stop_buf.bytes + ps->wp_buf.bytes
             : 0;
 }
 
@@ -2595,29 +2469,24 @@ int tpamd_planner_set_stop_parameters(tpamd_planner_set *ps, int count, const in
   if (count == 0) return 0;
   TPAMD_ON_DEVICE(ps->e);
   const size_t n = (size_t)count;
-  // one copy up ([time_ns][ids]), one launch, one copy down ([s][duration][status])
-  std::vector<char> in(n * (ids ? 12 : 8)), out(n * 20);
-  std::memcpy(in.data(), time_ns, n * 8);
-  if (ids) std::memcpy(in.data() + n * 8, ids, n * 4);
   hipStream_t st = nullptr;
-  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // the limits of a device set_waypoints
-  HIPCHK(hipMemcpyAsync(ps->d_stop_in, in.data(), in.size(), hipMemcpyHostToDevice, st));
+  // one copy up ([time_ns][ids]), one launch, one copy down ([s][duration][status]), unpadded
   FastestStopParams p{};
+  HostStage in(/*packed=*/true, /*tight=*/true, /*align=*/1), out(/*packed=*/true, /*tight=*/true, /*align=*/1);
+  in.up(&p.query_ns, time_ns, n);
+  in.up(&p.ids, ids, n);
+  out.down(&p.stop_s, stop_parameter, n);
+  out.down_or_scratch(&p.duration, duration, n);
+  out.down(&p.status, status, n);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // the limits of a device set_waypoints
+  if (in.upload(ps->d_stop_in, st) || out.upload(ps->d_stop_out, st)) return TPAMD_E_HIP;
   p.Q = count; p.stride = ps->tcap;
   p.time = S.t_time; p.s = S.t_s; p.qd = S.t_qd; p.qdd = S.t_qdd;
   p.count = S.t_count; p.first = S.t_first; p.initial_plan = S.initial_plan;
-  p.ids = ids ? (const int *)(ps->d_stop_in + n * 8) : nullptr;
-  p.amax = S.amax; p.query_ns = (const long long *)ps->d_stop_in;
-  p.stop_s = (double *)ps->d_stop_out; p.duration = (double *)(ps->d_stop_out + n * 8);
-  p.status = (int *)(ps->d_stop_out + n * 16);
+  p.amax = S.amax;
   if (!launch_fastest_stop(S.D, p, st)) return TPAMD_E_UNSUPPORTED;
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out.data(), ps->d_stop_out, out.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(stop_parameter, out.data(), n * 8);
-  if (duration) std::memcpy(duration, out.data() + n * 8, n * 8);
-  std::memcpy(status, out.data() + n * 16, n * 4);
-  return 0;
+  return out.download(st);
 }
 
 }  // extern "C"
@@ -2663,58 +2532,40 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
   const size_t per_query = (size_t)scr_points + 3 + (size_t)scr_points * D + scr_work;
   // device buffer: in [time_ns][keep][ids][offsets][waypoints] | out [stop][num_points][status] |
   // stop status | scratch
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_time = take(n * 8), o_keep = take(keep_path_until ? n * 8 : 0), o_ids = take(n * 4),
-               o_off = take((n + 1) * 4), o_wps = take(rows * D * 8);
-  const size_t in_end = off;
-  const size_t o_stop = take(n * 8), o_np = take(n * 4), o_status = take(n * 4);
-  const size_t out_begin = o_stop, out_end = off;
-  const size_t o_stop_status = take(n * 4), o_scr = take(n * per_query * 8);
-  if (off > ps->sw_bytes) {
-    if (ps->sw_buf) HIPCHK(hipFree(ps->sw_buf));
-    ps->sw_buf = nullptr;
-    ps->sw_bytes = 0;
-    HIPCHK(hipMalloc(&ps->sw_buf, off));
-    ps->sw_bytes = off;
-  }
-  char *base = (char *)ps->sw_buf;
-  std::vector<char> in(in_end, 0), out(out_end - out_begin);
-  std::memcpy(in.data() + o_time, time_ns, n * 8);
-  if (keep_path_until) std::memcpy(in.data() + o_keep, keep_path_until, n * 8);
-  std::memcpy(in.data() + o_ids, id.data(), n * 4);
-  std::memcpy(in.data() + o_off, waypoint_offsets, (n + 1) * 4);
-  if (rows) std::memcpy(in.data() + o_wps, waypoints, rows * D * 8);
-  HIPCHK(hipMemcpyAsync(base, in.data(), in_end, hipMemcpyHostToDevice, st));
+  SwitchParams p{};
+  HostStage s(/*packed=*/true);
+  s.up(&p.time_ns, time_ns, n);
+  s.up(&p.keep, keep_path_until, n);
+  s.up(&p.ids, id.data(), n);
+  s.up(&p.offsets, waypoint_offsets, n + 1);
+  s.up(&p.wps, waypoints, rows * D);
+  s.down(&p.stop_out, stop_parameter, n);
+  s.down(&p.np_out, num_points, n);
+  s.down(&p.status_out, status, n);
+  s.scratch(&p.stop_status, n);
+  s.scratch(&p.scr, n * per_query);
+  rc = s.upload(ps->sw_buf, st);
+  if (rc) return rc;
+  p.stop_in = p.stop_out;
   if (!keep_path_until) {       // GetPathStopParameter(time) on the resident trajectories
     FastestStopParams f{};
     f.Q = count; f.stride = ps->tcap;
     f.time = S.t_time; f.s = S.t_s; f.qd = S.t_qd; f.qdd = S.t_qdd;
     f.count = S.t_count; f.first = S.t_first; f.initial_plan = S.initial_plan;
-    f.ids = (const int *)(base + o_ids);
-    f.amax = S.amax; f.query_ns = (const long long *)(base + o_time);
-    f.stop_s = (double *)(base + o_stop); f.status = (int *)(base + o_stop_status);
+    f.ids = p.ids;
+    f.amax = S.amax; f.query_ns = p.time_ns;
+    f.stop_s = p.stop_out; f.status = (int *)p.stop_status;
     if (!launch_fastest_stop((int)D, f, st)) return TPAMD_E_UNSUPPORTED;
   }
-  SwitchParams p{};
   p.Q = count; p.D = (int)D; p.K = S.K; p.pcap = ps->pcap; p.tcap = ps->tcap;
   p.scr_points = scr_points; p.scr_work = scr_work;
-  p.ids = (const int *)(base + o_ids); p.time_ns = (const long long *)(base + o_time);
-  p.keep = keep_path_until ? (const double *)(base + o_keep) : nullptr;
-  p.stop_in = (const double *)(base + o_stop); p.stop_status = (const int *)(base + o_stop_status);
-  p.offsets = (const int *)(base + o_off); p.wps = (const double *)(base + o_wps);
   p.knots = (double *)S.knots; p.cps = ps->d_cp; p.iv = ps->d_iv; p.np = S.np; p.path_state = S.path_state;
   p.has_path = S.has_path; p.initial_plan = S.initial_plan; p.t_first = S.t_first; p.t_count = S.t_count;
   p.t_time = S.t_time; p.t_qd = S.t_qd;
-  p.scr = (double *)(base + o_scr);
-  p.stop_out = (double *)(base + o_stop); p.np_out = (int *)(base + o_np); p.status_out = (int *)(base + o_status);
   hipLaunchKernelGGL(k_pset_switch, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out.data(), base + out_begin, out.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(stop_parameter, out.data() + (o_stop - out_begin), n * 8);
-  std::memcpy(num_points, out.data() + (o_np - out_begin), n * 4);
-  std::memcpy(status, out.data() + (o_status - out_begin), n * 4);
+  rc = s.download(st);
+  if (rc) return rc;
   for (size_t k = 0; k < n; k++)
     if (status[k] == TPAMD_PLAN_OK) ps->h_np[id[k]] = num_points[k];
   return 0;
@@ -2754,9 +2605,9 @@ int waypoint_args(const tpamd_planner_set *ps, int count, const int32_t *ids, co
 
 // Grow the set_waypoints device buffer (contents are not kept); a device call in flight may use it.
 int ensure_wp_buf(tpamd_planner_set *ps, size_t bytes) {
-  if (bytes <= ps->wp_bytes) return 0;
+  if (bytes <= ps->wp_buf.bytes) return 0;
   if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
-  return ensure_staging(&ps->wp_buf, &ps->wp_bytes, bytes);
+  return ps->wp_buf.reserve(bytes);
 }
 
 FitParams fit_params(const tpamd_planner_set *ps, int count, double rounding) {
@@ -2797,38 +2648,27 @@ int tpamd_planner_set_set_waypoints(tpamd_planner_set *ps, int count, const int3
   hipStream_t st = nullptr;
   const size_t n = (size_t)count, D = ps->S.D, rows = (size_t)waypoint_offsets[count];
   // device buffer: in [ids][offsets][waypoints][vmax][amax][delta][iv] | out [num_points][status]
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_ids = take(n * 4), o_off = take((n + 1) * 4), o_wps = take(rows * D * 8), o_vmax = take(n * D * 8),
-               o_amax = take(n * D * 8), o_delta = take(n * 8), o_iv = take(initial_velocity ? n * D * 8 : 0);
-  const size_t in_end = off;
-  const size_t o_np = take(n * 4), o_status = take(n * 4);
-  if (ensure_wp_buf(ps, off)) return TPAMD_E_HIP;
+  FitParams p{};
+  HostStage s(/*packed=*/true);
+  s.up(&p.ids, id.data(), n);
+  s.up(&p.offsets, waypoint_offsets, n + 1);
+  s.up(&p.wps, waypoints, rows * D);
+  s.up(&p.vmax, max_velocity, n * D);
+  s.up(&p.amax, max_acceleration, n * D);
+  s.up(&p.delta, delta, n);
+  s.up(&p.iv, initial_velocity, n * D);
+  s.down_or_scratch(&p.np_out, num_points, n);
+  s.down(&p.status_out, status, n);
+  if (ensure_wp_buf(ps, s.bytes())) return TPAMD_E_HIP;
   if (order_after_readouts(ps)) return TPAMD_E_HIP;
   rc = ensure_pcap(ps, need, st);
   if (rc) return rc;
-  std::vector<char> in(in_end, 0), out(off - o_np);
-  std::memcpy(in.data() + o_ids, id.data(), n * 4);
-  std::memcpy(in.data() + o_off, waypoint_offsets, (n + 1) * 4);
-  if (rows) std::memcpy(in.data() + o_wps, waypoints, rows * D * 8);
-  std::memcpy(in.data() + o_vmax, max_velocity, n * D * 8);
-  std::memcpy(in.data() + o_amax, max_acceleration, n * D * 8);
-  std::memcpy(in.data() + o_delta, delta, n * 8);
-  if (initial_velocity) std::memcpy(in.data() + o_iv, initial_velocity, n * D * 8);
-  char *base = (char *)ps->wp_buf;
-  HIPCHK(hipMemcpyAsync(base, in.data(), in_end, hipMemcpyHostToDevice, st));
-  FitParams p = fit_params(ps, count, rounding);
-  p.ids = (const int *)(base + o_ids); p.offsets = (const int *)(base + o_off);
-  p.wps = (const double *)(base + o_wps); p.vmax = (const double *)(base + o_vmax);
-  p.amax = (const double *)(base + o_amax); p.delta = (const double *)(base + o_delta);
-  p.iv = initial_velocity ? (const double *)(base + o_iv) : nullptr;
-  p.np_out = (int *)(base + o_np); p.status_out = (int *)(base + o_status);
+  p = fit_params(ps, count, rounding);    // the set's arrays after any growth; upload() adds the staged ones
+  if (s.upload(ps->wp_buf.p, st)) return TPAMD_E_HIP;
   launch_set_waypoints(p, st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out.data(), base + o_np, out.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (num_points) std::memcpy(num_points, out.data(), n * 4);
-  std::memcpy(status, out.data() + (o_status - o_np), n * 4);
+  rc = s.download(st);
+  if (rc) return rc;
   fit_bookkeeping(ps, count, id, waypoint_offsets);
   return 0;
 }
@@ -2865,7 +2705,7 @@ int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *ps, int count, con
     HIPCHK(hipHostMalloc(&ps->wp_pin, bytes, hipHostMallocDefault));
     ps->wp_pin_bytes = bytes;
   }
-  char *pin = (char *)ps->wp_pin, *base = (char *)ps->wp_buf;
+  char *pin = (char *)ps->wp_pin, *base = (char *)ps->wp_buf.p;
   std::memcpy(pin, id.data(), n * 4);
   std::memcpy(pin + align_up(n * 4, 256), waypoint_offsets, (n + 1) * 4);
   if (readout_begin(ps, st)) return TPAMD_E_HIP;
@@ -2898,41 +2738,27 @@ int tpamd_planner_set_sample_at_ticks(tpamd_planner_set *ps, int count, const in
   TPAMD_ON_DEVICE(ps->e);
   hipStream_t st = nullptr;
   // one copy up [start_ns][ids], one launch, one copy down per requested array
-  const size_t o_ids = align_up(n * 8, 256), in_bytes = o_ids + (ids ? n * 4 : 0);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_st = take(ticks * 4), o_q = take(q ? ticks * D * 8 : 0), o_qd = take(qd ? ticks * D * 8 : 0),
-               o_qdd = take(qdd ? ticks * D * 8 : 0);
-  if (ensure_staging(&ps->rd_in, &ps->rd_in_bytes, in_bytes) || ensure_staging(&ps->rd_out, &ps->rd_out_bytes, off))
-    return TPAMD_E_HIP;
-  std::vector<char> in(in_bytes);
-  std::memcpy(in.data(), start_ns, n * 8);
-  if (ids) std::memcpy(in.data() + o_ids, ids, n * 4);
-  char *din = (char *)ps->rd_in, *dout = (char *)ps->rd_out;
-  HIPCHK(hipMemcpyAsync(din, in.data(), in_bytes, hipMemcpyHostToDevice, st));
   ReadoutParams p = readout_params(ps);
-  p.count = count; p.num_ticks = num_ticks;
-  p.ids = ids ? (const int *)(din + o_ids) : nullptr;
-  p.start_ns = (const long long *)din; p.step_ns = step_ns;
-  p.status = (int *)(dout + o_st);
-  p.q = q ? (double *)(dout + o_q) : nullptr;
-  p.qd = qd ? (double *)(dout + o_qd) : nullptr;
-  p.qdd = qdd ? (double *)(dout + o_qdd) : nullptr;
+  std::vector<double> values[3];   // q, qd, qdd as they come down
+  double *dst[3] = {q, qd, qdd}, **dev[3] = {&p.q, &p.qd, &p.qdd};
+  HostStage in(/*packed=*/true, /*tight=*/true), out;
+  in.up(&p.start_ns, start_ns, n);
+  in.up(&p.ids, ids, n);
+  out.down(&p.status, status, ticks);
+  for (int a = 0; a < 3; a++) {
+    if (dst[a]) values[a].resize(ticks * D);
+    out.down(dev[a], dst[a] ? values[a].data() : nullptr, ticks * D);
+  }
+  if (in.upload(ps->rd_in, st) || out.upload(ps->rd_out, st)) return TPAMD_E_HIP;
+  p.count = count; p.num_ticks = num_ticks; p.step_ns = step_ns;
   hipLaunchKernelGGL(k_pset_sample_at_ticks, dim3((unsigned)((ticks + 255) / 256)), dim3(256), 0, st, p);
   HIPCHK(hipGetLastError());
   // the values come down whole; only the OK ticks reach the caller's arrays
-  std::vector<char> out(off);
-  HIPCHK(hipMemcpyAsync(status, dout + o_st, ticks * 4, hipMemcpyDeviceToHost, st));
-  for (size_t o : {q ? o_q : SIZE_MAX, qd ? o_qd : SIZE_MAX, qdd ? o_qdd : SIZE_MAX})
-    if (o != SIZE_MAX) HIPCHK(hipMemcpyAsync(out.data() + o, dout + o, ticks * D * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const double *src[3] = {(const double *)(out.data() + o_q), (const double *)(out.data() + o_qd),
-                          (const double *)(out.data() + o_qdd)};
-  double *dst[3] = {q, qd, qdd};
+  if (int rc = out.download(st)) return rc;
   for (int a = 0; a < 3; a++) {
     if (!dst[a]) continue;
     for (size_t i = 0; i < ticks; i++)
-      if (status[i] == TPAMD_PLAN_OK) std::memcpy(dst[a] + i * D, src[a] + i * D, D * 8);
+      if (status[i] == TPAMD_PLAN_OK) std::memcpy(dst[a] + i * D, values[a].data() + i * D, D * 8);
   }
   return 0;
 }
@@ -2969,43 +2795,34 @@ int tpamd_planner_set_download_trajectories(tpamd_planner_set *ps, int count, co
   hipStream_t st = nullptr;
   const size_t n = count, D = ps->S.D;
   // [offsets][ids] up (ids only), the scan, offsets down; then the pack and one copy per array
-  const size_t o_ids = align_up((n + 1) * 8, 256), in_bytes = o_ids + (ids ? n * 4 : 0);
-  if (ensure_staging(&ps->rd_in, &ps->rd_in_bytes, in_bytes)) return TPAMD_E_HIP;
-  char *din = (char *)ps->rd_in;
-  if (ids) HIPCHK(hipMemcpyAsync(din + o_ids, ids, n * 4, hipMemcpyHostToDevice, st));
   ReadoutParams p = readout_params(ps);
+  HostStage in(/*packed=*/false, /*tight=*/true);
+  in.down(&p.offsets, offsets, n + 1);
+  in.up(&p.ids, ids, n);
+  int rc = in.upload(ps->rd_in, st);
+  if (rc) return rc;
   p.count = count;
-  p.ids = ids ? (const int *)(din + o_ids) : nullptr;
-  p.offsets = (long long *)din;
   hipLaunchKernelGGL(k_pset_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(offsets, din, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  rc = in.download(st);
+  if (rc) return rc;
   const size_t rows = (size_t)offsets[count];
   if ((int64_t)rows > capacity) return TPAMD_E_INVALID_ARGUMENT;
-  double *dst1[4] = {time, s, sd, sdd}, *dstD[3] = {q, qd, qdd};
-  size_t off = 0, o1[4], oD[3];
-  for (int a = 0; a < 4; a++) { o1[a] = off; if (dst1[a]) off = align_up(off + rows * 8, 256); }
-  for (int a = 0; a < 3; a++) { oD[a] = off; if (dstD[a]) off = align_up(off + rows * D * 8, 256); }
-  if (rows == 0 || off == 0) return 0;
-  if (ensure_staging(&ps->rd_out, &ps->rd_out_bytes, off)) return TPAMD_E_HIP;
-  char *dout = (char *)ps->rd_out;
+  HostStage out;
+  out.down(&p.o_time, time, rows);
+  out.down(&p.o_s, s, rows);
+  out.down(&p.o_sd, sd, rows);
+  out.down(&p.o_sdd, sdd, rows);
+  out.down(&p.o_q, q, rows * D);
+  out.down(&p.o_qd, qd, rows * D);
+  out.down(&p.o_qdd, qdd, rows * D);
+  if (rows == 0 || out.bytes() == 0) return 0;
+  rc = out.upload(ps->rd_out, st);
+  if (rc) return rc;
   p.capacity = (long long)rows;
-  p.o_time = time ? (double *)(dout + o1[0]) : nullptr;
-  p.o_s = s ? (double *)(dout + o1[1]) : nullptr;
-  p.o_sd = sd ? (double *)(dout + o1[2]) : nullptr;
-  p.o_sdd = sdd ? (double *)(dout + o1[3]) : nullptr;
-  p.o_q = q ? (double *)(dout + oD[0]) : nullptr;
-  p.o_qd = qd ? (double *)(dout + oD[1]) : nullptr;
-  p.o_qdd = qdd ? (double *)(dout + oD[2]) : nullptr;
   hipLaunchKernelGGL(k_pset_pack_trajectories, dim3((unsigned)n), dim3(256), 0, st, p);
   HIPCHK(hipGetLastError());
-  for (int a = 0; a < 4; a++)
-    if (dst1[a]) HIPCHK(hipMemcpyAsync(dst1[a], dout + o1[a], rows * 8, hipMemcpyDeviceToHost, st));
-  for (int a = 0; a < 3; a++)
-    if (dstD[a]) HIPCHK(hipMemcpyAsync(dstD[a], dout + oD[a], rows * D * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  return out.download(st);
 }
 
 int tpamd_planner_set_download_trajectories_device(tpamd_planner_set *ps, int count, const int32_t *ids,
@@ -3042,59 +2859,44 @@ int tpamd_planner_set_stop_trajectories(tpamd_planner_set *ps, int count, const 
   hipStream_t st = nullptr;
   const size_t n = count, D = ps->S.D;
   // up: [time_ns][max_acceleration][ids]; scratch: [first][last][status][keep][shift][length][offsets]
-  const size_t o_am = align_up(n * 8, 256), o_ids = align_up(o_am + n * D * 8, 256),
-               in_bytes = o_ids + (ids ? n * 4 : 0);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_fi = take(n * 4), o_la = take(n * 4), o_st = take(n * 4), o_kp = take(n * 4), o_sh = take(n * 8),
-               o_len = take(n * 8), o_off = take((n + 1) * 8);
-  if (ensure_stop_buf(ps, off) || ensure_staging(&ps->rd_in, &ps->rd_in_bytes, in_bytes)) return TPAMD_E_HIP;
+  StopTrajParams p = stop_params(ps);
+  long long *d_offsets = nullptr;
+  HostStage in(/*packed=*/true, /*tight=*/true), sb;
+  in.up(&p.stop_ns, time_ns, n);
+  in.up(&p.amax, max_acceleration, n * D);
+  in.up(&p.ids, ids, n);
+  sb.scratch(&p.seg_first, n);
+  sb.scratch(&p.seg_last, n);
+  sb.down(&p.status, status, n);
+  sb.down(&p.keep, keep, n);
+  sb.scratch(&p.seg_offset, n);
+  sb.scratch(&p.seg_len, n);
+  sb.down(&d_offsets, offsets, n + 1);
+  if (ensure_stop_buf(ps, sb.bytes()) || ps->rd_in.reserve(in.bytes())) return TPAMD_E_HIP;
   // a device stop in flight on another stream may still use the scratch
   if (ps->read_pending) HIPCHK(hipStreamWaitEvent(st, ps->ev_read, 0));
-  std::vector<char> in(in_bytes);
-  std::memcpy(in.data(), time_ns, n * 8);
-  std::memcpy(in.data() + o_am, max_acceleration, n * D * 8);
-  if (ids) std::memcpy(in.data() + o_ids, ids, n * 4);
-  char *din = (char *)ps->rd_in, *sb = (char *)ps->stop_buf;
-  HIPCHK(hipMemcpyAsync(din, in.data(), in_bytes, hipMemcpyHostToDevice, st));
-  StopTrajParams p = stop_params(ps);
-  p.Q = count; p.mode = kRsSetFind;
-  p.ids = ids ? (const int *)(din + o_ids) : nullptr;
-  p.stop_ns = (const long long *)din; p.amax = (const double *)(din + o_am); p.time_step = time_step;
-  p.seg_first = (int *)(sb + o_fi); p.seg_last = (int *)(sb + o_la); p.status = (int *)(sb + o_st);
-  p.keep = (int *)(sb + o_kp); p.seg_offset = (double *)(sb + o_sh); p.seg_len = (long long *)(sb + o_len);
+  if (in.upload(ps->rd_in.p, st) || sb.upload(ps->stop_buf.p, st)) return TPAMD_E_HIP;
+  p.Q = count; p.mode = kRsSetFind; p.time_step = time_step;
   if (!launch_stop_trajectories((int)D, p, st)) return TPAMD_E_UNSUPPORTED;
-  hipLaunchKernelGGL(k_stop_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, count, p.seg_len,
-                     (long long *)(sb + o_off));
+  hipLaunchKernelGGL(k_stop_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, count, p.seg_len, d_offsets);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(status, sb + o_st, n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(keep, sb + o_kp, n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(offsets, sb + o_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  int rc = sb.download(st);
+  if (rc) return rc;
   const size_t rows = (size_t)offsets[count];
   if ((int64_t)rows > capacity) return TPAMD_E_INVALID_ARGUMENT;
-  double *dst[4] = {time, q, qd, qdd};
-  const size_t width[4] = {1, D, D, D};
-  size_t o_out[4], out_bytes = 0;
-  for (int a = 0; a < 4; a++) {
-    o_out[a] = out_bytes;
-    if (dst[a]) out_bytes = align_up(out_bytes + rows * width[a] * 8, 256);
-  }
-  if (rows == 0 || out_bytes == 0) return 0;
-  if (ensure_staging(&ps->rd_out, &ps->rd_out_bytes, out_bytes)) return TPAMD_E_HIP;
-  char *dout = (char *)ps->rd_out;
+  HostStage out;
+  out.down(&p.o_time, time, rows);
+  out.down(&p.o_q, q, rows * D);
+  out.down(&p.o_qd, qd, rows * D);
+  out.down(&p.o_qdd, qdd, rows * D);
+  if (rows == 0 || out.bytes() == 0) return 0;
+  rc = out.upload(ps->rd_out, st);
+  if (rc) return rc;
   p.mode = kRsSetWrite;
-  p.offsets = (const long long *)(sb + o_off); p.capacity = (long long)rows;
-  p.o_time = time ? (double *)(dout + o_out[0]) : nullptr;
-  p.o_q = q ? (double *)(dout + o_out[1]) : nullptr;
-  p.o_qd = qd ? (double *)(dout + o_out[2]) : nullptr;
-  p.o_qdd = qdd ? (double *)(dout + o_out[3]) : nullptr;
+  p.offsets = d_offsets; p.capacity = (long long)rows;
   launch_stop_trajectories((int)D, p, st);
   HIPCHK(hipGetLastError());
-  for (int a = 0; a < 4; a++)
-    if (dst[a]) HIPCHK(hipMemcpyAsync(dst[a], dout + o_out[a], rows * width[a] * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  return out.download(st);
 }
 
 int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *ps, int count, const int32_t *ids,
@@ -3108,18 +2910,18 @@ int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *ps, int count,
   TPAMD_ON_DEVICE(ps->e);
   hipStream_t st = (hipStream_t)hip_stream;
   const size_t n = count;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_fi = take(n * 4), o_la = take(n * 4), o_sh = take(n * 8), o_len = take(n * 8);
-  if (off > 0 && ensure_stop_buf(ps, off)) return TPAMD_E_HIP;
-  if (readout_begin(ps, st)) return TPAMD_E_HIP;
-  char *sb = (char *)ps->stop_buf;
   StopTrajParams p = stop_params(ps);
+  HostStage sb;
+  sb.scratch(&p.seg_first, n);
+  sb.scratch(&p.seg_last, n);
+  sb.scratch(&p.seg_offset, n);
+  sb.scratch(&p.seg_len, n);
+  if (sb.bytes() > 0 && ensure_stop_buf(ps, sb.bytes())) return TPAMD_E_HIP;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  if (sb.upload(ps->stop_buf.p, st)) return TPAMD_E_HIP;   // no copies: the scratch's addresses only
   p.Q = count; p.mode = kRsSetFind;
   p.ids = ids; p.stop_ns = (const long long *)time_ns; p.amax = max_acceleration; p.time_step = time_step;
   p.status = status; p.keep = keep;
-  p.seg_first = (int *)(sb + o_fi); p.seg_last = (int *)(sb + o_la);
-  p.seg_offset = (double *)(sb + o_sh); p.seg_len = (long long *)(sb + o_len);
   launch_stop_trajectories(ps->S.D, p, st);
   hipLaunchKernelGGL(k_stop_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, count, p.seg_len,
                      (long long *)offsets);                                               // offsets[0] = 0 for none
