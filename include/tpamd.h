@@ -558,6 +558,144 @@ void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *set, size_t *hos
  * which grows as calls need it. */
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *set);
 
+/* ---- buffer sets: B TrajectoryBuffers resident on the device -------------------------------
+ * A buffer set keeps B TrajectoryBuffers (trajectory_buffer.{h,cc}) of D joints on the device:
+ * per buffer the samples (time, q, qd, qdd), the sample count and the sequence number. Every
+ * operation takes a list of buffers (ids[count], or buffers 0..count-1 if ids is NULL), runs in one
+ * launch and leaves each listed buffer as the same call on a TrajectoryBuffer would, bit for bit.
+ * Per-buffer outcomes are TPAMD_PLAN_* in status[count].
+ *
+ * Host-pointer entries take host arrays, run on the null stream and synchronise. Call-level errors
+ * (TPAMD_E_*: a NULL set or required array, count < 0, count > B with a NULL ids, an id out of
+ * range, and in a call that changes buffers a buffer listed twice) change nothing; every id is
+ * checked before the first copy. Entries that add samples grow the set's per-buffer capacity (by
+ * doubling) before anything changes.
+ * _device entries take device pointers for every array, ids included, only enqueue on hip_stream
+ * (NULL: the null stream) and never allocate or synchronise, so after tpamd_buffer_set_reserve
+ * they can be captured in a hipGraph and replayed with other lists (the exception is
+ * tpamd_buffer_set_insert_from_planner_set_device, see there). An id out of range gets
+ * TPAMD_PLAN_INVALID_ARGUMENT in the kernel; listing a buffer twice in a call that changes buffers
+ * is outside the contract. A listed buffer whose result would not fit the capacity gets
+ * TPAMD_PLAN_MORE and is left unchanged. status may be NULL where nothing but the id check can
+ * fail (discard_before, add_offset, clear, info). Calls on one stream are ordered by that stream;
+ * the caller orders calls on different streams. */
+typedef struct tpamd_buffer_set tpamd_buffer_set;
+
+/* num_buffers >= 1, num_dofs in [1, 16], capacity rows per buffer (0: 256), timestep_tolerance > 0
+ * (TrajectoryBuffer::Create rejects the others: TPAMD_E_INVALID_ARGUMENT). The set must not
+ * outlive the engine. */
+int tpamd_buffer_set_create(tpamd_engine *engine, int num_buffers, int num_dofs, int capacity,
+                            double timestep_tolerance, tpamd_buffer_set **out);
+/* Waits for the device before it frees the set. */
+void tpamd_buffer_set_destroy(tpamd_buffer_set *set);
+/* At least `capacity` rows per buffer (TrajectoryBuffer::Reserve); contents unchanged.
+ * Synchronises the device. */
+int tpamd_buffer_set_reserve(tpamd_buffer_set *set, int capacity);
+int tpamd_buffer_set_capacity(const tpamd_buffer_set *set);
+/* Device memory the set holds: its state and the staging of the host-pointer entries. _device
+ * entries never change it. */
+size_t tpamd_buffer_set_device_bytes(const tpamd_buffer_set *set);
+
+/* InsertSegment (trajectory_buffer.cc:79-133). Listed buffer k receives rows offsets[k] ..
+ * offsets[k+1) of time [rows] and q / qd / qdd [rows][D]: the packed layout that
+ * tpamd_planner_set_download_trajectories* and tpamd_planner_set_stop_trajectories* write. The
+ * sequence number goes up (an empty segment included) and back to 0 when the segment replaces the
+ * whole buffer. status: TPAMD_PLAN_OK. offsets must not decrease (call-level error). Up: offsets,
+ * the rows, ids in one copy; down: status. */
+int tpamd_buffer_set_insert(tpamd_buffer_set *set, int count, const int32_t *ids, const int64_t *offsets,
+                            const double *time, const double *q, const double *qd, const double *qdd,
+                            int32_t *status);
+/* The same on the device; `capacity` is the number of rows the arrays hold. An entry whose row
+ * range is negative or ends behind `capacity` (a producer that ran out of room leaves its rows
+ * unwritten and offsets[count] > capacity) gets TPAMD_PLAN_INVALID_ARGUMENT, a buffer without room
+ * TPAMD_PLAN_MORE; both leave the buffer unchanged. */
+int tpamd_buffer_set_insert_device(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                   const int64_t *offsets, int64_t capacity, const double *time,
+                                   const double *q, const double *qd, const double *qdd, int32_t *status,
+                                   void *hip_stream);
+/* InsertSegment of the resident trajectory of planner planner_ids[k] (NULL: planner k) of a
+ * planner set on the same engine and with the same D into listed buffer k, device to device:
+ * nothing crosses PCIe but the lists and the statuses. A planner without samples is an empty
+ * segment. Call-level errors also: another engine or D, a planner out of range. */
+int tpamd_buffer_set_insert_from_planner_set(tpamd_buffer_set *set, tpamd_planner_set *planners, int count,
+                                             const int32_t *ids, const int32_t *planner_ids,
+                                             int32_t *status);
+/* The same with ids, planner_ids and status on the device; a planner out of range gets
+ * TPAMD_PLAN_INVALID_ARGUMENT. It counts as a device readout of the planner set and joins its
+ * event chain (tpamd_planner_set_download_trajectories_device): it records and waits on the
+ * planner set's events, so a later Plan cannot overwrite a trajectory it is still reading. That
+ * event record is on the null stream: this entry is not meant to be captured in a graph. */
+int tpamd_buffer_set_insert_from_planner_set_device(tpamd_buffer_set *set, tpamd_planner_set *planners,
+                                                    int count, const int32_t *ids,
+                                                    const int32_t *planner_ids, int32_t *status,
+                                                    void *hip_stream);
+/* AppendSample (:135-149): time [count], q / qd / qdd [count][D]. status TPAMD_PLAN_OK, or
+ * TPAMD_PLAN_INVALID_ARGUMENT unless the time is after the buffer's last sample. */
+int tpamd_buffer_set_append_sample(tpamd_buffer_set *set, int count, const int32_t *ids, const double *time,
+                                   const double *q, const double *qd, const double *qdd, int32_t *status);
+int tpamd_buffer_set_append_sample_device(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                          const double *time, const double *q, const double *qd,
+                                          const double *qdd, int32_t *status, void *hip_stream);
+/* DiscardSegmentBefore (:151-208) at time_ns[k] (converted as (double)ns / 1e9) or time_sec[k]:
+ * exactly one of the two arrays is given. No sample moves: the buffer's first row advances, and
+ * the new first sample is the interpolated state where the reference creates one. A time after
+ * the last sample clears the buffer, sequence number included. */
+int tpamd_buffer_set_discard_before(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                    const int64_t *time_ns, const double *time_sec);
+int tpamd_buffer_set_discard_before_device(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                           const int64_t *time_ns, const double *time_sec, int32_t *status,
+                                           void *hip_stream);
+/* StopBeforeTime (:296-385) that changes the buffer: the samples from the kept count on become
+ * the tail time-scaled to rest, and count and sequence number follow InsertSegment; on the last
+ * sample at rest only its velocity and acceleration are zeroed. status as
+ * tpamd_planner_set_stop_trajectories (TPAMD_PLAN_INTERNAL where the reference aborts); a stop
+ * that fails leaves the buffer untouched. max_acceleration [count][D]. A stop never needs more
+ * rows than the buffer holds. */
+int tpamd_buffer_set_stop_before_time(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                      const int64_t *time_ns, const double *time_sec,
+                                      const double *max_acceleration, double time_step, int32_t *status);
+int tpamd_buffer_set_stop_before_time_device(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                             const int64_t *time_ns, const double *time_sec,
+                                             const double *max_acceleration, double time_step,
+                                             int32_t *status, void *hip_stream);
+/* Get{Position,Velocity,Acceleration}AtTime at ticks start_ns[k] + j step_ns: arguments, outputs
+ * and statuses as tpamd_planner_set_sample_at_ticks, on the buffers (repeats allowed). */
+int tpamd_buffer_set_sample_at_ticks(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                     const int64_t *start_ns, int64_t step_ns, int num_ticks, double *q,
+                                     double *qd, double *qdd, int32_t *status);
+int tpamd_buffer_set_sample_at_ticks_device(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                            const int64_t *start_ns, int64_t step_ns, int num_ticks,
+                                            double *q, double *qd, double *qdd, int32_t *status,
+                                            void *hip_stream);
+/* AddOffsetToTimestamps (:387-393): offset_sec[k], or offset_ns[k] / 1e9 (a duration); exactly one
+ * of the two arrays is given. */
+int tpamd_buffer_set_add_offset(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                const int64_t *offset_ns, const double *offset_sec);
+int tpamd_buffer_set_add_offset_device(tpamd_buffer_set *set, int count, const int32_t *ids,
+                                       const int64_t *offset_ns, const double *offset_sec, int32_t *status,
+                                       void *hip_stream);
+/* Clear (:64-70): no samples, sequence number 0. */
+int tpamd_buffer_set_clear(tpamd_buffer_set *set, int count, const int32_t *ids);
+int tpamd_buffer_set_clear_device(tpamd_buffer_set *set, int count, const int32_t *ids, int32_t *status,
+                                  void *hip_stream);
+/* GetNumSamples, GetSequenceNumber, GetStartTime and GetEndTime (nanoseconds; :50-62: both 0 for
+ * an empty buffer) and, if time_ns is given, the size of GetPositionsUpToTime(time_ns[k])
+ * (:210-226) of each listed buffer (repeats allowed). Any output may be NULL. */
+int tpamd_buffer_set_info(tpamd_buffer_set *set, int count, const int32_t *ids, const int64_t *time_ns,
+                          int32_t *num_samples, int32_t *sequence, int64_t *start_ns, int64_t *end_ns,
+                          int32_t *positions_up_to);
+int tpamd_buffer_set_info_device(tpamd_buffer_set *set, int count, const int32_t *ids, const int64_t *time_ns,
+                                 int32_t *num_samples, int32_t *sequence, int64_t *start_ns, int64_t *end_ns,
+                                 int32_t *positions_up_to, void *hip_stream);
+/* The samples of the listed buffers (repeats allowed), packed as
+ * tpamd_planner_set_download_trajectories packs trajectories: offsets [count + 1] always written,
+ * rows only if offsets[count] <= capacity (host variant: TPAMD_E_INVALID_ARGUMENT otherwise). */
+int tpamd_buffer_set_download(tpamd_buffer_set *set, int count, const int32_t *ids, int64_t *offsets,
+                              int64_t capacity, double *time, double *q, double *qd, double *qdd);
+int tpamd_buffer_set_download_device(tpamd_buffer_set *set, int count, const int32_t *ids, int64_t *offsets,
+                                     int64_t capacity, double *time, double *q, double *qd, double *qdd,
+                                     void *hip_stream);
+
 /* Batched TimeOptimalPathProfile::FindMaxSd2Simplex (time_optimal_path_timing.cc:1149-1363)
  * on num_lps independent constraint sets of C rows each ([num_lps][C] arrays);
  * outputs sd2max/sddmax/sd2zero [num_lps]. Host pointers. */

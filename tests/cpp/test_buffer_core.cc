@@ -1,0 +1,524 @@
+// CPU test of the trajectory buffer (run by tests/test_buffer_set_cpu.py):
+//   1. the mirror's TrajectoryBuffer (host/trajectory_buffer.cc) on the cases of the reference's
+//      trajectory_buffer_test.cc for InsertSegment, AppendSample, DiscardSegmentBefore,
+//      GetPositionsUpToTime, AddOffsetToTimestamps, Clear and the sequence number, restated as data
+//      generated here;
+//   2. the host/device core of csrc/tpamd_buffer.h, compiled here for the host, driven through
+//      seeded random operation sequences (insert / discard / stop / append / offset / clear) next
+//      to a mirror TrajectoryBuffer that receives the same operations: after every operation the
+//      times, positions, velocities, accelerations, the sample count and the sequence number are
+//      equal bit for bit, and the statuses are equal. The categories are decided from the mirror's
+//      state before the operation; every one must be reached.
+// Prints one line per category and "ALL OK".
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../x-edr-trajectory-planning_amd/csrc/tpamd_buffer.h"
+#include "../../x-edr-trajectory-planning_amd/host/trajectory_buffer.h"
+
+using namespace trajectory_planning;
+using tpamd::compat::StatusCode;
+
+static int g_fail = 0;
+#define CHECK(cond)                                                                          \
+  do {                                                                                       \
+    if (!(cond)) {                                                                           \
+      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
+      g_fail++;                                                                              \
+    }                                                                                        \
+  } while (0)
+
+static unsigned long long g_seed = 20261017ULL;
+static double Rnd() {
+  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
+  return (double)(g_seed >> 11) / 9007199254740992.0;
+}
+static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
+
+static int Code(const Status &s) {
+  switch (s.code()) {
+    case StatusCode::kOk: return tpamd::kRsOk;
+    case StatusCode::kFailedPrecondition: return 1;
+    case StatusCode::kOutOfRange: return tpamd::kRsOutOfRange;
+    case StatusCode::kInvalidArgument: return tpamd::kRsInvalidArgument;
+    case StatusCode::kInternal: return tpamd::kRsInternal;
+    case StatusCode::kNotFound: return tpamd::kRsNotFound;
+    default: return 99;
+  }
+}
+
+static VectorXd Constant(int n, double v) { return VectorXd((size_t)n, v); }
+static Time TimeFromSec(double s) { return tpamd::compat::FromUnixSeconds(s); }
+static bool AllEqual(const VectorXd &v, double x) {
+  for (size_t j = 0; j < v.size(); j++)
+    if (v[j] != x) return false;
+  return true;
+}
+
+struct Segment {
+  std::vector<double> times;
+  std::vector<VectorXd> positions, velocities, accelerations;
+};
+
+// GetTestTrajectory of trajectory_buffer_test.cc: sample i at i dt + offset with q = i, v = 10 i, a = 100 i
+static Segment TestTrajectory(double time_offset, int sample_count, double dt = 8e-3, int joints = 9) {
+  Segment t;
+  for (int i = 0; i < sample_count; ++i) {
+    t.times.push_back(i * dt + time_offset);
+    t.positions.push_back(Constant(joints, i));
+    t.velocities.push_back(Constant(joints, 10 * i));
+    t.accelerations.push_back(Constant(joints, 100 * i));
+  }
+  return t;
+}
+static Status Insert(TrajectoryBuffer &b, const Segment &s) {
+  return b.InsertSegment(s.times, s.positions, s.velocities, s.accelerations);
+}
+
+static void ReferenceCases() {
+  const int J = 9;
+  const double dt = 8e-3;
+  {  // InsertSegmentWorks
+    auto b = *TrajectoryBuffer::Create();
+    CHECK(b->GetNumSamples() == 0 && b->GetStartTime() == TimeFromSec(0) && b->GetSequenceNumber() == 0);
+    CHECK(b->InsertSegment({}, {}, {}, {}).ok());         // an empty segment only moves the sequence number
+    CHECK(b->GetStartTime() == TimeFromSec(0) && b->GetEndTime() == TimeFromSec(0));
+    CHECK(b->GetSequenceNumber() == 1 && b->GetNumSamples() == 0);
+    b->Clear();
+    Segment t = TestTrajectory(1.0, 10);
+    CHECK(Insert(*b, t).ok());
+    CHECK(b->GetStartTime() == TimeFromSec(t.times.front()) && b->GetEndTime() == TimeFromSec(t.times.back()));
+    CHECK(b->GetSequenceNumber() == 0 && b->GetNumSamples() == 10);
+    for (int i = 0; i < 10; i++)
+      CHECK(b->GetTimes()[i] == t.times[i] && AllEqual(b->GetPositions()[i], i) &&
+            AllEqual(b->GetVelocities()[i], 10 * i) && AllEqual(b->GetAccelerations()[i], 100 * i));
+    t = TestTrajectory(1.0 + 3 * dt, 5);                  // replaces the samples from the fourth on
+    CHECK(Insert(*b, t).ok());
+    CHECK(b->GetStartTime() == TimeFromSec(1) && b->GetEndTime() == TimeFromSec(t.times.back()));
+    CHECK(b->GetSequenceNumber() == 1 && b->GetNumSamples() == 8);
+    CHECK(b->GetPositions().size() == 8 && b->GetVelocities().size() == 8 && b->GetAccelerations().size() == 8);
+    const int expect[8] = {0, 1, 2, 0, 1, 2, 3, 4};
+    for (int i = 0; i < 8 && b->GetNumSamples() == 8; i++)
+      CHECK(b->GetTimes()[i] == 1.0 + i * dt && AllEqual(b->GetPositions()[i], expect[i]) &&
+            AllEqual(b->GetVelocities()[i], 10 * expect[i]) && AllEqual(b->GetAccelerations()[i], 100 * expect[i]));
+  }
+  {  // AppendSampleWorks
+    auto b = *TrajectoryBuffer::Create();
+    CHECK(b->AppendSample(1.0, Constant(J, 1), Constant(J, 2), Constant(J, 3)).ok());
+    CHECK(b->AppendSample(1.0, Constant(J, 1), Constant(J, 2), Constant(J, 3)).code() == StatusCode::kInvalidArgument);
+    CHECK(b->AppendSample(-1.0, Constant(J, 1), Constant(J, 2), Constant(J, 3)).code() == StatusCode::kInvalidArgument);
+    CHECK(b->AppendSample(1.1, Constant(J, 1.1), Constant(J, 2.1), Constant(J, 3.1)).ok());
+    CHECK(b->GetNumSamples() == 2 && b->GetSequenceNumber() == 0);
+    if (b->GetNumSamples() == 2)
+      CHECK(AllEqual(b->GetPositions()[0], 1) && AllEqual(b->GetPositions()[1], 1.1) &&
+            AllEqual(b->GetVelocities()[0], 2) && AllEqual(b->GetVelocities()[1], 2.1) &&
+            AllEqual(b->GetAccelerations()[0], 3) && AllEqual(b->GetAccelerations()[1], 3.1));
+  }
+  for (double sign : {-1.0, 1.0}) {  // InsertSegmentUsesTimestepTolerance: half a tolerance off the fourth sample
+    const double tol = 1e-5;
+    auto b = *TrajectoryBuffer::Create(TrajectoryBufferOptions{tol});
+    CHECK(Insert(*b, TestTrajectory(1.0, 10)).ok());
+    Segment t = TestTrajectory(1.0 + 3 * dt, 5);
+    t.times.front() += sign * 0.5 * tol;
+    CHECK(Insert(*b, t).ok());
+    CHECK(b->GetNumSamples() == 8);
+    for (int i = 0; i < 8 && b->GetNumSamples() == 8; i++)
+      CHECK(b->GetTimes()[i] == (i == 3 ? 1.0 + 3 * dt + sign * 0.5 * tol : 1.0 + i * dt));
+  }
+  {  // InsertSegmentFailsForInvalidArguments
+    auto b = *TrajectoryBuffer::Create();
+    Segment t = TestTrajectory(1.0, 10);
+    const std::vector<double> short_times(5);
+    const std::vector<VectorXd> short_rows(5);
+    CHECK(b->InsertSegment(short_times, t.positions, t.velocities, t.accelerations).code() == StatusCode::kInvalidArgument);
+    CHECK(b->InsertSegment(t.times, short_rows, t.velocities, t.accelerations).code() == StatusCode::kInvalidArgument);
+    CHECK(b->InsertSegment(t.times, t.positions, short_rows, t.accelerations).code() == StatusCode::kInvalidArgument);
+    CHECK(b->InsertSegment(t.times, t.positions, t.velocities, short_rows).code() == StatusCode::kInvalidArgument);
+    CHECK(b->GetSequenceNumber() == 0);
+    t.times.front() = (double)tpamd::compat::ToUnixNanos(b->GetEndTime()) / 1e9;   // at the end time works
+    for (size_t i = 1; i < t.times.size(); ++i) t.times[i] = t.times[i - 1] + dt;
+    CHECK(Insert(*b, t).ok());
+  }
+  {  // ClearWorks
+    auto b = *TrajectoryBuffer::Create();
+    CHECK(Insert(*b, TestTrajectory(1.0, 10)).ok());
+    CHECK(Insert(*b, TestTrajectory(1.0 + 3 * dt, 5)).ok() && b->GetSequenceNumber() == 1);
+    b->Clear();
+    CHECK(b->GetSequenceNumber() == 0 && b->GetNumSamples() == 0 && b->GetStartTime() == TimeFromSec(0));
+  }
+  {  // DiscardWorks
+    auto b = *TrajectoryBuffer::Create();
+    b->DiscardSegmentBefore(TimeFromSec(10));
+    CHECK(b->GetSequenceNumber() == 0 && b->GetNumSamples() == 0);
+    b->DiscardSegmentBefore(TimeFromSec(-10));
+    CHECK(b->GetSequenceNumber() == 0 && b->GetNumSamples() == 0);
+    const Segment t = TestTrajectory(1.0, 10);
+    CHECK(Insert(*b, t).ok());
+    b->DiscardSegmentBefore(b->GetStartTime());           // nothing before the start time
+    CHECK(b->GetStartTime() == TimeFromSec(t.times.front()) && b->GetEndTime() == TimeFromSec(t.times.back()));
+    CHECK(b->GetNumSamples() == 10 && b->GetTimes().size() == 10 && b->GetPositions().size() == 10);
+    b->DiscardSegmentBefore(TimeFromSec(t.times[4]));     // the sample at the time stays
+    CHECK(b->GetStartTime() == TimeFromSec(t.times[4]) && b->GetTimes()[0] == t.times[4]);
+    CHECK(b->GetEndTime() == TimeFromSec(t.times.back()) && b->GetNumSamples() == 6);
+    CHECK(b->GetPositions().size() == 6 && b->GetVelocities().size() == 6 && b->GetAccelerations().size() == 6);
+    b->DiscardSegmentBefore(TimeFromSec(t.times.back() + 1.0 / 1e9));   // after the end: Clear()
+    CHECK(b->GetStartTime() == TimeFromSec(0) && b->GetEndTime() == TimeFromSec(0) && b->GetNumSamples() == 0);
+    CHECK(b->GetTimes().size() == 0 && b->GetPositions().size() == 0);
+    const double eps = 1e-10;
+    auto spacing_ok = [&](double most) {
+      for (size_t i = 1; i < b->GetNumSamples(); ++i)
+        if (!(b->GetTimes()[i] - b->GetTimes()[i - 1] <= most)) return false;
+      return true;
+    };
+    auto near = [&](const VectorXd &v, double x, double tol) {
+      for (size_t j = 0; j < v.size(); j++)
+        if (!(std::fabs(v[j] - x) <= tol)) return false;
+      return true;
+    };
+    b->Clear();                                           // exactly on a sample
+    CHECK(Insert(*b, t).ok());
+    b->DiscardSegmentBefore(t.times[3]);
+    CHECK(std::fabs(b->GetTimes()[0] - t.times[3]) <= eps && near(b->GetPositions()[0], 3, 100 * eps));
+    CHECK(b->GetNumSamples() == 7 && spacing_ok(dt + eps));
+    b->Clear();                                           // just before a sample
+    CHECK(Insert(*b, t).ok());
+    const double before6 = std::nextafter(t.times[6], -1e99);
+    b->DiscardSegmentBefore(before6);
+    CHECK(std::fabs(b->GetTimes()[0] - before6) <= eps && near(b->GetPositions()[0], 6, 100 * eps) && spacing_ok(dt + eps));
+    b->Clear();                                           // just after a sample
+    CHECK(Insert(*b, t).ok());
+    const double after6 = std::nextafter(t.times[6], 1e99);
+    b->DiscardSegmentBefore(after6);
+    CHECK(std::fabs(b->GetTimes()[0] - after6) <= eps && near(b->GetPositions()[0], 6, 100 * eps) && spacing_ok(dt + eps));
+    b->Clear();                                           // between two samples: interpolated
+    CHECK(Insert(*b, t).ok());
+    const double between = 0.5 * (t.times[5] + t.times[6]);
+    b->DiscardSegmentBefore(between);
+    CHECK(std::fabs(b->GetTimes()[0] - between) <= eps);
+    CHECK(!near(b->GetPositions()[0], 6, eps) && !near(b->GetPositions()[0], 5, eps) && near(b->GetPositions()[0], 5.5, 1e-9));
+    CHECK(near(b->GetVelocities()[0], 55, 1e-8) && near(b->GetAccelerations()[0], 550, 1e-7));
+    CHECK(b->GetNumSamples() == 5 && spacing_ok(dt + 2 * eps));
+  }
+  {  // GetPositionsUpToTime
+    auto b = *TrajectoryBuffer::Create();
+    CHECK(b->GetPositionsUpToTime(TimeFromSec(1.0)).size() == 0);
+    const Segment t = TestTrajectory(1.0, 5);
+    CHECK(Insert(*b, t).ok());
+    CHECK(b->GetPositionsUpToTime(TimeFromSec(10)).size() == 0 && b->GetPositionsUpToTime(TimeFromSec(-1)).size() == 0);
+    auto span = b->GetPositionsUpToTime(TimeFromSec(t.times[2]));                        // excludes the sample
+    CHECK(span.size() == 2 && AllEqual(span[span.size() - 1], 1));
+    span = b->GetPositionsUpToTime(TimeFromSec(std::nexttoward(t.times[2], (long double)t.times[1])));
+    CHECK(span.size() == 1 && AllEqual(span[span.size() - 1], 0));
+    span = b->GetPositionsUpToTime(TimeFromSec(std::nexttoward(t.times[2], (long double)t.times[3])));
+    CHECK(span.size() == 2 && AllEqual(span[span.size() - 1], 1));
+  }
+  {  // AddOffsetToTimestamps: seconds and a duration; values and the sequence number stay
+    auto b = *TrajectoryBuffer::Create();
+    const Segment t = TestTrajectory(1.0, 6);
+    CHECK(Insert(*b, t).ok());
+    b->AddOffsetToTimestamps(0.25);
+    for (int i = 0; i < 6; i++) CHECK(b->GetTimes()[i] == t.times[i] + 0.25 && AllEqual(b->GetPositions()[i], i));
+    b->AddOffsetToTimestamps(tpamd::compat::Milliseconds(-250));
+    for (int i = 0; i < 6; i++) CHECK(b->GetTimes()[i] == (t.times[i] + 0.25) + -0.25);
+    CHECK(b->GetSequenceNumber() == 0 && b->GetNumSamples() == 6);
+    b->Reserve(100);
+    CHECK(b->GetNumSamples() == 6);
+  }
+  {  // a stop moves the sequence number through InsertSegment; the at-rest early return does not
+    auto b = *TrajectoryBuffer::Create();
+    Segment t;
+    const int n = 200;
+    for (int i = 0; i < n; i++) {                         // q = 0.5 (t - T)^2: decelerating to rest at the end
+      const double time = 1e-3 * i, trel = time - 1e-3 * (n - 1);
+      t.times.push_back(time);
+      t.positions.push_back(Constant(2, 0.5 * trel * trel));
+      t.velocities.push_back(Constant(2, trel));
+      t.accelerations.push_back(Constant(2, 1.0));
+    }
+    CHECK(Insert(*b, t).ok() && b->GetSequenceNumber() == 0);
+    CHECK(b->StopBeforeTime(10.0, Constant(2, 5.0), 1e-3).ok());      // last sample, at rest
+    CHECK(b->GetSequenceNumber() == 0 && b->GetNumSamples() == (size_t)n);
+    CHECK(b->StopAtIndex(n / 2, Constant(2, 5.0), 1e-3).ok());
+    CHECK(b->GetSequenceNumber() == 1);
+    CHECK(b->StopAtIndex(2, Constant(2, 1e-3), 1e-3).code() == StatusCode::kNotFound && b->GetSequenceNumber() == 1);
+  }
+  std::printf("reference cases: done\n");
+}
+
+// ------------------------------------------------------------------ the core next to the mirror
+struct CoreBuffer {
+  int D, cap, first = 0, count = 0, sequence = 0;
+  double tol;
+  std::vector<double> time, q, qd, qdd;
+  CoreBuffer(int D_, int cap_, double tol_)
+      : D(D_), cap(cap_), tol(tol_), time(cap_, std::nan("")), q((size_t)cap_ * D_, std::nan("")),
+        qd((size_t)cap_ * D_, std::nan("")), qdd((size_t)cap_ * D_, std::nan("")) {}
+  tpamd::BufRef ref() {
+    return tpamd::BufRef{&first, &count, &sequence, time.data(), q.data(), qd.data(), qdd.data(), cap, D, tol};
+  }
+};
+
+static bool Same(CoreBuffer &c, const TrajectoryBuffer &m) {
+  if ((size_t)c.count != m.GetNumSamples() || c.sequence != m.GetSequenceNumber()) return false;
+  if (c.first < 0 || c.first + c.count > c.cap) return false;
+  const size_t D = c.D;
+  for (int i = 0; i < c.count; i++) {
+    const size_t r = (size_t)c.first + i;
+    if (std::memcmp(&c.time[r], &m.GetTimes()[i], 8) || std::memcmp(&c.q[r * D], m.GetPositions()[i].data(), 8 * D) ||
+        std::memcmp(&c.qd[r * D], m.GetVelocities()[i].data(), 8 * D) ||
+        std::memcmp(&c.qdd[r * D], m.GetAccelerations()[i].data(), 8 * D))
+      return false;
+  }
+  return true;
+}
+
+struct Flat {
+  std::vector<double> time, q, qd, qdd;
+};
+static Segment ToSegment(const Flat &f, int D) {
+  Segment s;
+  s.times = f.time;
+  for (size_t i = 0; i < f.time.size(); i++) {
+    s.positions.push_back(VectorXd(&f.q[i * D], D));
+    s.velocities.push_back(VectorXd(&f.qd[i * D], D));
+    s.accelerations.push_back(VectorXd(&f.qdd[i * D], D));
+  }
+  return s;
+}
+
+// n rows from `front` on: a velocity profile that is constant, decelerates to rest at the end, or
+// is random; sometimes a last row nearly at rest, a row at rest mid-way, a repeated time stamp
+static Flat MakeRows(int n, int D, double front) {
+  Flat f;
+  const double dt = RndInt(0, 1) ? 1e-3 * RndInt(1, 8) : 1e-3 * (0.5 + Rnd());
+  for (int i = 0; i < n; i++) f.time.push_back(i == 0 ? front : f.time[i - 1] + dt * (RndInt(0, 1) ? 1.0 : 0.5 + Rnd()));
+  if (n > 3 && RndInt(0, 60) == 0) f.time[RndInt(2, n - 1)] = f.time[1];      // not increasing
+  f.q.resize((size_t)n * D); f.qd.resize((size_t)n * D); f.qdd.resize((size_t)n * D);
+  const int shape = RndInt(0, 2);
+  for (int j = 0; j < D; j++) {
+    const double v0 = (2.0 * Rnd() - 1.0) * (shape == 2 ? 3.0 : 1.0);
+    for (int i = 0; i < n; i++) {
+      const double frac = n > 1 ? (double)i / (n - 1) : 0.0;
+      const double v = shape == 0 ? v0 : shape == 1 ? v0 * (1.0 - frac) : v0 * (0.5 + Rnd());
+      f.qd[(size_t)i * D + j] = v;
+      f.qdd[(size_t)i * D + j] = shape == 1 ? -v0 / std::max(1e-3, f.time[n - 1] - f.time[0]) : (2.0 * Rnd() - 1.0);
+      f.q[(size_t)i * D + j] = 10.0 * Rnd();
+    }
+  }
+  if (n > 0 && RndInt(0, 5) == 0)
+    for (int j = 0; j < D; j++) f.qd[(size_t)(n - 1) * D + j] = RndInt(0, 1) ? 0.0 : 5e-5 * (2.0 * Rnd() - 1.0);
+  if (n > 2 && RndInt(0, 6) == 0) {
+    const int r = RndInt(1, n - 2);
+    for (int j = 0; j < D; j++) f.qd[(size_t)r * D + j] = RndInt(0, 1) ? 0.0 : 5e-9;
+  }
+  return f;
+}
+
+static std::map<std::string, long> g_counts;
+static long g_ops = 0;
+
+static void Sequence(int D, int ops) {
+  const int cap = RndInt(40, 120);
+  const double tol = RndInt(0, 1) ? 1e-6 : 1e-5;
+  CoreBuffer core(D, cap, tol);
+  auto mirror = *TrajectoryBuffer::Create(TrajectoryBufferOptions{tol});
+  for (int op = 0; op < ops; op++, g_ops++) {
+    const size_t n = mirror->GetNumSamples();
+    const std::vector<double> t(mirror->GetTimes().begin(), mirror->GetTimes().end());
+    const int seq_before = mirror->GetSequenceNumber();
+    const int kind = RndInt(0, 99);
+    if (kind < 40) {  // ---------------------------------------------------------------- insert
+      int rows = RndInt(0, 14) == 0 ? 0 : RndInt(0, 40) == 0 ? RndInt(cap - 10, cap + 10) : RndInt(1, 30);
+      double front = 1.0 + Rnd();
+      std::string cat = "insert: into an empty buffer";
+      if (n > 0) {
+        const int where = RndInt(0, 7);
+        const size_t i = (size_t)RndInt(0, (int)n - 1);
+        switch (where) {
+          case 0: front = RndInt(0, 1) ? t[0] : t[0] - 1e-3 * Rnd(); break;
+          case 1: front = t[n - 1]; break;
+          case 2: front = t[i] + 0.3 * tol; break;
+          case 3: front = t[i] + 1.5 * tol; break;
+          case 4: case 5: front = i + 1 < n ? t[i] + (t[i + 1] - t[i]) * (0.2 + 0.6 * Rnd()) : t[i] + 1e-3; break;
+          default: front = t[n - 1] + 1e-3 * (0.5 + Rnd()); break;
+        }
+        // the category, from the mirror's samples
+        const size_t lo = std::lower_bound(t.begin(), t.end(), front) - t.begin();
+        if (lo == 0) cat = "insert: at or before the front (sequence back to 0)";
+        else if (front == t[n - 1]) cat = "insert: exactly at the last sample";
+        else if (lo < n && t[lo] == front) cat = "insert: exactly at a sample";
+        else if (front - t[lo - 1] < tol) cat = "insert: within tolerance just after a sample (replaced)";
+        else if (front - t[lo - 1] < 2 * tol) cat = "insert: just outside tolerance (kept)";
+        else if (lo < n) cat = "insert: strictly inside";
+        else cat = "insert: behind the last sample";
+      }
+      if (rows == 0) cat = "insert: empty segment";
+      const Flat f = MakeRows(rows, D, front);
+      const tpamd::InsertPlan plan =
+          tpamd::bs_plan_insert(core.time.data() + core.first, core.first, core.count, core.sequence, cap, tol, rows, front);
+      if (plan.status == tpamd::kBsMore) {
+        g_counts["capacity: TPAMD_PLAN_MORE, buffer unchanged"]++;
+      } else {
+        CHECK(plan.status == tpamd::kBsOk);
+        if (plan.move > 0) g_counts["capacity: compaction taken"]++;
+        tpamd::bs_apply_serial(core.ref(), plan, rows, f.time.data(), f.q.data(), f.qd.data(), f.qdd.data());
+        CHECK(Insert(*mirror, ToSegment(f, D)).ok());
+        g_counts[cat]++;
+        if (cat == "insert: at or before the front (sequence back to 0)" || cat == "insert: into an empty buffer")
+          CHECK(mirror->GetSequenceNumber() == 0);
+        else
+          CHECK(mirror->GetSequenceNumber() == seq_before + 1);
+      }
+    } else if (kind < 62) {  // --------------------------------------------------------- discard
+      double time = Rnd();
+      std::string cat = "discard: empty buffer";
+      if (n > 0) {
+        const int where = RndInt(0, 9);
+        const size_t i = (size_t)RndInt(0, (int)n - 1);
+        switch (where) {
+          case 0: time = RndInt(0, 1) ? t[0] : t[0] - 1e-3 * Rnd(); break;
+          case 1: time = t[n - 1] + 1e-9 + 1e-3 * Rnd() * RndInt(0, 1); break;
+          case 2: case 3: time = t[i]; break;
+          case 4: time = t[i] + 0.5 * tol; break;
+          case 5: time = t[i] - 0.5 * tol; break;
+          default: time = i + 1 < n ? t[i] + (t[i + 1] - t[i]) * (0.1 + 0.8 * Rnd()) : t[i]; break;
+        }
+        if (time <= t[0]) cat = "discard: at or before the front";
+        else if (time > t[n - 1]) cat = "discard: after the back (cleared)";
+        else {
+          const size_t lo = std::lower_bound(t.begin(), t.end(), time) - t.begin();
+          if (lo < n && std::fabs(t[lo] - time) > tol) cat = "discard: interpolated new first sample";
+          else if (lo > 0 && time - t[lo - 1] <= tol) cat = "discard: within tolerance of the sample before";
+          else cat = "discard: on a sample";
+        }
+      }
+      const int what = tpamd::bs_discard(core.ref(), time);
+      mirror->DiscardSegmentBefore(time);
+      g_counts[cat]++;
+      const char *expect[6] = {"discard: empty buffer", "discard: at or before the front", "discard: after the back (cleared)",
+                               "discard: on a sample", "discard: within tolerance of the sample before",
+                               "discard: interpolated new first sample"};
+      CHECK(cat == expect[what]);
+      if (cat == "discard: after the back (cleared)") CHECK(mirror->GetNumSamples() == 0 && mirror->GetSequenceNumber() == 0);
+      else CHECK(mirror->GetSequenceNumber() == seq_before);
+    } else if (kind < 84) {  // --------------------------------------------------------- stop
+      std::vector<double> amax(D);
+      for (int j = 0; j < D; j++) amax[j] = 0.5 + 5.0 * Rnd();
+      const bool bad_amax = RndInt(0, 40) == 0;
+      if (bad_amax) amax[RndInt(0, D - 1)] = RndInt(0, 1) ? 0.0 : -1.0;
+      const double time_step = RndInt(0, 40) == 0 ? (RndInt(0, 1) ? 0.0 : -1e-3) : 1e-3;
+      const bool by_index = RndInt(0, 4) == 0;
+      int stop_index = RndInt(-1, (int)n);
+      double time = Rnd();
+      if (n > 0) {
+        const int where = RndInt(0, 6);
+        const size_t i = (size_t)RndInt(0, (int)n - 1);
+        time = where == 0 ? t[0] - 1e-3 * Rnd() - 1e-9 : where == 1 ? t[i] : where == 2 ? t[n - 1] + 0.5 * Rnd()
+               : where == 3 ? t[n - 1] : (i + 1 < n ? t[i] + (t[i + 1] - t[i]) * Rnd() : t[i]);
+        if (where == 5)                                     // aim at a sample at rest before the end
+          for (size_t r = 1; r + 1 < n; r++)
+            if (mirror->GetVelocities()[r].maxAbs() < 1e-8) { time = t[r - 1]; break; }
+      }
+      // the category, from the mirror's samples
+      std::string cat;
+      int index = stop_index;
+      if (!by_index && n > 0) {
+        const int lower = (int)(std::lower_bound(t.begin(), t.end(), time) - t.begin());
+        index = std::min<int>(lower + 1, (int)n - 1);
+      }
+      const bool increasing = [&] { for (int i = 0; i + 1 <= index && i + 1 < (int)n; i++) if (t[i + 1] <= t[i]) return false; return true; }();
+      const VectorXd am(amax.data(), D);
+      const Status ms = by_index ? mirror->StopAtIndex(stop_index, am, time_step) : mirror->StopBeforeTime(time, am, time_step);
+      const int mcode = Code(ms);
+      if (n == 0) cat = by_index ? "stop: empty, by index (OutOfRange)" : "stop: empty (OK)";
+      else if (!by_index && time < t[0]) cat = "stop: before the front (OutOfRange)";
+      else if (index <= 0 || index > (int)n - 1) cat = "stop: index out of range";
+      else if (bad_amax) cat = "stop: bad max_acceleration";
+      else if (time_step <= 0) cat = "stop: bad time_step";
+      else if (mcode == tpamd::kRsOk && mirror->GetSequenceNumber() == seq_before && mirror->GetNumSamples() == n &&
+               index == (int)n - 1 && mirror->GetVelocities()[n - 1].maxAbs() == 0.0)
+        cat = "stop: sequence unchanged (at-rest last sample)";
+      else if (mcode == tpamd::kRsInvalidArgument) cat = increasing ? "stop: other InvalidArgument" : "stop: non-increasing times";
+      else if (mcode == tpamd::kRsInternal) cat = "stop: at-rest mid (Internal)";
+      else if (mcode == tpamd::kRsNotFound) cat = "stop: NotFound";
+      else if (mcode == tpamd::kRsOk) {
+        cat = "stop: sequence moved";
+        CHECK(mirror->GetSequenceNumber() == seq_before + 1 || mirror->GetSequenceNumber() == 0);
+        CHECK(mirror->GetVelocities()[mirror->GetNumSamples() - 1].maxAbs() == 0.0);
+      } else cat = "stop: other status " + std::to_string(mcode);
+      if (mcode != tpamd::kRsOk) CHECK(mirror->GetNumSamples() == n && mirror->GetSequenceNumber() == seq_before);
+      int what = -1;
+      const int st = tpamd::bs_stop_in_place_any(core.ref(), by_index, stop_index, time, amax.data(), time_step, &what);
+      CHECK(st == mcode);
+      if (cat == "stop: sequence moved") {
+        CHECK(what == tpamd::kBsStopInserted);
+        // how the segment ended, and InsertSegment's step back by one
+        const size_t after = mirror->GetNumSamples();
+        g_counts[after >= 2 && mirror->GetTimes()[0] == t[0] && after <= n ? "stop: OK, cut behind the front" : "stop: OK, other"]++;
+      }
+      if (cat == "stop: sequence unchanged (at-rest last sample)") CHECK(what == tpamd::kBsStopRestOnLast);
+      if (!by_index && n > 1 && time > t[n - 1]) g_counts["stop: clamped beyond the end"]++;
+      g_counts[cat]++;
+    } else if (kind < 92) {  // --------------------------------------------------------- append
+      const bool late = n == 0 || RndInt(0, 3) != 0;
+      const double time = n == 0 ? Rnd() : late ? t[n - 1] + 1e-3 * (0.5 + Rnd()) : (RndInt(0, 1) ? t[n - 1] : t[n - 1] - 1e-3 * Rnd());
+      const Flat f = MakeRows(1, D, time);
+      const tpamd::InsertPlan plan = tpamd::bs_plan_append(core.time.data() + core.first, core.first, core.count, core.sequence, cap, time);
+      if (plan.status == tpamd::kBsMore) {
+        g_counts["capacity: TPAMD_PLAN_MORE, buffer unchanged"]++;
+      } else {
+        if (plan.move > 0) g_counts["capacity: compaction taken"]++;
+        tpamd::bs_apply_serial(core.ref(), plan, 1, f.time.data(), f.q.data(), f.qd.data(), f.qdd.data());
+        const Segment s = ToSegment(f, D);
+        const Status ms = mirror->AppendSample(time, s.positions[0], s.velocities[0], s.accelerations[0]);
+        CHECK(Code(ms) == plan.status);
+        g_counts[ms.ok() ? "append: behind the last sample" : "append: not behind the last sample (InvalidArgument)"]++;
+        CHECK(mirror->GetSequenceNumber() == seq_before);
+      }
+    } else if (kind < 98) {  // --------------------------------------------------------- offset
+      const double offset = RndInt(0, 1) ? 2.0 * Rnd() - 1.0 : (double)RndInt(-500, 500) * 1e6 / 1e9;
+      double *tm = core.time.data() + core.first;
+      for (int i = 0; i < core.count; i++) tm[i] = tm[i] + offset;       // k_bset_add_offset's statement
+      mirror->AddOffsetToTimestamps(offset);
+      g_counts["offset"]++;
+    } else {  // ------------------------------------------------------------------------ clear
+      core.first = 0; core.count = 0; core.sequence = 0;
+      mirror->Clear();
+      g_counts["clear"]++;
+    }
+    const bool same = Same(core, *mirror);
+    CHECK(same);
+    if (!same && g_fail < 25)
+      std::printf("  D %d op %d kind %d: core first %d count %d seq %d, mirror count %zu seq %d\n", D, op, kind, core.first,
+                  core.count, core.sequence, mirror->GetNumSamples(), mirror->GetSequenceNumber());
+    if (!same) return;
+    // the getters of the info readout
+    const double *ct = core.time.data() + core.first;
+    CHECK(tpamd::bs_start_ns(ct, core.count) == tpamd::compat::ToUnixNanos(mirror->GetStartTime()));
+    CHECK(tpamd::bs_end_ns(ct, core.count) == tpamd::compat::ToUnixNanos(mirror->GetEndTime()));
+    if (core.count > 0) {
+      const long long ns = (long long)((ct[0] + (ct[core.count - 1] - ct[0]) * (1.2 * Rnd() - 0.1)) * 1e9);
+      CHECK((size_t)tpamd::bs_positions_up_to(ct, core.count, (double)ns / 1e9) ==
+            mirror->GetPositionsUpToTime(tpamd::compat::FromUnixNanos(ns)).size());
+    }
+  }
+}
+
+int main() {
+  ReferenceCases();
+  const int dofs[5] = {1, 6, 7, 14, 16};
+  for (int s = 0; s < 75; s++) Sequence(dofs[s % 5], 320);
+  std::printf("operations: %ld\n", g_ops);
+  for (const auto &kv : g_counts) std::printf("category %s: %ld\n", kv.first.c_str(), kv.second);
+  if (g_fail) {
+    std::printf("%d FAILURES\n", g_fail);
+    return 1;
+  }
+  std::printf("ALL OK\n");
+  return 0;
+}

@@ -17,6 +17,7 @@
 #include "tpamd_planner_set.h"
 #include "tpamd_readout.h"
 #include "tpamd_rescale.h"
+#include "tpamd_buffer.h"
 #include "tpamd_stop.h"
 #include "tpamd_switch.h"
 #include "tpamd_fit.h"
@@ -2931,6 +2932,542 @@ int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *ps, int count,
   launch_stop_trajectories(ps->S.D, p, st);
   HIPCHK(hipGetLastError());
   return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- buffer sets
+struct tpamd_buffer_set {
+  tpamd_engine *e = nullptr;
+  void *fixed = nullptr, *rows = nullptr;   // first | count | sequence; time | q | qd | qdd (grows)
+  size_t fixed_bytes = 0, rows_bytes = 0;
+  BufferSetState S{};
+  DeviceBuffer in, out;                     // staging of the host-pointer entries; they grow
+};
+
+namespace {
+
+size_t carve_buffer_rows(char *base, size_t B, size_t cap, size_t D, BufferSetState *S) {
+  Stage st(base);
+  double *t = st.take<double>(B * cap), *q = st.take<double>(B * cap * D), *qd = st.take<double>(B * cap * D),
+         *qdd = st.take<double>(B * cap * D);
+  if (S) { S->time = t; S->q = q; S->qd = qd; S->qdd = qdd; S->cap = (int)cap; }
+  return st.off;
+}
+
+// Rows of a larger per-buffer capacity; every buffer's samples move to row 0. Synchronises.
+int bset_grow(tpamd_buffer_set *bs, int new_cap, hipStream_t st) {
+  const BufferSetState old = bs->S;
+  void *old_rows = bs->rows, *fresh = nullptr;
+  const size_t need = carve_buffer_rows(nullptr, old.B, new_cap, old.D, nullptr);
+  HIPCHK(hipMalloc(&fresh, need));
+  carve_buffer_rows((char *)fresh, old.B, new_cap, old.D, &bs->S);
+  bs->rows = fresh; bs->rows_bytes = need;
+  hipLaunchKernelGGL(k_bset_regrow, dim3((unsigned)old.B), dim3(kBsThreads), 0, st, old, bs->S);
+  hipLaunchKernelGGL(k_bset_zero_first, dim3((unsigned)((old.B + 255) / 256)), dim3(256), 0, st, old.B, old.first);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipFree(old_rows));
+  return 0;
+}
+
+// Host-pointer inserts: the listed buffers' sample counts come down, and the capacity doubles
+// until count + extra[k] rows fit every listed buffer -- before anything changes.
+int bset_make_room(tpamd_buffer_set *bs, int count, const int32_t *ids, const std::vector<long long> &extra,
+                   hipStream_t st) {
+  std::vector<int> have(bs->S.B);
+  HIPCHK(hipMemcpyAsync(have.data(), bs->S.count, have.size() * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  long long need = 0;
+  for (int k = 0; k < count; k++) need = std::max(need, (long long)have[ids ? ids[k] : k] + extra[k]);
+  if (need <= bs->S.cap) return 0;
+  long long cap = std::max(bs->S.cap, 1);
+  while (cap < need) cap *= 2;
+  if (cap > 0x3fffffff) return TPAMD_E_UNSUPPORTED;
+  return bset_grow(bs, (int)cap, st);
+}
+
+// count and ids of a call: ids null lists buffers 0 .. count-1; host ids are range-checked, and in
+// a call that changes buffers each may be listed once.
+bool bset_list_ok(const tpamd_buffer_set *bs, int count, const int32_t *ids, bool host_ids, bool mutating) {
+  if (!bs || count < 0) return false;
+  if (!ids && count > bs->S.B) return false;
+  if (ids && host_ids) {
+    std::vector<char> seen(mutating ? bs->S.B : 0, 0);
+    for (int k = 0; k < count; k++) {
+      if (ids[k] < 0 || ids[k] >= bs->S.B) return false;
+      if (mutating && seen[ids[k]]++) return false;
+    }
+  }
+  return true;
+}
+
+BufferOpParams bset_params(const tpamd_buffer_set *bs, int count) {
+  BufferOpParams p{};
+  p.S = bs->S;
+  p.count = count;
+  return p;
+}
+
+// ReadoutParams view of a buffer set: its layout is that of a planner set's resident trajectories
+ReadoutParams bset_readout_params(const tpamd_buffer_set *bs) {
+  const BufferSetState &S = bs->S;
+  ReadoutParams p{};
+  p.B = S.B; p.D = S.D; p.tcap = S.cap;
+  p.t_first = S.first; p.t_count = S.count;
+  p.t_time = S.time; p.t_q = S.q; p.t_qd = S.qd; p.t_qdd = S.qdd;
+  return p;
+}
+
+enum BsetOp { kOpInsert, kOpDiscard, kOpStop, kOpAddOffset, kOpClear, kOpInfo };
+
+// one launch on st
+int bset_launch(BsetOp op, const BufferOpParams &p, hipStream_t st) {
+  if (p.count <= 0) return 0;
+  const dim3 per_lane((unsigned)((p.count + 63) / 64)), per_group((unsigned)p.count);
+  switch (op) {
+    case kOpInsert: hipLaunchKernelGGL(k_bset_insert, per_group, dim3(kBsThreads), 0, st, p); break;
+    case kOpDiscard: hipLaunchKernelGGL(k_bset_discard, per_lane, dim3(64), 0, st, p); break;
+    case kOpStop: if (!launch_bset_stop(p, st)) return TPAMD_E_UNSUPPORTED; break;
+    case kOpAddOffset: hipLaunchKernelGGL(k_bset_add_offset, per_group, dim3(kBsThreads), 0, st, p); break;
+    case kOpClear: hipLaunchKernelGGL(k_bset_clear, per_lane, dim3(64), 0, st, p); break;
+    case kOpInfo: hipLaunchKernelGGL(k_bset_info, per_lane, dim3(64), 0, st, p); break;
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the staged form of a host-pointer call: inputs up in one copy, the launch, outputs down
+int bset_run_host(tpamd_buffer_set *bs, BsetOp op, const BufferOpParams &p, HostStage &in, HostStage &out,
+                  hipStream_t st) {
+  if (int rc = bset_launch(op, p, st)) return rc;
+  (void)bs; (void)in;
+  return out.download(st);
+}
+
+bool one_time(const void *a, const void *b) { return (a != nullptr) != (b != nullptr); }
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_buffer_set_create(tpamd_engine *e, int num_buffers, int num_dofs, int capacity, double timestep_tolerance,
+                            tpamd_buffer_set **out) {
+  if (!e || !out || num_buffers < 1 || num_dofs < 1 || capacity < 0 || !(timestep_tolerance > 0))
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (num_dofs > kRsMaxDofs) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(e);
+  tpamd_buffer_set *bs = new (std::nothrow) tpamd_buffer_set;
+  if (!bs) return TPAMD_E_HIP;
+  bs->e = e;
+  BufferSetState &S = bs->S;
+  S.B = num_buffers; S.D = num_dofs; S.tol = timestep_tolerance;
+  const int cap = capacity > 0 ? capacity : 256;
+  Stage fx(nullptr);
+  fx.take<int>(S.B); fx.take<int>(S.B); fx.take<int>(S.B);
+  bs->fixed_bytes = fx.off;
+  bs->rows_bytes = carve_buffer_rows(nullptr, S.B, cap, S.D, nullptr);
+  if (hipMalloc(&bs->fixed, bs->fixed_bytes) != hipSuccess || hipMalloc(&bs->rows, bs->rows_bytes) != hipSuccess ||
+      hipMemset(bs->fixed, 0, bs->fixed_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    tpamd_buffer_set_destroy(bs);
+    return TPAMD_E_HIP;
+  }
+  Stage f2(bs->fixed);
+  S.first = f2.take<int>(S.B); S.count = f2.take<int>(S.B); S.sequence = f2.take<int>(S.B);
+  carve_buffer_rows((char *)bs->rows, S.B, cap, S.D, &S);
+  *out = bs;
+  return 0;
+}
+
+void tpamd_buffer_set_destroy(tpamd_buffer_set *bs) {
+  if (!bs) return;
+  DeviceScope scope(bs->e->device);
+  (void)hipDeviceSynchronize();          // calls enqueued on the caller's streams may still use the rows
+  if (bs->fixed) (void)hipFree(bs->fixed);
+  if (bs->rows) (void)hipFree(bs->rows);
+  bs->in.release();
+  bs->out.release();
+  delete bs;
+}
+
+int tpamd_buffer_set_reserve(tpamd_buffer_set *bs, int capacity) {
+  if (!bs || capacity < 0) return TPAMD_E_INVALID_ARGUMENT;
+  if (capacity <= bs->S.cap) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  HIPCHK(hipDeviceSynchronize());        // earlier _device calls on other streams
+  return bset_grow(bs, capacity, nullptr);
+}
+
+int tpamd_buffer_set_capacity(const tpamd_buffer_set *bs) { return bs ? bs->S.cap : 0; }
+
+size_t tpamd_buffer_set_device_bytes(const tpamd_buffer_set *bs) {
+  return bs ? bs->fixed_bytes + bs->rows_bytes + bs->in.bytes + bs->out.bytes : 0;
+}
+
+// ---- insert
+int tpamd_buffer_set_insert(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *offsets,
+                            const double *time, const double *q, const double *qd, const double *qdd,
+                            int32_t *status) {
+  if (!bset_list_ok(bs, count, ids, true, true) || !offsets || !status) return TPAMD_E_INVALID_ARGUMENT;
+  if (offsets[0] < 0) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<long long> extra(count);
+  for (int k = 0; k < count; k++) {
+    if (offsets[k + 1] < offsets[k]) return TPAMD_E_INVALID_ARGUMENT;
+    extra[k] = offsets[k + 1] - offsets[k];
+  }
+  const size_t rows = (size_t)offsets[count], n = count, D = bs->S.D;
+  if (rows > 0 && (!time || !q || !qd || !qdd)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  if (int rc = bset_make_room(bs, count, ids, extra, st)) return rc;
+  BufferOpParams p = bset_params(bs, count);
+  HostStage in(/*packed=*/true), out;
+  in.up(&p.offsets, offsets, n + 1);
+  in.up(&p.i_time, time, rows);
+  in.up(&p.i_q, q, rows * D);
+  in.up(&p.i_qd, qd, rows * D);
+  in.up(&p.i_qdd, qdd, rows * D);
+  in.up(&p.ids, ids, n);
+  out.down(&p.status, status, n);
+  if (in.upload(bs->in, st) || out.upload(bs->out, st)) return TPAMD_E_HIP;
+  p.source = kBsFromRows; p.capacity = (long long)rows;
+  return bset_run_host(bs, kOpInsert, p, in, out, st);
+}
+
+int tpamd_buffer_set_insert_device(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *offsets,
+                                   int64_t capacity, const double *time, const double *q, const double *qd,
+                                   const double *qdd, int32_t *status, void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, true) || !offsets || !status || capacity < 0)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (capacity > 0 && (!time || !q || !qd || !qdd)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  BufferOpParams p = bset_params(bs, count);
+  p.ids = ids; p.status = status; p.source = kBsFromRows;
+  p.offsets = (const long long *)offsets; p.capacity = capacity;
+  p.i_time = time; p.i_q = q; p.i_qd = qd; p.i_qdd = qdd;
+  return bset_launch(kOpInsert, p, (hipStream_t)hip_stream);
+}
+
+static int bset_from_planner_args(const tpamd_buffer_set *bs, const tpamd_planner_set *ps) {
+  if (!bs || !ps || bs->e != ps->e || bs->S.D != ps->S.D) return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+static void bset_planner_source(BufferOpParams &p, const tpamd_planner_set *ps) {
+  p.source = kBsFromPlanners;
+  p.pB = ps->S.B; p.ptcap = ps->tcap;
+  p.t_first = ps->S.t_first; p.t_count = ps->S.t_count;
+  p.i_time = ps->S.t_time; p.i_q = ps->S.t_q; p.i_qd = ps->S.t_qd; p.i_qdd = ps->S.t_qdd;
+}
+
+int tpamd_buffer_set_insert_from_planner_set(tpamd_buffer_set *bs, tpamd_planner_set *ps, int count,
+                                             const int32_t *ids, const int32_t *planner_ids, int32_t *status) {
+  if (bset_from_planner_args(bs, ps) || !bset_list_ok(bs, count, ids, true, true) || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (!planner_ids && count > ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (planner_ids)
+    for (int k = 0; k < count; k++)
+      if (planner_ids[k] < 0 || planner_ids[k] >= ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  // a device readout of the planner set: behind its last change and its readouts in flight
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  std::vector<int> samples(ps->S.B);
+  HIPCHK(hipMemcpyAsync(samples.data(), ps->S.t_count, samples.size() * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<long long> extra(count);
+  for (int k = 0; k < count; k++) extra[k] = samples[planner_ids ? planner_ids[k] : k];
+  if (int rc = bset_make_room(bs, count, ids, extra, st)) return rc;
+  BufferOpParams p = bset_params(bs, count);
+  const size_t n = count;
+  HostStage in(/*packed=*/true), out;
+  in.up(&p.ids, ids, n);
+  in.up(&p.planner_ids, planner_ids, n);
+  out.down(&p.status, status, n);
+  if (in.upload(bs->in, st) || out.upload(bs->out, st)) return TPAMD_E_HIP;
+  bset_planner_source(p, ps);
+  return bset_run_host(bs, kOpInsert, p, in, out, st);
+}
+
+int tpamd_buffer_set_insert_from_planner_set_device(tpamd_buffer_set *bs, tpamd_planner_set *ps, int count,
+                                                    const int32_t *ids, const int32_t *planner_ids,
+                                                    int32_t *status, void *hip_stream) {
+  if (bset_from_planner_args(bs, ps) || !bset_list_ok(bs, count, ids, false, true) || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (!planner_ids && count > ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  BufferOpParams p = bset_params(bs, count);
+  p.ids = ids; p.planner_ids = planner_ids; p.status = status;
+  bset_planner_source(p, ps);
+  if (int rc = bset_launch(kOpInsert, p, st)) return rc;
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+// ---- append
+int tpamd_buffer_set_append_sample(tpamd_buffer_set *bs, int count, const int32_t *ids, const double *time,
+                                   const double *q, const double *qd, const double *qdd, int32_t *status) {
+  if (!bset_list_ok(bs, count, ids, true, true) || !time || !q || !qd || !qdd || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  if (int rc = bset_make_room(bs, count, ids, std::vector<long long>(count, 1), st)) return rc;
+  BufferOpParams p = bset_params(bs, count);
+  const size_t n = count, D = bs->S.D;
+  HostStage in(/*packed=*/true), out;
+  in.up(&p.i_time, time, n);
+  in.up(&p.i_q, q, n * D);
+  in.up(&p.i_qd, qd, n * D);
+  in.up(&p.i_qdd, qdd, n * D);
+  in.up(&p.ids, ids, n);
+  out.down(&p.status, status, n);
+  if (in.upload(bs->in, st) || out.upload(bs->out, st)) return TPAMD_E_HIP;
+  p.source = kBsAppend;
+  return bset_run_host(bs, kOpInsert, p, in, out, st);
+}
+
+int tpamd_buffer_set_append_sample_device(tpamd_buffer_set *bs, int count, const int32_t *ids, const double *time,
+                                          const double *q, const double *qd, const double *qdd, int32_t *status,
+                                          void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, true) || !time || !q || !qd || !qdd || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  BufferOpParams p = bset_params(bs, count);
+  p.ids = ids; p.status = status; p.source = kBsAppend;
+  p.i_time = time; p.i_q = q; p.i_qd = qd; p.i_qdd = qdd;
+  return bset_launch(kOpInsert, p, (hipStream_t)hip_stream);
+}
+
+// ---- discard, add_offset, clear: a time (or none) per listed buffer, nothing comes back
+static int bset_simple_host(tpamd_buffer_set *bs, BsetOp op, int count, const int32_t *ids, const int64_t *time_ns,
+                            const double *time_sec) {
+  if (!bset_list_ok(bs, count, ids, true, true)) return TPAMD_E_INVALID_ARGUMENT;
+  if (op != kOpClear && !one_time(time_ns, time_sec)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  BufferOpParams p = bset_params(bs, count);
+  const size_t n = count;
+  HostStage in(/*packed=*/true), out;
+  in.up(&p.time_ns, time_ns, n);
+  in.up(&p.time_sec, time_sec, n);
+  in.up(&p.ids, ids, n);
+  if (in.upload(bs->in, st)) return TPAMD_E_HIP;
+  return bset_run_host(bs, op, p, in, out, st);
+}
+static int bset_simple_device(tpamd_buffer_set *bs, BsetOp op, int count, const int32_t *ids, const int64_t *time_ns,
+                              const double *time_sec, int32_t *status, void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, true)) return TPAMD_E_INVALID_ARGUMENT;
+  if (op != kOpClear && !one_time(time_ns, time_sec)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  BufferOpParams p = bset_params(bs, count);
+  p.ids = ids; p.status = status;
+  p.time_ns = (const long long *)time_ns; p.time_sec = time_sec;
+  return bset_launch(op, p, (hipStream_t)hip_stream);
+}
+
+int tpamd_buffer_set_discard_before(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *time_ns,
+                                    const double *time_sec) {
+  return bset_simple_host(bs, kOpDiscard, count, ids, time_ns, time_sec);
+}
+int tpamd_buffer_set_discard_before_device(tpamd_buffer_set *bs, int count, const int32_t *ids,
+                                           const int64_t *time_ns, const double *time_sec, int32_t *status,
+                                           void *hip_stream) {
+  return bset_simple_device(bs, kOpDiscard, count, ids, time_ns, time_sec, status, hip_stream);
+}
+int tpamd_buffer_set_add_offset(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *offset_ns,
+                                const double *offset_sec) {
+  return bset_simple_host(bs, kOpAddOffset, count, ids, offset_ns, offset_sec);
+}
+int tpamd_buffer_set_add_offset_device(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *offset_ns,
+                                       const double *offset_sec, int32_t *status, void *hip_stream) {
+  return bset_simple_device(bs, kOpAddOffset, count, ids, offset_ns, offset_sec, status, hip_stream);
+}
+int tpamd_buffer_set_clear(tpamd_buffer_set *bs, int count, const int32_t *ids) {
+  return bset_simple_host(bs, kOpClear, count, ids, nullptr, nullptr);
+}
+int tpamd_buffer_set_clear_device(tpamd_buffer_set *bs, int count, const int32_t *ids, int32_t *status,
+                                  void *hip_stream) {
+  return bset_simple_device(bs, kOpClear, count, ids, nullptr, nullptr, status, hip_stream);
+}
+
+// ---- stop
+int tpamd_buffer_set_stop_before_time(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *time_ns,
+                                      const double *time_sec, const double *max_acceleration, double time_step,
+                                      int32_t *status) {
+  if (!bset_list_ok(bs, count, ids, true, true) || !one_time(time_ns, time_sec) || !max_acceleration || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  BufferOpParams p = bset_params(bs, count);
+  const size_t n = count, D = bs->S.D;
+  HostStage in(/*packed=*/true), out;
+  in.up(&p.time_ns, time_ns, n);
+  in.up(&p.time_sec, time_sec, n);
+  in.up(&p.amax, max_acceleration, n * D);
+  in.up(&p.ids, ids, n);
+  out.down(&p.status, status, n);
+  if (in.upload(bs->in, st) || out.upload(bs->out, st)) return TPAMD_E_HIP;
+  p.time_step = time_step;
+  return bset_run_host(bs, kOpStop, p, in, out, st);
+}
+
+int tpamd_buffer_set_stop_before_time_device(tpamd_buffer_set *bs, int count, const int32_t *ids,
+                                             const int64_t *time_ns, const double *time_sec,
+                                             const double *max_acceleration, double time_step, int32_t *status,
+                                             void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, true) || !one_time(time_ns, time_sec) || !max_acceleration || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  BufferOpParams p = bset_params(bs, count);
+  p.ids = ids; p.status = status;
+  p.time_ns = (const long long *)time_ns; p.time_sec = time_sec;
+  p.amax = max_acceleration; p.time_step = time_step;
+  return bset_launch(kOpStop, p, (hipStream_t)hip_stream);
+}
+
+// ---- info
+int tpamd_buffer_set_info(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *time_ns,
+                          int32_t *num_samples, int32_t *sequence, int64_t *start_ns, int64_t *end_ns,
+                          int32_t *positions_up_to) {
+  if (!bset_list_ok(bs, count, ids, true, false) || (positions_up_to && !time_ns)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  BufferOpParams p = bset_params(bs, count);
+  const size_t n = count;
+  HostStage in(/*packed=*/true), out(/*packed=*/true);
+  in.up(&p.time_ns, time_ns, n);
+  in.up(&p.ids, ids, n);
+  out.down(&p.o_start_ns, start_ns, n);
+  out.down(&p.o_end_ns, end_ns, n);
+  out.down(&p.o_count, num_samples, n);
+  out.down(&p.o_sequence, sequence, n);
+  out.down(&p.o_up_to, positions_up_to, n);
+  if (in.upload(bs->in, st) || out.upload(bs->out, st)) return TPAMD_E_HIP;
+  return bset_run_host(bs, kOpInfo, p, in, out, st);
+}
+
+int tpamd_buffer_set_info_device(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *time_ns,
+                                 int32_t *num_samples, int32_t *sequence, int64_t *start_ns, int64_t *end_ns,
+                                 int32_t *positions_up_to, void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, false) || (positions_up_to && !time_ns)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  BufferOpParams p = bset_params(bs, count);
+  p.ids = ids; p.time_ns = (const long long *)time_ns;
+  p.o_count = num_samples; p.o_sequence = sequence; p.o_up_to = positions_up_to;
+  p.o_start_ns = (long long *)start_ns; p.o_end_ns = (long long *)end_ns;
+  return bset_launch(kOpInfo, p, (hipStream_t)hip_stream);
+}
+
+// ---- sample_at_ticks and the packed download: the readout kernels on the buffer set's rows
+int tpamd_buffer_set_sample_at_ticks(tpamd_buffer_set *bs, int count, const int32_t *ids, const int64_t *start_ns,
+                                     int64_t step_ns, int num_ticks, double *q, double *qd, double *qdd,
+                                     int32_t *status) {
+  if (!bset_list_ok(bs, count, ids, true, false) || !start_ns || !status || step_ns <= 0 || num_ticks < 1)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  const size_t n = count, T = num_ticks, D = bs->S.D, ticks = n * T;
+  if ((ticks + 255) / 256 > 0x7fffffff) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  ReadoutParams p = bset_readout_params(bs);
+  std::vector<double> values[3];   // q, qd, qdd as they come down
+  double *dst[3] = {q, qd, qdd}, **dev[3] = {&p.q, &p.qd, &p.qdd};
+  HostStage in(/*packed=*/true, /*tight=*/true), out;
+  in.up(&p.start_ns, start_ns, n);
+  in.up(&p.ids, ids, n);
+  out.down(&p.status, status, ticks);
+  for (int a = 0; a < 3; a++) {
+    if (dst[a]) values[a].resize(ticks * D);
+    out.down(dev[a], dst[a] ? values[a].data() : nullptr, ticks * D);
+  }
+  if (in.upload(bs->in, st) || out.upload(bs->out, st)) return TPAMD_E_HIP;
+  p.count = count; p.num_ticks = num_ticks; p.step_ns = step_ns;
+  hipLaunchKernelGGL(k_pset_sample_at_ticks, dim3((unsigned)((ticks + 255) / 256)), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  if (int rc = out.download(st)) return rc;
+  for (int a = 0; a < 3; a++) {    // only the OK ticks reach the caller's arrays
+    if (!dst[a]) continue;
+    for (size_t i = 0; i < ticks; i++)
+      if (status[i] == TPAMD_PLAN_OK) std::memcpy(dst[a] + i * D, values[a].data() + i * D, D * 8);
+  }
+  return 0;
+}
+
+int tpamd_buffer_set_sample_at_ticks_device(tpamd_buffer_set *bs, int count, const int32_t *ids,
+                                            const int64_t *start_ns, int64_t step_ns, int num_ticks, double *q,
+                                            double *qd, double *qdd, int32_t *status, void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, false) || !start_ns || !status || step_ns <= 0 || num_ticks < 1)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  const size_t ticks = (size_t)count * num_ticks;
+  if ((ticks + 255) / 256 > 0x7fffffff) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(bs->e);
+  ReadoutParams p = bset_readout_params(bs);
+  p.count = count; p.num_ticks = num_ticks; p.ids = ids;
+  p.start_ns = (const long long *)start_ns; p.step_ns = step_ns;
+  p.q = q; p.qd = qd; p.qdd = qdd; p.status = status;
+  hipLaunchKernelGGL(k_pset_sample_at_ticks, dim3((unsigned)((ticks + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, p);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_buffer_set_download(tpamd_buffer_set *bs, int count, const int32_t *ids, int64_t *offsets,
+                              int64_t capacity, double *time, double *q, double *qd, double *qdd) {
+  if (!bset_list_ok(bs, count, ids, true, false) || !offsets || capacity < 0) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) {
+    offsets[0] = 0;
+    return 0;
+  }
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = nullptr;
+  const size_t n = count, D = bs->S.D;
+  ReadoutParams p = bset_readout_params(bs);
+  HostStage in(/*packed=*/false, /*tight=*/true);
+  in.down(&p.offsets, offsets, n + 1);
+  in.up(&p.ids, ids, n);
+  int rc = in.upload(bs->in, st);
+  if (rc) return rc;
+  p.count = count;
+  hipLaunchKernelGGL(k_pset_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, p);
+  HIPCHK(hipGetLastError());
+  rc = in.download(st);
+  if (rc) return rc;
+  const size_t rows = (size_t)offsets[count];
+  if ((int64_t)rows > capacity) return TPAMD_E_INVALID_ARGUMENT;
+  HostStage out;
+  out.down(&p.o_time, time, rows);
+  out.down(&p.o_q, q, rows * D);
+  out.down(&p.o_qd, qd, rows * D);
+  out.down(&p.o_qdd, qdd, rows * D);
+  if (rows == 0 || out.bytes() == 0) return 0;
+  rc = out.upload(bs->out, st);
+  if (rc) return rc;
+  p.capacity = (long long)rows;
+  hipLaunchKernelGGL(k_pset_pack_trajectories, dim3((unsigned)n), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  return out.download(st);
+}
+
+int tpamd_buffer_set_download_device(tpamd_buffer_set *bs, int count, const int32_t *ids, int64_t *offsets,
+                                     int64_t capacity, double *time, double *q, double *qd, double *qdd,
+                                     void *hip_stream) {
+  if (!bset_list_ok(bs, count, ids, false, false) || !offsets || capacity < 0) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(bs->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  ReadoutParams p = bset_readout_params(bs);
+  p.count = count; p.ids = ids; p.offsets = (long long *)offsets; p.capacity = capacity;
+  p.o_time = time; p.o_q = q; p.o_qd = qd; p.o_qdd = qdd;
+  hipLaunchKernelGGL(k_pset_scan_offsets, dim3(1), dim3(kScanThreads), 0, st, p);      // offsets[0] = 0 for none
+  if (count > 0) hipLaunchKernelGGL(k_pset_pack_trajectories, dim3((unsigned)count), dim3(256), 0, st, p);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

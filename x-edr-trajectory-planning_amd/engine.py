@@ -16,7 +16,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
-            "tpamd_rescale.h", "tpamd_fit.h", "tpamd_fit.hip"]
+            "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -214,6 +214,18 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
     "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
     "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
+    "tpamd_buffer_set_create", "tpamd_buffer_set_destroy", "tpamd_buffer_set_reserve", "tpamd_buffer_set_capacity",
+    "tpamd_buffer_set_device_bytes",
+    "tpamd_buffer_set_insert", "tpamd_buffer_set_insert_device",
+    "tpamd_buffer_set_insert_from_planner_set", "tpamd_buffer_set_insert_from_planner_set_device",
+    "tpamd_buffer_set_append_sample", "tpamd_buffer_set_append_sample_device",
+    "tpamd_buffer_set_discard_before", "tpamd_buffer_set_discard_before_device",
+    "tpamd_buffer_set_stop_before_time", "tpamd_buffer_set_stop_before_time_device",
+    "tpamd_buffer_set_sample_at_ticks", "tpamd_buffer_set_sample_at_ticks_device",
+    "tpamd_buffer_set_add_offset", "tpamd_buffer_set_add_offset_device",
+    "tpamd_buffer_set_clear", "tpamd_buffer_set_clear_device",
+    "tpamd_buffer_set_info", "tpamd_buffer_set_info_device",
+    "tpamd_buffer_set_download", "tpamd_buffer_set_download_device",
     "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
     "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
     "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_kernel_vgprs",
@@ -324,6 +336,29 @@ def load_library():
     L.tpamd_planner_set_stop_trajectories_device.argtypes = (
         [vp, i, vp, vp, vp, C.c_double, vp, vp, vp, i64] + [vp] * 4 + [vp])
     L.tpamd_stop_trajectories_device.argtypes = [vp, vp, vp]
+    dbl = C.c_double
+    for name, args in (
+            ("create", [vp, i, i, i, dbl, C.POINTER(vp)]), ("reserve", [vp, i]), ("capacity", [vp]),
+            ("insert", [vp, i] + [vp] * 7), ("insert_device", [vp, i, vp, vp, i64] + [vp] * 6),
+            ("insert_from_planner_set", [vp, vp, i, vp, vp, vp]),
+            ("insert_from_planner_set_device", [vp, vp, i, vp, vp, vp, vp]),
+            ("append_sample", [vp, i] + [vp] * 6), ("append_sample_device", [vp, i] + [vp] * 7),
+            ("discard_before", [vp, i, vp, vp, vp]), ("discard_before_device", [vp, i] + [vp] * 5),
+            ("stop_before_time", [vp, i, vp, vp, vp, vp, dbl, vp]),
+            ("stop_before_time_device", [vp, i, vp, vp, vp, vp, dbl, vp, vp]),
+            ("sample_at_ticks", [vp, i, vp, vp, i64, i] + [vp] * 4),
+            ("sample_at_ticks_device", [vp, i, vp, vp, i64, i] + [vp] * 5),
+            ("add_offset", [vp, i, vp, vp, vp]), ("add_offset_device", [vp, i] + [vp] * 5),
+            ("clear", [vp, i, vp]), ("clear_device", [vp, i, vp, vp, vp]),
+            ("info", [vp, i] + [vp] * 7), ("info_device", [vp, i] + [vp] * 8),
+            ("download", [vp, i, vp, vp, i64] + [vp] * 4), ("download_device", [vp, i, vp, vp, i64] + [vp] * 5)):
+        f = getattr(L, "tpamd_buffer_set_" + name)
+        f.restype = i
+        f.argtypes = args
+    L.tpamd_buffer_set_destroy.restype = None
+    L.tpamd_buffer_set_destroy.argtypes = [vp]
+    L.tpamd_buffer_set_device_bytes.restype = C.c_size_t
+    L.tpamd_buffer_set_device_bytes.argtypes = [vp]
     L.tpamd_stop_trajectories_host.argtypes = [vp, vp]
     # planner sets (PlannerSet)
     for name in ("tpamd_planner_set_create", "tpamd_planner_set_upload_paths",
@@ -1013,6 +1048,251 @@ class PlannerSet:
             capacity = rows
         for k in ("time", "q", "qd", "qdd"):
             out[k] = out[k][:rows]
+        return out
+
+
+class BufferSet:
+    """B trajectory buffers (TrajectoryBuffer: samples of time, q, qd, qdd, a sample count and a
+    sequence number each) resident on the device (include/tpamd.h tpamd_buffer_set_*). It is what
+    a controller executes: after each plan the new trajectory is spliced in, consumed samples are
+    discarded, setpoints are read at control ticks, and a stop changes the buffer:
+
+        with BufferSet(engine, B, D, capacity=2048) as bs:
+            ps.plan(start_ns, horizon_ns)
+            bs.insert_from(ps)                                  # device to device
+            bs.discard_before(now_ns)
+            sp = bs.sample_at_ticks(now_ns, step_ns, 1)         # CUDA [B][1][D]
+
+    Every array is a CUDA tensor and every call goes through the _device entry on torch's current
+    stream (or `stream`); ids (int32 CUDA tensor, each buffer listed once in calls that change
+    buffers; None: buffers 0..count-1). Results are dicts of CUDA tensors; per-buffer outcomes are
+    TPAMD_PLAN_* codes in `status` (100, TPAMD_PLAN_MORE: no room, call reserve()). Errors of the
+    call itself raise TpamdError."""
+
+    def __init__(self, engine, num_buffers, num_dofs, capacity=0, timestep_tolerance=1e-6):
+        self._lib = load_library()
+        self.B, self.D = int(num_buffers), int(num_dofs)
+        self.device = engine.device
+        h = C.c_void_p()
+        _check(self._lib.tpamd_buffer_set_create(engine._h, self.B, self.D, int(capacity), float(timestep_tolerance),
+                                                 C.byref(h)), "tpamd_buffer_set_create")
+        self._engine = engine          # the set must not outlive its engine
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tpamd_buffer_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise TpamdError("the buffer set is closed")
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._lib.tpamd_buffer_set_device_bytes(self._handle())
+
+    @property
+    def capacity(self):
+        return self._lib.tpamd_buffer_set_capacity(self._handle())
+
+    def reserve(self, capacity):
+        """Room for `capacity` samples per buffer (synchronises; the other calls never allocate)."""
+        _check(self._lib.tpamd_buffer_set_reserve(self._handle(), int(capacity)), "tpamd_buffer_set_reserve")
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    def _t(self, x, dtype, shape, what):
+        import torch
+        if x is None:
+            return None
+        if not _is_cuda(x):
+            x = torch.as_tensor(x).to(self._dev())
+        x = x.to(dtype).contiguous()
+        if shape is not None and tuple(x.shape) != tuple(shape):
+            raise TpamdError("%s has shape %s, expected %s" % (what, tuple(x.shape), tuple(shape)))
+        return x
+
+    def _list(self, ids, count):
+        import torch
+        if ids is None:
+            n = self.B if count is None else int(count)
+            if n > self.B:
+                raise TpamdError("more entries than buffers")
+            return None, n
+        idt = self._t(ids, torch.int32, None, "ids").reshape(-1)
+        if count is not None and idt.shape[0] != count:
+            raise TpamdError("one entry per listed buffer")
+        return idt, idt.shape[0]
+
+    def _status(self, n):
+        import torch
+        return torch.full((n,), -1, dtype=torch.int32, device=self._dev())
+
+    def _times(self, time_ns, time_sec):
+        import torch
+        if (time_ns is None) == (time_sec is None):
+            raise TpamdError("give the time either in nanoseconds or in seconds")
+        if time_ns is not None:
+            t = self._t(time_ns, torch.int64, None, "time_ns").reshape(-1)
+            return t, None, t.shape[0]
+        t = self._t(time_sec, torch.float64, None, "time_sec").reshape(-1)
+        return None, t, t.shape[0]
+
+    def insert(self, time, q, qd, qdd, offsets, ids=None, stream=None):
+        """InsertSegment: buffer k receives rows offsets[k]:offsets[k + 1] of time [rows] and q, qd,
+        qdd [rows][D], the packed layout of PlannerSet.download_trajectories / stop_trajectories
+        (their dicts can be passed on as they are). Returns dict status."""
+        import torch
+        off = self._t(offsets, torch.int64, None, "offsets").reshape(-1)
+        idt, n = self._list(ids, off.shape[0] - 1)
+        tm = self._t(time, torch.float64, None, "time").reshape(-1)
+        rows = tm.shape[0]
+        arr = [self._t(a, torch.float64, (rows, self.D), k) for k, a in (("q", q), ("qd", qd), ("qdd", qdd))]
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_insert_device(
+            self._handle(), n, _ptr(idt), _ptr(off), rows, *[_ptr(a) if rows else None for a in [tm] + arr],
+            _ptr(st), _stream_ptr(stream)), "tpamd_buffer_set_insert_device")
+        return dict(status=st, _keep=(idt, off, tm, arr))
+
+    def insert_from(self, planner_set, ids=None, planner_ids=None, stream=None):
+        """InsertSegment of the resident trajectories of a PlannerSet on the same engine, device to
+        device: buffer ids[k] receives planner planner_ids[k]'s trajectory. Returns dict status."""
+        import torch
+        pid = None if planner_ids is None else self._t(planner_ids, torch.int32, None, "planner_ids").reshape(-1)
+        idt, n = self._list(ids, None if pid is None else pid.shape[0])
+        if pid is None and ids is None:
+            n = min(self.B, planner_set.B)
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_insert_from_planner_set_device(
+            self._handle(), planner_set._handle(), n, _ptr(idt), _ptr(pid), _ptr(st), _stream_ptr(stream)),
+            "tpamd_buffer_set_insert_from_planner_set_device")
+        return dict(status=st, _keep=(idt, pid))
+
+    def append_sample(self, time, q, qd, qdd, ids=None, stream=None):
+        """AppendSample: time [count], q, qd, qdd [count][D]. Returns dict status."""
+        import torch
+        tm = self._t(time, torch.float64, None, "time").reshape(-1)
+        idt, n = self._list(ids, tm.shape[0])
+        arr = [self._t(a, torch.float64, (n, self.D), k) for k, a in (("q", q), ("qd", qd), ("qdd", qdd))]
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_append_sample_device(
+            self._handle(), n, _ptr(idt), _ptr(tm), *[_ptr(a) for a in arr], _ptr(st), _stream_ptr(stream)),
+            "tpamd_buffer_set_append_sample_device")
+        return dict(status=st, _keep=(idt, tm, arr))
+
+    def discard_before(self, time_ns=None, time_sec=None, ids=None, stream=None):
+        """DiscardSegmentBefore at time_ns [count] (int64) or time_sec [count]. Returns dict status."""
+        tn, ts, n = self._times(time_ns, time_sec)
+        idt, n = self._list(ids, n)
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_discard_before_device(
+            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(ts), _ptr(st), _stream_ptr(stream)),
+            "tpamd_buffer_set_discard_before_device")
+        return dict(status=st, _keep=(idt, tn, ts))
+
+    def stop_before_time(self, max_acceleration, time_step, time_ns=None, time_sec=None, ids=None, stream=None):
+        """StopBeforeTime in place: max_acceleration [count][D]. Returns dict status."""
+        import torch
+        tn, ts, n = self._times(time_ns, time_sec)
+        idt, n = self._list(ids, n)
+        am = self._t(max_acceleration, torch.float64, (n, self.D), "max_acceleration")
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_stop_before_time_device(
+            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(ts), _ptr(am), float(time_step), _ptr(st),
+            _stream_ptr(stream)), "tpamd_buffer_set_stop_before_time_device")
+        return dict(status=st, _keep=(idt, tn, ts, am))
+
+    def sample_at_ticks(self, start_ns, step_ns, num_ticks, ids=None, stream=None):
+        """Setpoints at ticks start_ns[k] + j step_ns: dict q, qd, qdd [count][num_ticks][D] (NaN
+        where the tick is not OK) and status [count][num_ticks]."""
+        import torch
+        s0 = self._t(start_ns, torch.int64, None, "start_ns").reshape(-1)
+        idt, n = self._list(ids, s0.shape[0])
+        T = int(num_ticks)
+        out = {k: torch.full((n, T, self.D), float("nan"), dtype=torch.float64, device=self._dev())
+               for k in ("q", "qd", "qdd")}
+        out["status"] = torch.full((n, T), -1, dtype=torch.int32, device=self._dev())
+        _check(self._lib.tpamd_buffer_set_sample_at_ticks_device(
+            self._handle(), n, _ptr(idt), _ptr(s0), int(step_ns), T, _ptr(out["q"]), _ptr(out["qd"]),
+            _ptr(out["qdd"]), _ptr(out["status"]), _stream_ptr(stream)), "tpamd_buffer_set_sample_at_ticks_device")
+        out["_keep"] = (idt, s0)
+        return out
+
+    def add_offset(self, offset_ns=None, offset_sec=None, ids=None, stream=None):
+        """AddOffsetToTimestamps: offset_sec [count], or offset_ns [count] (a duration)."""
+        tn, ts, n = self._times(offset_ns, offset_sec)
+        idt, n = self._list(ids, n)
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_add_offset_device(
+            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(ts), _ptr(st), _stream_ptr(stream)),
+            "tpamd_buffer_set_add_offset_device")
+        return dict(status=st, _keep=(idt, tn, ts))
+
+    def clear(self, ids=None, stream=None):
+        idt, n = self._list(ids, None)
+        st = self._status(n)
+        _check(self._lib.tpamd_buffer_set_clear_device(self._handle(), n, _ptr(idt), _ptr(st), _stream_ptr(stream)),
+               "tpamd_buffer_set_clear_device")
+        return dict(status=st, _keep=(idt,))
+
+    def info(self, time_ns=None, ids=None, stream=None):
+        """dict num_samples, sequence (int32), start_ns, end_ns (int64) and, with time_ns,
+        positions_up_to (the size of GetPositionsUpToTime) per listed buffer."""
+        import torch
+        tn = None if time_ns is None else self._t(time_ns, torch.int64, None, "time_ns").reshape(-1)
+        idt, n = self._list(ids, None if tn is None else tn.shape[0])
+        dev = self._dev()
+        out = dict(num_samples=torch.zeros(n, dtype=torch.int32, device=dev),
+                   sequence=torch.zeros(n, dtype=torch.int32, device=dev),
+                   start_ns=torch.zeros(n, dtype=torch.int64, device=dev),
+                   end_ns=torch.zeros(n, dtype=torch.int64, device=dev))
+        if tn is not None:
+            out["positions_up_to"] = torch.zeros(n, dtype=torch.int32, device=dev)
+        _check(self._lib.tpamd_buffer_set_info_device(
+            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(out["num_samples"]), _ptr(out["sequence"]),
+            _ptr(out["start_ns"]), _ptr(out["end_ns"]), _ptr(out.get("positions_up_to")), _stream_ptr(stream)),
+            "tpamd_buffer_set_info_device")
+        out["_keep"] = (idt, tn)
+        return out
+
+    def download(self, ids=None, capacity=None, stream=None):
+        """The listed buffers' samples packed into CUDA tensors: dict offsets [count + 1] and time
+        [rows], q, qd, qdd [rows][D]; buffer k's rows are offsets[k]:offsets[k + 1]. `capacity`
+        rows are allocated (default: count x the set's capacity)."""
+        import torch
+        idt, n = self._list(ids, None)
+        dev = self._dev()
+        rows = int(capacity) if capacity is not None else n * self.capacity
+        out = dict(offsets=torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                   time=torch.empty(rows, dtype=torch.float64, device=dev))
+        for k in ("q", "qd", "qdd"):
+            out[k] = torch.empty(rows, self.D, dtype=torch.float64, device=dev)
+        _check(self._lib.tpamd_buffer_set_download_device(
+            self._handle(), n, _ptr(idt), _ptr(out["offsets"]), rows,
+            *[_ptr(out[k]) if rows else None for k in ("time", "q", "qd", "qdd")], _stream_ptr(stream)),
+            "tpamd_buffer_set_download_device")
+        total = int(out["offsets"][-1].item())
+        if total > rows:
+            raise TpamdError("the buffers hold %d rows, capacity %d" % (total, rows))
+        for k in ("time", "q", "qd", "qdd"):
+            out[k] = out[k][:total]
+        out["_keep"] = (idt,)
         return out
 
 

@@ -141,6 +141,10 @@ class PathTimingTrajectorySet {
   // Bytes the last Plan call moved over PCIe, both directions.
   size_t LastPlanBytesOverPcie() const;
   size_t DeviceBytes() const;
+  // The C-ABI set and its engine, for objects that work on the resident trajectories in place
+  // (TrajectoryBufferSet::InsertFromPlannerSet). They stay owned by this set.
+  tpamd_planner_set *native_handle() const { return set_; }
+  tpamd_engine *engine() const { return lease_.get(); }
 
  private:
   const PathTimingTrajectoryOptions options_;

@@ -1,5 +1,4 @@
-// TrajectoryBuffer (trajectory_buffer.cc), the part that stopping needs, restated on the compat
-// types. Quirks of the reference are kept on purpose: InsertSegment's upper_bound with a <= b and
+// TrajectoryBuffer (trajectory_buffer.cc) restated on the compat types. Quirks of the reference are kept on purpose: InsertSegment's upper_bound with a <= b and
 // its step back by one within the tolerance, and StopAtIndex validating time_step without using it.
 #include "trajectory_buffer.h"
 
@@ -19,7 +18,22 @@ StatusOr<std::shared_ptr<TrajectoryBuffer>> TrajectoryBuffer::Create(TrajectoryB
   return std::shared_ptr<TrajectoryBuffer>(new TrajectoryBuffer(options));
 }
 
+static double TimeToSec(Time time) { return (double)::tpamd::compat::ToUnixNanos(time) / 1e9; }
+static Time TimeFromSec(double seconds) { return ::tpamd::compat::FromUnixSeconds(seconds); }
+
+Time TrajectoryBuffer::GetStartTime() const { return TimeFromSec(times_.empty() ? 0.0 : times_.front()); }
+
+Time TrajectoryBuffer::GetEndTime() const { return times_.empty() ? Time() : TimeFromSec(times_.back()); }
+
+void TrajectoryBuffer::Reserve(size_t size) {
+  times_.reserve(size);
+  positions_.reserve(size);
+  velocities_.reserve(size);
+  accelerations_.reserve(size);
+}
+
 void TrajectoryBuffer::Clear() {
+  sequence_number_ = 0;
   times_.clear();
   positions_.clear();
   velocities_.clear();
@@ -34,6 +48,7 @@ Status TrajectoryBuffer::InsertSegment(Span<const double> times, Span<const Vect
     return ::tpamd::compat::InvalidArgumentError("positions and accelerations arguments have different size.");
   if (positions.size() != times.size())
     return ::tpamd::compat::InvalidArgumentError("positions and times arguments have different size.");
+  sequence_number_++;
   if (positions.empty()) return ::tpamd::compat::OkStatus();
 
   // the first sample later than times.front()
@@ -44,6 +59,7 @@ Status TrajectoryBuffer::InsertSegment(Span<const double> times, Span<const Vect
     positions_.assign(positions.begin(), positions.end());
     velocities_.assign(velocities.begin(), velocities.end());
     accelerations_.assign(accelerations.begin(), accelerations.end());
+    sequence_number_ = 0;
     return ::tpamd::compat::OkStatus();
   }
   // the new first sample is just after an existing one: replace that one
@@ -73,7 +89,69 @@ StatusOr<VectorXd> TrajectoryBuffer::ValueAtTime(const std::vector<VectorXd> &va
   return v;
 }
 
-static double TimeToSec(Time time) { return (double)::tpamd::compat::ToUnixNanos(time) / 1e9; }
+Status TrajectoryBuffer::AppendSample(double time, const VectorXd &positions, const VectorXd &velocities,
+                                      const VectorXd &accelerations) {
+  if (!times_.empty() && times_.back() >= time)
+    return ::tpamd::compat::InvalidArgumentError("time must be > times_.back().");
+  times_.push_back(time);
+  positions_.push_back(positions);
+  velocities_.push_back(velocities);
+  accelerations_.push_back(accelerations);
+  return ::tpamd::compat::OkStatus();
+}
+
+void TrajectoryBuffer::DiscardSegmentBefore(Time time) { DiscardSegmentBefore(TimeToSec(time)); }
+
+void TrajectoryBuffer::DiscardSegmentBefore(const double time_sec) {
+  if (times_.empty()) return;
+  if (time_sec <= times_.front()) return;
+  if (time_sec > times_.back()) {
+    Clear();
+    return;
+  }
+  // the first sample at or after time_sec
+  int offset = (int)(std::upper_bound(times_.begin(), times_.end(), time_sec,
+                                      [](const double a, const double b) { return a <= b; }) -
+                     times_.begin());
+  if (offset <= 0) return;
+  if (offset >= (int)times_.size()) offset = (int)times_.size() - 1;   // unsorted times only
+  // The sample before it stays if it is within the tolerance of time_sec, or if it is to become
+  // the interpolated first sample.
+  const bool close_to_existing_sample = time_sec - times_[offset - 1] <= options_.timestep_tolerance;
+  const bool create_initial_sample_by_interpolation =
+      std::fabs(times_[offset] - time_sec) > options_.timestep_tolerance;
+  if (close_to_existing_sample || create_initial_sample_by_interpolation) --offset;
+  if (create_initial_sample_by_interpolation) {
+    const auto start_position = GetPositionAtTime(time_sec);
+    const auto start_velocity = GetVelocityAtTime(time_sec);
+    const auto start_acceleration = GetAccelerationAtTime(time_sec);
+    if (start_position.ok() && start_velocity.ok() && start_acceleration.ok()) {   // by construction
+      times_[offset] = time_sec;
+      positions_[offset] = *start_position;
+      velocities_[offset] = *start_velocity;
+      accelerations_[offset] = *start_acceleration;
+    }
+  }
+  times_.erase(times_.begin(), times_.begin() + offset);
+  positions_.erase(positions_.begin(), positions_.begin() + offset);
+  velocities_.erase(velocities_.begin(), velocities_.begin() + offset);
+  accelerations_.erase(accelerations_.begin(), accelerations_.begin() + offset);
+}
+
+Span<const VectorXd> TrajectoryBuffer::GetPositionsUpToTime(Time time) const {
+  if (times_.empty()) return Span<const VectorXd>();
+  const double time_sec = TimeToSec(time);
+  if (time_sec < times_.front() || time_sec > times_.back()) return Span<const VectorXd>();
+  const auto it = std::upper_bound(times_.begin(), times_.end(), time_sec);   // the first sample after time
+  return Span<const VectorXd>(positions_.data(), (size_t)((it - 1) - times_.begin()));
+}
+
+void TrajectoryBuffer::AddOffsetToTimestamps(::tpamd::compat::Duration offset) {
+  AddOffsetToTimestamps(offset / ::tpamd::compat::Seconds(1));
+}
+void TrajectoryBuffer::AddOffsetToTimestamps(const double offset) {
+  for (double &time : times_) time = time + offset;
+}
 
 StatusOr<VectorXd> TrajectoryBuffer::GetPositionAtTime(double time_sec) const {
   return ValueAtTime(positions_, time_sec);
