@@ -456,6 +456,65 @@ int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *set, int count, co
                                            const double *max_acceleration, const double *delta,
                                            const double *initial_velocity, int32_t *num_points,
                                            int32_t *status, void *hip_stream);
+/* ---- Cartesian planner sets --------------------------------------------------------------
+ * A set of the second kind: every planner's path is the IK table of a TimeableCartesianSplinePath
+ * (path_ik_positions_, one row per multiple of delta_parameter, timeable_path_cartesian_spline.cc
+ * :464-549, plus the Jacobian at each row). The IK and Jacobian callbacks are user code and run
+ * before the upload; tpamd_planner_set_plan then plans entirely on the device: a window is rows
+ * PathIkIndex(path_start) .. +N-1 of the resident table (SamplePath :527-542), differenced
+ * (:39-68) and turned into 2D+2 constraint rows (:551-595). A planner whose table does not hold
+ * its window gets TPAMD_PLAN_INTERNAL; the others are unaffected. A set holds one kind: the
+ * joint-spline entries (upload_paths[_ragged], download_path, switch_paths, set_waypoints[_device])
+ * return TPAMD_E_INVALID_ARGUMENT on a Cartesian set and change nothing, and so do the IK-table
+ * entries on a joint set. Every other tpamd_planner_set_* entry and
+ * tpamd_buffer_set_insert_from_planner_set[_device] work on both kinds.
+ *
+ * create_cartesian takes the same config (num_points is ignored); table_capacity (>= 1) is the
+ * number of table rows per planner to start with. It grows by doubling, with a copy, before
+ * anything else changes. */
+int tpamd_planner_set_create_cartesian(tpamd_engine *engine, const tpamd_planner_set_config *config,
+                                       int table_capacity, tpamd_planner_set **out);
+/* The IK tables of `count` planners (ids[count], each listed once, or planners 0..count-1 if ids is
+ * NULL). Planner k's table is rows row_offsets[k] .. row_offsets[k + 1]) of ik_positions [rows][D]
+ * and jacobians [rows][6][D] (row-major, the layout of tpamd_cartesian_inputs); row r belongs to
+ * path parameter r * delta[k]. path_end[k] is knots.back() (what CloseToEnd compares against);
+ * max_velocity / max_acceleration / initial_velocity [count][D] (initial_velocity NULL: zero),
+ * max_translational_velocity / max_rotational_velocity / delta [count]; path_state[k] 1 (kNewPath)
+ * or 2 (kModifiedPath) as in tpamd_planner_set_upload_paths. Every id, state and size is checked
+ * before the first copy: a NULL array, count < 0 or > B, a bad or repeated id, a state other than
+ * 1 or 2, row_offsets[0] != 0 or decreasing, a planner with fewer than num_samples rows or
+ * delta <= 0 fail the call and change nothing. Host pointers; synchronises. The tables are staged
+ * in device memory for the call; staging above 16 MiB is freed before it returns. */
+int tpamd_planner_set_upload_ik_tables(tpamd_planner_set *set, int count, const int32_t *ids,
+                                       const int32_t *row_offsets, const double *ik_positions,
+                                       const double *jacobians, const double *path_end,
+                                       const double *max_velocity, const double *max_acceleration,
+                                       const double *max_translational_velocity,
+                                       const double *max_rotational_velocity, const double *delta,
+                                       const double *initial_velocity, const int32_t *path_state);
+/* The same with ik_positions .. initial_velocity and path_state device pointers; ids and row_offsets
+ * stay HOST arrays (the checks and the capacity growth need them before the launch; they go up
+ * through pinned staging on hip_stream). delta[k] and path_state[k] cannot be checked on the host
+ * here; the kernel checks them: a planner whose delta is not > 0 or whose state is not 1 / 2 is left
+ * WITHOUT a path (its Plan gives TPAMD_PLAN_FAILED_PRECONDITION; a path it had before is gone)
+ * while the others are loaded. Its rows are written all the same, and
+ * tpamd_planner_set_download_ik_table returns what was uploaded, whether the kernel accepted the
+ * planner or not. Enqueues on hip_stream and does not synchronise,
+ * except when the capacity grows or the previous call's staging is still in use. Stream ordering
+ * as documented for tpamd_planner_set_set_waypoints_device. */
+int tpamd_planner_set_upload_ik_tables_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                              const int32_t *row_offsets, const double *ik_positions,
+                                              const double *jacobians, const double *path_end,
+                                              const double *max_velocity, const double *max_acceleration,
+                                              const double *max_translational_velocity,
+                                              const double *max_rotational_velocity, const double *delta,
+                                              const double *initial_velocity, const int32_t *path_state,
+                                              void *hip_stream);
+/* The resident table of one planner: *rows (0: no table) and, if the arrays are not NULL,
+ * ik_positions [rows][D] and jacobians [rows][6][D]. `capacity` is the number of rows the arrays
+ * can hold; a longer table gives TPAMD_E_INVALID_ARGUMENT (*rows is still written). */
+int tpamd_planner_set_download_ik_table(tpamd_planner_set *set, int planner, int32_t *rows,
+                                        double *ik_positions, double *jacobians, int capacity);
 /* TrajectoryPlanner::Reset for the listed planners (ids NULL: all): no path, no plan. */
 int tpamd_planner_set_reset(tpamd_planner_set *set, int count, const int32_t *ids);
 /* Plan(start, time_horizon) for every planner: start_ns / horizon_ns [B] host arrays;

@@ -196,6 +196,8 @@ struct tpamd_engine {
   DeviceBuffer ws_buf;         // the current workspace
   DeviceBuffer stage;          // staging for the _host entry points
   DeviceBuffer rows;           // assembled constraint rows of Cartesian batches
+  bool rows_for_plan = false;  // rows holds only zeros and rows written by window chaining (of any set on
+                               // this engine, under its own split of the buffer: finite values, no more)
   Workspace ws{};
   int last_B = 0, last_N = 0;
   const double *last_time = nullptr;   // out->time of the last solve (tpamd_query_device's check)
@@ -1069,6 +1071,114 @@ int cartesian_args(const tpamd_cartesian_batch *bt, const tpamd_cartesian_inputs
     return TPAMD_E_INVALID_ARGUMENT;
   return 0;
 }
+
+// The Cartesian solve. The batch entry reads [B][N] rows of IK positions and Jacobians. The window
+// loop of a Cartesian planner set (`plan`) reads, in place, N rows of each planner's IK table
+// ([B][table_stride] rows) from row plan->first[b] on, and adds what solve_joint adds: skip marks
+// after the set-up kernel, the start-velocity projection after K1 (q'(0) is the first record's
+// finite-difference derivative); out->q is then a gather of the table segments. Planners that are
+// not looping keep the outputs of the sweep (time, s, sd, sdd, status); on the generic route
+// k_epilogue rewrites their qd / qdd from their last records, which nothing reads.
+int solve_cartesian(tpamd_engine *e, const tpamd_cartesian_batch *bt, const tpamd_cartesian_inputs *in,
+                    const tpamd_path_outputs *out, void *hip_stream, const PlanParams *plan, int table_stride) {
+  if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
+  const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
+  if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = cartesian_args(bt, in, out)) return rc;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int C = 2 * D + 2;
+  const int max_loops = bt->max_solver_loops > 0 ? bt->max_solver_loops : 0;
+  const bool fused = (D == 6 || D == 7) && !e->force_generic;
+  const int stride = plan ? table_stride : N;
+  const int *first = plan ? plan->first : nullptr;
+  const unsigned gb = (unsigned)((B + 127) / 128);
+  PlanParams pp{};
+  if (plan) {
+    pp = *plan;
+    pp.rec_stride = fused ? C + 2 : 2 * D + 2;
+  }
+  SlotGuard slot_guard(e, st);
+  int rc = ensure_workspace(e, B, N, C);
+  if (rc) return rc;
+  e->last_B = B; e->last_N = N; e->last_time = out->time;
+  e->ws.ns = nullptr;
+  e->ws.order = nullptr;
+  e->ws.amax = in->max_acceleration;
+  {
+    Timer t(e, st, KI_SETUP);
+    hipLaunchKernelGGL(k_setup_cartesian, dim3((B + 127) / 128), dim3(128), 0, st, B, N, D,
+                       bt->constraint_safety, in->max_velocity, in->max_acceleration,
+                       in->max_translational_velocity, in->max_rotational_velocity,
+                       in->path_start, in->delta, in->sd_start, in->sdd_start, in->time_start,
+                       e->ws);
+    if (plan) hipLaunchKernelGGL(k_plan_mark_skipped, dim3(gb), dim3(128), 0, st, pp, e->ws);
+  }
+  if (fused) {
+    // rows never materialised: K1 writes records, the joint-structured kernels do the rest
+    const Workspace &ws = e->ws;
+    {
+      Timer t(e, st, KI_SAMPLE_LP);
+      const int tpb = 256;
+      const size_t lds = (2 * (size_t)C + (2 * (size_t)D + 2) * tpb) * 8;
+      const dim3 grid((N + tpb - 1) / tpb, B);
+      if (D == 6)
+        hipLaunchKernelGGL((k_cartesian_lp<1, 6>), grid, dim3(tpb), lds, st, N, in->ik_positions,
+                           in->jacobians, ws, stride, first);
+      else
+        hipLaunchKernelGGL((k_cartesian_lp<1, 7>), grid, dim3(tpb), lds, st, N, in->ik_positions,
+                           in->jacobians, ws, stride, first);
+      if (plan) hipLaunchKernelGGL(k_plan_project, dim3(gb), dim3(128), 0, st, pp, ws);
+    }
+    JointSource src;
+    src.q12 = ws.q12; src.lim = ws.lim; src.D = D; src.E = 2;
+    e->ws.sd2_out = out->sd2;
+    {
+      Timer t(e, st, KI_SWEEP);
+      if (D == 6) launch_sweep_cartesian<6>(st, B, N, max_loops, src, e->ws, out);
+      else launch_sweep_cartesian<7>(st, B, N, max_loops, src, e->ws, out);
+    }
+  } else {
+    const size_t nrow = align_up((size_t)B * N * C * 8, 256);
+    if (4 * nrow > e->rows.bytes) e->rows_for_plan = false;
+    if (e->rows.reserve(4 * nrow)) return TPAMD_E_HIP;
+    // window chaining: planners that do not loop have no rows written, and the LP kernel still reads
+    // theirs (its results for them are dropped). They read zeros or an earlier window's rows, never
+    // what a new allocation or a batch solve left there.
+    if (plan && !e->rows_for_plan) HIPCHK(hipMemsetAsync(e->rows.p, 0, 4 * nrow, st));
+    e->rows_for_plan = plan != nullptr;
+    const Workspace &ws = e->ws;
+    double *A = (double *)e->rows.p, *Bm = (double *)((char *)e->rows.p + nrow),
+           *LO = (double *)((char *)e->rows.p + 2 * nrow),
+           *HI = (double *)((char *)e->rows.p + 3 * nrow);
+    {
+      Timer t(e, st, KI_SETUP);
+      hipLaunchKernelGGL(k_cartesian_rows, dim3((N + 127) / 128, B), dim3(128), 0, st, N, D,
+                         bt->constraint_safety, in->ik_positions, in->jacobians, in->max_velocity,
+                         in->max_acceleration, in->max_translational_velocity,
+                         in->max_rotational_velocity, A, Bm, LO, HI, ws, stride, first);
+      if (plan) hipLaunchKernelGGL(k_plan_project, dim3(gb), dim3(128), 0, st, pp, ws);
+    }
+    rc = run_rows(e, st, B, N, C, max_loops, A, Bm, LO, HI, out);
+    if (rc) return rc;
+    if (out->qd || out->qdd) {
+      Timer t(e, st, KI_EPILOGUE);
+      const size_t total = (size_t)B * N * D;
+      hipLaunchKernelGGL(k_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, B, N,
+                         D, ws.q12, out->sd, out->sdd, in->max_acceleration, out->status, ws.ns,
+                         out->qd, out->qdd);
+    }
+  }
+  if (out->q) {
+    if (plan)
+      hipLaunchKernelGGL(k_gather_window_q, dim3((unsigned)((N * D + 255) / 256), (unsigned)B), dim3(256), 0, st, N,
+                         D, in->ik_positions, stride, first, pp.active, out->q);
+    else
+      HIPCHK(hipMemcpyAsync(out->q, in->ik_positions, (size_t)B * N * D * 8, hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1101,86 +1211,7 @@ int tpamd_optimize_rows_device(tpamd_engine *e, const tpamd_rows_batch *bt,
 int tpamd_time_cartesian_paths_device(tpamd_engine *e, const tpamd_cartesian_batch *bt,
                                       const tpamd_cartesian_inputs *in,
                                       const tpamd_path_outputs *out, void *hip_stream) {
-  if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
-  const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
-  if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (int rc = cartesian_args(bt, in, out)) return rc;
-  TPAMD_ON_DEVICE(e);
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int C = 2 * D + 2;
-  const int max_loops = bt->max_solver_loops > 0 ? bt->max_solver_loops : 0;
-  const bool fused = (D == 6 || D == 7) && !e->force_generic;
-  SlotGuard slot_guard(e, st);
-  int rc = ensure_workspace(e, B, N, C);
-  if (rc) return rc;
-  e->last_B = B; e->last_N = N; e->last_time = out->time;
-  e->ws.ns = nullptr;
-  e->ws.order = nullptr;
-  e->ws.amax = in->max_acceleration;
-  {
-    Timer t(e, st, KI_SETUP);
-    hipLaunchKernelGGL(k_setup_cartesian, dim3((B + 127) / 128), dim3(128), 0, st, B, N, D,
-                       bt->constraint_safety, in->max_velocity, in->max_acceleration,
-                       in->max_translational_velocity, in->max_rotational_velocity,
-                       in->path_start, in->delta, in->sd_start, in->sdd_start, in->time_start,
-                       e->ws);
-  }
-  if (fused) {
-    // rows never materialised: K1 writes records, the joint-structured kernels do the rest
-    const Workspace &ws = e->ws;
-    {
-      Timer t(e, st, KI_SAMPLE_LP);
-      const int tpb = 256;
-      const size_t lds = (2 * (size_t)C + (2 * (size_t)D + 2) * tpb) * 8;
-      const dim3 grid((N + tpb - 1) / tpb, B);
-      if (D == 6)
-        hipLaunchKernelGGL((k_cartesian_lp<1, 6>), grid, dim3(tpb), lds, st, N, in->ik_positions,
-                           in->jacobians, ws);
-      else
-        hipLaunchKernelGGL((k_cartesian_lp<1, 7>), grid, dim3(tpb), lds, st, N, in->ik_positions,
-                           in->jacobians, ws);
-    }
-    JointSource src;
-    src.q12 = ws.q12; src.lim = ws.lim; src.D = D; src.E = 2;
-    e->ws.sd2_out = out->sd2;
-    {
-      Timer t(e, st, KI_SWEEP);
-      if (D == 6) launch_sweep_cartesian<6>(st, B, N, max_loops, src, e->ws, out);
-      else launch_sweep_cartesian<7>(st, B, N, max_loops, src, e->ws, out);
-    }
-    if (out->q)
-      HIPCHK(hipMemcpyAsync(out->q, in->ik_positions, (size_t)B * N * D * 8,
-                            hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  const size_t nrow = align_up((size_t)B * N * C * 8, 256);
-  if (e->rows.reserve(4 * nrow)) return TPAMD_E_HIP;
-  const Workspace &ws = e->ws;
-  double *A = (double *)e->rows.p, *Bm = (double *)((char *)e->rows.p + nrow),
-         *LO = (double *)((char *)e->rows.p + 2 * nrow),
-         *HI = (double *)((char *)e->rows.p + 3 * nrow);
-  {
-    Timer t(e, st, KI_SETUP);
-    hipLaunchKernelGGL(k_cartesian_rows, dim3((N + 127) / 128, B), dim3(128), 0, st, N, D,
-                       bt->constraint_safety, in->ik_positions, in->jacobians, in->max_velocity,
-                       in->max_acceleration, in->max_translational_velocity,
-                       in->max_rotational_velocity, A, Bm, LO, HI, ws);
-  }
-  rc = run_rows(e, st, B, N, C, max_loops, A, Bm, LO, HI, out);
-  if (rc) return rc;
-  if (out->q)
-    HIPCHK(hipMemcpyAsync(out->q, in->ik_positions, (size_t)B * N * D * 8,
-                          hipMemcpyDeviceToDevice, st));
-  if (out->qd || out->qdd) {
-    Timer t(e, st, KI_EPILOGUE);
-    const size_t total = (size_t)B * N * D;
-    hipLaunchKernelGGL(k_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, B, N,
-                       D, ws.q12, out->sd, out->sdd, in->max_acceleration, out->status, ws.ns,
-                       out->qd, out->qdd);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
+  return solve_cartesian(e, bt, in, out, hip_stream, nullptr, 0);
 }
 
 int tpamd_time_cartesian_paths_host(tpamd_engine *e, const tpamd_cartesian_batch *bt,
@@ -1907,6 +1938,17 @@ struct tpamd_planner_set {
   size_t wp_pin_bytes = 0;
   hipEvent_t ev_wp = nullptr;
   bool wp_pin_busy = false;
+  // Cartesian sets: the IK tables [B][table_cap][D] | [B][table_cap][6][D] (one allocation; it
+  // grows), a host copy of the row counts, and the per-planner Cartesian limits and path ends
+  // (part of `fixed`). The upload entries share wp_buf / wp_pin with set_waypoints.
+  bool cartesian = false;
+  int table_cap = 0;
+  void *table = nullptr;
+  size_t table_bytes = 0;
+  double *d_tq = nullptr, *d_tJ = nullptr;
+  std::vector<int> h_rows;
+  double *d_vtrans = nullptr, *d_vrot = nullptr, *d_path_end = nullptr;
+  int *d_rows = nullptr, *d_first = nullptr;
 };
 
 namespace {
@@ -1939,10 +1981,23 @@ size_t carve_trajectory(char *base, size_t B, size_t tcap, size_t D, tpamd_plann
   return st.off;
 }
 
+// IK positions [B][rows][D] | Jacobians [B][rows][6][D]
+size_t carve_table(char *base, size_t B, size_t rows, size_t D, tpamd_planner_set *ps) {
+  Stage st(base);
+  double *q = st.take<double>(B * rows * D), *J = st.take<double>(B * rows * 6 * D);
+  if (ps) { ps->d_tq = q; ps->d_tJ = J; }
+  return st.off;
+}
+
 // PlanParams view of the set (the window-loop kernels of tpamd_kernels.h)
 void refresh_plan_params(tpamd_planner_set *ps) {
   PlannerSetState &S = ps->S;
   PlanParams &p = ps->P;
+  S.path_end = ps->cartesian ? ps->d_path_end : nullptr;
+  p.path_end = S.path_end;
+  p.rows = ps->cartesian ? ps->d_rows : nullptr;
+  p.first = ps->d_first;
+  p.rec_stride = 0;
   p.B = S.B; p.N = S.N; p.D = S.D; p.K = S.K; p.cap = ps->cap; p.np = S.np;
   p.max_iterations = ps->cfg.max_planning_iterations;
   p.max_initial_velocity_error = ps->cfg.max_initial_velocity_error;
@@ -2016,6 +2071,35 @@ int ensure_pcap(tpamd_planner_set *ps, int need, hipStream_t st) {
   int p = ps->pcap;
   while (p < need) p *= 2;
   return grow_paths(ps, p, st);
+}
+
+// Move the IK tables to arrays of a larger per-planner capacity (rows); contents unchanged.
+int grow_table(tpamd_planner_set *ps, int new_cap, hipStream_t st) {
+  const size_t B = ps->S.B, D = ps->S.D, old_r = ps->table_cap, new_r = new_cap;
+  const double *old_q = ps->d_tq, *old_J = ps->d_tJ;
+  void *old_base = ps->table;
+  const size_t need = carve_table(nullptr, B, new_r, D, nullptr);
+  void *fresh = nullptr;
+  HIPCHK(hipMalloc(&fresh, need));
+  carve_table((char *)fresh, B, new_r, D, ps);
+  ps->table = fresh; ps->table_bytes = need; ps->table_cap = new_cap;
+  HIPCHK(hipMemsetAsync(fresh, 0, need, st));
+  HIPCHK(hipMemcpy2DAsync(ps->d_tq, new_r * D * 8, old_q, old_r * D * 8, old_r * D * 8, B, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpy2DAsync(ps->d_tJ, new_r * 6 * D * 8, old_J, old_r * 6 * D * 8, old_r * 6 * D * 8, B,
+                          hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipFree(old_base));
+  refresh_plan_params(ps);
+  return 0;
+}
+
+// table capacity by doubling until `need` rows fit
+int ensure_table_cap(tpamd_planner_set *ps, int need, hipStream_t st) {
+  if (need <= ps->table_cap) return 0;
+  long long r = ps->table_cap;
+  while (r < need) r *= 2;
+  if (r > (1 << 28)) return TPAMD_E_UNSUPPORTED;
+  return grow_table(ps, (int)r, st);
 }
 
 int largest_points(const tpamd_planner_set *ps) {
@@ -2108,6 +2192,7 @@ int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, co
                         const double *knots, const double *cps, const double *vmax, const double *amax,
                         const double *delta, const double *iv, const int32_t *path_state) {
   if (!ps || count < 0 || !knots || !cps || !vmax || !amax || !delta || !path_state) return TPAMD_E_INVALID_ARGUMENT;
+  if (ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;     // a Cartesian set's paths are IK tables
   const size_t B = ps->S.B, D = ps->S.D, P0 = ps->cfg.num_points;
   if ((size_t)count > B) return TPAMD_E_INVALID_ARGUMENT;
   // every id, state and size is checked before the first copy
@@ -2173,13 +2258,15 @@ int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, co
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cfg, tpamd_planner_set **out) {
-  if (!e || !cfg || !out) return TPAMD_E_INVALID_ARGUMENT;
+// Both kinds of set. A Cartesian set keeps the (unused) spline arrays at their smallest size.
+int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, bool cartesian, int table_capacity,
+                       tpamd_planner_set **out) {
+  if (!e || !cfg_in || !out) return TPAMD_E_INVALID_ARGUMENT;
   *out = nullptr;
+  tpamd_planner_set_config config = *cfg_in;
+  if (cartesian) config.num_points = 3;
+  if (cartesian && (table_capacity < 1 || table_capacity > (1 << 28))) return TPAMD_E_INVALID_ARGUMENT;
+  const tpamd_planner_set_config *cfg = &config;
   const size_t B = cfg->num_planners, D = cfg->num_dofs, N = cfg->num_samples, P = cfg->num_points;
   if (cfg->num_planners <= 0 || cfg->time_step_ns <= 0) return TPAMD_E_INVALID_ARGUMENT;
   if (D < 1 || D > 16 || N < 3 || N > 8192 || P < 3) return TPAMD_E_UNSUPPORTED;
@@ -2194,6 +2281,8 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
   ps->pcap = (int)P;
   ps->h_np.assign(B, (int)P);
   ps->h_has.assign(B, 0);
+  ps->cartesian = cartesian;
+  ps->h_rows.assign(B, 0);
   PlannerSetState &S = ps->S;
   for (int pass = 0; pass < 2; pass++) {
     Stage s(pass ? ps->fixed : nullptr);
@@ -2218,6 +2307,10 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
     ps->P.old_state = s.take<int>(B); ps->P.offset = s.take<int>(B); ps->P.loop = s.take<int>(B); ps->P.append = s.take<int>(B);
     ps->d_summary = s.take<PlannerSummaryDev>(B);
     ps->d_stop_in = s.take<char>(B * 12); ps->d_stop_out = s.take<char>(B * 20);
+    if (cartesian) {
+      ps->d_vtrans = s.take<double>(B); ps->d_vrot = s.take<double>(B); ps->d_path_end = s.take<double>(B);
+      ps->d_rows = s.take<int>(B); ps->d_first = s.take<int>(B);
+    }
     if (!pass) {
       ps->fixed_bytes = s.off;
       if (hipMalloc(&ps->fixed, s.off) != hipSuccess) { delete ps; return TPAMD_E_HIP; }
@@ -2244,6 +2337,15 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
     tpamd_planner_set_destroy(ps);
     return TPAMD_E_HIP;
   }
+  if (cartesian) {
+    ps->table_cap = table_capacity;
+    ps->table_bytes = carve_table(nullptr, B, ps->table_cap, D, nullptr);
+    if (hipMalloc(&ps->table, ps->table_bytes) != hipSuccess || hipMemset(ps->table, 0, ps->table_bytes) != hipSuccess) {
+      tpamd_planner_set_destroy(ps);
+      return TPAMD_E_HIP;
+    }
+    carve_table((char *)ps->table, B, ps->table_cap, D, ps);
+  }
   // a planner without a path still has a count the sampling kernel can read (its knots are zero)
   if (hipMemcpy(S.np, ps->h_np.data(), B * 4, hipMemcpyHostToDevice) != hipSuccess) {
     tpamd_planner_set_destroy(ps);
@@ -2265,6 +2367,18 @@ int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cf
   *out = ps;
   return 0;
 }
+}  // namespace
+
+extern "C" {
+
+int tpamd_planner_set_create(tpamd_engine *e, const tpamd_planner_set_config *cfg, tpamd_planner_set **out) {
+  return create_planner_set(e, cfg, /*cartesian=*/false, 0, out);
+}
+
+int tpamd_planner_set_create_cartesian(tpamd_engine *e, const tpamd_planner_set_config *cfg, int table_capacity,
+                                       tpamd_planner_set **out) {
+  return create_planner_set(e, cfg, /*cartesian=*/true, table_capacity, out);
+}
 
 void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (!ps) return;
@@ -2279,6 +2393,7 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
   if (ps->path) (void)hipFree(ps->path);
+  if (ps->table) (void)hipFree(ps->table);
   ps->sw_buf.release();
   ps->wp_buf.release();
   if (ps->wp_pin) (void)hipHostFree(ps->wp_pin);
@@ -2287,7 +2402,7 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
 }
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
-  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->sw_buf.bytes +
+  return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->table_bytes + ps->sw_buf.bytes +
                    ps->rd_in.bytes + ps->rd_out.bytes + ps->stop_buf.bytes + ps->wp_buf.bytes
             : 0;
 }
@@ -2313,7 +2428,7 @@ int tpamd_planner_set_upload_paths_ragged(tpamd_planner_set *ps, int count, cons
 
 int tpamd_planner_set_download_path(tpamd_planner_set *ps, int planner, int32_t *num_points, double *knots,
                                     double *cps, int capacity) {
-  if (!ps || !num_points || planner < 0 || planner >= ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (!ps || !num_points || planner < 0 || planner >= ps->S.B || ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
   const int P = ps->h_has[planner] ? ps->h_np[planner] : 0;
   *num_points = P;
   if (P == 0 || (!knots && !cps)) return 0;
@@ -2389,7 +2504,16 @@ int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const
     tpamd_path_outputs dout{ps->w_time, ps->w_s, ps->w_sd, ps->w_sdd, ps->w_q, ps->w_qd, ps->w_qdd, ps->w_lei,
                             ps->w_dtm, ps->w_st, nullptr};
     hipLaunchKernelGGL(k_plan_begin, dim3(gb), dim3(128), 0, st, ps->P, e->ws);
-    const int rc = solve_joint(e, &bt, &din, &dout, st, &ps->P);
+    int rc;
+    if (ps->cartesian) {
+      // the windows are read out of the resident IK tables, each from its planner's row first[b]
+      tpamd_cartesian_batch cb{(int)B, (int)D, (int)N, 0, ps->cfg.constraint_safety};
+      tpamd_cartesian_inputs cin{ps->d_tq, ps->d_tJ, ps->d_vmax, S.amax, ps->d_vtrans, ps->d_vrot, S.path_start,
+                                 ps->d_delta, S.path_start_velocity, ps->d_sdd0, S.path_time_start};
+      rc = solve_cartesian(e, &cb, &cin, &dout, st, &ps->P, ps->table_cap);
+    } else {
+      rc = solve_joint(e, &bt, &din, &dout, st, &ps->P);
+    }
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
     hipLaunchKernelGGL(k_plan_end, dim3(gb), dim3(128), 0, st, ps->P);
@@ -2500,6 +2624,7 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
                                    int32_t *status) {
   if (!ps || count < 0 || !time_ns || !waypoint_offsets || !waypoints || !stop_parameter || !num_points || !status)
     return TPAMD_E_INVALID_ARGUMENT;
+  if (ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;     // SwitchToWaypointPath edits a joint spline
   const PlannerSetState &S = ps->S;
   const size_t B = S.B, D = S.D;
   if ((size_t)count > B) return TPAMD_E_INVALID_ARGUMENT;
@@ -2584,6 +2709,7 @@ int waypoint_args(const tpamd_planner_set *ps, int count, const int32_t *ids, co
                   const double *waypoints, const double *vmax, const double *amax, const double *delta,
                   const int32_t *status, std::vector<int32_t> *id, int *need) {
   if (!ps || count < 0 || !offsets || !vmax || !amax || !delta || !status) return TPAMD_E_INVALID_ARGUMENT;
+  if (ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;     // the fit makes a joint spline
   const size_t B = ps->S.B;
   if ((size_t)count > B || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
   std::vector<char> seen(B, 0);
@@ -2609,6 +2735,37 @@ int ensure_wp_buf(tpamd_planner_set *ps, size_t bytes) {
   if (bytes <= ps->wp_buf.bytes) return 0;
   if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
   return ps->wp_buf.reserve(bytes);
+}
+
+// The _device entries that change paths (set_waypoints_device, upload_ik_tables_device): ids[n] and
+// offsets[n + 1] go up through pinned staging on `st`, into wp_buf at [0, n) and at the next
+// 256-byte boundary. The previous call's copy out of the staging has to be done first; the copy is
+// ordered like a device readout (readout_begin), and ev_wp guards the staging against the next
+// call. The caller ends with readout_end(ps, st).
+int stage_ids_and_offsets(tpamd_planner_set *ps, const std::vector<int32_t> &id, const int32_t *offsets, hipStream_t st,
+                          const int **d_ids, const int **d_offsets) {
+  const size_t n = id.size(), bytes = align_up(n * 4, 256) + (n + 1) * 4;
+  if (ps->wp_pin_busy) {
+    HIPCHK(hipEventSynchronize(ps->ev_wp));
+    ps->wp_pin_busy = false;
+  }
+  if (bytes > ps->wp_pin_bytes) {
+    if (ps->wp_pin) HIPCHK(hipHostFree(ps->wp_pin));
+    ps->wp_pin = nullptr;
+    ps->wp_pin_bytes = 0;
+    HIPCHK(hipHostMalloc(&ps->wp_pin, bytes, hipHostMallocDefault));
+    ps->wp_pin_bytes = bytes;
+  }
+  char *pin = (char *)ps->wp_pin, *base = (char *)ps->wp_buf.p;
+  std::memcpy(pin, id.data(), n * 4);
+  std::memcpy(pin + align_up(n * 4, 256), offsets, (n + 1) * 4);
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  HIPCHK(hipMemcpyAsync(base, pin, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ps->ev_wp, st));
+  ps->wp_pin_busy = true;
+  *d_ids = (const int *)base;
+  *d_offsets = (const int *)(base + align_up(n * 4, 256));
+  return 0;
 }
 
 FitParams fit_params(const tpamd_planner_set *ps, int count, double rounding) {
@@ -2694,33 +2851,178 @@ int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *ps, int count, con
     rc = ensure_pcap(ps, need, nullptr);
     if (rc) return rc;
   }
-  // ids and offsets through pinned staging; the previous call's copy out of it has to be done
-  if (ps->wp_pin_busy) {
-    HIPCHK(hipEventSynchronize(ps->ev_wp));
-    ps->wp_pin_busy = false;
-  }
-  if (bytes > ps->wp_pin_bytes) {
-    if (ps->wp_pin) HIPCHK(hipHostFree(ps->wp_pin));
-    ps->wp_pin = nullptr;
-    ps->wp_pin_bytes = 0;
-    HIPCHK(hipHostMalloc(&ps->wp_pin, bytes, hipHostMallocDefault));
-    ps->wp_pin_bytes = bytes;
-  }
-  char *pin = (char *)ps->wp_pin, *base = (char *)ps->wp_buf.p;
-  std::memcpy(pin, id.data(), n * 4);
-  std::memcpy(pin + align_up(n * 4, 256), waypoint_offsets, (n + 1) * 4);
-  if (readout_begin(ps, st)) return TPAMD_E_HIP;
-  HIPCHK(hipMemcpyAsync(base, pin, bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(ps->ev_wp, st));
-  ps->wp_pin_busy = true;
   FitParams p = fit_params(ps, count, rounding);
-  p.ids = (const int *)base; p.offsets = (const int *)(base + align_up(n * 4, 256));
+  if (stage_ids_and_offsets(ps, id, waypoint_offsets, st, &p.ids, &p.offsets)) return TPAMD_E_HIP;
   p.wps = waypoints; p.vmax = max_velocity; p.amax = max_acceleration; p.delta = delta; p.iv = initial_velocity;
   p.np_out = num_points; p.status_out = status;
   launch_set_waypoints(p, st);
   HIPCHK(hipGetLastError());
   fit_bookkeeping(ps, count, id, waypoint_offsets);
   return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- Cartesian planner sets: IK tables
+namespace {
+
+// The call-level checks of the two upload_ik_tables entries (before anything changes): a Cartesian
+// set, the arrays, every id in range and listed once (ids NULL: 0..count-1), a state of 1 or 2 and
+// delta > 0 where those arrays are host arrays (null here: device arrays), offsets from 0 and
+// non-decreasing, at least num_samples rows per planner. Fills id[count] and *longest.
+int ik_table_args(const tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *offsets, const double *q,
+                  const double *J, const double *path_end, const double *vmax, const double *amax,
+                  const double *vtrans, const double *vrot, const double *delta, const int32_t *state,
+                  const double *host_delta, const int32_t *host_state, std::vector<int32_t> *id, int *longest) {
+  if (!ps || !ps->cartesian || count < 0 || !offsets || !q || !J || !path_end || !vmax || !amax || !vtrans || !vrot ||
+      !delta || !state)
+    return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = ps->S.B;
+  if ((size_t)count > B || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<char> seen(B, 0);
+  id->resize(count);
+  long long most = 0;
+  for (int k = 0; k < count; k++) {
+    const long long b = ids ? (long long)ids[k] : (long long)k;
+    if (b < 0 || b >= (long long)B || seen[b]) return TPAMD_E_INVALID_ARGUMENT;
+    seen[b] = 1;
+    (*id)[k] = (int32_t)b;
+    const long long rows = (long long)offsets[k + 1] - offsets[k];
+    if (rows < ps->S.N) return TPAMD_E_INVALID_ARGUMENT;
+    if (host_delta && !(host_delta[k] > 0.0)) return TPAMD_E_INVALID_ARGUMENT;
+    if (host_state && host_state[k] != 1 && host_state[k] != 2) return TPAMD_E_INVALID_ARGUMENT;
+    most = std::max(most, rows);
+  }
+  if (most > (1 << 28)) return TPAMD_E_UNSUPPORTED;
+  *longest = (int)most;
+  return 0;
+}
+
+constexpr size_t kIkStagingKept = (size_t)16 << 20;   // upload staging above this size is freed after the call
+
+// The scatter of the packed tables (device pointers in p) into the set's arrays.
+void launch_ik_upload(const tpamd_planner_set *ps, IkUploadParams p, int longest, hipStream_t st) {
+  const PlannerSetState &S = ps->S;
+  const int D = S.D;
+  p.D = D; p.table_stride = ps->table_cap;
+  p.t_q = ps->d_tq; p.t_J = ps->d_tJ;
+  p.s_path_end = ps->d_path_end; p.s_vmax = ps->d_vmax; p.s_amax = (double *)S.amax; p.s_vtrans = ps->d_vtrans;
+  p.s_vrot = ps->d_vrot; p.s_delta = ps->d_delta; p.s_iv = ps->d_iv;
+  p.s_rows = ps->d_rows; p.s_state = S.path_state; p.s_has = S.has_path;
+  const unsigned n = (unsigned)p.count;
+  hipLaunchKernelGGL(k_pset_ik_rows, dim3((unsigned)(((size_t)longest * D + 255) / 256), n), dim3(256), 0, st, p, D,
+                     p.q, p.t_q);
+  hipLaunchKernelGGL(k_pset_ik_rows, dim3((unsigned)(((size_t)longest * 6 * D + 255) / 256), n), dim3(256), 0, st, p,
+                     6 * D, p.J, p.t_J);
+  hipLaunchKernelGGL(k_pset_ik_scalars, dim3((n + 127) / 128), dim3(128), 0, st, p);
+}
+
+void ik_bookkeeping(tpamd_planner_set *ps, int count, const std::vector<int32_t> &id, const int32_t *offsets) {
+  for (int k = 0; k < count; k++) {
+    ps->h_rows[id[k]] = offsets[k + 1] - offsets[k];
+    ps->h_has[id[k]] = 1;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_planner_set_upload_ik_tables(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                       const int32_t *row_offsets, const double *ik_positions,
+                                       const double *jacobians, const double *path_end, const double *max_velocity,
+                                       const double *max_acceleration, const double *max_translational_velocity,
+                                       const double *max_rotational_velocity, const double *delta,
+                                       const double *initial_velocity, const int32_t *path_state) {
+  std::vector<int32_t> id;
+  int longest = 0;
+  int rc = ik_table_args(ps, count, ids, row_offsets, ik_positions, jacobians, path_end, max_velocity,
+                         max_acceleration, max_translational_velocity, max_rotational_velocity, delta, path_state,
+                         delta, path_state, &id, &longest);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)count, D = ps->S.D, rows = (size_t)row_offsets[count];
+  // device buffer: [ids][offsets][q][J][path_end][vmax][amax][vtrans][vrot][delta][iv][state]
+  IkUploadParams p{};
+  HostStage s;
+  s.up(&p.ids, id.data(), n);
+  s.up(&p.offsets, row_offsets, n + 1);
+  s.up(&p.q, ik_positions, rows * D);
+  s.up(&p.J, jacobians, rows * 6 * D);
+  s.up(&p.path_end, path_end, n);
+  s.up(&p.vmax, max_velocity, n * D);
+  s.up(&p.amax, max_acceleration, n * D);
+  s.up(&p.vtrans, max_translational_velocity, n);
+  s.up(&p.vrot, max_rotational_velocity, n);
+  s.up(&p.delta, delta, n);
+  s.up(&p.iv, initial_velocity, n * D);
+  s.up(&p.state, path_state, n);
+  if (ensure_wp_buf(ps, s.bytes())) return TPAMD_E_HIP;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  rc = ensure_table_cap(ps, longest, st);
+  if (rc) return rc;
+  if (s.upload(ps->wp_buf.p, st)) return TPAMD_E_HIP;
+  p.count = count;
+  launch_ik_upload(ps, p, longest, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  // the staging of a whole table is as large as the table: it does not stay with the set
+  if (ps->wp_buf.bytes > kIkStagingKept) ps->wp_buf.release();
+  ik_bookkeeping(ps, count, id, row_offsets);
+  return 0;
+}
+
+int tpamd_planner_set_upload_ik_tables_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                              const int32_t *row_offsets, const double *ik_positions,
+                                              const double *jacobians, const double *path_end,
+                                              const double *max_velocity, const double *max_acceleration,
+                                              const double *max_translational_velocity,
+                                              const double *max_rotational_velocity, const double *delta,
+                                              const double *initial_velocity, const int32_t *path_state,
+                                              void *hip_stream) {
+  std::vector<int32_t> id;
+  int longest = 0;
+  int rc = ik_table_args(ps, count, ids, row_offsets, ik_positions, jacobians, path_end, max_velocity,
+                         max_acceleration, max_translational_velocity, max_rotational_velocity, delta, path_state,
+                         nullptr, nullptr, &id, &longest);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t n = (size_t)count, bytes = align_up(n * 4, 256) + (n + 1) * 4;
+  if (ensure_wp_buf(ps, bytes)) return TPAMD_E_HIP;
+  if (longest > ps->table_cap) {   // the growth runs on the null stream, after the device calls in flight
+    if (order_after_readouts(ps)) return TPAMD_E_HIP;
+    rc = ensure_table_cap(ps, longest, nullptr);
+    if (rc) return rc;
+  }
+  IkUploadParams p{};
+  p.count = count;
+  if (stage_ids_and_offsets(ps, id, row_offsets, st, &p.ids, &p.offsets)) return TPAMD_E_HIP;
+  p.q = ik_positions; p.J = jacobians; p.path_end = path_end; p.vmax = max_velocity; p.amax = max_acceleration;
+  p.vtrans = max_translational_velocity; p.vrot = max_rotational_velocity; p.delta = delta; p.iv = initial_velocity;
+  p.state = path_state;
+  launch_ik_upload(ps, p, longest, st);
+  HIPCHK(hipGetLastError());
+  ik_bookkeeping(ps, count, id, row_offsets);
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+int tpamd_planner_set_download_ik_table(tpamd_planner_set *ps, int planner, int32_t *rows, double *ik_positions,
+                                        double *jacobians, int capacity) {
+  if (!ps || !rows || planner < 0 || planner >= ps->S.B || !ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
+  const int R = ps->h_has[planner] ? ps->h_rows[planner] : 0;
+  *rows = R;
+  if (R == 0 || (!ik_positions && !jacobians)) return 0;
+  if (R > capacity) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // a device upload may still be writing
+  const size_t D = ps->S.D, o = (size_t)planner * ps->table_cap;
+  if (ik_positions) HIPCHK(hipMemcpy(ik_positions, ps->d_tq + o * D, (size_t)R * D * 8, hipMemcpyDeviceToHost));
+  if (jacobians) HIPCHK(hipMemcpy(jacobians, ps->d_tJ + o * 6 * D, (size_t)R * 6 * D * 8, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 }  // extern "C"

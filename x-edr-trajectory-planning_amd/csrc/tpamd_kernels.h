@@ -14,6 +14,7 @@
 #pragma once
 
 #include "tpamd_device.h"
+#include "tpamd_cartesian_window.h"
 
 namespace tpamd {
 
@@ -573,49 +574,25 @@ static __global__ void k_sample_pose_splines(int N, int P, const double *knots_g
 // two rows bounding |(J q')_{1..3}|^2 and |(J q')_{4..6}|^2 with lower = -upper. The
 // Jacobians [B][N][6][D] are evaluated by the caller's jacobian_func_ (:576); J q' is
 // accumulated over the dofs in index order. Rows go to A/Bm/LO/HI [B][N][2D+2]; the
-// (q', q'') pairs go to the sample's record for k_epilogue.
+// (q', q'') pairs go to the sample's record for k_epilogue. The arithmetic is cw_rows_at
+// (tpamd_cartesian_window.h). Inputs are [B][N] rows (table_stride = N, first = null) or, for a
+// Cartesian planner set, N rows of each planner's IK table from row first[b] on.
 static __global__ void k_cartesian_rows(int N, int D, double safety, const double *q_g,
                                  const double *J_g, const double *vmax, const double *amax,
                                  const double *vtrans, const double *vrot, double *A,
-                                 double *Bm, double *LO, double *HI, Workspace ws) {
+                                 double *Bm, double *LO, double *HI, Workspace ws, int table_stride,
+                                 const int *first) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
+  if (first && (ws.err_bits[b] & kErrSkip)) return;   // window chaining: this planner is not looping
   const int C = 2 * D + 2;
   const size_t o = (size_t)b * N + i;
-  const double inv = 1.0 / ws.delta[b];
-  const double *q = q_g + o * D;
-  const double *J = J_g + o * 6 * D;
-  double *rec = ws.q12 + o * (2 * D + 2);
-  double *a = A + o * C, *bb = Bm + o * C, *lo = LO + o * C, *hi = HI + o * C;
-  double v6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int d = 0; d < D; d++) {
-    double q1 = 0.0, q2 = 0.0;
-    if (i < N - 1) {
-      q1 = inv * (q[D + d] - q[d]);
-      if (i >= 1) {
-        const double q1n = (i + 1 < N - 1) ? inv * (q[2 * D + d] - q[D + d]) : 0.0;
-        q2 = inv * (q1n - q1);
-      }
-    }
-    rec[2 * d] = q1;
-    rec[2 * d + 1] = q2;
-    const double am = amax[(size_t)b * D + d] * safety;
-    const double vm = vmax[(size_t)b * D + d] * safety;
-    a[d] = q1;       bb[d] = q2;          hi[d] = am;          lo[d] = -am;
-    a[D + d] = 0.0;  bb[D + d] = q1 * q1; hi[D + d] = vm * vm; lo[D + d] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 6; r++) v6[r] += J[r * D + d] * q1;
-  }
-  const double vt = vtrans[b], vr = vrot[b];
-  a[2 * D] = 0.0;
-  bb[2 * D] = (v6[0] * v6[0] + v6[1] * v6[1]) + v6[2] * v6[2];
-  hi[2 * D] = vt * vt;
-  lo[2 * D] = -(vt * vt);
-  a[2 * D + 1] = 0.0;
-  bb[2 * D + 1] = (v6[3] * v6[3] + v6[4] * v6[4]) + v6[5] * v6[5];
-  hi[2 * D + 1] = vr * vr;
-  lo[2 * D + 1] = -(vr * vr);
+  // the sample's row: of a [B][N] batch, or of the planner's IK table from its window's first row on
+  const size_t row = (size_t)b * table_stride + (first ? first[b] : 0) + i;
+  cw_rows_at(i, N, D, 1.0 / ws.delta[b], q_g + row * D, J_g + row * 6 * D, vmax + (size_t)b * D,
+             amax + (size_t)b * D, safety, vtrans[b], vrot[b], ws.q12 + o * (2 * D + 2), A + o * C, Bm + o * C,
+             LO + o * C, HI + o * C);
 }
 
 // Setup for Cartesian paths: s_end = path_start + delta (N-1) as
@@ -670,13 +647,19 @@ static __global__ void k_setup_cartesian(int B, int N, int D, double safety, con
 // values go to the sample's record ([q'_d, q''_d]*D | bt, br | m, type), the LP reads them
 // from LDS, FindSddMax/Min from registers. grid = (ceil(N/TPB), B); dynamic LDS:
 //   lim_lo[C] | lim_hi[C] | q'[D][TPB] | q''[D][TPB] | extras[2][TPB]
+// Inputs as for k_cartesian_rows: [B][N] rows (table_stride = N, first = null), or the window of
+// each planner's IK table that starts at row first[b]. A block's Jacobians stay one contiguous,
+// 16-byte aligned run either way (a sample's six Jacobian rows are 48 D bytes).
 template <int WORDS, int D>
-__global__ void k_cartesian_lp(int N, const double *q_g, const double *J_g, Workspace ws) {
+__global__ void k_cartesian_lp(int N, const double *q_g, const double *J_g, Workspace ws, int table_stride,
+                               const int *first) {
   extern __shared__ double lds[];
   constexpr int C = 2 * D + 2;
   const int TPB = blockDim.x;
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
+  if (first && (ws.err_bits[b] & kErrSkip)) return;   // window chaining: this planner is not looping
+  const size_t row0 = (size_t)b * table_stride + (first ? first[b] : 0);
   double *s_lo = lds, *s_hi = s_lo + C;
   double *s_Q1 = s_hi + C, *s_Q2 = s_Q1 + (size_t)D * TPB, *s_X = s_Q2 + (size_t)D * TPB;
   for (int k = tid; k < 2 * C; k += TPB) s_lo[k] = ws.lim[(size_t)b * 2 * C + k];
@@ -685,7 +668,7 @@ __global__ void k_cartesian_lp(int N, const double *q_g, const double *J_g, Work
   const bool live = i < N;
   const size_t o = (size_t)b * N + (live ? i : N - 1);
   const double inv = 1.0 / ws.delta[b];
-  const double *q = q_g + o * D;
+  const double *q = q_g + (row0 + (live ? i : N - 1)) * D;
   double *Q1 = s_Q1 + tid, *Q2 = s_Q2 + tid, *X = s_X + tid;
   double q1r[D], q2r[D];
 #pragma unroll
@@ -710,7 +693,7 @@ __global__ void k_cartesian_lp(int N, const double *q_g, const double *J_g, Work
   {
     double *V6 = s_Q2;                        // [6][TPB] <= [D][TPB]
     const int nvalid = min(TPB, N - i0);
-    const double *Jb = J_g + ((size_t)b * N + i0) * 6 * D;
+    const double *Jb = J_g + (row0 + i0) * 6 * D;
     for (int p = tid; p < 6 * nvalid; p += TPB) {
       const int sm = p / 6, r = p - 6 * sm;
       const double *Jr = Jb + (size_t)p * D;
@@ -1674,6 +1657,12 @@ struct PlanParams {
   // outputs of the window just solved
   const double *w_time, *w_s, *w_sd, *w_sdd, *w_q, *w_qd, *w_qdd;   // [B][N](x D)
   const int *w_status, *w_lei;
+  // Cartesian planner sets (null / 0 otherwise): the path is an IK table of rows[b] rows, row r at
+  // path parameter r * delta[b]; the window being solved starts at row first[b]
+  const double *path_end;          // [B] knots.back() of the Cartesian path (CloseToEnd)
+  const int *rows;                 // [B]
+  int *first;                      // [B]
+  int rec_stride;                  // doubles per sample record of the solve; 0: 2D + 2
 };
 enum { kPlanOk = 0, kPlanFailedPrecondition = 1, kPlanOutOfRange = 2, kPlanInvalidArgument = 3,
        kPlanInternal = 4, kPlanDeadlineExceeded = 5 };
@@ -1709,6 +1698,17 @@ static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
   }
   p.offset[b] = offset;
   p.path_horizon[b] = p.path_start[b] + p.delta[b] * (p.N - 1);
+  if (p.rows) {
+    // SamplePath of a Cartesian path (timeable_path_cartesian_spline.cc:527-542): the window is a
+    // segment of the IK table; a table that does not hold it fails this planner alone
+    int first, last;
+    if (!cw_window(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last)) {
+      p.status[b] = kPlanInternal;
+      p.active[b] = 0;
+      return;
+    }
+    p.first[b] = first;
+  }
   p.path_state[b] = 3;                          // SamplePath: kPathWasSampled
 }
 
@@ -1728,7 +1728,7 @@ static __global__ void k_plan_project(PlanParams p, Workspace ws) {
   const int old_state = p.old_state[b];
   if (old_state != 1 && old_state != 2) return;
   const int D = p.D;
-  const double *rec0 = ws.q12 + (size_t)b * p.N * (2 * D + 2);
+  const double *rec0 = ws.q12 + (size_t)b * p.N * (p.rec_stride ? p.rec_stride : 2 * D + 2);
   const double *iv = p.initial_velocity + (size_t)b * D;
   double nrm2 = 0.0;
   for (int d = 0; d < D; d++) nrm2 += rec0[2 * d] * rec0[2 * d];
@@ -1770,7 +1770,7 @@ static __global__ void k_plan_end(PlanParams p) {
   const int decel_start = max(lei, N / 2);
   p.final_decel_start_ns[b] = (long long)(t[decel_start] * 1e9);
   const int kb = p.np ? p.np[b] + 3 : p.K;
-  const double kend = p.knots[(size_t)b * p.K + kb - 1];
+  const double kend = p.path_end ? p.path_end[b] : p.knots[(size_t)b * p.K + kb - 1];
   const int planned_to_end = p.path_horizon[b] >= kend - 1e-4;     // CloseToEnd, kSmall
   p.planned_to_end[b] = planned_to_end;
   const bool reached = (t[N - 1] - (double)p.start_ns[b] / 1e9) > (double)p.horizon_ns[b] / 1e9;
@@ -1800,6 +1800,15 @@ static __global__ void k_plan_append(PlanParams p) {
     p.h_qdd[dst * D + d] = p.w_qdd[src * D + d];
   }
   if (i == 0) p.count[b] = p.offset[b] + N;
+}
+
+// A Cartesian window's q output: the N table rows of each looping planner from row first[b] on
+static __global__ void k_gather_window_q(int N, int D, const double *table_q, int table_stride, const int *first,
+                                         const int *active, double *w_q) {
+  const int b = blockIdx.y;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N * D || !active[b]) return;
+  w_q[(size_t)b * N * D + e] = table_q[((size_t)b * table_stride + first[b]) * D + e];
 }
 
 // (q', q'') pairs of the records -> separate [B][N][D] arrays (GetFirst/SecondPathDerivativeAt)

@@ -31,6 +31,7 @@ struct PlannerSetState {
   // path
   const double *knots;                  // [B][K]: K = P_cap + 3, the stride
   int *np;                              // [B] control points of each planner's path (<= P_cap)
+  const double *path_end;               // Cartesian sets: [B] knots.back() of each path; joint sets: null
   const double *amax;                   // [B][D]
   int *path_state;                      // [B]
   int *has_path;                        // [B]
@@ -98,7 +99,7 @@ static __global__ void k_pset_prologue(PlannerSetState S) {
     S.path_horizon[b] = 0.0;
     S.path_start[b] = 0.0;
   } else {
-    const double kend = S.knots[(size_t)b * S.K + S.np[b] + 2];
+    const double kend = S.path_end ? S.path_end[b] : S.knots[(size_t)b * S.K + S.np[b] + 2];
     planned_to_end = S.path_horizon[b] >= kend - 1e-4;    // CloseToEnd
     if (planned_to_end) {
       if (!fresh) {
@@ -239,6 +240,58 @@ static __global__ void k_pset_regrow(int B, int old_cap, int new_cap, int width,
   const int n = (f + count[b]) * width;
   if (i >= n) return;
   dst[(size_t)b * new_cap * width + i] = src[(size_t)b * old_cap * width + i];
+}
+
+// ---- Cartesian sets: IK tables of the listed planners into the resident arrays
+// (tpamd_planner_set_upload_ik_tables*). Planner ids[k]'s table is rows offsets[k] .. offsets[k+1])
+// of the packed inputs; it goes to rows 0.. of the planner's [table_stride] rows.
+struct IkUploadParams {
+  int count, D, table_stride;
+  const int *ids, *offsets;             // [count], [count + 1]
+  // packed inputs (device)
+  const double *q, *J;                  // [rows][D], [rows][6][D]
+  const double *path_end, *vmax, *amax, *vtrans, *vrot, *delta, *iv;   // iv may be null (zero)
+  const int *state;
+  // the set's arrays
+  double *t_q, *t_J;
+  double *s_path_end, *s_vmax, *s_amax, *s_vtrans, *s_vrot, *s_delta, *s_iv;
+  int *s_rows, *s_state, *s_has;
+};
+
+// rows of `width` doubles; grid = (ceil(longest table * width / 256), count)
+static __global__ void k_pset_ik_rows(IkUploadParams p, int width, const double *src, double *dst) {
+  const int k = blockIdx.y;
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n = (size_t)(p.offsets[k + 1] - p.offsets[k]) * width;
+  if (e >= n) return;
+  dst[(size_t)p.ids[k] * p.table_stride * width + e] = src[(size_t)p.offsets[k] * width + e];
+}
+
+// limits, delta, initial velocity, state and row count; one thread per listed planner. The _device
+// entry cannot check delta and the state on the host: a planner whose delta is not > 0 or whose
+// state is not 1 / 2 is left without a path (Plan: failed precondition).
+static __global__ void k_pset_ik_scalars(IkUploadParams p) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  const int b = p.ids[k], D = p.D;
+  if (!(p.delta[k] > 0.0) || (p.state[k] != 1 && p.state[k] != 2)) {
+    p.s_rows[b] = 0;
+    p.s_state[b] = 0;
+    p.s_has[b] = 0;
+    return;
+  }
+  for (int d = 0; d < D; d++) {
+    p.s_vmax[(size_t)b * D + d] = p.vmax[(size_t)k * D + d];
+    p.s_amax[(size_t)b * D + d] = p.amax[(size_t)k * D + d];
+    p.s_iv[(size_t)b * D + d] = p.iv ? p.iv[(size_t)k * D + d] : 0.0;
+  }
+  p.s_path_end[b] = p.path_end[k];
+  p.s_vtrans[b] = p.vtrans[k];
+  p.s_vrot[b] = p.vrot[k];
+  p.s_delta[b] = p.delta[k];
+  p.s_rows[b] = p.offsets[k + 1] - p.offsets[k];
+  p.s_state[b] = p.state[k];
+  p.s_has[b] = 1;
 }
 
 // summary record per planner (what the mirror's getters need without a trajectory download)

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
-            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
+            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
             "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
@@ -213,6 +213,8 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device",
     "tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
     "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
+    "tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
+    "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table",
     "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
     "tpamd_buffer_set_create", "tpamd_buffer_set_destroy", "tpamd_buffer_set_reserve", "tpamd_buffer_set_capacity",
     "tpamd_buffer_set_device_bytes",
@@ -365,8 +367,14 @@ def load_library():
                  "tpamd_planner_set_upload_paths_ragged", "tpamd_planner_set_download_path",
                  "tpamd_planner_set_reset", "tpamd_planner_set_plan",
                  "tpamd_planner_set_download_trajectory", "tpamd_planner_set_switch_paths",
-                 "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device"):
+                 "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
+                 "tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
+                 "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table"):
         getattr(L, name).restype = i
+    L.tpamd_planner_set_create_cartesian.argtypes = [vp, C.POINTER(_PlannerSetConfig), i, C.POINTER(vp)]
+    L.tpamd_planner_set_upload_ik_tables.argtypes = [vp, i] + [vp] * 12
+    L.tpamd_planner_set_upload_ik_tables_device.argtypes = [vp, i] + [vp] * 12 + [vp]
+    L.tpamd_planner_set_download_ik_table.argtypes = [vp, i, vp, vp, vp, i]
     L.tpamd_planner_set_create.argtypes = [vp, C.POINTER(_PlannerSetConfig), C.POINTER(vp)]
     L.tpamd_planner_set_destroy.restype = None
     L.tpamd_planner_set_destroy.argtypes = [vp]
@@ -745,11 +753,17 @@ class PlannerSet:
     CUDA tensors go through the _device entries on torch's current stream (or `stream`); CPU
     tensors and numpy arrays through the host entries, which synchronise. ids (int32, each listed
     once where a call changes planners; None: planners 0..count-1) and waypoint offsets are host
-    arrays in every call (a CUDA tensor is copied to the host first). Errors raise TpamdError."""
+    arrays in every call (a CUDA tensor is copied to the host first). Errors raise TpamdError.
+
+    cartesian=True makes a set of the second kind: every planner's path is the IK table of a
+    Cartesian path (set_ik_tables; table_capacity rows per planner to start with, it grows). The
+    joint-spline calls (set_waypoints, set_paths, download_path, switch_paths) fail on such a set,
+    set_ik_tables / download_ik_table on a joint set; everything else works on both kinds."""
 
     def __init__(self, engine, num_planners, num_dofs, num_samples, num_points=16, time_step_ns=4_000_000,
                  sampling_method=0, max_planning_iterations=200, constraint_safety=0.8,
-                 max_initial_velocity_error=1e-2, history_capacity=0, trajectory_capacity=0):
+                 max_initial_velocity_error=1e-2, history_capacity=0, trajectory_capacity=0, cartesian=False,
+                 table_capacity=0):
         self._lib = load_library()
         self.B, self.D, self.N = int(num_planners), int(num_dofs), int(num_samples)
         self.device = engine.device
@@ -757,7 +771,13 @@ class PlannerSet:
                                 int(trajectory_capacity), int(sampling_method), int(max_planning_iterations),
                                 float(constraint_safety), float(max_initial_velocity_error), int(time_step_ns))
         h = C.c_void_p()
-        _check(self._lib.tpamd_planner_set_create(engine._h, C.byref(cfg), C.byref(h)), "tpamd_planner_set_create")
+        self.cartesian = bool(cartesian)
+        if self.cartesian:
+            rows = int(table_capacity) if table_capacity else 4 * self.N
+            _check(self._lib.tpamd_planner_set_create_cartesian(engine._h, C.byref(cfg), rows, C.byref(h)),
+                   "tpamd_planner_set_create_cartesian")
+        else:
+            _check(self._lib.tpamd_planner_set_create(engine._h, C.byref(cfg), C.byref(h)), "tpamd_planner_set_create")
         self._engine = engine          # the set must not outlive its engine
         self._h = h
         self._num_samples = np.zeros(self.B, dtype=np.int64)    # GetNumTimeSamples after the last plan
@@ -875,6 +895,67 @@ class PlannerSet:
         _check(self._lib.tpamd_planner_set_upload_paths_ragged(
             self._handle(), n, _ptr(ida), _ptr(npts), _ptr(k), _ptr(c), _ptr(vm), _ptr(am), _ptr(dl), _ptr(iv),
             _ptr(ps)), "tpamd_planner_set_upload_paths_ragged")
+
+    def set_ik_tables(self, ik_positions, jacobians, row_offsets, path_end, max_velocity, max_acceleration,
+                      max_translational_velocity, max_rotational_velocity, delta, initial_velocity=None, ids=None,
+                      path_state=None, stream=None):
+        """The IK tables of a Cartesian set's planners (tpamd_planner_set_upload_ik_tables*): listed
+        planner k (ids[k], or k) gets rows row_offsets[k]:row_offsets[k + 1] of ik_positions
+        [rows][D] and jacobians [rows][6][D]; row r belongs to path parameter r * delta[k]. path_end,
+        max_translational_velocity, max_rotational_velocity, delta [count] (or one number each),
+        max_velocity / max_acceleration / initial_velocity [count][D] (initial_velocity None: zero),
+        path_state [count] int32 (1 kNewPath, the default, or 2 kModifiedPath). With a CUDA
+        `ik_positions` every array is taken on its device and the call only enqueues on `stream`
+        (default: torch's current stream); otherwise the host entry runs and synchronises."""
+        import torch
+        off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("row offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        D = self.D
+        rows = int(off[-1]) if n else 0
+        if _is_cuda(ik_positions):
+            dev = ik_positions.device
+            f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
+            per = lambda x, what: f(x if hasattr(x, "shape") else torch.full((n,), float(x), dtype=torch.float64),
+                                    (n,), what)
+            q, J = f(ik_positions, (rows, D), "ik_positions"), f(jacobians, (rows, 6, D), "jacobians")
+            pe, vt, vr, dl = (per(path_end, "path_end"), per(max_translational_velocity, "max_translational_velocity"),
+                              per(max_rotational_velocity, "max_rotational_velocity"), per(delta, "delta"))
+            vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
+            iv = None if initial_velocity is None else f(initial_velocity, (n, D), "initial_velocity")
+            ps = self._cuda(torch.ones(n, dtype=torch.int32) if path_state is None else path_state, torch.int32, dev,
+                            (n,), "path_state")
+            _check(self._lib.tpamd_planner_set_upload_ik_tables_device(
+                self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _ptr(pe), _ptr(vm), _ptr(am), _ptr(vt),
+                _ptr(vr), _ptr(dl), _ptr(iv), _ptr(ps), _stream_ptr(stream)),
+                "tpamd_planner_set_upload_ik_tables_device")
+            return
+        per = lambda x, what: _host(np.broadcast_to(_host(x, np.float64), (n,)), np.float64, (n,), what)
+        q = _host(ik_positions, np.float64, (rows, D), "ik_positions")
+        J = _host(jacobians, np.float64, (rows, 6, D), "jacobians")
+        pe, vt, vr, dl = (per(path_end, "path_end"), per(max_translational_velocity, "max_translational_velocity"),
+                          per(max_rotational_velocity, "max_rotational_velocity"), per(delta, "delta"))
+        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
+        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
+        iv = _host(initial_velocity, np.float64, (n, D), "initial_velocity")
+        ps = np.ones(n, dtype=np.int32) if path_state is None else _host(path_state, np.int32, (n,), "path_state")
+        _check(self._lib.tpamd_planner_set_upload_ik_tables(
+            self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _ptr(pe), _ptr(vm), _ptr(am), _ptr(vt),
+            _ptr(vr), _ptr(dl), _ptr(iv), _ptr(ps)), "tpamd_planner_set_upload_ik_tables")
+
+    def download_ik_table(self, planner):
+        """The resident IK table of one planner of a Cartesian set: (ik_positions [rows][D],
+        jacobians [rows][6][D]) numpy; rows = 0: no table."""
+        R = C.c_int32(0)
+        _check(self._lib.tpamd_planner_set_download_ik_table(self._handle(), int(planner), C.byref(R), None, None, 0),
+               "tpamd_planner_set_download_ik_table")
+        q, J = np.zeros((R.value, self.D)), np.zeros((R.value, 6, self.D))
+        if R.value:
+            _check(self._lib.tpamd_planner_set_download_ik_table(self._handle(), int(planner), C.byref(R), _ptr(q),
+                                                                 _ptr(J), R.value),
+                   "tpamd_planner_set_download_ik_table")
+        return q, J
 
     def download_path(self, planner):
         """The resident spline of one planner: (knots [P + 3], control_points [P][D]) numpy; P = 0:

@@ -15,12 +15,9 @@ using ::tpamd::compat::OkStatus;
 using ::tpamd::compat::OutOfRangeError;
 using ::tpamd::compat::StatusOr;
 
-PathTimingTrajectorySet::PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
-                                                 size_t num_control_points, double constraint_safety, int device)
-    : options_(options), num_planners_(num_planners), num_control_points_(num_control_points),
-      constraint_safety_(constraint_safety), summary_(num_planners) {
-  lease_ = ::tpamd::acquire_engine(device);
-  if (!lease_) { init_status_ = InternalError("no GPU engine"); return; }
+namespace {
+tpamd_planner_set_config SetConfig(const PathTimingTrajectoryOptions &options, size_t num_planners,
+                                   size_t num_control_points, double constraint_safety) {
   tpamd_planner_set_config cfg{};
   cfg.num_planners = (int32_t)num_planners; cfg.num_dofs = (int32_t)options.GetNumDofs();
   cfg.num_samples = (int32_t)options.GetNumPathSamples(); cfg.num_points = (int32_t)num_control_points;
@@ -31,7 +28,30 @@ PathTimingTrajectorySet::PathTimingTrajectorySet(const PathTimingTrajectoryOptio
   cfg.constraint_safety = constraint_safety;
   cfg.max_initial_velocity_error = options.GetMaxInitialVelocityError();
   cfg.time_step_ns = options.GetTimeStep().nanos();
+  return cfg;
+}
+}  // namespace
+
+PathTimingTrajectorySet::PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
+                                                 size_t num_control_points, double constraint_safety, int device)
+    : options_(options), num_planners_(num_planners), num_control_points_(num_control_points),
+      constraint_safety_(constraint_safety), summary_(num_planners) {
+  lease_ = ::tpamd::acquire_engine(device);
+  if (!lease_) { init_status_ = InternalError("no GPU engine"); return; }
+  const tpamd_planner_set_config cfg = SetConfig(options, num_planners, num_control_points, constraint_safety);
   const int rc = tpamd_planner_set_create(lease_.get(), &cfg, &set_);
+  if (rc != 0) init_status_ = InternalError(tpamd_error_string(rc));
+}
+
+PathTimingTrajectorySet::PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
+                                                 CartesianTableCapacity table_capacity, double constraint_safety,
+                                                 int device)
+    : options_(options), num_planners_(num_planners), num_control_points_(3), constraint_safety_(constraint_safety),
+      cartesian_(true), summary_(num_planners) {
+  lease_ = ::tpamd::acquire_engine(device);
+  if (!lease_) { init_status_ = InternalError("no GPU engine"); return; }
+  const tpamd_planner_set_config cfg = SetConfig(options, num_planners, 3, constraint_safety);
+  const int rc = tpamd_planner_set_create_cartesian(lease_.get(), &cfg, (int)table_capacity.rows, &set_);
   if (rc != 0) init_status_ = InternalError(tpamd_error_string(rc));
 }
 
@@ -52,6 +72,7 @@ int StateCode(TimeablePath::State s) {
 
 Status PathTimingTrajectorySet::SetPath(size_t planner, const TimeableJointSplinePath &path) {
   if (!init_status_.ok()) return init_status_;
+  if (cartesian_) return FailedPreconditionError("a Cartesian set takes IK tables (SetCartesianPath)");
   if (planner >= num_planners_) return InvalidArgumentError("no such planner");
   if (path.NumDofs() != options_.GetNumDofs()) return InvalidArgumentError("Path and planner disagree on the number of dofs");
   if (path.NumPathSamples() != options_.GetNumPathSamples())
@@ -70,8 +91,118 @@ Status PathTimingTrajectorySet::SetPath(size_t planner, const TimeableJointSplin
   return OkStatus();
 }
 
+Status PathTimingTrajectorySet::SetCartesianPath(size_t planner, TimeableCartesianSplinePath &path) {
+  if (!init_status_.ok()) return init_status_;
+  if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetPath)");
+  if (planner >= num_planners_) return InvalidArgumentError("no such planner");
+  const size_t D = options_.GetNumDofs();
+  if (path.NumDofs() != D || path.NumPathSamples() != options_.GetNumPathSamples() ||
+      path.options().constraint_safety() != constraint_safety_)
+    return InvalidArgumentError("path does not have the shape of the set");
+  const int state = StateCode(path.GetState());
+  if (state != 1 && state != 2) return FailedPreconditionError("SetWaypoints first");
+  if (path.GetMaxJointVelocity().size() != D || path.GetMaxJointAcceleration().size() != D)
+    return FailedPreconditionError("set the joint limits first");
+  IkTables t;
+  if (Status st = path.BuildIkTable(&t.ik_positions, &t.jacobians); !st.ok()) return st;
+  t.row_offsets = {0, (int32_t)(t.ik_positions.size() / D)};
+  t.path_end = {path.knots().back()};
+  t.max_translational_velocity = {path.max_translational_velocity()};
+  t.max_rotational_velocity = {path.max_rotational_velocity()};
+  t.delta = {path.GetPathSamplingDistance()};
+  t.max_velocity.assign(path.GetMaxJointVelocity().begin(), path.GetMaxJointVelocity().end());
+  t.max_acceleration.assign(path.GetMaxJointAcceleration().begin(), path.GetMaxJointAcceleration().end());
+  if (path.GetInitialVelocity().size() == D)
+    t.initial_velocity.assign(path.GetInitialVelocity().begin(), path.GetInitialVelocity().end());
+  t.path_state = {state};
+  return SetIkTables({planner}, t);
+}
+
+Status PathTimingTrajectorySet::SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths) {
+  if (!init_status_.ok()) return init_status_;
+  if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetPaths)");
+  if (paths.size() > num_planners_) return InvalidArgumentError("more paths than planners");
+  const size_t n = paths.size(), D = options_.GetNumDofs();
+  IkTables t;
+  std::vector<size_t> planners(n);
+  t.row_offsets.assign(1, 0);
+  t.initial_velocity.assign(n * D, 0.0);
+  for (size_t k = 0; k < n; k++) {
+    TimeableCartesianSplinePath &p = *paths[k];
+    planners[k] = k;
+    if (p.NumDofs() != D || p.NumPathSamples() != options_.GetNumPathSamples() ||
+        p.options().constraint_safety() != constraint_safety_)
+      return InvalidArgumentError("path does not have the shape of the set");
+    const int state = StateCode(p.GetState());
+    if (state != 1 && state != 2) return FailedPreconditionError("SetWaypoints first");
+    if (p.GetMaxJointVelocity().size() != D || p.GetMaxJointAcceleration().size() != D)
+      return FailedPreconditionError("set the joint limits first");
+    if (Status st = p.BuildIkTable(&t.ik_positions, &t.jacobians); !st.ok()) return st;
+    t.row_offsets.push_back((int32_t)(t.ik_positions.size() / D));
+    t.path_end.push_back(p.knots().back());
+    t.max_translational_velocity.push_back(p.max_translational_velocity());
+    t.max_rotational_velocity.push_back(p.max_rotational_velocity());
+    t.delta.push_back(p.GetPathSamplingDistance());
+    t.max_velocity.insert(t.max_velocity.end(), p.GetMaxJointVelocity().begin(), p.GetMaxJointVelocity().end());
+    t.max_acceleration.insert(t.max_acceleration.end(), p.GetMaxJointAcceleration().begin(),
+                              p.GetMaxJointAcceleration().end());
+    if (p.GetInitialVelocity().size() == D)
+      std::copy(p.GetInitialVelocity().begin(), p.GetInitialVelocity().end(), t.initial_velocity.begin() + k * D);
+    t.path_state.push_back(state);
+  }
+  return SetIkTables(planners, t);
+}
+
+Status PathTimingTrajectorySet::SetIkTables(const std::vector<size_t> &planners, const IkTables &t) {
+  if (!init_status_.ok()) return init_status_;
+  if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetPaths)");
+  const size_t n = planners.size(), D = options_.GetNumDofs();
+  if (t.row_offsets.size() != n + 1 || t.path_end.size() != n || t.max_translational_velocity.size() != n ||
+      t.max_rotational_velocity.size() != n || t.delta.size() != n || t.max_velocity.size() != n * D ||
+      t.max_acceleration.size() != n * D || (!t.initial_velocity.empty() && t.initial_velocity.size() != n * D) ||
+      (!t.path_state.empty() && t.path_state.size() != n))
+    return InvalidArgumentError("one entry per listed planner");
+  if (n == 0) return OkStatus();
+  const size_t rows = t.row_offsets.back() > 0 ? (size_t)t.row_offsets.back() : 0;
+  if (t.ik_positions.size() != rows * D || t.jacobians.size() != rows * 6 * D)
+    return InvalidArgumentError("the tables do not hold row_offsets.back() rows");
+  std::vector<int32_t> ids(n), state(t.path_state.empty() ? std::vector<int32_t>(n, 1) : t.path_state);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_) return InvalidArgumentError("no such planner");
+    ids[k] = (int32_t)planners[k];
+  }
+  const int rc = tpamd_planner_set_upload_ik_tables(
+      set_, (int)n, ids.data(), t.row_offsets.data(), t.ik_positions.data(), t.jacobians.data(), t.path_end.data(),
+      t.max_velocity.data(), t.max_acceleration.data(), t.max_translational_velocity.data(),
+      t.max_rotational_velocity.data(), t.delta.data(), t.initial_velocity.empty() ? nullptr : t.initial_velocity.data(),
+      state.data());
+  if (rc == TPAMD_E_INVALID_ARGUMENT)
+    return InvalidArgumentError("a planner listed twice, a state other than new / modified, a table shorter than the "
+                                "window, delta <= 0 or row offsets that do not start at 0 and increase");
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  for (size_t k = 0; k < n; k++) summary_[planners[k]].path_state = state[k];
+  return OkStatus();
+}
+
+Status PathTimingTrajectorySet::GetIkTable(size_t planner, std::vector<double> *ik_positions,
+                                           std::vector<double> *jacobians) const {
+  if (!init_status_.ok()) return init_status_;
+  if (!cartesian_) return FailedPreconditionError("a joint set has no IK tables (GetPath)");
+  if (planner >= num_planners_) return InvalidArgumentError("no such planner");
+  int32_t rows = 0;
+  int rc = tpamd_planner_set_download_ik_table(set_, (int)planner, &rows, nullptr, nullptr, 0);
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  const size_t D = options_.GetNumDofs();
+  ik_positions->assign((size_t)rows * D, 0.0);
+  jacobians->assign((size_t)rows * 6 * D, 0.0);
+  if (rows == 0) return OkStatus();
+  rc = tpamd_planner_set_download_ik_table(set_, (int)planner, &rows, ik_positions->data(), jacobians->data(), rows);
+  return rc == 0 ? OkStatus() : InternalError(tpamd_error_string(rc));
+}
+
 Status PathTimingTrajectorySet::SetPaths(const std::vector<std::shared_ptr<TimeableJointSplinePath>> &paths) {
   if (!init_status_.ok()) return init_status_;
+  if (cartesian_) return FailedPreconditionError("a Cartesian set takes IK tables (SetCartesianPaths)");
   if (paths.size() > num_planners_) return InvalidArgumentError("more paths than planners");
   const size_t n = paths.size(), D = options_.GetNumDofs();
   std::vector<double> knots, cps, vmax(n * D), amax(n * D), dl(n), iv(n * D);
@@ -191,6 +322,7 @@ std::vector<Status> PathTimingTrajectorySet::SwitchToWaypointPaths(const std::ve
                                                                   const std::vector<std::vector<VectorXd>> &waypoints) {
   const size_t n = planners.size(), D = options_.GetNumDofs();
   if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
+  if (cartesian_) return std::vector<Status>(n, FailedPreconditionError("a Cartesian set has no joint spline to switch"));
   if (time.size() != n || waypoints.size() != n)
     return std::vector<Status>(n, InvalidArgumentError("one time and one waypoint list per planner"));
   std::vector<int32_t> ids(n), offsets(n + 1, 0), np(n), st(n);
@@ -232,6 +364,7 @@ std::vector<Status> PathTimingTrajectorySet::SetWaypointPaths(const std::vector<
                                                              double rounding, double delta_parameter) {
   const size_t n = planners.size(), D = options_.GetNumDofs();
   if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
+  if (cartesian_) return std::vector<Status>(n, FailedPreconditionError("a Cartesian set takes IK tables"));
   if (waypoints.size() != n || max_velocity.size() != n || max_acceleration.size() != n ||
       (!initial_velocity.empty() && initial_velocity.size() != n))
     return std::vector<Status>(n, InvalidArgumentError("one waypoint list and one set of limits per planner"));
@@ -284,6 +417,7 @@ std::vector<Status> PathTimingTrajectorySet::SetWaypointPaths(const std::vector<
 Status PathTimingTrajectorySet::GetPath(size_t planner, std::vector<double> *knots,
                                         std::vector<double> *control_points) const {
   if (!init_status_.ok()) return init_status_;
+  if (cartesian_) return FailedPreconditionError("a Cartesian set has IK tables (GetIkTable)");
   if (planner >= num_planners_ || !knots || !control_points) return InvalidArgumentError("no such planner");
   const size_t P = NumControlPoints(planner), D = options_.GetNumDofs();
   knots->assign(P ? P + 3 : 0, 0.0);
@@ -295,7 +429,7 @@ Status PathTimingTrajectorySet::GetPath(size_t planner, std::vector<double> *kno
 }
 
 size_t PathTimingTrajectorySet::NumControlPoints(size_t planner) const {
-  if (!init_status_.ok() || planner >= num_planners_) return 0;
+  if (!init_status_.ok() || planner >= num_planners_ || cartesian_) return 0;
   int32_t np = 0;
   tpamd_planner_set_download_path(set_, (int)planner, &np, nullptr, nullptr, 0);   // host copy: no transfer
   return (size_t)np;

@@ -21,6 +21,7 @@
 
 #include "engine_handle.h"
 #include "path_timing_trajectory.h"
+#include "timeable_path_cartesian_spline.h"
 #include "timeable_path_joint_spline.h"
 
 namespace trajectory_planning {
@@ -49,6 +50,24 @@ struct StoppingSegment {
   std::vector<double> time, positions, velocities, accelerations;
 };
 
+// The paths of a Cartesian set as raw IK tables (SetIkTables), for callers whose IK is not a
+// std::function: planner k's table is rows row_offsets[k] .. row_offsets[k + 1]) of ik_positions
+// [rows][dofs] and jacobians [rows][6][dofs] (row-major); row r belongs to path parameter
+// r * delta[k]. path_end[k] is the path's last knot (CloseToEnd). initial_velocity may be empty
+// (zero); path_state[k] is 1 (kNewPath) or 2 (kModifiedPath), empty: all new.
+struct IkTables {
+  std::vector<int32_t> row_offsets;
+  std::vector<double> ik_positions, jacobians;
+  std::vector<double> path_end, max_translational_velocity, max_rotational_velocity, delta;
+  std::vector<double> max_velocity, max_acceleration, initial_velocity;   // [planners][dofs]
+  std::vector<int32_t> path_state;
+};
+
+// Constructor tag of a Cartesian set: rows per planner the IK tables hold to start with (they grow).
+struct CartesianTableCapacity {
+  size_t rows;
+};
+
 class PathTimingTrajectorySet {
  public:
   // All planners share the planner options and the path options (dofs, samples; delta may differ
@@ -56,7 +75,28 @@ class PathTimingTrajectorySet {
   // set starts with; paths of any size are accepted and the capacity grows as needed.
   PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
                           size_t num_control_points, double constraint_safety = 0.8, int device = -1);
+  // A set of the second kind: every planner's path is the IK table of a
+  // TimeableCartesianSplinePath (tpamd_planner_set_create_cartesian). Plan runs on the device on
+  // the resident tables and leaves every planner in the state a PathTimingTrajectory that plans
+  // the same path window by window is in -- provided the IK callback's result for a sample does not
+  // depend on how the samples were split into calls (closed-form and per-sample solvers qualify; a
+  // solver warm-started across the samples of one call does not). The contract of the set is the
+  // table. A set holds one kind: the joint-spline methods (SetPath(s), SetWaypointPaths,
+  // SwitchToWaypointPaths, GetPath) return FailedPrecondition on a Cartesian set, the Cartesian
+  // ones on a joint set. Everything that reads the trajectories works on both.
+  PathTimingTrajectorySet(const PathTimingTrajectoryOptions &options, size_t num_planners,
+                          CartesianTableCapacity table_capacity, double constraint_safety = 0.8, int device = -1);
   ~PathTimingTrajectorySet();
+  bool is_cartesian() const { return cartesian_; }
+  // BuildIkTable on the path (one IK callback call over the whole path, one Jacobian callback per
+  // row), then the table with the path's limits, delta, initial velocity and state go to the
+  // device. The path must be kNewPath or kModifiedPath; its state does not change.
+  Status SetCartesianPath(size_t planner, TimeableCartesianSplinePath &path);
+  Status SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths);
+  // Raw tables for the listed planners (each listed once).
+  Status SetIkTables(const std::vector<size_t> &planners, const IkTables &tables);
+  // The planner's resident table (no table: empty).
+  Status GetIkTable(size_t planner, std::vector<double> *ik_positions, std::vector<double> *jacobians) const;
   PathTimingTrajectorySet(const PathTimingTrajectorySet &) = delete;
   PathTimingTrajectorySet &operator=(const PathTimingTrajectorySet &) = delete;
 
@@ -150,6 +190,7 @@ class PathTimingTrajectorySet {
   const PathTimingTrajectoryOptions options_;
   const size_t num_planners_, num_control_points_;
   const double constraint_safety_;
+  const bool cartesian_ = false;
   Status init_status_;
   ::tpamd::EngineLease lease_;
   tpamd_planner_set *set_ = nullptr;

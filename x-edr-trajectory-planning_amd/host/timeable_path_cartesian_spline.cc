@@ -215,10 +215,29 @@ double TimeableCartesianSplinePath::PathIkParameter(const int index) const {
 // timeable_path_cartesian_spline.cc:484-549
 Status TimeableCartesianSplinePath::SamplePath(const double path_start) {
   if (knots_.empty()) return FailedPreconditionError("Call SetWaypoints first.");
-  const size_t N = options_.num_path_samples(), D = options_.num_dofs();
+  const size_t N = options_.num_path_samples();
   const double delta = options_.delta_parameter();
   const double path_horizon = path_start + delta * (N - 1);
   const int horizon_ik_upper_index = PathIkIndex(path_horizon);
+  if (Status st = ExtendIkSolution(horizon_ik_upper_index); !st.ok()) return st;
+  const int path_start_index = PathIkIndex(path_start);
+  if (path_start_index < 0 || horizon_ik_upper_index - path_start_index != (int)N - 1 ||
+      horizon_ik_upper_index >= (int)path_ik_positions_.size())
+    return InternalError("IK solution does not cover the sampled window");   // the reference CHECKs
+  std::copy(path_ik_positions_.begin() + path_start_index, path_ik_positions_.begin() + horizon_ik_upper_index + 1,
+            path_position_.begin());
+  ComputePathDerivatives(path_position_, delta, &first_path_derivative_, &second_path_derivative_);
+  path_state_ = State::kPathWasSampled;
+  parameter_start_ = path_start;
+  parameter_end_ = path_horizon;
+  return OkStatus();
+}
+
+// The part of SamplePath that runs the IK callback (:484-526): the table up to row
+// horizon_ik_upper_index.
+Status TimeableCartesianSplinePath::ExtendIkSolution(const int horizon_ik_upper_index) {
+  const size_t D = options_.num_dofs();
+  const double delta = options_.delta_parameter();
   const int current_ik_upper_index = (int)path_ik_positions_.size() - 1;
   if (horizon_ik_upper_index >= current_ik_upper_index) {
     // Pose and joint targets for the part of the path that has no IK solution yet, re-evaluating
@@ -270,16 +289,22 @@ Status TimeableCartesianSplinePath::SamplePath(const double path_start) {
       path_ik_positions_.insert(path_ik_positions_.end(), new_ik_path_.begin() + 1, new_ik_path_.end());
     if (!ik_status.ok()) return ik_status;
   }
-  const int path_start_index = PathIkIndex(path_start);
-  if (path_start_index < 0 || horizon_ik_upper_index - path_start_index != (int)N - 1 ||
-      horizon_ik_upper_index >= (int)path_ik_positions_.size())
-    return InternalError("IK solution does not cover the sampled window");   // the reference CHECKs
-  std::copy(path_ik_positions_.begin() + path_start_index, path_ik_positions_.begin() + horizon_ik_upper_index + 1,
-            path_position_.begin());
-  ComputePathDerivatives(path_position_, delta, &first_path_derivative_, &second_path_derivative_);
-  path_state_ = State::kPathWasSampled;
-  parameter_start_ = path_start;
-  parameter_end_ = path_horizon;
+  return OkStatus();
+}
+
+Status TimeableCartesianSplinePath::BuildIkTable(std::vector<double> *ik_positions, std::vector<double> *jacobians) {
+  if (knots_.empty()) return FailedPreconditionError("Call SetWaypoints first.");
+  const size_t N = options_.num_path_samples(), D = options_.num_dofs();
+  const int rows = PathIkIndex(knots_.back()) + (int)N + 1;
+  if (Status st = ExtendIkSolution(rows - 1); !st.ok()) return st;
+  if ((int)path_ik_positions_.size() < rows) return InternalError("IK solution does not cover the path");
+  Matrix6Xd jacobian(6, D);
+  for (const VectorXd &q : path_ik_positions_) {
+    ik_positions->insert(ik_positions->end(), q.begin(), q.end());
+    jacobian.setZero();
+    if (Status st = jacobian_func_(q, &jacobian); !st.ok()) return st;
+    jacobians->insert(jacobians->end(), jacobian.data(), jacobian.data() + 6 * D);
+  }
   return OkStatus();
 }
 

@@ -102,9 +102,21 @@ class TimeableCartesianSplinePath : public TimeablePath {
   // The sampled window as the engine takes it: ik_positions [N][D] and the Jacobian callback's
   // result at every sample [N][6][D] (row-major), appended to q / J.
   Status PackSampledWindow(std::vector<double> *q, std::vector<double> *J) const;
+  // The IK table of the whole path, as a Cartesian planner set takes it
+  // (PathTimingTrajectorySet::SetCartesianPath): path_ik_positions_ is extended to
+  // PathIkIndex(knots.back()) + N + 1 rows in ONE call of the IK callback (the pose targets are the
+  // ones SamplePath samples, the repeated last pose beyond the end included), and the Jacobian
+  // callback is evaluated once per row. ik_positions [rows][D] and jacobians [rows][6][D]
+  // (row-major) are appended; afterwards the table equals GetSplineIKPosition(). GetState() stays
+  // as it was. The table equals what window-by-window sampling builds if the IK callback's result
+  // for a sample does not depend on how the samples were split into calls (closed-form and
+  // per-sample solvers; not a solver warm-started across the samples of one call).
+  Status BuildIkTable(std::vector<double> *ik_positions, std::vector<double> *jacobians);
 
  private:
   Status FitSplineToWaypoints();
+  // path_ik_positions_ up to row horizon_ik_upper_index (SamplePath :484-526)
+  Status ExtendIkSolution(int horizon_ik_upper_index);
 
   static constexpr int kSplineOrder = 2;
   CartesianPathOptions options_;
