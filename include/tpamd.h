@@ -894,8 +894,10 @@ int tpamd_fastest_stop_host(tpamd_engine *engine, const tpamd_fastest_stop_args 
  * before the first sample), INVALID_ARGUMENT (max_acceleration <= 0, time_step <= 0, times not
  * strictly increasing up to index), NOT_FOUND (the stop needs every sample and still misses the
  * velocity there by more than 1e-2), INTERNAL (sample index < count - 1 already at rest: the
- * reference aborts there), OK; keep[b], the samples of the row kept before the segment; first[b],
- * last[b], the segment's rows within the row. out_time [B][stride] and out_qd / out_qdd
+ * reference aborts there; or no admissible deceleration at sample index, every candidate invalid
+ * at rate 0: the reference builds a segment with NaN times there), OK; keep[b], the samples of
+ * the row kept before the segment; first[b], last[b], the segment's rows within the row.
+ * out_time [B][stride] and out_qd / out_qdd
  * [B][stride][D] are written at rows [first, last] only; the segment's positions are the input's
  * q[first .. last], unchanged. The trajectory after the stop is input[0, keep) ++ segment. No
  * samples: OK, keep 0 and an empty segment (first 0, last -1); a failed stop: keep = count and an

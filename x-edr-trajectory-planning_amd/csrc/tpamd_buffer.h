@@ -168,13 +168,14 @@ enum { kBsStopNothing = 0, kBsStopRestOnLast = 1, kBsStopInserted = 2 };
 
 // StopBeforeTime(time_sec, amax, time_step), or StopAtIndex(stop_index, ...) if by_index, that
 // changes the buffer: the status; on kRsOk the samples from keep on are the rescaled tail (rows
-// [index + 1 - m, index] rescaled where they stand, then moved to row keep if that is another
-// row), and count / sequence follow InsertSegment. A stop that fails changes nothing; so the
+// [index + 1 - m, index] rescaled where they stand and then moved down to row keep if keep is
+// before them, or written straight at row keep if it is behind their first row, whose sample is
+// kept then), and count / sequence follow InsertSegment. A stop that fails changes nothing; so the
 // segment is found first without a write (pass 0) and written in a second pass, as
 // rs_stop_serial does. Writing in place, sample i - 1 is read before row i - 1 is written.
 // kBsMore only if the segment's front time lies more than the tolerance behind the sample it was
-// computed from (keep beyond that sample) on a buffer without room: not reachable with
-// tolerances above the rounding of a time stamp.
+// computed from (keep beyond that sample) on a buffer without room: that takes a tolerance below
+// the rounding of a time stamp (1e-6 s and stamps of 2^34 s, tests/stop_reference.py "late_clock").
 template <int D>
 TPAMD_HD inline int bs_stop_in_place(const BufRef &r, bool by_index, int stop_index, double time_sec,
                                      const double *amax_in, double time_step, int *what) {
@@ -206,9 +207,16 @@ TPAMD_HD inline int bs_stop_in_place(const BufRef &r, bool by_index, int stop_in
     for (int j = 0; j < D; j++) { v[j] = qd[(size_t)index * D + j]; acc[j] = qdd[(size_t)index * D + j]; vf[j] = 0.0; }
     double t_cur = t[index], rate2 = 0.0, rt = 0.0;
     const int lo = pass == 0 ? 1 : f;
+    // A segment that goes behind its own first sample (keep > f) is written where it belongs: row
+    // i - 1 + up is at or behind sample i, which is in registers by then, and samples [f, keep)
+    // stay as they are. One that goes before it (keep < f) is written in place and moved after.
+    const int up = (pass == 1 && keep > f) ? keep - f : 0;
     if (pass == 1) {
-      t[index] = 0.0 + offset;
-      for (int j = 0; j < D; j++) qd[(size_t)index * D + j] = qdd[(size_t)index * D + j] = 0.0;
+      t[index + up] = 0.0 + offset;
+      for (int j = 0; j < D; j++) {
+        qd[(size_t)(index + up) * D + j] = qdd[(size_t)(index + up) * D + j] = 0.0;
+        if (up) r.q[(size_t)(first + index + up) * D + j] = r.q[(size_t)(first + index) * D + j];
+      }
     }
     int rows = 1;
     for (int i = index; i > lo; --i) {
@@ -226,10 +234,11 @@ TPAMD_HD inline int bs_stop_in_place(const BufRef &r, bool by_index, int stop_in
       rows++;
       for (int j = 0; j < D; j++) vf[j] = rate * v[j];
       if (pass == 1) {
-        t[i - 1] = rt + offset;
+        t[i - 1 + up] = rt + offset;
         for (int j = 0; j < D; j++) {
-          qd[(size_t)(i - 1) * D + j] = vf[j];
-          qdd[(size_t)(i - 1) * D + j] = acc[j] * rate2 + 0.5 * v[j] * d;
+          qd[(size_t)(i - 1 + up) * D + j] = vf[j];
+          qdd[(size_t)(i - 1 + up) * D + j] = acc[j] * rate2 + 0.5 * v[j] * d;
+          if (up) r.q[(size_t)(first + i - 1 + up) * D + j] = r.q[(size_t)(first + i - 1) * D + j];
         }
       }
       if (pass == 0 && next >= 1.0) break;
@@ -242,6 +251,7 @@ TPAMD_HD inline int bs_stop_in_place(const BufRef &r, bool by_index, int stop_in
     f = index + 1 - m;
     offset = t[f] - rt;
     const double front = rt + offset;
+    if (!rs_front_finite(front)) return kRsInternal;
     if (m == index) {
       const int mst = rs_match(t, n, qd, D, front, vf);
       if (mst != kRsOk) return mst;
@@ -250,7 +260,7 @@ TPAMD_HD inline int bs_stop_in_place(const BufRef &r, bool by_index, int stop_in
     keep = whole ? 0 : rs_kept_count(t, n, front, r.tol);
     if (first + keep + m > r.cap) return kBsMore;
   }
-  if (keep != f) bs_move_rows_serial(r, first + f, first + keep, m);
+  if (keep < f) bs_move_rows_serial(r, first + f, first + keep, m);
   *r.count = keep + m;
   *r.sequence = whole ? 0 : *r.sequence + 1;
   *what = kBsStopInserted;

@@ -6,7 +6,8 @@
 // Per trajectory (n samples) and stop time: index = min(lower_bound(time) + 1, n - 1); the checks
 // (index in [1, n - 1], max_acceleration > 0, time_step > 0); on the last sample with |v| < 1e-4
 // only its v and a become 0; times strictly increasing up to index; |v[index]| < 1e-8 is
-// TPAMD_PLAN_INTERNAL, where the reference aborts. Then the squared time-scaling rate, 0 at
+// TPAMD_PLAN_INTERNAL, where the reference aborts (and so is a rest sample without an admissible
+// deceleration, rs_front_finite). Then the squared time-scaling rate, 0 at
 // sample `index`, is integrated backward: for every joint c with |qd_c| >= 1e-8 the candidates
 // d = -2 (qdd_c rate2 -+ a_c) / qd_c; a candidate is valid if every joint's
 // qdd_j rate2 + 0.5 qd_j d lies in [-a_j, a_j] up to 1e-8; d = min(0, smallest valid candidate);
@@ -99,6 +100,14 @@ TPAMD_HD inline bool rs_increasing(const double *t, int lo, int hi) {
 
 // The rescaling's "already at rest" test on sample index (rescale_to_stop.cc)
 TPAMD_HD inline bool rs_at_rest(const double *qd_index, int D) { return rs_max_abs(qd_index, D) < 1e-8; }
+
+// A rest sample whose moving joints all fail the validity test (a joint at the 1e-8 cut that asks
+// more of a joint under the cut than its limit allows) has d = 0 at rate2 = 0: the first rescaled
+// step is 2 dt / 0, rt is -inf and the segment's front time rt + (t[first] - rt) is NaN. The
+// reference goes on and inserts rows with NaN times; here that stop is kRsInternal and nothing
+// changes (the second deviation, next to the sample already at rest). Checked before the front
+// time reaches a search.
+TPAMD_HD inline bool rs_front_finite(double front) { return front - front == 0.0; }
 
 // Candidate c (joint c / 2; c odd: +max_acceleration, even: -) of a sample with velocity v and
 // acceleration acc at rate2: its diff_rate_squared if the joint moves, every scaled acceleration
@@ -226,6 +235,7 @@ inline int rs_stop_serial(const double *t, const double *qd, const double *qdd, 
     const int f = index + 1 - m;
     offset = t[f] - rt;
     const double front = rt + offset;
+    if (!rs_front_finite(front)) return kRsInternal;
     if (m == index) {
       const int mst = rs_match(t, n, qd, D, front, vf);
       if (mst != kRsOk) return mst;
@@ -373,7 +383,8 @@ __global__ __launch_bounds__(64) void k_stop_trajectories(StopTrajParams p) {
         first = index + 1 - m;
         offset = tm[first] - rt;
         const double front = rt + offset;
-        if (m == index) st = rs_match(tm, n, qd, D, front, vf);
+        if (!rs_front_finite(front)) st = kRsInternal;
+        else if (m == index) st = rs_match(tm, n, qd, D, front, vf);
         if (st == kRsOk) keep = rs_kept_count(tm, n, front, kRsTolerance);
         else first = n;
       }

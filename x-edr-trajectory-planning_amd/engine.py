@@ -174,6 +174,15 @@ class _FastestStopArgs(C.Structure):
                                            "profile_drate2")])
 
 
+class _StopTrajectoryArgs(C.Structure):
+    _fields_ = ([("num_paths", C.c_int32), ("stride", C.c_int32), ("num_dofs", C.c_int32),
+                 ("reserved", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("time", "qd", "qdd", "count", "max_acceleration")] +
+                [("time_step", C.c_double)] +
+                [(n, C.c_void_p) for n in ("stop_time", "stop_index", "status", "keep", "first", "last",
+                                           "out_time", "out_qd", "out_qdd")])
+
+
 class _PlannerSetConfig(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in (
         "num_planners", "num_dofs", "num_samples", "num_points", "history_capacity",
@@ -668,6 +677,46 @@ class Engine:
             _check(self._lib.tpamd_fastest_stop_device(self._h, C.byref(args), _stream_ptr(stream)),
                    "tpamd_fastest_stop_device")
         return out
+
+    def stop_trajectories(self, time, qd, qdd, max_acceleration, time_step, stop_time=None, stop_index=None,
+                          count=None, out=None, stream=None, host=False):
+        """StopBeforeTime / StopAtIndex for a batch (tpamd_stop_trajectories_*): time [B][stride],
+        qd, qdd [B][stride][D], max_acceleration [B][D], and per row either stop_time [B] seconds or
+        stop_index [B] int32; count [B] int32 or None (every row has stride samples). Returns a dict
+        status, keep, first, last [B] int32 and out_time [B][stride], out_qd, out_qdd
+        [B][stride][D], written at rows [first, last] only; `out` may bring these three arrays
+        (to see what a call leaves untouched), else they start as zeros. host=False: CUDA tensors,
+        enqueued on `stream`; host=True: CPU arrays (numpy or torch), numpy outputs, synchronous."""
+        if (stop_time is None) == (stop_index is None):
+            raise TpamdError("give either stop_time or stop_index")
+        B, M, D = qd.shape
+        if host:
+            cv = lambda x, dt: None if x is None else np.ascontiguousarray(
+                x.numpy() if hasattr(x, "numpy") else x, dtype=dt)
+            time, qd, qdd, max_acceleration, stop_time = (
+                cv(x, np.float64) for x in (time, qd, qdd, max_acceleration, stop_time))
+            count, stop_index = cv(count, np.int32), cv(stop_index, np.int32)
+            new = lambda shape, dt: np.zeros(shape, dtype=dt)
+            f64, i32 = np.float64, np.int32
+        else:
+            import torch
+            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=qd.device)
+            f64, i32 = torch.float64, torch.int32
+        res = {k: new((B,), i32) for k in ("status", "keep", "first", "last")}
+        for k, shape in (("out_time", (B, M)), ("out_qd", (B, M, D)), ("out_qdd", (B, M, D))):
+            res[k] = out[k] if out is not None else new(shape, f64)
+            if tuple(res[k].shape) != shape:
+                raise TpamdError("%s has shape %s, expected %s" % (k, tuple(res[k].shape), shape))
+        args = _StopTrajectoryArgs(
+            B, M, D, 0, _ptr(time), _ptr(qd), _ptr(qdd), _ptr(count), _ptr(max_acceleration), float(time_step),
+            _ptr(stop_time), _ptr(stop_index),
+            *[_ptr(res[k]) for k in ("status", "keep", "first", "last", "out_time", "out_qd", "out_qdd")])
+        if host:
+            _check(self._lib.tpamd_stop_trajectories_host(self._h, C.byref(args)), "tpamd_stop_trajectories_host")
+        else:
+            _check(self._lib.tpamd_stop_trajectories_device(self._h, C.byref(args), _stream_ptr(stream)),
+                   "tpamd_stop_trajectories_device")
+        return res
 
     def debug_boundary(self, B, N):
         arr = {k: np.zeros((B, N)) for k in ("sd2_max", "sdd_max", "sdd_min", "sd2_zero", "sd2")}

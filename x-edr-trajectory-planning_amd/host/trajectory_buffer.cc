@@ -3,6 +3,7 @@
 #include "trajectory_buffer.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 #include "rescale_to_stop.h"
@@ -202,6 +203,12 @@ Status TrajectoryBuffer::StopAtIndex(int index, const VectorXd &max_acceleration
   if (stop.times.empty())
     return ::tpamd::compat::InternalError("sample " + std::to_string(index) +
                                           " is at rest before the end: no stopping trajectory");
+
+  // A rest sample without an admissible deceleration (every candidate invalid at rate 0) makes the
+  // first rescaled step 2 dt / 0 and the segment's times NaN; the reference inserts them.
+  if (!std::isfinite(stop.times.front()))
+    return ::tpamd::compat::InternalError("sample " + std::to_string(index) +
+                                          " has no admissible deceleration: no stopping trajectory");
 
   // A stop that needs every sample must match the original velocity where it starts.
   if (stop.times.size() == (size_t)index) {

@@ -9,7 +9,9 @@
 // One deliberate deviation: a StopAtIndex whose sample is already at rest (|v| < 1e-8) before the
 // last sample makes the rescaling return nothing, and the reference then aborts
 // (CHECK(!rescaled_stop.times.empty())). Here it returns InternalError and leaves the buffer
-// unchanged.
+// unchanged. So does a StopAtIndex whose sample has no admissible deceleration (its joints at or
+// above the 1e-8 cut all ask too much of another joint): the first rescaled time step is 2 dt / 0,
+// and the reference inserts a segment with NaN times.
 #ifndef TPAMD_HOST_TRAJECTORY_BUFFER_H_
 #define TPAMD_HOST_TRAJECTORY_BUFFER_H_
 
