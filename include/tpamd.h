@@ -955,6 +955,10 @@ void tpamd_debug_keep_boundary(tpamd_engine *engine, int on);
  * [B][64] int64: slots 0..31 of the backward wave, 32..63 of the forward wave (meaning of a
  * slot: csrc/tpamd_sweep_joint.h, JointSweep::diag). The product build leaves them zero. */
 int tpamd_debug_copy_diag(tpamd_engine *engine, int num_paths, long long *out);
+/* The further slots of the same counters, [B][32] int64: 0..15 of the backward wave, 16..31 of
+ * the forward wave (JointSweep::diagx: how the wait at a switching-point loop's closing barrier
+ * splits up, trips of the qd/qdd emission). */
+int tpamd_debug_copy_diag_ext(tpamd_engine *engine, int num_paths, long long *out);
 /* Registers per lane of the two hot kernels of the 7-joint path as the loaded code object
  * reports them (hipFuncGetAttributes): which = 0 the sampling/LP kernel, 1 the sweep kernel.
  * The pipelined modes rely on 2 x sweep + 1 x sampling/LP <= 512 (one SIMD's register file);

@@ -1,5 +1,6 @@
 """Diagnostic build run: where do the sweep kernel's cycles go? (not a timing run)
-Slots: csrc/tpamd_sweep_joint.h JointSweep::diag; 0..23 backward wave, 24..47 forward wave."""
+Slots: csrc/tpamd_sweep_joint.h JointSweep::diag / diagx; 0..31 backward wave, 32..63 forward wave.
+DIAG_SO names another library of csrc/ (the light form: -DTPAMD_DIAG -DTPAMD_DIAG_LIGHT)."""
 import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,6 +33,19 @@ for k, n in enumerate(names):
 # (the literal walk of the diagnostic build runs in the forward wave since the search moved there)
 net = d[:, 32 + 15] - d[:, 32 + 18]
 print("whole kernel minus the literal walk (forward wave): mean %.0f min %.0f max %.0f" % (net.mean(), net.min(), net.max()))
+
+# The closing barrier of a switching-point loop, split by what the backward wave was doing when the
+# forward wave posted "done" (JointSweep::diagx, backward wave's slots), and the trips of emit_range.
+x = E.debug_diag_ext(B).astype(np.float64)[:, :16]
+loops = np.maximum(x[:, 0] + x[:, 1] + x[:, 2], 1)
+print("closing barrier, per path (mean): loops %.1f = backward wave still in its extremal %.1f + emission stopped %.1f + "
+      "backward wave through first %.1f" % (loops.mean(), x[:, 0].mean(), x[:, 1].mean(), x[:, 2].mean()))
+print("  emission stopped: (a) done-post -> backward wave leaves emit_range %.0f cycles (%.0f per loop), (b) its fence before the "
+      "barrier %.0f (%.0f per loop), forward wave stood at the barrier %.0f"
+      % (x[:, 3].mean(), x[:, 3].sum() / max(x[:, 1].sum(), 1), x[:, 4].mean(), x[:, 4].sum() / max(x[:, 1].sum(), 1), x[:, 5].mean()))
+print("  (c) backward wave still in its extremal: forward wave stood at the barrier %.0f cycles (%.0f per loop)"
+      % (x[:, 6].mean(), x[:, 6].sum() / max(x[:, 0].sum(), 1)))
+print("  fence cycles of all loops %.0f; emit_range trips started inside loops %.1f" % (x[:, 7].mean(), x[:, 8].mean()))
 
 # per-path cycles of the whole kernel (the launch lasts as long as its slowest path): histogram for
 # profiles/ (DIAG_HIST=path.json)

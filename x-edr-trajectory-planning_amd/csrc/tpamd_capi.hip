@@ -282,7 +282,7 @@ size_t carve_workspace(char *base, int B, int N, int C, Workspace *ws) {
   w.Y = s.take<double>(ns);
   w.type = s.take<uint8_t>(ns);
   w.sd2 = s.take<double>(ns);
-  w.diag = s.take<long long>(nb * 64);
+  w.diag = s.take<long long>(nb * kDiagRow);
   w.order = s.take<int32_t>(nb);
   if (ws) *ws = w;
   return s.off;
@@ -1807,7 +1807,20 @@ int tpamd_debug_copy_diag(tpamd_engine *e, int B, long long *out) {
   if (!e || !out || B != e->last_B) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(e);
   HIPCHK(hipDeviceSynchronize());
+#ifdef TPAMD_K1_STUDY   // (the study build's flat timestamp buffer, see ensure_workspace)
   HIPCHK(hipMemcpy(out, e->ws.diag, (size_t)B * 64 * 8, hipMemcpyDeviceToHost));
+#else
+  HIPCHK(hipMemcpy2D(out, 64 * 8, e->ws.diag, kDiagRow * 8, 64 * 8, (size_t)B, hipMemcpyDeviceToHost));
+#endif
+  return 0;
+}
+
+int tpamd_debug_copy_diag_ext(tpamd_engine *e, int B, long long *out) {
+  if (!e || !out || B != e->last_B) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy2D(out, 2 * kDiagExt * 8, e->ws.diag + 64, kDiagRow * 8, 2 * kDiagExt * 8, (size_t)B,
+                     hipMemcpyDeviceToHost));
   return 0;
 }
 

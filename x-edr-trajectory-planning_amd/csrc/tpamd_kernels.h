@@ -19,6 +19,11 @@
 namespace tpamd {
 
 // ------------------------------------------------------------------ workspace
+// Diagnostic counters of one path: 32 slots of the backward wave, 32 of the forward wave, then
+// kDiagExt further slots of each (JointSweep::diag / diagx).
+constexpr int kDiagExt = 16;
+constexpr int kDiagRow = 64 + 2 * kDiagExt;
+
 struct Workspace {
   // per path
   double *ds, *s_start, *s_end, *sd_start, *sdd_start, *t_start, *delta;
@@ -45,7 +50,7 @@ struct Workspace {
   double *m, *X, *Y;  // final boundary
   uint8_t *type;
   double *sd2;
-  long long *diag;  // [B][64] cycle counters; filled only by -DTPAMD_DIAG builds
+  long long *diag;  // [B][kDiagRow] cycle counters; filled only by -DTPAMD_DIAG builds
   double *sd2_out;  // optional caller copy of sd2 ([B][N]); may be null
   int keep_boundary;  // the fused boundary passes also store sdd_max/sdd_min/type (debug copy)
   // Planner sets with paths of different sizes: control points of each path (null: every path

@@ -48,6 +48,12 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// A word of LDS that another wave of the workgroup may be writing, read as LDS (ds_read, waited for
+// on lgkmcnt alone). Through a generic volatile pointer the same read is a system-scope flat load,
+// and the wait for it (vmcnt(0)) also waits for every global load and store the wave has in flight.
+__device__ __forceinline__ int lds_word(const int *p) {
+  return *(const volatile __attribute__((address_space(3))) int *)p;
+}
 
 // (bound_ctrl with a zero "old": every lane is written, so the destination needs no copy of the
 // source first -- two moves per value instead of four. A lane whose source lies outside the
@@ -200,6 +206,7 @@ __device__ __forceinline__ long long tpamd_stamp() {
 #endif
 #define TPAMD_CNT(slot) diag[slot] += 1
 #define TPAMD_ADD(slot, v) diag[slot] += (v)
+#define TPAMD_CNTX(slot) diagx[slot] += 1
 // the coarse stamps (phases of the kernel: a dozen per path); -DTPAMD_DIAG_LIGHT keeps only these, so
 // that the build runs like the product (the fine stamps serialise the hot loops)
 #define TPAMD_T0C(var) const long long var = tpamd_stamp()
@@ -217,6 +224,7 @@ __device__ __forceinline__ long long tpamd_stamp() {
 #define TPAMD_ACCC(slot, var)
 #define TPAMD_CNT(slot)
 #define TPAMD_ADD(slot, v)
+#define TPAMD_CNTX(slot)
 #endif
 
 #ifndef TPAMD_TILE_SAMPLES
@@ -331,6 +339,14 @@ struct JointSweep {
   // 24 scalar-step cycles, 25 boundary-follow cycles, 26 init_carry cycles, 27 tile fills, 28 tile-fill
   // cycles, 29 init_carry calls, 30 blocks started from a guessed constraint
   long long diag[32];
+  // further slots. Backward wave, the closing barrier (C) of a switching-point loop by what the
+  // backward wave was doing when the forward wave posted "done": 0 loops in which it was still in
+  // its own extremal, 1 loops in which the post stopped its qd/qdd emission, 2 loops in which it was
+  // through with both; of the loops of case 1: 3 cycles from the post to the backward wave leaving
+  // emit_range, 4 cycles of its fence before the barrier, 5 cycles the forward wave then stood at
+  // the barrier before the backward wave reached it; 6 the same wait in the loops of case 0; 7 fence
+  // cycles of all loops; 8 trips of emit_range started inside loops.
+  mutable long long diagx[kDiagExt];
 #endif
   int N, lane;
   double ds, two_ds;
@@ -470,11 +486,11 @@ struct JointSweep {
   // (mostly from L2: the forward wave streamed them shortly before), but spread over the whole
   // kernel instead of as one bandwidth-bound pass by every path at once.
   __device__ __forceinline__ bool emitting() const { return qd_g != nullptr || qdd_g != nullptr; }
-  __device__ __forceinline__ void emit_value(int i, int d, f64x2 pr, double v, double a,
-                                             double amx) const {
-    const size_t o = (size_t)i * D + d;
-    if (qd_g) qd_g[o] = pr.x * v;
-    if (qdd_g) {
+  // (which outputs exist is a template argument where a caller has branched on it once: emit_trips)
+  template <bool QD, bool QDD>
+  __device__ __forceinline__ void emit_pair(size_t o, f64x2 pr, double v, double a, double amx) const {
+    if (QD) qd_g[o] = pr.x * v;
+    if (QDD) {
       const double v2 = v * v;
       double acc = pr.x * a + pr.y * v2;
       if (acc < -amx) acc = -amx;
@@ -482,56 +498,122 @@ struct JointSweep {
       qdd_g[o] = acc;
     }
   }
+  __device__ __forceinline__ void emit_value(int i, int d, f64x2 pr, double v, double a,
+                                             double amx) const {
+    const size_t o = (size_t)i * D + d;
+    if (qd_g) emit_pair<true, false>(o, pr, v, a, amx);
+    if (qdd_g) emit_pair<false, true>(o, pr, v, a, amx);
+  }
   // Samples lo..hi (inclusive) from the current sd2 (LDS), sdd and records (global), 64 samples
   // per trip of a wave: lane l first takes sample s0 + l -- sd = sqrt(sd2) and sdd once per sample,
   // one coalesced load -- then the trip's 64*D (sample, joint) pairs are spread over D passes of
   // 64 lanes, consecutive lanes storing consecutive addresses, every lane fetching its sample's sd
-  // and sdd from the lane that holds them (ds_bpermute: the LDS crossbar, no LDS memory). All
-  // loads of a trip are issued before its arithmetic. Wave `wv` of `nwv` waves takes every nwv-th
-  // trip (one wave: 0 of 1; the workgroup: tid >> 6 of 2).
-  // stop != nullptr: give up as soon as *stop == stop_value (checked between trips) -- the
-  // partner wave has finished and must not be kept waiting. Returns the first sample NOT
+  // and sdd from the lane that holds them (ds_bpermute: the LDS crossbar, no LDS memory). The trips
+  // are software-pipelined: the loads of the next trip are issued before the arithmetic and the
+  // stores of this one (emit_trips). Wave `wv` of `nwv` waves takes every nwv-th trip (one wave:
+  // 0 of 1; the workgroup: tid >> 6 of 2).
+  // stop != nullptr (a word of LDS): give up as soon as *stop == stop_value, checked between trips
+  // -- the partner wave has finished and must not be kept waiting. Returns the first sample NOT
   // written (hi + 1 if the range was completed).
-  __device__ __forceinline__ int emit_range(int lo, int hi, int wv, int nwv,
-                                            const volatile int *stop = nullptr,
+  __device__ __forceinline__ int emit_range(int lo, int hi, int wv, int nwv, const int *stop = nullptr,
                                             int stop_value = 0) const {
-    if (!emitting() || hi < lo) return hi + 1;
+    if (qd_g != nullptr && qdd_g != nullptr) return emit_trips<true, true>(lo, hi, wv, nwv, stop, stop_value);
+    if (qd_g != nullptr) return emit_trips<true, false>(lo, hi, wv, nwv, stop, stop_value);
+    if (qdd_g != nullptr) return emit_trips<false, true>(lo, hi, wv, nwv, stop, stop_value);
+    return hi + 1;
+  }
+  template <bool QD, bool QDD>
+  __device__ __forceinline__ int emit_trips(int lo, int hi, int wv, int nwv, const int *stop,
+                                            int stop_value) const {
+    int s0 = lo + 64 * wv;
+    if (hi < lo || s0 > hi) return hi + 1;
+    if (stop != nullptr && uniform_i32(lds_word(stop)) == stop_value) return s0;
+    const int step = 64 * nwv;
     const f64x2 *rec2 = reinterpret_cast<const f64x2 *>(rec);
-    for (int s0 = lo + 64 * wv; s0 <= hi; s0 += 64 * nwv) {
-      if (stop != nullptr && *stop == stop_value) return s0;                // (uniform)
-      const int cnt = min(64, hi - s0 + 1);                                  // samples of this trip
-      const int mine = s0 + min(lane, cnt - 1);
-      const double s2l = sd2[mine];
-      const double al = sdd_g[mine];
-      const double vl = sqrt(s2l);
-      constexpr int G = (D <= 8) ? D : 7;                                    // passes in flight
+    // (a whole trip ahead where the register budget allows it: D <= 8 stays under the 208 VGPRs
+    // of the pipelined modes; five passes of a wide record keep the 14-joint kernel below what
+    // it needed before)
+    constexpr int G = (D <= 8) ? D : 5;                                      // passes of a unit
+    constexpr int NG = (D + G - 1) / G;                                      // units per trip
+    // Pass p of a trip: lane l has element 64 p + l of the trip's [64][D] block, that is joint dd of
+    // the trip's sample se0[p] -- the same in every trip.
+    // (worked out per call from a lane number the compiler cannot see through: as invariants of
+    // the switching-point loop these would be hoisted out of it and stay live through the extremals)
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    int se0[D];
 #pragma unroll
-      for (int u0 = 0; u0 < D; u0 += G) {
-        f64x2 pr[G];
-        double amx[G];
-        int se[G];
+    for (int p = 0; p < D; p++) se0[p] = (64 * p + ln) / D;
+    auto joint_of = [&](int p) { return 64 * p + ln - se0[p] * D; };
+    // Two sets of load registers, used in turn by the units (trip, group of passes) in the order
+    // they run: while one unit's arithmetic and stores issue, the loads of the next are in flight.
+    // The body of a trip has no branch around a load or a store: the compiler counts
+    // outstanding memory operations per path and, where paths that issued different numbers of
+    // them meet, waits as the shortest one needs -- after a skipped prefetch or a skipped store
+    // that is a wait for the loads just issued. Hence: the prefetch after the last trip of a range
+    // reads that trip again (dropped, as is the prefetch in flight when emission stops); a lane
+    // past the end of the range (last trip only) computes and stores the same (sample, joint) as
+    // the lane that owns the range's last sample and that joint -- the same bits on the same
+    // address --; and the two outputs are template arguments.
+    f64x2 pr[2][G];
+    double s2l[2], al[2];
+    auto issue_sample = [&](int t0, int h) {
+      const int mine = min(t0 + lane, hi);
+      s2l[h] = sd2[mine];
+      al[h] = sdd_g[mine];
+    };
+    auto issue_pairs = [&](int t0, int k, f64x2(&dst)[G]) {
+      const int last = hi - t0;
 #pragma unroll
-        for (int g = 0; g < G; g++) {
-          const int e = min(64 * (u0 + g) + lane, cnt * D - 1);
-          se[g] = e / D;                                                     // sample within the trip
-          const int dd = e - se[g] * D;
-          pr[g] = rec2[(size_t)(s0 + se[g]) * (R / 2) + dd];
-          amx[g] = aml[dd];
+      for (int g = 0; g < G; g++) {
+        const int p = k * G + g;
+        if (p >= D) continue;
+        dst[g] = rec2[(size_t)(t0 + min(se0[p], last)) * (R / 2) + joint_of(p)];
+      }
+    };
+    issue_sample(s0, 0);
+    issue_pairs(s0, 0, pr[0]);
+    for (;;) {
+#pragma unroll
+      for (int h = 0; h < 2; h++) {                                          // two trips per round
+        const int last = hi - s0;                                            // >= 63 but in the last trip
+        const int nxt = s0 + step;
+        const int pre = (nxt <= hi) ? nxt : s0;                              // (uniform)
+        if (stop != nullptr) TPAMD_CNTX(8);
+        double vl = 0;
+#pragma unroll
+        for (int k = 0; k < NG; k++) {
+          constexpr int kSetsPerTrip = NG & 1;                               // (NG even: unit k always in set k & 1)
+          const int set = (h * kSetsPerTrip + k) & 1;
+          // the next unit's loads first
+          if (k + 1 < NG) {
+            issue_pairs(s0, k + 1, pr[set ^ 1]);
+          } else {
+            issue_sample(pre, h ^ 1);
+            issue_pairs(pre, 0, pr[set ^ 1]);
+          }
+          if (k == 0) vl = sqrt(s2l[h]);
+#pragma unroll
+          for (int g = 0; g < G; g++) {
+            const int p = k * G + g;
+            if (p >= D) continue;
+            const int se = min(se0[p], last), dd = joint_of(p);
+            const int src = se << 2;
+            const double v = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(vl)),
+                                              __builtin_amdgcn_ds_bpermute(src, __double2loint(vl)));
+            const double a = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(al[h])),
+                                              __builtin_amdgcn_ds_bpermute(src, __double2loint(al[h])));
+            emit_pair<QD, QDD>((size_t)(s0 + se) * D + dd, pr[set][g], v, a, aml[dd]);
+            // (two passes at a time: left alone the scheduler interleaves all passes of a trip, and
+            // the 7-joint kernel then needs 212 VGPRs, more than the 208 the pipelined modes rest on)
+            if (p & 1) __builtin_amdgcn_sched_barrier(0);
+          }
         }
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-          if (u0 + g >= D) continue;
-          const int src = se[g] << 2;
-          const double v = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(vl)),
-                                            __builtin_amdgcn_ds_bpermute(src, __double2loint(vl)));
-          const double a = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(al)),
-                                            __builtin_amdgcn_ds_bpermute(src, __double2loint(al)));
-          const int e = 64 * (u0 + g) + lane;
-          if (e < cnt * D) emit_value(s0 + se[g], e - se[g] * D, pr[g], v, a, amx[g]);
-        }
+        s0 = nxt;
+        if (s0 > hi) return hi + 1;
+        if (stop != nullptr && uniform_i32(lds_word(stop)) == stop_value) return s0;
       }
     }
-    return hi + 1;
   }
   __device__ __forceinline__ void mark_dirty(int i) const {
     if (lane == 0) atomicOr(&dirty[i >> 5], 1u << (i & 31));
@@ -1922,7 +2004,12 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   const double sd_start = ws.sd_start[b];
 #ifdef TPAMD_DIAG
   long long(&diag)[32] = S.diag;
+  long long(&diagx)[kDiagExt] = S.diagx;
   for (int k = 0; k < 32; k++) diag[k] = 0;
+  for (int k = 0; k < kDiagExt; k++) diagx[k] = 0;
+  // (closing barrier of a loop: the forward wave leaves its stamps in two spare words of the
+  // reduction scratch, which the product uses only at the kernel's end)
+  volatile long long *fw_stamp = reinterpret_cast<volatile long long *>(red + 2);   // [0] done-post, [1] at the barrier
 #define TPAMD_DIAG_PTR S.diag
 #else
 #define TPAMD_DIAG_PTR nullptr
@@ -2132,6 +2219,10 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   for (int loop = 0; loop < max_loops; loop++) {
     if (iforw_hi >= icrit_hi) break;
     TPAMD_CNT(11);
+#ifdef TPAMD_DIAG
+    int bw_case = 2;
+    long long bw_left = 0;
+#endif
     icrit = uniform_i32(xchg[9]);
     const double m_c = uniform_f64(crit_m[0]), m_p = uniform_f64(crit_m[1]);
     if (w == 0 && icrit >= 1) {
@@ -2155,32 +2246,65 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
       if (w == 0) {
         const int r = S.template add_extremal<false>(iback_hi, pf, /*pair_signal=*/true);   // B inside
         if (lane == 0) xchg[0] = r;
+#ifdef TPAMD_DIAG
+        const bool fw_was_done = lds_word(xchg + 6) == loop + 1;
+#endif
         // The forward extremal of this loop works on samples >= icrit and usually takes
         // longer: write qd/qdd for everything below icrit that is new or was changed by this
         // backward extremal (it ended at end_idx) while waiting for it.
         // -- but only until that one is done (xchg[6] then holds this loop's number): the
         // rest waits for the next loop or the tail.
-        TPAMD_T0(te);
+        TPAMD_T0C(te);
         if (TPAMD_EMIT_IN_LOOP) {
           emitted_hi = uniform_i32(S.emit_range(max(min(S.end_idx - 1, emitted_hi), 0), icrit - 1,
                                                 0, 1, xchg + 6, loop + 1));
         }
-        TPAMD_ACC(12, te);
+        TPAMD_ACCC(12, te);
+#ifdef TPAMD_DIAG
+        bw_case = fw_was_done ? 0 : (lds_word(xchg + 6) == loop + 1) ? 1 : 2;
+        bw_left = tpamd_stamp();
+#endif
       } else {
         const int r = S.template add_extremal<true>(iforw_lo, pf, false, /*wait_pair=*/true);   // B inside
+#ifdef TPAMD_DIAG
+        { const long long t = tpamd_stamp(); if (lane == 0) fw_stamp[0] = t; }
+#endif
         if (lane == 0) {
           xchg[1] = r;
           *reinterpret_cast<volatile int *>(xchg + 6) = loop + 1;
         }
         if (r < icrit_hi) post_next_critical_point(r);      // for the next loop, if there is one
+#ifdef TPAMD_DIAG
+        { const long long t = tpamd_stamp(); if (lane == 0) fw_stamp[1] = t; }
+#endif
       }
       TPAMD_ACCC(0, t0);
     }
     {
       TPAMD_T0C(t0);
       __threadfence_block();
+#ifdef TPAMD_DIAG
+      const long long fenced = tpamd_stamp();
+#endif
       __syncthreads();               // C
       TPAMD_ACCC(1, t0);             // time spent waiting for the partner's extremal
+#ifdef TPAMD_DIAG
+      if (w == 0) {                  // how the forward wave's wait splits up (JointSweep::diagx)
+        const long long fw_done = fw_stamp[0], fw_at_c = fw_stamp[1];
+        const long long fw_wait = (fenced > fw_at_c) ? fenced - fw_at_c : 0;
+        diagx[0] += bw_case == 0;      // (constant slots: a computed one would put the arrays in scratch memory)
+        diagx[1] += bw_case == 1;
+        diagx[2] += bw_case == 2;
+        diagx[7] += fenced - t0;
+        if (bw_case == 1) {
+          diagx[3] += bw_left - fw_done;
+          diagx[4] += fenced - t0;
+          diagx[5] += fw_wait;
+        } else if (bw_case == 0) {
+          diagx[6] += fw_wait;
+        }
+      }
+#endif
     }
     iback_lo = uniform_i32(xchg[0]);
     iforw_hi = uniform_i32(xchg[1]);
@@ -2271,7 +2395,7 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
     }
 #ifdef TPAMD_DIAG
     if (lane == 0 && ws.diag)
-      for (int k = 0; k < 32; k++) ws.diag[(size_t)b * 64 + 32 * w + k] = S.diag[k];
+      for (int k = 0; k < 32; k++) ws.diag[(size_t)b * kDiagRow + 32 * w + k] = S.diag[k];
 #endif
     return;
   }
@@ -2460,8 +2584,10 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   TPAMD_ACCC(3, t_tail);
   TPAMD_ACCC(15, t_all);
 #ifdef TPAMD_DIAG
-  if (lane == 0 && ws.diag)
-    for (int k = 0; k < 32; k++) ws.diag[(size_t)b * 64 + 32 * w + k] = S.diag[k];
+  if (lane == 0 && ws.diag) {
+    for (int k = 0; k < 32; k++) ws.diag[(size_t)b * kDiagRow + 32 * w + k] = S.diag[k];
+    for (int k = 0; k < kDiagExt; k++) ws.diag[(size_t)b * kDiagRow + 64 + kDiagExt * w + k] = S.diagx[k];
+  }
 #endif
 }
 

@@ -239,7 +239,8 @@ ABI_SYMBOLS = [
     "tpamd_buffer_set_download", "tpamd_buffer_set_download_device",
     "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
     "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
-    "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_kernel_vgprs",
+    "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_copy_diag_ext",
+    "tpamd_debug_kernel_vgprs",
     "tpamd_rebuild_time_device", "tpamd_profile_reset", "tpamd_profile_enable",
     "tpamd_profile_mean_ms", "tpamd_profile_kernel_name", "tpamd_profile_num_kernels",
 ]
@@ -405,6 +406,8 @@ def load_library():
     L.tpamd_debug_keep_boundary.argtypes = [vp, i]
     L.tpamd_debug_copy_diag.restype = i
     L.tpamd_debug_copy_diag.argtypes = [vp, i, vp]
+    L.tpamd_debug_copy_diag_ext.restype = i
+    L.tpamd_debug_copy_diag_ext.argtypes = [vp, i, vp]
     L.tpamd_debug_kernel_vgprs.restype = i
     L.tpamd_debug_kernel_vgprs.argtypes = [vp, i]
     L.tpamd_rebuild_time_device.restype = i
@@ -750,6 +753,11 @@ class Engine:
     def debug_diag(self, B):
         out = np.zeros((B, 64), dtype=np.int64)
         _check(self._lib.tpamd_debug_copy_diag(self._h, B, _ptr(out)), "tpamd_debug_copy_diag")
+        return out
+
+    def debug_diag_ext(self, B):
+        out = np.zeros((B, 32), dtype=np.int64)
+        _check(self._lib.tpamd_debug_copy_diag_ext(self._h, B, _ptr(out)), "tpamd_debug_copy_diag_ext")
         return out
 
     # ---------------------------------------------------------------- timing
