@@ -267,6 +267,91 @@ int tpamd_sample_pose_splines_host(tpamd_engine *engine, int num_paths, int num_
                                    const double *translation_points, const double *rotation_points,
                                    const double *path_start, const double *delta, double *poses);
 
+/* ---- Cartesian goals: the two device stages around the caller's IK ------------------------
+ * A Cartesian goal is pose waypoints plus joint seed waypoints. tpamd_fit_pose_waypoints_* turns
+ * them into the pose spline and the joint seed spline; tpamd_sample_ik_targets_* turns both into
+ * one pose target and one joint target per row of the IK table; the caller's IK (on the device)
+ * turns the targets into the table tpamd_planner_set_upload_ik_tables_device takes. The IK stays
+ * user code.
+ *
+ * Rows of a path's IK table as TimeableCartesianSplinePath::BuildIkTable counts them:
+ * PathIkIndex(knots.back()) + N + 1 = round(path_end / delta) + num_samples + 1
+ * (timeable_path_cartesian_spline.cc:671-674 with std::round). -1 for delta <= 0 or
+ * num_samples < 1. Host arithmetic only. */
+int tpamd_ik_table_rows(double path_end, double delta, int num_samples);
+/* TimeableCartesianSplinePath::SetWaypoints / FitSplineToWaypoints
+ * (timeable_path_cartesian_spline.cc:415-482) for num_paths paths at once. Path k takes waypoints
+ * waypoint_offsets[k] .. waypoint_offsets[k + 1]) of pose_waypoints [rows][7] (tx, ty, tz, qw, qx,
+ * qy, qz; quaternions are not normalised) and joint_waypoints [rows][D], with
+ * translation_rounding[k] and rotation_rounding[k] (any value passes through; CornerOffset's 1e-6
+ * rule is the only one):
+ *   - joint control points: PolyLineToControlPoints with the rotation rounding as the radius
+ *     (timeable_path_joint_spline.cc:252-292, the mirror passes options_.rounding());
+ *   - pose control points: PolyLineToBspline3Waypoints on poses with CornerOffset
+ *     (splines/spline_utils.cc:104-204);
+ *   - uniform degree-2 knots on [0, 1] (splines/bspline_base.cc:356-381), every knot multiplied by
+ *     max(L + L, 0.1) * 10, L the length of the translation control polygon (:436-438).
+ * Path k has P_k = max(3 W_k - 2, 4) control points. The outputs are packed raggedly, path k behind
+ * path k - 1, as tpamd_planner_set_upload_paths_ragged packs splines: knots (sum of P_k + 3 values),
+ * translation_points [sum P_k][3], rotation_points [sum P_k][4] (w, x, y, z), joint_control_points
+ * [sum P_k][D]. Per path: num_points[k], path_end[k] (the last knot) and status[k] TPAMD_PLAN_*. A
+ * path without waypoints gets TPAMD_PLAN_INVALID_ARGUMENT, num_points 0 and path_end 0, occupies no
+ * slots and leaves the other paths as they are without it. point_offsets [num_paths + 1] (may be
+ * NULL) receives the first control point of every path; it is always a HOST array, computed from
+ * the waypoint counts before the launch. The joint control points are bit-identical to the host
+ * mirror; the pose control points and knots agree with it to rounding (atan2 / sin / cos of the
+ * device math library).
+ * Call-level errors write nothing: a NULL engine or required array, num_paths < 0, num_dofs
+ * outside 1..16, waypoint_offsets[0] != 0 or decreasing offsets (TPAMD_E_INVALID_ARGUMENT); more
+ * than 65535 paths (TPAMD_E_UNSUPPORTED). Host pointers; synchronises. */
+int tpamd_fit_pose_waypoints_host(tpamd_engine *engine, int num_paths, int num_dofs,
+                                  const int32_t *waypoint_offsets, const double *pose_waypoints,
+                                  const double *joint_waypoints, const double *translation_rounding,
+                                  const double *rotation_rounding, double *knots,
+                                  double *translation_points, double *rotation_points,
+                                  double *joint_control_points, int32_t *num_points,
+                                  int32_t *point_offsets, double *path_end, int32_t *status);
+/* The same with every array except waypoint_offsets and point_offsets a device pointer. Enqueues
+ * on hip_stream (NULL: the null stream) and does not synchronise; the offsets go up on hip_stream
+ * first, into a buffer of the engine that the next call of these _device entries reuses (that call
+ * waits on its stream for this one's kernel). path_end lands in DEVICE memory: a caller that sizes
+ * the target buffers copies num_paths doubles down and calls tpamd_ik_table_rows. */
+int tpamd_fit_pose_waypoints_device(tpamd_engine *engine, int num_paths, int num_dofs,
+                                    const int32_t *waypoint_offsets, const double *pose_waypoints,
+                                    const double *joint_waypoints, const double *translation_rounding,
+                                    const double *rotation_rounding, double *knots,
+                                    double *translation_points, double *rotation_points,
+                                    double *joint_control_points, int32_t *num_points,
+                                    int32_t *point_offsets, double *path_end, int32_t *status,
+                                    void *hip_stream);
+/* The inputs of the IK callback as TimeableCartesianSplinePath::ExtendIkSolution evaluates them
+ * (timeable_path_cartesian_spline.cc:484-526), for a ragged batch. Path k has num_points[k] >= 3
+ * control points, packed as tpamd_fit_pose_waypoints_* packs them (no empty paths), and rows
+ * row_offsets[k] .. row_offsets[k + 1]); row r belongs to parameter r * delta[k]. Below
+ * knots.back() - delta the pose target is the translation spline (BSplineT::EvalCurve,
+ * splines/bspline.h:512-536) and the quaternion spline (BSplineQ::EvalCurve,
+ * splines/bsplineq.cc:223-244), exactly as tpamd_sample_pose_splines_* with path_start 0, and the
+ * joint target the joint spline's EvalCurve; from there on (:488, :499-502) the last control pose
+ * and the last joint control point, bit for bit. pose_targets [rows][7], joint_targets [rows][D].
+ * Paths of any size are sampled (control points are read from global memory, not staged).
+ * Call-level errors write nothing: a NULL engine or array, num_paths < 0, num_dofs outside 1..16,
+ * num_points[k] < 3, row_offsets[0] != 0 or decreasing, delta[k] <= 0. Host pointers; synchronises. */
+int tpamd_sample_ik_targets_host(tpamd_engine *engine, int num_paths, int num_dofs,
+                                 const int32_t *num_points, const int32_t *row_offsets,
+                                 const double *knots, const double *translation_points,
+                                 const double *rotation_points, const double *joint_control_points,
+                                 const double *delta, double *pose_targets, double *joint_targets);
+/* The same with the four spline arrays, delta and the two outputs device pointers; num_points and
+ * row_offsets stay HOST arrays. delta[k] cannot be checked on the host here: the kernel leaves the
+ * rows of a path whose delta is not > 0 untouched. Enqueues on hip_stream and does not synchronise
+ * (the staging of the offsets is that of tpamd_fit_pose_waypoints_device). */
+int tpamd_sample_ik_targets_device(tpamd_engine *engine, int num_paths, int num_dofs,
+                                   const int32_t *num_points, const int32_t *row_offsets,
+                                   const double *knots, const double *translation_points,
+                                   const double *rotation_points, const double *joint_control_points,
+                                   const double *delta, double *pose_targets, double *joint_targets,
+                                   void *hip_stream);
+
 /* ------------------------------------------------------------------------
  * Receding-horizon planning: the window loop of PathTimingTrajectory::Plan
  * (path_timing_trajectory.cc:628-660 around ComputeTimingProfile :307-475) for B planners with

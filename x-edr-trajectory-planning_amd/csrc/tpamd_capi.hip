@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "tpamd_stop.h"
 #include "tpamd_switch.h"
 #include "tpamd_fit.h"
+#include "tpamd_pose_fit.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 
 using namespace tpamd;
@@ -196,6 +198,9 @@ struct tpamd_engine {
   DeviceBuffer ws_buf;         // the current workspace
   DeviceBuffer stage;          // staging for the _host entry points
   DeviceBuffer rows;           // assembled constraint rows of Cartesian batches
+  DeviceBuffer pose_ints;      // the offset arrays of the _device pose-fit / IK-target calls
+  hipEvent_t ev_pose = nullptr;   // the last of those calls has read pose_ints
+  bool pose_busy = false;
   bool rows_for_plan = false;  // rows holds only zeros and rows written by window chaining (of any set on
                                // this engine, under its own split of the buffer: finite values, no more)
   Workspace ws{};
@@ -679,6 +684,8 @@ void tpamd_engine_destroy(tpamd_engine *e) {
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   e->stage.release();
   e->rows.release();
+  e->pose_ints.release();
+  if (e->ev_pose) (void)hipEventDestroy(e->ev_pose);
   delete e;
 }
 
@@ -1518,6 +1525,248 @@ int tpamd_sample_pose_splines_host(tpamd_engine *e, int num_paths, int num_sampl
   int rc = s.upload(e->stage, st);
   if (rc) return rc;
   rc = tpamd_sample_pose_splines_device(e, num_paths, num_samples, num_points, d_k, d_t, d_r, d_ps, d_dl, d_out, st);
+  return rc ? rc : s.download(st);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- Cartesian goals: pose fit and IK targets
+namespace {
+
+constexpr int kMaxPosePaths = 65535;      // the target kernel's grid has one row of blocks per path
+
+// The packing of a ragged batch of fitted paths: path k's control points start at point[k], its knots
+// at knot[k] = point[k] + 3 (paths with points before k). A path without points takes no slots.
+struct PosePacking {
+  std::vector<int32_t> point, knot;       // [n + 1]
+  bool build(int n, const int32_t *num_points) {
+    point.assign((size_t)n + 1, 0);
+    knot.assign((size_t)n + 1, 0);
+    long long pts = 0, kn = 0;
+    for (int k = 0; k < n; k++) {
+      pts += num_points[k];
+      kn += num_points[k] > 0 ? num_points[k] + 3 : 0;
+      if (kn * 16 > INT32_MAX) return false;      // [points][D <= 16] stays below 2^31 elements
+      point[k + 1] = (int32_t)pts;
+      knot[k + 1] = (int32_t)kn;
+    }
+    return true;
+  }
+  size_t points() const { return (size_t)point.back(); }
+  size_t knots() const { return (size_t)knot.back(); }
+};
+
+// The call-level checks of the two fit entries; fills the control-point count of every path.
+int pose_fit_args(const tpamd_engine *e, int num_paths, int num_dofs, const int32_t *offsets, const double *pose_wps,
+                  const double *joint_wps, const double *tround, const double *rround, const double *knots,
+                  const double *trans, const double *rot, const double *jcp, const int32_t *num_points,
+                  const double *path_end, const int32_t *status, std::vector<int32_t> *np, PosePacking *pk) {
+  if (!e || num_paths < 0 || !offsets || !tround || !rround || !num_points || !path_end || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (num_dofs < 1 || num_dofs > 16 || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  if (num_paths > kMaxPosePaths) return TPAMD_E_UNSUPPORTED;
+  np->resize(num_paths);
+  for (int k = 0; k < num_paths; k++) {
+    if (offsets[k + 1] < offsets[k]) return TPAMD_E_INVALID_ARGUMENT;
+    const long long W = (long long)offsets[k + 1] - offsets[k];
+    if (W > (1 << 24)) return TPAMD_E_UNSUPPORTED;
+    (*np)[k] = W < 1 ? 0 : fit_points((int)W);
+  }
+  if (!pk->build(num_paths, np->data())) return TPAMD_E_UNSUPPORTED;
+  if (num_paths && offsets[num_paths] > 0 && (!pose_wps || !joint_wps || !knots || !trans || !rot || !jcp))
+    return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+
+// The call-level checks of the two target entries (delta is checked by the host entry itself).
+int ik_target_args(const tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                   const int32_t *row_offsets, const double *knots, const double *trans, const double *rot,
+                   const double *jcp, const double *delta, const double *pose_targets, const double *joint_targets,
+                   PosePacking *pk, int *max_rows) {
+  if (!e || num_paths < 0 || !num_points || !row_offsets || !knots || !trans || !rot || !jcp || !delta ||
+      !pose_targets || !joint_targets)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (num_dofs < 1 || num_dofs > 16 || row_offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  if (num_paths > kMaxPosePaths) return TPAMD_E_UNSUPPORTED;
+  int most = 0;
+  for (int k = 0; k < num_paths; k++) {
+    if (num_points[k] < 3 || row_offsets[k + 1] < row_offsets[k]) return TPAMD_E_INVALID_ARGUMENT;
+    most = std::max(most, row_offsets[k + 1] - row_offsets[k]);
+  }
+  if (!pk->build(num_paths, num_points)) return TPAMD_E_UNSUPPORTED;
+  *max_rows = most;
+  return 0;
+}
+
+// The int arrays of a _device call go up on `st` into the engine's pose_ints (from pageable memory:
+// the copy has left `ints` when the call returns). The previous call's kernel may still read the
+// buffer on another stream: `st` waits for it; if the buffer has to grow, the host does.
+int stage_pose_ints(tpamd_engine *e, const std::vector<int32_t> &ints, hipStream_t st, const int32_t **dev) {
+  const size_t bytes = ints.size() * sizeof(int32_t);
+  if (!e->ev_pose) HIPCHK(hipEventCreateWithFlags(&e->ev_pose, hipEventDisableTiming));
+  if (e->pose_busy) {
+    if (bytes > e->pose_ints.bytes) {
+      HIPCHK(hipEventSynchronize(e->ev_pose));
+      e->pose_busy = false;
+    } else {
+      HIPCHK(hipStreamWaitEvent(st, e->ev_pose, 0));
+    }
+  }
+  if (e->pose_ints.reserve(std::max(bytes, (size_t)4096))) return TPAMD_E_HIP;
+  HIPCHK(hipMemcpyAsync(e->pose_ints.p, ints.data(), bytes, hipMemcpyHostToDevice, st));
+  *dev = (const int32_t *)e->pose_ints.p;
+  return 0;
+}
+int pose_ints_done(tpamd_engine *e, hipStream_t st) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e->ev_pose, st));
+  e->pose_busy = true;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_ik_table_rows(double path_end, double delta, int num_samples) {
+  if (!(delta > 0.0) || num_samples < 1) return -1;
+  return (int)std::round(path_end / delta) + num_samples + 1;     // PathIkIndex(knots.back()) + N + 1
+}
+
+int tpamd_fit_pose_waypoints_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *waypoint_offsets,
+                                    const double *pose_waypoints, const double *joint_waypoints,
+                                    const double *translation_rounding, const double *rotation_rounding,
+                                    double *knots, double *translation_points, double *rotation_points,
+                                    double *joint_control_points, int32_t *num_points, int32_t *point_offsets,
+                                    double *path_end, int32_t *status, void *hip_stream) {
+  std::vector<int32_t> np;
+  PosePacking pk;
+  if (int rc = pose_fit_args(e, num_paths, num_dofs, waypoint_offsets, pose_waypoints, joint_waypoints,
+                             translation_rounding, rotation_rounding, knots, translation_points, rotation_points,
+                             joint_control_points, num_points, path_end, status, &np, &pk))
+    return rc;
+  const size_t n = (size_t)num_paths;
+  if (point_offsets) std::memcpy(point_offsets, pk.point.data(), (n + 1) * sizeof(int32_t));
+  if (num_paths == 0) return 0;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  std::vector<int32_t> ints(waypoint_offsets, waypoint_offsets + n + 1);
+  ints.insert(ints.end(), pk.point.begin(), pk.point.end());
+  ints.insert(ints.end(), pk.knot.begin(), pk.knot.end());
+  const int32_t *d = nullptr;
+  if (int rc = stage_pose_ints(e, ints, st, &d)) return rc;
+  PoseFitParams p{};
+  p.Q = num_paths; p.D = num_dofs;
+  p.offsets = d; p.point_offsets = d + (n + 1); p.knot_offsets = d + 2 * (n + 1);
+  p.pose_wps = pose_waypoints; p.joint_wps = joint_waypoints;
+  p.translation_rounding = translation_rounding; p.rotation_rounding = rotation_rounding;
+  p.knots = knots; p.trans = translation_points; p.rot = rotation_points; p.joint_cp = joint_control_points;
+  p.num_points = num_points; p.path_end = path_end; p.status = status;
+  launch_fit_pose_waypoints(p, st);
+  return pose_ints_done(e, st);
+}
+
+int tpamd_fit_pose_waypoints_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *waypoint_offsets,
+                                  const double *pose_waypoints, const double *joint_waypoints,
+                                  const double *translation_rounding, const double *rotation_rounding,
+                                  double *knots, double *translation_points, double *rotation_points,
+                                  double *joint_control_points, int32_t *num_points, int32_t *point_offsets,
+                                  double *path_end, int32_t *status) {
+  std::vector<int32_t> np;
+  PosePacking pk;
+  if (int rc = pose_fit_args(e, num_paths, num_dofs, waypoint_offsets, pose_waypoints, joint_waypoints,
+                             translation_rounding, rotation_rounding, knots, translation_points, rotation_points,
+                             joint_control_points, num_points, path_end, status, &np, &pk))
+    return rc;
+  const size_t n = (size_t)num_paths, D = (size_t)num_dofs;
+  if (num_paths == 0) {
+    if (point_offsets) point_offsets[0] = 0;
+    return 0;
+  }
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  const size_t rows = (size_t)waypoint_offsets[n], P = pk.points();
+  const double *d_pw, *d_jw, *d_tr, *d_rr;
+  double *d_k, *d_t, *d_r, *d_j, *d_pe;
+  int32_t *d_np, *d_st;
+  HostStage s;
+  s.up(&d_pw, pose_waypoints, rows * 7);
+  s.up(&d_jw, joint_waypoints, rows * D);
+  s.up(&d_tr, translation_rounding, n);
+  s.up(&d_rr, rotation_rounding, n);
+  s.down(&d_k, knots, pk.knots());
+  s.down(&d_t, translation_points, P * 3);
+  s.down(&d_r, rotation_points, P * 4);
+  s.down(&d_j, joint_control_points, P * D);
+  s.down(&d_np, num_points, n);
+  s.down(&d_pe, path_end, n);
+  s.down(&d_st, status, n);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  int rc = tpamd_fit_pose_waypoints_device(e, num_paths, num_dofs, waypoint_offsets, d_pw, d_jw, d_tr, d_rr, d_k, d_t,
+                                           d_r, d_j, d_np, point_offsets, d_pe, d_st, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_sample_ik_targets_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                   const int32_t *row_offsets, const double *knots,
+                                   const double *translation_points, const double *rotation_points,
+                                   const double *joint_control_points, const double *delta, double *pose_targets,
+                                   double *joint_targets, void *hip_stream) {
+  PosePacking pk;
+  int max_rows = 0;
+  if (int rc = ik_target_args(e, num_paths, num_dofs, num_points, row_offsets, knots, translation_points,
+                              rotation_points, joint_control_points, delta, pose_targets, joint_targets, &pk,
+                              &max_rows))
+    return rc;
+  if (num_paths == 0 || max_rows == 0) return 0;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t n = (size_t)num_paths;
+  std::vector<int32_t> ints(num_points, num_points + n);
+  ints.push_back(0);
+  ints.insert(ints.end(), pk.point.begin(), pk.point.end());
+  ints.insert(ints.end(), pk.knot.begin(), pk.knot.end());
+  ints.insert(ints.end(), row_offsets, row_offsets + n + 1);
+  const int32_t *d = nullptr;
+  if (int rc = stage_pose_ints(e, ints, st, &d)) return rc;
+  IkTargetParams p{};
+  p.Q = num_paths; p.D = num_dofs;
+  p.num_points = d; p.point_offsets = d + (n + 1); p.knot_offsets = d + 2 * (n + 1); p.row_offsets = d + 3 * (n + 1);
+  p.knots = knots; p.trans = translation_points; p.rot = rotation_points; p.joint_cp = joint_control_points;
+  p.delta = delta; p.pose_targets = pose_targets; p.joint_targets = joint_targets;
+  launch_sample_ik_targets(p, max_rows, st);
+  return pose_ints_done(e, st);
+}
+
+int tpamd_sample_ik_targets_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                 const int32_t *row_offsets, const double *knots, const double *translation_points,
+                                 const double *rotation_points, const double *joint_control_points,
+                                 const double *delta, double *pose_targets, double *joint_targets) {
+  PosePacking pk;
+  int max_rows = 0;
+  if (int rc = ik_target_args(e, num_paths, num_dofs, num_points, row_offsets, knots, translation_points,
+                              rotation_points, joint_control_points, delta, pose_targets, joint_targets, &pk,
+                              &max_rows))
+    return rc;
+  for (int k = 0; k < num_paths; k++)
+    if (!(delta[k] > 0.0)) return TPAMD_E_INVALID_ARGUMENT;
+  if (num_paths == 0 || max_rows == 0) return 0;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)num_paths, D = (size_t)num_dofs, P = pk.points(), rows = (size_t)row_offsets[n];
+  const double *d_k, *d_t, *d_r, *d_j, *d_dl;
+  double *d_pose, *d_joint;
+  HostStage s;
+  s.up(&d_k, knots, pk.knots());
+  s.up(&d_t, translation_points, P * 3);
+  s.up(&d_r, rotation_points, P * 4);
+  s.up(&d_j, joint_control_points, P * D);
+  s.up(&d_dl, delta, n);
+  s.down(&d_pose, pose_targets, rows * 7);
+  s.down(&d_joint, joint_targets, rows * D);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  int rc = tpamd_sample_ik_targets_device(e, num_paths, num_dofs, num_points, row_offsets, d_k, d_t, d_r, d_j, d_dl,
+                                          d_pose, d_joint, st);
   return rc ? rc : s.download(st);
 }
 

@@ -16,7 +16,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
-            "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip"]
+            "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
+            "tpamd_pose_fit.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -55,7 +56,8 @@ def _compile(target, extra_flags, force, verbose):
     os.makedirs(objdir, exist_ok=True)
     flags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags)
     units = [(os.path.join(objdir, "capi.o"), ["tpamd_capi.hip"]),
-             (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"])]
+             (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"]),
+             (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"])]
     for d, e in SWEEP_INSTANCES:
         units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
                       ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
@@ -208,6 +210,8 @@ ABI_SYMBOLS = [
     "tpamd_engine_workspace_bytes",
     "tpamd_time_joint_paths_device",
     "tpamd_time_joint_paths_host", "tpamd_sample_joint_paths_host",
+    "tpamd_ik_table_rows", "tpamd_fit_pose_waypoints_host", "tpamd_fit_pose_waypoints_device",
+    "tpamd_sample_ik_targets_host", "tpamd_sample_ik_targets_device",
     "tpamd_time_joint_groups_device", "tpamd_time_joint_groups_host",
     "tpamd_optimize_rows_device", "tpamd_optimize_rows_host",
     "tpamd_time_cartesian_paths_device", "tpamd_time_cartesian_paths_host",
@@ -315,6 +319,15 @@ def load_library():
     L.tpamd_sample_pose_splines_host.argtypes = [vp, i, i, i] + [vp] * 6
     L.tpamd_sample_pose_splines_device.restype = i
     L.tpamd_sample_pose_splines_device.argtypes = [vp, i, i, i] + [vp] * 6 + [vp]
+    L.tpamd_ik_table_rows.restype = i
+    L.tpamd_ik_table_rows.argtypes = [C.c_double, C.c_double, i]
+    for name in ("tpamd_fit_pose_waypoints_host", "tpamd_fit_pose_waypoints_device",
+                 "tpamd_sample_ik_targets_host", "tpamd_sample_ik_targets_device"):
+        getattr(L, name).restype = i
+    L.tpamd_fit_pose_waypoints_host.argtypes = [vp, i, i] + [vp] * 13
+    L.tpamd_fit_pose_waypoints_device.argtypes = [vp, i, i] + [vp] * 13 + [vp]
+    L.tpamd_sample_ik_targets_host.argtypes = [vp, i, i] + [vp] * 9
+    L.tpamd_sample_ik_targets_device.argtypes = [vp, i, i] + [vp] * 9 + [vp]
     L.tpamd_find_max_sd2_host.restype = i
     L.tpamd_find_max_sd2_host.argtypes = [vp, i, i] + [vp] * 7
     L.tpamd_query_device.restype = i
@@ -600,6 +613,111 @@ class Engine:
                                                         _ptr(tr), _ptr(ro), _ptr(ps), _ptr(dl),
                                                         _ptr(out)), "tpamd_sample_pose_splines_host")
         return out
+
+    # ------------------------------------------------------------ Cartesian goals
+    def fit_pose_waypoints(self, pose_waypoints, joint_waypoints, offsets, translation_rounding=0.05,
+                           rotation_rounding=0.2, stream=None):
+        """TimeableCartesianSplinePath::SetWaypoints for B paths (tpamd_fit_pose_waypoints_*): path k
+        takes rows offsets[k]:offsets[k + 1] of pose_waypoints [rows][7] (translation, then the
+        quaternion w, x, y, z) and joint_waypoints [rows][D]; the roundings are [B] (or one number).
+        Returns a dict: knots, translation_points [sum P][3], rotation_points [sum P][4],
+        joint_control_points [sum P][D] (packed raggedly), num_points, path_end, status [B] and
+        point_offsets [B + 1] (always a numpy array). CUDA inputs go through the _device entry on
+        `stream` (default: torch's current stream) and give CUDA tensors; numpy arrays go through
+        the host entry, which synchronises, and give numpy arrays."""
+        import torch
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        B = off.shape[0] - 1
+        if B < 0:
+            raise TpamdError("waypoint offsets need at least one entry")
+        W = np.diff(off.astype(np.int64))
+        npts = np.where(W < 1, 0, np.where(W == 1, 4, 3 * W - 2))
+        P, K = int(npts.sum()), int((npts + 3 * (npts > 0)).sum())
+        rows = int(off[-1])
+        point_offsets = np.zeros(B + 1, dtype=np.int32)
+        if _is_cuda(pose_waypoints):
+            dev = pose_waypoints.device
+            f = lambda x, shape, what: PlannerSet._cuda(x, torch.float64, dev, shape, what)
+            per = lambda x, what: f(x if hasattr(x, "shape") else torch.full((B,), float(x), dtype=torch.float64),
+                                    (B,), what)
+            pw = f(pose_waypoints, (rows, 7), "pose_waypoints")
+            D = int(joint_waypoints.shape[-1])
+            jw = f(joint_waypoints, (rows, D), "joint_waypoints")
+            tr, rr = per(translation_rounding, "translation_rounding"), per(rotation_rounding, "rotation_rounding")
+            new = lambda shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+            out = dict(knots=new((K,)), translation_points=new((P, 3)), rotation_points=new((P, 4)),
+                       joint_control_points=new((P, D)), num_points=new((B,), torch.int32), path_end=new((B,)),
+                       status=torch.full((B,), -1, dtype=torch.int32, device=dev))
+            _check(self._lib.tpamd_fit_pose_waypoints_device(
+                self._h, B, D, _ptr(off), _ptr(pw), _ptr(jw), _ptr(tr), _ptr(rr), _ptr(out["knots"]),
+                _ptr(out["translation_points"]), _ptr(out["rotation_points"]), _ptr(out["joint_control_points"]),
+                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"]),
+                _stream_ptr(stream)), "tpamd_fit_pose_waypoints_device")
+        else:
+            pw = _host(pose_waypoints, np.float64, (rows, 7), "pose_waypoints")
+            jw = _host(joint_waypoints, np.float64, what="joint_waypoints")
+            if jw.ndim != 2 or jw.shape[0] != rows:
+                raise TpamdError("joint_waypoints has shape %s, expected (%d, D)" % (jw.shape, rows))
+            D = jw.shape[1]
+            per = lambda x, what: _host(np.broadcast_to(_host(x, np.float64), (B,)), np.float64, (B,), what)
+            tr, rr = per(translation_rounding, "translation_rounding"), per(rotation_rounding, "rotation_rounding")
+            out = dict(knots=np.zeros(K), translation_points=np.zeros((P, 3)), rotation_points=np.zeros((P, 4)),
+                       joint_control_points=np.zeros((P, D)), num_points=np.zeros(B, dtype=np.int32),
+                       path_end=np.zeros(B), status=np.full(B, -1, dtype=np.int32))
+            _check(self._lib.tpamd_fit_pose_waypoints_host(
+                self._h, B, D, _ptr(off), _ptr(pw), _ptr(jw), _ptr(tr), _ptr(rr), _ptr(out["knots"]),
+                _ptr(out["translation_points"]), _ptr(out["rotation_points"]), _ptr(out["joint_control_points"]),
+                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"])),
+                "tpamd_fit_pose_waypoints_host")
+        out["point_offsets"] = point_offsets
+        return out
+
+    def sample_ik_targets(self, fit, delta, row_offsets, stream=None):
+        """The IK callback's inputs for a ragged batch (tpamd_sample_ik_targets_*): `fit` holds knots,
+        translation_points, rotation_points, joint_control_points (packed, as fit_pose_waypoints
+        returns them; every path needs at least 3 control points) and point_offsets [B + 1] or
+        num_points [B]; row r of path k, rows row_offsets[k]:row_offsets[k + 1], belongs to parameter
+        r * delta[k]. Returns (pose_targets [rows][7], joint_targets [rows][D]) on the side the
+        spline arrays are on."""
+        import torch
+        off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
+        B = off.shape[0] - 1
+        if fit.get("point_offsets") is not None:
+            npts = np.diff(_host(fit["point_offsets"], np.int32).reshape(-1)).astype(np.int32)
+        else:
+            npts = _host(fit["num_points"], np.int32).reshape(-1)
+        npts = np.ascontiguousarray(npts)
+        if npts.shape[0] != B:
+            raise TpamdError("row offsets need one entry per path plus one")
+        rows = int(off[-1]) if B else 0
+        jc = fit["joint_control_points"]
+        D = int(jc.shape[-1])
+        if _is_cuda(jc):
+            dev = jc.device
+            f = lambda x, what: PlannerSet._cuda(x, torch.float64, dev, None, what)
+            dl = f(delta if hasattr(delta, "shape") else torch.full((B,), float(delta), dtype=torch.float64), "delta")
+            if tuple(dl.shape) != (B,):
+                raise TpamdError("delta has shape %s, expected (%d,)" % (tuple(dl.shape), B))
+            pose = torch.zeros((rows, 7), dtype=torch.float64, device=dev)
+            joint = torch.zeros((rows, D), dtype=torch.float64, device=dev)
+            _check(self._lib.tpamd_sample_ik_targets_device(
+                self._h, B, D, _ptr(npts), _ptr(off), _ptr(f(fit["knots"], "knots")),
+                _ptr(f(fit["translation_points"], "translation_points")),
+                _ptr(f(fit["rotation_points"], "rotation_points")), _ptr(f(jc, "joint_control_points")), _ptr(dl),
+                _ptr(pose), _ptr(joint), _stream_ptr(stream)), "tpamd_sample_ik_targets_device")
+            return pose, joint
+        h = lambda x, what: _host(x, np.float64, what=what)
+        dl = _host(np.broadcast_to(_host(delta, np.float64), (B,)), np.float64, (B,), "delta")
+        pose, joint = np.zeros((rows, 7)), np.zeros((rows, D))
+        _check(self._lib.tpamd_sample_ik_targets_host(
+            self._h, B, D, _ptr(npts), _ptr(off), _ptr(h(fit["knots"], "knots")),
+            _ptr(h(fit["translation_points"], "translation_points")), _ptr(h(fit["rotation_points"], "rotation_points")),
+            _ptr(h(jc, "joint_control_points")), _ptr(dl), _ptr(pose), _ptr(joint)), "tpamd_sample_ik_targets_host")
+        return pose, joint
+
+    def ik_table_rows(self, path_end, delta, num_samples):
+        """BuildIkTable's row count round(path_end / delta) + num_samples + 1 (tpamd_ik_table_rows)."""
+        return self._lib.tpamd_ik_table_rows(float(path_end), float(delta), int(num_samples))
 
     def find_max_sd2(self, a, b, lower, upper):
         """Host numpy [num][C] -> (sd2max, sddmax, sd2zero) [num]."""
@@ -1000,6 +1118,72 @@ class PlannerSet:
         _check(self._lib.tpamd_planner_set_upload_ik_tables(
             self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _ptr(pe), _ptr(vm), _ptr(am), _ptr(vt),
             _ptr(vr), _ptr(dl), _ptr(iv), _ptr(ps)), "tpamd_planner_set_upload_ik_tables")
+
+    def set_pose_waypoints(self, pose_waypoints, joint_waypoints, offsets, ik, max_velocity, max_acceleration,
+                           max_translational_velocity, max_rotational_velocity, delta, translation_rounding=0.05,
+                           rotation_rounding=0.2, initial_velocity=None, ids=None, stream=None):
+        """New Cartesian goals for the listed planners of a Cartesian set, without the host touching
+        per-row data: listed planner k (ids[k], or k) takes rows offsets[k]:offsets[k + 1] of
+        pose_waypoints [rows][7] (translation, then quaternion w, x, y, z) and joint_waypoints
+        [rows][D], CUDA tensors (host arrays are copied up). The chain:
+          1. Engine.fit_pose_waypoints on the device (TimeableCartesianSplinePath::SetWaypoints with
+             CartesianPathOptions' roundings; translation_rounding defaults to its 0.05);
+          2. path_end comes down (count doubles) and sizes each table with tpamd_ik_table_rows;
+          3. Engine.sample_ik_targets;
+          4. ik(pose_targets [rows][7], joint_targets [rows][D], row_offsets) -> (ik_positions
+             [rows][D], jacobians [rows][6][D]) as CUDA tensors: the caller's IK;
+          5. set_ik_tables with those tensors, path_end of the fit and path_state 1 (kNewPath).
+        A planner whose fit failed (no waypoints: TPAMD_PLAN_INVALID_ARGUMENT) is left out of steps 3-5
+        and keeps its path and plan. Limits and delta as for set_ik_tables ([count][D], [count] or one
+        number). Returns (status int32 [count], rows int32 [count]) as CPU tensors; rows is 0 where the
+        fit failed. Raises TpamdError on a joint set, as set_ik_tables does."""
+        import torch
+        if not self.cartesian:
+            _check(-1, "tpamd_planner_set_upload_ik_tables_device")      # what the entry returns on a joint set
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("waypoint offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        D = self.D
+        dev = pose_waypoints.device if _is_cuda(pose_waypoints) else torch.device("cuda", self.device)
+        f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
+        per = lambda x, what: f(x if hasattr(x, "shape") else torch.full((n,), float(x), dtype=torch.float64),
+                                (n,), what)
+        rows_w = int(off[-1]) if n else 0
+        pw, jw = f(pose_waypoints, (rows_w, 7), "pose_waypoints"), f(joint_waypoints, (rows_w, D), "joint_waypoints")
+        dl = per(delta, "delta")
+        vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
+        vt, vr = per(max_translational_velocity, "max_translational_velocity"), per(max_rotational_velocity,
+                                                                                    "max_rotational_velocity")
+        iv = None if initial_velocity is None else f(initial_velocity, (n, D), "initial_velocity")
+        E = self._engine
+        fit = E.fit_pose_waypoints(pw, jw, off, per(translation_rounding, "translation_rounding"),
+                                   per(rotation_rounding, "rotation_rounding"), stream=stream)
+        if stream is not None:                                    # the copies below run on torch's stream
+            stream.synchronize() if hasattr(stream, "synchronize") else torch.cuda.synchronize(dev)
+        path_end = fit["path_end"].cpu().numpy()                  # count doubles; orders after the fit
+        status = fit["status"].cpu().numpy()
+        dl_h = dl.cpu().numpy()
+        ok = np.flatnonzero(status == 0)
+        rows = np.zeros(n, dtype=np.int32)
+        for k in ok:
+            r = self._lib.tpamd_ik_table_rows(float(path_end[k]), float(dl_h[k]), self.N)
+            if r < 0:
+                raise TpamdError("delta[%d] = %r is not positive" % (k, float(dl_h[k])))
+            rows[k] = r
+        if ok.size:
+            sel = torch.as_tensor(ok, device=dev)
+            row_offsets = np.concatenate([[0], np.cumsum(rows[ok])]).astype(np.int32)
+            # the spline arrays hold exactly the fitted paths: a path without waypoints has no slots
+            sub = dict(fit, point_offsets=np.concatenate([[0], np.cumsum(fit["point_offsets"][1:][ok]
+                                                                         - fit["point_offsets"][:-1][ok])]))
+            pose_t, joint_t = E.sample_ik_targets(sub, dl[sel].contiguous(), row_offsets, stream=stream)
+            q, J = ik(pose_t, joint_t, row_offsets)
+            all_ids = np.arange(n, dtype=np.int32) if ida is None else ida
+            take = lambda x: None if x is None else x[sel].contiguous()
+            self.set_ik_tables(q, J, row_offsets, fit["path_end"][sel].contiguous(), take(vm), take(am), take(vt),
+                               take(vr), take(dl), initial_velocity=take(iv), ids=all_ids[ok], stream=stream)
+        return torch.from_numpy(status.astype(np.int32)), torch.from_numpy(rows)
 
     def download_ik_table(self, planner):
         """The resident IK table of one planner of a Cartesian set: (ik_positions [rows][D],

@@ -1,8 +1,11 @@
 #include "path_timing_trajectory_set.h"
 
+#include <hip/hip_runtime_api.h>
+
 #include <algorithm>
 #include <cstdio>
 #include <limits>
+#include <string>
 
 namespace trajectory_planning {
 
@@ -182,6 +185,146 @@ Status PathTimingTrajectorySet::SetIkTables(const std::vector<size_t> &planners,
   if (rc != 0) return InternalError(tpamd_error_string(rc));
   for (size_t k = 0; k < n; k++) summary_[planners[k]].path_state = state[k];
   return OkStatus();
+}
+
+namespace {
+// Device memory of one SetCartesianWaypointPaths call: freed when the call ends.
+struct DeviceArrays {
+  std::vector<void *> ptrs;
+  bool failed = false;
+  template <typename T>
+  T *take(size_t count, const T *from = nullptr) {
+    void *p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { failed = true; return nullptr; }
+    ptrs.push_back(p);
+    if (from && count && hipMemcpy(p, from, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) failed = true;
+    return (T *)p;
+  }
+  ~DeviceArrays() { for (void *p : ptrs) (void)hipFree(p); }
+};
+}  // namespace
+
+Status PathTimingTrajectorySet::SetCartesianWaypointPaths(const std::vector<size_t> &planners,
+                                                          const std::vector<std::vector<Pose3d>> &pose_waypoints,
+                                                          const std::vector<std::vector<VectorXd>> &joint_waypoints,
+                                                          const CartesianPathLimits &lim, const DeviceIkFunc &ik) {
+  if (!init_status_.ok()) return init_status_;
+  if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetWaypointPaths)");
+  const size_t n = planners.size(), D = options_.GetNumDofs(), N = options_.GetNumPathSamples();
+  if (!ik) return InvalidArgumentError("no IK function");
+  if (pose_waypoints.size() != n || joint_waypoints.size() != n || lim.max_velocity.size() != n ||
+      lim.max_acceleration.size() != n || lim.max_translational_velocity.size() != n ||
+      lim.max_rotational_velocity.size() != n || (!lim.initial_velocity.empty() && lim.initial_velocity.size() != n))
+    return InvalidArgumentError("one waypoint list and one set of limits per listed planner");
+  if (!(lim.delta_parameter > 0.0)) return InvalidArgumentError("delta_parameter must be positive");
+  std::vector<char> seen(num_planners_, 0);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_ || seen[planners[k]]) return InvalidArgumentError("no such planner, or listed twice");
+    seen[planners[k]] = 1;
+    if (lim.max_velocity[k].size() != D || lim.max_acceleration[k].size() != D ||
+        (!lim.initial_velocity.empty() && lim.initial_velocity[k].size() != D))
+      return InvalidArgumentError("a limit or an initial velocity of the wrong dimension");
+  }
+  if (n == 0) return OkStatus();
+  // the waypoints, packed; a planner whose lists do not fit goes to the device without waypoints
+  std::vector<int32_t> offsets(n + 1, 0);
+  std::vector<double> pose, joint;
+  for (size_t k = 0; k < n; k++) {
+    bool ok = pose_waypoints[k].size() == joint_waypoints[k].size();
+    for (const VectorXd &w : joint_waypoints[k]) ok = ok && w.size() == D;
+    if (ok) {
+      for (const Pose3d &p : pose_waypoints[k]) {
+        const Quaterniond &q = p.quaternion();
+        const double row[7] = {p.translation()[0], p.translation()[1], p.translation()[2], q.w, q.x, q.y, q.z};
+        pose.insert(pose.end(), row, row + 7);
+      }
+      for (const VectorXd &w : joint_waypoints[k]) joint.insert(joint.end(), w.begin(), w.end());
+    }
+    offsets[k + 1] = offsets[k] + (ok ? (int32_t)pose_waypoints[k].size() : 0);
+  }
+  int previous = 0;
+  if (hipGetDevice(&previous) != hipSuccess || hipSetDevice(lease_.device()) != hipSuccess)
+    return InternalError("no HIP device");
+  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{previous};
+  hipStream_t st = nullptr;
+  DeviceArrays mem;
+  // 1. the fit
+  size_t points = 0, knots = 0;
+  for (size_t k = 0; k < n; k++) {
+    const size_t W = (size_t)(offsets[k + 1] - offsets[k]);
+    const size_t P = W < 1 ? 0 : (W == 1 ? 4 : 3 * W - 2);
+    points += P;
+    knots += P ? P + 3 : 0;
+  }
+  const std::vector<double> tr(n, lim.translation_rounding), rr(n, lim.rotation_rounding);
+  double *d_pose = mem.take<double>(pose.size(), pose.data()), *d_joint = mem.take<double>(joint.size(), joint.data());
+  double *d_tr = mem.take<double>(n, tr.data()), *d_rr = mem.take<double>(n, rr.data());
+  double *d_knots = mem.take<double>(knots), *d_t = mem.take<double>(points * 3), *d_r = mem.take<double>(points * 4);
+  double *d_j = mem.take<double>(points * D), *d_end = mem.take<double>(n);
+  int32_t *d_np = mem.take<int32_t>(n), *d_st = mem.take<int32_t>(n);
+  if (mem.failed) return InternalError("device memory for the fit");
+  std::vector<int32_t> point_offsets(n + 1, 0), fit_status(n, 0);
+  std::vector<double> path_end(n, 0.0);
+  int rc = tpamd_fit_pose_waypoints_device(lease_.get(), (int)n, (int)D, offsets.data(), d_pose, d_joint, d_tr, d_rr,
+                                           d_knots, d_t, d_r, d_j, d_np, point_offsets.data(), d_end, d_st, st);
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  // 2. path_end and the statuses come down (n values each)
+  if (hipMemcpy(path_end.data(), d_end, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(fit_status.data(), d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return InternalError("reading the fit's results");
+  // 3. the rows of every fitted planner; a planner without waypoints has no slots in the spline arrays
+  std::vector<int32_t> ids, num_points, row_offsets(1, 0), state;
+  std::vector<double> end_ok, vmax, amax, iv, vt, vr;
+  Status first_bad = OkStatus();
+  for (size_t k = 0; k < n; k++) {
+    if (fit_status[k] != TPAMD_PLAN_OK) {
+      if (first_bad.ok())
+        first_bad = InvalidArgumentError("planner " + std::to_string(planners[k]) +
+                                         ": no waypoints, or pose and joint waypoints that do not match");
+      continue;
+    }
+    const int rows = tpamd_ik_table_rows(path_end[k], lim.delta_parameter, (int)N);
+    if (rows < 0) return InternalError("tpamd_ik_table_rows");
+    ids.push_back((int32_t)planners[k]);
+    num_points.push_back(point_offsets[k + 1] - point_offsets[k]);
+    row_offsets.push_back(row_offsets.back() + rows);
+    end_ok.push_back(path_end[k]);
+    vmax.insert(vmax.end(), lim.max_velocity[k].begin(), lim.max_velocity[k].end());
+    amax.insert(amax.end(), lim.max_acceleration[k].begin(), lim.max_acceleration[k].end());
+    if (!lim.initial_velocity.empty()) iv.insert(iv.end(), lim.initial_velocity[k].begin(), lim.initial_velocity[k].end());
+    vt.push_back(lim.max_translational_velocity[k]);
+    vr.push_back(lim.max_rotational_velocity[k]);
+    state.push_back(1);                 // kNewPath
+  }
+  const size_t m = ids.size(), rows = (size_t)row_offsets.back();
+  if (m == 0) return first_bad;
+  const std::vector<double> dl(m, lim.delta_parameter);
+  double *d_dl = mem.take<double>(m, dl.data()), *d_end_ok = mem.take<double>(m, end_ok.data());
+  double *d_vmax = mem.take<double>(m * D, vmax.data()), *d_amax = mem.take<double>(m * D, amax.data());
+  double *d_iv = iv.empty() ? nullptr : mem.take<double>(m * D, iv.data());
+  double *d_vt = mem.take<double>(m, vt.data()), *d_vr = mem.take<double>(m, vr.data());
+  int32_t *d_state = mem.take<int32_t>(m, state.data());
+  double *d_pose_t = mem.take<double>(rows * 7), *d_joint_t = mem.take<double>(rows * D);
+  double *d_q = mem.take<double>(rows * D), *d_J = mem.take<double>(rows * 6 * D);
+  if (mem.failed) return InternalError("device memory for the targets and the tables");
+  // 4. the targets, 5. the caller's IK, 6. the tables
+  rc = tpamd_sample_ik_targets_device(lease_.get(), (int)m, (int)D, num_points.data(), row_offsets.data(), d_knots, d_t,
+                                      d_r, d_j, d_dl, d_pose_t, d_joint_t, st);
+  if (rc != 0) {
+    (void)hipDeviceSynchronize();
+    return InternalError(tpamd_error_string(rc));
+  }
+  const Status ik_status = ik(d_pose_t, d_joint_t, row_offsets, d_q, d_J, st);
+  if (!ik_status.ok()) {
+    (void)hipDeviceSynchronize();
+    return ik_status;
+  }
+  rc = tpamd_planner_set_upload_ik_tables_device(set_, (int)m, ids.data(), row_offsets.data(), d_q, d_J, d_end_ok, d_vmax,
+                                                 d_amax, d_vt, d_vr, d_dl, d_iv, d_state, st);
+  if (hipDeviceSynchronize() != hipSuccess) return InternalError("the device chain failed");   // before mem goes
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  for (size_t k = 0; k < m; k++) summary_[ids[k]].path_state = 1;
+  return first_bad;
 }
 
 Status PathTimingTrajectorySet::GetIkTable(size_t planner, std::vector<double> *ik_positions,

@@ -16,6 +16,7 @@
 #ifndef TPAMD_HOST_PATH_TIMING_TRAJECTORY_SET_H_
 #define TPAMD_HOST_PATH_TIMING_TRAJECTORY_SET_H_
 
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -63,6 +64,24 @@ struct IkTables {
   std::vector<int32_t> path_state;
 };
 
+// Limits and path options of the planners listed in SetCartesianWaypointPaths, one entry per listed
+// planner (initial_velocity may be empty: zero). The roundings and delta_parameter are the
+// CartesianPathOptions of every listed path (translation_rounding 0.05, rounding 0.2 and
+// delta_parameter 0.005 are the options' defaults).
+struct CartesianPathLimits {
+  std::vector<VectorXd> max_velocity, max_acceleration, initial_velocity;
+  std::vector<double> max_translational_velocity, max_rotational_velocity;
+  double translation_rounding = 0.05, rotation_rounding = 0.2, delta_parameter = 0.005;
+};
+
+// The caller's IK on the device (SetCartesianWaypointPaths): pose_targets [rows][7] (translation, then
+// quaternion w, x, y, z) and joint_targets [rows][dofs] are DEVICE pointers, row_offsets (host) says
+// which rows belong to which loaded planner; the function fills the DEVICE arrays ik_positions
+// [rows][dofs] and jacobians [rows][6][dofs] (row-major), enqueueing on hip_stream (a hipStream_t).
+using DeviceIkFunc = std::function<Status(const double *pose_targets, const double *joint_targets,
+                                          const std::vector<int32_t> &row_offsets, double *ik_positions,
+                                          double *jacobians, void *hip_stream)>;
+
 // Constructor tag of a Cartesian set: rows per planner the IK tables hold to start with (they grow).
 struct CartesianTableCapacity {
   size_t rows;
@@ -95,6 +114,21 @@ class PathTimingTrajectorySet {
   Status SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths);
   // Raw tables for the listed planners (each listed once).
   Status SetIkTables(const std::vector<size_t> &planners, const IkTables &tables);
+  // New Cartesian goals for the listed planners (each listed once) without per-row data on the host:
+  // pose_waypoints[k] / joint_waypoints[k] are fitted on the device
+  // (tpamd_fit_pose_waypoints_device: TimeableCartesianSplinePath::SetWaypoints), path_end comes
+  // down and sizes each table (tpamd_ik_table_rows), the pose and joint targets of every table row
+  // are sampled on the device (tpamd_sample_ik_targets_device), `ik` turns them into the tables in
+  // device memory, and tpamd_planner_set_upload_ik_tables_device loads them as new paths. A planner
+  // whose waypoint lists are empty, differ in length or hold a joint waypoint of the wrong
+  // dimension is left as it is (path and plan); the others are loaded and the call returns
+  // InvalidArgument naming the first such planner. FailedPrecondition on a joint set; a planner out
+  // of range or listed twice, vectors of the wrong length or a non-positive delta_parameter fail the
+  // call and change nothing. Synchronises.
+  Status SetCartesianWaypointPaths(const std::vector<size_t> &planners,
+                                   const std::vector<std::vector<Pose3d>> &pose_waypoints,
+                                   const std::vector<std::vector<VectorXd>> &joint_waypoints,
+                                   const CartesianPathLimits &limits, const DeviceIkFunc &ik);
   // The planner's resident table (no table: empty).
   Status GetIkTable(size_t planner, std::vector<double> *ik_positions, std::vector<double> *jacobians) const;
   PathTimingTrajectorySet(const PathTimingTrajectorySet &) = delete;
