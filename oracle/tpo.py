@@ -439,6 +439,13 @@ class Planner:
         knots, cps = _f64(knots), _f64(cps)
         self._L.tpo_planner_set_spline(self._p, knots, len(knots), cps, cps.shape[0], int(state))
 
+    def set_initial_velocity(self, velocity):
+        """TimeablePath::SetInitialVelocity: the joint velocity the next Plan of a new or modified
+        path starts from."""
+        v = _f64(velocity).reshape(-1)
+        assert v.shape[0] == self.D
+        self._L.tpo_planner_set_initial_velocity(self._p, v)
+
     def plan(self, start_ns, horizon_ns):
         return self._L.tpo_planner_plan(self._p, int(start_ns), int(horizon_ns))
 

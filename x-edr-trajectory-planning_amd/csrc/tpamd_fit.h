@@ -15,6 +15,12 @@
 // fit_waypoints compiles for the host as well (TPAMD_HD): tests/cpp/test_fit_waypoints.cc holds it
 // bit-equal to the mirror and to the oracle's fit. The operations are the mirror's, in its order (the library
 // is built with -ffp-contract=off; '/' and sqrt are correctly rounded on both sides).
+// tests/switch_reference.py restates the fit from the reference's sources and checks what a fit
+// means (waypoints on control points 0, 3, 6, ..., uniform knots, the last knot against the polygon
+// length in high precision): tests/test_switch_reference_cpu.py holds fit_waypoints, the mirror,
+// the oracle and that restatement bit-equal for every D = 1..16, tests/test_gpu_switch_all_dofs.py
+// holds k_pset_set_waypoints to it at every D through both entries, and
+// tests/cpp/test_set_waypoints.cc runs 260-planner sets at D = 3 and 7.
 //
 // k_pset_set_waypoints: one thread per listed planner fits into the planner's own slot and writes
 // what tpamd_planner_set_upload_paths_ragged writes with path_state 1 (kNewPath): knots, control

@@ -18,6 +18,15 @@
 // -ffp-contract=off; '/' and sqrt are correctly rounded on both sides), so the results are
 // bit-identical. One thread per planner: the work is O(P D + W D) control flow whose sums are
 // ordered, which leaves nothing to split across lanes.
+//
+// What holds them besides the mirror: tests/switch_reference.py restates the edit from the
+// reference's sources and checks what a switch means in exact arithmetic (kept curve, join,
+// knots, end point, least-distance projection). tests/cpp/test_switch_reference.cc with
+// tests/test_switch_reference_cpu.py holds the routines, the mirror and that restatement
+// bit-equal for every D = 1..16; tests/test_gpu_switch_all_dofs.py holds k_pset_switch to it at
+// every D (every edge branch, shuffled ids, a partly filled last wave, P_cap growth, the
+// committed velocity through the next Plan); tests/cpp/test_set_switch.cc follows 260-planner
+// sets at D = 3 and 7 against the mirror. DESIGN.md "What holds the spline edits".
 #pragma once
 
 #include <math.h>
