@@ -351,6 +351,23 @@ int tpamd_sample_ik_targets_device(tpamd_engine *engine, int num_paths, int num_
                                    const double *rotation_points, const double *joint_control_points,
                                    const double *delta, double *pose_targets, double *joint_targets,
                                    void *hip_stream);
+/* The same two entries for a part of every table: path k's output rows row_offsets[k] ..
+ * row_offsets[k + 1]) are table rows first_row[k] .. first_row[k] + n_k - 1 (first_row is a HOST
+ * array in both, >= 0). Table row r belongs to parameter r * delta[k], never to an accumulated
+ * parameter, so the rows are bit-equal to the same rows of a whole-path sampling: the targets of
+ * a streamed IK table (tpamd_planner_set_append_ik_rows*) do not depend on the chunking. */
+int tpamd_sample_ik_target_rows_host(tpamd_engine *engine, int num_paths, int num_dofs,
+                                     const int32_t *num_points, const int32_t *row_offsets,
+                                     const int32_t *first_row, const double *knots,
+                                     const double *translation_points, const double *rotation_points,
+                                     const double *joint_control_points, const double *delta,
+                                     double *pose_targets, double *joint_targets);
+int tpamd_sample_ik_target_rows_device(tpamd_engine *engine, int num_paths, int num_dofs,
+                                       const int32_t *num_points, const int32_t *row_offsets,
+                                       const int32_t *first_row, const double *knots,
+                                       const double *translation_points, const double *rotation_points,
+                                       const double *joint_control_points, const double *delta,
+                                       double *pose_targets, double *joint_targets, void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Receding-horizon planning: the window loop of PathTimingTrajectory::Plan
@@ -373,6 +390,7 @@ int tpamd_sample_ik_targets_device(tpamd_engine *engine, int num_paths, int num_
 #define TPAMD_PLAN_INTERNAL 4            /* solver set-up / optimisation failed (:394-417) */
 #define TPAMD_PLAN_DEADLINE_EXCEEDED 5   /* planning-loop limit (:655-658) */
 #define TPAMD_PLAN_NOT_FOUND 6           /* stopping trajectories: no safe stop (trajectory_buffer.cc:333-349) */
+#define TPAMD_PLAN_NEEDS_ROWS 7          /* Cartesian set, streaming Plan: the next window is not resident yet */
 #define TPAMD_PLAN_MORE 100              /* history_capacity exhausted: call again with more room */
 
 typedef struct tpamd_plan_args {
@@ -595,6 +613,65 @@ int tpamd_planner_set_upload_ik_tables_device(tpamd_planner_set *set, int count,
                                               const double *max_rotational_velocity, const double *delta,
                                               const double *initial_velocity, const int32_t *path_state,
                                               void *hip_stream);
+/* ---- Streaming IK tables: plan, suspend, append ---------------------------------------------
+ * A table need not cover its whole path. TimeableCartesianSplinePath::SamplePath extends
+ * path_ik_positions_ lazily (:464-549): each window asks the IK callback only for the rows between
+ * the table's last row and the window's last row. The streaming entries do the same for a set:
+ *
+ *   upload_ik_tables[_device]   rows 0 .. N-1 (or more) of every path
+ *   plan_streaming              Plan; a planner whose next window is not resident WAITS
+ *   while (num_waiting > 0):
+ *     append_ik_rows[_device]   rows need_first[b] .. need_first[b] + need_count[b] - 1 (or more)
+ *     plan_resume               the waiting planners re-enter the window loop where they stopped
+ *
+ * append_ik_rows: planner ids[k] (each listed once; ids NULL: 0..count-1) gets rows
+ * row_offsets[k] .. row_offsets[k + 1]) of ik_positions [rows][D] / jacobians [rows][6][D] behind
+ * its last resident row; a count of 0 is allowed. Limits, delta, path_end and the path state stay
+ * as they are. The capacity grows by doubling, with a copy, before anything else changes. A joint
+ * set, a NULL array, count < 0 or > B, a bad or repeated id, row_offsets[0] != 0 or decreasing, or
+ * a planner that has no table as far as the host knows fail the call and change nothing. A planner
+ * whose table the kernel rejected at a _device upload is left untouched by the kernel (the
+ * destination row is the device's own row count; for such a planner
+ * tpamd_planner_set_download_ik_table keeps reporting what the host was handed, as after the
+ * rejected upload itself). Host pointers; synchronises. */
+int tpamd_planner_set_append_ik_rows(tpamd_planner_set *set, int count, const int32_t *ids,
+                                     const int32_t *row_offsets, const double *ik_positions,
+                                     const double *jacobians);
+/* The same with ik_positions and jacobians device pointers; ids and row_offsets stay HOST arrays.
+ * Enqueues on hip_stream and does not synchronise, except when the capacity grows or the previous
+ * call's staging is still in use. Stream ordering as for tpamd_planner_set_upload_ik_tables_device:
+ * the next Plan / resume (null stream) waits for it. */
+int tpamd_planner_set_append_ik_rows_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                            const int32_t *row_offsets, const double *ik_positions,
+                                            const double *jacobians, void *hip_stream);
+/* tpamd_planner_set_plan with suspension (Cartesian sets only; TPAMD_E_INVALID_ARGUMENT on a joint
+ * set). A planner whose next window is well formed but reaches past its table's last row does not
+ * fail: its summary record carries TPAMD_PLAN_NEEDS_ROWS and the windows solved so far, its
+ * trajectory, end time and final deceleration start stay as the call's prologue and its finished
+ * windows left them, and need_first[b] / need_count[b] name the rows it lacks (need_first is the
+ * table's row count; after the append the table has need_first + need_count rows, the size
+ * SamplePath leaves it with). The other planners are not held up. need_first / need_count [B]
+ * (host, may be NULL) are 0 / 0 for planners that do not wait; *num_waiting (may be NULL) counts
+ * those that do. A window that no table can hold still gives TPAMD_PLAN_INTERNAL. Down: what
+ * tpamd_planner_set_plan moves plus 8 bytes per planner. */
+int tpamd_planner_set_plan_streaming(tpamd_planner_set *set, const int64_t *start_ns,
+                                     const int64_t *horizon_ns, tpamd_planner_summary *summary,
+                                     int32_t *need_first, int32_t *need_count, int32_t *num_waiting);
+/* Re-enters the window loop for the planners that wait. Legal only while planners wait (otherwise
+ * TPAMD_E_INVALID_ARGUMENT, nothing changes). A waiting planner whose table now holds its window
+ * goes on with the loop state of the suspending call -- its start and horizon arguments, the loop's
+ * start time, the windows and iterations counted so far (max_planning_iterations counts across
+ * suspensions) -- and, when it finishes, reports what an uninterrupted Plan would report; it may
+ * wait again at a later window. One still short of rows keeps waiting with a fresh need. Summary
+ * records of planners that were not waiting repeat the previous call's. Nothing goes up.
+ *
+ * Dropping a suspension: any other tpamd_planner_set_plan / _plan_streaming, an upload_ik_tables*
+ * that lists the planner, or tpamd_planner_set_reset drop it without error. The planner is then in
+ * the state of a reference planner whose Plan returned an error in that window: the windows it
+ * finished are in its history, its trajectory is cut at the Plan's start time. (This describes the
+ * state; the reference has no suspension to compare with.) */
+int tpamd_planner_set_plan_resume(tpamd_planner_set *set, tpamd_planner_summary *summary,
+                                  int32_t *need_first, int32_t *need_count, int32_t *num_waiting);
 /* The resident table of one planner: *rows (0: no table) and, if the arrays are not NULL,
  * ik_positions [rows][D] and jacobians [rows][6][D]. `capacity` is the number of rows the arrays
  * can hold; a longer table gives TPAMD_E_INVALID_ARGUMENT (*rows is still written). */

@@ -1707,17 +1707,22 @@ int tpamd_fit_pose_waypoints_host(tpamd_engine *e, int num_paths, int num_dofs, 
   return rc ? rc : s.download(st);
 }
 
-int tpamd_sample_ik_targets_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
-                                   const int32_t *row_offsets, const double *knots,
-                                   const double *translation_points, const double *rotation_points,
-                                   const double *joint_control_points, const double *delta, double *pose_targets,
-                                   double *joint_targets, void *hip_stream) {
+// first_row (host, may be null: 0): path k's rows are first_row[k] .. first_row[k] + n_k - 1 of its table
+static int sample_ik_targets_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                    const int32_t *row_offsets, const int32_t *first_row, const double *knots,
+                                    const double *translation_points, const double *rotation_points,
+                                    const double *joint_control_points, const double *delta, double *pose_targets,
+                                    double *joint_targets, void *hip_stream) {
   PosePacking pk;
   int max_rows = 0;
   if (int rc = ik_target_args(e, num_paths, num_dofs, num_points, row_offsets, knots, translation_points,
                               rotation_points, joint_control_points, delta, pose_targets, joint_targets, &pk,
                               &max_rows))
     return rc;
+  if (first_row)
+    for (int k = 0; k < num_paths; k++)
+      if (first_row[k] < 0 || (long long)first_row[k] + (row_offsets[k + 1] - row_offsets[k]) > (1LL << 30))
+        return TPAMD_E_INVALID_ARGUMENT;
   if (num_paths == 0 || max_rows == 0) return 0;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = (hipStream_t)hip_stream;
@@ -1727,21 +1732,43 @@ int tpamd_sample_ik_targets_device(tpamd_engine *e, int num_paths, int num_dofs,
   ints.insert(ints.end(), pk.point.begin(), pk.point.end());
   ints.insert(ints.end(), pk.knot.begin(), pk.knot.end());
   ints.insert(ints.end(), row_offsets, row_offsets + n + 1);
+  if (first_row) ints.insert(ints.end(), first_row, first_row + n);
   const int32_t *d = nullptr;
   if (int rc = stage_pose_ints(e, ints, st, &d)) return rc;
   IkTargetParams p{};
   p.Q = num_paths; p.D = num_dofs;
   p.num_points = d; p.point_offsets = d + (n + 1); p.knot_offsets = d + 2 * (n + 1); p.row_offsets = d + 3 * (n + 1);
+  p.first_row = first_row ? d + 4 * (n + 1) : nullptr;
   p.knots = knots; p.trans = translation_points; p.rot = rotation_points; p.joint_cp = joint_control_points;
   p.delta = delta; p.pose_targets = pose_targets; p.joint_targets = joint_targets;
   launch_sample_ik_targets(p, max_rows, st);
   return pose_ints_done(e, st);
 }
 
-int tpamd_sample_ik_targets_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
-                                 const int32_t *row_offsets, const double *knots, const double *translation_points,
-                                 const double *rotation_points, const double *joint_control_points,
-                                 const double *delta, double *pose_targets, double *joint_targets) {
+int tpamd_sample_ik_targets_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                   const int32_t *row_offsets, const double *knots,
+                                   const double *translation_points, const double *rotation_points,
+                                   const double *joint_control_points, const double *delta, double *pose_targets,
+                                   double *joint_targets, void *hip_stream) {
+  return sample_ik_targets_device(e, num_paths, num_dofs, num_points, row_offsets, nullptr, knots, translation_points,
+                                  rotation_points, joint_control_points, delta, pose_targets, joint_targets, hip_stream);
+}
+
+int tpamd_sample_ik_target_rows_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                       const int32_t *row_offsets, const int32_t *first_row, const double *knots,
+                                       const double *translation_points, const double *rotation_points,
+                                       const double *joint_control_points, const double *delta, double *pose_targets,
+                                       double *joint_targets, void *hip_stream) {
+  if (!first_row) return TPAMD_E_INVALID_ARGUMENT;
+  return sample_ik_targets_device(e, num_paths, num_dofs, num_points, row_offsets, first_row, knots, translation_points,
+                                  rotation_points, joint_control_points, delta, pose_targets, joint_targets, hip_stream);
+}
+
+static int sample_ik_targets_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                  const int32_t *row_offsets, const int32_t *first_row, const double *knots,
+                                  const double *translation_points, const double *rotation_points,
+                                  const double *joint_control_points, const double *delta, double *pose_targets,
+                                  double *joint_targets) {
   PosePacking pk;
   int max_rows = 0;
   if (int rc = ik_target_args(e, num_paths, num_dofs, num_points, row_offsets, knots, translation_points,
@@ -1765,9 +1792,27 @@ int tpamd_sample_ik_targets_host(tpamd_engine *e, int num_paths, int num_dofs, c
   s.down(&d_pose, pose_targets, rows * 7);
   s.down(&d_joint, joint_targets, rows * D);
   if (int rc = s.upload(e->stage, st)) return rc;
-  int rc = tpamd_sample_ik_targets_device(e, num_paths, num_dofs, num_points, row_offsets, d_k, d_t, d_r, d_j, d_dl,
-                                          d_pose, d_joint, st);
+  int rc = sample_ik_targets_device(e, num_paths, num_dofs, num_points, row_offsets, first_row, d_k, d_t, d_r, d_j,
+                                    d_dl, d_pose, d_joint, st);
   return rc ? rc : s.download(st);
+}
+
+int tpamd_sample_ik_targets_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                 const int32_t *row_offsets, const double *knots, const double *translation_points,
+                                 const double *rotation_points, const double *joint_control_points,
+                                 const double *delta, double *pose_targets, double *joint_targets) {
+  return sample_ik_targets_host(e, num_paths, num_dofs, num_points, row_offsets, nullptr, knots, translation_points,
+                                rotation_points, joint_control_points, delta, pose_targets, joint_targets);
+}
+
+int tpamd_sample_ik_target_rows_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *num_points,
+                                     const int32_t *row_offsets, const int32_t *first_row, const double *knots,
+                                     const double *translation_points, const double *rotation_points,
+                                     const double *joint_control_points, const double *delta, double *pose_targets,
+                                     double *joint_targets) {
+  if (!first_row) return TPAMD_E_INVALID_ARGUMENT;
+  return sample_ik_targets_host(e, num_paths, num_dofs, num_points, row_offsets, first_row, knots, translation_points,
+                                rotation_points, joint_control_points, delta, pose_targets, joint_targets);
 }
 
 int tpamd_optimize_rows_host(tpamd_engine *e, const tpamd_rows_batch *bt,
@@ -2211,6 +2256,13 @@ struct tpamd_planner_set {
   std::vector<int> h_rows;
   double *d_vtrans = nullptr, *d_vrot = nullptr, *d_path_end = nullptr;
   int *d_rows = nullptr, *d_first = nullptr;
+  // streaming Plan: the planners that wait for rows (device flags and host copy), what they lack
+  // ([need_first[B]][need_count[B]], one copy down per call) and whether P carries the arrays
+  int *d_suspended = nullptr, *d_need = nullptr;
+  std::vector<char> h_wait;
+  std::vector<int32_t> h_need;
+  int num_waiting = 0;
+  bool streaming = false;
 };
 
 namespace {
@@ -2260,6 +2312,9 @@ void refresh_plan_params(tpamd_planner_set *ps) {
   p.rows = ps->cartesian ? ps->d_rows : nullptr;
   p.first = ps->d_first;
   p.rec_stride = 0;
+  p.suspended = ps->streaming ? ps->d_suspended : nullptr;
+  p.need_first = ps->streaming ? ps->d_need : nullptr;
+  p.need_count = ps->streaming ? ps->d_need + S.B : nullptr;
   p.B = S.B; p.N = S.N; p.D = S.D; p.K = S.K; p.cap = ps->cap; p.np = S.np;
   p.max_iterations = ps->cfg.max_planning_iterations;
   p.max_initial_velocity_error = ps->cfg.max_initial_velocity_error;
@@ -2368,6 +2423,15 @@ int largest_points(const tpamd_planner_set *ps) {
   int m = 3;
   for (int v : ps->h_np) m = std::max(m, v);
   return m;
+}
+
+// A planner that waits for rows (streaming Plan) stops waiting: its table is replaced or it is reset.
+int drop_suspension(tpamd_planner_set *ps, int b, hipStream_t st) {
+  if (!ps->num_waiting || !ps->h_wait[b]) return 0;
+  HIPCHK(hipMemsetAsync(ps->d_suspended + b, 0, 4, st));
+  ps->h_wait[b] = 0;
+  ps->num_waiting--;
+  return 0;
 }
 
 // Called by every call that changes planner state, before its first copy or launch (all of them
@@ -2545,6 +2609,8 @@ int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, 
   ps->h_has.assign(B, 0);
   ps->cartesian = cartesian;
   ps->h_rows.assign(B, 0);
+  ps->h_wait.assign(B, 0);
+  ps->h_need.assign(2 * B, 0);
   PlannerSetState &S = ps->S;
   for (int pass = 0; pass < 2; pass++) {
     Stage s(pass ? ps->fixed : nullptr);
@@ -2572,6 +2638,7 @@ int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, 
     if (cartesian) {
       ps->d_vtrans = s.take<double>(B); ps->d_vrot = s.take<double>(B); ps->d_path_end = s.take<double>(B);
       ps->d_rows = s.take<int>(B); ps->d_first = s.take<int>(B);
+      ps->d_suspended = s.take<int>(B); ps->d_need = s.take<int>(2 * B);
     }
     if (!pass) {
       ps->fixed_bytes = s.off;
@@ -2722,15 +2789,21 @@ int tpamd_planner_set_reset(tpamd_planner_set *ps, int count, const int32_t *ids
     for (long long *a : {S.start_time_ns, S.end_time_ns, S.final_decel_start_ns})
       HIPCHK(hipMemsetAsync(a + b, 0, 8, nullptr));
     HIPCHK(hipMemcpyAsync(S.planned_to_end + b, &one, 4, hipMemcpyHostToDevice, nullptr));
+    if (drop_suspension(ps, (int)b, nullptr)) return TPAMD_E_HIP;
   }
   HIPCHK(hipStreamSynchronize(nullptr));
   for (int k = 0; k < n; k++) ps->h_has[ids ? (size_t)ids[k] : (size_t)k] = 0;
   return 0;
 }
 
-int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const int64_t *horizon_ns,
-                           tpamd_planner_summary *summary) {
-  if (!ps || !start_ns || !horizon_ns) return TPAMD_E_INVALID_ARGUMENT;
+// Plan for every planner of a set. kPlanFresh is tpamd_planner_set_plan; kPlanStreaming is the same
+// with the streaming arrays set (a planner whose window is not resident waits); kPlanResume
+// re-enters the window loop for the planners that waited (k_pset_resume in place of the prologue,
+// nothing goes up). A fresh or streaming Plan drops every suspension left from an earlier call.
+enum PlanKind { kPlanFresh, kPlanStreaming, kPlanResume };
+static int planner_set_plan_run(tpamd_planner_set *ps, PlanKind kind, const int64_t *start_ns, const int64_t *horizon_ns,
+                                tpamd_planner_summary *summary, int32_t *need_first, int32_t *need_count,
+                                int32_t *num_waiting) {
   static_assert(sizeof(tpamd_planner_summary) == sizeof(PlannerSummaryDev), "summary layouts must agree");
   tpamd_engine *e = ps->e;
   TPAMD_ON_DEVICE(e);
@@ -2740,15 +2813,28 @@ int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const
   hipStream_t st = nullptr;
   if (order_after_readouts(ps)) return TPAMD_E_HIP;
   ps->last_h2d = ps->last_d2h = 0;
-  HIPCHK(hipMemcpyAsync(ps->d_start, start_ns, B * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ps->d_horizon, horizon_ns, B * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ps->d_loop_start, start_ns, B * 8, hipMemcpyHostToDevice, st));   // :630
-  ps->last_h2d += 3 * B * 8;
-  for (int *z : {ps->P.old_state, ps->P.offset, ps->P.loop, ps->P.append, ps->d_windows})
-    HIPCHK(hipMemsetAsync(z, 0, B * 4, st));
-  HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
   const unsigned gb = (unsigned)((B + 127) / 128);
-  hipLaunchKernelGGL(k_pset_prologue, dim3(gb), dim3(128), 0, st, S);
+  ps->streaming = kind != kPlanFresh;
+  refresh_plan_params(ps);
+  if (kind == kPlanResume) {
+    HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
+    hipLaunchKernelGGL(k_pset_resume, dim3(gb), dim3(128), 0, st, S, ps->P);
+  } else {
+    if (ps->num_waiting || kind == kPlanStreaming) {
+      HIPCHK(hipMemsetAsync(ps->d_suspended, 0, B * 4, st));
+      HIPCHK(hipMemsetAsync(ps->d_need, 0, 2 * B * 4, st));
+      std::fill(ps->h_wait.begin(), ps->h_wait.end(), 0);
+      ps->num_waiting = 0;
+    }
+    HIPCHK(hipMemcpyAsync(ps->d_start, start_ns, B * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->d_horizon, horizon_ns, B * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps->d_loop_start, start_ns, B * 8, hipMemcpyHostToDevice, st));   // :630
+    ps->last_h2d += 3 * B * 8;
+    for (int *z : {ps->P.old_state, ps->P.offset, ps->P.loop, ps->P.append, ps->d_windows})
+      HIPCHK(hipMemsetAsync(z, 0, B * 4, st));
+    HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
+    hipLaunchKernelGGL(k_pset_prologue, dim3(gb), dim3(128), 0, st, S);
+  }
   hipLaunchKernelGGL(k_pset_check_capacity, dim3(gb), dim3(128), 0, st, S);
   int na[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(na, S.num_active, 8, hipMemcpyDeviceToHost, st));
@@ -2820,8 +2906,41 @@ int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const
     HIPCHK(hipMemcpyAsync(summary, ps->d_summary, B * sizeof(PlannerSummaryDev), hipMemcpyDeviceToHost, st));
     ps->last_d2h += B * sizeof(PlannerSummaryDev);
   }
+  if (kind != kPlanFresh) {
+    HIPCHK(hipMemcpyAsync(ps->h_need.data(), ps->d_need, 2 * B * 4, hipMemcpyDeviceToHost, st));
+    ps->last_d2h += 2 * B * 4;
+  }
   HIPCHK(hipStreamSynchronize(st));
+  if (kind != kPlanFresh) {
+    ps->num_waiting = 0;
+    for (size_t b = 0; b < B; b++) {
+      ps->h_wait[b] = ps->h_need[B + b] > 0;
+      ps->num_waiting += ps->h_wait[b];
+    }
+    if (need_first) std::memcpy(need_first, ps->h_need.data(), B * 4);
+    if (need_count) std::memcpy(need_count, ps->h_need.data() + B, B * 4);
+    if (num_waiting) *num_waiting = ps->num_waiting;
+  }
   return 0;
+}
+
+int tpamd_planner_set_plan(tpamd_planner_set *ps, const int64_t *start_ns, const int64_t *horizon_ns,
+                           tpamd_planner_summary *summary) {
+  if (!ps || !start_ns || !horizon_ns) return TPAMD_E_INVALID_ARGUMENT;
+  return planner_set_plan_run(ps, kPlanFresh, start_ns, horizon_ns, summary, nullptr, nullptr, nullptr);
+}
+
+int tpamd_planner_set_plan_streaming(tpamd_planner_set *ps, const int64_t *start_ns, const int64_t *horizon_ns,
+                                     tpamd_planner_summary *summary, int32_t *need_first, int32_t *need_count,
+                                     int32_t *num_waiting) {
+  if (!ps || !ps->cartesian || !start_ns || !horizon_ns) return TPAMD_E_INVALID_ARGUMENT;
+  return planner_set_plan_run(ps, kPlanStreaming, start_ns, horizon_ns, summary, need_first, need_count, num_waiting);
+}
+
+int tpamd_planner_set_plan_resume(tpamd_planner_set *ps, tpamd_planner_summary *summary, int32_t *need_first,
+                                  int32_t *need_count, int32_t *num_waiting) {
+  if (!ps || !ps->cartesian || ps->num_waiting == 0) return TPAMD_E_INVALID_ARGUMENT;
+  return planner_set_plan_run(ps, kPlanResume, nullptr, nullptr, summary, need_first, need_count, num_waiting);
 }
 
 int tpamd_planner_set_download_trajectory(tpamd_planner_set *ps, int planner, int first, int count, double *time,
@@ -3004,9 +3123,11 @@ int ensure_wp_buf(tpamd_planner_set *ps, size_t bytes) {
 // 256-byte boundary. The previous call's copy out of the staging has to be done first; the copy is
 // ordered like a device readout (readout_begin), and ev_wp guards the staging against the next
 // call. The caller ends with readout_end(ps, st).
+// `extra` (may be null): n more ints behind the offsets (an append's destination rows).
 int stage_ids_and_offsets(tpamd_planner_set *ps, const std::vector<int32_t> &id, const int32_t *offsets, hipStream_t st,
-                          const int **d_ids, const int **d_offsets) {
-  const size_t n = id.size(), bytes = align_up(n * 4, 256) + (n + 1) * 4;
+                          const int **d_ids, const int **d_offsets, const std::vector<int32_t> *extra = nullptr,
+                          const int **d_extra = nullptr) {
+  const size_t n = id.size(), bytes = align_up(n * 4, 256) + (n + 1) * 4 + (extra ? n * 4 : 0);
   if (ps->wp_pin_busy) {
     HIPCHK(hipEventSynchronize(ps->ev_wp));
     ps->wp_pin_busy = false;
@@ -3021,12 +3142,14 @@ int stage_ids_and_offsets(tpamd_planner_set *ps, const std::vector<int32_t> &id,
   char *pin = (char *)ps->wp_pin, *base = (char *)ps->wp_buf.p;
   std::memcpy(pin, id.data(), n * 4);
   std::memcpy(pin + align_up(n * 4, 256), offsets, (n + 1) * 4);
+  if (extra) std::memcpy(pin + align_up(n * 4, 256) + (n + 1) * 4, extra->data(), n * 4);
   if (readout_begin(ps, st)) return TPAMD_E_HIP;
   HIPCHK(hipMemcpyAsync(base, pin, bytes, hipMemcpyHostToDevice, st));
   HIPCHK(hipEventRecord(ps->ev_wp, st));
   ps->wp_pin_busy = true;
   *d_ids = (const int *)base;
   *d_offsets = (const int *)(base + align_up(n * 4, 256));
+  if (extra) *d_extra = (const int *)(base + align_up(n * 4, 256) + (n + 1) * 4);
   return 0;
 }
 
@@ -3227,6 +3350,8 @@ int tpamd_planner_set_upload_ik_tables(tpamd_planner_set *ps, int count, const i
   if (rc) return rc;
   if (s.upload(ps->wp_buf.p, st)) return TPAMD_E_HIP;
   p.count = count;
+  for (int32_t b : id)
+    if (drop_suspension(ps, b, st)) return TPAMD_E_HIP;
   launch_ik_upload(ps, p, longest, st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
@@ -3266,9 +3391,125 @@ int tpamd_planner_set_upload_ik_tables_device(tpamd_planner_set *ps, int count, 
   p.q = ik_positions; p.J = jacobians; p.path_end = path_end; p.vmax = max_velocity; p.amax = max_acceleration;
   p.vtrans = max_translational_velocity; p.vrot = max_rotational_velocity; p.delta = delta; p.iv = initial_velocity;
   p.state = path_state;
+  for (int32_t b : id)
+    if (drop_suspension(ps, b, st)) return TPAMD_E_HIP;
   launch_ik_upload(ps, p, longest, st);
   HIPCHK(hipGetLastError());
   ik_bookkeeping(ps, count, id, row_offsets);
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The call-level checks of the two append_ik_rows entries (before anything changes): a Cartesian
+// set, the arrays, every id in range, listed once and with a table as far as the host knows,
+// offsets from 0 and non-decreasing. Fills id[count], dst[count] (each planner's first new row),
+// *longest (the largest count) and *need (the rows the longest table has after the append).
+int ik_append_args(const tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *offsets, const double *q,
+                   const double *J, std::vector<int32_t> *id, std::vector<int32_t> *dst, int *longest, int *need) {
+  if (!ps || !ps->cartesian || count < 0 || !offsets || !q || !J) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = ps->S.B;
+  if ((size_t)count > B || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<char> seen(B, 0);
+  id->resize(count);
+  dst->resize(count);
+  long long most = 0, rows_after = 0;
+  for (int k = 0; k < count; k++) {
+    const long long b = ids ? (long long)ids[k] : (long long)k;
+    if (b < 0 || b >= (long long)B || seen[b]) return TPAMD_E_INVALID_ARGUMENT;
+    seen[b] = 1;
+    if (!ps->h_has[b] || ps->h_rows[b] < 1) return TPAMD_E_INVALID_ARGUMENT;
+    const long long rows = (long long)offsets[k + 1] - offsets[k];
+    if (rows < 0) return TPAMD_E_INVALID_ARGUMENT;
+    (*id)[k] = (int32_t)b;
+    (*dst)[k] = ps->h_rows[b];
+    most = std::max(most, rows);
+    rows_after = std::max(rows_after, (long long)ps->h_rows[b] + rows);
+  }
+  if (rows_after > (1 << 28)) return TPAMD_E_UNSUPPORTED;
+  *longest = (int)most;
+  *need = (int)rows_after;
+  return 0;
+}
+
+// The scatter of the packed rows (device pointers in p) behind the planners' last rows.
+void launch_ik_append(const tpamd_planner_set *ps, IkUploadParams p, int longest, hipStream_t st) {
+  const int D = ps->S.D;
+  p.D = D; p.table_stride = ps->table_cap;
+  p.t_q = ps->d_tq; p.t_J = ps->d_tJ;
+  p.s_rows = ps->d_rows; p.s_has = ps->S.has_path;
+  const unsigned n = (unsigned)p.count;
+  if (longest > 0) {
+    hipLaunchKernelGGL(k_pset_ik_rows, dim3((unsigned)(((size_t)longest * D + 255) / 256), n), dim3(256), 0, st, p, D,
+                       p.q, p.t_q);
+    hipLaunchKernelGGL(k_pset_ik_rows, dim3((unsigned)(((size_t)longest * 6 * D + 255) / 256), n), dim3(256), 0, st, p,
+                       6 * D, p.J, p.t_J);
+  }
+  hipLaunchKernelGGL(k_pset_ik_append_scalars, dim3((n + 127) / 128), dim3(128), 0, st, p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_planner_set_append_ik_rows(tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *row_offsets,
+                                     const double *ik_positions, const double *jacobians) {
+  std::vector<int32_t> id, dst;
+  int longest = 0, need = 0;
+  int rc = ik_append_args(ps, count, ids, row_offsets, ik_positions, jacobians, &id, &dst, &longest, &need);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)count, D = ps->S.D, rows = (size_t)row_offsets[count];
+  // device buffer: [ids][offsets][dst_first][q][J]
+  IkUploadParams p{};
+  HostStage s;
+  s.up(&p.ids, id.data(), n);
+  s.up(&p.offsets, row_offsets, n + 1);
+  s.up(&p.dst_first, dst.data(), n);
+  s.up(&p.q, ik_positions, rows * D);
+  s.up(&p.J, jacobians, rows * 6 * D);
+  if (ensure_wp_buf(ps, s.bytes())) return TPAMD_E_HIP;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  rc = ensure_table_cap(ps, need, st);
+  if (rc) return rc;
+  if (s.upload(ps->wp_buf.p, st)) return TPAMD_E_HIP;
+  p.count = count;
+  launch_ik_append(ps, p, longest, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  if (ps->wp_buf.bytes > kIkStagingKept) ps->wp_buf.release();
+  for (int k = 0; k < count; k++) ps->h_rows[id[k]] += row_offsets[k + 1] - row_offsets[k];
+  return 0;
+}
+
+int tpamd_planner_set_append_ik_rows_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                            const int32_t *row_offsets, const double *ik_positions,
+                                            const double *jacobians, void *hip_stream) {
+  std::vector<int32_t> id, dst;
+  int longest = 0, need = 0;
+  int rc = ik_append_args(ps, count, ids, row_offsets, ik_positions, jacobians, &id, &dst, &longest, &need);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t n = (size_t)count, bytes = align_up(n * 4, 256) + (n + 1) * 4 + n * 4;
+  if (ensure_wp_buf(ps, bytes)) return TPAMD_E_HIP;
+  if (need > ps->table_cap) {      // the growth runs on the null stream, after the device calls in flight
+    if (order_after_readouts(ps)) return TPAMD_E_HIP;
+    rc = ensure_table_cap(ps, need, nullptr);
+    if (rc) return rc;
+  }
+  IkUploadParams p{};
+  p.count = count;
+  if (stage_ids_and_offsets(ps, id, row_offsets, st, &p.ids, &p.offsets, &dst, &p.dst_first)) return TPAMD_E_HIP;
+  p.q = ik_positions; p.J = jacobians;
+  launch_ik_append(ps, p, longest, st);
+  HIPCHK(hipGetLastError());
+  for (int k = 0; k < count; k++) ps->h_rows[id[k]] += row_offsets[k + 1] - row_offsets[k];
   return readout_end(ps, st) ? TPAMD_E_HIP : 0;
 }
 

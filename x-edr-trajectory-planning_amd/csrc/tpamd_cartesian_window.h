@@ -4,6 +4,7 @@
 // delta_parameter (timeable_path_cartesian_spline.cc:464-549, PathIkIndex = round(parameter /
 // delta) :671-674). A window is arithmetic on N consecutive rows of that table:
 //   cw_window     which rows (SamplePath :527-542), and whether the table holds them
+//   cw_window_need  the same, and which rows a growing table still lacks (streaming Plan)
 //   cw_rows_at    ComputePathDerivatives :39-68 (forward differences, q'[N-1] = 0, q''[0] =
 //                 q''[N-1] = 0) and ConstraintSetup :551-595 (the 2D joint rows plus two rows
 //                 bounding |(J q')_{1..3}|^2 and |(J q')_{4..6}|^2 with lower = -upper; J q' is
@@ -36,6 +37,27 @@ TPAMD_HD inline bool cw_window(double path_start, double path_horizon, double de
   *first = f;
   *last = l;
   return !(f < 0 || l - f != N - 1 || l >= rows);
+}
+
+// cw_window with a three-way answer, for tables that grow as SamplePath grows path_ik_positions_
+// (:464-549: each call appends the rows between the table's last row and the window's last row).
+//   kCwResident   as cw_window's true
+//   kCwMalformed  as cw_window's false for a window no table can hold: delta not positive,
+//                 first < 0 or last - first != N - 1
+//   kCwNeedsRows  a well-formed window with last >= rows: rows need_first = rows .. need_first +
+//                 need_count - 1 = last are missing; once they are appended the table has last + 1
+//                 rows, the size SamplePath leaves it with (:516-517)
+// need_first / need_count are 0 unless rows are needed.
+enum { kCwResident = 0, kCwNeedsRows = 1, kCwMalformed = 2 };
+TPAMD_HD inline int cw_window_need(double path_start, double path_horizon, double delta, int N, int rows, int *first,
+                                   int *last, int *need_first, int *need_count) {
+  *need_first = *need_count = 0;
+  if (cw_window(path_start, path_horizon, delta, N, rows, first, last)) return kCwResident;
+  if (!(delta > 0.0)) return kCwMalformed;
+  if (*first < 0 || *last - *first != N - 1) return kCwMalformed;
+  *need_first = rows;
+  *need_count = *last + 1 - rows;
+  return kCwNeedsRows;
 }
 
 // Sample i of a window of N: q points at the sample's table row ([.][D], the next two rows are read

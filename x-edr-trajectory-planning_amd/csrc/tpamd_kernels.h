@@ -1594,9 +1594,13 @@ struct PlanParams {
   const int *rows;                 // [B]
   int *first;                      // [B]
   int rec_stride;                  // doubles per sample record of the solve; 0: 2D + 2
+  // streaming Plan of a Cartesian set (null otherwise: a window that is not resident is an error):
+  // a planner whose window the table does not hold yet waits for rows need_first .. + need_count - 1
+  int *suspended;                  // [B]
+  int *need_first, *need_count;    // [B]
 };
 enum { kPlanOk = 0, kPlanFailedPrecondition = 1, kPlanOutOfRange = 2, kPlanInvalidArgument = 3,
-       kPlanInternal = 4, kPlanDeadlineExceeded = 5 };
+       kPlanInternal = 4, kPlanDeadlineExceeded = 5, kPlanNeedsRows = 7 };
 
 // where the next window starts (path_timing_trajectory.cc:318-341)
 static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
@@ -1634,6 +1638,18 @@ static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
     // segment of the IK table; a table that does not hold it fails this planner alone
     int first, last;
     if (!cw_window(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last)) {
+      int need_first, need_count;
+      if (p.suspended && cw_window_need(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last,
+                                        &need_first, &need_count) == kCwNeedsRows) {
+        // streaming: the planner waits for its rows. Everything written so far is recomputed from
+        // the unchanged history when the loop is re-entered; the path state is not touched.
+        p.status[b] = kPlanNeedsRows;
+        p.suspended[b] = 1;
+        p.need_first[b] = need_first;
+        p.need_count[b] = need_count;
+        p.active[b] = 0;
+        return;
+      }
       p.status[b] = kPlanInternal;
       p.active[b] = 0;
       return;

@@ -9,6 +9,9 @@
 //   k_pset_prologue  HandleTimeArguments :502-538, UpdatePathTrackingStatus :477-500, the
 //                    "already planned enough" branch with EraseTrajectoryBefore :540-577, and the
 //                    truncation at GetTimeOffsetAfter :289-305 / :604-621
+//   k_pset_resume    in place of the prologue when a streaming Plan of a Cartesian set is resumed
+//                    (tpamd_planner_set_plan_resume): the planners that waited for IK rows re-enter
+//                    the window loop with the loop state they had
 //   window loop      k_plan_begin / set-up / K1 / k_plan_project / sweep / k_plan_end /
 //                    k_plan_append (tpamd_kernels.h), as in tpamd_plan_joint_windows_host
 //   resample         k_resample / k_resample_skip over the histories (:755-836)
@@ -181,6 +184,37 @@ static __global__ void k_pset_prologue(PlannerSetState S) {
   }
 }
 
+// A resume of a streaming Plan (tpamd_planner_set_plan_resume) runs this in place of the prologue.
+// A planner that waited and whose table now holds its window re-enters the window loop: loop,
+// windows, loop_start_ns, start_sec and the start_ns / horizon_ns of the suspending call are kept,
+// so k_plan_begin recomputes the same window from the unchanged history and the
+// max_planning_iterations deadline counts across suspensions. A planner still short of rows keeps
+// waiting with a fresh need. Every other planner takes no part: neither the resample nor the
+// epilogue touches its trajectory again.
+static __global__ void k_pset_resume(PlannerSetState S, PlanParams p) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  S.active[b] = 0;
+  S.finish[b] = 0;
+  S.resample_skip[b] = 1;
+  p.need_first[b] = 0;
+  p.need_count[b] = 0;
+  if (!p.suspended[b]) return;
+  int first, last, need_first, need_count;
+  if (cw_window_need(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last, &need_first,
+                     &need_count) == kCwNeedsRows) {
+    p.need_first[b] = need_first;
+    p.need_count[b] = need_count;
+    return;
+  }
+  p.suspended[b] = 0;
+  S.status[b] = kPlanOk;
+  S.active[b] = 1;
+  S.finish[b] = 1;
+  S.resample_skip[b] = 0;
+  atomicAdd(S.num_active, 1);
+}
+
 // "does every looping planner's history have room for one more window?" (count + N <= cap)
 static __global__ void k_pset_check_capacity(PlannerSetState S) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -256,15 +290,40 @@ struct IkUploadParams {
   double *t_q, *t_J;
   double *s_path_end, *s_vmax, *s_amax, *s_vtrans, *s_vrot, *s_delta, *s_iv;
   int *s_rows, *s_state, *s_has;
+  // append (tpamd_planner_set_append_ik_rows*): not null, and the planner's rows go behind its last
+  // resident row as the DEVICE counts it (s_rows); dst_first[k] is the host's count, the same number
+  // for every planner the kernels accept. null: an upload, rows 0..
+  const int *dst_first;                 // [count]
 };
 
-// rows of `width` doubles; grid = (ceil(longest table * width / 256), count)
+// rows of `width` doubles; grid = (ceil(longest table * width / 256), count). An append leaves a
+// planner without a path (its table was rejected at the upload) untouched. A destination row offset
+// moves a planner's run of Jacobians by a multiple of a row, 48 D bytes: for D = 6 that is 288
+// bytes, so the runs k_cartesian_lp<1, 6> reads as double2 stay 16-byte aligned.
 static __global__ void k_pset_ik_rows(IkUploadParams p, int width, const double *src, double *dst) {
   const int k = blockIdx.y;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t n = (size_t)(p.offsets[k + 1] - p.offsets[k]) * width;
   if (e >= n) return;
-  dst[(size_t)p.ids[k] * p.table_stride * width + e] = src[(size_t)p.offsets[k] * width + e];
+  size_t row0 = (size_t)p.ids[k] * p.table_stride;
+  if (p.dst_first) {
+    // the device's own row count is the destination; a planner whose count the host sees differently
+    // (its table was rejected at a _device upload) has no path and is skipped, and nothing is ever
+    // written past the planner's rows
+    const int b = p.ids[k], have = p.s_rows[b];
+    if (!p.s_has[b] || have != p.dst_first[k] || have + (p.offsets[k + 1] - p.offsets[k]) > p.table_stride) return;
+    row0 += (size_t)have;
+  }
+  dst[row0 * width + e] = src[(size_t)p.offsets[k] * width + e];
+}
+
+// an append's row counts; one thread per listed planner. A planner without a table is skipped.
+static __global__ void k_pset_ik_append_scalars(IkUploadParams p) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  const int b = p.ids[k];
+  if (!p.s_has[b] || p.s_rows[b] != p.dst_first[k] || p.s_rows[b] + (p.offsets[k + 1] - p.offsets[k]) > p.table_stride) return;
+  p.s_rows[b] += p.offsets[k + 1] - p.offsets[k];
 }
 
 // limits, delta, initial velocity, state and row count; one thread per listed planner. The _device

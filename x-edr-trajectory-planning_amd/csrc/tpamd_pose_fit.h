@@ -208,6 +208,7 @@ struct IkTargetParams {
   const int *point_offsets;            // [Q + 1]
   const int *knot_offsets;             // [Q + 1]
   const int *row_offsets;              // [Q + 1]
+  const int *first_row;                // [Q] table row of the path's first output row; null: 0
   const double *knots, *trans, *rot, *joint_cp;
   const double *delta;                 // [Q]; a path whose delta is not > 0 is left untouched
   double *pose_targets;                // [rows][7]

@@ -52,7 +52,9 @@ static __global__ void __launch_bounds__(256) k_sample_ik_targets(IkTargetParams
   double *pose = p.pose_targets + ((size_t)r0 + r) * 7;
   double *joint = p.joint_targets + ((size_t)r0 + r) * D;
   const double kend = knots[K - 1];
-  const double parameter = r * delta;
+  // table row first_row[k] + r belongs to (first_row[k] + r) * delta, never to an accumulated
+  // parameter: a row's targets do not depend on which call samples it
+  const double parameter = ((p.first_row ? p.first_row[k] : 0) + r) * delta;
   if (!(parameter < kend - delta) || parameter < knots[0]) {
     // from knots.back() - delta on: the last control pose and joint control point (a first knot
     // above 0 is the caller's error; its rows get the last pose as well rather than garbage)

@@ -228,6 +228,9 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
     "tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
     "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table",
+    "tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
+    "tpamd_planner_set_plan_streaming", "tpamd_planner_set_plan_resume",
+    "tpamd_sample_ik_target_rows_host", "tpamd_sample_ik_target_rows_device",
     "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
     "tpamd_buffer_set_create", "tpamd_buffer_set_destroy", "tpamd_buffer_set_reserve", "tpamd_buffer_set_capacity",
     "tpamd_buffer_set_device_bytes",
@@ -398,6 +401,16 @@ def load_library():
     L.tpamd_planner_set_upload_ik_tables.argtypes = [vp, i] + [vp] * 12
     L.tpamd_planner_set_upload_ik_tables_device.argtypes = [vp, i] + [vp] * 12 + [vp]
     L.tpamd_planner_set_download_ik_table.argtypes = [vp, i, vp, vp, vp, i]
+    for name in ("tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
+                 "tpamd_planner_set_plan_streaming", "tpamd_planner_set_plan_resume",
+                 "tpamd_sample_ik_target_rows_host", "tpamd_sample_ik_target_rows_device"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_append_ik_rows.argtypes = [vp, i] + [vp] * 4
+    L.tpamd_planner_set_append_ik_rows_device.argtypes = [vp, i] + [vp] * 4 + [vp]
+    L.tpamd_planner_set_plan_streaming.argtypes = [vp] + [vp] * 6
+    L.tpamd_planner_set_plan_resume.argtypes = [vp] + [vp] * 4
+    L.tpamd_sample_ik_target_rows_host.argtypes = [vp, i, i] + [vp] * 10
+    L.tpamd_sample_ik_target_rows_device.argtypes = [vp, i, i] + [vp] * 10 + [vp]
     L.tpamd_planner_set_create.argtypes = [vp, C.POINTER(_PlannerSetConfig), C.POINTER(vp)]
     L.tpamd_planner_set_destroy.restype = None
     L.tpamd_planner_set_destroy.argtypes = [vp]
@@ -672,16 +685,19 @@ class Engine:
         out["point_offsets"] = point_offsets
         return out
 
-    def sample_ik_targets(self, fit, delta, row_offsets, stream=None):
+    def sample_ik_targets(self, fit, delta, row_offsets, stream=None, first_row=None):
         """The IK callback's inputs for a ragged batch (tpamd_sample_ik_targets_*): `fit` holds knots,
         translation_points, rotation_points, joint_control_points (packed, as fit_pose_waypoints
         returns them; every path needs at least 3 control points) and point_offsets [B + 1] or
         num_points [B]; row r of path k, rows row_offsets[k]:row_offsets[k + 1], belongs to parameter
-        r * delta[k]. Returns (pose_targets [rows][7], joint_targets [rows][D]) on the side the
-        spline arrays are on."""
+        r * delta[k]. With first_row [B] (host int32; tpamd_sample_ik_target_rows_*) path k's output
+        rows are table rows first_row[k] .. of its path: (first_row[k] + r) * delta[k], bit-equal to
+        the same rows of a whole-path call. Returns (pose_targets [rows][7], joint_targets [rows][D])
+        on the side the spline arrays are on."""
         import torch
         off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
         B = off.shape[0] - 1
+        fr = None if first_row is None else _host(first_row, np.int32, (B,), "first_row")
         if fit.get("point_offsets") is not None:
             npts = np.diff(_host(fit["point_offsets"], np.int32).reshape(-1)).astype(np.int32)
         else:
@@ -700,19 +716,28 @@ class Engine:
                 raise TpamdError("delta has shape %s, expected (%d,)" % (tuple(dl.shape), B))
             pose = torch.zeros((rows, 7), dtype=torch.float64, device=dev)
             joint = torch.zeros((rows, D), dtype=torch.float64, device=dev)
-            _check(self._lib.tpamd_sample_ik_targets_device(
-                self._h, B, D, _ptr(npts), _ptr(off), _ptr(f(fit["knots"], "knots")),
-                _ptr(f(fit["translation_points"], "translation_points")),
-                _ptr(f(fit["rotation_points"], "rotation_points")), _ptr(f(jc, "joint_control_points")), _ptr(dl),
-                _ptr(pose), _ptr(joint), _stream_ptr(stream)), "tpamd_sample_ik_targets_device")
+            splines = (_ptr(f(fit["knots"], "knots")), _ptr(f(fit["translation_points"], "translation_points")),
+                       _ptr(f(fit["rotation_points"], "rotation_points")), _ptr(f(jc, "joint_control_points")), _ptr(dl),
+                       _ptr(pose), _ptr(joint), _stream_ptr(stream))
+            if fr is not None:
+                _check(self._lib.tpamd_sample_ik_target_rows_device(self._h, B, D, _ptr(npts), _ptr(off), _ptr(fr),
+                                                                    *splines), "tpamd_sample_ik_target_rows_device")
+            else:
+                _check(self._lib.tpamd_sample_ik_targets_device(self._h, B, D, _ptr(npts), _ptr(off), *splines),
+                       "tpamd_sample_ik_targets_device")
             return pose, joint
         h = lambda x, what: _host(x, np.float64, what=what)
         dl = _host(np.broadcast_to(_host(delta, np.float64), (B,)), np.float64, (B,), "delta")
         pose, joint = np.zeros((rows, 7)), np.zeros((rows, D))
-        _check(self._lib.tpamd_sample_ik_targets_host(
-            self._h, B, D, _ptr(npts), _ptr(off), _ptr(h(fit["knots"], "knots")),
-            _ptr(h(fit["translation_points"], "translation_points")), _ptr(h(fit["rotation_points"], "rotation_points")),
-            _ptr(h(jc, "joint_control_points")), _ptr(dl), _ptr(pose), _ptr(joint)), "tpamd_sample_ik_targets_host")
+        splines = (_ptr(h(fit["knots"], "knots")), _ptr(h(fit["translation_points"], "translation_points")),
+                   _ptr(h(fit["rotation_points"], "rotation_points")), _ptr(h(jc, "joint_control_points")), _ptr(dl),
+                   _ptr(pose), _ptr(joint))
+        if fr is not None:
+            _check(self._lib.tpamd_sample_ik_target_rows_host(self._h, B, D, _ptr(npts), _ptr(off), _ptr(fr), *splines),
+                   "tpamd_sample_ik_target_rows_host")
+        else:
+            _check(self._lib.tpamd_sample_ik_targets_host(self._h, B, D, _ptr(npts), _ptr(off), *splines),
+                   "tpamd_sample_ik_targets_host")
         return pose, joint
 
     def ik_table_rows(self, path_end, delta, num_samples):
@@ -1121,7 +1146,7 @@ class PlannerSet:
 
     def set_pose_waypoints(self, pose_waypoints, joint_waypoints, offsets, ik, max_velocity, max_acceleration,
                            max_translational_velocity, max_rotational_velocity, delta, translation_rounding=0.05,
-                           rotation_rounding=0.2, initial_velocity=None, ids=None, stream=None):
+                           rotation_rounding=0.2, initial_velocity=None, ids=None, stream=None, streaming=False):
         """New Cartesian goals for the listed planners of a Cartesian set, without the host touching
         per-row data: listed planner k (ids[k], or k) takes rows offsets[k]:offsets[k + 1] of
         pose_waypoints [rows][7] (translation, then quaternion w, x, y, z) and joint_waypoints
@@ -1136,7 +1161,11 @@ class PlannerSet:
         A planner whose fit failed (no waypoints: TPAMD_PLAN_INVALID_ARGUMENT) is left out of steps 3-5
         and keeps its path and plan. Limits and delta as for set_ik_tables ([count][D], [count] or one
         number). Returns (status int32 [count], rows int32 [count]) as CPU tensors; rows is 0 where the
-        fit failed. Raises TpamdError on a joint set, as set_ik_tables does."""
+        fit failed. Raises TpamdError on a joint set, as set_ik_tables does.
+        With streaming=True only rows 0 .. N-1 of every table are sampled, solved and uploaded
+        (`rows` reports N); the fitted splines stay on the device with the set, and plan_streaming
+        extends the tables as the windows reach past them. The listed planners must then be all of
+        the set's (ids None)."""
         import torch
         if not self.cartesian:
             _check(-1, "tpamd_planner_set_upload_ik_tables_device")      # what the entry returns on a joint set
@@ -1166,11 +1195,17 @@ class PlannerSet:
         dl_h = dl.cpu().numpy()
         ok = np.flatnonzero(status == 0)
         rows = np.zeros(n, dtype=np.int32)
+        if streaming and (ida is not None or ok.size != n or n != self.B):
+            raise TpamdError("streaming=True takes a goal for every planner of the set")
         for k in ok:
             r = self._lib.tpamd_ik_table_rows(float(path_end[k]), float(dl_h[k]), self.N)
             if r < 0:
                 raise TpamdError("delta[%d] = %r is not positive" % (k, float(dl_h[k])))
-            rows[k] = r
+            rows[k] = self.N if streaming else r
+        # streaming: the fit stays on the device; the whole-table row counts bound every extension
+        self._stream_fit = dict(fit=fit, delta=dl, full_rows=np.array(
+            [self._lib.tpamd_ik_table_rows(float(path_end[k]), float(dl_h[k]), self.N) for k in range(n)],
+            dtype=np.int64)) if streaming else None
         if ok.size:
             sel = torch.as_tensor(ok, device=dev)
             row_offsets = np.concatenate([[0], np.cumsum(rows[ok])]).astype(np.int32)
@@ -1179,6 +1214,8 @@ class PlannerSet:
                                                                          - fit["point_offsets"][:-1][ok])]))
             pose_t, joint_t = E.sample_ik_targets(sub, dl[sel].contiguous(), row_offsets, stream=stream)
             q, J = ik(pose_t, joint_t, row_offsets)
+            if streaming:      # the last resident row of every table: the seed of its next extension
+                self._stream_last = q[torch.as_tensor(row_offsets[1:].astype(np.int64) - 1, device=dev)].clone()
             all_ids = np.arange(n, dtype=np.int32) if ida is None else ida
             take = lambda x: None if x is None else x[sel].contiguous()
             self.set_ik_tables(q, J, row_offsets, fit["path_end"][sel].contiguous(), take(vm), take(am), take(vt),
@@ -1231,9 +1268,111 @@ class PlannerSet:
         out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
         _check(self._lib.tpamd_planner_set_plan(self._handle(), _ptr(s), _ptr(h), out.ctypes.data),
                "tpamd_planner_set_plan")
+        return self._summary(out)
+
+    def last_plan_bytes(self):
+        """(host to device, device to host) bytes the last plan / plan_streaming / plan_resume moved."""
+        up, down = C.c_size_t(0), C.c_size_t(0)
+        self._lib.tpamd_planner_set_last_plan_bytes(self._handle(), C.byref(up), C.byref(down))
+        return int(up.value), int(down.value)
+
+    def _summary(self, out):
+        import torch
         self._num_samples[:] = out["num_samples"]
         return {name: torch.from_numpy(np.ascontiguousarray(out[name]))
                 for name in PLANNER_SUMMARY_DTYPE.names if name != "reserved"}
+
+    def append_ik_rows(self, ik_positions, jacobians, row_offsets, ids=None, stream=None):
+        """More rows behind the resident IK tables of the listed planners of a Cartesian set
+        (tpamd_planner_set_append_ik_rows*): listed planner k gets rows row_offsets[k]:row_offsets[k + 1]
+        of ik_positions [rows][D] and jacobians [rows][6][D] behind its last row; limits, delta and
+        path state stay. CUDA tensors take the _device entry and only enqueue on `stream`."""
+        import torch
+        off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("row offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        rows, D = (int(off[-1]) if n else 0), self.D
+        if _is_cuda(ik_positions):
+            dev = ik_positions.device
+            q = self._cuda(ik_positions, torch.float64, dev, (rows, D), "ik_positions")
+            J = self._cuda(jacobians, torch.float64, dev, (rows, 6, D), "jacobians")
+            _check(self._lib.tpamd_planner_set_append_ik_rows_device(
+                self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _stream_ptr(stream)),
+                "tpamd_planner_set_append_ik_rows_device")
+            return
+        q = _host(ik_positions, np.float64, (rows, D), "ik_positions")
+        J = _host(jacobians, np.float64, (rows, 6, D), "jacobians")
+        _check(self._lib.tpamd_planner_set_append_ik_rows(self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J)),
+               "tpamd_planner_set_append_ik_rows")
+
+    def _plan_streaming(self, start_ns, horizon_ns):
+        s = _host(np.broadcast_to(_host(start_ns, np.int64), (self.B,)), np.int64)
+        h = _host(np.broadcast_to(_host(horizon_ns, np.int64), (self.B,)), np.int64)
+        out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
+        need = np.zeros((2, self.B), dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_plan_streaming(self._handle(), _ptr(s), _ptr(h), out.ctypes.data,
+                                                          _ptr(need[0]), _ptr(need[1]), None),
+               "tpamd_planner_set_plan_streaming")
+        return self._summary(out), need[0], need[1]
+
+    def plan_resume(self):
+        """tpamd_planner_set_plan_resume: the planners that wait for rows re-enter the window loop.
+        Returns (summary dict as plan(), need_first [B], need_count [B] int32 numpy)."""
+        out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
+        need = np.zeros((2, self.B), dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_plan_resume(self._handle(), out.ctypes.data, _ptr(need[0]), _ptr(need[1]),
+                                                       None), "tpamd_planner_set_plan_resume")
+        return self._summary(out), need[0], need[1]
+
+    def plan_streaming(self, start_ns, horizon_ns, ik=None, lookahead_rows=0):
+        """Plan with IK tables that grow as TimeableCartesianSplinePath::SamplePath grows them. Returns
+        (summary, need_first, need_count) as plan_resume does. Without `ik` this is one
+        tpamd_planner_set_plan_streaming call; the caller appends and resumes while need_count > 0.
+        With `ik` (after set_pose_waypoints(..., streaming=True)) the whole loop runs here and the
+        completed Plan is returned (need_count all zero): while planners wait, the targets of table
+        rows need_first - 1 .. need_first + need_count + lookahead_rows - 1 (never past the whole
+        table's tpamd_ik_table_rows) are sampled on the device from the resident fit,
+        ik(pose_targets, joint_targets, row_offsets, seed_rows) solves them (the first row of every
+        planner's run is the re-evaluated last resident row, as in the reference's callback;
+        seed_rows [waiting][D] is that resident row, its initial value), everything but that first
+        row is appended, and the plan resumes. Per-row data stays on the device; the host sends the
+        two time arrays and, per round, the row offsets of the waiting planners (ints), and reads the
+        summaries and need_*. Counters of the last call: self.last_stream_stats."""
+        import torch
+        summary, nf, nc = self._plan_streaming(start_ns, horizon_ns)
+        h2d, d2h = self.last_plan_bytes()
+        stats = dict(suspensions=0, appended_rows=0, h2d=[h2d], d2h=[d2h])
+        self.last_stream_stats = stats
+        if ik is None:
+            return summary, nf, nc
+        if getattr(self, "_stream_fit", None) is None:
+            raise TpamdError("plan_streaming with an IK needs set_pose_waypoints(..., streaming=True) first")
+        fit, dl, full = self._stream_fit["fit"], self._stream_fit["delta"], self._stream_fit["full_rows"]
+        while (nc > 0).any():
+            wait = np.flatnonzero(nc > 0)
+            cnt = np.minimum(nc[wait] + int(lookahead_rows), np.maximum(full[wait] - nf[wait], nc[wait])).astype(np.int64)
+            # the fit is sampled in place: the planners that do not wait take no rows
+            per = np.zeros(self.B, dtype=np.int64)
+            per[wait] = cnt + 1
+            first = np.zeros(self.B, dtype=np.int32)
+            first[wait] = nf[wait] - 1
+            pose_t, joint_t = self._engine.sample_ik_targets(
+                fit, dl, np.concatenate([[0], np.cumsum(per)]).astype(np.int32), first_row=first)
+            row_offsets = np.concatenate([[0], np.cumsum(cnt + 1)]).astype(np.int32)
+            q, J = ik(pose_t, joint_t, row_offsets, torch.stack([self._stream_last[int(b)] for b in wait]))
+            runs = [(int(row_offsets[k]) + 1, int(row_offsets[k + 1])) for k in range(wait.size)]
+            for k, b in enumerate(wait):
+                self._stream_last[int(b)] = q[runs[k][1] - 1]
+            self.append_ik_rows(torch.cat([q[a:e] for a, e in runs]), torch.cat([J[a:e] for a, e in runs]),
+                                np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32), ids=wait.astype(np.int32))
+            stats["suspensions"] += int(wait.size)
+            stats["appended_rows"] += int(cnt.sum())
+            summary, nf, nc = self.plan_resume()
+            h2d, d2h = self.last_plan_bytes()
+            stats["h2d"].append(h2d)
+            stats["d2h"].append(d2h)
+        return summary, nf, nc
 
     def stop_parameters(self, time_ns, ids=None):
         """GetPathStopParameter(time) on the resident trajectories (tpamd_planner_set_stop_parameters):

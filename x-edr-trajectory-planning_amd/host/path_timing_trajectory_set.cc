@@ -1,5 +1,7 @@
 #include "path_timing_trajectory_set.h"
 
+#include <chrono>
+
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -63,6 +65,9 @@ PathTimingTrajectorySet::~PathTimingTrajectorySet() {
 }
 
 namespace {
+double NowSeconds() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 int StateCode(TimeablePath::State s) {
   switch (s) {
     case TimeablePath::State::kNewPath: return 1;
@@ -94,7 +99,7 @@ Status PathTimingTrajectorySet::SetPath(size_t planner, const TimeableJointSplin
   return OkStatus();
 }
 
-Status PathTimingTrajectorySet::SetCartesianPath(size_t planner, TimeableCartesianSplinePath &path) {
+Status PathTimingTrajectorySet::SetCartesianPath(size_t planner, TimeableCartesianSplinePath &path, bool streaming) {
   if (!init_status_.ok()) return init_status_;
   if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetPath)");
   if (planner >= num_planners_) return InvalidArgumentError("no such planner");
@@ -107,7 +112,12 @@ Status PathTimingTrajectorySet::SetCartesianPath(size_t planner, TimeableCartesi
   if (path.GetMaxJointVelocity().size() != D || path.GetMaxJointAcceleration().size() != D)
     return FailedPreconditionError("set the joint limits first");
   IkTables t;
-  if (Status st = path.BuildIkTable(&t.ik_positions, &t.jacobians); !st.ok()) return st;
+  const double t0 = NowSeconds();
+  if (Status st = streaming ? path.ExtendIkTable(0, (int)options_.GetNumPathSamples() - 1, &t.ik_positions, &t.jacobians)
+                            : path.BuildIkTable(&t.ik_positions, &t.jacobians);
+      !st.ok())
+    return st;
+  callback_seconds_ = NowSeconds() - t0;
   t.row_offsets = {0, (int32_t)(t.ik_positions.size() / D)};
   t.path_end = {path.knots().back()};
   t.max_translational_velocity = {path.max_translational_velocity()};
@@ -118,10 +128,13 @@ Status PathTimingTrajectorySet::SetCartesianPath(size_t planner, TimeableCartesi
   if (path.GetInitialVelocity().size() == D)
     t.initial_velocity.assign(path.GetInitialVelocity().begin(), path.GetInitialVelocity().end());
   t.path_state = {state};
-  return SetIkTables({planner}, t);
+  const Status up = SetIkTables({planner}, t);
+  if (up.ok() && streaming) stream_paths_[planner] = &path;      // SetIkTables forgot the planner's previous source
+  return up;
 }
 
-Status PathTimingTrajectorySet::SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths) {
+Status PathTimingTrajectorySet::SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths,
+                                                  bool streaming) {
   if (!init_status_.ok()) return init_status_;
   if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetPaths)");
   if (paths.size() > num_planners_) return InvalidArgumentError("more paths than planners");
@@ -130,6 +143,7 @@ Status PathTimingTrajectorySet::SetCartesianPaths(const std::vector<std::shared_
   std::vector<size_t> planners(n);
   t.row_offsets.assign(1, 0);
   t.initial_velocity.assign(n * D, 0.0);
+  callback_seconds_ = 0.0;
   for (size_t k = 0; k < n; k++) {
     TimeableCartesianSplinePath &p = *paths[k];
     planners[k] = k;
@@ -140,7 +154,12 @@ Status PathTimingTrajectorySet::SetCartesianPaths(const std::vector<std::shared_
     if (state != 1 && state != 2) return FailedPreconditionError("SetWaypoints first");
     if (p.GetMaxJointVelocity().size() != D || p.GetMaxJointAcceleration().size() != D)
       return FailedPreconditionError("set the joint limits first");
-    if (Status st = p.BuildIkTable(&t.ik_positions, &t.jacobians); !st.ok()) return st;
+    const double t0 = NowSeconds();
+    if (Status st = streaming ? p.ExtendIkTable(0, (int)options_.GetNumPathSamples() - 1, &t.ik_positions, &t.jacobians)
+                              : p.BuildIkTable(&t.ik_positions, &t.jacobians);
+        !st.ok())
+      return st;
+    callback_seconds_ += NowSeconds() - t0;
     t.row_offsets.push_back((int32_t)(t.ik_positions.size() / D));
     t.path_end.push_back(p.knots().back());
     t.max_translational_velocity.push_back(p.max_translational_velocity());
@@ -153,7 +172,12 @@ Status PathTimingTrajectorySet::SetCartesianPaths(const std::vector<std::shared_
       std::copy(p.GetInitialVelocity().begin(), p.GetInitialVelocity().end(), t.initial_velocity.begin() + k * D);
     t.path_state.push_back(state);
   }
-  return SetIkTables(planners, t);
+  const Status up = SetIkTables(planners, t);
+  for (size_t k = 0; k < n && up.ok() && streaming; k++) {     // SetIkTables forgot the planners' previous sources
+    stream_paths_[k] = paths[k].get();
+    stream_keep_[k] = paths[k];
+  }
+  return up;
 }
 
 Status PathTimingTrajectorySet::SetIkTables(const std::vector<size_t> &planners, const IkTables &t) {
@@ -183,7 +207,10 @@ Status PathTimingTrajectorySet::SetIkTables(const std::vector<size_t> &planners,
     return InvalidArgumentError("a planner listed twice, a state other than new / modified, a table shorter than the "
                                 "window, delta <= 0 or row offsets that do not start at 0 and increase");
   if (rc != 0) return InternalError(tpamd_error_string(rc));
-  for (size_t k = 0; k < n; k++) summary_[planners[k]].path_state = state[k];
+  for (size_t k = 0; k < n; k++) {
+    summary_[planners[k]].path_state = state[k];
+    ForgetStreamSource(planners[k]);
+  }
   return OkStatus();
 }
 
@@ -200,14 +227,63 @@ struct DeviceArrays {
     if (from && count && hipMemcpy(p, from, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) failed = true;
     return (T *)p;
   }
+  // the allocation is no longer this object's to free
+  void release(void *p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
   ~DeviceArrays() { for (void *p : ptrs) (void)hipFree(p); }
 };
 }  // namespace
+
+// The fitted splines of the planners one streaming SetCartesianWaypointPaths call loaded, packed as the
+// fit left them (paths without waypoints have no slots), each planner's last resident table row and
+// the caller's IK.
+struct PathTimingTrajectorySet::StreamFit {
+  double *knots = nullptr, *trans = nullptr, *rot = nullptr, *joint_cp = nullptr, *delta = nullptr, *last = nullptr;
+  std::vector<int32_t> num_points, planner;       // [m]
+  DeviceSeededIkFunc ik;
+  ~StreamFit() {
+    for (void *p : {(void *)knots, (void *)trans, (void *)rot, (void *)joint_cp, (void *)delta, (void *)last})
+      if (p) (void)hipFree(p);
+  }
+};
+
+void PathTimingTrajectorySet::ForgetStreamSource(size_t planner) {
+  stream_paths_.resize(num_planners_, nullptr);
+  stream_keep_.resize(num_planners_);
+  stream_fits_.resize(num_planners_);
+  stream_fit_index_.resize(num_planners_, -1);
+  stream_paths_[planner] = nullptr;
+  stream_keep_[planner] = nullptr;
+  stream_fits_[planner] = nullptr;
+  stream_fit_index_[planner] = -1;
+}
 
 Status PathTimingTrajectorySet::SetCartesianWaypointPaths(const std::vector<size_t> &planners,
                                                           const std::vector<std::vector<Pose3d>> &pose_waypoints,
                                                           const std::vector<std::vector<VectorXd>> &joint_waypoints,
                                                           const CartesianPathLimits &lim, const DeviceIkFunc &ik) {
+  if (!ik) return WaypointPathsImpl(planners, pose_waypoints, joint_waypoints, lim, nullptr, false);
+  return WaypointPathsImpl(planners, pose_waypoints, joint_waypoints, lim,
+                           [&ik](const double *pose_targets, const double *joint_targets,
+                                 const std::vector<int32_t> &row_offsets, const double *, double *ik_positions,
+                                 double *jacobians, void *hip_stream) {
+                             return ik(pose_targets, joint_targets, row_offsets, ik_positions, jacobians, hip_stream);
+                           },
+                           false);
+}
+
+Status PathTimingTrajectorySet::SetCartesianWaypointPaths(const std::vector<size_t> &planners,
+                                                          const std::vector<std::vector<Pose3d>> &pose_waypoints,
+                                                          const std::vector<std::vector<VectorXd>> &joint_waypoints,
+                                                          const CartesianPathLimits &lim, const DeviceSeededIkFunc &ik,
+                                                          bool streaming) {
+  return WaypointPathsImpl(planners, pose_waypoints, joint_waypoints, lim, ik, streaming);
+}
+
+Status PathTimingTrajectorySet::WaypointPathsImpl(const std::vector<size_t> &planners,
+                                                  const std::vector<std::vector<Pose3d>> &pose_waypoints,
+                                                  const std::vector<std::vector<VectorXd>> &joint_waypoints,
+                                                  const CartesianPathLimits &lim, const DeviceSeededIkFunc &ik,
+                                                  bool streaming) {
   if (!init_status_.ok()) return init_status_;
   if (!cartesian_) return FailedPreconditionError("a joint set takes joint spline paths (SetWaypointPaths)");
   const size_t n = planners.size(), D = options_.GetNumDofs(), N = options_.GetNumPathSamples();
@@ -283,7 +359,8 @@ Status PathTimingTrajectorySet::SetCartesianWaypointPaths(const std::vector<size
                                          ": no waypoints, or pose and joint waypoints that do not match");
       continue;
     }
-    const int rows = tpamd_ik_table_rows(path_end[k], lim.delta_parameter, (int)N);
+    // streaming: the first window's rows only, as the path's first SamplePath solves them
+    const int rows = streaming ? (int)N : tpamd_ik_table_rows(path_end[k], lim.delta_parameter, (int)N);
     if (rows < 0) return InternalError("tpamd_ik_table_rows");
     ids.push_back((int32_t)planners[k]);
     num_points.push_back(point_offsets[k + 1] - point_offsets[k]);
@@ -314,17 +391,125 @@ Status PathTimingTrajectorySet::SetCartesianWaypointPaths(const std::vector<size
     (void)hipDeviceSynchronize();
     return InternalError(tpamd_error_string(rc));
   }
-  const Status ik_status = ik(d_pose_t, d_joint_t, row_offsets, d_q, d_J, st);
+  const Status ik_status = ik(d_pose_t, d_joint_t, row_offsets, nullptr, d_q, d_J, st);
   if (!ik_status.ok()) {
     (void)hipDeviceSynchronize();
     return ik_status;
+  }
+  std::shared_ptr<StreamFit> fit;
+  if (streaming) {
+    // the splines stay; every planner's last resident row is the seed of its first extension
+    fit = std::make_shared<StreamFit>();
+    fit->num_points = num_points;
+    fit->planner = ids;
+    fit->ik = ik;
+    bool ok = hipMalloc((void **)&fit->last, m * D * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&fit->delta, m * sizeof(double)) == hipSuccess &&
+              hipMemcpyAsync(fit->delta, d_dl, m * sizeof(double), hipMemcpyDeviceToDevice, st) == hipSuccess;
+    for (size_t k = 0; k < m && ok; k++)
+      ok = hipMemcpyAsync(fit->last + k * D, d_q + ((size_t)row_offsets[k + 1] - 1) * D, D * sizeof(double),
+                          hipMemcpyDeviceToDevice, st) == hipSuccess;
+    if (!ok) {
+      (void)hipDeviceSynchronize();
+      return InternalError("device memory for the resident splines");
+    }
   }
   rc = tpamd_planner_set_upload_ik_tables_device(set_, (int)m, ids.data(), row_offsets.data(), d_q, d_J, d_end_ok, d_vmax,
                                                  d_amax, d_vt, d_vr, d_dl, d_iv, d_state, st);
   if (hipDeviceSynchronize() != hipSuccess) return InternalError("the device chain failed");   // before mem goes
   if (rc != 0) return InternalError(tpamd_error_string(rc));
-  for (size_t k = 0; k < m; k++) summary_[ids[k]].path_state = 1;
+  for (size_t k = 0; k < m; k++) {
+    summary_[ids[k]].path_state = 1;
+    ForgetStreamSource((size_t)ids[k]);
+    if (fit) {
+      stream_fits_[ids[k]] = fit;
+      stream_fit_index_[ids[k]] = (int)k;
+    }
+  }
+  if (fit) {
+    for (double *p : {d_knots, d_t, d_r, d_j}) mem.release(p);
+    fit->knots = d_knots; fit->trans = d_t; fit->rot = d_r; fit->joint_cp = d_j;
+  }
   return first_bad;
+}
+
+// One round of extensions through the device chain: every waiting planner whose path came from a
+// streaming SetCartesianWaypointPaths call gets the rows it lacks. A fit's paths are sampled in place
+// (the planners that do not wait take no rows), so nothing is repacked.
+Status PathTimingTrajectorySet::ExtendOnDevice(const std::vector<int32_t> &need_first,
+                                               const std::vector<int32_t> &need_count, std::vector<Status> *failed) {
+  const size_t D = options_.GetNumDofs();
+  std::vector<std::shared_ptr<StreamFit>> fits;
+  for (size_t b = 0; b < num_planners_; b++)
+    if (need_count[b] > 0 && (*failed)[b].ok() && b < stream_fits_.size() && stream_fits_[b] &&
+        std::find(fits.begin(), fits.end(), stream_fits_[b]) == fits.end())
+      fits.push_back(stream_fits_[b]);
+  if (fits.empty()) return OkStatus();
+  int previous = 0;
+  if (hipGetDevice(&previous) != hipSuccess || hipSetDevice(lease_.device()) != hipSuccess)
+    return InternalError("no HIP device");
+  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{previous};
+  hipStream_t st = nullptr;
+  for (const std::shared_ptr<StreamFit> &fit : fits) {
+    const size_t m = fit->planner.size();
+    std::vector<int32_t> rows_of(m + 1, 0), first_row(m, 0), ids, run(1, 0), kept(1, 0);
+    std::vector<size_t> which;
+    for (size_t k = 0; k < m; k++) {
+      const size_t b = (size_t)fit->planner[k];
+      const bool waits = stream_fits_[b] == fit && stream_fit_index_[b] == (int)k && need_count[b] > 0 && (*failed)[b].ok();
+      rows_of[k + 1] = rows_of[k] + (waits ? need_count[b] + 1 : 0);     // the last resident row once more, then the new rows
+      if (!waits) continue;
+      first_row[k] = need_first[b] - 1;
+      ids.push_back((int32_t)b);
+      which.push_back(k);
+      run.push_back(rows_of[k + 1]);
+      kept.push_back(kept.back() + need_count[b]);
+    }
+    const size_t w = ids.size(), rows = (size_t)rows_of[m], keep = (size_t)kept.back();
+    if (w == 0) continue;
+    DeviceArrays mem;
+    double *d_pose_t = mem.take<double>(rows * 7), *d_joint_t = mem.take<double>(rows * D);
+    double *d_q = mem.take<double>(rows * D), *d_J = mem.take<double>(rows * 6 * D), *d_seed = mem.take<double>(w * D);
+    double *d_q2 = mem.take<double>(keep * D), *d_J2 = mem.take<double>(keep * 6 * D);
+    Status bad = mem.failed ? InternalError("device memory for the new rows") : OkStatus();
+    int rc = 0;
+    if (bad.ok()) {
+      rc = tpamd_sample_ik_target_rows_device(lease_.get(), (int)m, (int)D, fit->num_points.data(), rows_of.data(),
+                                              first_row.data(), fit->knots, fit->trans, fit->rot, fit->joint_cp, fit->delta,
+                                              d_pose_t, d_joint_t, st);
+      if (rc != 0) bad = InternalError(tpamd_error_string(rc));
+    }
+    for (size_t k = 0; k < w && bad.ok(); k++)
+      if (hipMemcpyAsync(d_seed + k * D, fit->last + which[k] * D, D * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        bad = InternalError("copying the seed rows");
+    if (bad.ok()) bad = fit->ik(d_pose_t, d_joint_t, run, d_seed, d_q, d_J, st);
+    for (size_t k = 0; k < w && bad.ok(); k++) {
+      // without the re-evaluated first row; the run's last row is the next seed
+      const size_t from = (size_t)run[k] + 1, n = (size_t)(kept[k + 1] - kept[k]);
+      if (hipMemcpyAsync(d_q2 + (size_t)kept[k] * D, d_q + from * D, n * D * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+          hipMemcpyAsync(d_J2 + (size_t)kept[k] * 6 * D, d_J + from * 6 * D, n * 6 * D * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+          hipMemcpyAsync(fit->last + which[k] * D, d_q + ((size_t)run[k + 1] - 1) * D, D * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        bad = InternalError("packing the new rows");
+    }
+    if (bad.ok()) {
+      rc = tpamd_planner_set_append_ik_rows_device(set_, (int)w, ids.data(), kept.data(), d_q2, d_J2, st);
+      if (rc != 0) bad = InternalError(tpamd_error_string(rc));
+    }
+    if (hipDeviceSynchronize() != hipSuccess && bad.ok()) bad = InternalError("the device chain failed");   // before mem goes
+    if (!bad.ok())
+      for (int32_t b : ids) (*failed)[b] = bad;
+    else
+      suspensions_ += (int)w;
+  }
+  return OkStatus();
+}
+
+int PathTimingTrajectorySet::GetIkTableRows(size_t planner) const {
+  int32_t rows = 0;
+  if (!init_status_.ok() || !cartesian_ || planner >= num_planners_ ||
+      tpamd_planner_set_download_ik_table(set_, (int)planner, &rows, nullptr, nullptr, 0) != 0)
+    return -1;
+  return rows;
 }
 
 Status PathTimingTrajectorySet::GetIkTable(size_t planner, std::vector<double> *ik_positions,
@@ -404,6 +589,11 @@ std::vector<Status> PathTimingTrajectorySet::Plan(const std::vector<Time> &start
     std::fill(result.begin(), result.end(), InternalError(tpamd_error_string(rc)));
     return result;
   }
+  return PlanStatuses();
+}
+
+std::vector<Status> PathTimingTrajectorySet::PlanStatuses() const {
+  std::vector<Status> result(num_planners_, OkStatus());
   for (size_t b = 0; b < num_planners_; b++) {
     switch (summary_[b].status) {
       case TPAMD_PLAN_OK: break;
@@ -412,9 +602,86 @@ std::vector<Status> PathTimingTrajectorySet::Plan(const std::vector<Time> &start
       case TPAMD_PLAN_INVALID_ARGUMENT:
         result[b] = InvalidArgumentError("start time / duration / initial velocity not acceptable"); break;
       case TPAMD_PLAN_DEADLINE_EXCEEDED: result[b] = DeadlineExceededError("Reached maximum number of planning loops"); break;
+      case TPAMD_PLAN_NEEDS_ROWS: result[b] = InternalError("IK solution does not cover the sampled window"); break;
       default: result[b] = InternalError("Error optimizing path parameter"); break;
     }
   }
+  return result;
+}
+
+std::vector<Status> PathTimingTrajectorySet::PlanStreaming(Time start, Duration time_horizon) {
+  return PlanStreaming(std::vector<Time>(num_planners_, start), std::vector<Duration>(num_planners_, time_horizon));
+}
+
+std::vector<Status> PathTimingTrajectorySet::PlanStreaming(const std::vector<Time> &start,
+                                                           const std::vector<Duration> &time_horizon) {
+  std::vector<Status> result(num_planners_, OkStatus());
+  Status bad = init_status_;
+  if (bad.ok() && !cartesian_) bad = FailedPreconditionError("a joint set has no IK tables (Plan)");
+  if (bad.ok() && (start.size() != num_planners_ || time_horizon.size() != num_planners_))
+    bad = InvalidArgumentError("one start time and horizon per planner");
+  if (!bad.ok()) {
+    std::fill(result.begin(), result.end(), bad);
+    return result;
+  }
+  std::vector<int64_t> s(num_planners_), h(num_planners_);
+  for (size_t b = 0; b < num_planners_; b++) {
+    s[b] = ::tpamd::compat::ToUnixNanos(start[b]);
+    h[b] = time_horizon[b].nanos();
+  }
+  std::vector<int32_t> need_first(num_planners_), need_count(num_planners_);
+  int32_t waiting = 0;
+  suspensions_ = 0;
+  int rc = tpamd_planner_set_plan_streaming(set_, s.data(), h.data(), summary_.data(), need_first.data(),
+                                            need_count.data(), &waiting);
+  std::vector<Status> ik_failed(num_planners_, OkStatus());
+  callback_seconds_ = 0.0;
+  const size_t D = options_.GetNumDofs();
+  while (rc == 0 && waiting > 0) {
+    // host route: every waiting planner's path extends its IK solution as SamplePath would for that
+    // window. A planner whose IK failed is not asked again: it keeps waiting, and the next Plan drops
+    // it, as after a failed SamplePath.
+    std::vector<int32_t> ids, offsets(1, 0);
+    std::vector<double> q, J;
+    for (size_t b = 0; b < num_planners_; b++) {
+      if (need_count[b] <= 0 || !ik_failed[b].ok()) continue;
+      if (b < stream_fits_.size() && stream_fits_[b]) continue;                  // device route below
+      TimeableCartesianSplinePath *path = b < stream_paths_.size() ? stream_paths_[b] : nullptr;
+      const double t0 = NowSeconds();
+      const Status st = path ? path->ExtendIkTable(need_first[b], need_first[b] + need_count[b] - 1, &q, &J)
+                             : InternalError("IK solution does not cover the sampled window");
+      callback_seconds_ += NowSeconds() - t0;
+      if (!st.ok()) {
+        ik_failed[b] = st;
+        q.resize((size_t)offsets.back() * D);
+        J.resize((size_t)offsets.back() * 6 * D);
+        continue;
+      }
+      ids.push_back((int32_t)b);
+      offsets.push_back((int32_t)(q.size() / D));
+    }
+    if (!ids.empty()) {
+      suspensions_ += (int)ids.size();
+      rc = tpamd_planner_set_append_ik_rows(set_, (int)ids.size(), ids.data(), offsets.data(), q.data(), J.data());
+    }
+    // device route
+    if (rc == 0)
+      if (const Status st = ExtendOnDevice(need_first, need_count, &ik_failed); !st.ok()) {
+        std::fill(result.begin(), result.end(), st);
+        return result;
+      }
+    bool progress = false;
+    for (size_t b = 0; b < num_planners_; b++) progress = progress || (need_count[b] > 0 && ik_failed[b].ok());
+    if (!progress) break;
+    if (rc == 0) rc = tpamd_planner_set_plan_resume(set_, summary_.data(), need_first.data(), need_count.data(), &waiting);
+  }
+  if (rc != 0) {
+    std::fill(result.begin(), result.end(), InternalError(tpamd_error_string(rc)));
+    return result;
+  }
+  result = PlanStatuses();
+  for (size_t b = 0; b < num_planners_; b++)
+    if (!ik_failed[b].ok()) result[b] = ik_failed[b];
   return result;
 }
 

@@ -82,6 +82,16 @@ using DeviceIkFunc = std::function<Status(const double *pose_targets, const doub
                                           const std::vector<int32_t> &row_offsets, double *ik_positions,
                                           double *jacobians, void *hip_stream)>;
 
+// The caller's IK on the device for streaming tables (SetCartesianWaypointPaths(..., streaming),
+// PlanStreaming): as DeviceIkFunc, plus seed_rows [planners][dofs] (DEVICE), the initial value of
+// each planner's run as the reference's callback receives it (initial_value,
+// timeable_path_cartesian_spline.cc:504-506): the table's last resident row, whose targets the
+// run's first row repeats. seed_rows is null for the first rows of a new path (the reference seeds
+// those with the first joint target, which the function has in joint_targets).
+using DeviceSeededIkFunc =
+    std::function<Status(const double *pose_targets, const double *joint_targets, const std::vector<int32_t> &row_offsets,
+                         const double *seed_rows, double *ik_positions, double *jacobians, void *hip_stream)>;
+
 // Constructor tag of a Cartesian set: rows per planner the IK tables hold to start with (they grow).
 struct CartesianTableCapacity {
   size_t rows;
@@ -110,8 +120,12 @@ class PathTimingTrajectorySet {
   // BuildIkTable on the path (one IK callback call over the whole path, one Jacobian callback per
   // row), then the table with the path's limits, delta, initial velocity and state go to the
   // device. The path must be kNewPath or kModifiedPath; its state does not change.
-  Status SetCartesianPath(size_t planner, TimeableCartesianSplinePath &path);
-  Status SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths);
+  // With `streaming` only rows 0 .. N-1 go up, built as the path's first SamplePath builds them
+  // (ExtendIkTable), and the set keeps a pointer to the path: PlanStreaming extends the table when
+  // a planner's window reaches past it. The path must outlive the set or its next path.
+  Status SetCartesianPath(size_t planner, TimeableCartesianSplinePath &path, bool streaming = false);
+  Status SetCartesianPaths(const std::vector<std::shared_ptr<TimeableCartesianSplinePath>> &paths,
+                           bool streaming = false);
   // Raw tables for the listed planners (each listed once).
   Status SetIkTables(const std::vector<size_t> &planners, const IkTables &tables);
   // New Cartesian goals for the listed planners (each listed once) without per-row data on the host:
@@ -129,8 +143,24 @@ class PathTimingTrajectorySet {
                                    const std::vector<std::vector<Pose3d>> &pose_waypoints,
                                    const std::vector<std::vector<VectorXd>> &joint_waypoints,
                                    const CartesianPathLimits &limits, const DeviceIkFunc &ik);
+  // The same chain for tables that grow: with `streaming` only rows 0 .. N-1 of every table are
+  // sampled, solved and uploaded, and the fitted splines stay in device memory with the set.
+  // PlanStreaming then extends a waiting planner's table on the device: the targets of rows
+  // need_first - 1 .. need_first + need_count - 1 (tpamd_sample_ik_target_rows_device), `ik` with
+  // the table's last row as the seed, and tpamd_planner_set_append_ik_rows_device for everything but
+  // the re-evaluated first row. Nothing per row touches the host. Without `streaming` this is the
+  // call above with a seeded IK (seed_rows null).
+  Status SetCartesianWaypointPaths(const std::vector<size_t> &planners,
+                                   const std::vector<std::vector<Pose3d>> &pose_waypoints,
+                                   const std::vector<std::vector<VectorXd>> &joint_waypoints,
+                                   const CartesianPathLimits &limits, const DeviceSeededIkFunc &ik, bool streaming);
+  // Seconds the last SetCartesianPath(s) / PlanStreaming call spent in the paths' IK and Jacobian
+  // callbacks on the host (measurement: tools/cartesian_stream_bench.cc).
+  double HostCallbackSecondsOfLastCall() const { return callback_seconds_; }
   // The planner's resident table (no table: empty).
   Status GetIkTable(size_t planner, std::vector<double> *ik_positions, std::vector<double> *jacobians) const;
+  // Rows of the planner's resident table (no download); -1 on a joint set or a planner out of range.
+  int GetIkTableRows(size_t planner) const;
   PathTimingTrajectorySet(const PathTimingTrajectorySet &) = delete;
   PathTimingTrajectorySet &operator=(const PathTimingTrajectorySet &) = delete;
 
@@ -145,6 +175,17 @@ class PathTimingTrajectorySet {
   // Plan(start, time_horizon) for every planner; one status per planner.
   std::vector<Status> Plan(Time start, Duration time_horizon);
   std::vector<Status> Plan(const std::vector<Time> &start, const std::vector<Duration> &time_horizon);
+  // Plan for a Cartesian set whose paths were loaded with `streaming`: the tables grow exactly as
+  // TimeableCartesianSplinePath::SamplePath grows path_ik_positions_ (:464-549). While planners wait
+  // for rows (tpamd_planner_set_plan_streaming), each waiting planner's path extends its IK solution
+  // to the last row its window needs -- one IK callback call, seeded with the table's last row --,
+  // the Jacobian callback runs on the new rows, one tpamd_planner_set_append_ik_rows takes all of
+  // them and tpamd_planner_set_plan_resume goes on. The set then equals one PathTimingTrajectory
+  // per planner planning window by window, also with an IK whose result depends on the split into
+  // calls.
+  std::vector<Status> PlanStreaming(Time start, Duration time_horizon);
+  std::vector<Status> PlanStreaming(const std::vector<Time> &start, const std::vector<Duration> &time_horizon);
+  int SuspensionsOfLastPlan() const { return suspensions_; }
 
   // State after the last Plan, from the summary record (no trajectory download).
   size_t GetNumTimeSamples(size_t planner) const { return (size_t)summary_[planner].num_samples; }
@@ -229,6 +270,23 @@ class PathTimingTrajectorySet {
   ::tpamd::EngineLease lease_;
   tpamd_planner_set *set_ = nullptr;
   std::vector<tpamd_planner_summary> summary_;
+  // streaming Cartesian sets: the path each planner's table is extended from (null: none)
+  std::vector<TimeableCartesianSplinePath *> stream_paths_;
+  std::vector<std::shared_ptr<TimeableCartesianSplinePath>> stream_keep_;
+  int suspensions_ = 0;
+  double callback_seconds_ = 0.0;
+  // streaming through the device chain: the fitted splines of one SetCartesianWaypointPaths call,
+  // resident until none of its planners refers to them
+  struct StreamFit;
+  std::vector<std::shared_ptr<StreamFit>> stream_fits_;      // [planner] (null: none)
+  std::vector<int> stream_fit_index_;                        // [planner] its path in the fit
+  void ForgetStreamSource(size_t planner);                   // the planner's table was replaced
+  Status WaypointPathsImpl(const std::vector<size_t> &planners, const std::vector<std::vector<Pose3d>> &pose_waypoints,
+                           const std::vector<std::vector<VectorXd>> &joint_waypoints, const CartesianPathLimits &limits,
+                           const DeviceSeededIkFunc &ik, bool streaming);
+  Status ExtendOnDevice(const std::vector<int32_t> &need_first, const std::vector<int32_t> &need_count,
+                        std::vector<Status> *failed);
+  std::vector<Status> PlanStatuses() const;
 };
 
 }  // namespace trajectory_planning

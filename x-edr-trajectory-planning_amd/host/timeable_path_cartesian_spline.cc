@@ -308,6 +308,24 @@ Status TimeableCartesianSplinePath::BuildIkTable(std::vector<double> *ik_positio
   return OkStatus();
 }
 
+Status TimeableCartesianSplinePath::ExtendIkTable(const int first_row, const int last_row,
+                                                  std::vector<double> *ik_positions, std::vector<double> *jacobians) {
+  if (knots_.empty()) return FailedPreconditionError("Call SetWaypoints first.");
+  if (first_row < 0 || last_row < first_row) return InvalidArgumentError("no such rows");
+  const size_t D = options_.num_dofs();
+  if (Status st = ExtendIkSolution(last_row); !st.ok()) return st;
+  if ((int)path_ik_positions_.size() <= last_row) return InternalError("IK solution does not cover the rows");
+  Matrix6Xd jacobian(6, D);
+  for (int r = first_row; r <= last_row; r++) {
+    const VectorXd &q = path_ik_positions_[r];
+    ik_positions->insert(ik_positions->end(), q.begin(), q.end());
+    jacobian.setZero();
+    if (Status st = jacobian_func_(q, &jacobian); !st.ok()) return st;
+    jacobians->insert(jacobians->end(), jacobian.data(), jacobian.data() + 6 * D);
+  }
+  return OkStatus();
+}
+
 // timeable_path_cartesian_spline.cc:551-595
 Status TimeableCartesianSplinePath::ConstraintSetup() {
   const size_t N = options_.num_path_samples(), D = options_.num_dofs();

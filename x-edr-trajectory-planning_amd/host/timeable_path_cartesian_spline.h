@@ -112,6 +112,13 @@ class TimeableCartesianSplinePath : public TimeablePath {
   // for a sample does not depend on how the samples were split into calls (closed-form and
   // per-sample solvers; not a solver warm-started across the samples of one call).
   Status BuildIkTable(std::vector<double> *ik_positions, std::vector<double> *jacobians);
+  // A part of the table, grown as SamplePath grows it (PathTimingTrajectorySet::PlanStreaming):
+  // path_ik_positions_ is extended to row last_row exactly as SamplePath extends it for a window
+  // that ends there (:484-526: one call of the IK callback for the rows behind the table's last
+  // row, which is re-evaluated and seeds the call; parameter 0 twice and the first joint target as
+  // the seed on the first call), then rows first_row .. last_row and the Jacobian callback's
+  // result at each are appended to ik_positions [.][D] / jacobians [.][6][D]. GetState() stays.
+  Status ExtendIkTable(int first_row, int last_row, std::vector<double> *ik_positions, std::vector<double> *jacobians);
 
  private:
   Status FitSplineToWaypoints();
