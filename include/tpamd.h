@@ -674,9 +674,64 @@ int tpamd_planner_set_plan_resume(tpamd_planner_set *set, tpamd_planner_summary 
                                   int32_t *need_first, int32_t *need_count, int32_t *num_waiting);
 /* The resident table of one planner: *rows (0: no table) and, if the arrays are not NULL,
  * ik_positions [rows][D] and jacobians [rows][6][D]. `capacity` is the number of rows the arrays
- * can hold; a longer table gives TPAMD_E_INVALID_ARGUMENT (*rows is still written). */
+ * can hold; a longer table gives TPAMD_E_INVALID_ARGUMENT (*rows is still written). For a planner
+ * whose front rows were discarded (first_row > 0, below) it writes *rows, the path rows supplied
+ * so far, and returns TPAMD_E_INVALID_ARGUMENT: it cannot deliver rows from 0;
+ * tpamd_planner_set_download_ik_rows reads such a table. */
 int tpamd_planner_set_download_ik_table(tpamd_planner_set *set, int planner, int32_t *rows,
                                         double *ik_positions, double *jacobians, int capacity);
+/* ---- Streaming IK tables: discarding the consumed rows ---------------------------------------
+ * A receding-horizon planner never reads a table row again once its trajectory has moved past it.
+ * Every planner has a first resident row, first_row[b]: the table holds path rows first_row ..
+ * rows - 1, `rows` keeps counting the path rows supplied since the upload (need_first / need_count
+ * and the append entries keep speaking in path rows), and rows - first_row rows are live. first_row
+ * is 0 after create, upload_ik_tables[_device] and reset, and a set on which discard_ik_rows is
+ * never called behaves, allocates and reports as before. With the discard in the loop,
+ *
+ *   plan_streaming / append_ik_rows / plan_resume      as above
+ *   discard_ik_rows(keep_from = NULL)                  after each completed Plan
+ *
+ * a table's footprint stays at the rows one Plan reads instead of growing to the whole path: the
+ * allocation is never shrunk, but an append whose rows fit into capacity - live rows does not
+ * reallocate, and a growth copies the live rows only.
+ *
+ * discard_ik_rows: planner ids[k] (each listed once; ids NULL: 0..count-1) keeps path rows from
+ * keep_from[k] on; its live rows move to the front of its table, in place, on the device.
+ * keep_from NULL: every listed planner keeps the rows from its safe floor on, the lowest row any
+ * later Plan or resume of that planner can read, computed on the device from its window history:
+ * PathIkIndex of the path parameter at start_time_, the start of its last Plan, before which
+ * HandleTimeArguments accepts no later start; 0 for a new path or a planner that has not planned.
+ * An explicit keep_from is the caller's responsibility and may lie above the floor: a planner
+ * whose next window starts below its first resident row gets TPAMD_PLAN_INTERNAL, that planner
+ * alone, and stays so until upload_ik_tables* gives it a table from row 0 again (an append only goes
+ * behind the last row). keep_from is clamped on the device to [first_row, rows - 1]: a value at or
+ * below first_row changes nothing for that planner, and the last resident row is never discarded,
+ * since the streaming chain seeds the next extension's IK with it. The call is legal while planners
+ * wait for rows. It synchronises; first_row_out [count] (host, may be NULL) receives the new first
+ * rows: 4 bytes per listed planner come down, the ids (and keep_from) go up. A joint set, count < 0
+ * or > B, a bad or repeated id, or a planner that has no table as far as the host knows fail the
+ * call, before the first launch, and change nothing. A planner whose table the kernel rejected at a
+ * _device upload is left untouched. */
+int tpamd_planner_set_discard_ik_rows(tpamd_planner_set *set, int count, const int32_t *ids,
+                                      const int32_t *keep_from, int32_t *first_row_out);
+/* Host bookkeeping of one planner's table, no device access: *first_row, *rows (path rows supplied;
+ * 0 / 0: no table) and *capacity (table rows allocated per planner, the same for every planner).
+ * Each pointer may be NULL. TPAMD_E_INVALID_ARGUMENT on a joint set or a bad planner index. */
+int tpamd_planner_set_ik_table_info(const tpamd_planner_set *set, int planner, int32_t *first_row,
+                                    int32_t *rows, int32_t *capacity);
+/* The live rows of one planner's table: *first_row, *rows_live = rows - first_row (0: no table) and,
+ * if the arrays are not NULL, ik_positions [rows_live][D] and jacobians [rows_live][6][D], path rows
+ * first_row .. rows - 1. `capacity` is the number of rows the arrays can hold; more live rows give
+ * TPAMD_E_INVALID_ARGUMENT (*first_row and *rows_live are still written). */
+int tpamd_planner_set_download_ik_rows(tpamd_planner_set *set, int planner, int32_t *first_row,
+                                       int32_t *rows_live, double *ik_positions, double *jacobians,
+                                       int capacity);
+/* The device addresses of the tables, [B][capacity][D] and [B][capacity][6][D] (either pointer may
+ * be NULL); planner b's path row r is in slot r - first_row[b]. They change when the capacity grows
+ * and only then, so a caller can tell that an append did not reallocate. Read-only. */
+int tpamd_planner_set_ik_table_device_pointers(const tpamd_planner_set *set,
+                                               const double **ik_positions,
+                                               const double **jacobians);
 /* TrajectoryPlanner::Reset for the listed planners (ids NULL: all): no path, no plan. */
 int tpamd_planner_set_reset(tpamd_planner_set *set, int count, const int32_t *ids);
 /* Plan(start, time_horizon) for every planner: start_ns / horizon_ns [B] host arrays;

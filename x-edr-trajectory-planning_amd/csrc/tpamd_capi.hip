@@ -2246,16 +2246,17 @@ struct tpamd_planner_set {
   hipEvent_t ev_wp = nullptr;
   bool wp_pin_busy = false;
   // Cartesian sets: the IK tables [B][table_cap][D] | [B][table_cap][6][D] (one allocation; it
-  // grows), a host copy of the row counts, and the per-planner Cartesian limits and path ends
-  // (part of `fixed`). The upload entries share wp_buf / wp_pin with set_waypoints.
+  // grows), a host copy of the row counts and of the first resident rows (slot 0 of planner b's
+  // table holds path row first_row[b]; rows below it were discarded), and the per-planner Cartesian
+  // limits and path ends (part of `fixed`). The upload entries share wp_buf / wp_pin with set_waypoints.
   bool cartesian = false;
   int table_cap = 0;
   void *table = nullptr;
   size_t table_bytes = 0;
   double *d_tq = nullptr, *d_tJ = nullptr;
-  std::vector<int> h_rows;
+  std::vector<int> h_rows, h_first_row;
   double *d_vtrans = nullptr, *d_vrot = nullptr, *d_path_end = nullptr;
-  int *d_rows = nullptr, *d_first = nullptr;
+  int *d_rows = nullptr, *d_first = nullptr, *d_first_row = nullptr;
   // streaming Plan: the planners that wait for rows (device flags and host copy), what they lack
   // ([need_first[B]][need_count[B]], one copy down per call) and whether P carries the arrays
   int *d_suspended = nullptr, *d_need = nullptr;
@@ -2310,6 +2311,7 @@ void refresh_plan_params(tpamd_planner_set *ps) {
   S.path_end = ps->cartesian ? ps->d_path_end : nullptr;
   p.path_end = S.path_end;
   p.rows = ps->cartesian ? ps->d_rows : nullptr;
+  p.first_row = ps->cartesian ? ps->d_first_row : nullptr;
   p.first = ps->d_first;
   p.rec_stride = 0;
   p.suspended = ps->streaming ? ps->d_suspended : nullptr;
@@ -2390,7 +2392,8 @@ int ensure_pcap(tpamd_planner_set *ps, int need, hipStream_t st) {
   return grow_paths(ps, p, st);
 }
 
-// Move the IK tables to arrays of a larger per-planner capacity (rows); contents unchanged.
+// Move the IK tables to arrays of a larger per-planner capacity (rows): the live rows (slots 0 ..
+// rows - first_row - 1 of every planner, as the host counts them) are copied, first_row stays.
 int grow_table(tpamd_planner_set *ps, int new_cap, hipStream_t st) {
   const size_t B = ps->S.B, D = ps->S.D, old_r = ps->table_cap, new_r = new_cap;
   const double *old_q = ps->d_tq, *old_J = ps->d_tJ;
@@ -2401,9 +2404,14 @@ int grow_table(tpamd_planner_set *ps, int new_cap, hipStream_t st) {
   carve_table((char *)fresh, B, new_r, D, ps);
   ps->table = fresh; ps->table_bytes = need; ps->table_cap = new_cap;
   HIPCHK(hipMemsetAsync(fresh, 0, need, st));
-  HIPCHK(hipMemcpy2DAsync(ps->d_tq, new_r * D * 8, old_q, old_r * D * 8, old_r * D * 8, B, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpy2DAsync(ps->d_tJ, new_r * 6 * D * 8, old_J, old_r * 6 * D * 8, old_r * 6 * D * 8, B,
-                          hipMemcpyDeviceToDevice, st));
+  size_t live = 0;
+  for (size_t b = 0; b < B; b++) live = std::max(live, (size_t)std::max(ps->h_rows[b] - ps->h_first_row[b], 0));
+  live = std::min(live, old_r);
+  if (live > 0) {
+    HIPCHK(hipMemcpy2DAsync(ps->d_tq, new_r * D * 8, old_q, old_r * D * 8, live * D * 8, B, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(ps->d_tJ, new_r * 6 * D * 8, old_J, old_r * 6 * D * 8, live * 6 * D * 8, B,
+                            hipMemcpyDeviceToDevice, st));
+  }
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipFree(old_base));
   refresh_plan_params(ps);
@@ -2609,6 +2617,7 @@ int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, 
   ps->h_has.assign(B, 0);
   ps->cartesian = cartesian;
   ps->h_rows.assign(B, 0);
+  ps->h_first_row.assign(B, 0);
   ps->h_wait.assign(B, 0);
   ps->h_need.assign(2 * B, 0);
   PlannerSetState &S = ps->S;
@@ -2638,6 +2647,7 @@ int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, 
     if (cartesian) {
       ps->d_vtrans = s.take<double>(B); ps->d_vrot = s.take<double>(B); ps->d_path_end = s.take<double>(B);
       ps->d_rows = s.take<int>(B); ps->d_first = s.take<int>(B);
+      ps->d_first_row = s.take<int>(B);
       ps->d_suspended = s.take<int>(B); ps->d_need = s.take<int>(2 * B);
     }
     if (!pass) {
@@ -2789,10 +2799,14 @@ int tpamd_planner_set_reset(tpamd_planner_set *ps, int count, const int32_t *ids
     for (long long *a : {S.start_time_ns, S.end_time_ns, S.final_decel_start_ns})
       HIPCHK(hipMemsetAsync(a + b, 0, 8, nullptr));
     HIPCHK(hipMemcpyAsync(S.planned_to_end + b, &one, 4, hipMemcpyHostToDevice, nullptr));
+    if (ps->cartesian) HIPCHK(hipMemsetAsync(ps->d_first_row + b, 0, 4, nullptr));
     if (drop_suspension(ps, (int)b, nullptr)) return TPAMD_E_HIP;
   }
   HIPCHK(hipStreamSynchronize(nullptr));
-  for (int k = 0; k < n; k++) ps->h_has[ids ? (size_t)ids[k] : (size_t)k] = 0;
+  for (int k = 0; k < n; k++) {
+    ps->h_has[ids ? (size_t)ids[k] : (size_t)k] = 0;
+    ps->h_first_row[ids ? (size_t)ids[k] : (size_t)k] = 0;
+  }
   return 0;
 }
 
@@ -3293,7 +3307,7 @@ void launch_ik_upload(const tpamd_planner_set *ps, IkUploadParams p, int longest
   p.t_q = ps->d_tq; p.t_J = ps->d_tJ;
   p.s_path_end = ps->d_path_end; p.s_vmax = ps->d_vmax; p.s_amax = (double *)S.amax; p.s_vtrans = ps->d_vtrans;
   p.s_vrot = ps->d_vrot; p.s_delta = ps->d_delta; p.s_iv = ps->d_iv;
-  p.s_rows = ps->d_rows; p.s_state = S.path_state; p.s_has = S.has_path;
+  p.s_rows = ps->d_rows; p.s_state = S.path_state; p.s_has = S.has_path; p.s_first_row = ps->d_first_row;
   const unsigned n = (unsigned)p.count;
   hipLaunchKernelGGL(k_pset_ik_rows, dim3((unsigned)(((size_t)longest * D + 255) / 256), n), dim3(256), 0, st, p, D,
                      p.q, p.t_q);
@@ -3305,6 +3319,7 @@ void launch_ik_upload(const tpamd_planner_set *ps, IkUploadParams p, int longest
 void ik_bookkeeping(tpamd_planner_set *ps, int count, const std::vector<int32_t> &id, const int32_t *offsets) {
   for (int k = 0; k < count; k++) {
     ps->h_rows[id[k]] = offsets[k + 1] - offsets[k];
+    ps->h_first_row[id[k]] = 0;
     ps->h_has[id[k]] = 1;
   }
 }
@@ -3406,7 +3421,8 @@ namespace {
 // The call-level checks of the two append_ik_rows entries (before anything changes): a Cartesian
 // set, the arrays, every id in range, listed once and with a table as far as the host knows,
 // offsets from 0 and non-decreasing. Fills id[count], dst[count] (each planner's first new row),
-// *longest (the largest count) and *need (the rows the longest table has after the append).
+// *longest (the largest count) and *need (the slots the longest table takes after the append: its
+// live rows, rows - first_row, plus the new ones).
 int ik_append_args(const tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *offsets, const double *q,
                    const double *J, std::vector<int32_t> *id, std::vector<int32_t> *dst, int *longest, int *need) {
   if (!ps || !ps->cartesian || count < 0 || !offsets || !q || !J) return TPAMD_E_INVALID_ARGUMENT;
@@ -3426,7 +3442,8 @@ int ik_append_args(const tpamd_planner_set *ps, int count, const int32_t *ids, c
     (*id)[k] = (int32_t)b;
     (*dst)[k] = ps->h_rows[b];
     most = std::max(most, rows);
-    rows_after = std::max(rows_after, (long long)ps->h_rows[b] + rows);
+    if ((long long)ps->h_rows[b] + rows > INT32_MAX) return TPAMD_E_UNSUPPORTED;
+    rows_after = std::max(rows_after, (long long)ps->h_rows[b] - ps->h_first_row[b] + rows);
   }
   if (rows_after > (1 << 28)) return TPAMD_E_UNSUPPORTED;
   *longest = (int)most;
@@ -3439,7 +3456,7 @@ void launch_ik_append(const tpamd_planner_set *ps, IkUploadParams p, int longest
   const int D = ps->S.D;
   p.D = D; p.table_stride = ps->table_cap;
   p.t_q = ps->d_tq; p.t_J = ps->d_tJ;
-  p.s_rows = ps->d_rows; p.s_has = ps->S.has_path;
+  p.s_rows = ps->d_rows; p.s_has = ps->S.has_path; p.s_first_row = ps->d_first_row;
   const unsigned n = (unsigned)p.count;
   if (longest > 0) {
     hipLaunchKernelGGL(k_pset_ik_rows, dim3((unsigned)(((size_t)longest * D + 255) / 256), n), dim3(256), 0, st, p, D,
@@ -3518,10 +3535,89 @@ int tpamd_planner_set_download_ik_table(tpamd_planner_set *ps, int planner, int3
   if (!ps || !rows || planner < 0 || planner >= ps->S.B || !ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
   const int R = ps->h_has[planner] ? ps->h_rows[planner] : 0;
   *rows = R;
+  if (R > 0 && ps->h_first_row[planner] > 0) return TPAMD_E_INVALID_ARGUMENT;   // rows from 0 are gone
   if (R == 0 || (!ik_positions && !jacobians)) return 0;
   if (R > capacity) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(ps->e);
   if (order_after_readouts(ps)) return TPAMD_E_HIP;      // a device upload may still be writing
+  const size_t D = ps->S.D, o = (size_t)planner * ps->table_cap;
+  if (ik_positions) HIPCHK(hipMemcpy(ik_positions, ps->d_tq + o * D, (size_t)R * D * 8, hipMemcpyDeviceToHost));
+  if (jacobians) HIPCHK(hipMemcpy(jacobians, ps->d_tJ + o * 6 * D, (size_t)R * 6 * D * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tpamd_planner_set_discard_ik_rows(tpamd_planner_set *ps, int count, const int32_t *ids, const int32_t *keep_from,
+                                      int32_t *first_row_out) {
+  if (!ps || !ps->cartesian || count < 0) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t B = ps->S.B, n = (size_t)count;
+  if (n > B) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<char> seen(B, 0);
+  std::vector<int32_t> id(n), first(n);
+  for (size_t k = 0; k < n; k++) {
+    const long long b = ids ? (long long)ids[k] : (long long)k;
+    if (b < 0 || b >= (long long)B || seen[b]) return TPAMD_E_INVALID_ARGUMENT;
+    seen[b] = 1;
+    if (!ps->h_has[b] || ps->h_rows[b] < 1) return TPAMD_E_INVALID_ARGUMENT;
+    id[k] = (int32_t)b;
+  }
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const PlannerSetState &S = ps->S;
+  // device buffer: [ids][keep_from][shift][first_out]; only first_out comes back
+  IkDiscardParams p{};
+  HostStage s;
+  s.up(&p.ids, id.data(), n);
+  s.up(&p.keep_from, keep_from, n);
+  s.scratch(&p.shift, n);
+  s.down(&p.first_out, first.data(), n);
+  if (ensure_wp_buf(ps, s.bytes())) return TPAMD_E_HIP;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // a device append may still be writing
+  if (s.upload(ps->wp_buf.p, st)) return TPAMD_E_HIP;
+  p.count = count; p.D = S.D; p.table_stride = ps->table_cap; p.cap = ps->cap;
+  p.t_q = ps->d_tq; p.t_J = ps->d_tJ;
+  p.s_rows = ps->d_rows; p.s_has = S.has_path; p.s_state = S.path_state; p.s_count = S.count;
+  p.s_first_row = ps->d_first_row;
+  p.h_time = S.h_time; p.h_s = S.h_s; p.delta = ps->d_delta; p.start_time_ns = S.start_time_ns;
+  hipLaunchKernelGGL(k_pset_discard_begin, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, p);
+  hipLaunchKernelGGL(k_pset_ik_compact, dim3(kCompactSplit, (unsigned)n, 2), dim3(kCompactThreads), 0, st, p);
+  HIPCHK(hipGetLastError());
+  if (s.download(st)) return TPAMD_E_HIP;
+  for (size_t k = 0; k < n; k++) ps->h_first_row[id[k]] = first[k];
+  if (first_row_out) std::memcpy(first_row_out, first.data(), n * 4);
+  return 0;
+}
+
+int tpamd_planner_set_ik_table_info(const tpamd_planner_set *ps, int planner, int32_t *first_row, int32_t *rows,
+                                    int32_t *capacity) {
+  if (!ps || planner < 0 || planner >= ps->S.B || !ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
+  const bool has = ps->h_has[planner] && ps->h_rows[planner] > 0;
+  if (first_row) *first_row = has ? ps->h_first_row[planner] : 0;
+  if (rows) *rows = has ? ps->h_rows[planner] : 0;
+  if (capacity) *capacity = ps->table_cap;
+  return 0;
+}
+
+int tpamd_planner_set_ik_table_device_pointers(const tpamd_planner_set *ps, const double **ik_positions,
+                                               const double **jacobians) {
+  if (!ps || !ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
+  if (ik_positions) *ik_positions = ps->d_tq;
+  if (jacobians) *jacobians = ps->d_tJ;
+  return 0;
+}
+
+int tpamd_planner_set_download_ik_rows(tpamd_planner_set *ps, int planner, int32_t *first_row, int32_t *rows_live,
+                                       double *ik_positions, double *jacobians, int capacity) {
+  if (!ps || !first_row || !rows_live || planner < 0 || planner >= ps->S.B || !ps->cartesian)
+    return TPAMD_E_INVALID_ARGUMENT;
+  const bool has = ps->h_has[planner] && ps->h_rows[planner] > 0;
+  const int R = has ? ps->h_rows[planner] - ps->h_first_row[planner] : 0;
+  *first_row = has ? ps->h_first_row[planner] : 0;
+  *rows_live = R;
+  if (R == 0 || (!ik_positions && !jacobians)) return 0;
+  if (R > capacity) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;      // a device append may still be writing
   const size_t D = ps->S.D, o = (size_t)planner * ps->table_cap;
   if (ik_positions) HIPCHK(hipMemcpy(ik_positions, ps->d_tq + o * D, (size_t)R * D * 8, hipMemcpyDeviceToHost));
   if (jacobians) HIPCHK(hipMemcpy(jacobians, ps->d_tJ + o * 6 * D, (size_t)R * 6 * D * 8, hipMemcpyDeviceToHost));

@@ -5,6 +5,8 @@
 // delta) :671-674). A window is arithmetic on N consecutive rows of that table:
 //   cw_window     which rows (SamplePath :527-542), and whether the table holds them
 //   cw_window_need  the same, and which rows a growing table still lacks (streaming Plan)
+//   cw_window_need_from / cw_discard_floor / cw_compact_*  the same for a table whose consumed
+//                 front rows were discarded, which rows are safe to discard, and the in-place move
 //   cw_rows_at    ComputePathDerivatives :39-68 (forward differences, q'[N-1] = 0, q''[0] =
 //                 q''[N-1] = 0) and ConstraintSetup :551-595 (the 2D joint rows plus two rows
 //                 bounding |(J q')_{1..3}|^2 and |(J q')_{4..6}|^2 with lower = -upper; J q' is
@@ -58,6 +60,69 @@ TPAMD_HD inline int cw_window_need(double path_start, double path_horizon, doubl
   *need_first = rows;
   *need_count = *last + 1 - rows;
   return kCwNeedsRows;
+}
+
+// cw_window_need for a table whose front has been discarded (tpamd_planner_set_discard_ik_rows):
+// the table holds path rows first_row .. rows - 1, row r in slot r - first_row. A well-formed window
+// whose first row lies below first_row is kCwMalformed (need_first = need_count = 0): those rows are
+// gone and cannot be supplied again, since an append only goes behind the last row. Every other
+// answer, and first / last in every case, is cw_window_need's; first_row = 0 is cw_window_need.
+TPAMD_HD inline int cw_window_need_from(double path_start, double path_horizon, double delta, int N, int rows,
+                                        int first_row, int *first, int *last, int *need_first, int *need_count) {
+  const int r = cw_window_need(path_start, path_horizon, delta, N, rows, first, last, need_first, need_count);
+  if (r == kCwMalformed || *first >= first_row) return r;
+  *need_first = *need_count = 0;
+  return kCwMalformed;
+}
+
+// The lowest table row any later Plan of a planner can read: rows below it may be discarded.
+//   * k_plan_begin starts a window at path_start = h_s[offset], offset = clamp(lower_bound(h_time,
+//     start_sec) - 1, 0, count - 1), and reads rows round(path_start / delta) .. + N - 1.
+//   * start_sec is the Plan's start, or a later loop start within the same Plan, and
+//     HandleTimeArguments rejects a start before start_time_. lower_bound is monotone in start_sec,
+//     so offset >= offset(start_time_).
+//   * A window replaces the history from its own offset on (k_plan_append) and starts at the
+//     parameter it found there; the samples below that offset stay. So the offset a later start
+//     finds in a later history is not below the one start_time_ finds now, and h_s there is not
+//     smaller: h_s is non-decreasing.
+//   * round is monotone, so every later window's first row is >= round(h_s[offset(start_time_)] /
+//     delta). A Plan that starts at start_time_ reads exactly that row: the floor is attained.
+//   * A planner that waits for rows (streaming Plan) recomputes its window from the same history
+//     with a loop start >= start_time_: the same floor covers it.
+//   * A new path (path_state 1) plans from parameter 0, and so does a planner without a history
+//     (count 0; the caller passes 0 for a planner without a path): floor 0.
+// h_time / h_s are the planner's window history (count samples), start_time_sec is start_time_ in
+// seconds as k_plan_begin converts it (ns / 1e9).
+TPAMD_HD inline int cw_discard_floor(const double *h_time, const double *h_s, int count, double start_time_sec,
+                                     int path_state, double delta) {
+  if (path_state == 1 || count <= 0 || !(delta > 0.0)) return 0;
+  int lo = 0, hi = count;                       // lower_bound(h_time, start_time_sec)
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (h_time[mid] < start_time_sec) lo = mid + 1; else hi = mid;
+  }
+  int offset = lo - 1;
+  if (offset < 0) offset = 0;
+  if (offset > count - 1) offset = count - 1;
+  const double f = round(h_s[offset] / delta);
+  if (!(f > 0.0)) return 0;
+  return f >= 2147483647.0 ? 2147483647 : (int)f;
+}
+
+// In-place compaction of a table's live rows after a discard (k_pset_ik_compact): n elements move
+// from index e + shift to index e, shift >= 1. The elements are visited in chunks of T = threads *
+// unroll, in ascending order; within a chunk every thread loads its `unroll` elements, the
+// workgroup meets at a barrier, then every thread stores them. Chunk c reads [cT + shift, (c+1)T +
+// shift) and writes [cT, (c+1)T): it writes nothing a later chunk still has to read (those start at
+// (c+1)T + shift) and only places that it or an earlier chunk has read, and the barrier puts all of
+// its loads before its stores. tests/cpp/test_cartesian_discard_window.cc replays this schedule.
+TPAMD_HD inline long long cw_compact_chunks(long long n, int threads, int unroll) {
+  const long long T = (long long)threads * unroll;
+  return (n + T - 1) / T;
+}
+// the destination index of load u (0 .. unroll-1) of thread tid in chunk c; it takes part if < n
+TPAMD_HD inline long long cw_compact_index(long long c, int threads, int unroll, int tid, int u) {
+  return (c * unroll + u) * threads + tid;
 }
 
 // Sample i of a window of N: q points at the sample's table row ([.][D], the next two rows are read

@@ -1589,10 +1589,12 @@ struct PlanParams {
   const double *w_time, *w_s, *w_sd, *w_sdd, *w_q, *w_qd, *w_qdd;   // [B][N](x D)
   const int *w_status, *w_lei;
   // Cartesian planner sets (null / 0 otherwise): the path is an IK table of rows[b] rows, row r at
-  // path parameter r * delta[b]; the window being solved starts at row first[b]
+  // path parameter r * delta[b]; the window being solved starts at slot first[b] = its first row -
+  // first_row[b]
   const double *path_end;          // [B] knots.back() of the Cartesian path (CloseToEnd)
-  const int *rows;                 // [B]
-  int *first;                      // [B]
+  const int *rows;                 // [B] path rows 0 .. rows-1 have been supplied
+  const int *first_row;            // [B] path row held in slot 0 of the table (rows below were discarded)
+  int *first;                      // [B] slot of the window's first row
   int rec_stride;                  // doubles per sample record of the solve; 0: 2D + 2
   // streaming Plan of a Cartesian set (null otherwise: a window that is not resident is an error):
   // a planner whose window the table does not hold yet waits for rows need_first .. + need_count - 1
@@ -1637,10 +1639,11 @@ static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
     // SamplePath of a Cartesian path (timeable_path_cartesian_spline.cc:527-542): the window is a
     // segment of the IK table; a table that does not hold it fails this planner alone
     int first, last;
-    if (!cw_window(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last)) {
+    const int first_row = p.first_row[b];     // rows below it were discarded (0: none)
+    if (!cw_window(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last) || first < first_row) {
       int need_first, need_count;
-      if (p.suspended && cw_window_need(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last,
-                                        &need_first, &need_count) == kCwNeedsRows) {
+      if (p.suspended && cw_window_need_from(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], first_row,
+                                             &first, &last, &need_first, &need_count) == kCwNeedsRows) {
         // streaming: the planner waits for its rows. Everything written so far is recomputed from
         // the unchanged history when the loop is re-entered; the path state is not touched.
         p.status[b] = kPlanNeedsRows;
@@ -1650,10 +1653,12 @@ static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
         p.active[b] = 0;
         return;
       }
+      // (a window that starts below the first resident row is among these: its rows are gone)
       p.status[b] = kPlanInternal;
       p.active[b] = 0;
       return;
     }
+    first -= first_row;                         // path row -> slot
     p.first[b] = first;
   }
   p.path_state[b] = 3;                          // SamplePath: kPathWasSampled

@@ -201,8 +201,8 @@ static __global__ void k_pset_resume(PlannerSetState S, PlanParams p) {
   p.need_count[b] = 0;
   if (!p.suspended[b]) return;
   int first, last, need_first, need_count;
-  if (cw_window_need(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], &first, &last, &need_first,
-                     &need_count) == kCwNeedsRows) {
+  if (cw_window_need_from(p.path_start[b], p.path_horizon[b], p.delta[b], p.N, p.rows[b], p.first_row[b], &first, &last,
+                          &need_first, &need_count) == kCwNeedsRows) {
     p.need_first[b] = need_first;
     p.need_count[b] = need_count;
     return;
@@ -290,16 +290,19 @@ struct IkUploadParams {
   double *t_q, *t_J;
   double *s_path_end, *s_vmax, *s_amax, *s_vtrans, *s_vrot, *s_delta, *s_iv;
   int *s_rows, *s_state, *s_has;
+  int *s_first_row;                     // [B] path row in slot 0 of each table (0 after an upload)
   // append (tpamd_planner_set_append_ik_rows*): not null, and the planner's rows go behind its last
-  // resident row as the DEVICE counts it (s_rows); dst_first[k] is the host's count, the same number
-  // for every planner the kernels accept. null: an upload, rows 0..
+  // resident row as the DEVICE counts it (path row s_rows, slot s_rows - s_first_row); dst_first[k] is
+  // the host's count, the same number for every planner the kernels accept. null: an upload, rows 0..
   const int *dst_first;                 // [count]
 };
 
 // rows of `width` doubles; grid = (ceil(longest table * width / 256), count). An append leaves a
 // planner without a path (its table was rejected at the upload) untouched. A destination row offset
 // moves a planner's run of Jacobians by a multiple of a row, 48 D bytes: for D = 6 that is 288
-// bytes, so the runs k_cartesian_lp<1, 6> reads as double2 stay 16-byte aligned.
+// bytes, so the runs k_cartesian_lp<1, 6> reads as double2 stay 16-byte aligned. A discard
+// (k_pset_ik_compact) moves the rows down by whole rows as well, so every slot offset stays a
+// multiple of a row and this holds after any sequence of discards and appends.
 static __global__ void k_pset_ik_rows(IkUploadParams p, int width, const double *src, double *dst) {
   const int k = blockIdx.y;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -310,9 +313,10 @@ static __global__ void k_pset_ik_rows(IkUploadParams p, int width, const double 
     // the device's own row count is the destination; a planner whose count the host sees differently
     // (its table was rejected at a _device upload) has no path and is skipped, and nothing is ever
     // written past the planner's rows
-    const int b = p.ids[k], have = p.s_rows[b];
-    if (!p.s_has[b] || have != p.dst_first[k] || have + (p.offsets[k + 1] - p.offsets[k]) > p.table_stride) return;
-    row0 += (size_t)have;
+    const int b = p.ids[k], have = p.s_rows[b], live = have - p.s_first_row[b];
+    if (!p.s_has[b] || have != p.dst_first[k] || live < 0 || live + (p.offsets[k + 1] - p.offsets[k]) > p.table_stride)
+      return;
+    row0 += (size_t)live;
   }
   dst[row0 * width + e] = src[(size_t)p.offsets[k] * width + e];
 }
@@ -322,7 +326,9 @@ static __global__ void k_pset_ik_append_scalars(IkUploadParams p) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= p.count) return;
   const int b = p.ids[k];
-  if (!p.s_has[b] || p.s_rows[b] != p.dst_first[k] || p.s_rows[b] + (p.offsets[k + 1] - p.offsets[k]) > p.table_stride) return;
+  const int live = p.s_rows[b] - p.s_first_row[b];
+  if (!p.s_has[b] || p.s_rows[b] != p.dst_first[k] || live < 0 || live + (p.offsets[k + 1] - p.offsets[k]) > p.table_stride)
+    return;
   p.s_rows[b] += p.offsets[k + 1] - p.offsets[k];
 }
 
@@ -333,6 +339,7 @@ static __global__ void k_pset_ik_scalars(IkUploadParams p) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= p.count) return;
   const int b = p.ids[k], D = p.D;
+  p.s_first_row[b] = 0;
   if (!(p.delta[k] > 0.0) || (p.state[k] != 1 && p.state[k] != 2)) {
     p.s_rows[b] = 0;
     p.s_state[b] = 0;
@@ -351,6 +358,99 @@ static __global__ void k_pset_ik_scalars(IkUploadParams p) {
   p.s_rows[b] = p.offsets[k + 1] - p.offsets[k];
   p.s_state[b] = p.state[k];
   p.s_has[b] = 1;
+}
+
+// ---- Cartesian sets: discarding the consumed rows at the front of the listed planners' tables
+// (tpamd_planner_set_discard_ik_rows). k_pset_discard_begin picks each planner's new first resident
+// row, k_pset_ik_compact moves the live rows down to slot 0.
+struct IkDiscardParams {
+  int count, D, table_stride, cap;
+  const int *ids;                       // [count]
+  const int *keep_from;                 // [count] path rows; null: cw_discard_floor of each planner
+  int *shift;                           // [count] out: rows each table moves down by (0: nothing to do)
+  int *first_out;                       // [count] out: the new first resident row
+  double *t_q, *t_J;
+  const int *s_rows, *s_has, *s_state, *s_count;
+  int *s_first_row;
+  const double *h_time, *h_s, *delta;   // the window histories [B][cap], delta [B]
+  const long long *start_time_ns;       // [B] start_time_
+};
+
+// One thread per listed planner. The new first row is keep_from (or the floor) clamped to
+// [first_row, rows - 1]: the last resident row always stays, the streaming chain seeds the IK with
+// it. A planner without a path on the device (its table was rejected at a _device upload) is left
+// as it is.
+static __global__ void k_pset_discard_begin(IkDiscardParams p) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  const int b = p.ids[k];
+  const int old_first = p.s_first_row[b], rows = p.s_rows[b];
+  int keep = old_first;
+  if (p.s_has[b] && rows - old_first >= 1) {
+    keep = p.keep_from ? p.keep_from[k]
+                       : cw_discard_floor(p.h_time + (size_t)b * p.cap, p.h_s + (size_t)b * p.cap, p.s_count[b],
+                                          (double)p.start_time_ns[b] / 1e9, p.s_state[b], p.delta[b]);
+    keep = min(max(keep, old_first), rows - 1);
+  }
+  p.shift[k] = keep - old_first;
+  p.first_out[k] = keep;
+  p.s_first_row[b] = keep;
+}
+
+// The move: rows (new) first_row .. rows - 1 of planner ids[k] from slot `shift` on to slot 0 on, in
+// place; blockIdx.z picks the array (0: q, width D; 1: J, width 6 D). Source and destination
+// overlap whenever shift < live rows, the normal case (a replan consumes a fraction of a window),
+// so the elements are visited in the order of cw_compact_chunks / cw_compact_index
+// (tpamd_cartesian_window.h, with the argument why one barrier per chunk is enough): one workgroup
+// (blockIdx.x == 0) walks the chunks in ascending order, kCompactUnroll loads in flight per thread,
+// all of them complete (vmcnt(0)) before the barrier, stores after it. Where they do not overlap
+// (shift >= live) the chunks are independent and the gridDim.x workgroups share them.
+// V is double2 where the planner's base, the shift and the length keep 16-byte alignment (J rows
+// are 48 D bytes: always; q rows at odd D only for even shifts and lengths), else double.
+constexpr int kCompactThreads = 256, kCompactUnroll = 4, kCompactSplit = 8;
+template <typename V>
+__device__ __forceinline__ void pset_compact_run(V *base, long long n, long long shift, bool overlap) {
+  const long long chunks = cw_compact_chunks(n, kCompactThreads, kCompactUnroll);
+  const long long c0 = overlap ? 0 : blockIdx.x, step = overlap ? 1 : gridDim.x;
+  const int tid = threadIdx.x;
+  static_assert(kCompactUnroll == 4, "the four loads below are written out");
+  for (long long c = c0; c < chunks; c += step) {
+    // written out rather than kept in an array: an indexed array lands in LDS, not in registers
+    const long long e0 = cw_compact_index(c, kCompactThreads, kCompactUnroll, tid, 0);
+    const long long e1 = cw_compact_index(c, kCompactThreads, kCompactUnroll, tid, 1);
+    const long long e2 = cw_compact_index(c, kCompactThreads, kCompactUnroll, tid, 2);
+    const long long e3 = cw_compact_index(c, kCompactThreads, kCompactUnroll, tid, 3);
+    // clamped, not branched: the loads stay in flight together
+    const V v0 = base[(e0 < n ? e0 : n - 1) + shift];
+    const V v1 = base[(e1 < n ? e1 : n - 1) + shift];
+    const V v2 = base[(e2 < n ? e2 : n - 1) + shift];
+    const V v3 = base[(e3 < n ? e3 : n - 1) + shift];
+    if (overlap) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the loads have landed, not merely been issued
+      __syncthreads();
+    }
+    if (e0 < n) base[e0] = v0;
+    if (e1 < n) base[e1] = v1;
+    if (e2 < n) base[e2] = v2;
+    if (e3 < n) base[e3] = v3;
+  }
+}
+static __global__ __launch_bounds__(kCompactThreads) void k_pset_ik_compact(IkDiscardParams p) {
+  const int k = blockIdx.y;
+  const int shift = p.shift[k];
+  if (shift <= 0) return;
+  const int b = p.ids[k];
+  const int live = p.s_rows[b] - p.s_first_row[b];       // rows that stay (first_row is the new one)
+  if (live <= 0 || shift + live > p.table_stride) return;
+  const bool overlap = shift < live;
+  if (overlap && blockIdx.x != 0) return;
+  const int width = blockIdx.z ? 6 * p.D : p.D;
+  double *base = (blockIdx.z ? p.t_J : p.t_q) + (size_t)b * p.table_stride * width;
+  const long long n = (long long)live * width, s = (long long)shift * width;
+  if ((((size_t)base >> 3) | (size_t)n | (size_t)s) & 1)
+    pset_compact_run<double>(base, n, s, overlap);
+  else
+    pset_compact_run<double2>((double2 *)base, n >> 1, s >> 1, overlap);
 }
 
 // summary record per planner (what the mirror's getters need without a trajectory download)

@@ -230,6 +230,8 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table",
     "tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
     "tpamd_planner_set_plan_streaming", "tpamd_planner_set_plan_resume",
+    "tpamd_planner_set_discard_ik_rows", "tpamd_planner_set_ik_table_info",
+    "tpamd_planner_set_download_ik_rows", "tpamd_planner_set_ik_table_device_pointers",
     "tpamd_sample_ik_target_rows_host", "tpamd_sample_ik_target_rows_device",
     "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
     "tpamd_buffer_set_create", "tpamd_buffer_set_destroy", "tpamd_buffer_set_reserve", "tpamd_buffer_set_capacity",
@@ -409,6 +411,13 @@ def load_library():
     L.tpamd_planner_set_append_ik_rows_device.argtypes = [vp, i] + [vp] * 4 + [vp]
     L.tpamd_planner_set_plan_streaming.argtypes = [vp] + [vp] * 6
     L.tpamd_planner_set_plan_resume.argtypes = [vp] + [vp] * 4
+    for name in ("tpamd_planner_set_discard_ik_rows", "tpamd_planner_set_ik_table_info",
+                 "tpamd_planner_set_download_ik_rows", "tpamd_planner_set_ik_table_device_pointers"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_discard_ik_rows.argtypes = [vp, i, vp, vp, vp]
+    L.tpamd_planner_set_ik_table_info.argtypes = [vp, i, vp, vp, vp]
+    L.tpamd_planner_set_download_ik_rows.argtypes = [vp, i, vp, vp, vp, vp, i]
+    L.tpamd_planner_set_ik_table_device_pointers.argtypes = [vp, vp, vp]
     L.tpamd_sample_ik_target_rows_host.argtypes = [vp, i, i] + [vp] * 10
     L.tpamd_sample_ik_target_rows_device.argtypes = [vp, i, i] + [vp] * 10 + [vp]
     L.tpamd_planner_set_create.argtypes = [vp, C.POINTER(_PlannerSetConfig), C.POINTER(vp)]
@@ -1235,6 +1244,44 @@ class PlannerSet:
                    "tpamd_planner_set_download_ik_table")
         return q, J
 
+    def discard_ik_rows(self, keep_from=None, ids=None):
+        """Discard the consumed rows at the front of the listed planners' IK tables (None: all) of a
+        Cartesian set (tpamd_planner_set_discard_ik_rows): planner k keeps path rows from
+        keep_from[k] on; keep_from None: from its safe floor on, the lowest row any later Plan of
+        that planner can read, computed on the device. Returns the new first resident rows
+        [count] int32 numpy. Up: the ids (and keep_from); down: 4 bytes per listed planner."""
+        ida, n = self._ids(ids)
+        keep = None
+        if keep_from is not None:
+            keep = _host(np.broadcast_to(_host(keep_from, np.int32), (n,)), np.int32)
+        out = np.zeros(n, dtype=np.int32)
+        _check(self._lib.tpamd_planner_set_discard_ik_rows(self._handle(), n, _ptr(ida), _ptr(keep), _ptr(out)),
+               "tpamd_planner_set_discard_ik_rows")
+        return out
+
+    def ik_table_info(self, planner):
+        """Host bookkeeping of one planner's IK table (tpamd_planner_set_ik_table_info):
+        (first_row, rows, capacity): the path row in slot 0, the path rows supplied so far (0: no
+        table) and the table rows allocated per planner."""
+        f, r, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(self._lib.tpamd_planner_set_ik_table_info(self._handle(), int(planner), C.byref(f), C.byref(r), C.byref(c)),
+               "tpamd_planner_set_ik_table_info")
+        return int(f.value), int(r.value), int(c.value)
+
+    def download_ik_rows(self, planner):
+        """The live rows of one planner's IK table (tpamd_planner_set_download_ik_rows):
+        (first_row, ik_positions [live][D], jacobians [live][6][D]) numpy, path rows first_row ..
+        first_row + live - 1."""
+        f, R = C.c_int32(0), C.c_int32(0)
+        _check(self._lib.tpamd_planner_set_download_ik_rows(self._handle(), int(planner), C.byref(f), C.byref(R), None,
+                                                            None, 0), "tpamd_planner_set_download_ik_rows")
+        q, J = np.zeros((R.value, self.D)), np.zeros((R.value, 6, self.D))
+        if R.value:
+            _check(self._lib.tpamd_planner_set_download_ik_rows(self._handle(), int(planner), C.byref(f), C.byref(R),
+                                                                _ptr(q), _ptr(J), R.value),
+                   "tpamd_planner_set_download_ik_rows")
+        return int(f.value), q, J
+
     def download_path(self, planner):
         """The resident spline of one planner: (knots [P + 3], control_points [P][D]) numpy; P = 0:
         no path."""
@@ -1325,7 +1372,7 @@ class PlannerSet:
                                                        None), "tpamd_planner_set_plan_resume")
         return self._summary(out), need[0], need[1]
 
-    def plan_streaming(self, start_ns, horizon_ns, ik=None, lookahead_rows=0):
+    def plan_streaming(self, start_ns, horizon_ns, ik=None, lookahead_rows=0, discard=False):
         """Plan with IK tables that grow as TimeableCartesianSplinePath::SamplePath grows them. Returns
         (summary, need_first, need_count) as plan_resume does. Without `ik` this is one
         tpamd_planner_set_plan_streaming call; the caller appends and resumes while need_count > 0.
@@ -1338,13 +1385,19 @@ class PlannerSet:
         seed_rows [waiting][D] is that resident row, its initial value), everything but that first
         row is appended, and the plan resumes. Per-row data stays on the device; the host sends the
         two time arrays and, per round, the row offsets of the waiting planners (ints), and reads the
-        summaries and need_*. Counters of the last call: self.last_stream_stats."""
+        summaries and need_*. Counters of the last call: self.last_stream_stats.
+        discard=True: once the Plan is complete (nobody waits), every planner that has a table
+        discards the rows below its safe floor (discard_ik_rows()), so the tables stop growing with
+        the distance travelled; last_stream_stats gains discard_h2d (the ids, 4 B per planner),
+        discard_d2h (the new first rows, 4 B per planner) and first_row [B]."""
         import torch
         summary, nf, nc = self._plan_streaming(start_ns, horizon_ns)
         h2d, d2h = self.last_plan_bytes()
         stats = dict(suspensions=0, appended_rows=0, h2d=[h2d], d2h=[d2h])
         self.last_stream_stats = stats
         if ik is None:
+            if discard and not (nc > 0).any():
+                self._discard_after_plan(stats)
             return summary, nf, nc
         if getattr(self, "_stream_fit", None) is None:
             raise TpamdError("plan_streaming with an IK needs set_pose_waypoints(..., streaming=True) first")
@@ -1372,7 +1425,17 @@ class PlannerSet:
             h2d, d2h = self.last_plan_bytes()
             stats["h2d"].append(h2d)
             stats["d2h"].append(d2h)
+        if discard:
+            self._discard_after_plan(stats)
         return summary, nf, nc
+
+    def _discard_after_plan(self, stats):
+        has = np.array([b for b in range(self.B) if self.ik_table_info(b)[1] > 0], dtype=np.int32)
+        first = np.zeros(self.B, dtype=np.int32)
+        if has.size:
+            first[has] = self.discard_ik_rows(ids=has)
+        stats["discard_h2d"], stats["discard_d2h"] = 4 * int(has.size), 4 * int(has.size)
+        stats["first_row"] = first
 
     def stop_parameters(self, time_ns, ids=None):
         """GetPathStopParameter(time) on the resident trajectories (tpamd_planner_set_stop_parameters):

@@ -507,9 +507,9 @@ Status PathTimingTrajectorySet::ExtendOnDevice(const std::vector<int32_t> &need_
 int PathTimingTrajectorySet::GetIkTableRows(size_t planner) const {
   int32_t rows = 0;
   if (!init_status_.ok() || !cartesian_ || planner >= num_planners_ ||
-      tpamd_planner_set_download_ik_table(set_, (int)planner, &rows, nullptr, nullptr, 0) != 0)
+      tpamd_planner_set_ik_table_info(set_, (int)planner, nullptr, &rows, nullptr) != 0)
     return -1;
-  return rows;
+  return rows;                // the path rows supplied so far, whether the front ones are still resident or not
 }
 
 Status PathTimingTrajectorySet::GetIkTable(size_t planner, std::vector<double> *ik_positions,
@@ -609,12 +609,36 @@ std::vector<Status> PathTimingTrajectorySet::PlanStatuses() const {
   return result;
 }
 
-std::vector<Status> PathTimingTrajectorySet::PlanStreaming(Time start, Duration time_horizon) {
-  return PlanStreaming(std::vector<Time>(num_planners_, start), std::vector<Duration>(num_planners_, time_horizon));
+std::vector<Status> PathTimingTrajectorySet::PlanStreaming(Time start, Duration time_horizon, bool discard) {
+  return PlanStreaming(std::vector<Time>(num_planners_, start), std::vector<Duration>(num_planners_, time_horizon),
+                       discard);
+}
+
+StatusOr<std::vector<int32_t>> PathTimingTrajectorySet::DiscardIkRows() {
+  if (!init_status_.ok()) return init_status_;
+  if (!cartesian_) return FailedPreconditionError("a joint set has no IK tables (DiscardIkRows)");
+  std::vector<int32_t> first(num_planners_, 0), ids, out;
+  for (size_t b = 0; b < num_planners_; b++) {
+    int32_t rows = 0;
+    if (tpamd_planner_set_ik_table_info(set_, (int)b, nullptr, &rows, nullptr) == 0 && rows > 0) ids.push_back((int32_t)b);
+  }
+  out.resize(ids.size());
+  const int rc = tpamd_planner_set_discard_ik_rows(set_, (int)ids.size(), ids.data(), nullptr, out.data());
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  for (size_t k = 0; k < ids.size(); k++) first[ids[k]] = out[k];
+  return first;
+}
+
+Status PathTimingTrajectorySet::GetIkTableInfo(size_t planner, int32_t *first_row, int32_t *rows,
+                                               int32_t *capacity) const {
+  if (!init_status_.ok()) return init_status_;
+  if (planner >= num_planners_) return InvalidArgumentError("no such planner");
+  const int rc = tpamd_planner_set_ik_table_info(set_, (int)planner, first_row, rows, capacity);
+  return rc == 0 ? OkStatus() : FailedPreconditionError("a joint set has no IK tables");
 }
 
 std::vector<Status> PathTimingTrajectorySet::PlanStreaming(const std::vector<Time> &start,
-                                                           const std::vector<Duration> &time_horizon) {
+                                                           const std::vector<Duration> &time_horizon, bool discard) {
   std::vector<Status> result(num_planners_, OkStatus());
   Status bad = init_status_;
   if (bad.ok() && !cartesian_) bad = FailedPreconditionError("a joint set has no IK tables (Plan)");
@@ -682,6 +706,10 @@ std::vector<Status> PathTimingTrajectorySet::PlanStreaming(const std::vector<Tim
   result = PlanStatuses();
   for (size_t b = 0; b < num_planners_; b++)
     if (!ik_failed[b].ok()) result[b] = ik_failed[b];
+  if (discard && waiting == 0) {            // a completed call: nobody waits for rows
+    const StatusOr<std::vector<int32_t>> first = DiscardIkRows();
+    if (!first.ok()) std::fill(result.begin(), result.end(), first.status());
+  }
   return result;
 }
 

@@ -157,9 +157,11 @@ class PathTimingTrajectorySet {
   // Seconds the last SetCartesianPath(s) / PlanStreaming call spent in the paths' IK and Jacobian
   // callbacks on the host (measurement: tools/cartesian_stream_bench.cc).
   double HostCallbackSecondsOfLastCall() const { return callback_seconds_; }
-  // The planner's resident table (no table: empty).
+  // The planner's resident table (no table: empty). An error once front rows were discarded
+  // (DiscardIkRows): the table no longer starts at row 0; GetIkTableInfo says where it starts.
   Status GetIkTable(size_t planner, std::vector<double> *ik_positions, std::vector<double> *jacobians) const;
-  // Rows of the planner's resident table (no download); -1 on a joint set or a planner out of range.
+  // Path rows supplied to the planner's table so far (no download; discarded front rows count);
+  // -1 on a joint set or a planner out of range.
   int GetIkTableRows(size_t planner) const;
   PathTimingTrajectorySet(const PathTimingTrajectorySet &) = delete;
   PathTimingTrajectorySet &operator=(const PathTimingTrajectorySet &) = delete;
@@ -183,9 +185,19 @@ class PathTimingTrajectorySet {
   // them and tpamd_planner_set_plan_resume goes on. The set then equals one PathTimingTrajectory
   // per planner planning window by window, also with an IK whose result depends on the split into
   // calls.
-  std::vector<Status> PlanStreaming(Time start, Duration time_horizon);
-  std::vector<Status> PlanStreaming(const std::vector<Time> &start, const std::vector<Duration> &time_horizon);
+  // With `discard` every completed call ends with DiscardIkRows(): the tables keep the rows a later
+  // Plan can read and stop growing with the distance travelled. Off by default; the plans are the
+  // same either way, bit for bit.
+  std::vector<Status> PlanStreaming(Time start, Duration time_horizon, bool discard = false);
+  std::vector<Status> PlanStreaming(const std::vector<Time> &start, const std::vector<Duration> &time_horizon,
+                                    bool discard = false);
   int SuspensionsOfLastPlan() const { return suspensions_; }
+  // Discards, for every planner that has a table, the consumed rows below its safe floor
+  // (tpamd_planner_set_discard_ik_rows with keep_from NULL: the lowest row a later Plan can read).
+  // Returns the first resident row of every planner (0 for one without a table).
+  ::tpamd::compat::StatusOr<std::vector<int32_t>> DiscardIkRows();
+  // (first resident row, path rows supplied, table rows allocated per planner) of one planner
+  Status GetIkTableInfo(size_t planner, int32_t *first_row, int32_t *rows, int32_t *capacity) const;
 
   // State after the last Plan, from the summary record (no trajectory download).
   size_t GetNumTimeSamples(size_t planner) const { return (size_t)summary_[planner].num_samples; }
