@@ -523,6 +523,14 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *set, int count, const int3
                                    const int64_t *time_ns, const double *keep_path_until,
                                    const int32_t *waypoint_offsets, const double *waypoints,
                                    double *stop_parameter, int32_t *num_points, int32_t *status);
+/* The same with the PathOptions::rounding radius of the new control polygon as an argument (any
+ * value passes through unchanged, 0 included): bit-identical to a host mirror path whose options
+ * carry that radius. tpamd_planner_set_switch_paths is this entry with rounding 0.2. */
+int tpamd_planner_set_switch_paths_rounded(tpamd_planner_set *set, int count, const int32_t *ids,
+                                           const int64_t *time_ns, const double *keep_path_until,
+                                           const int32_t *waypoint_offsets, const double *waypoints,
+                                           double rounding, double *stop_parameter,
+                                           int32_t *num_points, int32_t *status);
 /* New waypoint paths for `count` planners of a set (ids[count], each listed once, or planners
  * 0..count-1 if ids is NULL), fitted on the device: TimeableJointSplinePath::SetWaypoints
  * (FitSplineToWaypoints, timeable_path_joint_spline.cc:199-206, :252-292) on planner k's waypoints
@@ -559,6 +567,99 @@ int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *set, int count, co
                                            const double *max_acceleration, const double *delta,
                                            const double *initial_velocity, int32_t *num_points,
                                            int32_t *status, void *hip_stream);
+/* Retargets `count` moving planners of a set (ids[count], each listed once, or planners 0..count-1
+ * if ids is NULL) onto new waypoints, abandoning the old path at time_ns[k], in one launch on the
+ * resident trajectories. Per listed planner, the reference's sequence (path_tools.h:44-53):
+ *   1. position and velocity at time_ns[k] on the resident trajectory
+ *      (TrajectoryBuffer::GetPositionAtTime / GetVelocityAtTime: TPAMD_PLAN_FAILED_PRECONDITION
+ *      without a plan, TPAMD_PLAN_OUT_OF_RANGE outside it);
+ *   2. ComputeStoppingPoint(position, velocity, stopping_acceleration[k], rounding) (path_tools.cc
+ *      :25-74; stopping_acceleration [count][D] may be NULL: max_acceleration[k]); a non-positive
+ *      limit gives TPAMD_PLAN_INVALID_ARGUMENT;
+ *   3. TimeableJointSplinePath::SetWaypoints on [position, stopping point, waypoints
+ *      [waypoint_offsets[k] .. waypoint_offsets[k + 1])[D]...] with the PathOptions::rounding radius
+ *      `rounding`; a planner at rest (every |velocity| < 100 epsilon) gets [position, waypoints...].
+ *      No waypoints (W = 0) is allowed: the path is the straight stop, or four copies of position;
+ *   4. planner k then holds what tpamd_planner_set_set_waypoints leaves (path_state 1, kNewPath)
+ *      with max_velocity[k] / max_acceleration[k] [count][D], delta[k] and the velocity of step 1 as
+ *      initial velocity, bit-identical to the host mirror; the next tpamd_planner_set_plan plans it
+ *      as a new path from time_ns[k] on.
+ * Steps 1 and 2 run before anything is written: a planner that fails keeps its state bit for bit.
+ * Per planner: status[k] TPAMD_PLAN_* (the first step that failed), num_points[k] (may be NULL; the
+ * planner's control points after the call, 0 for no path) and, each [count][D] and each may be
+ * NULL, position / velocity / stopping_point (for a planner at rest the position); the rows of a
+ * planner that failed are not written. Call-level errors are those of
+ * tpamd_planner_set_set_waypoints plus a NULL time_ns, and change nothing; a Cartesian set gives
+ * TPAMD_E_UNSUPPORTED. The set's per-planner capacity grows first if max(3 (W + 2) - 2, 4) points
+ * do not fit. Host pointers; synchronises. */
+int tpamd_planner_set_retarget(tpamd_planner_set *set, int count, const int32_t *ids,
+                               const int64_t *time_ns, const int32_t *waypoint_offsets,
+                               const double *waypoints, double rounding, const double *max_velocity,
+                               const double *max_acceleration, const double *delta,
+                               const double *stopping_acceleration, int32_t *num_points,
+                               int32_t *status, double *position, double *velocity,
+                               double *stopping_point);
+/* The same with time_ns, waypoints, max_velocity, max_acceleration, delta, stopping_acceleration,
+ * num_points (required here), status, position, velocity and stopping_point device pointers; ids
+ * and waypoint_offsets stay HOST arrays. Contract and stream ordering exactly as
+ * tpamd_planner_set_set_waypoints_device: enqueues on hip_stream and does not synchronise, except
+ * when the capacity grows or the previous call's staging is still in use. How many control points
+ * a planner ends with is decided on the device: tpamd_planner_set_download_path reads the count
+ * back (after this call has finished) the first time it is asked about such a planner. */
+int tpamd_planner_set_retarget_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                      const int64_t *time_ns, const int32_t *waypoint_offsets,
+                                      const double *waypoints, double rounding,
+                                      const double *max_velocity, const double *max_acceleration,
+                                      const double *delta, const double *stopping_acceleration,
+                                      int32_t *num_points, int32_t *status, double *position,
+                                      double *velocity, double *stopping_point, void *hip_stream);
+/* ---- path_tools.{h,cc} as batch calls -------------------------------------------------------
+ * ComputeStoppingPoint (path_tools.cc:25-74) for `count` rows: position, velocity and
+ * acceleration_limit [count][num_dofs], corner_rounding [count]. point [count][num_dofs] receives
+ * where the robot can come to rest on the straight line along its velocity without exceeding the
+ * limits, shifted further by the corner rounding (CornerOffset, splines/spline_utils.cc:25-45);
+ * position itself if every |velocity| is below 100 epsilon. status [count] is TPAMD_PLAN_OK, or
+ * TPAMD_PLAN_INVALID_ARGUMENT ("Acceleration limits must be strictly positive.") for a row whose
+ * smallest limit is <= 0: its point is not written. Bit-identical to the host mirror
+ * (host/path_tools.h); eigenmath::ScaleDownToLimits is restated as a uniform scaling
+ * (INTEGRATION.md). Call-level errors write nothing: a NULL engine, count < 0, num_dofs < 1, a NULL
+ * array with count > 0 (TPAMD_E_INVALID_ARGUMENT). Host pointers; synchronises. */
+int tpamd_compute_stopping_points_host(tpamd_engine *engine, int count, int num_dofs,
+                                       const double *position, const double *velocity,
+                                       const double *acceleration_limit,
+                                       const double *corner_rounding, double *point,
+                                       int32_t *status);
+/* The same with every array a device pointer. Enqueues one kernel on hip_stream (NULL: the null
+ * stream) and does not synchronise. */
+int tpamd_compute_stopping_points_device(tpamd_engine *engine, int count, int num_dofs,
+                                         const double *position, const double *velocity,
+                                         const double *acceleration_limit,
+                                         const double *corner_rounding, double *point,
+                                         int32_t *status, void *hip_stream);
+/* ProjectPointOnPath (path_tools.h:56-100) for a ragged batch: list k is rows waypoint_offsets[k] ..
+ * waypoint_offsets[k + 1]) of waypoints [rows][num_dofs], projected onto is point[k] [num_dofs].
+ * Per list the fields of ProjectedPointResult: waypoint_index[k] (the closest segment's first
+ * waypoint), distance_to_path[k], line_parameter[k] (limited to 1 above, not below: a negative
+ * value says "before the first waypoint") and projected_point [count][num_dofs]; a single waypoint
+ * gives index 0, parameter 0 and that waypoint. status[k] is TPAMD_PLAN_OK, or
+ * TPAMD_PLAN_INVALID_ARGUMENT ("No waypoints.") for an empty list, whose outputs are not written.
+ * Bit-identical to the host mirror. Call-level errors write nothing: a NULL engine or array,
+ * count < 0, num_dofs < 1, waypoint_offsets[0] != 0 or decreasing offsets
+ * (TPAMD_E_INVALID_ARGUMENT). Host pointers; synchronises. */
+int tpamd_project_points_on_paths_host(tpamd_engine *engine, int count, int num_dofs,
+                                       const int32_t *waypoint_offsets, const double *waypoints,
+                                       const double *point, int32_t *waypoint_index,
+                                       double *distance_to_path, double *line_parameter,
+                                       double *projected_point, int32_t *status);
+/* The same with every array except waypoint_offsets a device pointer. Enqueues on hip_stream and
+ * does not synchronise; the offsets go up on hip_stream first, into the buffer the _device pose-fit
+ * entries use (tpamd_fit_pose_waypoints_device), with the same ordering between such calls. */
+int tpamd_project_points_on_paths_device(tpamd_engine *engine, int count, int num_dofs,
+                                         const int32_t *waypoint_offsets, const double *waypoints,
+                                         const double *point, int32_t *waypoint_index,
+                                         double *distance_to_path, double *line_parameter,
+                                         double *projected_point, int32_t *status,
+                                         void *hip_stream);
 /* ---- Cartesian planner sets --------------------------------------------------------------
  * A set of the second kind: every planner's path is the IK table of a TimeableCartesianSplinePath
  * (path_ik_positions_, one row per multiple of delta_parameter, timeable_path_cartesian_spline.cc

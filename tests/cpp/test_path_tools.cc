@@ -1,0 +1,273 @@
+// CPU test of path_tools (run by tests/test_path_tools_cpu.py; a stand-alone program: it compiles
+// host/path_tools.cc and host/spline_edit.cc itself and needs no engine library):
+// rt_stopping_point and rt_project of csrc/tpamd_retarget.h, compiled here for the host, against the
+// mirror's ComputeStoppingPoint and ProjectPointOnPath, bit for bit, statuses and texts included.
+//
+//   test_path_tools DUMP      seeded cases for every D = 1..16, 70 stopping rows and 70 waypoint
+//                             lists per D, checked and written to DUMP, one line per case with
+//                             every double as a hex float:
+//                               stop D category status rounding pos[D] vel[D] acc[D] out[D]
+//                               proj D W status index point[D] wps[W][D] distance parameter proj[D]
+//                             (status TPAMD_PLAN_*; out / index .. proj are 0 where status is not 0).
+//                             Prints one line per category and "ALL OK".
+//   test_path_tools --eval IN evaluates the cases of IN ("stop D rounding pos vel acc" / "proj D W
+//                             point wps", decimal or hex floats) with mirror and routines and prints
+//                             "stop status out[D]" / "proj status index distance parameter proj[D]"
+//                             per case, after checking that both sides agree.
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../x-edr-trajectory-planning_amd/csrc/tpamd_retarget.h"
+#include "../../x-edr-trajectory-planning_amd/host/path_tools.h"
+
+using namespace trajectory_planning;
+using ::tpamd::compat::StatusCode;
+
+static int g_fail = 0;
+#define CHECK(cond)                                                                          \
+  do {                                                                                       \
+    if (!(cond)) {                                                                           \
+      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
+      g_fail++;                                                                              \
+    }                                                                                        \
+  } while (0)
+
+static unsigned long long g_seed = 20261019ULL;
+static double Rnd() {
+  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
+  return (double)(g_seed >> 11) / 9007199254740992.0;
+}
+static double Uniform(double lo, double hi) { return lo + (hi - lo) * Rnd(); }
+
+static bool SameBits(const double *a, const double *b, size_t n) { return n == 0 || std::memcmp(a, b, n * 8) == 0; }
+static void Put(FILE *f, const double *v, size_t n) {
+  for (size_t i = 0; i < n; i++) std::fprintf(f, " %a", v[i]);
+}
+
+// Both sides on one stopping row; returns the TPAMD_PLAN_* status, the point into out.
+static int StopBothSides(int D, double rounding, const double *pos, const double *vel, const double *acc, double *out) {
+  std::vector<double> rt(D, -7.0);
+  int at_rest = -1;
+  const int st = tpamd::rt_stopping_point(pos, vel, acc, rounding, D, rt.data(), &at_rest);
+  const auto mirror = ComputeStoppingPoint({pos, (size_t)D}, {vel, (size_t)D}, {acc, (size_t)D}, rounding);
+  CHECK(mirror.ok() == (st == tpamd::kSwOk));
+  for (int d = 0; d < D; d++) out[d] = 0.0;
+  if (st != tpamd::kSwOk) {
+    CHECK(st == tpamd::kSwInvalidArgument && mirror.status().code() == StatusCode::kInvalidArgument);
+    CHECK(mirror.status().message() == "Acceleration limits must be strictly positive.");
+    for (int d = 0; d < D; d++) CHECK(rt[d] == -7.0);       // nothing written
+    return st;
+  }
+  CHECK(mirror.value().size() == (size_t)D && SameBits(mirror.value().data(), rt.data(), D));
+  double vabs = 0.0;
+  for (int d = 0; d < D; d++) vabs = std::fmax(vabs, std::fabs(vel[d]));
+  CHECK(at_rest == (vabs < 100 * DBL_EPSILON ? 1 : 0));
+  if (at_rest) CHECK(SameBits(rt.data(), pos, D));
+  // in place: out may be pos
+  std::vector<double> inplace(pos, pos + D);
+  CHECK(tpamd::rt_stopping_point(inplace.data(), vel, acc, rounding, D, inplace.data()) == tpamd::kSwOk);
+  CHECK(SameBits(inplace.data(), rt.data(), D));
+  for (int d = 0; d < D; d++) out[d] = rt[d];
+  return st;
+}
+
+struct Projection {
+  int status = 0, index = 0;
+  double distance = 0.0, parameter = 0.0;
+  std::vector<double> proj;
+};
+
+static Projection ProjectBothSides(int D, int W, const double *point, const double *wps) {
+  Projection r;
+  r.proj.assign(D, 0.0);
+  std::vector<VectorXd> list;
+  for (int i = 0; i < W; i++) list.push_back(VectorXd(wps + (size_t)i * D, D));
+  const VectorXd pt(point, D);
+  const auto mirror = ProjectPointOnPath({list.data(), list.size()}, pt);
+  int index = -1;
+  double t = -1.0, dist = -1.0;
+  std::vector<double> proj(D, -7.0);
+  r.status = tpamd::rt_project(wps, W, D, point, &index, &t, &dist, proj.data());
+  CHECK(mirror.ok() == (r.status == tpamd::kSwOk));
+  if (r.status != tpamd::kSwOk) {
+    CHECK(W == 0 && r.status == tpamd::kSwInvalidArgument && mirror.status().message() == "No waypoints.");
+    return r;
+  }
+  const ProjectedPointResult &m = mirror.value();
+  CHECK(m.waypoint_index == index);
+  CHECK(SameBits(&m.distance_to_path, &dist, 1) && SameBits(&m.line_parameter, &t, 1));
+  CHECK(m.projected_point.size() == (size_t)D && SameBits(m.projected_point.data(), proj.data(), D));
+  // the switch's view (sw_project) is the same projection
+  int sw_index = -1;
+  double sw_t = -1.0;
+  std::vector<double> sw_proj(D, -7.0);
+  CHECK(tpamd::sw_project(wps, W, D, point, &sw_index, &sw_t, sw_proj.data()) == tpamd::kSwOk);
+  CHECK(sw_index == index && SameBits(&sw_t, &t, 1) && SameBits(sw_proj.data(), proj.data(), D));
+  r.index = index; r.distance = dist; r.parameter = t; r.proj = proj;
+  return r;
+}
+
+static std::map<std::string, int> g_seen;
+
+enum { kRandom = 0, kRest, kBelowThreshold, kOneJoint, kSmallestLimitAxis, kEqualLimits, kBadLimit };
+static const char *kCategory[] = {"random", "rest", "below 100 eps", "one moving joint",
+                                  "velocity along the axis of the smallest limit", "equal limits",
+                                  "non-positive limit"};
+
+static void StopCase(FILE *dump, int D, int category, int which_rounding) {
+  std::vector<double> pos(D), vel(D), acc(D), out(D);
+  for (int d = 0; d < D; d++) {
+    pos[d] = Uniform(-1.5, 1.5);
+    vel[d] = Uniform(-2.0, 2.0);
+    acc[d] = Uniform(2.0, 5.0);
+  }
+  const int axis = (int)(Rnd() * D) % D;
+  switch (category) {
+    case kRest: for (int d = 0; d < D; d++) vel[d] = Rnd() < 0.5 ? 0.0 : -0.0; break;
+    case kBelowThreshold: for (int d = 0; d < D; d++) vel[d] = Uniform(-99.0, 99.0) * DBL_EPSILON; break;
+    case kOneJoint:
+      for (int d = 0; d < D; d++) vel[d] = 0.0;
+      vel[axis] = Rnd() < 0.3 ? 101.0 * DBL_EPSILON : Uniform(-2.0, 2.0);     // just above the threshold, too
+      break;
+    case kSmallestLimitAxis:
+      for (int d = 0; d < D; d++) vel[d] = 0.0;
+      acc[axis] = 1.0;
+      vel[axis] = Uniform(0.5, 2.0) * (Rnd() < 0.5 ? -1.0 : 1.0);
+      break;
+    case kEqualLimits: for (int d = 0; d < D; d++) acc[d] = acc[0]; break;
+    case kBadLimit: acc[axis] = Rnd() < 0.5 ? 0.0 : -Uniform(0.1, 3.0); break;
+    default: break;
+  }
+  // rounding 0, the default 0.2, and one larger than |delta| / 4 (|delta| <= |vel|^2 / (2 * 1.0) <= 2 D)
+  const double rounding = which_rounding == 0 ? 0.0 : which_rounding == 1 ? 0.2 : 0.5 * D + Uniform(0.1, 10.0);
+  const int st = StopBothSides(D, rounding, pos.data(), vel.data(), acc.data(), out.data());
+  CHECK((st != tpamd::kSwOk) == (category == kBadLimit));
+  g_seen[std::string("stop: ") + kCategory[category] +
+         (which_rounding == 0 ? ", rounding 0" : which_rounding == 1 ? ", rounding 0.2" : ", large rounding")]++;
+  std::fprintf(dump, "stop %d %d %d %a", D, category, st, rounding);
+  Put(dump, pos.data(), D); Put(dump, vel.data(), D); Put(dump, acc.data(), D); Put(dump, out.data(), D);
+  std::fprintf(dump, "\n");
+}
+
+enum { kPointRandom = 0, kPointOnWaypoint, kPointOnSegment, kPointBeyondEnd, kPointBeforeStart, kRepeatedWaypoints };
+static const char *kProjCategory[] = {"random point", "point on a waypoint", "point on a segment", "point beyond the end",
+                                      "point before the start", "repeated waypoints"};
+
+static void ProjCase(FILE *dump, int D, int W, int category) {
+  std::vector<double> wps((size_t)W * D + 1), point(D);
+  for (size_t i = 0; i < (size_t)W * D; i++) wps[i] = Uniform(-1.5, 1.5);
+  for (int d = 0; d < D; d++) point[d] = Uniform(-2.0, 2.0);
+  if (W >= 2) {
+    const int seg = (int)(Rnd() * (W - 1)) % (W - 1);
+    const double *a = &wps[(size_t)seg * D], *b = a + D, *first = &wps[0], *last = &wps[(size_t)(W - 1) * D];
+    const double t = Rnd();
+    for (int d = 0; d < D; d++) {
+      if (category == kPointOnWaypoint) point[d] = a[d];
+      if (category == kPointOnSegment) point[d] = a[d] + t * (b[d] - a[d]);
+      if (category == kPointBeyondEnd) point[d] = last[d] + (1.0 + t) * (last[d] - last[d - D]);
+      if (category == kPointBeforeStart) point[d] = first[d] - (1.0 + t) * (first[D + d] - first[d]);
+    }
+    if (category == kRepeatedWaypoints)
+      for (int d = 0; d < D; d++) wps[(size_t)(seg + 1) * D + d] = wps[(size_t)seg * D + d];
+  }
+  const Projection r = ProjectBothSides(D, W, point.data(), wps.data());
+  g_seen[W == 0 ? "proj: no waypoints" : W == 1 ? "proj: one waypoint" : std::string("proj: ") + kProjCategory[category]]++;
+  std::fprintf(dump, "proj %d %d %d %d", D, W, r.status, r.index);
+  Put(dump, point.data(), D); Put(dump, wps.data(), (size_t)W * D);
+  Put(dump, &r.distance, 1); Put(dump, &r.parameter, 1); Put(dump, r.proj.data(), D);
+  std::fprintf(dump, "\n");
+}
+
+static int Generate(const char *path) {
+  FILE *dump = std::fopen(path, "w");
+  if (!dump) return 2;
+  for (int D = 1; D <= 16; D++) {
+    // 70 stopping rows: 6 categories x 3 roundings x 3, 12 more random ones, and 4 with a bad limit
+    // spread through the rows
+    int row = 0;
+    for (int rep = 0; rep < 3; rep++)
+      for (int cat = kRandom; cat <= kEqualLimits; cat++)
+        for (int r = 0; r < 3; r++, row++) {
+          StopCase(dump, D, cat, r);
+          if (row % 16 == 5) StopCase(dump, D, kBadLimit, row % 3);
+        }
+    for (int i = 0; i < 12; i++) StopCase(dump, D, kRandom, i % 3);
+    // 70 waypoint lists: none (2), one waypoint (4), then W = 2..6 through the categories
+    ProjCase(dump, D, 0, kPointRandom);
+    for (int i = 0; i < 4; i++) ProjCase(dump, D, 1, kPointRandom);
+    for (int i = 0; i < 64; i++) {
+      if (i == 30) ProjCase(dump, D, 0, kPointRandom);
+      ProjCase(dump, D, 2 + i % 5, i % 6);
+    }
+  }
+  std::fclose(dump);
+  int stops = 0, projs = 0;
+  for (const auto &kv : g_seen) {
+    std::printf("category %s: %d\n", kv.first.c_str(), kv.second);
+    (kv.first[0] == 's' ? stops : projs) += kv.second;
+  }
+  std::printf("stop cases: %d\nproj cases: %d\n", stops, projs);
+  CHECK(stops == 16 * 70 && projs == 16 * 70);
+  return 0;
+}
+
+static int Evaluate(const char *path) {
+  FILE *in = std::fopen(path, "r");
+  if (!in) return 2;
+  char kind[16];
+  while (std::fscanf(in, "%15s", kind) == 1) {
+    int D = 0, W = 0;
+    auto read = [&](std::vector<double> &v, size_t n) {
+      v.resize(n);
+      for (size_t i = 0; i < n; i++)
+        if (std::fscanf(in, "%lf", &v[i]) != 1) return false;
+      return true;
+    };
+    if (!std::strcmp(kind, "stop")) {
+      double rounding = 0.0;
+      std::vector<double> pos, vel, acc;
+      if (std::fscanf(in, "%d %lf", &D, &rounding) != 2 || D < 1 || !read(pos, D) || !read(vel, D) || !read(acc, D)) return 2;
+      std::vector<double> out(D);
+      const int st = StopBothSides(D, rounding, pos.data(), vel.data(), acc.data(), out.data());
+      std::printf("stop %d", st);
+      Put(stdout, out.data(), D);
+    } else if (!std::strcmp(kind, "proj")) {
+      std::vector<double> point, wps;
+      if (std::fscanf(in, "%d %d", &D, &W) != 2 || D < 1 || W < 0 || !read(point, D) || !read(wps, (size_t)W * D)) return 2;
+      wps.push_back(0.0);
+      const Projection r = ProjectBothSides(D, W, point.data(), wps.data());
+      std::printf("proj %d %d", r.status, r.index);
+      Put(stdout, &r.distance, 1); Put(stdout, &r.parameter, 1); Put(stdout, r.proj.data(), D);
+    } else {
+      return 2;
+    }
+    std::printf("\n");
+  }
+  std::fclose(in);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  int rc = 2;
+  if (argc == 3 && !std::strcmp(argv[1], "--eval")) rc = Evaluate(argv[2]);
+  else if (argc == 2) rc = Generate(argv[1]);
+  else std::printf("usage: test_path_tools DUMP | --eval IN\n");
+  // the size checks of the mirror (path_tools.cc:28-33)
+  const std::vector<double> two(2, 1.0), one(1, 1.0);
+  const auto a = ComputeStoppingPoint({two.data(), 2}, {one.data(), 1}, {two.data(), 2}, 0.0);
+  const auto b = ComputeStoppingPoint({two.data(), 2}, {two.data(), 2}, {one.data(), 1}, 0.0);
+  CHECK(!a.ok() && a.status().code() == StatusCode::kInvalidArgument && a.status().message() == "position.size != velocity.size.");
+  CHECK(!b.ok() && b.status().code() == StatusCode::kInvalidArgument && b.status().message() == "position.size != acceleration.size.");
+  if (rc != 0) return rc;
+  if (g_fail) {
+    std::printf("FAILED: %d checks\n", g_fail);
+    return 1;
+  }
+  std::printf("ALL OK\n");
+  return 0;
+}

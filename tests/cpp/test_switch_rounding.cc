@@ -1,0 +1,165 @@
+// GPU test of the path switch's rounding radius (run by tests/test_gpu_switch_rounding.py):
+// PathTimingTrajectorySet::SwitchToWaypointPaths(..., rounding) / tpamd_planner_set_switch_paths_rounded
+// with rounding 0, 0.05 and 1.0 at D = 3 and 7, 70 planners each, against one mirror planner per
+// set member whose path's PathOptions::rounding has that value, running the reference's flow:
+//   GetPathStopParameter(t) -> path->SwitchToWaypointPath(stop, waypoints) ->
+//   path->SetInitialVelocity(GetVelocityAtTime(t)).
+// Statuses and resident splines must equal the mirrors' bit for bit, and the next Plan's states too.
+// The entry without the argument on a twin set equals rounding 0.2.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../../include/tpamd.h"
+#include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory.h"
+#include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
+#include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
+
+using namespace trajectory_planning;
+using tpamd::compat::FromUnixNanos;
+using tpamd::compat::Milliseconds;
+using tpamd::compat::Nanoseconds;
+using tpamd::compat::StatusCode;
+using tpamd::compat::ToUnixNanos;
+
+static int g_fail = 0;
+#define CHECK(cond)                                                                          \
+  do {                                                                                       \
+    if (!(cond)) {                                                                           \
+      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
+      g_fail++;                                                                              \
+    }                                                                                        \
+  } while (0)
+
+static const int64_t kMs = 1000000;
+static unsigned long long g_seed = 1;
+static double Rnd() {
+  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
+  return (double)(g_seed >> 11) / 9007199254740992.0;
+}
+static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
+static bool SameBits(const std::vector<double> &a, const std::vector<double> &b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * 8) == 0);
+}
+static std::vector<double> Flatten(const std::vector<VectorXd> &v) {
+  std::vector<double> r;
+  for (const auto &x : v) r.insert(r.end(), x.begin(), x.end());
+  return r;
+}
+static std::vector<VectorXd> RandomWaypoints(int W, int D) {
+  std::vector<VectorXd> w;
+  for (int i = 0; i < W; i++) {
+    VectorXd v(D);
+    for (int d = 0; d < D; d++) v[d] = 3.0 * Rnd() - 1.5;
+    w.push_back(v);
+  }
+  return w;
+}
+
+static bool SameState(const PathTimingTrajectorySet &set, int b, const PathTimingTrajectory &m,
+                      const TimeableJointSplinePath &path) {
+  PlannedTrajectory t;
+  std::vector<double> k, c;
+  return set.GetNumTimeSamples(b) == m.GetNumTimeSamples() && set.GetTrajectory(b, &t).ok() &&
+         SameBits(t.time, m.GetTime()) && SameBits(t.positions, Flatten(m.GetPositions())) &&
+         SameBits(t.velocities, Flatten(m.GetVelocities())) && set.GetPath(b, &k, &c).ok() &&
+         SameBits(k, path.knots()) && SameBits(c, path.packed_control_points());
+}
+
+// rounding < 0: the entry without the argument, against mirrors with the default radius 0.2
+static void TestRounding(int D, double rounding) {
+  const int B = 70, N = 100;
+  const bool old_entry = rounding < 0;
+  const double radius = old_entry ? 0.2 : rounding;
+  g_seed = 4400 + D;                       // the same planners and waypoints for every radius
+  PathTimingTrajectoryOptions opt;
+  opt.SetNumDofs(D).SetNumPathSamples(N).SetTimeStep(Milliseconds(1));
+  PathTimingTrajectorySet set(opt, B, 7);
+  CHECK(set.status().ok());
+  if (!set.status().ok()) return;
+  std::vector<std::shared_ptr<TimeableJointSplinePath>> paths(B);
+  std::vector<std::unique_ptr<PathTimingTrajectory>> mirrors(B);
+  for (int b = 0; b < B; b++) {
+    const std::vector<VectorXd> wps = RandomWaypoints(RndInt(3, 5), D);
+    paths[b] = std::make_shared<TimeableJointSplinePath>(
+        JointPathOptions().set_num_dofs(D).set_num_path_samples(N).set_delta_parameter(0.005).set_rounding(radius));
+    std::vector<double> vmax(D), amax(D);
+    for (int d = 0; d < D; d++) { vmax[d] = 1.0 + Rnd(); amax[d] = 2.0 + 3.0 * Rnd(); }
+    CHECK(paths[b]->SetMaxJointVelocity({vmax.data(), vmax.size()}).ok());
+    CHECK(paths[b]->SetMaxJointAcceleration({amax.data(), amax.size()}).ok());
+    CHECK(paths[b]->SetWaypoints({wps.data(), wps.size()}).ok());
+    mirrors[b] = std::make_unique<PathTimingTrajectory>(opt);
+    CHECK(mirrors[b]->SetPath(paths[b]).ok());
+  }
+  CHECK(set.SetPaths(paths).ok());
+  const int64_t start = 2000 * kMs, horizon = 400 * kMs, next = start + 120 * kMs;
+  std::vector<PathTimingTrajectory *> batch;
+  for (int b = 0; b < B; b++) batch.push_back(mirrors[b].get());
+  const auto st = set.Plan(FromUnixNanos(start), Nanoseconds(horizon));
+  const auto ms = PathTimingTrajectory::PlanBatch(batch, FromUnixNanos(start), Nanoseconds(horizon));
+  for (int b = 0; b < B; b++) CHECK(st[b].ok() && ms[b].ok() && SameState(set, b, *mirrors[b], *paths[b]));
+  // every planner but each seventh, shuffled, switches at `next`
+  std::vector<size_t> ids;
+  for (int b = 0; b < B; b++)
+    if (b % 7 != 6) ids.push_back(b);
+  for (size_t i = ids.size() - 1; i > 0; i--) std::swap(ids[i], ids[RndInt(0, (int)i)]);
+  std::vector<Time> times(ids.size(), FromUnixNanos(next));
+  std::vector<std::vector<VectorXd>> wps;
+  for (size_t k = 0; k < ids.size(); k++) wps.push_back(RandomWaypoints(RndInt(1, 5), D));
+  const auto got = old_entry ? set.SwitchToWaypointPaths(ids, times, wps) : set.SwitchToWaypointPaths(ids, times, wps, rounding);
+  CHECK(got.size() == ids.size());
+  int switched = 0;
+  std::vector<char> diverged(B, 0);
+  for (size_t k = 0; k < ids.size(); k++) {
+    const int b = (int)ids[k];
+    const auto stop = mirrors[b]->GetPathStopParameter(times[k]);
+    const auto v = mirrors[b]->GetVelocityAtTime(times[k]);
+    StatusCode want = !stop.ok() ? stop.status().code() : !v.ok() ? v.status().code() : StatusCode::kOk;
+    if (want == StatusCode::kOk) {
+      const auto e = paths[b]->SwitchToWaypointPath(*stop, {wps[k].data(), wps[k].size()});
+      want = e.code();
+      if (e.ok()) CHECK(paths[b]->SetInitialVelocity({(*v).data(), (*v).size()}).ok());
+      else diverged[b] = 1;                // the mirror's path state changed anyway
+    }
+    CHECK(got[k].code() == want);
+    if (want != StatusCode::kOk) continue;
+    switched++;
+    std::vector<double> kn, cp;
+    CHECK(set.GetPath(b, &kn, &cp).ok());
+    CHECK(SameBits(kn, paths[b]->knots()) && SameBits(cp, paths[b]->packed_control_points()));
+  }
+  CHECK(switched > (int)ids.size() / 2);
+  const auto st2 = set.Plan(FromUnixNanos(next), Nanoseconds(horizon));
+  const auto ms2 = PathTimingTrajectory::PlanBatch(batch, FromUnixNanos(next), Nanoseconds(horizon));
+  int compared = 0;
+  for (int b = 0; b < B; b++) {
+    if (diverged[b]) continue;
+    CHECK(st2[b].code() == ms2[b].code());
+    // a failed first window leaves the path sampled in the set only (DESIGN.md "Path switch")
+    if (st2[b].code() == StatusCode::kInvalidArgument) continue;
+    CHECK(SameState(set, b, *mirrors[b], *paths[b]));
+    compared++;
+  }
+  CHECK(compared > B / 2);
+  if (old_entry)
+    std::printf("switch without the argument (D %d): %d switches bit-equal to mirrors of rounding 0.2\n", D, switched);
+  else
+    std::printf("switch rounding %g (D %d): %d switches and %d planner states bit-equal to the mirrors\n", rounding, D,
+                switched, compared);
+}
+
+int main() {
+  for (int D : {3, 7}) {
+    for (double r : {0.0, 0.05, 1.0}) TestRounding(D, r);
+    TestRounding(D, -1.0);
+  }
+  if (g_fail) {
+    std::printf("%d FAILURES\n", g_fail);
+    return 1;
+  }
+  std::printf("ALL OK\n");
+  return 0;
+}

@@ -22,6 +22,7 @@
 #include "tpamd_stop.h"
 #include "tpamd_switch.h"
 #include "tpamd_fit.h"
+#include "tpamd_retarget.h"
 #include "tpamd_pose_fit.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 
@@ -2216,6 +2217,9 @@ struct tpamd_planner_set {
   // host copies of S.np and S.has_path: they change only through uploads, switches and resets
   std::vector<int> h_np;
   std::vector<char> h_has;
+  // a device retarget's outcome is known on the device only: h_np holds an upper bound until
+  // refresh_path_counts reads the planner's count back
+  std::vector<char> h_stale;
   DeviceBuffer sw_buf;                  // switch calls: inputs, outputs and the edit's scratch
   PlannerSetState S{};
   PlanParams P{};
@@ -2427,6 +2431,21 @@ int ensure_table_cap(tpamd_planner_set *ps, int need, hipStream_t st) {
   return grow_table(ps, (int)r, st);
 }
 
+// The host copies of np / has_path of a planner that a device retarget touched (h_stale), read
+// back after that call has finished.
+int refresh_path_counts(tpamd_planner_set *ps, int b) {
+  if (!ps->h_stale[b]) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
+  int np = 0, has = 0;
+  HIPCHK(hipMemcpy(&np, ps->S.np + b, 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&has, ps->S.has_path + b, 4, hipMemcpyDeviceToHost));
+  ps->h_np[b] = np;
+  ps->h_has[b] = (char)has;
+  ps->h_stale[b] = 0;
+  return 0;
+}
+
 int largest_points(const tpamd_planner_set *ps) {
   int m = 3;
   for (int v : ps->h_np) m = std::max(m, v);
@@ -2587,6 +2606,7 @@ int upload_paths_common(tpamd_planner_set *ps, int count, const int32_t *ids, co
   for (size_t k = 0; k < n; k++) {
     const size_t b = ids ? (size_t)ids[k] : k;
     ps->h_np[b] = np[k];
+    ps->h_stale[b] = 0;
     ps->h_has[b] = 1;
   }
   return 0;
@@ -2615,6 +2635,7 @@ int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, 
   ps->pcap = (int)P;
   ps->h_np.assign(B, (int)P);
   ps->h_has.assign(B, 0);
+  ps->h_stale.assign(B, 0);
   ps->cartesian = cartesian;
   ps->h_rows.assign(B, 0);
   ps->h_first_row.assign(B, 0);
@@ -2768,6 +2789,7 @@ int tpamd_planner_set_upload_paths_ragged(tpamd_planner_set *ps, int count, cons
 int tpamd_planner_set_download_path(tpamd_planner_set *ps, int planner, int32_t *num_points, double *knots,
                                     double *cps, int capacity) {
   if (!ps || !num_points || planner < 0 || planner >= ps->S.B || ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = refresh_path_counts(ps, planner)) return rc;
   const int P = ps->h_has[planner] ? ps->h_np[planner] : 0;
   *num_points = P;
   if (P == 0 || (!knots && !cps)) return 0;
@@ -3013,10 +3035,10 @@ int tpamd_planner_set_stop_parameters(tpamd_planner_set *ps, int count, const in
 
 extern "C" {
 
-int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
-                                   const double *keep_path_until, const int32_t *waypoint_offsets,
-                                   const double *waypoints, double *stop_parameter, int32_t *num_points,
-                                   int32_t *status) {
+int tpamd_planner_set_switch_paths_rounded(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                                           const double *keep_path_until, const int32_t *waypoint_offsets,
+                                           const double *waypoints, double rounding, double *stop_parameter,
+                                           int32_t *num_points, int32_t *status) {
   if (!ps || count < 0 || !time_ns || !waypoint_offsets || !waypoints || !stop_parameter || !num_points || !status)
     return TPAMD_E_INVALID_ARGUMENT;
   if (ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;     // SwitchToWaypointPath edits a joint spline
@@ -3079,7 +3101,7 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
     if (!launch_fastest_stop((int)D, f, st)) return TPAMD_E_UNSUPPORTED;
   }
   p.Q = count; p.D = (int)D; p.K = S.K; p.pcap = ps->pcap; p.tcap = ps->tcap;
-  p.scr_points = scr_points; p.scr_work = scr_work;
+  p.scr_points = scr_points; p.scr_work = scr_work; p.radius = rounding;
   p.knots = (double *)S.knots; p.cps = ps->d_cp; p.iv = ps->d_iv; p.np = S.np; p.path_state = S.path_state;
   p.has_path = S.has_path; p.initial_plan = S.initial_plan; p.t_first = S.t_first; p.t_count = S.t_count;
   p.t_time = S.t_time; p.t_qd = S.t_qd;
@@ -3088,8 +3110,19 @@ int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32
   rc = s.download(st);
   if (rc) return rc;
   for (size_t k = 0; k < n; k++)
-    if (status[k] == TPAMD_PLAN_OK) ps->h_np[id[k]] = num_points[k];
+    if (status[k] == TPAMD_PLAN_OK) {
+      ps->h_np[id[k]] = num_points[k];
+      ps->h_stale[id[k]] = 0;
+    }
   return 0;
+}
+
+int tpamd_planner_set_switch_paths(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                                   const double *keep_path_until, const int32_t *waypoint_offsets,
+                                   const double *waypoints, double *stop_parameter, int32_t *num_points,
+                                   int32_t *status) {
+  return tpamd_planner_set_switch_paths_rounded(ps, count, ids, time_ns, keep_path_until, waypoint_offsets, waypoints,
+                                                kSwitchRounding, stop_parameter, num_points, status);
 }
 
 }  // extern "C"
@@ -3183,6 +3216,7 @@ void fit_bookkeeping(tpamd_planner_set *ps, int count, const std::vector<int32_t
     const int W = offsets[k + 1] - offsets[k];
     if (W < 1) continue;
     ps->h_np[id[k]] = fit_points(W);
+    ps->h_stale[id[k]] = 0;
     ps->h_has[id[k]] = 1;
   }
 }
@@ -3257,6 +3291,241 @@ int tpamd_planner_set_set_waypoints_device(tpamd_planner_set *ps, int count, con
   launch_set_waypoints(p, st);
   HIPCHK(hipGetLastError());
   fit_bookkeeping(ps, count, id, waypoint_offsets);
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- path_tools batches and the retarget
+namespace {
+
+bool path_tool_offsets_ok(int count, const int32_t *offsets) {
+  if (!offsets || offsets[0] != 0) return false;
+  for (int k = 0; k < count; k++)
+    if (offsets[k + 1] < offsets[k]) return false;
+  return true;
+}
+
+// The call-level checks of the two retarget entries (before anything changes): those of
+// set_waypoints, the times, and TPAMD_E_UNSUPPORTED on a Cartesian set. *need is the largest
+// control-point count a fit of [position, stopping point, waypoints...] can have.
+int retarget_args(const tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                  const int32_t *offsets, const double *waypoints, const double *vmax, const double *amax,
+                  const double *delta, const int32_t *status, std::vector<int32_t> *id, int *need) {
+  if (ps && ps->cartesian) return TPAMD_E_UNSUPPORTED;      // the fit makes a joint spline
+  if (!time_ns) return TPAMD_E_INVALID_ARGUMENT;
+  int fit = 0;
+  const int rc = waypoint_args(ps, count, ids, offsets, waypoints, vmax, amax, delta, status, id, &fit);
+  if (rc) return rc;
+  long long most = 0;
+  for (int k = 0; k < count; k++) most = std::max(most, (long long)offsets[k + 1] - offsets[k]);
+  if (most + 2 > (1 << 22)) return TPAMD_E_UNSUPPORTED;
+  *need = fit_points((int)most + 2);
+  return 0;
+}
+
+RetargetParams retarget_params(const tpamd_planner_set *ps, int count, double rounding) {
+  const PlannerSetState &S = ps->S;
+  RetargetParams p{};
+  p.Q = count; p.D = S.D; p.K = S.K; p.pcap = ps->pcap; p.tcap = ps->tcap; p.rounding = rounding;
+  p.knots = (double *)S.knots; p.cps = ps->d_cp;
+  p.s_vmax = ps->d_vmax; p.s_amax = (double *)S.amax; p.s_delta = ps->d_delta; p.s_iv = ps->d_iv;
+  p.np = S.np; p.path_state = S.path_state; p.has_path = S.has_path;
+  p.initial_plan = S.initial_plan; p.t_first = S.t_first; p.t_count = S.t_count;
+  p.t_time = S.t_time; p.t_q = S.t_q; p.t_qd = S.t_qd;
+  return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_compute_stopping_points_device(tpamd_engine *e, int count, int num_dofs, const double *position,
+                                         const double *velocity, const double *acceleration_limit,
+                                         const double *corner_rounding, double *point, int32_t *status,
+                                         void *hip_stream) {
+  if (!e || count < 0 || num_dofs < 1) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!position || !velocity || !acceleration_limit || !corner_rounding || !point || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  StoppingPointParams p{};
+  p.count = count; p.D = num_dofs;
+  p.position = position; p.velocity = velocity; p.acceleration_limit = acceleration_limit;
+  p.corner_rounding = corner_rounding; p.point = point; p.status = status;
+  launch_stopping_points(p, (hipStream_t)hip_stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_compute_stopping_points_host(tpamd_engine *e, int count, int num_dofs, const double *position,
+                                       const double *velocity, const double *acceleration_limit,
+                                       const double *corner_rounding, double *point, int32_t *status) {
+  if (!e || count < 0 || num_dofs < 1) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!position || !velocity || !acceleration_limit || !corner_rounding || !point || !status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)count, D = (size_t)num_dofs;
+  const double *d_pos, *d_vel, *d_acc, *d_round;
+  double *d_point;
+  int32_t *d_st;
+  HostStage s(/*packed=*/true);
+  s.up(&d_pos, position, n * D);
+  s.up(&d_vel, velocity, n * D);
+  s.up(&d_acc, acceleration_limit, n * D);
+  s.up(&d_round, corner_rounding, n);
+  s.both(&d_point, point, n * D);       // a row with a bad limit keeps its point
+  s.down(&d_st, status, n);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  const int rc = tpamd_compute_stopping_points_device(e, count, num_dofs, d_pos, d_vel, d_acc, d_round, d_point, d_st, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_project_points_on_paths_device(tpamd_engine *e, int count, int num_dofs, const int32_t *waypoint_offsets,
+                                         const double *waypoints, const double *point, int32_t *waypoint_index,
+                                         double *distance_to_path, double *line_parameter, double *projected_point,
+                                         int32_t *status, void *hip_stream) {
+  if (!e || count < 0 || num_dofs < 1 || !path_tool_offsets_ok(count, waypoint_offsets)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!point || !waypoint_index || !distance_to_path || !line_parameter || !projected_point || !status ||
+      (waypoint_offsets[count] > 0 && !waypoints))
+    return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const std::vector<int32_t> ints(waypoint_offsets, waypoint_offsets + count + 1);
+  const int32_t *d = nullptr;
+  if (int rc = stage_pose_ints(e, ints, st, &d)) return rc;
+  ProjectParams p{};
+  p.count = count; p.D = num_dofs;
+  p.offsets = d; p.wps = waypoints; p.point = point;
+  p.waypoint_index = waypoint_index; p.distance = distance_to_path; p.line_parameter = line_parameter;
+  p.projected = projected_point; p.status = status;
+  launch_project_points(p, st);
+  return pose_ints_done(e, st);
+}
+
+int tpamd_project_points_on_paths_host(tpamd_engine *e, int count, int num_dofs, const int32_t *waypoint_offsets,
+                                       const double *waypoints, const double *point, int32_t *waypoint_index,
+                                       double *distance_to_path, double *line_parameter, double *projected_point,
+                                       int32_t *status) {
+  if (!e || count < 0 || num_dofs < 1 || !path_tool_offsets_ok(count, waypoint_offsets)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!point || !waypoint_index || !distance_to_path || !line_parameter || !projected_point || !status ||
+      (waypoint_offsets[count] > 0 && !waypoints))
+    return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)count, D = (size_t)num_dofs, rows = (size_t)waypoint_offsets[count];
+  const double *d_wps, *d_point;
+  int32_t *d_index, *d_st;
+  double *d_dist, *d_t, *d_proj;
+  HostStage s(/*packed=*/true);
+  s.up(&d_wps, waypoints, rows * D);
+  s.up(&d_point, point, n * D);
+  s.both(&d_index, waypoint_index, n);  // an empty list keeps its outputs
+  s.both(&d_dist, distance_to_path, n);
+  s.both(&d_t, line_parameter, n);
+  s.both(&d_proj, projected_point, n * D);
+  s.down(&d_st, status, n);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  const int rc = tpamd_project_points_on_paths_device(e, count, num_dofs, waypoint_offsets, d_wps, d_point, d_index,
+                                                      d_dist, d_t, d_proj, d_st, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_planner_set_retarget(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                               const int32_t *waypoint_offsets, const double *waypoints, double rounding,
+                               const double *max_velocity, const double *max_acceleration, const double *delta,
+                               const double *stopping_acceleration, int32_t *num_points, int32_t *status,
+                               double *position, double *velocity, double *stopping_point) {
+  std::vector<int32_t> id;
+  int need = 0;
+  int rc = retarget_args(ps, count, ids, time_ns, waypoint_offsets, waypoints, max_velocity, max_acceleration, delta,
+                         status, &id, &need);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const size_t n = (size_t)count, D = ps->S.D, rows = (size_t)waypoint_offsets[count];
+  // device buffer: in [time_ns][ids][offsets][waypoints][vmax][amax][delta][stop acc] |
+  // out [num_points][status][position][velocity][stopping point] | scratch
+  RetargetParams p{};
+  std::vector<int32_t> np(n);
+  HostStage s(/*packed=*/true);
+  s.up(&p.time_ns, time_ns, n);
+  s.up(&p.ids, id.data(), n);
+  s.up(&p.offsets, waypoint_offsets, n + 1);
+  s.up(&p.wps, waypoints, rows * D);
+  s.up(&p.vmax, max_velocity, n * D);
+  s.up(&p.amax, max_acceleration, n * D);
+  s.up(&p.delta, delta, n);
+  s.up(&p.stop_acc, stopping_acceleration, n * D);
+  s.down(&p.np_out, np.data(), n);
+  s.down(&p.status_out, status, n);
+  s.both(&p.pos_out, position, n * D);        // a planner that fails keeps its rows
+  s.both(&p.vel_out, velocity, n * D);
+  s.both(&p.stop_out, stopping_point, n * D);
+  s.scratch(&p.scr, (rows + 3 * n) * D);
+  if (ensure_wp_buf(ps, s.bytes())) return TPAMD_E_HIP;
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  rc = ensure_pcap(ps, need, st);
+  if (rc) return rc;
+  p = retarget_params(ps, count, rounding);    // the set's arrays after any growth; upload() adds the staged ones
+  if (s.upload(ps->wp_buf.p, st)) return TPAMD_E_HIP;
+  launch_pset_retarget(p, st);
+  HIPCHK(hipGetLastError());
+  rc = s.download(st);
+  if (rc) return rc;
+  for (size_t k = 0; k < n; k++) {
+    if (num_points) num_points[k] = np[k];
+    if (status[k] != TPAMD_PLAN_OK) continue;
+    ps->h_np[id[k]] = np[k];
+    ps->h_has[id[k]] = 1;
+    ps->h_stale[id[k]] = 0;
+  }
+  return 0;
+}
+
+int tpamd_planner_set_retarget_device(tpamd_planner_set *ps, int count, const int32_t *ids, const int64_t *time_ns,
+                                      const int32_t *waypoint_offsets, const double *waypoints, double rounding,
+                                      const double *max_velocity, const double *max_acceleration, const double *delta,
+                                      const double *stopping_acceleration, int32_t *num_points, int32_t *status,
+                                      double *position, double *velocity, double *stopping_point, void *hip_stream) {
+  std::vector<int32_t> id;
+  int need = 0;
+  int rc = retarget_args(ps, count, ids, time_ns, waypoint_offsets, waypoints, max_velocity, max_acceleration, delta,
+                         status, &id, &need);
+  if (rc) return rc;
+  if (!num_points) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t n = (size_t)count, D = ps->S.D, rows = (size_t)waypoint_offsets[count];
+  // wp_buf: [ids][offsets] (stage_ids_and_offsets) | scratch
+  const size_t ints = align_up(align_up(n * 4, 256) + (n + 1) * 4, 256);
+  if (ensure_wp_buf(ps, ints + (rows + 3 * n) * D * 8)) return TPAMD_E_HIP;
+  if (need > ps->pcap) {         // the growth runs on the null stream, after the device calls in flight
+    if (order_after_readouts(ps)) return TPAMD_E_HIP;
+    rc = ensure_pcap(ps, need, nullptr);
+    if (rc) return rc;
+  }
+  RetargetParams p = retarget_params(ps, count, rounding);
+  if (stage_ids_and_offsets(ps, id, waypoint_offsets, st, &p.ids, &p.offsets)) return TPAMD_E_HIP;
+  p.time_ns = (const long long *)time_ns; p.wps = waypoints; p.vmax = max_velocity; p.amax = max_acceleration;
+  p.delta = delta; p.stop_acc = stopping_acceleration;
+  p.scr = (double *)((char *)ps->wp_buf.p + ints);
+  p.np_out = num_points; p.status_out = status;
+  p.pos_out = position; p.vel_out = velocity; p.stop_out = stopping_point;
+  launch_pset_retarget(p, st);
+  HIPCHK(hipGetLastError());
+  // the outcome stays on the device: the host copies hold an upper bound until they are read back
+  for (size_t k = 0; k < n; k++) {
+    const int W = waypoint_offsets[k + 1] - waypoint_offsets[k];
+    ps->h_np[id[k]] = std::max(ps->h_np[id[k]], fit_points(W + 2));
+    ps->h_stale[id[k]] = 1;
+  }
   return readout_end(ps, st) ? TPAMD_E_HIP : 0;
 }
 

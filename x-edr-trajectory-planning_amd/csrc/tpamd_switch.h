@@ -7,7 +7,8 @@
 //      host mirror restates it: host/timeable_path_joint_spline.cc, host/spline_edit.cc):
 //      TruncateSplineAt (knot insertion, NURBS A5.1), EvalCurve at the stop point,
 //      ProjectPointOnPath, the 1e-3 rule for the projected first waypoint,
-//      PolyLineToControlPoints and ExtendWithControlPoints;
+//      PolyLineToControlPoints (rounding radius SwitchParams::radius: the PathOptions default 0.2,
+//      or the argument of tpamd_planner_set_switch_paths_rounded) and ExtendWithControlPoints;
 //   4. the commit: new knots / control points / count, the velocity as the initial velocity
 //      (SetInitialVelocity) and path_state = 2 (kModifiedPath). A planner whose switch failed
 //      keeps its state bit for bit.
@@ -335,6 +336,7 @@ TPAMD_HD inline int sw_velocity_at_time(const double *time, const double *vel, i
 struct SwitchParams {
   int Q, D, K, pcap, tcap;             // queries; joints; knot / point strides of the set (K = pcap + 3)
   int scr_points, scr_work;            // scratch per query: points (knots: + 3) and work doubles
+  double radius;                       // PathOptions::rounding of the new control polygon
   const int *ids;                      // [Q] planner of query k
   const long long *time_ns;            // [Q] switch time
   const double *keep;                  // [Q] caller's stop parameters, or null: stop_in / stop_status
@@ -390,7 +392,7 @@ static __global__ void __launch_bounds__(64) k_pset_switch(SwitchParams p) {
       for (int i = 0; i < P + 3; i++) sk[i] = kb[i];
       for (int i = 0; i < P * D; i++) sp[i] = cb[i];
       const int w0 = p.offsets[k], W = p.offsets[k + 1] - w0;
-      st = sw_switch_to_waypoint_path(sk, sp, P + 3, P, D, stop, p.wps + (size_t)w0 * D, W, kSwitchRounding, work,
+      st = sw_switch_to_waypoint_path(sk, sp, P + 3, P, D, stop, p.wps + (size_t)w0 * D, W, p.radius, work,
                                       &nk, &npts);
     }
   }

@@ -17,7 +17,7 @@ _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # 
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
             "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
-            "tpamd_pose_fit.hip"]
+            "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -57,7 +57,8 @@ def _compile(target, extra_flags, force, verbose):
     flags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags)
     units = [(os.path.join(objdir, "capi.o"), ["tpamd_capi.hip"]),
              (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"]),
-             (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"])]
+             (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"]),
+             (os.path.join(objdir, "retarget.o"), ["tpamd_retarget.hip"])]
     for d, e in SWEEP_INSTANCES:
         units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
                       ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
@@ -226,6 +227,9 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device",
     "tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
     "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
+    "tpamd_planner_set_switch_paths_rounded", "tpamd_planner_set_retarget", "tpamd_planner_set_retarget_device",
+    "tpamd_compute_stopping_points_host", "tpamd_compute_stopping_points_device",
+    "tpamd_project_points_on_paths_host", "tpamd_project_points_on_paths_device",
     "tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
     "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table",
     "tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
@@ -432,6 +436,18 @@ def load_library():
     L.tpamd_planner_set_switch_paths.argtypes = [vp, i] + [vp] * 8
     L.tpamd_planner_set_set_waypoints.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6
     L.tpamd_planner_set_set_waypoints_device.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6 + [vp]
+    for name in ("tpamd_planner_set_switch_paths_rounded", "tpamd_planner_set_retarget",
+                 "tpamd_planner_set_retarget_device", "tpamd_compute_stopping_points_host",
+                 "tpamd_compute_stopping_points_device", "tpamd_project_points_on_paths_host",
+                 "tpamd_project_points_on_paths_device"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_switch_paths_rounded.argtypes = [vp, i] + [vp] * 5 + [C.c_double] + [vp] * 3
+    L.tpamd_planner_set_retarget.argtypes = [vp, i] + [vp] * 4 + [C.c_double] + [vp] * 9
+    L.tpamd_planner_set_retarget_device.argtypes = [vp, i] + [vp] * 4 + [C.c_double] + [vp] * 9 + [vp]
+    L.tpamd_compute_stopping_points_host.argtypes = [vp, i, i] + [vp] * 6
+    L.tpamd_compute_stopping_points_device.argtypes = [vp, i, i] + [vp] * 6 + [vp]
+    L.tpamd_project_points_on_paths_host.argtypes = [vp, i, i] + [vp] * 8
+    L.tpamd_project_points_on_paths_device.argtypes = [vp, i, i] + [vp] * 8 + [vp]
     L.tpamd_planner_set_last_plan_bytes.restype = None
     L.tpamd_planner_set_last_plan_bytes.argtypes = [vp, vp, vp]
     L.tpamd_planner_set_device_bytes.restype = C.c_size_t
@@ -692,6 +708,93 @@ class Engine:
                 _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"])),
                 "tpamd_fit_pose_waypoints_host")
         out["point_offsets"] = point_offsets
+        return out
+
+    # ------------------------------------------------------------ path_tools
+    def compute_stopping_points(self, position, velocity, acceleration_limit, corner_rounding=0.2, stream=None):
+        """ComputeStoppingPoint for a batch (tpamd_compute_stopping_points_*): position, velocity and
+        acceleration_limit [count][D] float64, corner_rounding [count] (or one number). Returns
+        (point [count][D], status [count] int32): where each robot can come to rest on the straight
+        line along its velocity within the limits, shifted by the corner rounding; a row with a
+        non-positive limit has status INVALID_ARGUMENT and a NaN point. CUDA inputs go through the
+        _device entry on `stream` (default: torch's current stream), which only enqueues, and give
+        CUDA tensors; anything else goes through the host entry, which synchronises, and gives
+        numpy arrays."""
+        import torch
+        if _is_cuda(position):
+            dev = position.device
+            f = lambda x, shape, what: PlannerSet._cuda(x, torch.float64, dev, shape, what)
+            pos = f(position, None, "position")
+            if pos.dim() != 2:
+                raise TpamdError("position has shape %s, expected (count, D)" % (tuple(pos.shape),))
+            n, D = pos.shape
+            vel, acc = f(velocity, (n, D), "velocity"), f(acceleration_limit, (n, D), "acceleration_limit")
+            rnd = f(corner_rounding if hasattr(corner_rounding, "shape") else
+                    torch.full((n,), float(corner_rounding), dtype=torch.float64), (n,), "corner_rounding")
+            point = torch.full((n, D), float("nan"), dtype=torch.float64, device=dev)
+            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            _check(self._lib.tpamd_compute_stopping_points_device(
+                self._h, n, D, _ptr(pos), _ptr(vel), _ptr(acc), _ptr(rnd), _ptr(point), _ptr(status),
+                _stream_ptr(stream)), "tpamd_compute_stopping_points_device")
+            return point, status
+        pos = _host(position, np.float64, what="position")
+        if pos.ndim != 2:
+            raise TpamdError("position has shape %s, expected (count, D)" % (pos.shape,))
+        n, D = pos.shape
+        vel = _host(velocity, np.float64, (n, D), "velocity")
+        acc = _host(acceleration_limit, np.float64, (n, D), "acceleration_limit")
+        rnd = _host(np.broadcast_to(_host(corner_rounding, np.float64), (n,)), np.float64, (n,), "corner_rounding")
+        point, status = np.full((n, D), np.nan), np.full(n, -1, dtype=np.int32)
+        _check(self._lib.tpamd_compute_stopping_points_host(
+            self._h, n, D, _ptr(pos), _ptr(vel), _ptr(acc), _ptr(rnd), _ptr(point), _ptr(status)),
+            "tpamd_compute_stopping_points_host")
+        return point, status
+
+    def project_points_on_paths(self, waypoints, offsets, point, stream=None):
+        """ProjectPointOnPath for a ragged batch (tpamd_project_points_on_paths_*): list k is
+        waypoints[offsets[k]:offsets[k + 1]] ([rows][D] float64), point [count][D]. Returns a dict:
+        waypoint_index, status [count] int32, distance_to_path, line_parameter [count] and
+        projected_point [count][D]; an empty list has status INVALID_ARGUMENT and NaN / -1 outputs.
+        offsets is a host array in both forms. CUDA waypoints go through the _device entry on
+        `stream`, which only enqueues, and give CUDA tensors; anything else goes through the host
+        entry, which synchronises, and gives numpy arrays."""
+        import torch
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        n = off.shape[0] - 1
+        if n < 0:
+            raise TpamdError("waypoint offsets need at least one entry")
+        if _is_cuda(point):
+            dev = point.device
+            f = lambda x, shape, what: PlannerSet._cuda(x, torch.float64, dev, shape, what)
+            pt = f(point, None, "point")
+            if pt.dim() != 2 or pt.shape[0] != n:
+                raise TpamdError("point has shape %s, expected (%d, D)" % (tuple(pt.shape), n))
+            D = pt.shape[1]
+            w = f(waypoints, (int(off[-1]), D), "waypoints")
+            out = dict(waypoint_index=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                       distance_to_path=torch.full((n,), float("nan"), dtype=torch.float64, device=dev),
+                       line_parameter=torch.full((n,), float("nan"), dtype=torch.float64, device=dev),
+                       projected_point=torch.full((n, D), float("nan"), dtype=torch.float64, device=dev),
+                       status=torch.full((n,), -1, dtype=torch.int32, device=dev))
+            _check(self._lib.tpamd_project_points_on_paths_device(
+                self._h, n, D, _ptr(off), w.data_ptr() if w.numel() else None, _ptr(pt), _ptr(out["waypoint_index"]),
+                _ptr(out["distance_to_path"]), _ptr(out["line_parameter"]), _ptr(out["projected_point"]),
+                _ptr(out["status"]), _stream_ptr(stream)), "tpamd_project_points_on_paths_device")
+            return out
+        pt = _host(point, np.float64, what="point")
+        if pt.ndim != 2 or pt.shape[0] != n:
+            raise TpamdError("point has shape %s, expected (%d, D)" % (pt.shape, n))
+        D = pt.shape[1]
+        w = _host(waypoints, np.float64, what="waypoints").reshape(-1, D)
+        if w.shape[0] != off[-1]:
+            raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+        out = dict(waypoint_index=np.full(n, -1, dtype=np.int32), distance_to_path=np.full(n, np.nan),
+                   line_parameter=np.full(n, np.nan), projected_point=np.full((n, D), np.nan),
+                   status=np.full(n, -1, dtype=np.int32))
+        _check(self._lib.tpamd_project_points_on_paths_host(
+            self._h, n, D, _ptr(off), _ptr(w) if w.size else None, _ptr(pt), _ptr(out["waypoint_index"]),
+            _ptr(out["distance_to_path"]), _ptr(out["line_parameter"]), _ptr(out["projected_point"]),
+            _ptr(out["status"])), "tpamd_project_points_on_paths_host")
         return out
 
     def sample_ik_targets(self, fit, delta, row_offsets, stream=None, first_row=None):
@@ -966,7 +1069,7 @@ class PlannerSet:
 
     cartesian=True makes a set of the second kind: every planner's path is the IK table of a
     Cartesian path (set_ik_tables; table_capacity rows per planner to start with, it grows). The
-    joint-spline calls (set_waypoints, set_paths, download_path, switch_paths) fail on such a set,
+    joint-spline calls (set_waypoints, set_paths, download_path, switch_paths, retarget) fail on such a set,
     set_ik_tables / download_ik_table on a joint set; everything else works on both kinds."""
 
     def __init__(self, engine, num_planners, num_dofs, num_samples, num_points=16, time_step_ns=4_000_000,
@@ -1072,6 +1175,64 @@ class PlannerSet:
             self._handle(), n, _ptr(ida), _ptr(off), _ptr(w) if w.size else None, float(rounding), _ptr(vm),
             _ptr(am), _ptr(dl), _ptr(iv), _ptr(num_points), _ptr(status)), "tpamd_planner_set_set_waypoints")
         return torch.from_numpy(status), torch.from_numpy(num_points)
+
+    def retarget(self, time_ns, waypoints, offsets, max_velocity, max_acceleration, delta, ids=None, rounding=0.2,
+                 stopping_acceleration=None, stream=None):
+        """Redirects moving planners onto new waypoints, abandoning the old path at time_ns [count]
+        (tpamd_planner_set_retarget*): per listed planner the position and velocity at that time on
+        the resident trajectory, ComputeStoppingPoint with stopping_acceleration [count][D] (None:
+        max_acceleration), the fit of [position, stopping point, waypoints[offsets[k]:offsets[k + 1]]...]
+        (a planner at rest: without the stopping point; no waypoints is allowed) and the commit of
+        set_waypoints with that velocity as initial velocity. The next plan(time_ns, ...) continues
+        from there. Returns a dict: status, num_points int32 [count], position, velocity,
+        stopping_point [count][D] (NaN rows for a planner that failed: it keeps its state). With a
+        CUDA `waypoints` (or, without waypoints, a CUDA time_ns) every array is taken on its device
+        and the call only enqueues on `stream` (default: torch's current stream); results are CUDA
+        tensors. Otherwise the host entry runs and synchronises; results are CPU tensors."""
+        import torch
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("waypoint offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        D = self.D
+        if _is_cuda(waypoints) or (_is_cuda(time_ns) and int(off[-1]) == 0):
+            dev = waypoints.device if _is_cuda(waypoints) else time_ns.device
+            f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
+            w = f(waypoints, None, "waypoints").reshape(-1, D) if int(off[-1]) else \
+                torch.zeros((0, D), dtype=torch.float64, device=dev)
+            if w.shape[0] != off[-1]:
+                raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+            t = self._cuda(time_ns, torch.int64, dev, (n,), "time_ns")
+            vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
+            dl = f(delta if hasattr(delta, "shape") else torch.full((n,), float(delta), dtype=torch.float64),
+                   (n,), "delta")
+            sa = None if stopping_acceleration is None else f(stopping_acceleration, (n, D), "stopping_acceleration")
+            nan = lambda: torch.full((n, D), float("nan"), dtype=torch.float64, device=dev)
+            out = dict(status=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                       num_points=torch.zeros((n,), dtype=torch.int32, device=dev),
+                       position=nan(), velocity=nan(), stopping_point=nan())
+            _check(self._lib.tpamd_planner_set_retarget_device(
+                self._handle(), n, _ptr(ida), _ptr(t), _ptr(off), w.data_ptr() if w.numel() else None,
+                float(rounding), _ptr(vm), _ptr(am), _ptr(dl), _ptr(sa), _ptr(out["num_points"]), _ptr(out["status"]),
+                _ptr(out["position"]), _ptr(out["velocity"]), _ptr(out["stopping_point"]), _stream_ptr(stream)),
+                "tpamd_planner_set_retarget_device")
+            return out
+        w = _host(waypoints, np.float64, what="waypoints").reshape(-1, D)
+        if w.shape[0] != off[-1]:
+            raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+        t = _host(time_ns, np.int64, (n,), "time_ns")
+        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
+        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
+        dl = _host(np.broadcast_to(_host(delta, np.float64), (n,)), np.float64, (n,), "delta")
+        sa = _host(stopping_acceleration, np.float64, (n, D), "stopping_acceleration")
+        out = dict(status=np.full(n, -1, dtype=np.int32), num_points=np.zeros(n, dtype=np.int32),
+                   position=np.full((n, D), np.nan), velocity=np.full((n, D), np.nan),
+                   stopping_point=np.full((n, D), np.nan))
+        _check(self._lib.tpamd_planner_set_retarget(
+            self._handle(), n, _ptr(ida), _ptr(t), _ptr(off), _ptr(w) if w.size else None, float(rounding), _ptr(vm),
+            _ptr(am), _ptr(dl), _ptr(sa), _ptr(out["num_points"]), _ptr(out["status"]), _ptr(out["position"]),
+            _ptr(out["velocity"]), _ptr(out["stopping_point"])), "tpamd_planner_set_retarget")
+        return {k: torch.from_numpy(v) for k, v in out.items()}
 
     @staticmethod
     def _cuda(x, dtype, device, shape, what):
@@ -1450,9 +1611,10 @@ class PlannerSet:
                                                            _ptr(st)), "tpamd_planner_set_stop_parameters")
         return dict(stop_parameter=torch.from_numpy(s), duration=torch.from_numpy(dur), status=torch.from_numpy(st))
 
-    def switch_paths(self, time_ns, waypoints, offsets, ids=None, keep_path_until=None):
-        """The online path switch (tpamd_planner_set_switch_paths) at time_ns [count] onto
-        waypoints[offsets[k]:offsets[k + 1]]: dict stop_parameter, num_points, status (CPU tensors)."""
+    def switch_paths(self, time_ns, waypoints, offsets, ids=None, keep_path_until=None, rounding=0.2):
+        """The online path switch (tpamd_planner_set_switch_paths_rounded) at time_ns [count] onto
+        waypoints[offsets[k]:offsets[k + 1]], the new control polygon rounded with the PathOptions
+        radius `rounding`: dict stop_parameter, num_points, status (CPU tensors)."""
         import torch
         off = _host(offsets, np.int32).reshape(-1)
         ida, n = self._ids(ids, off.shape[0] - 1)
@@ -1466,9 +1628,9 @@ class PlannerSet:
             w = np.zeros((1, self.D))    # the entry takes a non-NULL array even without rows
         keep = _host(keep_path_until, np.float64, (n,), "keep_path_until")
         s, npts, st = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_switch_paths(self._handle(), n, _ptr(ida), _ptr(t), _ptr(keep), _ptr(off),
-                                                        _ptr(w), _ptr(s), _ptr(npts), _ptr(st)),
-               "tpamd_planner_set_switch_paths")
+        _check(self._lib.tpamd_planner_set_switch_paths_rounded(
+            self._handle(), n, _ptr(ida), _ptr(t), _ptr(keep), _ptr(off), _ptr(w), float(rounding), _ptr(s), _ptr(npts),
+            _ptr(st)), "tpamd_planner_set_switch_paths_rounded")
         return dict(stop_parameter=torch.from_numpy(s), num_points=torch.from_numpy(npts), status=torch.from_numpy(st))
 
     # ------------------------------------------------------------ readouts

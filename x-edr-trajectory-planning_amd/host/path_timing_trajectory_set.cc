@@ -758,6 +758,13 @@ std::vector<StatusOr<double>> PathTimingTrajectorySet::GetPathStopParameters(con
 std::vector<Status> PathTimingTrajectorySet::SwitchToWaypointPaths(const std::vector<size_t> &planners,
                                                                   const std::vector<Time> &time,
                                                                   const std::vector<std::vector<VectorXd>> &waypoints) {
+  return SwitchToWaypointPaths(planners, time, waypoints, 0.2);      // the PathOptions default
+}
+
+std::vector<Status> PathTimingTrajectorySet::SwitchToWaypointPaths(const std::vector<size_t> &planners,
+                                                                  const std::vector<Time> &time,
+                                                                  const std::vector<std::vector<VectorXd>> &waypoints,
+                                                                  double rounding) {
   const size_t n = planners.size(), D = options_.GetNumDofs();
   if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
   if (cartesian_) return std::vector<Status>(n, FailedPreconditionError("a Cartesian set has no joint spline to switch"));
@@ -777,8 +784,8 @@ std::vector<Status> PathTimingTrajectorySet::SwitchToWaypointPaths(const std::ve
     offsets[k + 1] = offsets[k] + (int32_t)waypoints[k].size();
   }
   if (wps.empty()) wps.push_back(0.0);      // the entry takes a non-NULL array even without rows
-  const int rc = tpamd_planner_set_switch_paths(set_, (int)n, ids.data(), t.data(), nullptr, offsets.data(),
-                                                wps.data(), stop.data(), np.data(), st.data());
+  const int rc = tpamd_planner_set_switch_paths_rounded(set_, (int)n, ids.data(), t.data(), nullptr, offsets.data(),
+                                                        wps.data(), rounding, stop.data(), np.data(), st.data());
   if (rc != 0) return std::vector<Status>(n, rc == TPAMD_E_INVALID_ARGUMENT ? InvalidArgumentError(tpamd_error_string(rc))
                                                                            : InternalError(tpamd_error_string(rc)));
   std::vector<Status> result(n, OkStatus());
@@ -848,6 +855,77 @@ std::vector<Status> PathTimingTrajectorySet::SetWaypointPaths(const std::vector<
     if (!result[k].ok()) continue;
     if (st[k] == TPAMD_PLAN_OK) summary_[planners[k]].path_state = 1;      // kNewPath
     else result[k] = InvalidArgumentError("Control point vector empty.");
+  }
+  return result;
+}
+
+std::vector<Status> PathTimingTrajectorySet::RetargetWaypointPaths(
+    const std::vector<size_t> &planners, const std::vector<Time> &time, const std::vector<std::vector<VectorXd>> &waypoints,
+    const std::vector<VectorXd> &max_velocity, const std::vector<VectorXd> &max_acceleration, double rounding,
+    double delta_parameter, const std::vector<VectorXd> &stopping_acceleration) {
+  const size_t n = planners.size(), D = options_.GetNumDofs();
+  if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
+  if (cartesian_) return std::vector<Status>(n, FailedPreconditionError("a Cartesian set takes IK tables"));
+  if (time.size() != n || waypoints.size() != n || max_velocity.size() != n || max_acceleration.size() != n ||
+      (!stopping_acceleration.empty() && stopping_acceleration.size() != n))
+    return std::vector<Status>(n, InvalidArgumentError("one time, one waypoint list and one set of limits per planner"));
+  std::vector<int32_t> ids(n), offsets(n + 1, 0), np(n), st(n);
+  std::vector<int64_t> t(n);
+  std::vector<double> wps, vmax(n * D, 0.0), amax(n * D, 0.0), sacc(n * D, 0.0), dl(n, delta_parameter);
+  std::vector<Status> result(n, OkStatus());
+  std::vector<char> seen(num_planners_, 0);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_ || seen[planners[k]])
+      return std::vector<Status>(n, InvalidArgumentError("no such planner, or listed twice"));
+    seen[planners[k]] = 1;
+    ids[k] = (int32_t)planners[k];
+    t[k] = ::tpamd::compat::ToUnixNanos(time[k]);
+    bool ok = true;
+    for (const VectorXd &w : waypoints[k])
+      if (w.size() != D) ok = false;
+    if (!ok) result[k] = InvalidArgumentError("waypoint has the wrong dimension");
+    if (ok && (max_velocity[k].size() != D || max_acceleration[k].size() != D)) {
+      result[k] = InvalidArgumentError("max_velocity / max_acceleration has the wrong dimension");
+      ok = false;
+    }
+    if (ok && !stopping_acceleration.empty() && stopping_acceleration[k].size() != D) {
+      result[k] = InvalidArgumentError("position.size != acceleration.size.");
+      ok = false;
+    }
+    if (ok) {
+      for (const VectorXd &w : waypoints[k]) wps.insert(wps.end(), w.begin(), w.end());
+      for (size_t d = 0; d < D; d++) {
+        vmax[k * D + d] = max_velocity[k][d];
+        amax[k * D + d] = max_acceleration[k][d];
+        sacc[k * D + d] = stopping_acceleration.empty() ? max_acceleration[k][d] : stopping_acceleration[k][d];
+      }
+    }
+    // a planner that failed a check goes to the device with a zero stopping acceleration: it is
+    // refused there before anything is written and keeps its state
+    offsets[k + 1] = offsets[k] + (ok ? (int32_t)waypoints[k].size() : 0);
+  }
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  retarget_position_.assign(n * D, nan);
+  retarget_velocity_.assign(n * D, nan);
+  retarget_stop_.assign(n * D, nan);
+  if (n == 0) return result;
+  if (wps.empty()) wps.push_back(0.0);
+  const int rc = tpamd_planner_set_retarget(set_, (int)n, ids.data(), t.data(), offsets.data(), wps.data(), rounding,
+                                            vmax.data(), amax.data(), dl.data(), sacc.data(), np.data(), st.data(),
+                                            retarget_position_.data(), retarget_velocity_.data(), retarget_stop_.data());
+  if (rc != 0) return std::vector<Status>(n, rc == TPAMD_E_INVALID_ARGUMENT ? InvalidArgumentError(tpamd_error_string(rc))
+                                                                           : InternalError(tpamd_error_string(rc)));
+  for (size_t k = 0; k < n; k++) {
+    if (!result[k].ok()) continue;
+    switch (st[k]) {
+      case TPAMD_PLAN_OK: summary_[planners[k]].path_state = 1; break;     // kNewPath
+      case TPAMD_PLAN_FAILED_PRECONDITION: result[k] = FailedPreconditionError("No samples."); break;
+      case TPAMD_PLAN_OUT_OF_RANGE: result[k] = OutOfRangeError("retarget time outside the trajectory"); break;
+      case TPAMD_PLAN_INVALID_ARGUMENT:
+        result[k] = InvalidArgumentError("Acceleration limits must be strictly positive.");
+        break;
+      default: result[k] = InternalError("retarget failed"); break;
+    }
   }
   return result;
 }

@@ -227,6 +227,41 @@ class PathTimingTrajectorySet {
   // with the PathOptions default radius (0.2).
   std::vector<Status> SwitchToWaypointPaths(const std::vector<size_t> &planners, const std::vector<Time> &time,
                                             const std::vector<std::vector<VectorXd>> &waypoints);
+  // The same with the new control polygon rounded with `rounding`, as a path whose
+  // PathOptions::rounding has that value switches (tpamd_planner_set_switch_paths_rounded).
+  std::vector<Status> SwitchToWaypointPaths(const std::vector<size_t> &planners, const std::vector<Time> &time,
+                                            const std::vector<std::vector<VectorXd>> &waypoints, double rounding);
+  // Redirects the listed moving planners (each listed once) onto new waypoints, abandoning the old
+  // path at `time[k]`, on the device (tpamd_planner_set_retarget). Planner planners[k] ends in the
+  // state that this sequence on a PathTimingTrajectory `planner` with a fresh path leaves, bit for
+  // bit (path_tools.h:44-53):
+  //   TrajectoryBuffer buffer(...); buffer.InsertTrajectory(planner's time / positions / velocities /
+  //       accelerations);
+  //   position = buffer.GetPositionAtTime(time[k]); velocity = buffer.GetVelocityAtTime(time[k]);
+  //   stop = ComputeStoppingPoint(position, velocity, stopping_acceleration[k], rounding);
+  //   path->SetWaypoints({position, stop, waypoints[k]...})   ({position, waypoints[k]...} if every
+  //       |velocity| is below 100 epsilon: ComputeStoppingPoint then returns the position), with
+  //       PathOptions rounding `rounding` and delta_parameter `delta_parameter`;
+  //   path->SetMaxJointVelocity(max_velocity[k]); path->SetMaxJointAcceleration(max_acceleration[k]);
+  //   path->SetInitialVelocity(velocity); planner.SetPath(path);
+  // so that the next Plan(time[k], horizon) continues from the trajectory at time[k].
+  // stopping_acceleration may be empty (max_acceleration for all); waypoints[k] may be empty (the
+  // path is the straight stop). One status per listed planner: FailedPrecondition without a plan,
+  // OutOfRange for a time outside the trajectory, InvalidArgument for a waypoint or limit of the
+  // wrong dimension or a non-positive stopping acceleration ("Acceleration limits must be strictly
+  // positive."); such a planner keeps its state. A planner out of range or listed twice, or
+  // vectors of the wrong length, fail the call and change nothing.
+  std::vector<Status> RetargetWaypointPaths(const std::vector<size_t> &planners, const std::vector<Time> &time,
+                                            const std::vector<std::vector<VectorXd>> &waypoints,
+                                            const std::vector<VectorXd> &max_velocity,
+                                            const std::vector<VectorXd> &max_acceleration, double rounding = 0.2,
+                                            double delta_parameter = 0.005,
+                                            const std::vector<VectorXd> &stopping_acceleration = {});
+  // Position, velocity and stopping point [listed planners][dofs] of the last RetargetWaypointPaths
+  // call (rows of planners that failed are NaN).
+  const std::vector<double> &LastRetargetPositions() const { return retarget_position_; }
+  const std::vector<double> &LastRetargetVelocities() const { return retarget_velocity_; }
+  const std::vector<double> &LastRetargetStoppingPoints() const { return retarget_stop_; }
   // New waypoint paths for the listed planners (each listed once), fitted on the device
   // (tpamd_planner_set_set_waypoints): planner planners[k] ends in the state that
   //   path->SetWaypoints(waypoints[k]) (with PathOptions rounding `rounding` and delta_parameter
@@ -286,6 +321,7 @@ class PathTimingTrajectorySet {
   std::vector<TimeableCartesianSplinePath *> stream_paths_;
   std::vector<std::shared_ptr<TimeableCartesianSplinePath>> stream_keep_;
   int suspensions_ = 0;
+  std::vector<double> retarget_position_, retarget_velocity_, retarget_stop_;
   double callback_seconds_ = 0.0;
   // streaming through the device chain: the fitted splines of one SetCartesianWaypointPaths call,
   // resident until none of its planners refers to them
