@@ -451,7 +451,8 @@ typedef struct tpamd_planner_set tpamd_planner_set;
 
 typedef struct tpamd_planner_set_config {
   int32_t num_planners, num_dofs, num_samples, num_points;
-  int32_t history_capacity;        /* samples per planner to start with; <= 0: 8 * num_samples */
+  int32_t history_capacity;        /* samples per planner to start with; <= 0: 8 * num_samples. It doubles
+                                    * when a Plan fills it; neither sampling method bounds it */
   int32_t trajectory_capacity;     /* resampled samples per planner to start with; <= 0: 4096 */
   int32_t sampling_method;         /* 0 kUniformlyInTime, 1 kSkipSamplesCloserThanTimeStep */
   int32_t max_planning_iterations; /* PathTimingTrajectoryOptions::GetMaxPlanningIterations */
@@ -1158,7 +1159,9 @@ int tpamd_resample_uniform_host(tpamd_engine *engine, const tpamd_resample_args 
  * the first output is interpolated at start_sec, then every path sample at least
  * 0.95 * time_step (GetMinTimeDeltaToKeep, :893-900) after the last kept one is taken
  * unchanged; the last output gets the end position and zero derivatives. Same argument
- * struct; count[b] = number of outputs of path b (at most num_samples + 1). */
+ * struct; count[b] = number of outputs of path b (at most num_samples + 1). There is no
+ * limit on num_samples: one wave per path walks the time stamps 64 at a time and keeps no
+ * per-sample table (a path's arrays must stay within int indexing, as everywhere). */
 int tpamd_resample_skip_device(tpamd_engine *engine, const tpamd_resample_args *args,
                                void *hip_stream);
 int tpamd_resample_skip_host(tpamd_engine *engine, const tpamd_resample_args *args);

@@ -452,7 +452,6 @@ int configure_kernels_for_device(int device) {
 #undef TPAMD_CONFIGURE_SWEEP
   TPAMD_BIG_LDS(k_cartesian_lp<1, 6>);
   TPAMD_BIG_LDS(k_cartesian_lp<1, 7>);
-  TPAMD_BIG_LDS(k_resample_skip, 128 * 1024);   // int[N], N <= 32768, next to 8 B static
 #undef TPAMD_BIG_LDS
   g_device_configured[device] = true;
   return 0;
@@ -1921,20 +1920,20 @@ int tpamd_query_device(tpamd_engine *e, int B, int N, int K, const double *time,
 
 namespace {
 // The checks of both resample entries after the null structs and num_paths <= 0.
-int resample_args(const tpamd_resample_args *a, bool skip_mode) {
+int resample_args(const tpamd_resample_args *a) {
   if (a->num_samples < 2 || a->num_dofs < 1 || a->max_out < 1 || !(a->time_step > 0))
     return TPAMD_E_INVALID_ARGUMENT;
   if (!a->time || !a->s || !a->sd || !a->sdd || !a->q || !a->qd || !a->qdd ||
       !a->max_acceleration || !a->start_sec || !a->out_time || !a->out_s || !a->out_sd ||
       !a->out_sdd || !a->out_q || !a->out_qd || !a->out_qdd || !a->count)
     return TPAMD_E_INVALID_ARGUMENT;
-  return skip_mode && a->num_samples > 32768 ? TPAMD_E_UNSUPPORTED : 0;
+  return 0;
 }
 
 int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_stream, bool skip_mode) {
   if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
   if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (int rc = resample_args(a, skip_mode)) return rc;
+  if (int rc = resample_args(a)) return rc;
   TPAMD_ON_DEVICE(e);
   ResampleParams p;
   p.B = a->num_paths; p.N = a->num_samples; p.D = a->num_dofs; p.max_out = a->max_out;
@@ -1945,8 +1944,7 @@ int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_str
   p.oq = a->out_q; p.oqd = a->out_qd; p.oqdd = a->out_qdd; p.count = a->count;
   if (skip_mode) {
     p.time_step = 0.95 * a->time_step;   // GetMinTimeDeltaToKeep, path_timing_trajectory.cc:893-900
-    hipLaunchKernelGGL(k_resample_skip, dim3(a->num_paths), dim3(64), (size_t)a->num_samples * 4,
-                       (hipStream_t)hip_stream, p);
+    hipLaunchKernelGGL(k_resample_skip, dim3(a->num_paths), dim3(64), 0, (hipStream_t)hip_stream, p);
   } else {
     hipLaunchKernelGGL(k_resample, dim3((a->max_out + 255) / 256, a->num_paths), dim3(256), 0,
                        (hipStream_t)hip_stream, p);
@@ -1958,7 +1956,7 @@ int resample_device(tpamd_engine *e, const tpamd_resample_args *a, void *hip_str
 int resample_host(tpamd_engine *e, const tpamd_resample_args *a, bool skip_mode) {
   if (!e || !a) return TPAMD_E_INVALID_ARGUMENT;
   if (a->num_paths <= 0) return a->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
-  if (int rc = resample_args(a, skip_mode)) return rc;
+  if (int rc = resample_args(a)) return rc;
   const size_t B = a->num_paths, N = a->num_samples, D = a->num_dofs, M = a->max_out;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = nullptr;
@@ -2922,9 +2920,8 @@ static int planner_set_plan_run(tpamd_planner_set *ps, PlanKind kind, const int6
       rp.time_step = S.time_step_sec;
       hipLaunchKernelGGL(k_resample, dim3((ps->tcap + 255) / 256, (unsigned)B), dim3(256), 0, st, rp);
     } else {
-      if (ps->cap > 32768) return TPAMD_E_UNSUPPORTED;
       rp.time_step = 0.95 * S.time_step_sec;            // GetMinTimeDeltaToKeep :893-900
-      hipLaunchKernelGGL(k_resample_skip, dim3((unsigned)B), dim3(64), (size_t)ps->cap * 4, st, rp);
+      hipLaunchKernelGGL(k_resample_skip, dim3((unsigned)B), dim3(64), 0, st, rp);
     }
     HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
     hipLaunchKernelGGL(k_pset_epilogue, dim3(gb), dim3(128), 0, st, S);

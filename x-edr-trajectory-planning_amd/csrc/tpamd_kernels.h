@@ -1910,14 +1910,77 @@ static __global__ void k_resample(ResampleParams p) {
 }
 
 // ResampleSkippingSamplesCloserThanTimeStep (path_timing_trajectory.cc:785-836), one
-// 64-lane wave per path. The "keep" decision is a sequential recurrence on the last kept
-// time (lane 0 walks the samples and records the kept indices in LDS); the first,
-// interpolated output and the copies of the kept samples are done by all lanes.
+// 64-lane wave per path, any number of samples: no LDS, no scratch memory.
 // p.time_step carries the minimum time delta to keep (0.95 time step, :893-900).
-// Dynamic LDS: int[N].
+//
+// The "keep" decision is a sequential recurrence on the last kept time, and its result must not
+// depend on the times being monotone, so the recurrence itself is evaluated: the wave loads 64
+// times at once, and each trip of the inner loop finds the next kept sample of the chunk with one
+// compare in every lane, a ballot and a read of the found lane -- no memory access. A kept sample
+// takes the run of samples behind it with it whose gap to their predecessor is no less than
+// min_delta: once sample j is kept, last = tm[j], so j + 1 is decided by exactly that gap. A
+// stretch in which nothing is skipped so costs one trip per chunk. Comparison, operand order and
+// fabs are the reference's, so ties and NaNs fall the same way.
+//
+// Lane (n & 63) holds the n-th kept index in a register. A full batch of 64 is copied out when
+// the 65th kept sample turns up (so the batch holding the last output is always copied by the
+// final call, which knows it), the rest after the scan. Output slot 0 is the interpolated start
+// sample, slot 1 + n the n-th kept sample; the last slot carries q[N-1] and zero qd, qdd.
+
+// Copies the kept samples first_n .. first_n + cnt - 1 (lane l holds the index of the l-th) to
+// the output slots 1 + first_n + l below max_out. q, qd, qdd go as one run of cnt * D doubles, so
+// the stores are contiguous across the wave. Every load of up to kResampleSkipGroup * 64 elements
+// is issued before the first store (the compiler cannot move a load over a store that may alias
+// it): a wave waits for memory once per batch at D <= 8. `final`: the batch's last sample is the
+// last output.
+constexpr int kResampleSkipGroup = 8;
+__device__ __forceinline__ void resample_skip_flush(const ResampleParams &p, int b, size_t pb, int N, int lane,
+                                                    int kidx, int first_n, int cnt, bool final) {
+  constexpr int G = kResampleSkipGroup;
+  const int D = p.D;
+  const size_t ob = (size_t)b * p.max_out + 1 + first_n;      // output slot of the batch's first sample
+  const long long room = (long long)p.max_out - 1 - first_n;  // slots of this batch below max_out
+  if (room <= 0) return;
+  const bool mine = lane < cnt && lane < room;
+  double ct = 0.0, cs = 0.0, csd = 0.0, csdd = 0.0;
+  if (mine) {
+    ct = p.time[pb + kidx]; cs = p.s[pb + kidx]; csd = p.sd[pb + kidx]; csdd = p.sdd[pb + kidx];
+  }
+  // element e = lane + 64 r of the run is joint d of batch sample l = e / D (l < 64 as e < 64 D)
+  int l = lane / D, d = lane - l * D;
+  const int ql = 64 / D, qd = 64 - ql * D;
+  for (int r0 = 0; r0 < D; r0 += G) {
+    double vq[G], vqd[G], vqdd[G];
+    size_t to[G];
+    bool on[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      on[g] = false;
+      if (r0 + g < D) {                           // the same in every lane
+        const int src = __shfl(kidx, l, 64);      // by every lane: the source lane must be active
+        on[g] = l < cnt && l < room;
+        if (on[g]) {
+          const bool last_out = final && l == cnt - 1;
+          const size_t from = (pb + (last_out ? N - 1 : src)) * D + d;
+          to[g] = (ob + l) * D + d;
+          vq[g] = p.q[from];
+          vqd[g] = last_out ? 0.0 : p.qd[from];
+          vqdd[g] = last_out ? 0.0 : p.qdd[from];
+        }
+        l += ql; d += qd;
+        if (d >= D) { d -= D; l++; }
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++)
+      if (on[g]) { p.oq[to[g]] = vq[g]; p.oqd[to[g]] = vqd[g]; p.oqdd[to[g]] = vqdd[g]; }
+  }
+  if (mine) {
+    p.ot[ob + lane] = ct; p.os[ob + lane] = cs; p.osd[ob + lane] = csd; p.osdd[ob + lane] = csdd;
+  }
+}
+
 static __global__ void __launch_bounds__(64) k_resample_skip(ResampleParams p) {
-  extern __shared__ int kept[];
-  __shared__ int s_count, s_lower;
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
   const int stride = p.N, D = p.D;
@@ -1926,67 +1989,90 @@ static __global__ void __launch_bounds__(64) k_resample_skip(ResampleParams p) {
     if (lane == 0) p.count[b] = 0;
     return;
   }
-  const double *tm = p.time + (size_t)b * stride;
+  const size_t pb = (size_t)b * stride;
+  const double *tm = p.time + pb;
   const double start = p.start_sec[b];
-  if (lane == 0) {
-    // TimeAtPathSamplesLowerIndex (:686-695): first i in [0, N-2] with tm[i+1] > start, else N-1
-    int lower = N - 1;
-    for (int i = 0; i < N - 1; i++)
-      if (tm[i + 1] > start) { lower = i; break; }
-    s_lower = lower;
-    int n = 0;
-    double last = start;
-    for (int i = lower + 1; i < N; i++) {
-      const double t = tm[i];
-      if (fabs(t - last) < p.time_step) continue;
-      last = t;
-      kept[n++] = i;
+  const double min_delta = p.time_step;
+  // TimeAtPathSamplesLowerIndex (:686-695): first i in [0, N-2] with tm[i+1] > start, else N-1;
+  // the serial scan's comparison, 64 at a time. A replan's start lies well inside the history: the
+  // loads of 512 samples are issued together, so the search waits for memory once per 512.
+  constexpr int G = kResampleSkipGroup;
+  int lower = N - 1;                                 // also "not found yet": a found index is <= N - 2
+  for (int base = 0; base < N - 1 && lower == N - 1; base += 64 * G) {
+    double v[G];
+#pragma unroll
+    for (int k = 0; k < G; k++) {
+      const int i = base + 64 * k + lane;
+      v[k] = i < N - 1 ? tm[i + 1] : start;          // past the end: start > start is false
     }
-    s_count = n + 1;
-    p.count[b] = n + 1;
+#pragma unroll
+    for (int k = 0; k < G; k++) {
+      const unsigned long long above = __ballot(v[k] > start);
+      if (above && lower == N - 1) lower = base + 64 * k + __ffsll(above) - 1;
+    }
   }
-  __syncthreads();
-  const int M = s_count, lower = s_lower;
+  // last = start; for i in lower+1 .. N-1: if (fabs(tm[i] - last) < min_delta) skip; else last = tm[i], keep i
+  int n = 0, kidx = 0;
+  double last = start;
+  int base = lower + 1;
+  double t_next = base + lane < N ? tm[base + lane] : 0.0;
+  for (; base < N; base += 64) {
+    const double t = t_next;
+    const bool valid = base + lane < N;
+    const int nb = base + 64 + lane;
+    t_next = nb < N ? tm[nb] : 0.0;                  // in flight while this chunk is decided
+    // bit j: sample base + j is kept if base + j - 1 is (lane 0's bit is not used)
+    const double t_before = __shfl_up(t, 1, 64);
+    const unsigned long long follows = __ballot(valid && !(fabs(t - t_before) < min_delta));
+    unsigned long long open = ~0ull;                 // lanes after the chunk's latest kept sample
+    for (;;) {
+      const unsigned long long keep = __ballot(valid && !(fabs(t - last) < min_delta)) & open;
+      if (!keep) break;
+      const int j = __ffsll(keep) - 1;
+      const int run = __ffsll(~((follows >> j) >> 1)) - 1;      // kept behind j without a gap; bit 63 is clear
+      last = wave_bcast_const(t, j + run);
+      open = ((~0ull << j) << run) << 1;
+      for (int first = base + j, c = 1 + run; c > 0;) {        // at most two rounds
+        if (n > 0 && (n & 63) == 0) resample_skip_flush(p, b, pb, N, lane, kidx, n - 64, 64, false);
+        const int slot = n & 63, take = c < 64 - slot ? c : 64 - slot;
+        const int rel = lane - slot;
+        if (rel >= 0 && rel < take) kidx = first + rel;
+        n += take; first += take; c -= take;
+      }
+    }
+  }
+  const int M = n + 1;
+  if (lane == 0) p.count[b] = M;
+  if (n > 0) {
+    const int cnt = ((n - 1) & 63) + 1;
+    resample_skip_flush(p, b, pb, N, lane, kidx, n - cnt, cnt, true);
+  }
+  // slot 0: InterpolateAtTime(start) (:709-753)
   const int upper = (N - 1 < lower + 1) ? N - 1 : lower + 1;
   const double at = (fabs(tm[upper] - tm[lower]) < DBL_EPSILON) ? 0.5 : (start - tm[lower]) / (tm[upper] - tm[lower]);
-  const size_t pb = (size_t)b * stride;
-  for (int k = lane; k < M && k < p.max_out; k += 64) {
-    const size_t ob = (size_t)b * p.max_out + k;
-    const bool last_out = (k == M - 1);
-    if (k == 0) {
-      p.ot[ob] = start;
-      p.os[ob] = lerp_ref(at, p.s[pb + lower], p.s[pb + upper]);
-      p.osd[ob] = lerp_ref(at, p.sd[pb + lower], p.sd[pb + upper]);
-      p.osdd[ob] = lerp_ref(at, p.sdd[pb + lower], p.sdd[pb + upper]);
+  const size_t ob = (size_t)b * p.max_out;
+  if (lane == 0) {
+    p.ot[ob] = start;
+    p.os[ob] = lerp_ref(at, p.s[pb + lower], p.s[pb + upper]);
+    p.osd[ob] = lerp_ref(at, p.sd[pb + lower], p.sd[pb + upper]);
+    p.osdd[ob] = lerp_ref(at, p.sdd[pb + lower], p.sdd[pb + upper]);
+  }
+  for (int d = lane; d < D; d += 64) {
+    double vq, vqd, vqdd;
+    if (M == 1) {
+      vq = p.q[(pb + (N - 1)) * D + d];
+      vqd = 0.0; vqdd = 0.0;
     } else {
-      const int i = kept[k - 1];
-      p.ot[ob] = tm[i];
-      p.os[ob] = p.s[pb + i];
-      p.osd[ob] = p.sd[pb + i];
-      p.osdd[ob] = p.sdd[pb + i];
+      const double am = p.amax[(size_t)b * D + d];
+      vq = lerp_ref(at, p.q[(pb + lower) * D + d], p.q[(pb + upper) * D + d]);
+      vqd = lerp_ref(at, p.qd[(pb + lower) * D + d], p.qd[(pb + upper) * D + d]);
+      vqdd = lerp_ref(at, p.qdd[(pb + lower) * D + d], p.qdd[(pb + upper) * D + d]);
+      if (vqdd < -am) vqdd = -am;
+      if (vqdd > am) vqdd = am;
     }
-    for (int d = 0; d < D; d++) {
-      double vq, vqd, vqdd;
-      if (last_out) {
-        vq = p.q[(pb + (N - 1)) * D + d];
-        vqd = 0.0; vqdd = 0.0;
-      } else if (k == 0) {
-        const double am = p.amax[(size_t)b * D + d];
-        vq = lerp_ref(at, p.q[(pb + lower) * D + d], p.q[(pb + upper) * D + d]);
-        vqd = lerp_ref(at, p.qd[(pb + lower) * D + d], p.qd[(pb + upper) * D + d]);
-        vqdd = lerp_ref(at, p.qdd[(pb + lower) * D + d], p.qdd[(pb + upper) * D + d]);
-        if (vqdd < -am) vqdd = -am;
-        if (vqdd > am) vqdd = am;
-      } else {
-        const int i = kept[k - 1];
-        vq = p.q[(pb + i) * D + d];
-        vqd = p.qd[(pb + i) * D + d];
-        vqdd = p.qdd[(pb + i) * D + d];
-      }
-      p.oq[ob * D + d] = vq;
-      p.oqd[ob * D + d] = vqd;
-      p.oqdd[ob * D + d] = vqdd;
-    }
+    p.oq[ob * D + d] = vq;
+    p.oqd[ob * D + d] = vqd;
+    p.oqdd[ob * D + d] = vqdd;
   }
 }
 

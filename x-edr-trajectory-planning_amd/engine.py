@@ -882,7 +882,8 @@ class Engine:
                          skip=False):
         """sol: dict time,s,sd,sdd [B][N], q,qd,qdd [B][N][D], status. out: dict out_time..
         [B][max_out], out_q.. [B][max_out][D], count [B] int32. skip=True: the
-        kSkipSamplesCloserThanTimeStep method instead of the uniform one."""
+        kSkipSamplesCloserThanTimeStep method instead of the uniform one (any N: the kernel
+        keeps no per-sample table; count reports every output, slots below max_out are written)."""
         B, N, D = sol["q"].shape
         max_out = out["out_time"].shape[1]
         args = _ResampleArgs(
