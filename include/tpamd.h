@@ -391,6 +391,7 @@ int tpamd_sample_ik_target_rows_device(tpamd_engine *engine, int num_paths, int 
 #define TPAMD_PLAN_DEADLINE_EXCEEDED 5   /* planning-loop limit (:655-658) */
 #define TPAMD_PLAN_NOT_FOUND 6           /* stopping trajectories: no safe stop (trajectory_buffer.cc:333-349) */
 #define TPAMD_PLAN_NEEDS_ROWS 7          /* Cartesian set, streaming Plan: the next window is not resident yet */
+#define TPAMD_PLAN_RESOURCE_EXHAUSTED 8  /* tpamd_planner_set_plan_device: the history or trajectory buffer is full */
 #define TPAMD_PLAN_MORE 100              /* history_capacity exhausted: call again with more room */
 
 typedef struct tpamd_plan_args {
@@ -840,6 +841,65 @@ int tpamd_planner_set_reset(tpamd_planner_set *set, int count, const int32_t *id
  * summary [B] (host, may be NULL) receives one record per planner, status included. */
 int tpamd_planner_set_plan(tpamd_planner_set *set, const int64_t *start_ns, const int64_t *horizon_ns,
                            tpamd_planner_summary *summary);
+/* Capacity ahead of time. tpamd_planner_set_capacity: samples per planner the history and the
+ * trajectory buffers hold now (either pointer may be NULL; no device access).
+ * tpamd_planner_set_reserve grows them to at least history_capacity / trajectory_capacity samples
+ * per planner, exactly as a synchronous Plan grows them when a planner needs room: it never
+ * shrinks, a value <= the current size (0 included) leaves that buffer alone, and every planner's
+ * state is kept bit for bit. It also sizes the engine's workspace for this set's windows, so that
+ * a tpamd_planner_set_plan_device that follows allocates nothing. Host call; synchronises when
+ * anything grows. Values above 2^28 give TPAMD_E_UNSUPPORTED. */
+int tpamd_planner_set_capacity(const tpamd_planner_set *set, int32_t *history, int32_t *trajectory);
+int tpamd_planner_set_reserve(tpamd_planner_set *set, int history_capacity, int trajectory_capacity);
+
+typedef struct tpamd_plan_device_info {   /* 32 bytes, written once per call, device memory */
+  int32_t num_ok, num_failed;      /* planners with status TPAMD_PLAN_OK / any other status */
+  int32_t num_exhausted;           /* of the failed: TPAMD_PLAN_RESOURCE_EXHAUSTED */
+  int32_t needed_history;          /* largest count + N a stopped planner asked for, 0 if none */
+  int32_t needed_trajectory;       /* largest resample count that did not fit, 0 if none */
+  int32_t max_windows_solved;      /* largest `windows` of any planner */
+  int32_t reserved[2];
+} tpamd_plan_device_info;
+/* tpamd_planner_set_plan, enqueued only: start_ns / horizon_ns [B] are DEVICE arrays, summary [B]
+ * (may be NULL) and info (may be NULL) are device memory, all of them valid until hip_stream (NULL:
+ * the null stream) has run the call. Nothing is copied to the host, nothing blocks, and
+ * tpamd_planner_set_last_plan_bytes reports 0 / 0 afterwards.
+ * The host cannot ask whether a planner still loops, so the window loop is bounded by the caller:
+ * exactly max_windows (>= 1) window iterations are enqueued, and every planner is left as
+ * tpamd_planner_set_plan leaves it on a set whose max_planning_iterations is
+ * min(config value, max_windows - 1) -- path state, history, planner scalars, resident trajectory,
+ * status and summary record, bit for bit. A planner that still loops in the last iteration gets
+ * TPAMD_PLAN_DEADLINE_EXCEEDED as there (:655-658); planners that do not loop take no part in an
+ * iteration (the solver skips their paths), so a max_windows larger than needed costs the launches
+ * of the empty iterations and nothing else.
+ * Nothing is allocated or grown by the call; a shortage is decided per planner on the device:
+ *   * a looping planner whose history has no room for one more window (history_count +
+ *     num_samples > history capacity) stops looping with TPAMD_PLAN_RESOURCE_EXHAUSTED and, like
+ *     any planner whose loop ended in an error, is neither resampled nor finished;
+ *   * a planner whose resampled trajectory exceeds the trajectory capacity gets
+ *     TPAMD_PLAN_RESOURCE_EXHAUSTED and an EMPTY resident trajectory (num_samples 0: a truncated
+ *     trajectory does not end at rest and must never be read out); its scalars are those of a
+ *     plan without samples, so its next Plan fails with TPAMD_PLAN_FAILED_PRECONDITION.
+ * No array is written out of bounds and no other planner is affected. info->needed_history /
+ * needed_trajectory are what tpamd_planner_set_reserve would have needed; the recovery is
+ * reserve, then tpamd_planner_set_reset and a new path (or a retarget) for those planners.
+ * Call tpamd_planner_set_reserve once before the first call (a Plan that ran before has sized the
+ * workspace as well): otherwise the first call allocates the engine's workspace and may block.
+ * Joint sets and Cartesian sets with resident tables; on a Cartesian set a window that is not
+ * resident gives that planner TPAMD_PLAN_INTERNAL as in tpamd_planner_set_plan, and suspensions
+ * left by a streaming Plan are dropped. Streaming needs the host for rows and has no _device entry.
+ * Stream ordering, as for tpamd_planner_set_set_waypoints_device: the call starts after the set's
+ * last change and after the device readouts in flight; later null-stream calls on the set (every
+ * host entry) and later device readouts on any stream wait for it. The engine's workspace is busy
+ * until the call has run: any later solve on the same engine, for this set or another, on any
+ * stream, is ordered behind it by the library. The caller synchronises only to read summary / info
+ * or its own outputs. Not for hipGraph capture.
+ * Call-level errors change nothing: a NULL set / start_ns / horizon_ns, max_windows < 1
+ * (TPAMD_E_INVALID_ARGUMENT). */
+int tpamd_planner_set_plan_device(tpamd_planner_set *set, const int64_t *start_ns,
+                                  const int64_t *horizon_ns, int max_windows,
+                                  tpamd_planner_summary *summary, tpamd_plan_device_info *info,
+                                  void *hip_stream);
 /* The trajectory of one planner after its last Plan: samples first .. first + count - 1 of
  * GetTime / GetPathParameters / ...Derivatives [count] and GetPositions / GetVelocities /
  * GetAccelerations [count][D] into host arrays (any may be NULL). */
@@ -929,7 +989,8 @@ int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *set, int count
                                                double time_step, int32_t *status, int32_t *keep,
                                                int64_t *offsets, int64_t capacity, double *time,
                                                double *q, double *qd, double *qdd, void *hip_stream);
-/* Bytes the last tpamd_planner_set_plan call moved over PCIe (host to device, device to host). */
+/* Bytes the last tpamd_planner_set_plan call moved over PCIe (host to device, device to host);
+ * 0 / 0 after tpamd_planner_set_plan_device. */
 void tpamd_planner_set_last_plan_bytes(const tpamd_planner_set *set, size_t *host_to_device,
                                        size_t *device_to_host);
 /* Device memory the set holds: its state, and the staging of the switch and the host readouts,

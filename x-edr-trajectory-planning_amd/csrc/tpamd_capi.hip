@@ -219,6 +219,10 @@ struct tpamd_engine {
   hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_sweep[2] = {nullptr, nullptr},
              ev_call[2] = {nullptr, nullptr};
   DeviceBuffer ws_spare;       // the workspace of the slot not in use
+  // tpamd_planner_set_plan_device leaves solves in flight on the caller's stream when it returns:
+  // ev_async is recorded behind them, and every later user of the workspace (SlotGuard) waits for it
+  hipEvent_t ev_async = nullptr;
+  bool async_pending = false;
   int slot = 0;                // workspace slot e->ws_buf currently refers to
   // Concurrent groups (tpamd_time_joint_groups_*): each lane is a stream of the engine with a
   // workspace of its own; the groups of one call are spread over the lanes and run side by side.
@@ -342,6 +346,8 @@ struct SlotGuard {
   SlotGuard(tpamd_engine *e_, hipStream_t st_, bool record_after = true, bool enable = true)
       : e(e_), st(st_), slot(e_->slot),
         on(enable && !e_->in_lane && e_->aux != nullptr && !stream_is_capturing(st_)) {
+    // an enqueued-only Plan (tpamd_planner_set_plan_device) may still be using the workspace
+    if (e->async_pending && !stream_is_capturing(st)) (void)hipStreamWaitEvent(st, e->ev_async, 0);
     if (!on) return;
     (void)hipStreamWaitEvent(st, e->ev_front[slot], 0);
     (void)hipStreamWaitEvent(st, e->ev_sweep[slot], 0);
@@ -682,6 +688,7 @@ void tpamd_engine_destroy(tpamd_engine *e) {
     ln.ws.release();
   }
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
+  if (e->ev_async) (void)hipEventDestroy(e->ev_async);
   e->stage.release();
   e->rows.release();
   e->pose_ints.release();
@@ -2229,6 +2236,7 @@ struct tpamd_planner_set {
   int *d_windows = nullptr;
   long long *d_start = nullptr, *d_horizon = nullptr, *d_loop_start = nullptr;
   PlannerSummaryDev *d_summary = nullptr;
+  int *d_need_cap = nullptr;            // plan_device: [2][B] history / trajectory samples a planner lacked
   char *d_stop_in = nullptr, *d_stop_out = nullptr;   // stop queries: [time_ns][ids], [s][duration][status]
   size_t last_h2d = 0, last_d2h = 0;
   // staging of the host readouts (inputs and offsets | packed rows or tick values); they grow
@@ -2662,6 +2670,7 @@ int create_planner_set(tpamd_engine *e, const tpamd_planner_set_config *cfg_in, 
     ps->d_windows = s.take<int>(B);
     ps->P.old_state = s.take<int>(B); ps->P.offset = s.take<int>(B); ps->P.loop = s.take<int>(B); ps->P.append = s.take<int>(B);
     ps->d_summary = s.take<PlannerSummaryDev>(B);
+    ps->d_need_cap = s.take<int>(2 * B);
     ps->d_stop_in = s.take<char>(B * 12); ps->d_stop_out = s.take<char>(B * 20);
     if (cartesian) {
       ps->d_vtrans = s.take<double>(B); ps->d_vrot = s.take<double>(B); ps->d_path_end = s.take<double>(B);
@@ -2974,6 +2983,110 @@ int tpamd_planner_set_plan_resume(tpamd_planner_set *ps, tpamd_planner_summary *
                                   int32_t *need_count, int32_t *num_waiting) {
   if (!ps || !ps->cartesian || ps->num_waiting == 0) return TPAMD_E_INVALID_ARGUMENT;
   return planner_set_plan_run(ps, kPlanResume, nullptr, nullptr, summary, need_first, need_count, num_waiting);
+}
+
+int tpamd_planner_set_capacity(const tpamd_planner_set *ps, int32_t *history, int32_t *trajectory) {
+  if (!ps) return TPAMD_E_INVALID_ARGUMENT;
+  if (history) *history = ps->cap;
+  if (trajectory) *trajectory = ps->tcap;
+  return 0;
+}
+
+int tpamd_planner_set_reserve(tpamd_planner_set *ps, int history_capacity, int trajectory_capacity) {
+  if (!ps) return TPAMD_E_INVALID_ARGUMENT;
+  if (history_capacity > (1 << 28) || trajectory_capacity > (1 << 28)) return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(ps->e);
+  if (history_capacity > ps->cap || trajectory_capacity > ps->tcap) {
+    // the copies run on the null stream, after the device calls in flight; grow_rows synchronises
+    if (order_after_readouts(ps)) return TPAMD_E_HIP;
+    if (history_capacity > ps->cap)
+      if (int rc = grow_rows(ps, /*history=*/true, history_capacity, nullptr)) return rc;
+    if (trajectory_capacity > ps->tcap)
+      if (int rc = grow_rows(ps, /*history=*/false, trajectory_capacity, nullptr)) return rc;
+  }
+  // the engine's workspace for this set's windows: an enqueued-only Plan then allocates nothing
+  const int C = ps->cartesian ? 2 * ps->S.D + 2 : 2 * ps->S.D;
+  if (carve_workspace(nullptr, ps->S.B, ps->S.N, C, nullptr) > ps->e->ws_buf.bytes) {
+    HIPCHK(hipDeviceSynchronize());         // solves in flight use the workspace that is replaced
+    if (int rc = ensure_workspace(ps->e, ps->S.B, ps->S.N, C)) return rc;
+  }
+  return 0;
+}
+
+// Plan, enqueued only (include/tpamd.h). The window loop of planner_set_plan_run with the host out
+// of it: max_windows iterations, each gated per planner on the device (tpamd_planner_set.h).
+int tpamd_planner_set_plan_device(tpamd_planner_set *ps, const int64_t *start_ns, const int64_t *horizon_ns,
+                                  int max_windows, tpamd_planner_summary *summary, tpamd_plan_device_info *info,
+                                  void *hip_stream) {
+  static_assert(sizeof(tpamd_plan_device_info) == 32 && sizeof(PlanDeviceInfoDev) == 32, "info layouts must agree");
+  if (!ps || !start_ns || !horizon_ns || max_windows < 1) return TPAMD_E_INVALID_ARGUMENT;
+  tpamd_engine *e = ps->e;
+  TPAMD_ON_DEVICE(e);
+  PlannerSetState &S = ps->S;
+  const size_t B = S.B, N = S.N, D = S.D, P = largest_points(ps);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (!e->ev_async) HIPCHK(hipEventCreateWithFlags(&e->ev_async, hipEventDisableTiming));
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  ps->last_h2d = ps->last_d2h = 0;
+  const unsigned gb = (unsigned)((B + 127) / 128);
+  ps->streaming = false;
+  refresh_plan_params(ps);
+  ps->P.max_iterations = std::min(ps->cfg.max_planning_iterations, max_windows - 1);
+  if (ps->num_waiting) {        // suspensions of an earlier streaming Plan are dropped
+    HIPCHK(hipMemsetAsync(ps->d_suspended, 0, B * 4, st));
+    HIPCHK(hipMemsetAsync(ps->d_need, 0, 2 * B * 4, st));
+    std::fill(ps->h_wait.begin(), ps->h_wait.end(), 0);
+    ps->num_waiting = 0;
+  }
+  HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
+  hipLaunchKernelGGL(k_pset_prologue_step, dim3(gb), dim3(128), 0, st, S, ps->P, (const long long *)start_ns,
+                     (const long long *)horizon_ns, ps->d_start, ps->d_horizon, ps->d_need_cap);
+  tpamd_joint_batch bt{(int)B, (int)D, (int)N, (int)P, 0, 0, ps->cfg.constraint_safety};
+  tpamd_joint_inputs din{S.knots, ps->d_cp, ps->d_vmax, S.amax, S.path_start, ps->d_delta, S.path_start_velocity,
+                         ps->d_sdd0, S.path_time_start, nullptr};
+  tpamd_path_outputs dout{ps->w_time, ps->w_s, ps->w_sd, ps->w_sdd, ps->w_q, ps->w_qd, ps->w_qdd, ps->w_lei,
+                          ps->w_dtm, ps->w_st, nullptr};
+  int rc = 0;
+  for (int w = 0; w < max_windows && !rc; w++) {
+    if (ps->cartesian) {
+      tpamd_cartesian_batch cb{(int)B, (int)D, (int)N, 0, ps->cfg.constraint_safety};
+      tpamd_cartesian_inputs cin{ps->d_tq, ps->d_tJ, ps->d_vmax, S.amax, ps->d_vtrans, ps->d_vrot, S.path_start,
+                                 ps->d_delta, S.path_start_velocity, ps->d_sdd0, S.path_time_start};
+      rc = solve_cartesian(e, &cb, &cin, &dout, st, &ps->P, ps->table_cap);
+    } else {
+      rc = solve_joint(e, &bt, &din, &dout, st, &ps->P);
+    }
+    if (rc) break;
+    hipLaunchKernelGGL(k_plan_append_early, dim3((unsigned)((N + 127) / 128), (unsigned)B), dim3(128), 0, st, ps->P);
+    if (w + 1 < max_windows) hipLaunchKernelGGL(k_pset_step, dim3(gb), dim3(128), 0, st, S, ps->P, ps->d_need_cap);
+    else hipLaunchKernelGGL(k_pset_last_step, dim3(gb), dim3(128), 0, st, S, ps->P);
+  }
+  if (!rc) {
+    ResampleParams rp;
+    rp.B = (int)B; rp.N = ps->cap; rp.D = (int)D; rp.max_out = ps->tcap;
+    rp.time = S.h_time; rp.s = S.h_s; rp.sd = S.h_sd; rp.sdd = S.h_sdd; rp.q = S.h_q; rp.qd = S.h_qd; rp.qdd = S.h_qdd;
+    rp.amax = S.amax; rp.start_sec = S.start_sec; rp.status = S.resample_skip; rp.ns = S.count;
+    rp.ot = S.t_time; rp.os = S.t_s; rp.osd = S.t_sd; rp.osdd = S.t_sdd; rp.oq = S.t_q; rp.oqd = S.t_qd; rp.oqdd = S.t_qdd;
+    rp.count = S.resample_count;
+    if (S.method == 0) {
+      rp.time_step = S.time_step_sec;
+      hipLaunchKernelGGL(k_resample, dim3((ps->tcap + 255) / 256, (unsigned)B), dim3(256), 0, st, rp);
+    } else {
+      rp.time_step = 0.95 * S.time_step_sec;            // GetMinTimeDeltaToKeep :893-900
+      hipLaunchKernelGGL(k_resample_skip, dim3((unsigned)B), dim3(64), 0, st, rp);
+    }
+    hipLaunchKernelGGL(k_pset_epilogue_device, dim3(gb), dim3(128), 0, st, S, ps->d_need_cap);
+    hipLaunchKernelGGL(k_pset_finish_device, dim3(1), dim3(kFinishThreads), 0, st, S, ps->d_windows, ps->d_need_cap,
+                       ps->d_summary, (PlannerSummaryDev *)summary, (PlanDeviceInfoDev *)info);
+    if (hipGetLastError() != hipSuccess) rc = TPAMD_E_HIP;
+  }
+  // whatever was enqueued (an error path included) is ordered in front of the set's and the
+  // engine's later work: the event after it, and the null stream behind the event
+  if (hipEventRecord(e->ev_async, st) != hipSuccess) return TPAMD_E_HIP;
+  e->async_pending = true;
+  if (readout_end(ps, st)) return TPAMD_E_HIP;
+  HIPCHK(hipStreamWaitEvent(nullptr, ps->ev_read, 0));
+  return rc;
 }
 
 int tpamd_planner_set_download_trajectory(tpamd_planner_set *ps, int planner, int first, int count, double *time,

@@ -1602,12 +1602,10 @@ struct PlanParams {
   int *need_first, *need_count;    // [B]
 };
 enum { kPlanOk = 0, kPlanFailedPrecondition = 1, kPlanOutOfRange = 2, kPlanInvalidArgument = 3,
-       kPlanInternal = 4, kPlanDeadlineExceeded = 5, kPlanNeedsRows = 7 };
+       kPlanInternal = 4, kPlanDeadlineExceeded = 5, kPlanNeedsRows = 7, kPlanResourceExhausted = 8 };
 
 // where the next window starts (path_timing_trajectory.cc:318-341)
-static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= p.B) return;
+__device__ __forceinline__ void plan_begin_planner(const PlanParams &p, int b) {
   if (!p.active[b]) return;
   const long long duration = p.start_ns[b] + p.horizon_ns[b] - p.loop_start_ns[b];
   if (duration <= 0) { p.status[b] = kPlanInvalidArgument; p.active[b] = 0; return; }   // :313-317
@@ -1663,6 +1661,11 @@ static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
   }
   p.path_state[b] = 3;                          // SamplePath: kPathWasSampled
 }
+static __global__ void k_plan_begin(PlanParams p, Workspace ws) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= p.B) return;
+  plan_begin_planner(p, b);
+}
 
 // skip marks for the planners that are not looping (after set-up wrote the error bits)
 static __global__ void k_plan_mark_skipped(PlanParams p, Workspace ws) {
@@ -1707,9 +1710,7 @@ static __global__ void k_plan_project(PlanParams p, Workspace ws) {
 }
 
 // loop bookkeeping after a window (path_timing_trajectory.cc:639-660)
-static __global__ void k_plan_end(PlanParams p) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= p.B) return;
+__device__ __forceinline__ void plan_end_planner(const PlanParams &p, int b) {
   p.append[b] = 0;
   if (!p.active[b]) return;
   const int st = p.w_status[b];
@@ -1732,12 +1733,14 @@ static __global__ void k_plan_end(PlanParams p) {
   if (planned_to_end || reached) p.active[b] = 0;
   else atomicAdd(p.num_active, 1);
 }
+static __global__ void k_plan_end(PlanParams p) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= p.B) return;
+  plan_end_planner(p, b);
+}
 
 // drop what the window replaces and append it (path_timing_trajectory.cc:418-472)
-static __global__ void k_plan_append(PlanParams p) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.N || !p.append[b]) return;
+__device__ __forceinline__ void plan_append_sample(const PlanParams &p, int b, int i) {
   const int N = p.N, D = p.D;
   const size_t src = (size_t)b * N + i;
   const size_t dst = (size_t)b * p.cap + p.offset[b] + i;
@@ -1752,6 +1755,22 @@ static __global__ void k_plan_append(PlanParams p) {
     p.h_qdd[dst * D + d] = p.w_qdd[src * D + d];
   }
   if (i == 0) p.count[b] = p.offset[b] + N;
+}
+static __global__ void k_plan_append(PlanParams p) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.N || !p.append[b]) return;
+  plan_append_sample(p, b, i);
+}
+// tpamd_planner_set_plan_device: the append runs BEFORE the loop bookkeeping (k_pset_step fuses
+// k_plan_end with the next window's gate and k_plan_begin, and the next window starts from the
+// appended history), so each thread works out k_plan_end's append flag itself: a planner that
+// looped and whose window was solved. Nothing k_plan_end reads is written here.
+static __global__ void k_plan_append_early(PlanParams p) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.N || !p.active[b] || p.w_status[b] != 0) return;
+  plan_append_sample(p, b, i);
 }
 
 // A Cartesian window's q output: the N table rows of each looping planner from row first[b] on

@@ -17,6 +17,9 @@
 //   resample         k_resample / k_resample_skip over the histories (:755-836)
 //   k_pset_epilogue  :662-684: end_time_, final_decel_start_ clamped to time-step multiples,
 //                    target_reached_
+// tpamd_planner_set_plan_device runs the same bodies with the host out of the loop (a bounded number
+// of window iterations, a per-planner capacity gate, fused bookkeeping kernels): see below,
+// k_pset_prologue_step .. k_pset_finish_device.
 // Times are int64 nanoseconds; TimeFromSec truncates seconds * 1e9, TimeToSec divides by 1e9
 // (trajectory_planning/time.h:22-29).
 #pragma once
@@ -71,9 +74,7 @@ __device__ __forceinline__ int pset_lower_index(const double *ht, int n, int sta
 }
 
 // Everything of Plan() before the window loop. One thread per planner.
-static __global__ void k_pset_prologue(PlannerSetState S) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= S.B) return;
+__device__ __forceinline__ void pset_prologue_planner(const PlannerSetState &S, int b) {
   const int D = S.D;
   S.mode[b] = kPsetIdle;
   S.active[b] = 0;
@@ -183,6 +184,11 @@ static __global__ void k_pset_prologue(PlannerSetState S) {
     atomicAdd(S.num_active, 1);
   }
 }
+static __global__ void k_pset_prologue(PlannerSetState S) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  pset_prologue_planner(S, b);
+}
 
 // A resume of a streaming Plan (tpamd_planner_set_plan_resume) runs this in place of the prologue.
 // A planner that waited and whose table now holds its window re-enters the window loop: loop,
@@ -223,9 +229,7 @@ static __global__ void k_pset_check_capacity(PlannerSetState S) {
 }
 
 // planners whose window loop ended in an error do not resample (Plan returned before :660)
-static __global__ void k_pset_before_resample(PlannerSetState S) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= S.B) return;
+__device__ __forceinline__ void pset_before_resample_planner(const PlannerSetState &S, int b) {
   if (S.finish[b] && S.status[b] != kPlanOk) { S.finish[b] = 0; S.resample_skip[b] = 1; }
   if (S.finish[b] && S.count[b] < 2) {
     S.resample_skip[b] = 1;
@@ -233,19 +237,32 @@ static __global__ void k_pset_before_resample(PlannerSetState S) {
     else { S.t_first[b] = 0; S.t_count[b] = 0; S.resample_count[b] = 0; }   // kSkip: cleared, no error
   }
 }
-
-// :662-684 after the resample. resample_count[b] = samples the resample produced (it may exceed
-// tcap: the host then grows the trajectory arrays and repeats the resample and this kernel).
-static __global__ void k_pset_epilogue(PlannerSetState S) {
+static __global__ void k_pset_before_resample(PlannerSetState S) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= S.B) return;
+  pset_before_resample_planner(S, b);
+}
+
+// :662-684 after the resample. resample_count[b] = samples the resample produced. It may exceed
+// tcap. The synchronous Plan (need_trajectory null) then reports the count to the host, which
+// grows the trajectory arrays and repeats the resample and this kernel.
+// tpamd_planner_set_plan_device cannot grow anything: the planner gets kPlanResourceExhausted and
+// an empty trajectory (the resample filled tcap slots of a trajectory that does not end at rest,
+// which nothing may read out), need_trajectory[b] receives the count, and the scalars are those of
+// a plan without samples -- the next Plan of this planner fails its precondition until it is reset.
+__device__ __forceinline__ void pset_epilogue_planner(const PlannerSetState &S, int b, int *need_trajectory) {
   if (!S.finish[b]) return;
   if (!S.resample_skip[b]) {
     const int M = S.resample_count[b];
     if (S.method == 0 && M < 1) { S.status[b] = kPlanInternal; return; }   // negative trajectory duration
-    if (M > S.tcap) atomicMax(&S.num_active[1], M);      // does not fit: the host grows the buffers and repeats
     S.t_first[b] = 0;
-    S.t_count[b] = min(M, S.tcap);
+    if (need_trajectory) {
+      if (M > S.tcap) { S.status[b] = kPlanResourceExhausted; need_trajectory[b] = M; }
+      S.t_count[b] = M > S.tcap ? 0 : M;
+    } else {
+      if (M > S.tcap) atomicMax(&S.num_active[1], M);      // does not fit: the host grows the buffers and repeats
+      S.t_count[b] = min(M, S.tcap);
+    }
   }
   S.initial_plan[b] = 1;
   const int tn = S.t_count[b];
@@ -262,6 +279,11 @@ static __global__ void k_pset_epilogue(PlannerSetState S) {
     S.final_decel_start_ns[b] = S.end_time_ns[b];
   }
   S.target_reached[b] = S.planned_to_end[b];
+}
+static __global__ void k_pset_epilogue(PlannerSetState S) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  pset_epilogue_planner(S, b, nullptr);
 }
 
 // rows of `count[b]` valid entries (x width doubles) from a buffer of stride old_cap to one of
@@ -453,6 +475,71 @@ static __global__ __launch_bounds__(kCompactThreads) void k_pset_ik_compact(IkDi
     pset_compact_run<double2>((double2 *)base, n >> 1, s >> 1, overlap);
 }
 
+// ---- tpamd_planner_set_plan_device: Plan with the host out of the loop. The number of window
+// iterations is an argument, so nothing has to come down between them; what the synchronous Plan
+// settles on the host (is there room for one more window? does the trajectory fit?) is settled
+// per planner here, and the one-thread-per-planner kernels that would run back to back are one
+// kernel:
+//   k_pset_prologue_step  time arguments from the caller's device arrays, loop state cleared,
+//                         k_pset_prologue, gate, k_plan_begin of window 0
+//   k_pset_step           k_plan_end of window i, gate, k_plan_begin of window i + 1
+//   k_pset_last_step      k_plan_end of the last window, k_pset_before_resample
+//   k_pset_epilogue_device, k_pset_finish_device
+// Each body is the synchronous kernel's (the same __device__ function), so a planner ends in the
+// same state bit for bit. k_plan_append_early (tpamd_kernels.h) runs in front of the step kernels.
+//
+// The gate, in place of the call-wide flag of k_pset_check_capacity: a looping planner whose
+// history has no room for one more window wherever it connects (count + N > cap) stops looping
+// with kPlanResourceExhausted; k_pset_before_resample then takes it out of the resample and the
+// epilogue like any planner whose loop ended in an error. need_history[b] = count + N.
+__device__ __forceinline__ void pset_gate_planner(const PlannerSetState &S, int b, int *need_history) {
+  if (!S.active[b]) return;
+  const int want = S.count[b] + S.N;
+  if (want <= S.cap) return;
+  S.status[b] = kPlanResourceExhausted;
+  S.active[b] = 0;
+  need_history[b] = want;
+}
+
+// need [2][B]: history samples / trajectory samples a planner lacked in this call (0: none)
+static __global__ void k_pset_prologue_step(PlannerSetState S, PlanParams p, const long long *start_ns,
+                                            const long long *horizon_ns, long long *d_start, long long *d_horizon,
+                                            int *need) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  const long long start = start_ns[b];
+  d_start[b] = start;
+  d_horizon[b] = horizon_ns[b];
+  p.loop_start_ns[b] = start;                 // :630
+  p.old_state[b] = 0; p.offset[b] = 0; p.loop[b] = 0; p.append[b] = 0; p.windows[b] = 0;
+  need[b] = 0;
+  need[S.B + b] = 0;
+  pset_prologue_planner(S, b);
+  pset_gate_planner(S, b, need);
+  plan_begin_planner(p, b);
+}
+
+static __global__ void k_pset_step(PlannerSetState S, PlanParams p, int *need) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  plan_end_planner(p, b);
+  pset_gate_planner(S, b, need);
+  plan_begin_planner(p, b);
+}
+
+static __global__ void k_pset_last_step(PlannerSetState S, PlanParams p) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  plan_end_planner(p, b);
+  pset_before_resample_planner(S, b);
+}
+
+static __global__ void k_pset_epilogue_device(PlannerSetState S, int *need) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  pset_epilogue_planner(S, b, need + S.B);
+}
+
 // summary record per planner (what the mirror's getters need without a trajectory download)
 struct PlannerSummaryDev {
   long long end_time_ns, final_decel_start_ns, start_time_ns;
@@ -468,6 +555,61 @@ static __global__ void k_pset_summary(PlannerSetState S, const int *windows, Pla
   r.windows = windows[b]; r.path_state = S.path_state[b]; r.history_count = S.count[b]; r.status = S.status[b];
   r.pad = 0;
   out[b] = r;
+}
+
+// tpamd_plan_device_info (include/tpamd.h)
+struct PlanDeviceInfoDev {
+  int num_ok, num_failed, num_exhausted, needed_history, needed_trajectory, max_windows_solved, reserved[2];
+};
+// The summaries (into the set's own array and, if not null, the caller's) and the call's info record:
+// one workgroup of kFinishThreads strides over the planners, each wave reduces its lanes' counts
+// with shuffles, LDS combines the waves.
+constexpr int kFinishThreads = 256;
+static __global__ __launch_bounds__(kFinishThreads) void k_pset_finish_device(PlannerSetState S, const int *windows,
+                                                                             const int *need, PlannerSummaryDev *own,
+                                                                             PlannerSummaryDev *out,
+                                                                             PlanDeviceInfoDev *info) {
+  int v[6] = {0, 0, 0, 0, 0, 0};     // ok, failed, exhausted (sums); history, trajectory, windows (maxima)
+  for (int b = threadIdx.x; b < S.B; b += kFinishThreads) {
+    PlannerSummaryDev r;
+    r.end_time_ns = S.end_time_ns[b]; r.final_decel_start_ns = S.final_decel_start_ns[b];
+    r.start_time_ns = S.start_time_ns[b];
+    r.num_samples = S.t_count[b]; r.target_reached = S.target_reached[b]; r.planned_to_end = S.planned_to_end[b];
+    r.windows = windows[b]; r.path_state = S.path_state[b]; r.history_count = S.count[b]; r.status = S.status[b];
+    r.pad = 0;
+    own[b] = r;
+    if (out) out[b] = r;
+    v[0] += r.status == kPlanOk;
+    v[1] += r.status != kPlanOk;
+    v[2] += r.status == kPlanResourceExhausted;
+    v[3] = max(v[3], need[b]);
+    v[4] = max(v[4], need[S.B + b]);
+    v[5] = max(v[5], r.windows);
+  }
+  if (!info) return;
+  __shared__ int part[kFinishThreads / 64][6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    int x = v[k];
+    for (int off = 32; off > 0; off >>= 1) {
+      const int y = __shfl_down(x, off, 64);
+      x = k < 3 ? x + y : max(x, y);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t[6];
+    for (int k = 0; k < 6; k++) {
+      t[k] = part[0][k];
+      for (int w = 1; w < kFinishThreads / 64; w++) t[k] = k < 3 ? t[k] + part[w][k] : max(t[k], part[w][k]);
+    }
+    PlanDeviceInfoDev r;
+    r.num_ok = t[0]; r.num_failed = t[1]; r.num_exhausted = t[2];
+    r.needed_history = t[3]; r.needed_trajectory = t[4]; r.max_windows_solved = t[5];
+    r.reserved[0] = r.reserved[1] = 0;
+    *info = r;
+  }
 }
 
 }  // namespace tpamd

@@ -201,6 +201,17 @@ PLANNER_SUMMARY_DTYPE = np.dtype([
     ("windows", np.int32), ("path_state", np.int32), ("history_count", np.int32),
     ("status", np.int32), ("reserved", np.int32)])
 
+# tpamd_plan_device_info
+PLAN_DEVICE_INFO_FIELDS = ("num_ok", "num_failed", "num_exhausted", "needed_history", "needed_trajectory",
+                           "max_windows_solved")
+
+
+class _PlanDeviceInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in PLAN_DEVICE_INFO_FIELDS] + [("reserved", C.c_int32 * 2)]
+
+
+PLAN_RESOURCE_EXHAUSTED = 8     # TPAMD_PLAN_RESOURCE_EXHAUSTED
+
 _LIB = None
 
 # every symbol include/tpamd.h declares
@@ -220,6 +231,7 @@ ABI_SYMBOLS = [
     "tpamd_plan_joint_windows_host",
     "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
     "tpamd_planner_set_reset", "tpamd_planner_set_plan", "tpamd_planner_set_download_trajectory",
+    "tpamd_planner_set_reserve", "tpamd_planner_set_capacity", "tpamd_planner_set_plan_device",
     "tpamd_planner_set_last_plan_bytes", "tpamd_planner_set_device_bytes",
     "tpamd_planner_set_stop_parameters", "tpamd_planner_set_upload_paths_ragged",
     "tpamd_planner_set_download_path", "tpamd_planner_set_switch_paths", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
@@ -432,6 +444,11 @@ def load_library():
     L.tpamd_planner_set_download_path.argtypes = [vp, i, vp, vp, vp, i]
     L.tpamd_planner_set_reset.argtypes = [vp, i, vp]
     L.tpamd_planner_set_plan.argtypes = [vp, vp, vp, vp]
+    for name in ("tpamd_planner_set_reserve", "tpamd_planner_set_capacity", "tpamd_planner_set_plan_device"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_reserve.argtypes = [vp, i, i]
+    L.tpamd_planner_set_capacity.argtypes = [vp, vp, vp]
+    L.tpamd_planner_set_plan_device.argtypes = [vp, vp, vp, i, vp, vp, vp]
     L.tpamd_planner_set_download_trajectory.argtypes = [vp, i, i, i] + [vp] * 7
     L.tpamd_planner_set_switch_paths.argtypes = [vp, i] + [vp] * 8
     L.tpamd_planner_set_set_waypoints.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6
@@ -1094,9 +1111,13 @@ class PlannerSet:
         self._engine = engine          # the set must not outlive its engine
         self._h = h
         self._num_samples = np.zeros(self.B, dtype=np.int64)    # GetNumTimeSamples after the last plan
+        self._pending = None           # the PlanHandle of a plan_async whose result() has not run yet
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_pending", None) is not None:
+                self._pending._stream.synchronize()      # the call writes the handle's tensors
+                self._pending = None
             self._lib.tpamd_planner_set_destroy(self._h)
             self._h = None
 
@@ -1116,6 +1137,13 @@ class PlannerSet:
         if not getattr(self, "_h", None):
             raise TpamdError("the planner set is closed")
         return self._h
+
+    def _sample_counts(self):
+        """The sample counts of the last plan; they are unknown while a plan_async is in flight."""
+        if self._pending is not None:
+            raise TpamdError("a plan_async call is in flight: its sample counts are on the device until "
+                             "PlanHandle.result()")
+        return self._num_samples
 
     def _ids(self, ids, count=None):
         if ids is None:
@@ -1472,6 +1500,8 @@ class PlannerSet:
         final_decel_start_ns, start_time_ns, target_reached, planned_to_end, windows, path_state,
         history_count)."""
         import torch
+        if self._pending is not None:
+            raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
         s = _host(np.broadcast_to(_host(start_ns, np.int64), (self.B,)), np.int64)
         h = _host(np.broadcast_to(_host(horizon_ns, np.int64), (self.B,)), np.int64)
         out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
@@ -1484,6 +1514,54 @@ class PlannerSet:
         up, down = C.c_size_t(0), C.c_size_t(0)
         self._lib.tpamd_planner_set_last_plan_bytes(self._handle(), C.byref(up), C.byref(down))
         return int(up.value), int(down.value)
+
+    def reserve(self, history=0, trajectory=0):
+        """Capacity ahead of time (tpamd_planner_set_reserve): the history and trajectory buffers
+        grow to at least this many samples per planner (never shrink; planner state is kept bit for
+        bit) and the engine's workspace is sized for this set, so that plan_async allocates nothing."""
+        if self._pending is not None:
+            raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
+        _check(self._lib.tpamd_planner_set_reserve(self._handle(), int(history), int(trajectory)),
+               "tpamd_planner_set_reserve")
+
+    def capacity(self):
+        """(history, trajectory) samples per planner the buffers hold."""
+        h, t = C.c_int32(0), C.c_int32(0)
+        _check(self._lib.tpamd_planner_set_capacity(self._handle(), C.byref(h), C.byref(t)),
+               "tpamd_planner_set_capacity")
+        return int(h.value), int(t.value)
+
+    def plan_async(self, start_ns, horizon_ns, max_windows=2, stream=None):
+        """Plan, enqueued only (tpamd_planner_set_plan_device): start_ns / horizon_ns are CUDA
+        int64 tensors [B], exactly max_windows window iterations are enqueued on `stream` (torch's
+        current stream if None) and every planner ends as plan() leaves it on a set with
+        max_planning_iterations = min(its value, max_windows - 1). Nothing comes to the host and
+        nothing blocks: retargets, readouts into CUDA tensors and BufferSet.insert_from can be
+        enqueued behind it on the same stream. Returns a PlanHandle holding the summary and info
+        tensors on the device; its result() synchronises the stream and returns plan()'s dict plus
+        `info`. Until then the sample counts of this plan are unknown on the host: methods that
+        size their outputs from them (download_trajectories, stop_trajectories without a capacity)
+        raise TpamdError. A planner without room in its history or for its trajectory gets status
+        PLAN_RESOURCE_EXHAUSTED; info says what reserve() needs (then reset and a new path)."""
+        import torch
+        if self._pending is not None:
+            raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
+        dev = torch.device("cuda", self.device)
+        for name, a in (("start_ns", start_ns), ("horizon_ns", horizon_ns)):
+            if not _is_cuda(a) or a.dtype != torch.int64 or tuple(a.shape) != (self.B,) or not a.is_contiguous():
+                raise TpamdError("%s must be a contiguous CUDA int64 tensor [%d]" % (name, self.B))
+        if int(max_windows) < 1:
+            raise TpamdError("max_windows must be at least 1")
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        summary = torch.zeros(self.B * PLANNER_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        info = torch.zeros(C.sizeof(_PlanDeviceInfo) // 4, dtype=torch.int32, device=dev)
+        if st != torch.cuda.current_stream(dev):      # the zero fills ran on the current stream
+            st.wait_stream(torch.cuda.current_stream(dev))
+        _check(self._lib.tpamd_planner_set_plan_device(self._handle(), _ptr(start_ns), _ptr(horizon_ns),
+                                                       int(max_windows), _ptr(summary), _ptr(info),
+                                                       _stream_ptr(st)), "tpamd_planner_set_plan_device")
+        self._pending = PlanHandle(self, st, summary, info, (start_ns, horizon_ns))
+        return self._pending
 
     def _summary(self, out):
         import torch
@@ -1684,7 +1762,8 @@ class PlannerSet:
         import torch
         dev = torch.device("cuda", self.device)
         ida, n = self._ids(ids)
-        rows = int(self._num_samples[ida].sum() if ida is not None else self._num_samples[:n].sum())
+        counts = self._sample_counts()
+        rows = int(counts[ida].sum() if ida is not None else counts[:n].sum())
         f = dict(dtype=torch.float64, device=dev)
         out = dict(offsets=torch.zeros(n + 1, dtype=torch.int64, device=dev))
         for k in ("time", "s", "sd", "sdd"):
@@ -1715,7 +1794,8 @@ class PlannerSet:
             raise TpamdError("more stop times than planners")
         am = self._cuda(max_acceleration, torch.float64, dev, (n, self.D), "max_acceleration")
         if capacity is None:
-            sel = self._num_samples[:n] if ids is None else self._num_samples[_host(ids, np.int64).reshape(-1)]
+            counts = self._sample_counts()
+            sel = counts[:n] if ids is None else counts[_host(ids, np.int64).reshape(-1)]
             capacity = int(sel.sum()) + 64 * n
         for _ in range(2):
             out = dict(status=torch.full((n,), -1, dtype=torch.int32, device=dev),
@@ -1736,6 +1816,34 @@ class PlannerSet:
         for k in ("time", "q", "qd", "qdd"):
             out[k] = out[k][:rows]
         return out
+
+
+class PlanHandle:
+    """A PlannerSet.plan_async call in flight: `summary` (the tpamd_planner_summary records as
+    bytes) and `info` (tpamd_plan_device_info as int32) are CUDA tensors the stream writes."""
+
+    def __init__(self, planner_set, stream, summary, info, keep):
+        self._set, self._stream, self.summary, self.info = planner_set, stream, summary, info
+        self._keep = keep              # the time arguments stay alive until the stream has read them
+        self._result = None
+
+    def result(self):
+        """Synchronises the call's stream; the dict plan() returns, plus `info` (dict of ints).
+        Refreshes the set's host-side sample counts."""
+        if self._result is None:
+            self._stream.synchronize()
+            out = self.summary.cpu().numpy().view(PLANNER_SUMMARY_DTYPE).copy()
+            info = self.info.cpu().numpy()
+            if self._set._pending is self:
+                self._set._pending = None
+                self._result = self._set._summary(out)
+            else:                      # the set was closed meanwhile: the records alone
+                import torch
+                self._result = {name: torch.from_numpy(np.ascontiguousarray(out[name]))
+                                for name in PLANNER_SUMMARY_DTYPE.names if name != "reserved"}
+            self._result["info"] = {k: int(info[j]) for j, k in enumerate(PLAN_DEVICE_INFO_FIELDS)}
+            self._keep = None
+        return self._result
 
 
 class BufferSet:

@@ -61,7 +61,9 @@ PathTimingTrajectorySet::PathTimingTrajectorySet(const PathTimingTrajectoryOptio
 }
 
 PathTimingTrajectorySet::~PathTimingTrajectorySet() {
+  if (plan_pending_) (void)hipStreamSynchronize((hipStream_t)plan_stream_);   // the call writes plan_results_
   if (set_) tpamd_planner_set_destroy(set_);     // before the engine goes back to the pool
+  if (plan_results_) (void)hipFree(plan_results_);
 }
 
 namespace {
@@ -592,6 +594,67 @@ std::vector<Status> PathTimingTrajectorySet::Plan(const std::vector<Time> &start
   return PlanStatuses();
 }
 
+Status PathTimingTrajectorySet::Reserve(int history, int trajectory) {
+  if (!init_status_.ok()) return init_status_;
+  if (plan_pending_) return FailedPreconditionError("a PlanDevice call is in flight (FinishPlanDevice)");
+  const int rc = tpamd_planner_set_reserve(set_, history, trajectory);
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  if (!plan_results_ &&
+      hipMalloc(&plan_results_, num_planners_ * sizeof(tpamd_planner_summary) + sizeof(tpamd_plan_device_info)) != hipSuccess)
+    return InternalError("no device memory for the summaries");
+  return OkStatus();
+}
+
+Status PathTimingTrajectorySet::GetCapacity(int *history, int *trajectory) const {
+  if (!init_status_.ok()) return init_status_;
+  int32_t h = 0, t = 0;
+  const int rc = tpamd_planner_set_capacity(set_, &h, &t);
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  if (history) *history = h;
+  if (trajectory) *trajectory = t;
+  return OkStatus();
+}
+
+Status PathTimingTrajectorySet::PlanDevice(const int64_t *start_ns_dev, const int64_t *horizon_ns_dev, int max_windows,
+                                           void *hip_stream) {
+  if (!init_status_.ok()) return init_status_;
+  if (plan_pending_) return FailedPreconditionError("a PlanDevice call is in flight (FinishPlanDevice)");
+  if (!start_ns_dev || !horizon_ns_dev || max_windows < 1)
+    return InvalidArgumentError("device arrays of start times and horizons, max_windows >= 1");
+  if (!plan_results_) {        // not reserved: the buffer for the summaries and the info is made here
+    const Status st = Reserve(0, 0);
+    if (!st.ok()) return st;
+  }
+  auto *summary = (tpamd_planner_summary *)plan_results_;
+  auto *info = (tpamd_plan_device_info *)(summary + num_planners_);
+  const int rc = tpamd_planner_set_plan_device(set_, start_ns_dev, horizon_ns_dev, max_windows, summary, info, hip_stream);
+  if (rc == TPAMD_E_INVALID_ARGUMENT) return InvalidArgumentError(tpamd_error_string(rc));
+  // any other error may have left work enqueued: FinishPlanDevice still waits for it
+  plan_pending_ = true;
+  plan_stream_ = hip_stream;
+  return rc == 0 ? OkStatus() : InternalError(tpamd_error_string(rc));
+}
+
+std::vector<Status> PathTimingTrajectorySet::FinishPlanDevice() {
+  std::vector<Status> result(num_planners_, OkStatus());
+  if (!init_status_.ok() || !plan_pending_) {
+    std::fill(result.begin(), result.end(),
+              init_status_.ok() ? FailedPreconditionError("no PlanDevice call is in flight") : init_status_);
+    return result;
+  }
+  plan_pending_ = false;
+  const size_t bytes = num_planners_ * sizeof(tpamd_planner_summary);
+  hipStream_t st = (hipStream_t)plan_stream_;
+  if (hipMemcpyAsync(summary_.data(), plan_results_, bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(&plan_info_, (const char *)plan_results_ + bytes, sizeof(plan_info_), hipMemcpyDeviceToHost, st) !=
+          hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    std::fill(result.begin(), result.end(), InternalError("could not read the summaries back"));
+    return result;
+  }
+  return PlanStatuses();
+}
+
 std::vector<Status> PathTimingTrajectorySet::PlanStatuses() const {
   std::vector<Status> result(num_planners_, OkStatus());
   for (size_t b = 0; b < num_planners_; b++) {
@@ -603,6 +666,8 @@ std::vector<Status> PathTimingTrajectorySet::PlanStatuses() const {
         result[b] = InvalidArgumentError("start time / duration / initial velocity not acceptable"); break;
       case TPAMD_PLAN_DEADLINE_EXCEEDED: result[b] = DeadlineExceededError("Reached maximum number of planning loops"); break;
       case TPAMD_PLAN_NEEDS_ROWS: result[b] = InternalError("IK solution does not cover the sampled window"); break;
+      case TPAMD_PLAN_RESOURCE_EXHAUSTED:
+        result[b] = ::tpamd::compat::ResourceExhaustedError("history or trajectory capacity exhausted (Reserve, Reset, new path)"); break;
       default: result[b] = InternalError("Error optimizing path parameter"); break;
     }
   }
@@ -953,6 +1018,7 @@ size_t PathTimingTrajectorySet::NumControlPoints(size_t planner) const {
 
 Status PathTimingTrajectorySet::GetTrajectory(size_t planner, PlannedTrajectory *out) const {
   if (!init_status_.ok()) return init_status_;
+  if (plan_pending_) return FailedPreconditionError("a PlanDevice call is in flight (FinishPlanDevice)");
   if (planner >= num_planners_ || !out) return InvalidArgumentError("no such planner");
   const size_t n = (size_t)summary_[planner].num_samples, D = options_.GetNumDofs();
   out->time.resize(n); out->path_parameter.resize(n); out->path_parameter_derivative.resize(n);
@@ -969,6 +1035,7 @@ Status PathTimingTrajectorySet::GetTrajectory(size_t planner, PlannedTrajectory 
 Status PathTimingTrajectorySet::GetTrajectories(const std::vector<size_t> &planners,
                                                 std::vector<PlannedTrajectory> *out) const {
   if (!init_status_.ok()) return init_status_;
+  if (plan_pending_) return FailedPreconditionError("a PlanDevice call is in flight (FinishPlanDevice)");
   if (!out) return InvalidArgumentError("no output");
   const size_t n = planners.size(), D = options_.GetNumDofs();
   std::vector<int32_t> ids(n);

@@ -192,6 +192,30 @@ class PathTimingTrajectorySet {
   std::vector<Status> PlanStreaming(const std::vector<Time> &start, const std::vector<Duration> &time_horizon,
                                     bool discard = false);
   int SuspensionsOfLastPlan() const { return suspensions_; }
+  // Capacity ahead of time (tpamd_planner_set_reserve / _capacity): the history and trajectory
+  // buffers grow to at least these samples per planner, never shrink, and keep every planner's
+  // state bit for bit; the engine's workspace is sized for this set. PlanDevice allocates nothing
+  // after a Reserve. Synchronises when anything grows.
+  Status Reserve(int history, int trajectory);
+  Status GetCapacity(int *history, int *trajectory) const;
+  // Plan, enqueued only (tpamd_planner_set_plan_device): start and horizon [planners] in
+  // nanoseconds are DEVICE arrays that stay valid until hip_stream (a hipStream_t; null: the null
+  // stream) has run the call; exactly max_windows window iterations are enqueued, and every planner
+  // ends as Plan leaves it with GetMaxPlanningIterations() = min(the options' value,
+  // max_windows - 1). Nothing is copied to the host and nothing blocks. A planner without room in
+  // its history or for its trajectory gets ResourceExhausted (LastPlanDeviceInfo() says what
+  // Reserve needs; then Reset and a new path). Work on the set may be enqueued behind the call on
+  // the same stream (retargets, TrajectoryBufferSet::InsertFromPlannerSet on the device, ...).
+  // Between PlanDevice and FinishPlanDevice the summary getters below (GetNumTimeSamples,
+  // GetEndTime, IsTrajectoryAtEnd, WindowsOfLastPlan, ...) are STALE: they still describe the Plan
+  // before; GetTrajectory / GetTrajectories, which size their download from them, and a second
+  // PlanDevice or a Reserve return FailedPrecondition.
+  Status PlanDevice(const int64_t *start_ns_dev, const int64_t *horizon_ns_dev, int max_windows, void *hip_stream);
+  // Waits for the PlanDevice call, downloads the summaries and the info record and refreshes the
+  // getters; one status per planner, as Plan returns them.
+  std::vector<Status> FinishPlanDevice();
+  bool PlanDevicePending() const { return plan_pending_; }
+  const tpamd_plan_device_info &LastPlanDeviceInfo() const { return plan_info_; }
   // Discards, for every planner that has a table, the consumed rows below its safe floor
   // (tpamd_planner_set_discard_ik_rows with keep_from NULL: the lowest row a later Plan can read).
   // Returns the first resident row of every planner (0 for one without a table).
@@ -321,6 +345,12 @@ class PathTimingTrajectorySet {
   std::vector<TimeableCartesianSplinePath *> stream_paths_;
   std::vector<std::shared_ptr<TimeableCartesianSplinePath>> stream_keep_;
   int suspensions_ = 0;
+  // PlanDevice: the summaries [planners] and the info record in device memory, the stream of the
+  // call in flight
+  void *plan_results_ = nullptr;
+  void *plan_stream_ = nullptr;
+  bool plan_pending_ = false;
+  tpamd_plan_device_info plan_info_{};
   std::vector<double> retarget_position_, retarget_velocity_, retarget_stop_;
   double callback_seconds_ = 0.0;
   // streaming through the device chain: the fitted splines of one SetCartesianWaypointPaths call,
