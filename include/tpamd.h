@@ -212,6 +212,21 @@ int tpamd_optimize_rows_host(tpamd_engine *engine, const tpamd_rows_batch *batch
                              const tpamd_rows_inputs *in,
                              const tpamd_path_outputs *out);
 
+/* Ragged rows batches: path b has n[b] = num_samples_per_path[b] samples, 3 <= n[b] <= num_samples,
+ * and is solved exactly as a uniform call with num_samples = n[b] would solve it: ds = (s_end -
+ * s_start) / (n[b] - 1), the last sample is n[b] - 1. The row arrays and every [B][N]-shaped
+ * output keep the stride num_samples; rows at i >= n[b] are not read, outputs there are not
+ * written. A count outside [2, num_samples] fails that path alone (TPAMD_PATH_TOO_FEW_SAMPLES, as a
+ * joint batch reports it). For B > 1 the sweep takes the paths longest first.
+ * num_samples_per_path [B] is a device array for _device, a host array for _host; NULL is
+ * TPAMD_E_INVALID_ARGUMENT. The engine reads it until the stream has run the call. */
+int tpamd_optimize_rows_ragged_device(tpamd_engine *engine, const tpamd_rows_batch *batch,
+                                      const tpamd_rows_inputs *in, const int32_t *num_samples_per_path,
+                                      const tpamd_path_outputs *out, void *hip_stream);
+int tpamd_optimize_rows_ragged_host(tpamd_engine *engine, const tpamd_rows_batch *batch,
+                                    const tpamd_rows_inputs *in, const int32_t *num_samples_per_path,
+                                    const tpamd_path_outputs *out);
+
 /* ------------------------------------------------------------------------
  * Form (iii): Cartesian-space paths after the IK callback (BASELINE.json configs[3]).
  * Replaces, for B paths at once, the arithmetic of TimeableCartesianSplinePath that
@@ -247,6 +262,40 @@ int tpamd_time_cartesian_paths_device(tpamd_engine *engine, const tpamd_cartesia
 int tpamd_time_cartesian_paths_host(tpamd_engine *engine, const tpamd_cartesian_batch *batch,
                                     const tpamd_cartesian_inputs *in,
                                     const tpamd_path_outputs *out);
+
+/* Ragged Cartesian batches: every path has its own sample count, and the IK rows may be packed.
+ * Path b has n[b] = num_samples_per_path[b] samples, 3 <= n[b] <= batch->num_samples, and is timed
+ * exactly as a uniform call with num_samples = n[b] would time it: s_end = path_start +
+ * delta (n[b] - 1), the forward differences end at n[b] - 1 (q'[n[b]-1] = 0, q''[0] = q''[n[b]-1] =
+ * 0), and max_solver_loops <= 0 means max(100, 10 n[b]). Same per-path results as separate uniform
+ * calls, bit for bit.
+ *   first_row == NULL  strided inputs: ik_positions [B][N][D] and jacobians [B][N][6][D] with
+ *                      N = num_samples; path b's samples beyond n[b] are not read.
+ *   first_row [B]      packed inputs: ik_positions [rows][D] and jacobians [rows][6][D] are row
+ *                      tables, and path b reads rows first_row[b] .. first_row[b] + n[b] - 1: the
+ *                      layout tpamd_sample_ik_targets_* writes, with first_row = row_offsets[0..B).
+ *                      The paths' ranges may lie in any order and may overlap (they are only read).
+ *                      rows < 2^31. num_rows tells the _host entry how many rows to stage.
+ * Every [B][N]-shaped output keeps the stride num_samples; entries at i >= n[b] are not written
+ * (the _host entry leaves the caller's memory there as it was). out->q, if given, receives path
+ * b's rows at [b][0 .. n[b])[D] (a gather in the packed case).
+ * A count outside [2, num_samples] fails that path alone with the status a ragged joint batch
+ * gives such a path (TPAMD_PATH_S_RANGE below 2, where s_end <= s_start; TPAMD_PATH_TOO_FEW_SAMPLES
+ * above num_samples); none of that path's rows is read, nothing but its per-path status entries
+ * is written, and the other paths are unaffected. For B > 1 the sweep takes the paths longest first (the
+ * device-side counting sort of ragged joint batches).
+ * num_samples_per_path and first_row are device arrays for _device and host arrays for _host; the
+ * engine reads them until the stream has run the call. Call-level errors as for the uniform entry;
+ * a NULL num_samples_per_path (or, for _host with first_row, num_rows < 1 or >= 2^31) is
+ * TPAMD_E_INVALID_ARGUMENT. Never pipelined. */
+int tpamd_time_cartesian_paths_ragged_device(tpamd_engine *engine, const tpamd_cartesian_batch *batch,
+                                             const tpamd_cartesian_inputs *in,
+                                             const int32_t *num_samples_per_path, const int32_t *first_row,
+                                             const tpamd_path_outputs *out, void *hip_stream);
+int tpamd_time_cartesian_paths_ragged_host(tpamd_engine *engine, const tpamd_cartesian_batch *batch,
+                                           const tpamd_cartesian_inputs *in,
+                                           const int32_t *num_samples_per_path, const int32_t *first_row,
+                                           int64_t num_rows, const tpamd_path_outputs *out);
 
 /* Pose targets of Cartesian-space paths: what TimeableCartesianSplinePath::SamplePath evaluates
  * before it calls the IK callback (timeable_path_cartesian_spline.cc:484-503), for B paths at

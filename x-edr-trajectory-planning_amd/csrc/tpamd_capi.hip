@@ -244,6 +244,7 @@ struct tpamd_engine {
   bool order_ragged = true;    // TPAMD_ORDER_RAGGED=0: A/B the longest-first order of ragged batches
   int k1_tpb = 0;              // TPAMD_K1_TPB: threads per block of the sampling/LP kernel (A/B)
   int k1_tpb_ragged = 64;      // TPAMD_K1_TPB_RAGGED: its upper limit for ragged batches (A/B)
+  int cartesian_tpb_ragged = 64;    // TPAMD_CARTESIAN_TPB_RAGGED: threads per block of the ragged Cartesian K1 (A/B)
   // Idle time in front of a pipelined front stage (TPAMD_FRONT_DELAY_US). The front stage of solve k+1
   // and the sweep of solve k become runnable at the same moment (the sweep of solve k-1 has ended); if
   // the sampling/LP kernel's 16 k blocks reach the CUs first, the sweep's workgroups (35 KB of LDS each)
@@ -458,6 +459,8 @@ int configure_kernels_for_device(int device) {
 #undef TPAMD_CONFIGURE_SWEEP
   TPAMD_BIG_LDS(k_cartesian_lp<1, 6>);
   TPAMD_BIG_LDS(k_cartesian_lp<1, 7>);
+  TPAMD_BIG_LDS(k_cartesian_lp<1, 6, true>);
+  TPAMD_BIG_LDS(k_cartesian_lp<1, 7, true>);
 #undef TPAMD_BIG_LDS
   g_device_configured[device] = true;
   return 0;
@@ -652,6 +655,8 @@ int tpamd_engine_create(int device_ordinal, tpamd_engine **out) {
     e->force_generic = fg && fg[0] == '1';
     const char *tr = std::getenv("TPAMD_K1_TPB_RAGGED");
     if (tr && (atoi(tr) == 64 || atoi(tr) == 128 || atoi(tr) == 256)) e->k1_tpb_ragged = atoi(tr);
+    const char *ctr = std::getenv("TPAMD_CARTESIAN_TPB_RAGGED");
+    if (ctr && (atoi(ctr) == 64 || atoi(ctr) == 128 || atoi(ctr) == 256)) e->cartesian_tpb_ragged = atoi(ctr);
     const char *fd = std::getenv("TPAMD_FRONT_DELAY_US");
     if (fd && std::atoi(fd) >= 0 && std::atoi(fd) <= 1000) e->front_delay_us = std::atoi(fd);
     const char *ml = std::getenv("TPAMD_LANES");
@@ -1047,19 +1052,32 @@ int tpamd_engine_set_pipelining(tpamd_engine *e, int on) {
 namespace {
 // The outputs of one solve in `s`; dout receives their device addresses. Every _host solve
 // entry stages its outputs this way.
+// `keep`: the per-sample arrays travel up first, so that entries the solve does not write (beyond a
+// ragged path's count) come back as the caller had them.
 void stage_path_outputs(HostStage &s, size_t B, size_t N, size_t D, const tpamd_path_outputs *out,
-                        tpamd_path_outputs *dout) {
-  s.down(&dout->time, out->time, B * N);
-  s.down(&dout->s, out->s, B * N);
-  s.down(&dout->sd, out->sd, B * N);
-  s.down(&dout->sdd, out->sdd, B * N);
-  s.down(&dout->q, out->q, B * N * D);
-  s.down(&dout->qd, out->qd, B * N * D);
-  s.down(&dout->qdd, out->qdd, B * N * D);
+                        tpamd_path_outputs *dout, bool keep = false) {
+  if (keep) {
+    s.both(&dout->time, out->time, B * N);
+    s.both(&dout->s, out->s, B * N);
+    s.both(&dout->sd, out->sd, B * N);
+    s.both(&dout->sdd, out->sdd, B * N);
+    s.both(&dout->q, out->q, B * N * D);
+    s.both(&dout->qd, out->qd, B * N * D);
+    s.both(&dout->qdd, out->qdd, B * N * D);
+  } else {
+    s.down(&dout->time, out->time, B * N);
+    s.down(&dout->s, out->s, B * N);
+    s.down(&dout->sd, out->sd, B * N);
+    s.down(&dout->sdd, out->sdd, B * N);
+    s.down(&dout->q, out->q, B * N * D);
+    s.down(&dout->qd, out->qd, B * N * D);
+    s.down(&dout->qdd, out->qdd, B * N * D);
+  }
   s.down_or_scratch(&dout->last_extremal_index, out->last_extremal_index, B);
   s.down_or_scratch(&dout->max_time_increment, out->max_time_increment, B);
   s.down(&dout->status, out->status, B);
-  s.down(&dout->sd2, out->sd2, B * N);
+  if (keep) s.both(&dout->sd2, out->sd2, B * N);
+  else s.down(&dout->sd2, out->sd2, B * N);
 }
 
 // The checks of a rows batch after the null structs and B <= 0 (both entries).
@@ -1093,12 +1111,20 @@ int cartesian_args(const tpamd_cartesian_batch *bt, const tpamd_cartesian_inputs
 // finite-difference derivative); out->q is then a gather of the table segments. Planners that are
 // not looping keep the outputs of the sweep (time, s, sd, sdd, status); on the generic route
 // k_epilogue rewrites their qd / qdd from their last records, which nothing reads.
+// A ragged batch entry (`ns` given, no plan) gives path b ns[b] samples in arrays of stride N and
+// reads its rows from first_row[b] of the row tables on, or from [b][0] of a [B][N] batch without
+// first_row; it takes the ragged forms of the set-up kernel and of K1 / k_cartesian_rows, orders
+// the sweep longest path first as solve_joint does, and out->q is a gather. Everything behind
+// those kernels reads the counts through ws.ns.
 int solve_cartesian(tpamd_engine *e, const tpamd_cartesian_batch *bt, const tpamd_cartesian_inputs *in,
-                    const tpamd_path_outputs *out, void *hip_stream, const PlanParams *plan, int table_stride) {
+                    const tpamd_path_outputs *out, void *hip_stream, const PlanParams *plan, int table_stride,
+                    const int32_t *ns = nullptr, const int32_t *first_row = nullptr) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
   if (int rc = cartesian_args(bt, in, out)) return rc;
+  const bool ragged = ns != nullptr;
+  if (ragged && plan) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(e);
   hipStream_t st = (hipStream_t)hip_stream;
   const int C = 2 * D + 2;
@@ -1116,27 +1142,47 @@ int solve_cartesian(tpamd_engine *e, const tpamd_cartesian_batch *bt, const tpam
   int rc = ensure_workspace(e, B, N, C);
   if (rc) return rc;
   e->last_B = B; e->last_N = N; e->last_time = out->time;
-  e->ws.ns = nullptr;
-  e->ws.order = nullptr;
+  e->ws.ns = ns;
+  // ragged batches: sweep workgroups take the paths longest first (k_order_paths), as in solve_joint
+  int32_t *order = const_cast<int32_t *>(e->ws.order);
+  const bool ordered = ragged && B > 1 && e->order_ragged;
+  if (!ordered) e->ws.order = nullptr;
   e->ws.amax = in->max_acceleration;
   {
     Timer t(e, st, KI_SETUP);
-    hipLaunchKernelGGL(k_setup_cartesian, dim3((B + 127) / 128), dim3(128), 0, st, B, N, D,
-                       bt->constraint_safety, in->max_velocity, in->max_acceleration,
-                       in->max_translational_velocity, in->max_rotational_velocity,
-                       in->path_start, in->delta, in->sd_start, in->sdd_start, in->time_start,
-                       e->ws);
+    if (ragged)
+      hipLaunchKernelGGL(k_setup_cartesian_ragged, dim3((B + 127) / 128), dim3(128), 0, st, B, N, D,
+                         bt->constraint_safety, in->max_velocity, in->max_acceleration,
+                         in->max_translational_velocity, in->max_rotational_velocity,
+                         in->path_start, in->delta, in->sd_start, in->sdd_start, in->time_start,
+                         e->ws);
+    else
+      hipLaunchKernelGGL(k_setup_cartesian, dim3((B + 127) / 128), dim3(128), 0, st, B, N, D,
+                         bt->constraint_safety, in->max_velocity, in->max_acceleration,
+                         in->max_translational_velocity, in->max_rotational_velocity,
+                         in->path_start, in->delta, in->sd_start, in->sdd_start, in->time_start,
+                         e->ws);
     if (plan) hipLaunchKernelGGL(k_plan_mark_skipped, dim3(gb), dim3(128), 0, st, pp, e->ws);
+    if (ordered) hipLaunchKernelGGL(k_order_paths, dim3(1), dim3(1024), 0, st, B, N, ns, order);
   }
   if (fused) {
     // rows never materialised: K1 writes records, the joint-structured kernels do the rest
     const Workspace &ws = e->ws;
     {
       Timer t(e, st, KI_SAMPLE_LP);
-      const int tpb = 256;
+      // Ragged batches take 64-thread blocks: fewer threads idle behind a path's end (measured,
+      // 1024 paths of 500..4000 samples, K1 alone: 0.24 / 0.36 / 0.34 ms at 64 / 128 / 256 threads;
+      // profiles/cartesian_ragged_ab.md).
+      const int tpb = ragged ? e->cartesian_tpb_ragged : 256;
       const size_t lds = (2 * (size_t)C + (2 * (size_t)D + 2) * tpb) * 8;
       const dim3 grid((N + tpb - 1) / tpb, B);
-      if (D == 6)
+      if (ragged && D == 6)
+        hipLaunchKernelGGL((k_cartesian_lp<1, 6, true>), grid, dim3(tpb), lds, st, N, in->ik_positions,
+                           in->jacobians, ws, 0, first_row);
+      else if (ragged)
+        hipLaunchKernelGGL((k_cartesian_lp<1, 7, true>), grid, dim3(tpb), lds, st, N, in->ik_positions,
+                           in->jacobians, ws, 0, first_row);
+      else if (D == 6)
         hipLaunchKernelGGL((k_cartesian_lp<1, 6>), grid, dim3(tpb), lds, st, N, in->ik_positions,
                            in->jacobians, ws, stride, first);
       else
@@ -1167,10 +1213,16 @@ int solve_cartesian(tpamd_engine *e, const tpamd_cartesian_batch *bt, const tpam
            *HI = (double *)((char *)e->rows.p + 3 * nrow);
     {
       Timer t(e, st, KI_SETUP);
-      hipLaunchKernelGGL(k_cartesian_rows, dim3((N + 127) / 128, B), dim3(128), 0, st, N, D,
-                         bt->constraint_safety, in->ik_positions, in->jacobians, in->max_velocity,
-                         in->max_acceleration, in->max_translational_velocity,
-                         in->max_rotational_velocity, A, Bm, LO, HI, ws, stride, first);
+      if (ragged)
+        hipLaunchKernelGGL(k_cartesian_rows_ragged, dim3((N + 127) / 128, B), dim3(128), 0, st, N, D,
+                           bt->constraint_safety, in->ik_positions, in->jacobians, in->max_velocity,
+                           in->max_acceleration, in->max_translational_velocity,
+                           in->max_rotational_velocity, A, Bm, LO, HI, ws, first_row);
+      else
+        hipLaunchKernelGGL(k_cartesian_rows, dim3((N + 127) / 128, B), dim3(128), 0, st, N, D,
+                           bt->constraint_safety, in->ik_positions, in->jacobians, in->max_velocity,
+                           in->max_acceleration, in->max_translational_velocity,
+                           in->max_rotational_velocity, A, Bm, LO, HI, ws, stride, first);
       if (plan) hipLaunchKernelGGL(k_plan_project, dim3(gb), dim3(128), 0, st, pp, ws);
     }
     rc = run_rows(e, st, B, N, C, max_loops, A, Bm, LO, HI, out);
@@ -1187,19 +1239,21 @@ int solve_cartesian(tpamd_engine *e, const tpamd_cartesian_batch *bt, const tpam
     if (plan)
       hipLaunchKernelGGL(k_gather_window_q, dim3((unsigned)((N * D + 255) / 256), (unsigned)B), dim3(256), 0, st, N,
                          D, in->ik_positions, stride, first, pp.active, out->q);
+    else if (ragged)
+      hipLaunchKernelGGL(k_gather_ragged_q, dim3((unsigned)((N * D + 255) / 256), (unsigned)B), dim3(256), 0, st, N,
+                         D, in->ik_positions, ns, first_row, out->q);
     else
       HIPCHK(hipMemcpyAsync(out->q, in->ik_positions, (size_t)B * N * D * 8, hipMemcpyDeviceToDevice, st));
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
-}  // namespace
 
-extern "C" {
-
-int tpamd_optimize_rows_device(tpamd_engine *e, const tpamd_rows_batch *bt,
-                               const tpamd_rows_inputs *in, const tpamd_path_outputs *out,
-                               void *hip_stream) {
+// The explicit-rows solve; `ns` (tpamd_optimize_rows_ragged_*) gives path b ns[b] samples in arrays
+// of stride N: the ragged set-up kernel, then what a uniform batch runs (k_lp_rows and everything
+// behind it read the counts through ws.ns), the sweep longest path first.
+int solve_rows(tpamd_engine *e, const tpamd_rows_batch *bt, const tpamd_rows_inputs *in, const int32_t *ns,
+               const tpamd_path_outputs *out, void *hip_stream) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, N = bt->num_samples, C = bt->num_rows;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
@@ -1210,16 +1264,47 @@ int tpamd_optimize_rows_device(tpamd_engine *e, const tpamd_rows_batch *bt,
   int rc = ensure_workspace(e, B, N, 1);
   if (rc) return rc;
   e->last_B = B; e->last_N = N; e->last_time = out->time;
-  e->ws.ns = nullptr;
-  e->ws.order = nullptr;
+  e->ws.ns = ns;
+  int32_t *order = const_cast<int32_t *>(e->ws.order);
+  const bool ordered = ns != nullptr && B > 1 && e->order_ragged;
+  if (!ordered) e->ws.order = nullptr;
   const Workspace &ws = e->ws;
   const int max_loops = bt->max_solver_loops > 0 ? bt->max_solver_loops : 100;
   {
     Timer t(e, st, KI_SETUP);
-    hipLaunchKernelGGL(k_setup_rows, dim3((B + 127) / 128), dim3(128), 0, st, B, N, in->s_start,
-                       in->s_end, in->sd_start, in->sdd_start, in->time_start, ws);
+    if (ns)
+      hipLaunchKernelGGL(k_setup_rows_ragged, dim3((B + 127) / 128), dim3(128), 0, st, B, N, in->s_start,
+                         in->s_end, in->sd_start, in->sdd_start, in->time_start, ws);
+    else
+      hipLaunchKernelGGL(k_setup_rows, dim3((B + 127) / 128), dim3(128), 0, st, B, N, in->s_start,
+                         in->s_end, in->sd_start, in->sdd_start, in->time_start, ws);
+    if (ordered) hipLaunchKernelGGL(k_order_paths, dim3(1), dim3(1024), 0, st, B, N, ns, order);
   }
   return run_rows(e, st, B, N, C, max_loops, in->a, in->b, in->lower, in->upper, out);
+}
+}  // namespace
+
+extern "C" {
+
+int tpamd_optimize_rows_device(tpamd_engine *e, const tpamd_rows_batch *bt,
+                               const tpamd_rows_inputs *in, const tpamd_path_outputs *out,
+                               void *hip_stream) {
+  return solve_rows(e, bt, in, nullptr, out, hip_stream);
+}
+
+int tpamd_optimize_rows_ragged_device(tpamd_engine *e, const tpamd_rows_batch *bt, const tpamd_rows_inputs *in,
+                                      const int32_t *num_samples_per_path, const tpamd_path_outputs *out,
+                                      void *hip_stream) {
+  if (!num_samples_per_path) return TPAMD_E_INVALID_ARGUMENT;
+  return solve_rows(e, bt, in, num_samples_per_path, out, hip_stream);
+}
+
+int tpamd_time_cartesian_paths_ragged_device(tpamd_engine *e, const tpamd_cartesian_batch *bt,
+                                             const tpamd_cartesian_inputs *in,
+                                             const int32_t *num_samples_per_path, const int32_t *first_row,
+                                             const tpamd_path_outputs *out, void *hip_stream) {
+  if (!num_samples_per_path) return TPAMD_E_INVALID_ARGUMENT;
+  return solve_cartesian(e, bt, in, out, hip_stream, nullptr, 0, num_samples_per_path, first_row);
 }
 
 int tpamd_time_cartesian_paths_device(tpamd_engine *e, const tpamd_cartesian_batch *bt,
@@ -1259,6 +1344,60 @@ int tpamd_time_cartesian_paths_host(tpamd_engine *e, const tpamd_cartesian_batch
   if (!rc) rc = s.download(st);
   if (rc) return rc;
   if (out->q && out->q != in->ik_positions) std::memcpy(out->q, in->ik_positions, B * N * D * 8);
+  return 0;
+}
+
+int tpamd_time_cartesian_paths_ragged_host(tpamd_engine *e, const tpamd_cartesian_batch *bt,
+                                           const tpamd_cartesian_inputs *in,
+                                           const int32_t *num_samples_per_path, const int32_t *first_row,
+                                           int64_t num_rows, const tpamd_path_outputs *out) {
+  if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
+  if (!num_samples_per_path) return TPAMD_E_INVALID_ARGUMENT;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = cartesian_args(bt, in, out)) return rc;
+  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
+  if (first_row && (num_rows < 1 || num_rows >= ((int64_t)1 << 31))) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t rows = first_row ? (size_t)num_rows : B * N;
+  // the rows of a path with a usable count must lie inside what is staged
+  if (first_row)
+    for (size_t b = 0; b < B; b++) {
+      const int64_t n = num_samples_per_path[b];
+      if (n < 2 || n > (int64_t)N) continue;
+      if (first_row[b] < 0 || (int64_t)first_row[b] + n > num_rows) return TPAMD_E_INVALID_ARGUMENT;
+    }
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_cartesian_inputs din{};
+  tpamd_path_outputs dout{}, staged = *out;
+  staged.q = nullptr;   // q is a gather of the caller's ik_positions: copied on the host below
+  const int32_t *d_ns = nullptr, *d_first = nullptr;
+  HostStage s;
+  s.up(&din.ik_positions, in->ik_positions, rows * D);
+  s.up(&din.jacobians, in->jacobians, rows * 6 * D);
+  s.up(&din.max_velocity, in->max_velocity, B * D);
+  s.up(&din.max_acceleration, in->max_acceleration, B * D);
+  s.up(&din.max_translational_velocity, in->max_translational_velocity, B);
+  s.up(&din.max_rotational_velocity, in->max_rotational_velocity, B);
+  s.up(&din.path_start, in->path_start, B);
+  s.up(&din.delta, in->delta, B);
+  s.up(&din.sd_start, in->sd_start, B);
+  s.up_or_zero(&din.sdd_start, in->sdd_start, B);
+  s.up(&din.time_start, in->time_start, B);
+  s.up(&d_ns, num_samples_per_path, B);
+  s.up(&d_first, first_row, B);
+  stage_path_outputs(s, B, N, D, &staged, &dout, /*keep=*/true);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = tpamd_time_cartesian_paths_ragged_device(e, bt, &din, d_ns, d_first, &dout, st);
+  if (!rc) rc = s.download(st);
+  if (rc) return rc;
+  if (out->q)
+    for (size_t b = 0; b < B; b++) {
+      const int64_t n = num_samples_per_path[b];
+      if (n < 2 || n > (int64_t)N) continue;
+      const size_t row0 = first_row ? (size_t)first_row[b] : b * N;
+      std::memmove(out->q + b * N * D, in->ik_positions + row0 * D, (size_t)n * D * 8);
+    }
   return 0;
 }
 
@@ -1847,6 +1986,37 @@ int tpamd_optimize_rows_host(tpamd_engine *e, const tpamd_rows_batch *bt,
   int rc = s.upload(e->stage, st);
   if (rc) return rc;
   rc = tpamd_optimize_rows_device(e, bt, &din, &dout, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_optimize_rows_ragged_host(tpamd_engine *e, const tpamd_rows_batch *bt, const tpamd_rows_inputs *in,
+                                    const int32_t *num_samples_per_path, const tpamd_path_outputs *out) {
+  if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
+  if (!num_samples_per_path) return TPAMD_E_INVALID_ARGUMENT;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = rows_args(bt, in, out)) return rc;
+  const size_t B = bt->num_paths, N = bt->num_samples, C = bt->num_rows;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_rows_inputs din{};
+  tpamd_path_outputs dout{}, staged = *out;
+  staged.q = staged.qd = staged.qdd = nullptr;   // a rows solve has no joint values
+  const int32_t *d_ns = nullptr;
+  HostStage s;
+  s.up(&din.a, in->a, B * N * C);
+  s.up(&din.b, in->b, B * N * C);
+  s.up(&din.lower, in->lower, B * N * C);
+  s.up(&din.upper, in->upper, B * N * C);
+  s.up(&din.s_start, in->s_start, B);
+  s.up(&din.s_end, in->s_end, B);
+  s.up(&din.sd_start, in->sd_start, B);
+  s.up_or_zero(&din.sdd_start, in->sdd_start, B);
+  s.up(&din.time_start, in->time_start, B);
+  s.up(&d_ns, num_samples_per_path, B);
+  stage_path_outputs(s, B, N, 0, &staged, &dout, /*keep=*/true);
+  int rc = s.upload(e->stage, st);
+  if (rc) return rc;
+  rc = tpamd_optimize_rows_ragged_device(e, bt, &din, d_ns, &dout, st);
   return rc ? rc : s.download(st);
 }
 

@@ -11,12 +11,15 @@
 //                 q''[N-1] = 0) and ConstraintSetup :551-595 (the 2D joint rows plus two rows
 //                 bounding |(J q')_{1..3}|^2 and |(J q')_{4..6}|^2 with lower = -upper; J q' is
 //                 accumulated over the dofs in index order)
-// Both compile for the host as well (TPAMD_HD): tests/cpp/test_cartesian_window.cc holds them
+//   cw_ragged_count / cw_ragged_first_row / cw_rows_ragged_at  the same arithmetic for a path of a
+//                 ragged batch: its own sample count, its own first row (strided or packed)
+// All compile for the host as well (TPAMD_HD): tests/cpp/test_cartesian_window.cc holds them
 // against the CPU restatement of the reference, bit for bit. k_plan_begin and k_cartesian_rows
 // (tpamd_kernels.h) call them.
 #pragma once
 
 #include <math.h>
+#include <stddef.h>
 
 #ifndef TPAMD_HD
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -162,6 +165,31 @@ TPAMD_HD inline void cw_rows_at(int i, int N, int D, double inv_delta, const dou
   bb[2 * D + 1] = (v6[3] * v6[3] + v6[4] * v6[4]) + v6[5] * v6[5];
   hi[2 * D + 1] = vr * vr;
   lo[2 * D + 1] = -(vr * vr);
+}
+
+// Ragged Cartesian batches (tpamd_time_cartesian_paths_ragged_*): path b has ns[b] samples in arrays
+// of stride `stride`, and its rows start at first_row[b] of a row table or, without first_row, at
+// b * stride of a [B][stride] batch. A count outside [2, stride] fails the path in the set-up kernel;
+// the kernels that read rows treat it as a path of no samples, so none of its rows is touched.
+TPAMD_HD inline int cw_ragged_count(int n, int stride) { return (n >= 2 && n <= stride) ? n : 0; }
+TPAMD_HD inline size_t cw_ragged_first_row(const int *first_row, int b, int stride) {
+  return first_row ? (size_t)first_row[b] : (size_t)b * stride;
+}
+// cw_rows_at for sample i of path b of a ragged batch: the window is the path's own ns[b] rows, so
+// the end conditions sit at ns[b] - 1 whatever follows the path in the table. q_table / J_table are
+// the whole inputs; vmax / amax the path's limits. False (nothing read or written) for i >= the
+// path's count.
+TPAMD_HD inline bool cw_rows_ragged_at(int b, int i, int stride, int D, const int *ns, const int *first_row,
+                                       double inv_delta, const double *q_table, const double *J_table,
+                                       const double *vmax, const double *amax, double safety, double vt, double vr,
+                                       double *rec, double *a, double *bb, double *lo, double *hi,
+                                       double *jq1 = nullptr) {
+  const int n = cw_ragged_count(ns[b], stride);
+  if (i >= n) return false;
+  const size_t row = cw_ragged_first_row(first_row, b, stride) + (size_t)i;
+  cw_rows_at(i, n, D, inv_delta, q_table + row * D, J_table + row * 6 * D, vmax, amax, safety, vt, vr, rec, a, bb,
+             lo, hi, jq1);
+  return true;
 }
 
 }  // namespace tpamd

@@ -214,22 +214,37 @@ static __global__ void k_delay(int ticks) {
   } while ((long long)(t - t0) < ticks);
 }
 
-static __global__ void k_setup_rows(int B, int N, const double *s_start, const double *s_end,
-                             const double *sd_start, const double *sdd_start,
-                             const double *t_start, Workspace ws) {
+// RAGGED (a compile-time switch: the uniform kernel keeps its code): path b has ws.ns[b] samples,
+// ds = (s_end - s_start) / (ns[b] - 1); a count outside [2, N] fails the path as k_setup_joint does.
+template <bool RAGGED>
+__device__ __forceinline__ void setup_rows_body(int B, int N, const double *s_start, const double *s_end,
+                                                const double *sd_start, const double *sdd_start,
+                                                const double *t_start, const Workspace &ws) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
+  const int Nb = RAGGED ? path_samples(ws, b, N) : N;
+  const bool too_many = RAGGED && ws.ns[b] > N;
   uint32_t bits = 0;
   if (s_start[b] >= s_end[b]) bits |= kErrSRange;
   if (sd_start[b] < 0) bits |= kErrSdStartNeg;
-  if (N < 2) bits |= kErrTooFew;
+  if (Nb < 2 || too_many) bits |= kErrTooFew;
   ws.err_bits[b] = bits;  // per-sample bits are OR-ed in by k_lp_rows
   ws.s_start[b] = s_start[b];
   ws.s_end[b] = s_end[b];
-  ws.ds[b] = (s_end[b] - s_start[b]) / (N - 1);
+  ws.ds[b] = (s_end[b] - s_start[b]) / (Nb - 1);
   ws.sd_start[b] = sd_start[b];
   ws.sdd_start[b] = sdd_start ? sdd_start[b] : 0.0;
   ws.t_start[b] = t_start[b];
+}
+static __global__ void k_setup_rows(int B, int N, const double *s_start, const double *s_end,
+                             const double *sd_start, const double *sdd_start,
+                             const double *t_start, Workspace ws) {
+  setup_rows_body<false>(B, N, s_start, s_end, sd_start, sdd_start, t_start, ws);
+}
+static __global__ void k_setup_rows_ragged(int B, int N, const double *s_start, const double *s_end,
+                                    const double *sd_start, const double *sdd_start,
+                                    const double *t_start, Workspace ws) {
+  setup_rows_body<true>(B, N, s_start, s_end, sd_start, sdd_start, t_start, ws);
 }
 
 // ------------------------------------------------- pass 1, common tail per sample
@@ -526,17 +541,64 @@ static __global__ void k_cartesian_rows(int N, int D, double safety, const doubl
              LO + o * C, HI + o * C);
 }
 
+// k_cartesian_rows for a ragged batch (tpamd_time_cartesian_paths_ragged_*): path b has ws.ns[b]
+// samples, its rows start at first_row[b] of the row tables q_g / J_g (packed) or at b * N (first_row
+// null); the arithmetic is cw_rows_ragged_at. Outputs keep the stride N. A path whose count the
+// set-up kernel refused has none of its input rows read; the constraint rows k_lp_rows would still
+// visit for it (min(ws.ns[b], N) samples, results dropped) get fixed well-posed values instead of
+// staying what an earlier call left there.
+static __global__ void k_cartesian_rows_ragged(int N, int D, double safety, const double *q_g,
+                                        const double *J_g, const double *vmax, const double *amax,
+                                        const double *vtrans, const double *vrot, double *A,
+                                        double *Bm, double *LO, double *HI, Workspace ws,
+                                        const int32_t *first_row) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int C = 2 * D + 2;
+  const size_t o = (size_t)b * N + i;
+  if (cw_ragged_count(ws.ns[b], N) == 0) {
+    // (k_lp_rows ORs what it finds wrong with a sample's rows into the path's error bits, which must
+    // stay those of the set-up kernel: well-posed rows, those of q' = 1, q'' = 0 under unit limits)
+    if (i < path_samples(ws, b, N))
+      for (int c = 0; c < C; c++) {
+        A[o * C + c] = c < D ? 1.0 : 0.0;
+        Bm[o * C + c] = c < D ? 0.0 : 1.0;
+        LO[o * C + c] = (c >= D && c < 2 * D) ? 0.0 : -1.0;
+        HI[o * C + c] = 1.0;
+      }
+    return;
+  }
+  cw_rows_ragged_at(b, i, N, D, ws.ns, first_row, 1.0 / ws.delta[b], q_g, J_g, vmax + (size_t)b * D,
+                    amax + (size_t)b * D, safety, vtrans[b], vrot[b], ws.q12 + o * (2 * D + 2), A + o * C,
+                    Bm + o * C, LO + o * C, HI + o * C);
+}
+
+// out->q of a ragged Cartesian batch: path b's rows to [b][0 .. ns[b])[D]. grid = (ceil(N D / 256), B).
+static __global__ void k_gather_ragged_q(int N, int D, const double *q_g, const int32_t *ns,
+                                  const int32_t *first_row, double *q_out) {
+  const int b = blockIdx.y;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= cw_ragged_count(ns[b], N) * D) return;
+  q_out[(size_t)b * N * D + k] = q_g[cw_ragged_first_row(first_row, b, N) * D + k];
+}
+
 // Setup for Cartesian paths: s_end = path_start + delta (N-1) as
 // path_timing_trajectory.cc:340-341; the limit rows of
 // timeable_path_cartesian_spline.cc:559-592 (C = 2D+2 per path, constant along the path) and
 // the SetupProblem / IsSetupValid checks on them (time_optimal_path_timing.cc:174-175, :557).
-static __global__ void k_setup_cartesian(int B, int N, int D, double safety, const double *vmax,
-                                  const double *amax, const double *vtrans, const double *vrot,
-                                  const double *path_start, const double *delta,
-                                  const double *sd_start, const double *sdd_start,
-                                  const double *t_start, Workspace ws) {
+// RAGGED (a compile-time switch: the uniform kernel keeps its code): path b has ws.ns[b] samples in
+// place of N, and a count outside [2, N] fails the path exactly as k_setup_joint fails it.
+template <bool RAGGED>
+__device__ __forceinline__ void setup_cartesian_body(int B, int N_launch, int D, double safety, const double *vmax,
+                                                     const double *amax, const double *vtrans, const double *vrot,
+                                                     const double *path_start, const double *delta,
+                                                     const double *sd_start, const double *sdd_start,
+                                                     const double *t_start, const Workspace &ws) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
+  const int N = RAGGED ? path_samples(ws, b, N_launch) : N_launch;
+  const bool too_many = RAGGED && ws.ns[b] > N_launch;
   const int C = 2 * D + 2;
   double *lo = ws.lim + (size_t)b * 2 * C, *hi = lo + C;
   for (int d = 0; d < D; d++) {
@@ -562,7 +624,7 @@ static __global__ void k_setup_cartesian(int B, int N, int D, double safety, con
   if (s0 >= s1) bits |= kErrSRange;
   if (sd_start[b] < 0) bits |= kErrSdStartNeg;
   if (lower_ge_upper) bits |= kErrLowerGeUpper;
-  if (N < 2) bits |= kErrTooFew;
+  if (N < 2 || too_many) bits |= kErrTooFew;   // (ragged: count outside [2, stride])
   ws.err_bits[b] = bits;
   ws.s_start[b] = s0;
   ws.s_end[b] = s1;
@@ -571,6 +633,22 @@ static __global__ void k_setup_cartesian(int B, int N, int D, double safety, con
   ws.sdd_start[b] = sdd_start ? sdd_start[b] : 0.0;
   ws.t_start[b] = t_start[b];
   ws.delta[b] = delta[b];
+}
+static __global__ void k_setup_cartesian(int B, int N, int D, double safety, const double *vmax,
+                                  const double *amax, const double *vtrans, const double *vrot,
+                                  const double *path_start, const double *delta,
+                                  const double *sd_start, const double *sdd_start,
+                                  const double *t_start, Workspace ws) {
+  setup_cartesian_body<false>(B, N, D, safety, vmax, amax, vtrans, vrot, path_start, delta, sd_start, sdd_start,
+                              t_start, ws);
+}
+static __global__ void k_setup_cartesian_ragged(int B, int N, int D, double safety, const double *vmax,
+                                         const double *amax, const double *vtrans, const double *vrot,
+                                         const double *path_start, const double *delta,
+                                         const double *sd_start, const double *sdd_start,
+                                         const double *t_start, Workspace ws) {
+  setup_cartesian_body<true>(B, N, D, safety, vmax, amax, vtrans, vrot, path_start, delta, sd_start, sdd_start,
+                             t_start, ws);
 }
 
 // K1 for Cartesian paths with the joint count fixed at compile time: the arithmetic of
@@ -581,23 +659,32 @@ static __global__ void k_setup_cartesian(int B, int N, int D, double safety, con
 // Inputs as for k_cartesian_rows: [B][N] rows (table_stride = N, first = null), or the window of
 // each planner's IK table that starts at row first[b]. A block's Jacobians stay one contiguous,
 // 16-byte aligned run either way (a sample's six Jacobian rows are 48 D bytes).
-template <int WORDS, int D>
-__global__ void k_cartesian_lp(int N, const double *q_g, const double *J_g, Workspace ws, int table_stride,
+// RAGGED (tpamd_time_cartesian_paths_ragged_*; a compile-time switch, the other instances keep their
+// code): N_launch is the stride of the workspace and the outputs, path b has ws.ns[b] samples in its
+// place everywhere else -- `live`, the block's valid samples and both end conditions of the
+// differences -- and its rows start at first[b] of the row tables (packed) or at b * N_launch (first
+// null; table_stride is not used). Blocks behind the path's end, and every block of a path whose
+// count the set-up kernel refused, leave at once.
+template <int WORDS, int D, bool RAGGED = false>
+__global__ void k_cartesian_lp(int N_launch, const double *q_g, const double *J_g, Workspace ws, int table_stride,
                                const int *first) {
   extern __shared__ double lds[];
   constexpr int C = 2 * D + 2;
   const int TPB = blockDim.x;
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
-  if (first && (ws.err_bits[b] & kErrSkip)) return;   // window chaining: this planner is not looping
-  const size_t row0 = (size_t)b * table_stride + (first ? first[b] : 0);
+  if (!RAGGED && first && (ws.err_bits[b] & kErrSkip)) return;   // window chaining: this planner is not looping
+  const int N = RAGGED ? cw_ragged_count(ws.ns[b], N_launch) : N_launch;   // samples of this path
+  if (RAGGED && (int)(blockIdx.x * TPB) >= N) return;
+  const size_t row0 = RAGGED ? cw_ragged_first_row(first, b, N_launch)
+                             : (size_t)b * table_stride + (first ? first[b] : 0);
   double *s_lo = lds, *s_hi = s_lo + C;
   double *s_Q1 = s_hi + C, *s_Q2 = s_Q1 + (size_t)D * TPB, *s_X = s_Q2 + (size_t)D * TPB;
   for (int k = tid; k < 2 * C; k += TPB) s_lo[k] = ws.lim[(size_t)b * 2 * C + k];
   const int i0 = blockIdx.x * TPB;
   const int i = i0 + tid;
   const bool live = i < N;
-  const size_t o = (size_t)b * N + (live ? i : N - 1);
+  const size_t o = (size_t)b * N_launch + (live ? i : N - 1);
   const double inv = 1.0 / ws.delta[b];
   const double *q = q_g + (row0 + (live ? i : N - 1)) * D;
   double *Q1 = s_Q1 + tid, *Q2 = s_Q2 + tid, *X = s_X + tid;
@@ -665,7 +752,7 @@ __global__ void k_cartesian_lp(int N, const double *q_g, const double *J_g, Work
   __syncthreads();
   {
     const int nvalid = min(TPB, N - i0);
-    double2 *recs = reinterpret_cast<double2 *>(ws.q12 + ((size_t)b * N + i0) * (C + 2));
+    double2 *recs = reinterpret_cast<double2 *>(ws.q12 + ((size_t)b * N_launch + i0) * (C + 2));
     constexpr int pairs = D + 2;
     for (int c = tid; c < nvalid * pairs; c += TPB) {
       const int sm = c / pairs, pr = c - sm * pairs;

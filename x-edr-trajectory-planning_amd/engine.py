@@ -227,6 +227,8 @@ ABI_SYMBOLS = [
     "tpamd_time_joint_groups_device", "tpamd_time_joint_groups_host",
     "tpamd_optimize_rows_device", "tpamd_optimize_rows_host",
     "tpamd_time_cartesian_paths_device", "tpamd_time_cartesian_paths_host",
+    "tpamd_optimize_rows_ragged_device", "tpamd_optimize_rows_ragged_host",
+    "tpamd_time_cartesian_paths_ragged_device", "tpamd_time_cartesian_paths_ragged_host",
     "tpamd_sample_pose_splines_device", "tpamd_sample_pose_splines_host",
     "tpamd_plan_joint_windows_host",
     "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
@@ -336,6 +338,20 @@ def load_library():
     L.tpamd_time_cartesian_paths_host.argtypes = [vp, C.POINTER(_CartesianBatch),
                                                   C.POINTER(_CartesianInputs),
                                                   C.POINTER(_PathOutputs)]
+    L.tpamd_optimize_rows_ragged_device.restype = i
+    L.tpamd_optimize_rows_ragged_device.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp,
+                                                    C.POINTER(_PathOutputs), vp]
+    L.tpamd_optimize_rows_ragged_host.restype = i
+    L.tpamd_optimize_rows_ragged_host.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp,
+                                                  C.POINTER(_PathOutputs)]
+    L.tpamd_time_cartesian_paths_ragged_device.restype = i
+    L.tpamd_time_cartesian_paths_ragged_device.argtypes = [vp, C.POINTER(_CartesianBatch),
+                                                           C.POINTER(_CartesianInputs), vp, vp,
+                                                           C.POINTER(_PathOutputs), vp]
+    L.tpamd_time_cartesian_paths_ragged_host.restype = i
+    L.tpamd_time_cartesian_paths_ragged_host.argtypes = [vp, C.POINTER(_CartesianBatch),
+                                                         C.POINTER(_CartesianInputs), vp, vp, C.c_int64,
+                                                         C.POINTER(_PathOutputs)]
     L.tpamd_sample_pose_splines_host.restype = i
     L.tpamd_sample_pose_splines_host.argtypes = [vp, i, i, i] + [vp] * 6
     L.tpamd_sample_pose_splines_device.restype = i
@@ -508,6 +524,22 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _int32_array(t, n, name):
+    """A contiguous int32 array of n entries (torch tensor or numpy array), as the C-ABI reads it."""
+    if isinstance(t, np.ndarray):
+        if t.dtype != np.int32:
+            raise TpamdError("%s must be int32" % name)
+        t = np.ascontiguousarray(t)
+    else:
+        import torch
+        if t.dtype != torch.int32:
+            raise TpamdError("%s must be int32" % name)
+        t = t.contiguous()
+    if tuple(t.shape) != (n,):
+        raise TpamdError("%s must have shape (%d,)" % (name, n))
+    return t
+
+
 class Engine:
     """One engine per GPU (tpamd_engine_create/destroy)."""
 
@@ -613,7 +645,11 @@ class Engine:
         return tuple(out)
 
     # ------------------------------------------------------- constraint rows
-    def optimize_rows(self, inputs, outputs, max_solver_loops=0, stream=None, host=False):
+    def optimize_rows(self, inputs, outputs, max_solver_loops=0, stream=None, host=False,
+                      num_samples_per_path=None):
+        """num_samples_per_path [B] int32 (a tensor on the device, or a numpy array with host=True):
+        a ragged batch, path b has that many samples in arrays of stride N
+        (tpamd_optimize_rows_ragged_*)."""
         a = inputs["a"]
         B, N, Cn = a.shape
         bt = _RowsBatch(B, N, Cn, int(max_solver_loops))
@@ -623,6 +659,17 @@ class Engine:
         po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
             "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
             "max_time_increment", "status", "sd2")])
+        if num_samples_per_path is not None:
+            ns = _int32_array(num_samples_per_path, B, "num_samples_per_path")
+            if host:
+                _check(self._lib.tpamd_optimize_rows_ragged_host(self._h, C.byref(bt), C.byref(ri), _ptr(ns),
+                                                                 C.byref(po)),
+                       "tpamd_optimize_rows_ragged_host")
+            else:
+                _check(self._lib.tpamd_optimize_rows_ragged_device(self._h, C.byref(bt), C.byref(ri), _ptr(ns),
+                                                                   C.byref(po), _stream_ptr(stream)),
+                       "tpamd_optimize_rows_ragged_device")
+            return
         if host:
             _check(self._lib.tpamd_optimize_rows_host(self._h, C.byref(bt), C.byref(ri),
                                                       C.byref(po)), "tpamd_optimize_rows_host")
@@ -633,12 +680,56 @@ class Engine:
 
     # ------------------------------------------------------- Cartesian paths
     def time_cartesian_paths(self, inputs, outputs, safety=0.8, max_solver_loops=0, stream=None,
-                             host=False):
+                             host=False, num_samples_per_path=None, first_row=None):
         """inputs: ik_positions [B][N][D], jacobians [B][N][6][D], max_velocity,
         max_acceleration [B][D], max_translational_velocity, max_rotational_velocity,
         path_start, delta, sd_start, time_start [B] (+ optional sdd_start). outputs as for
-        time_joint_paths (q, if given, receives the IK positions)."""
-        B, N, D = inputs["ik_positions"].shape
+        time_joint_paths (q, if given, receives the IK positions).
+
+        Ragged batches (tpamd_time_cartesian_paths_ragged_*): num_samples_per_path [B] int32 gives
+        path b its own sample count in arrays of stride N. With first_row [B] int32 the inputs are
+        packed row tables, ik_positions [rows][D] and jacobians [rows][6][D], path b reading rows
+        first_row[b] .. first_row[b] + n[b] - 1 (what sample_ik_targets writes, first_row =
+        row_offsets[:B]); B and the stride N are then those of outputs["time"] [B][N]. first_row
+        alone means every path has N samples. Both are device tensors, or numpy arrays with
+        host=True."""
+        ik = inputs["ik_positions"]
+        if num_samples_per_path is not None or first_row is not None:
+            if first_row is None:
+                B, N, D = ik.shape
+            else:
+                if len(ik.shape) != 2:
+                    raise TpamdError("packed inputs: ik_positions must be [rows][D]")
+                rows, D = ik.shape
+                B, N = outputs["time"].shape
+                if inputs["jacobians"].shape[0] != rows:
+                    raise TpamdError("packed inputs: jacobians must have one [6][D] block per row")
+            if num_samples_per_path is None:
+                if host:
+                    num_samples_per_path = np.full(B, N, dtype=np.int32)
+                else:
+                    import torch
+                    num_samples_per_path = torch.full((B,), N, dtype=torch.int32, device=ik.device)
+            ns = _int32_array(num_samples_per_path, B, "num_samples_per_path")
+            fr = None if first_row is None else _int32_array(first_row, B, "first_row")
+            bt = _CartesianBatch(B, D, N, int(max_solver_loops), float(safety))
+            ci = _CartesianInputs(*[_ptr(inputs.get(k)) for k in _CARTESIAN_INPUT_KEYS])
+            po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
+                "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
+                "max_time_increment", "status", "sd2")])
+            if host:
+                _check(self._lib.tpamd_time_cartesian_paths_ragged_host(
+                    self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr),
+                    int(ik.shape[0]) if fr is not None else 0, C.byref(po)),
+                    "tpamd_time_cartesian_paths_ragged_host")
+            else:
+                _check(self._lib.tpamd_time_cartesian_paths_ragged_device(
+                    self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr), C.byref(po), _stream_ptr(stream)),
+                    "tpamd_time_cartesian_paths_ragged_device")
+                # the engine reads the two arrays until the stream has run the call
+                self._ragged_keepalive = (ns, fr)
+            return
+        B, N, D = ik.shape
         bt = _CartesianBatch(B, D, N, int(max_solver_loops), float(safety))
         ci = _CartesianInputs(*[_ptr(inputs.get(k)) for k in _CARTESIAN_INPUT_KEYS])
         po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (

@@ -1,9 +1,7 @@
 #include "batch_cartesian_timing.h"
 
 #include <algorithm>
-#include <map>
 #include <thread>
-#include <tuple>
 
 #include "engine_handle.h"
 
@@ -65,38 +63,57 @@ Status BatchCartesianTiming::ComputeTimingProfiles(double time_start_sec, BatchT
   std::vector<int32_t> begin(nd + 1);
   tpamd_shard_bounds_balanced((int)Bt, cost.data(), nd, begin.data());
   std::vector<Status> st(nd, OkStatus());
+  std::vector<int> calls(nd, 0);
   std::vector<std::thread> threads;
   for (int k = 1; k < nd; k++)
-    threads.emplace_back([&, k] { st[k] = ComputeBlock(devices[k], begin[k], begin[k + 1], time_start_sec, r); });
-  st[0] = ComputeBlock(devices[0], begin[0], begin[1], time_start_sec, r);
+    threads.emplace_back(
+        [&, k] { st[k] = ComputeBlock(devices[k], begin[k], begin[k + 1], time_start_sec, r, &calls[k]); });
+  st[0] = ComputeBlock(devices[0], begin[0], begin[1], time_start_sec, r, &calls[0]);
   for (auto &t : threads) t.join();
+  engine_calls_ = 0;
+  for (int c : calls) engine_calls_ += c;
   for (const Status &s : st)
     if (!s.ok()) return s;
   return OkStatus();
 }
 
 Status BatchCartesianTiming::ComputeBlock(int device, size_t lo, size_t hi, double time_start_sec,
-                                          BatchTimingResult *r) const {
+                                          BatchTimingResult *r, int *engine_calls) const {
+  *engine_calls = 0;
   if (hi <= lo) return OkStatus();
   ::tpamd::EngineLease lease = ::tpamd::acquire_engine(device);
   tpamd_engine *engine = lease.get();
   if (!engine) return InternalError("no GPU engine");
-  std::map<std::tuple<size_t, size_t, double>, std::vector<size_t>> groups;
-  for (size_t b = lo; b < hi; b++)
-    groups[std::make_tuple(paths_[b].ik_positions[0].size(), paths_[b].ik_positions.size(),
-                           paths_[b].constraint_safety)].push_back(b);
+  std::vector<size_t> dofs(paths_.size()), samples(paths_.size());
+  std::vector<double> safety(paths_.size());
+  for (size_t b = lo; b < hi; b++) {
+    dofs[b] = paths_[b].ik_positions[0].size();
+    samples[b] = paths_[b].ik_positions.size();
+    safety[b] = paths_[b].constraint_safety;
+  }
 
-  for (const auto &kv : groups) {
-    const std::vector<size_t> &ids = kv.second;
-    const size_t B = ids.size(), D = std::get<0>(kv.first), N = std::get<1>(kv.first);
-    std::vector<double> q(B * N * D), J(B * N * 6 * D), vmax(B * D), amax(B * D), vt(B), vr(B), ps(B),
+  for (const std::vector<size_t> &ids : CartesianTimingBuckets(dofs, samples, safety, lo, hi)) {
+    // one ragged call: the rows of the bucket's paths packed path after path, outputs of the
+    // stride of its longest path
+    const size_t B = ids.size(), D = dofs[ids[0]];
+    size_t N = 0, rows = 0;
+    std::vector<int32_t> count(B), first(B);
+    for (size_t g = 0; g < B; g++) {
+      count[g] = (int32_t)samples[ids[g]];
+      first[g] = (int32_t)rows;
+      rows += samples[ids[g]];
+      N = std::max(N, samples[ids[g]]);
+    }
+    if (rows >= ((size_t)1 << 31)) return InvalidArgumentError("too many samples in one bucket");
+    std::vector<double> q(rows * D), J(rows * 6 * D), vmax(B * D), amax(B * D), vt(B), vr(B), ps(B),
         dl(B), sd0(B), sdd0(B, 0.0), t0(B, time_start_sec);
     for (size_t g = 0; g < B; g++) {
       const CartesianPathSamples &p = paths_[ids[g]];
-      for (size_t i = 0; i < N; i++) {
-        std::copy(p.ik_positions[i].begin(), p.ik_positions[i].end(), q.begin() + (g * N + i) * D);
+      for (size_t i = 0; i < (size_t)count[g]; i++) {
+        const size_t row = (size_t)first[g] + i;
+        std::copy(p.ik_positions[i].begin(), p.ik_positions[i].end(), q.begin() + row * D);
         // the user's callback, once per sample, as ConstraintSetup does (:576)
-        const Status st = p.jacobian(p.ik_positions[i], &J[(g * N + i) * 6 * D]);
+        const Status st = p.jacobian(p.ik_positions[i], &J[row * 6 * D]);
         if (!st.ok()) return st;
       }
       for (size_t d = 0; d < D; d++) {
@@ -108,26 +125,28 @@ Status BatchCartesianTiming::ComputeBlock(int device, size_t lo, size_t hi, doub
     }
     std::vector<double> time(B * N), s(B * N), sd(B * N), sdd(B * N), qd(B * N * D), qdd(B * N * D);
     std::vector<int32_t> status(B, -1), lei(B, 0);
-    tpamd_cartesian_batch batch{(int)B, (int)D, (int)N, 0, std::get<2>(kv.first)};
+    tpamd_cartesian_batch batch{(int)B, (int)D, (int)N, 0, safety[ids[0]]};
     tpamd_cartesian_inputs in{q.data(), J.data(), vmax.data(), amax.data(), vt.data(), vr.data(),
                               ps.data(), dl.data(), sd0.data(), sdd0.data(), t0.data()};
     tpamd_path_outputs out{time.data(), s.data(), sd.data(), sdd.data(), nullptr, qd.data(), qdd.data(),
                            lei.data(), nullptr, status.data(), nullptr};
     {
-      const int rc = tpamd_time_cartesian_paths_host(engine, &batch, &in, &out);
+      const int rc = tpamd_time_cartesian_paths_ragged_host(engine, &batch, &in, count.data(), first.data(),
+                                                            (int64_t)rows, &out);
+      ++*engine_calls;
       if (rc != 0) return InternalError(tpamd_error_string(rc));
     }
     for (size_t g = 0; g < B; g++) {
-      const size_t b = ids[g];
+      const size_t b = ids[g], n = (size_t)count[g];
       r->status[b] = status[g]; r->last_extremal_index[b] = lei[g];
-      std::copy_n(q.begin() + g * N * D, N * D, r->q.begin() + r->joint_offset[b]);
+      std::copy_n(q.begin() + (size_t)first[g] * D, n * D, r->q.begin() + r->joint_offset[b]);
       if (status[g] != 0) continue;
-      std::copy_n(time.begin() + g * N, N, r->time.begin() + r->sample_offset[b]);
-      std::copy_n(s.begin() + g * N, N, r->s.begin() + r->sample_offset[b]);
-      std::copy_n(sd.begin() + g * N, N, r->sd.begin() + r->sample_offset[b]);
-      std::copy_n(sdd.begin() + g * N, N, r->sdd.begin() + r->sample_offset[b]);
-      std::copy_n(qd.begin() + g * N * D, N * D, r->qd.begin() + r->joint_offset[b]);
-      std::copy_n(qdd.begin() + g * N * D, N * D, r->qdd.begin() + r->joint_offset[b]);
+      std::copy_n(time.begin() + g * N, n, r->time.begin() + r->sample_offset[b]);
+      std::copy_n(s.begin() + g * N, n, r->s.begin() + r->sample_offset[b]);
+      std::copy_n(sd.begin() + g * N, n, r->sd.begin() + r->sample_offset[b]);
+      std::copy_n(sdd.begin() + g * N, n, r->sdd.begin() + r->sample_offset[b]);
+      std::copy_n(qd.begin() + g * N * D, n * D, r->qd.begin() + r->joint_offset[b]);
+      std::copy_n(qdd.begin() + g * N * D, n * D, r->qdd.begin() + r->joint_offset[b]);
     }
   }
   return OkStatus();

@@ -6,11 +6,15 @@
 // Jacobian callback per sample, :576), the solver and the planner epilogue. This class
 // takes over from the point where the IK solution exists: per path the IK positions
 // (path_position_) and the Jacobian callback. The callbacks run on the host, everything
-// after them on the GPU (tpamd_time_cartesian_paths_host).
+// after them on the GPU (tpamd_time_cartesian_paths_ragged_host: paths of different lengths share
+// one call).
 #ifndef TPAMD_HOST_BATCH_CARTESIAN_TIMING_H_
 #define TPAMD_HOST_BATCH_CARTESIAN_TIMING_H_
 
 #include <functional>
+#include <map>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "batch_path_timing.h"
@@ -33,10 +37,30 @@ struct CartesianPathSamples {
   double start_velocity = 0.0;            // path_start_velocity_ (sd at the first sample)
 };
 
+// The engine calls of a block of paths: paths lo .. hi - 1 bucketed by (dofs, constraint safety,
+// ceil(samples / 512)), as BatchPathTiming buckets joint paths. Every bucket is one
+// ragged engine call whose stride is its largest sample count, so a bucket's stride is less than
+// 512 above its shortest path. The buckets come in key order, the paths of a bucket in index order.
+// A pure function of the three lists (dofs / samples / safety: one entry per path).
+constexpr size_t kCartesianSampleBucket = 512;
+inline std::vector<std::vector<size_t>> CartesianTimingBuckets(const std::vector<size_t> &dofs,
+                                                               const std::vector<size_t> &samples,
+                                                               const std::vector<double> &safety, size_t lo,
+                                                               size_t hi) {
+  std::map<std::tuple<size_t, double, size_t>, std::vector<size_t>> keyed;
+  for (size_t b = lo; b < hi; b++)
+    keyed[std::make_tuple(dofs[b], safety[b], (samples[b] + kCartesianSampleBucket - 1) / kCartesianSampleBucket)]
+        .push_back(b);
+  std::vector<std::vector<size_t>> buckets;
+  for (auto &kv : keyed) buckets.push_back(std::move(kv.second));
+  return buckets;
+}
+
 class BatchCartesianTiming {
  public:
-  // Paths may differ in joint count and sample count; they are grouped by
-  // (dofs, samples, constraint safety), one engine call per group.
+  // Paths may differ in joint count and sample count; they are bucketed by (dofs, constraint safety,
+  // ceil(samples / 512)) -- CartesianTimingBuckets -- and every bucket is one ragged engine call
+  // (tpamd_time_cartesian_paths_ragged_host) on the packed rows of its paths.
   Status SetPaths(std::vector<CartesianPathSamples> paths);
   // HIP devices that share the batch: contiguous blocks of roughly equal cost (samples x rows^2),
   // one engine from the pool and one host thread per device (the Jacobian callbacks of a block run
@@ -45,11 +69,15 @@ class BatchCartesianTiming {
   Status SetDevices(const std::vector<int> &devices);
   // Results in the packed layout of BatchTimingResult; q holds the IK positions.
   Status ComputeTimingProfiles(double time_start_sec, BatchTimingResult *result);
+  // Engine calls the last ComputeTimingProfiles made, over all devices: its number of buckets.
+  int EngineCallsOfLastCompute() const { return engine_calls_; }
 
  private:
-  Status ComputeBlock(int device, size_t lo, size_t hi, double time_start_sec, BatchTimingResult *r) const;
+  Status ComputeBlock(int device, size_t lo, size_t hi, double time_start_sec, BatchTimingResult *r,
+                      int *engine_calls) const;
   std::vector<CartesianPathSamples> paths_;
   std::vector<int> devices_;
+  int engine_calls_ = 0;
 };
 
 }  // namespace trajectory_planning
