@@ -87,6 +87,28 @@ def test_product_does_not_touch_the_oracle():
                 assert "from oracle" not in text and "import oracle" not in text, f
 
 
+def test_environment_switches_are_the_documented_ones():
+    """Every TPAMD_* variable the native code reads is in the table of INTEGRATION.md section 4, and
+    the table lists nothing else (TPAMD_LIBRARY is read by the ctypes binding). Text only."""
+    read = set()
+    for sub in ("csrc", "host"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, PKG_NAME, sub)):
+            for f in files:
+                if f.endswith((".h", ".hip", ".cc", ".cpp", ".hpp")):
+                    text = open(os.path.join(dirpath, f)).read()
+                    read |= set(re.findall(r'getenv\(\s*"(TPAMD_[A-Z0-9_]+)"', text))
+                    assert len(re.findall(r"getenv\(", text)) == len(re.findall(r'getenv\(\s*"TPAMD_', text)), f
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 4. Environment switches"):]
+    section = section.split("\n## ", 1)[0]
+    rows = [ln for ln in section.splitlines() if ln.startswith("| `TPAMD_")]
+    documented = set()
+    for ln in rows:
+        documented |= set(re.findall(r"`(TPAMD_[A-Z0-9_]+)`", ln.split("|")[1]))
+    assert read == documented - {"TPAMD_LIBRARY"}
+    assert read == {"TPAMD_FORCE_GENERIC", "TPAMD_ORDER_RAGGED", "TPAMD_FRONT_DELAY_US", "TPAMD_DEVICE"}
+
+
 def test_synthetic_generator_is_deterministic_and_matches_spec():
     syn = importlib.import_module(PKG_NAME + ".synthetic")
     from oracle import tpo

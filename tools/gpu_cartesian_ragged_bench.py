@@ -2,9 +2,7 @@
 
   --mode ragged    1024 six-joint paths with 500..4000 samples: one ragged call (strided and packed)
                    against one uniform call per distinct sample count, same engine, same run;
-                   wall time and the engine's own kernel timers (tpamd_profile_*). With
-                   --block-sizes the ragged call is also timed on engines created with
-                   TPAMD_CARTESIAN_TPB_RAGGED = 64, 128, 256.
+                   wall time and the engine's own kernel timers (tpamd_profile_*).
   --mode uniform   4096 x 6 x 2000 (BASELINE.json configs[3]) through the uniform entry: the K1 and
                    sweep means of the library TPAMD_LIBRARY selects (for an A/B of two builds).
 
@@ -108,18 +106,6 @@ def mode_ragged(args, torch, eng):
         for k in ("time", "sd", "sdd", "qd", "qdd"):
             same = same and bool(torch.equal(out[k][ids, :n], o[k]))
     res["solved"], res["bit_equal_to_per_count_loop"] = solved, same
-    if args.block_sizes:
-        res["ragged_k1_block_sizes"] = {}
-        for tpb in (64, 128, 256):
-            os.environ["TPAMD_CARTESIAN_TPB_RAGGED"] = str(tpb)
-            Eb = eng.Engine(0)
-            del os.environ["TPAMD_CARTESIAN_TPB_RAGGED"]
-            k1 = []
-            for rep in range(3):
-                k = kernel_ms(torch, Eb, lambda: ragged_packed(Eb))
-                k1.append(k["per_kernel_ms"])
-            wall = timed(torch, lambda: ragged_packed(Eb), args.reps)
-            res["ragged_k1_block_sizes"][tpb] = dict(kernels_ms=k1, wall_min_ms=round(wall["min_ms"], 3))
     print(json.dumps(res))
 
 
@@ -151,7 +137,6 @@ def main():
     ap.add_argument("--paths", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--block-sizes", action="store_true")
     ap.add_argument("--engine-module", default=None,
                     help="load the binding from this file: an older engine.py for an older library (TPAMD_LIBRARY)")
     args = ap.parse_args()

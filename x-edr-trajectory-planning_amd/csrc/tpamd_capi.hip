@@ -232,19 +232,12 @@ struct tpamd_engine {
     hipEvent_t front = nullptr;   // this lane's sampling/LP kernel has finished
     DeviceBuffer ws;
   };
-  static constexpr int kMaxLanes = 8;
-  Lane lanes[kMaxLanes];
+  static constexpr int kLanes = 4;   // lanes used side by side (the runtime has 4 hardware queues)
+  Lane lanes[kLanes];
   hipEvent_t ev_fork = nullptr;
   bool in_lane = false;        // a lane's workspace is swapped in: no slot bookkeeping
   hipEvent_t front_wait = nullptr, front_record = nullptr;   // see tpamd_time_joint_groups_device
-  int phase = 0;               // joint solve: 0 all of it, 1 the front stage only, 2 the rest only
-  std::vector<hipEvent_t> back_wait;   // phase 2: events the sweep's stream waits for first
-  int max_lanes = 4;           // TPAMD_LANES: lanes used side by side (the runtime has 4 hardware queues)
-  int chain_fronts = 2;        // TPAMD_CHAIN_FRONTS: 0 none, 1 every front stage behind the previous group's, 2 behind the heaviest group's (A/B)
   bool order_ragged = true;    // TPAMD_ORDER_RAGGED=0: A/B the longest-first order of ragged batches
-  int k1_tpb = 0;              // TPAMD_K1_TPB: threads per block of the sampling/LP kernel (A/B)
-  int k1_tpb_ragged = 64;      // TPAMD_K1_TPB_RAGGED: its upper limit for ragged batches (A/B)
-  int cartesian_tpb_ragged = 64;    // TPAMD_CARTESIAN_TPB_RAGGED: threads per block of the ragged Cartesian K1 (A/B)
   // Idle time in front of a pipelined front stage (TPAMD_FRONT_DELAY_US). The front stage of solve k+1
   // and the sweep of solve k become runnable at the same moment (the sweep of solve k-1 has ended); if
   // the sampling/LP kernel's 16 k blocks reach the CUs first, the sweep's workgroups (35 KB of LDS each)
@@ -303,20 +296,9 @@ int ensure_workspace(tpamd_engine *e, int B, int N, int C) {
   const size_t need = carve_workspace(nullptr, B, N, C, nullptr);
   if (need > e->ws_buf.bytes) {
     if (e->ws_buf.reserve(need)) return TPAMD_E_HIP;
-#ifdef TPAMD_K1_STUDY
-    HIPCHK(hipMemset(e->ws_buf.p, 0, need));
-#endif
   }
   carve_workspace((char *)e->ws_buf.p, B, N, C, &e->ws);
   e->ws.keep_boundary = e->keep_boundary ? 1 : 0;
-#ifdef TPAMD_K1_STUDY
-  {   // study build: both workspace slots share one timestamp buffer; the slot goes along in bit 1
-    static void *g_study = nullptr;
-    if (!g_study) { HIPCHK(hipMalloc(&g_study, 65536 * 8)); HIPCHK(hipMemset(g_study, 0, 65536 * 8)); }
-    e->ws.diag = (long long *)g_study;
-    e->ws.keep_boundary |= (e->slot & 1) << 1;
-  }
-#endif
   return 0;
 }
 
@@ -653,20 +635,10 @@ int tpamd_engine_create(int device_ordinal, tpamd_engine **out) {
   {
     const char *fg = std::getenv("TPAMD_FORCE_GENERIC");
     e->force_generic = fg && fg[0] == '1';
-    const char *tr = std::getenv("TPAMD_K1_TPB_RAGGED");
-    if (tr && (atoi(tr) == 64 || atoi(tr) == 128 || atoi(tr) == 256)) e->k1_tpb_ragged = atoi(tr);
-    const char *ctr = std::getenv("TPAMD_CARTESIAN_TPB_RAGGED");
-    if (ctr && (atoi(ctr) == 64 || atoi(ctr) == 128 || atoi(ctr) == 256)) e->cartesian_tpb_ragged = atoi(ctr);
     const char *fd = std::getenv("TPAMD_FRONT_DELAY_US");
     if (fd && std::atoi(fd) >= 0 && std::atoi(fd) <= 1000) e->front_delay_us = std::atoi(fd);
-    const char *ml = std::getenv("TPAMD_LANES");
-    if (ml && std::atoi(ml) >= 1 && std::atoi(ml) <= tpamd_engine::kMaxLanes) e->max_lanes = std::atoi(ml);
-    const char *cf = std::getenv("TPAMD_CHAIN_FRONTS");
-    if (cf && cf[0] >= '0' && cf[0] <= '3') e->chain_fronts = cf[0] - '0';
     const char *orr = std::getenv("TPAMD_ORDER_RAGGED");
     e->order_ragged = !(orr && orr[0] == '0');
-    const char *tb = std::getenv("TPAMD_K1_TPB");
-    e->k1_tpb = tb ? std::atoi(tb) : 0;
   }
   *out = e;
   return 0;
@@ -749,8 +721,7 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
   // the block size of the sampling/LP kernel and its LDS: checked before anything is launched or
   // the workspace slot changes
   int tpb = piped ? 128 : (D <= 7 ? 256 : (D < 14 ? 128 : 64));
-  if (!piped && in->num_samples_per_path && tpb > e->k1_tpb_ragged) tpb = e->k1_tpb_ragged;
-  if (e->k1_tpb == 64 || e->k1_tpb == 128 || e->k1_tpb == 256) tpb = e->k1_tpb;
+  if (!piped && in->num_samples_per_path) tpb = 64;
   const size_t lds = ((size_t)(P + 3) + (size_t)P * D + 2 * C + 2 * (size_t)D * tpb) * 8;
   if (lds > 160 * 1024) return TPAMD_E_UNSUPPORTED;
   if (piped) select_slot(e, 1 - e->slot);
@@ -776,10 +747,9 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
     fs = e->aux;
     HIPCHK(hipStreamWaitEvent(fs, e->ev_sweep[slot], 0));
   }
-  const bool do_front = e->phase != 2, do_back = e->phase != 1;
-  if (do_front && piped && e->front_delay_us > 0)
+  if (piped && e->front_delay_us > 0)
     hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, fs, e->front_delay_us * 100);
-  if (do_front) {
+  {
     Timer t(e, fs, KI_SETUP);
     hipLaunchKernelGGL(k_setup_joint, dim3((B + 127) / 128), dim3(128), 0, fs, B, N, D,
                        bt->constraint_safety, in->max_velocity, in->max_acceleration,
@@ -790,8 +760,8 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
     if (ordered)
       hipLaunchKernelGGL(k_order_paths, dim3(1), dim3(1024), 0, fs, B, N, in->num_samples_per_path, order);
   }
-  if (do_front && e->front_wait) HIPCHK(hipStreamWaitEvent(fs, e->front_wait, 0));
-  if (do_front) {
+  if (e->front_wait) HIPCHK(hipStreamWaitEvent(fs, e->front_wait, 0));
+  {
     Timer t(e, fs, KI_SAMPLE_LP);
     // (tpb, above) 128 threads (16 KB of LDS at D = 7) fit next to four resident sweep workgroups
     // of an earlier solve. Otherwise the block size follows the record width (measured, K1 alone:
@@ -815,12 +785,7 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
 #undef TPAMD_K1
     if (plan) hipLaunchKernelGGL(k_plan_project, dim3((B + 127) / 128), dim3(128), 0, fs, *plan, ws);
   }
-  if (do_front && e->front_record) HIPCHK(hipEventRecord(e->front_record, fs));
-  if (!do_back) {
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  for (hipEvent_t ev : e->back_wait) HIPCHK(hipStreamWaitEvent(st, ev, 0));
+  if (e->front_record) HIPCHK(hipEventRecord(e->front_record, fs));
   // Mode 2: the sweep goes to one of two engine streams as well, so that it can start while the
   // previous solve's slowest paths are still running; it is ordered behind this call's position
   // in the caller's stream (the output buffers are free) and behind its own front stage. The
@@ -1021,11 +986,7 @@ int tpamd_engine_set_pipelining(tpamd_engine *e, int on) {
     // free; it must not take workgroup slots from a sweep that is being dispatched
     int least = 0, greatest = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const char *pr = std::getenv("TPAMD_AUX_PRIORITY");   // A/B: "high", "default"
-    int prio = least;
-    if (pr && pr[0] == 'h') prio = greatest;
-    if (pr && pr[0] == 'd') prio = 0;
-    HIPCHK(hipStreamCreateWithPriority(&e->aux, hipStreamNonBlocking, prio));
+    HIPCHK(hipStreamCreateWithPriority(&e->aux, hipStreamNonBlocking, least));
     for (int k = 0; k < 2; k++) {
       HIPCHK(hipEventCreateWithFlags(&e->ev_front[k], hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&e->ev_sweep[k], hipEventDisableTiming));
@@ -1173,7 +1134,7 @@ int solve_cartesian(tpamd_engine *e, const tpamd_cartesian_batch *bt, const tpam
       // Ragged batches take 64-thread blocks: fewer threads idle behind a path's end (measured,
       // 1024 paths of 500..4000 samples, K1 alone: 0.24 / 0.36 / 0.34 ms at 64 / 128 / 256 threads;
       // profiles/cartesian_ragged_ab.md).
-      const int tpb = ragged ? e->cartesian_tpb_ragged : 256;
+      const int tpb = ragged ? 64 : 256;
       const size_t lds = (2 * (size_t)C + (2 * (size_t)D + 2) * tpb) * 8;
       const dim3 grid((N + tpb - 1) / tpb, B);
       if (ragged && D == 6)
@@ -1436,9 +1397,7 @@ int ensure_lane(tpamd_engine *e, int k) {
   if (ln.stream) return 0;
   int least = 0, greatest = 0;
   HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-  const char *pr = std::getenv("TPAMD_LANE_PRIORITY");   // A/B: "0" = all lanes at the default priority
-  const int prio = (k == 0 && !(pr && pr[0] == '0')) ? greatest : 0;
-  HIPCHK(hipStreamCreateWithPriority(&ln.stream, hipStreamNonBlocking, prio));
+  HIPCHK(hipStreamCreateWithPriority(&ln.stream, hipStreamNonBlocking, k == 0 ? greatest : 0));
   HIPCHK(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&ln.front, hipEventDisableTiming));
   if (!e->ev_fork) HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
@@ -1485,7 +1444,7 @@ int tpamd_time_joint_groups_device(tpamd_engine *e, int num_groups, const tpamd_
     }
     return 0;
   }
-  const int nl = std::min(num_groups, e->max_lanes);
+  const int nl = std::min(num_groups, tpamd_engine::kLanes);
   for (int k = 0; k < nl; k++) {
     const int rc = ensure_lane(e, k);
     if (rc) return rc;
@@ -1497,41 +1456,22 @@ int tpamd_time_joint_groups_device(tpamd_engine *e, int num_groups, const tpamd_
   // The sampling/LP kernels of the groups run one after another in weight order, each with the
   // whole machine to itself, so that the heaviest group's sweep -- whose longest path is the
   // call's critical path -- starts as early as it can; the sweeps then overlap each other and the
-  // later groups' sampling/LP kernels (a lane's front stage waits for the previous lane's).
-  // (TPAMD_CHAIN_FRONTS, A/B: 0 no order among the front stages; 1 each behind the previous
-  // group's; 2 all behind the heaviest group's; 3 as 2, and no sweep starts before every front
-  // stage of the call is done -- for calls with at most one group per lane.)
+  // later groups' sampling/LP kernels (every later front stage waits for the heaviest group's).
   int rc_all = 0;
-  hipEvent_t prev_front = nullptr;
-  const bool two_phase = e->chain_fronts == 3 && num_groups <= nl;
+  hipEvent_t heaviest_front = nullptr;
   for (int n = 0; n < num_groups && rc_all == 0; n++) {
     const int g = idx[n];
     if (batches[g].num_paths <= 0) continue;
     const int k = n % nl;
-    e->front_wait = e->chain_fronts ? prev_front : nullptr;
+    e->front_wait = heaviest_front;
     e->front_record = e->lanes[k].front;
-    e->phase = two_phase ? 1 : 0;
     rc_all = with_lane_workspace(e, k, [&](hipStream_t st) {
       return solve_joint(e, &batches[g], &inputs[g], &outputs[g], st, nullptr, false);
     });
-    if (e->chain_fronts == 1 || prev_front == nullptr) prev_front = e->lanes[k].front;
+    if (heaviest_front == nullptr) heaviest_front = e->lanes[k].front;
   }
   e->front_wait = nullptr;
   e->front_record = nullptr;
-  if (two_phase) {
-    for (int n = 0; n < num_groups; n++)
-      if (batches[idx[n]].num_paths > 0) e->back_wait.push_back(e->lanes[n % nl].front);
-    e->phase = 2;
-    for (int n = 0; n < num_groups && rc_all == 0; n++) {
-      const int g = idx[n];
-      if (batches[g].num_paths <= 0) continue;
-      rc_all = with_lane_workspace(e, n % nl, [&](hipStream_t st) {
-        return solve_joint(e, &batches[g], &inputs[g], &outputs[g], st, nullptr, false);
-      });
-    }
-    e->back_wait.clear();
-  }
-  e->phase = 0;
   // join (also after an error: whatever was launched is ordered before the caller goes on)
   for (int k = 0; k < nl; k++) {
     HIPCHK(hipEventRecord(e->lanes[k].done, e->lanes[k].stream));
@@ -2277,11 +2217,7 @@ int tpamd_debug_copy_diag(tpamd_engine *e, int B, long long *out) {
   if (!e || !out || B != e->last_B) return TPAMD_E_INVALID_ARGUMENT;
   TPAMD_ON_DEVICE(e);
   HIPCHK(hipDeviceSynchronize());
-#ifdef TPAMD_K1_STUDY   // (the study build's flat timestamp buffer, see ensure_workspace)
-  HIPCHK(hipMemcpy(out, e->ws.diag, (size_t)B * 64 * 8, hipMemcpyDeviceToHost));
-#else
   HIPCHK(hipMemcpy2D(out, 64 * 8, e->ws.diag, kDiagRow * 8, 64 * 8, (size_t)B, hipMemcpyDeviceToHost));
-#endif
   return 0;
 }
 

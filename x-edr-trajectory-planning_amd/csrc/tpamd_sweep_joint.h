@@ -199,11 +199,7 @@ __device__ __forceinline__ long long tpamd_stamp() {
   return (long long)t;
 }
 #define TPAMD_T0(var) const long long var = tpamd_stamp()
-#ifdef TPAMD_DIAG_REASONS   // (study build: slots 12, 13, 17, 19..23, 31 count why chain blocks end instead)
-#define TPAMD_ACC(slot, var) do { if (!((slot) == 12 || (slot) == 13 || (slot) == 17 || ((slot) >= 19 && (slot) <= 23) || (slot) == 31)) diag[slot] += tpamd_stamp() - (var); } while (0)
-#else
 #define TPAMD_ACC(slot, var) diag[slot] += tpamd_stamp() - (var)
-#endif
 #define TPAMD_CNT(slot) diag[slot] += 1
 #define TPAMD_ADD(slot, v) diag[slot] += (v)
 #define TPAMD_CNTX(slot) diagx[slot] += 1
@@ -227,9 +223,6 @@ __device__ __forceinline__ long long tpamd_stamp() {
 #define TPAMD_CNTX(slot)
 #endif
 
-#ifndef TPAMD_TILE_SAMPLES
-#define TPAMD_TILE_SAMPLES 32
-#endif
 // After a speculative block that ended because the active constraint changed, speculate on the
 // constraint that took over instead of finding it with a scalar FindSdd step. Measured (round 3):
 // scalar steps per path 97 -> 89 and the mean path 2 % shorter in cycles, but 2.4 M VALU instructions
@@ -238,18 +231,13 @@ __device__ __forceinline__ long long tpamd_stamp() {
 #ifndef TPAMD_CHAIN_GUESS
 #define TPAMD_CHAIN_GUESS 0
 #endif
-// A speculative block whose first failing step fails only because its (verified) new sd2 lies above
-// the limit curve finishes that step itself (leave_on_curve) instead of handing it to a scalar step.
-#ifndef TPAMD_CURVE_EXIT
-#define TPAMD_CURVE_EXIT 1
-#endif
-constexpr int kTileSamples = TPAMD_TILE_SAMPLES;   // largest tile (the engine pads the records by one)
+constexpr int kTileSamples = 32;   // largest tile (the engine pads the records by one)
 // Samples per tile of the D-joint sweep: wide records (D > 8: 30 doubles at D = 14) take 16-sample
 // tiles, which halves the prefetch registers and the rings (the 14-joint kernel spilled 288 bytes
 // per lane with 32-sample tiles).
 template <int D>
 struct TileCfg {
-  static constexpr int kSamples = (D > 8 && TPAMD_TILE_SAMPLES > 16) ? 16 : TPAMD_TILE_SAMPLES;
+  static constexpr int kSamples = (D > 8) ? 16 : kTileSamples;
 };
 
 // 16-byte pair as a native vector type: plain loads/stores that the compiler keeps in
@@ -296,10 +284,7 @@ struct JointLayout {
   static_assert(kCandLanes <= 64, "candidate lanes must fit one wave");
   // Chain verification (follow_chain): kChain steps x GRP lanes; lane part p of a step's
   // group owns candidates p, p+GRP, ... and rows p, p+GRP, ...
-#ifndef TPAMD_CHAIN_STEPS
-#define TPAMD_CHAIN_STEPS 16
-#endif
-  static constexpr int kChain = TPAMD_CHAIN_STEPS;
+  static constexpr int kChain = 16;
   static constexpr int GRP = 64 / kChain;
   static constexpr int CPL = (2 * D + GRP - 1) / GRP;
   static constexpr int VPL = (D + GRP - 1) / GRP;
@@ -337,7 +322,7 @@ struct JointSweep {
   // pass. During the boundary passes 10 / 11 count the re-fits of the final / the first pass
   // (the sweep then counts on top: scalar FindSdd steps / loops).
   // 24 scalar-step cycles, 25 boundary-follow cycles, 26 init_carry cycles, 27 tile fills, 28 tile-fill
-  // cycles, 29 init_carry calls, 30 blocks started from a guessed constraint
+  // cycles, 29 init_carry calls, 30 blocks that finished their last step on the limit curve (leave_on_curve)
   long long diag[32];
   // further slots. Backward wave, the closing barrier (C) of a switching-point loop by what the
   // backward wave was doing when the forward wave posted "done": 0 loops in which it was still in
@@ -1071,18 +1056,6 @@ struct JointSweep {
     if (G >= 4) fm |= fm >> 2;
     const unsigned long long miss = fm & L::kPart0;     // bit 4k: step k failed
     const int Lc = miss ? ((__ffsll((long long)miss) - 1) / G) : K;
-#ifdef TPAMD_DIAG_REASONS
-    if (Lc < K) {
-      const unsigned long long lanes_ = ((1ull << G) - 1ull) << (G * Lc);
-      const bool r_loop = (__ballot(!in_loop) & lanes_) != 0, r_eq = (__ballot(!bits_equal) & lanes_) != 0;
-      const bool r_ride = (__ballot(riding) & lanes_) != 0, r_isect = (__ballot(!isnan(nxt) & (nxt < my_new)) & lanes_) != 0;
-      const bool r_curve = (__ballot(my_new > m_n) & lanes_) != 0, r_neg = (__ballot((my_new < 0) | isnan(my_new)) & lanes_) != 0;
-      const bool r_bad = (__ballot(bad) & lanes_) != 0, r_hint = (__ballot(guess >= 0) & lanes_) != 0;
-      if (r_loop) diag[19]++; else if (r_ride) diag[20]++; else if (r_isect) diag[21]++; else if (r_curve) diag[22]++;
-      else if (r_neg) diag[23]++; else if (r_eq) diag[31]++; else if (r_bad && r_hint) diag[13]++; else if (r_bad) diag[12]++;
-      if (Lc == 0) diag[17]++;
-    }
-#endif
     if (TPAMD_CHAIN_GUESS && Lc > 0 && Lc < K) {
       // Why did step Lc fail? If only because another constraint became active (no special case of
       // the scalar step, the chain value itself was right), its lanes know which one: the next
@@ -1095,7 +1068,9 @@ struct JointSweep {
         next_win = __builtin_amdgcn_readlane(guess, src) * L::PARTS;
       }
     }
-    if (TPAMD_CURVE_EXIT && Lc < K) {
+    // A block whose first failing step fails only because its (verified) new sd2 lies above the
+    // limit curve finishes that step itself (leave_on_curve) instead of handing it to a scalar step.
+    if (Lc < K) {
       // (my_new > m_n is then the reason: a step fails for one of the terms of `fm`)
       const unsigned long long lanes = ((1ull << G) - 1ull) << (G * Lc);
       if ((fo & lanes) == 0ull) {
@@ -1513,9 +1488,6 @@ __device__ __forceinline__ void boundary_passes_for_path(const JointSource &src,
   __syncthreads();
   TPAMD_ACCC(19, tp0);
 
-#ifndef TPAMD_BOUNDARY_FAST
-#define TPAMD_BOUNDARY_FAST 1
-#endif
   // Passes 2 (second half), 3 and 4 from ONE round of loads per segment of 2108 samples, with no
   // load, branch or cross-lane operation inside the per-sample arithmetic. The path is cut into
   // chunks of 62 samples; a wave takes every other chunk and loads it with one sample of overlap
@@ -1538,7 +1510,7 @@ __device__ __forceinline__ void boundary_passes_for_path(const JointSource &src,
   // kernel beside two sweep waves), so the one-segment form is compiled separately.
   constexpr int kSegChunks = 2 * UF;
   const int nseg = (N + 62 * kSegChunks - 1) / (62 * kSegChunks);
-  if (TPAMD_BOUNDARY_FAST && 3 * flag_bytes + 8 * slow_cap <= 8 * N) {
+  if (3 * flag_bytes + 8 * slow_cap <= 8 * N) {
     // kOne: the path is one segment (N <= 2108) -- the segment loops fold away and the registers of
     // the second pass serve the third, as before the segments existed; both forms are compiled.
     auto fast_form = [&](auto one_segment) {
@@ -1921,28 +1893,18 @@ __host__ __device__ inline size_t sweep_joint_lds_bytes(int N) {
 // are data-independent after the backward extremal's first step, see add_extremal). Both
 // waves keep identical copies of the loop scalars. qd/qdd are written by the extremals as
 // the backward wave finishes with its share (emit_range); the tail is shared by the two waves.
-// TPAMD_SWEEP_WAVES_PER_EU (build-time, A/B): ask the compiler for a register budget that lets
-// that many waves share a SIMD (3 -> 168 VGPRs).
+// kSweepWavesPerEu asks the compiler for a register budget that lets that many waves share a
+// SIMD (3 -> 168 VGPRs).
 // Wide records (D > 8) get the budget of ONE wave per SIMD: the 14-joint kernel needs 300
 // registers (256 + 44 in the accumulation half of the unified file) and spilled 184 bytes per
 // lane to scratch memory -- loads on the sequential chain -- when held to 256. At 304 allocated
 // registers one 7-joint sweep wave (196) or two sampling/LP waves still fit beside it on a SIMD.
-#ifndef TPAMD_SWEEP_WAVES_PER_EU
-#define TPAMD_SWEEP_WAVES_PER_EU 2
-#endif
-#ifndef TPAMD_SWEEP_WAVES_PER_EU_WIDE
-#define TPAMD_SWEEP_WAVES_PER_EU_WIDE 1
-#endif
-#define TPAMD_SWEEP_OCCUPANCY                                                                          \
-  __attribute__((amdgpu_waves_per_eu((D > 8) ? TPAMD_SWEEP_WAVES_PER_EU_WIDE : TPAMD_SWEEP_WAVES_PER_EU, \
-                                     (D > 8) ? TPAMD_SWEEP_WAVES_PER_EU_WIDE : TPAMD_SWEEP_WAVES_PER_EU)))
-#ifdef TPAMD_K1_STUDY
-#define TPAMD_SWEEP_STUDY_REGS __attribute__((amdgpu_num_vgpr(200)))
-#else
-#define TPAMD_SWEEP_STUDY_REGS
-#endif
+constexpr int kSweepWavesPerEu = 2;
+constexpr int kSweepWavesPerEuWide = 1;
 template <int D, int E = 0>
-__global__ void __launch_bounds__(128) TPAMD_SWEEP_OCCUPANCY TPAMD_SWEEP_STUDY_REGS
+__global__ void __launch_bounds__(128)
+__attribute__((amdgpu_waves_per_eu((D > 8) ? kSweepWavesPerEuWide : kSweepWavesPerEu,
+                                   (D > 8) ? kSweepWavesPerEuWide : kSweepWavesPerEu)))
 k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *t_out, double *s_out,
               double *sd_out, double *sdd_out, int32_t *lei_out, double *dtmax_out,
               int32_t *status_out, double *qd_out, double *qdd_out) {
@@ -1965,17 +1927,6 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
     }
     return;
   }
-#ifdef TPAMD_K1_STUDY
-  // study build: start / end clock of every sweep workgroup, per workspace slot
-  unsigned long long *study = reinterpret_cast<unsigned long long *>(ws.diag) + 40960 + ((ws.keep_boundary >> 1) & 1) * 4096;
-  if (tid == 0) {
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    study[2 * b] = t | ((unsigned long long)(xcc & 15u) << 60);
-  }
-#endif
   JS S;
   S.N = N; S.lane = lane;
   S.ds = ws.ds[b];
@@ -2111,39 +2062,31 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   // qd/qdd bookkeeping of wave 0: samples below emitted_hi and from upper_lo up have been
   // written (see emit_range)
   int emitted_hi = 0, upper_lo = N;
-#ifndef TPAMD_FIRST_PAIR_CONCURRENT
-#define TPAMD_FIRST_PAIR_CONCURRENT 1
-#endif
-#ifndef TPAMD_EMIT_IN_LOOP
-#define TPAMD_EMIT_IN_LOOP 1
-#endif
-  bool first_pair_in_order = !TPAMD_FIRST_PAIR_CONCURRENT;
-  if (TPAMD_FIRST_PAIR_CONCURRENT) {
-    if (w == 0) {
-      const int r = S.template add_extremal<false>(iback_hi, pf);
-      if (lane == 0) { xchg[0] = r; xchg[7] = S.end_idx; }
-    } else {
-      const int r = S.template add_extremal<true>(iforw_lo, pf);
-      if (lane == 0) { xchg[1] = r; xchg[8] = S.end_idx; }
+  bool first_pair_in_order = false;
+  if (w == 0) {
+    const int r = S.template add_extremal<false>(iback_hi, pf);
+    if (lane == 0) { xchg[0] = r; xchg[7] = S.end_idx; }
+  } else {
+    const int r = S.template add_extremal<true>(iforw_lo, pf);
+    if (lane == 0) { xchg[1] = r; xchg[8] = S.end_idx; }
+  }
+  __threadfence_block();
+  __syncthreads();
+  const int end_b = uniform_i32(xchg[7]), end_f = uniform_i32(xchg[8]);
+  if (!(end_f + 70 < end_b)) {                     // (uniform over the workgroup)
+    // the two met or came close: back to the state before the attempt
+    first_pair_in_order = true;
+    for (int i = tid; i < N; i += 128) {
+      sd2[i] = qnan();
+      S.sdd_g[i] = qnan();
+    }
+    __syncthreads();
+    if (tid == 0) {
+      sd2[0] = sd_start * sd_start;
+      sd2[N - 1] = 0;
     }
     __threadfence_block();
     __syncthreads();
-    const int end_b = uniform_i32(xchg[7]), end_f = uniform_i32(xchg[8]);
-    if (!(end_f + 70 < end_b)) {                     // (uniform over the workgroup)
-      // the two met or came close: back to the state before the attempt
-      first_pair_in_order = true;
-      for (int i = tid; i < N; i += 128) {
-        sd2[i] = qnan();
-        S.sdd_g[i] = qnan();
-      }
-      __syncthreads();
-      if (tid == 0) {
-        sd2[0] = sd_start * sd_start;
-        sd2[N - 1] = 0;
-      }
-      __threadfence_block();
-      __syncthreads();
-    }
   }
   if (first_pair_in_order) {
     if (w == 0) {
@@ -2159,10 +2102,8 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
       // meanwhile: the region the first backward extremal has just set, short of its lower end
       // (which the NaN mark below and the connecting forward extremal may still change; what
       // the latter rewrites is redone in the tail)
-      if (TPAMD_EMIT_IN_LOOP) {
-        upper_lo = min(S.end_idx + 3, N);
-        S.emit_range(upper_lo, N - 1, 0, 1);
-      }
+      upper_lo = min(S.end_idx + 3, N);
+      S.emit_range(upper_lo, N - 1, 0, 1);
     }
     __threadfence_block();
     __syncthreads();
@@ -2255,10 +2196,8 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
         // -- but only until that one is done (xchg[6] then holds this loop's number): the
         // rest waits for the next loop or the tail.
         TPAMD_T0C(te);
-        if (TPAMD_EMIT_IN_LOOP) {
-          emitted_hi = uniform_i32(S.emit_range(max(min(S.end_idx - 1, emitted_hi), 0), icrit - 1,
-                                                0, 1, xchg + 6, loop + 1));
-        }
+        emitted_hi = uniform_i32(S.emit_range(max(min(S.end_idx - 1, emitted_hi), 0), icrit - 1,
+                                              0, 1, xchg + 6, loop + 1));
         TPAMD_ACCC(12, te);
 #ifdef TPAMD_DIAG
         bw_case = fw_was_done ? 0 : (lds_word(xchg + 6) == loop + 1) ? 1 : 2;
@@ -2574,13 +2513,6 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
     status_out[b] = 0;
     if (dtmax_out) dtmax_out[b] = (red[0] > red[1]) ? red[0] : red[1];
   }
-#ifdef TPAMD_K1_STUDY
-  if (tid == 0) {
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    study[2 * b + 1] = t;
-  }
-#endif
   TPAMD_ACCC(3, t_tail);
   TPAMD_ACCC(15, t_all);
 #ifdef TPAMD_DIAG
