@@ -1201,6 +1201,11 @@ int tpamd_find_max_sd2_host(tpamd_engine *engine, int num_lps, int num_rows,
  * sd2_ it keeps from its LAST solve, and returns TPAMD_E_STALE unless `time` is that solve's
  * output array and the shape matches (a later solve into other buffers invalidates it).
  * Every path has num_samples samples (no ragged batches). status may be NULL. Device pointers.
+ * A path whose status is not 0 gets ok = 0 and its out_* entries are not written; ok may be
+ * NULL; where ok is 0 on a live path (the reference returns false and leaves its outputs
+ * alone) out_s, out_sd, out_sdd are unspecified. Query times that are not finite are outside
+ * the bit-for-bit agreement with the reference (its search and this one end in different
+ * brackets on a NaN), and so are start_sec values of tpamd_resample_* that are not finite.
  * ------------------------------------------------------------------------ */
 int tpamd_query_device(tpamd_engine *engine, int num_paths, int num_samples,
                        int num_queries, const double *time, const double *s,
@@ -1244,7 +1249,11 @@ void tpamd_shard_bounds_balanced(int num_paths, const double *cost, int num_shar
  * batch of solved paths. Output row b holds count[b] = ceil((t_end-start)/dt)+1
  * samples, written at [b][0..count) of arrays with stride max_out; if
  * count[b] > max_out only max_out samples are written (count still reports the
- * full number). Device pointers.
+ * full number), and the end sample (end position, zero qd and qdd) is special only if
+ * it is among them. No slot at or above min(count[b], max_out) is written. For a
+ * start_sec more than a time step past the last time stamp count[b] is 0 or negative
+ * (the formula above, as the reference evaluates it) and nothing but count[b] is
+ * written. A path skipped by status gets count 0. Device pointers.
  * ------------------------------------------------------------------------ */
 typedef struct tpamd_resample_args {
   int32_t num_paths, num_samples, num_dofs, max_out;
