@@ -5,7 +5,15 @@ statuses), the control loop with a planner set on the structured path families o
 tests/structured_paths.py (written to a file here), the in-place stop against
 tpamd_planner_set_stop_trajectories, packed device outputs inserted on the device, a linear
 hipGraph capture and the capacity rules. The second test drives engine.BufferSet with CUDA tensors
-against the C-ABI's host-pointer entries."""
+against the C-ABI's host-pointer entries.
+
+Not covered here: the reference of these tests is the project's own mirror, at D = 7, 14, 1 and 6;
+the fuzz's _device set holds 2048 rows and receives at most 30 a call, and the host-entry set grows
+before it fills, so the in-kernel compaction (bs_move_down_wg) practically never runs; id lists
+stay far below the 1024 threads of the offset scans; no difference equals the tolerance exactly.
+tests/test_gpu_buffer_readout_all_dofs.py covers those: every D = 1..16 against the independent
+restatement of tests/buffer_reference.py, every layout case a compaction, lists of up to 2500 ids,
+capacities on and one row beside the total, ticks on and 1 ns beside the stamps."""
 import ctypes as C
 import importlib
 import os
