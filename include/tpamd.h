@@ -52,6 +52,7 @@ extern "C" {
 #define TPAMD_PATH_NAN_SD2 8
 #define TPAMD_PATH_NONZERO_END 9
 #define TPAMD_PATH_CRIT_INDEX_ZERO 10 /* reference reads sd2_max[-1] here (.cc:361,:372) */
+#define TPAMD_PATH_NO_WAYPOINTS 11 /* tpamd_time_waypoint_paths_*: a path without waypoints has no spline (timeable_path_joint_spline.cc:200-207) */
 
 typedef struct tpamd_engine tpamd_engine;
 
@@ -182,6 +183,104 @@ int tpamd_sample_joint_paths_host(tpamd_engine *engine, int num_paths, int num_d
                                   int num_samples, int num_points, const double *knots,
                                   const double *control_points, const double *path_start,
                                   const double *delta, double *q, double *q1, double *q2);
+
+/* ---- Waypoint batches: fit on the device, any waypoint count per path ------------------------
+ * TimeableJointSplinePath::SetWaypoints / FitSplineToWaypoints
+ * (timeable_path_joint_spline.cc:200-207, :252-292) for num_paths paths at once, the joint
+ * counterpart of tpamd_fit_pose_waypoints_*. Path k takes waypoints waypoint_offsets[k] ..
+ * waypoint_offsets[k + 1]) of waypoints [rows][D] and rounding[k] (rounding NULL: 0.2, the default
+ * of PathOptions::rounding):
+ *   - control points: PolyLineToBspline3Waypoints with the rounding radius (:253-254), P_k =
+ *     max(3 W_k - 2, 4);
+ *   - uniform degree-2 knots on [0, 1] (splines/bspline_base.cc:356-381), every knot multiplied by
+ *     max(length of the control polygon, 0.1) (:271-285).
+ * The outputs are packed raggedly, path k behind path k - 1, as tpamd_fit_pose_waypoints_* packs
+ * them: knots (sum of P_k + 3 values), control_points [sum P_k][D]. Per path: num_points[k],
+ * path_end[k] (the last knot) and status[k] TPAMD_PLAN_*. A path without waypoints gets
+ * TPAMD_PLAN_INVALID_ARGUMENT, num_points 0 and path_end 0, occupies no slots and leaves the other
+ * paths as they are without it. point_offsets [num_paths + 1] (may be NULL) receives the first
+ * control point of every path; it is always a HOST array, computed from the waypoint counts before
+ * the launch (path k's knots start at point_offsets[k] + 3 * (paths with waypoints before k)).
+ * Knots and control points are bit-identical to the host mirror's fit.
+ * Call-level errors write nothing: a NULL engine or required array, num_paths < 0, num_dofs
+ * outside 1..16, waypoint_offsets[0] != 0 or decreasing offsets (TPAMD_E_INVALID_ARGUMENT); more
+ * than 65535 paths (TPAMD_E_UNSUPPORTED). Host pointers; synchronises. */
+int tpamd_fit_joint_waypoints_host(tpamd_engine *engine, int num_paths, int num_dofs,
+                                   const int32_t *waypoint_offsets, const double *waypoints,
+                                   const double *rounding, double *knots, double *control_points,
+                                   int32_t *num_points, int32_t *point_offsets, double *path_end,
+                                   int32_t *status);
+/* The same with every array except waypoint_offsets and point_offsets a device pointer. Enqueues
+ * on hip_stream (NULL: the null stream) and does not synchronise; the offsets go up on hip_stream
+ * first, into the buffer of the engine that tpamd_fit_pose_waypoints_device documents (shared with
+ * it: the next call of any of these _device entries waits on its stream for this one's kernel). */
+int tpamd_fit_joint_waypoints_device(tpamd_engine *engine, int num_paths, int num_dofs,
+                                     const int32_t *waypoint_offsets, const double *waypoints,
+                                     const double *rounding, double *knots, double *control_points,
+                                     int32_t *num_points, int32_t *point_offsets, double *path_end,
+                                     int32_t *status, void *hip_stream);
+
+/* Waypoints in, trajectories out: SetWaypoints (as above) and then, per path, what
+ * tpamd_time_joint_paths_* computes (SamplePath .. OptimizePathParameter .. the epilogue, see Form
+ * (i)) with path_start 0, in ONE call for paths of any waypoint count and any sample count. The
+ * fit runs on the device into a scratch of the engine in which every path has a slot of
+ * max_k P_k control points (it grows on demand and lives until tpamd_engine_destroy); the
+ * sampling/LP kernel reads every path's own count from it, so nothing is bucketed by size. */
+typedef struct tpamd_waypoint_batch {
+  int32_t num_paths;        /* B */
+  int32_t num_dofs;         /* D, 1..16 */
+  int32_t num_samples;      /* N, 3..8192: stride of the [B][N] outputs and the largest per-path count */
+  int32_t max_solver_loops; /* as tpamd_joint_batch */
+  double constraint_safety; /* as tpamd_joint_batch */
+} tpamd_waypoint_batch;
+
+typedef struct tpamd_waypoint_inputs {
+  const int32_t *waypoint_offsets;     /* [B+1] HOST array in both entries */
+  const double *waypoints;             /* [rows][D] */
+  const double *rounding;              /* [B] PathOptions::rounding; NULL = 0.2 */
+  const double *max_velocity;          /* [B][D] */
+  const double *max_acceleration;      /* [B][D] */
+  const int32_t *num_samples_per_path; /* [B] n_k <= num_samples; NULL = every path has num_samples */
+  /* [B] PathOptions::delta_parameter; NULL = every path is covered exactly by its samples:
+   * delta_k = path_end_k / (n_k - 1), one IEEE division on the device, where the length is known */
+  const double *delta;
+  const double *sd_start;              /* [B]; NULL = 0 */
+  const double *time_start;            /* [B]; NULL = 0 */
+} tpamd_waypoint_inputs;
+
+/* What the fit found, each array optional (a NULL struct: none). knots / control_points have one
+ * slot of S = max(3 max_k W_k - 2, 4) control points per path -- [B][S + 3] and [B][S][D]; path k
+ * uses the first num_points[k] + 3 and num_points[k] entries of its slot; what the rest of a slot
+ * holds afterwards is unspecified. */
+typedef struct tpamd_waypoint_fit_outputs {
+  int32_t *num_points;    /* [B] P_k; 0 without waypoints */
+  double *path_end;       /* [B] the last knot; 0 without waypoints */
+  double *delta_used;     /* [B] the delta the path was sampled with */
+  double *knots;          /* [B][S + 3] */
+  double *control_points; /* [B][S][D] */
+} tpamd_waypoint_fit_outputs;
+
+/* `out` has the layout and meaning of tpamd_time_joint_paths_* (time, s, sd, sdd and status are
+ * required). A path without waypoints gets status TPAMD_PATH_NO_WAYPOINTS whatever else is wrong
+ * with it, none of its other outputs is written, and the other paths are what they are without it,
+ * bit for bit. A count n_k outside [2, num_samples] fails path k alone (TPAMD_PATH_TOO_FEW_SAMPLES).
+ * With per-path counts the sweep takes the paths longest first, as tpamd_time_joint_paths_* does.
+ * Never pipelined (tpamd_engine_set_pipelining): the fit precedes the front stage on the caller's
+ * stream. Call-level errors write nothing: a NULL engine, struct or required array, num_paths < 0,
+ * waypoint_offsets[0] != 0 or decreasing offsets (TPAMD_E_INVALID_ARGUMENT); num_dofs outside
+ * 1..16, num_samples outside 3..8192, more than 65535 paths, or a largest P_k whose knots and
+ * control points do not fit the sampling/LP kernel's 160 KB of LDS (TPAMD_E_UNSUPPORTED); the
+ * _host entry also refuses a per-path count above num_samples (TPAMD_E_INVALID_ARGUMENT). Host
+ * pointers; synchronises. */
+int tpamd_time_waypoint_paths_host(tpamd_engine *engine, const tpamd_waypoint_batch *batch,
+                                   const tpamd_waypoint_inputs *in, const tpamd_path_outputs *out,
+                                   const tpamd_waypoint_fit_outputs *fit);
+/* The same with every array except waypoint_offsets a device pointer. Enqueues on hip_stream and
+ * does not synchronise, except when the engine's scratch has to grow; the offsets go up as
+ * tpamd_fit_joint_waypoints_device stages them. */
+int tpamd_time_waypoint_paths_device(tpamd_engine *engine, const tpamd_waypoint_batch *batch,
+                                     const tpamd_waypoint_inputs *in, const tpamd_path_outputs *out,
+                                     const tpamd_waypoint_fit_outputs *fit, void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Form (ii): explicit constraint rows  lower <= A*sdd + B*sd^2 <= upper.

@@ -24,6 +24,7 @@
 #include "tpamd_fit.h"
 #include "tpamd_retarget.h"
 #include "tpamd_pose_fit.h"
+#include "tpamd_joint_fit.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 
 using namespace tpamd;
@@ -202,6 +203,8 @@ struct tpamd_engine {
   DeviceBuffer pose_ints;      // the offset arrays of the _device pose-fit / IK-target calls
   hipEvent_t ev_pose = nullptr;   // the last of those calls has read pose_ints
   bool pose_busy = false;
+  DeviceBuffer wp_fit;         // waypoint batches (tpamd_time_waypoint_paths_*): the fitted splines, one slot of
+                               // the largest control-point count per path, and what the fit knows per path
   bool rows_for_plan = false;  // rows holds only zeros and rows written by window chaining (of any set on
                                // this engine, under its own split of the buffer: finite values, no more)
   Workspace ws{};
@@ -578,6 +581,7 @@ const char *tpamd_error_string(int code) {
     case TPAMD_PATH_NAN_SD2: return "no solution found (NaN in sd2)";
     case TPAMD_PATH_NONZERO_END: return "non-zero terminal velocity";
     case TPAMD_PATH_CRIT_INDEX_ZERO: return "critical point search degenerated to index 0";
+    case TPAMD_PATH_NO_WAYPOINTS: return "path without waypoints";
     default: return "unknown";
   }
 }
@@ -669,6 +673,7 @@ void tpamd_engine_destroy(tpamd_engine *e) {
   e->stage.release();
   e->rows.release();
   e->pose_ints.release();
+  e->wp_fit.release();
   if (e->ev_pose) (void)hipEventDestroy(e->ev_pose);
   delete e;
 }
@@ -700,11 +705,31 @@ int joint_args(const tpamd_joint_batch *bt, const tpamd_joint_inputs *in, const 
   return 0;
 }
 
+// Block size of the sampling/LP kernel and the LDS it then needs for paths of up to P control points.
+int sample_lp_block(bool piped, bool ragged, int D) {
+  if (piped) return 128;
+  return ragged ? 64 : (D <= 7 ? 256 : (D < 14 ? 128 : 64));
+}
+size_t sample_lp_lds(int P, int D, int tpb) {
+  return ((size_t)(P + 3) + (size_t)P * D + 2 * (size_t)(2 * D) + 2 * (size_t)D * tpb) * 8;
+}
+constexpr size_t kSampleLpLdsLimit = 160 * 1024;
+
+// Waypoint batches (tpamd_time_waypoint_paths_*): the splines were fitted on the device into slots
+// of p_stride control points; path k has np[k] of them, 0 if it has no waypoints.
+struct FittedPaths {
+  const int32_t *np;
+  int p_stride;
+  bool any_empty;
+};
+
 // The joint-space solve; `plan` (window chaining, tpamd_plan_joint_windows_host) adds two small
-// kernels: skip marks after the set-up kernel, the start-velocity projection after K1.
+// kernels: skip marks after the set-up kernel, the start-velocity projection after K1. `fitted`
+// (waypoint batches) gives every path its own control-point count, as a planner set does, and adds
+// one small kernel behind the set-up kernel if a path has no waypoints.
 int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
                 const tpamd_path_outputs *out, void *hip_stream, const PlanParams *plan,
-                bool allow_pipelining = true) {
+                bool allow_pipelining = true, const FittedPaths *fitted = nullptr) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
@@ -720,10 +745,9 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
   if (piped && stream_is_capturing(st)) piped = false;
   // the block size of the sampling/LP kernel and its LDS: checked before anything is launched or
   // the workspace slot changes
-  int tpb = piped ? 128 : (D <= 7 ? 256 : (D < 14 ? 128 : 64));
-  if (!piped && in->num_samples_per_path) tpb = 64;
-  const size_t lds = ((size_t)(P + 3) + (size_t)P * D + 2 * C + 2 * (size_t)D * tpb) * 8;
-  if (lds > 160 * 1024) return TPAMD_E_UNSUPPORTED;
+  const int tpb = sample_lp_block(piped, in->num_samples_per_path != nullptr, D);
+  const size_t lds = sample_lp_lds(P, D, tpb);
+  if (lds > kSampleLpLdsLimit) return TPAMD_E_UNSUPPORTED;
   if (piped) select_slot(e, 1 - e->slot);
   const int slot = e->slot;
   // an unpipelined solve on an engine with streams of its own: ordered against them
@@ -736,6 +760,10 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
   // planner sets: paths of their own sizes in arrays of stride P_cap; P is the largest in use
   e->ws.np = plan ? plan->np : nullptr;
   e->ws.p_stride = (plan && plan->np) ? plan->K - 3 : P;
+  if (fitted) {
+    e->ws.np = fitted->np;
+    e->ws.p_stride = fitted->p_stride;
+  }
   // ragged batches: sweep workgroups take the paths longest first (k_order_paths, below)
   int32_t *order = const_cast<int32_t *>(e->ws.order);
   const bool ordered = in->num_samples_per_path != nullptr && B > 1 && e->order_ragged && plan == nullptr;
@@ -757,6 +785,7 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
                        ws);
     if (plan)
       hipLaunchKernelGGL(k_plan_mark_skipped, dim3((B + 127) / 128), dim3(128), 0, fs, *plan, ws);
+    if (fitted && fitted->any_empty) launch_skip_empty_paths(B, fitted->np, ws.err_bits, fs);
     if (ordered)
       hipLaunchKernelGGL(k_order_paths, dim3(1), dim3(1024), 0, fs, B, N, in->num_samples_per_path, order);
   }
@@ -2031,6 +2060,248 @@ int tpamd_query_device(tpamd_engine *e, int B, int N, int K, const double *time,
                      osd, osdd, ok);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- waypoint batches: fit and timing in one call
+namespace {
+
+// The call-level checks on the waypoint rows of a batch; fills the control-point count of every path.
+int waypoint_rows_args(int num_paths, const int32_t *offsets, std::vector<int32_t> *np) {
+  if (num_paths < 0 || !offsets || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  if (num_paths > kMaxPosePaths) return TPAMD_E_UNSUPPORTED;
+  np->resize(num_paths);
+  for (int k = 0; k < num_paths; k++) {
+    if (offsets[k + 1] < offsets[k]) return TPAMD_E_INVALID_ARGUMENT;
+    const long long W = (long long)offsets[k + 1] - offsets[k];
+    if (W > (1 << 24)) return TPAMD_E_UNSUPPORTED;
+    (*np)[k] = W < 1 ? 0 : fit_points((int)W);
+  }
+  return 0;
+}
+
+int joint_fit_args(const tpamd_engine *e, int num_paths, int num_dofs, const int32_t *offsets, const double *wps,
+                   const double *knots, const double *cps, const int32_t *num_points, const double *path_end,
+                   const int32_t *status, std::vector<int32_t> *np, PosePacking *pk) {
+  if (!e || !num_points || !path_end || !status || num_dofs < 1 || num_dofs > 16) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = waypoint_rows_args(num_paths, offsets, np)) return rc;
+  if (!pk->build(num_paths, np->data())) return TPAMD_E_UNSUPPORTED;
+  if (num_paths && offsets[num_paths] > 0 && (!wps || !knots || !cps)) return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+
+// The engine's scratch of a waypoint batch: B slots of S control points, and what the fit knows per path.
+struct WaypointScratch {
+  double *knots, *cps, *path_end, *delta, *zero;
+  int32_t *np, *ns;
+};
+size_t carve_waypoint_scratch(char *base, size_t B, size_t S, size_t D, WaypointScratch *w) {
+  Stage s(base);
+  w->knots = s.take<double>(B * (S + 3));
+  w->cps = s.take<double>(B * S * D);
+  w->path_end = s.take<double>(B);
+  w->delta = s.take<double>(B);
+  w->zero = s.take<double>(B);
+  w->np = s.take<int32_t>(B);
+  w->ns = s.take<int32_t>(B);
+  return s.off;
+}
+
+// What both timing entries check before anything is written; *slot = the largest control-point count
+// (at least 4: the slot size of the scratch and of the optional spline outputs).
+int waypoint_timing_args(const tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                         const tpamd_path_outputs *out, std::vector<int32_t> *np, int *slot, bool *any_empty) {
+  if (!e || !bt || !in || !out || bt->num_paths < 0) return TPAMD_E_INVALID_ARGUMENT;
+  const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
+  if (D < 1 || D > 16 || N < 3 || N > 8192) return TPAMD_E_UNSUPPORTED;
+  if (!in->waypoint_offsets || !in->max_velocity || !in->max_acceleration || !out->time || !out->s || !out->sd ||
+      !out->sdd || !out->status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = waypoint_rows_args(B, in->waypoint_offsets, np)) return rc;
+  if (B && in->waypoint_offsets[B] > 0 && !in->waypoints) return TPAMD_E_INVALID_ARGUMENT;
+  int S = 4;
+  bool empty = false;
+  for (int k = 0; k < B; k++) {
+    S = std::max(S, (*np)[k]);
+    empty = empty || (*np)[k] == 0;
+  }
+  // the sampling/LP kernel stages a path's knots and control points in LDS: sized by the largest P
+  const bool ragged = in->num_samples_per_path != nullptr || empty;
+  if (sample_lp_lds(S, D, sample_lp_block(false, ragged, D)) > kSampleLpLdsLimit) return TPAMD_E_UNSUPPORTED;
+  *slot = S;
+  *any_empty = empty;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_fit_joint_waypoints_device(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *waypoint_offsets,
+                                     const double *waypoints, const double *rounding, double *knots,
+                                     double *control_points, int32_t *num_points, int32_t *point_offsets,
+                                     double *path_end, int32_t *status, void *hip_stream) {
+  std::vector<int32_t> np;
+  PosePacking pk;
+  if (int rc = joint_fit_args(e, num_paths, num_dofs, waypoint_offsets, waypoints, knots, control_points, num_points,
+                              path_end, status, &np, &pk))
+    return rc;
+  const size_t n = (size_t)num_paths;
+  if (point_offsets) std::memcpy(point_offsets, pk.point.data(), (n + 1) * sizeof(int32_t));
+  if (num_paths == 0) return 0;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  std::vector<int32_t> ints(waypoint_offsets, waypoint_offsets + n + 1);
+  ints.insert(ints.end(), pk.point.begin(), pk.point.end());
+  ints.insert(ints.end(), pk.knot.begin(), pk.knot.end());
+  const int32_t *d = nullptr;
+  if (int rc = stage_pose_ints(e, ints, st, &d)) return rc;
+  JointFitParams p{};
+  p.Q = num_paths; p.D = num_dofs;
+  p.offsets = d; p.point_offsets = d + (n + 1); p.knot_offsets = d + 2 * (n + 1);
+  p.wps = waypoints; p.rounding = rounding;
+  p.knots = knots; p.cps = control_points;
+  p.num_points = num_points; p.path_end = path_end;
+  p.status = status; p.status_empty = TPAMD_PLAN_INVALID_ARGUMENT; p.status_all = 1;
+  launch_fit_joint_waypoints(p, st);
+  return pose_ints_done(e, st);
+}
+
+int tpamd_fit_joint_waypoints_host(tpamd_engine *e, int num_paths, int num_dofs, const int32_t *waypoint_offsets,
+                                   const double *waypoints, const double *rounding, double *knots,
+                                   double *control_points, int32_t *num_points, int32_t *point_offsets,
+                                   double *path_end, int32_t *status) {
+  std::vector<int32_t> np;
+  PosePacking pk;
+  if (int rc = joint_fit_args(e, num_paths, num_dofs, waypoint_offsets, waypoints, knots, control_points, num_points,
+                              path_end, status, &np, &pk))
+    return rc;
+  const size_t n = (size_t)num_paths, D = (size_t)num_dofs;
+  if (num_paths == 0) {
+    if (point_offsets) point_offsets[0] = 0;
+    return 0;
+  }
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  const double *d_w, *d_r;
+  double *d_k, *d_c, *d_pe;
+  int32_t *d_np, *d_st;
+  HostStage s;
+  s.up(&d_w, waypoints, (size_t)waypoint_offsets[n] * D);
+  s.up(&d_r, rounding, n);
+  s.down(&d_k, knots, pk.knots());
+  s.down(&d_c, control_points, pk.points() * D);
+  s.down(&d_np, num_points, n);
+  s.down(&d_pe, path_end, n);
+  s.down(&d_st, status, n);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  int rc = tpamd_fit_joint_waypoints_device(e, num_paths, num_dofs, waypoint_offsets, d_w, d_r, d_k, d_c, d_np,
+                                            point_offsets, d_pe, d_st, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_time_waypoint_paths_device(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                                     const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit,
+                                     void *hip_stream) {
+  std::vector<int32_t> np;
+  int S = 0;
+  bool any_empty = false;
+  if (int rc = waypoint_timing_args(e, bt, in, out, &np, &S, &any_empty)) return rc;
+  const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
+  if (B == 0) return 0;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  // the scratch: an earlier call's kernels may still read it (on any stream) when it has to move
+  WaypointScratch w{};
+  const size_t need = carve_waypoint_scratch(nullptr, B, S, D, &w);
+  if (need > e->wp_fit.bytes) {
+    HIPCHK(hipDeviceSynchronize());
+    if (e->wp_fit.reserve(need)) return TPAMD_E_HIP;
+  }
+  carve_waypoint_scratch((char *)e->wp_fit.p, B, S, D, &w);
+  const std::vector<int32_t> ints(in->waypoint_offsets, in->waypoint_offsets + B + 1);
+  const int32_t *d_off = nullptr;
+  if (int rc = stage_pose_ints(e, ints, st, &d_off)) return rc;
+  // a path without waypoints leaves the solve through its sample count (0), so such a batch is ragged
+  const bool ragged = in->num_samples_per_path != nullptr || any_empty;
+  JointFitParams p{};
+  p.Q = B; p.D = D;
+  p.offsets = d_off; p.wps = in->waypoints; p.rounding = in->rounding;
+  p.p_stride = S; p.knots = w.knots; p.cps = w.cps;
+  p.num_points = (fit && fit->num_points) ? fit->num_points : w.np;
+  p.path_end = (fit && fit->path_end) ? fit->path_end : w.path_end;
+  p.status = out->status; p.status_empty = TPAMD_PATH_NO_WAYPOINTS; p.status_all = 0;
+  p.N = N; p.samples_in = in->num_samples_per_path; p.delta_in = in->delta;
+  p.delta = (fit && fit->delta_used) ? fit->delta_used : w.delta;
+  p.samples = ragged ? w.ns : nullptr;
+  p.zero = w.zero;
+  launch_fit_joint_waypoints(p, st);
+  if (int rc = pose_ints_done(e, st)) return rc;
+  const tpamd_joint_batch jb{B, D, N, S, bt->max_solver_loops, 0, bt->constraint_safety};
+  tpamd_joint_inputs ji{};
+  ji.knots = w.knots; ji.control_points = w.cps;
+  ji.max_velocity = in->max_velocity; ji.max_acceleration = in->max_acceleration;
+  ji.path_start = w.zero; ji.delta = p.delta;
+  ji.sd_start = in->sd_start ? in->sd_start : w.zero;
+  ji.time_start = in->time_start ? in->time_start : w.zero;
+  ji.num_samples_per_path = p.samples;
+  const FittedPaths fitted{p.num_points, S, any_empty};
+  // never pipelined: the front stage reads what the fit, just enqueued on this stream, writes
+  if (int rc = solve_joint(e, &jb, &ji, out, st, nullptr, /*allow_pipelining=*/false, &fitted)) return rc;
+  if (fit && fit->knots)
+    HIPCHK(hipMemcpyAsync(fit->knots, w.knots, (size_t)B * (S + 3) * 8, hipMemcpyDeviceToDevice, st));
+  if (fit && fit->control_points)
+    HIPCHK(hipMemcpyAsync(fit->control_points, w.cps, (size_t)B * S * D * 8, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+int tpamd_time_waypoint_paths_host(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                                   const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit) {
+  std::vector<int32_t> np;
+  int slot = 0;
+  bool any_empty = false;
+  if (int rc = waypoint_timing_args(e, bt, in, out, &np, &slot, &any_empty)) return rc;
+  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, S = slot;
+  if (in->num_samples_per_path)
+    for (size_t k = 0; k < B; k++)
+      if (in->num_samples_per_path[k] > bt->num_samples) return TPAMD_E_INVALID_ARGUMENT;
+  if (B == 0) return 0;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_waypoint_inputs din{};
+  tpamd_path_outputs dout{};
+  tpamd_waypoint_fit_outputs dfit{};
+  HostStage s;
+  din.waypoint_offsets = in->waypoint_offsets;
+  s.up(&din.waypoints, in->waypoints, (size_t)in->waypoint_offsets[B] * D);
+  s.up(&din.rounding, in->rounding, B);
+  s.up(&din.max_velocity, in->max_velocity, B * D);
+  s.up(&din.max_acceleration, in->max_acceleration, B * D);
+  s.up(&din.num_samples_per_path, in->num_samples_per_path, B);
+  s.up(&din.delta, in->delta, B);
+  s.up(&din.sd_start, in->sd_start, B);
+  s.up(&din.time_start, in->time_start, B);
+  // a path without waypoints, and a path's rows behind its own sample count, keep what the caller's
+  // arrays hold: those go up as well then
+  stage_path_outputs(s, B, N, D, out, &dout, /*keep=*/any_empty || in->num_samples_per_path != nullptr);
+  if (fit) {
+    s.down(&dfit.num_points, fit->num_points, B);
+    s.down(&dfit.path_end, fit->path_end, B);
+    s.down(&dfit.delta_used, fit->delta_used, B);
+    s.down(&dfit.knots, fit->knots, B * (S + 3));
+    s.down(&dfit.control_points, fit->control_points, B * S * D);
+  }
+  if (int rc = s.upload(e->stage, st)) return rc;
+  if (any_empty) {
+    // (the two per-path outputs that are staged either way)
+    if (out->last_extremal_index)
+      HIPCHK(hipMemcpyAsync(dout.last_extremal_index, out->last_extremal_index, B * 4, hipMemcpyHostToDevice, st));
+    if (out->max_time_increment)
+      HIPCHK(hipMemcpyAsync(dout.max_time_increment, out->max_time_increment, B * 8, hipMemcpyHostToDevice, st));
+  }
+  int rc = tpamd_time_waypoint_paths_device(e, bt, &din, &dout, &dfit, st);
+  return rc ? rc : s.download(st);
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # 
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
             "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
-            "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip"]
+            "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip", "tpamd_joint_fit.h", "tpamd_joint_fit.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -26,7 +26,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-s
 PATH_STATUS = {
     0: "ok", 2: "infeasible_bounds", 3: "s_range", 4: "sd_start_negative",
     5: "lower_ge_upper", 6: "too_few_samples", 7: "no_connection", 8: "nan_sd2",
-    9: "nonzero_end", 10: "crit_index_zero",
+    9: "nonzero_end", 10: "crit_index_zero", 11: "no_waypoints",
 }
 
 KERNEL_SWEEP = 4
@@ -58,7 +58,8 @@ def _compile(target, extra_flags, force, verbose):
     units = [(os.path.join(objdir, "capi.o"), ["tpamd_capi.hip"]),
              (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"]),
              (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"]),
-             (os.path.join(objdir, "retarget.o"), ["tpamd_retarget.hip"])]
+             (os.path.join(objdir, "retarget.o"), ["tpamd_retarget.hip"]),
+             (os.path.join(objdir, "joint_fit.o"), ["tpamd_joint_fit.hip"])]
     for d, e in SWEEP_INSTANCES:
         units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
                       ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
@@ -132,6 +133,21 @@ class _PathOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
         "max_time_increment", "status", "sd2")]
+
+
+class _WaypointBatch(C.Structure):
+    _fields_ = [("num_paths", C.c_int32), ("num_dofs", C.c_int32), ("num_samples", C.c_int32),
+                ("max_solver_loops", C.c_int32), ("constraint_safety", C.c_double)]
+
+
+class _WaypointInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "waypoint_offsets", "waypoints", "rounding", "max_velocity", "max_acceleration",
+        "num_samples_per_path", "delta", "sd_start", "time_start")]
+
+
+class _WaypointFitOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("num_points", "path_end", "delta_used", "knots", "control_points")]
 
 
 class _RowsBatch(C.Structure):
@@ -223,6 +239,8 @@ ABI_SYMBOLS = [
     "tpamd_time_joint_paths_device",
     "tpamd_time_joint_paths_host", "tpamd_sample_joint_paths_host",
     "tpamd_ik_table_rows", "tpamd_fit_pose_waypoints_host", "tpamd_fit_pose_waypoints_device",
+    "tpamd_fit_joint_waypoints_host", "tpamd_fit_joint_waypoints_device",
+    "tpamd_time_waypoint_paths_host", "tpamd_time_waypoint_paths_device",
     "tpamd_sample_ik_targets_host", "tpamd_sample_ik_targets_device",
     "tpamd_time_joint_groups_device", "tpamd_time_joint_groups_host",
     "tpamd_optimize_rows_device", "tpamd_optimize_rows_host",
@@ -365,6 +383,13 @@ def load_library():
     L.tpamd_fit_pose_waypoints_device.argtypes = [vp, i, i] + [vp] * 13 + [vp]
     L.tpamd_sample_ik_targets_host.argtypes = [vp, i, i] + [vp] * 9
     L.tpamd_sample_ik_targets_device.argtypes = [vp, i, i] + [vp] * 9 + [vp]
+    for name in ("tpamd_fit_joint_waypoints_host", "tpamd_fit_joint_waypoints_device",
+                 "tpamd_time_waypoint_paths_host", "tpamd_time_waypoint_paths_device"):
+        getattr(L, name).restype = i
+    L.tpamd_fit_joint_waypoints_host.argtypes = [vp, i, i] + [vp] * 9
+    L.tpamd_fit_joint_waypoints_device.argtypes = [vp, i, i] + [vp] * 9 + [vp]
+    L.tpamd_time_waypoint_paths_host.argtypes = [vp] * 5
+    L.tpamd_time_waypoint_paths_device.argtypes = [vp] * 5 + [vp]
     L.tpamd_find_max_sd2_host.restype = i
     L.tpamd_find_max_sd2_host.argtypes = [vp, i, i] + [vp] * 7
     L.tpamd_query_device.restype = i
@@ -816,6 +841,117 @@ class Engine:
                 _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"])),
                 "tpamd_fit_pose_waypoints_host")
         out["point_offsets"] = point_offsets
+        return out
+
+    # ------------------------------------------------------------ waypoint batches
+    def fit_joint_waypoints(self, waypoints, offsets, rounding=None, stream=None):
+        """TimeableJointSplinePath::SetWaypoints for B paths (tpamd_fit_joint_waypoints_*): path k takes
+        rows offsets[k]:offsets[k + 1] of waypoints [rows][D]; rounding is [B], one number, or None
+        (0.2). Returns a dict: knots, control_points [sum P][D] (packed raggedly), num_points,
+        path_end, status [B] (TPAMD_PLAN_*) and point_offsets [B + 1] (always a numpy array). CUDA
+        waypoints go through the _device entry on `stream` (default: torch's current stream) and give
+        CUDA tensors; numpy arrays go through the host entry, which synchronises, and give numpy
+        arrays."""
+        import torch
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        B = off.shape[0] - 1
+        if B < 0:
+            raise TpamdError("waypoint offsets need at least one entry")
+        W = np.diff(off.astype(np.int64))
+        npts = np.where(W < 1, 0, np.where(W == 1, 4, 3 * W - 2))
+        P, K = int(npts.sum()), int((npts + 3 * (npts > 0)).sum())
+        rows = int(off[-1])
+        if waypoints.ndim != 2 or waypoints.shape[0] != rows:
+            raise TpamdError("waypoints has shape %s, expected (%d, D)" % (tuple(waypoints.shape), rows))
+        D = int(waypoints.shape[1])
+        point_offsets = np.zeros(B + 1, dtype=np.int32)
+        if _is_cuda(waypoints):
+            dev = waypoints.device
+            w = PlannerSet._cuda(waypoints, torch.float64, dev, (rows, D), "waypoints")
+            r = None
+            if rounding is not None:
+                r = PlannerSet._cuda(rounding if hasattr(rounding, "shape") and len(rounding.shape) else
+                                     torch.full((B,), float(rounding), dtype=torch.float64), torch.float64, dev, (B,),
+                                     "rounding")
+            new = lambda shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+            out = dict(knots=new((K,)), control_points=new((P, D)), num_points=new((B,), torch.int32),
+                       path_end=new((B,)), status=torch.full((B,), -1, dtype=torch.int32, device=dev))
+            _check(self._lib.tpamd_fit_joint_waypoints_device(
+                self._h, B, D, _ptr(off), _ptr(w), _ptr(r), _ptr(out["knots"]), _ptr(out["control_points"]),
+                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"]),
+                _stream_ptr(stream)), "tpamd_fit_joint_waypoints_device")
+        else:
+            w = _host(waypoints, np.float64, (rows, D), "waypoints")
+            r = None if rounding is None else _host(np.broadcast_to(_host(rounding, np.float64), (B,)), np.float64,
+                                                    (B,), "rounding")
+            out = dict(knots=np.zeros(K), control_points=np.zeros((P, D)), num_points=np.zeros(B, dtype=np.int32),
+                       path_end=np.zeros(B), status=np.full(B, -1, dtype=np.int32))
+            _check(self._lib.tpamd_fit_joint_waypoints_host(
+                self._h, B, D, _ptr(off), _ptr(w), _ptr(r), _ptr(out["knots"]), _ptr(out["control_points"]),
+                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"])),
+                "tpamd_fit_joint_waypoints_host")
+        out["point_offsets"] = point_offsets
+        return out
+
+    def time_waypoint_paths(self, waypoints, offsets, max_velocity, max_acceleration, num_samples,
+                            num_samples_per_path=None, delta=None, rounding=None, sd_start=None, time_start=None,
+                            safety=0.8, outputs=None, stream=None, host=False):
+        """Waypoints in, trajectories out (tpamd_time_waypoint_paths_*): path k takes rows
+        offsets[k]:offsets[k + 1] of waypoints [rows][D] (offsets: host int32 [B + 1]), is fitted on the
+        device and timed from path parameter 0 with num_samples_per_path[k] samples (None: num_samples
+        each) at delta[k] (None: the samples cover exactly the whole path). max_velocity and
+        max_acceleration are [B][D]; rounding, sd_start and time_start [B] or None (0.2, 0, 0).
+        Torch CUDA tensors on `stream` (host=False; nothing synchronises unless the engine's scratch
+        grows) or numpy arrays (host=True). Returns a dict with time, s, sd, sdd [B][N], q, qd, qdd
+        [B][N][D], status, last_extremal_index, num_points [B] int32 and max_time_increment, path_end,
+        delta_used [B] -- the arrays of `outputs` where it has them (also knots [B][S + 3] and
+        control_points [B][S][D], S = max(3 max W - 2, 4), filled only if given), new ones otherwise.
+        A path without waypoints gets status 11 (PATH_STATUS) and nothing else of it is written."""
+        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+        B = off.shape[0] - 1
+        if B < 0:
+            raise TpamdError("waypoint offsets need at least one entry")
+        N, D = int(num_samples), int(max_velocity.shape[-1])
+        out = dict(outputs) if outputs else {}
+        if host:
+            f = lambda x, shape, what, dt=np.float64: _host(x, dt, shape, what)
+            new = lambda shape, dt=np.float64: np.zeros(shape, dtype=dt)
+            i32 = np.int32
+        else:
+            import torch
+            dev = max_velocity.device
+            f = lambda x, shape, what, dt=torch.float64: None if x is None else PlannerSet._cuda(x, dt, dev, shape, what)
+            new = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
+            i32 = torch.int32
+        rows = int(off[-1])
+        w = f(waypoints, (rows, D), "waypoints")
+        vm, am = f(max_velocity, (B, D), "max_velocity"), f(max_acceleration, (B, D), "max_acceleration")
+        ns = f(num_samples_per_path, (B,), "num_samples_per_path", i32)
+        dl, rd = f(delta, (B,), "delta"), f(rounding, (B,), "rounding")
+        sd0, t0 = f(sd_start, (B,), "sd_start"), f(time_start, (B,), "time_start")
+        for k in ("time", "s", "sd", "sdd"):
+            out.setdefault(k, new((B, N)))
+        for k in ("q", "qd", "qdd"):
+            out.setdefault(k, new((B, N, D)))
+        for k in ("status", "last_extremal_index", "num_points"):
+            out.setdefault(k, new((B,), i32))
+        for k in ("max_time_increment", "path_end", "delta_used"):
+            out.setdefault(k, new((B,)))
+        bt = _WaypointBatch(B, D, N, 0, float(safety))
+        wi = _WaypointInputs(_ptr(off), _ptr(w), _ptr(rd), _ptr(vm), _ptr(am), _ptr(ns), _ptr(dl), _ptr(sd0),
+                             _ptr(t0))
+        po = _PathOutputs(*[_ptr(out.get(k)) for k in (
+            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index", "max_time_increment", "status",
+            "sd2")])
+        fo = _WaypointFitOutputs(*[_ptr(out.get(k)) for k in (
+            "num_points", "path_end", "delta_used", "knots", "control_points")])
+        if host:
+            _check(self._lib.tpamd_time_waypoint_paths_host(self._h, C.byref(bt), C.byref(wi), C.byref(po),
+                                                            C.byref(fo)), "tpamd_time_waypoint_paths_host")
+        else:
+            _check(self._lib.tpamd_time_waypoint_paths_device(self._h, C.byref(bt), C.byref(wi), C.byref(po),
+                                                              C.byref(fo), _stream_ptr(stream)),
+                   "tpamd_time_waypoint_paths_device")
         return out
 
     # ------------------------------------------------------------ path_tools
