@@ -1477,6 +1477,94 @@ int tpamd_planner_set_stop_parameters(tpamd_planner_set *set, int count, const i
                                       double *duration, int32_t *status);
 
 /* ------------------------------------------------------------------------
+ * Checking a batch's solutions against its constraint rows:
+ * TimeOptimalPathProfile::SolutionSatisfiesConstraints (time_optimal_path_timing.cc:492-518) for
+ * every path of a batch. TPAMD_PATH_OK does NOT imply that a path keeps its constraints: on an
+ * undersampled path the reference's solver returns OK with violated rows, and so does this engine,
+ * bit for bit ("Checking a batch against its constraints").
+ *
+ * The calls are stateless: the caller passes the batch description it gave the solve and the
+ * solution the solve wrote. For path b, samples i < n_b and rows c < C, with sd2 = sol->sd2[b][i] and
+ * sdd = sol->sdd[b][i]:
+ *   v = a(i,c) * sdd + b(i,c) * sd2           (two products and one sum, not contracted)
+ *   row (i,c) is violated  <=>  v + kTiny < lower || v - kTiny > upper, kTiny = 1e5 * DBL_EPSILON
+ *                               (time_optimal_path_timing.h:275-279, the reference's test)
+ *   excess(i,c) = max(lower - v, v - upper): negative where the row has margin
+ * and the rows a, b, lower, upper are exactly those the matching solve forms. Per path:
+ *   violations    the number of violated rows; -1: the path is not checked -- sol->status[b] is not
+ *                 TPAMD_PATH_OK (the reference's "No valid solution"), or its sample count is one
+ *                 for which the solve entry fails the path (outside [2, num_samples]); its
+ *                 worst_excess is then NaN and its three indices are -1
+ *   worst_excess  the largest excess over the rows whose excess is not NaN; NaN if there is none
+ *   worst_sample, worst_row   i and c of that row; among equal values the smallest i * C + c (so no
+ *                 order of evaluation can change the answer); -1 if there is none
+ *   first_sample  the smallest i with a violated row; -1 if there is none
+ * A NaN v violates nothing (both comparisons are false, as in the reference) and has no excess.
+ * Without sol->sd2, sd[i] * sd[i] takes its place; the count can then differ from the reference's
+ * where a row sits at the kTiny edge, because sqrt followed by the square does not give sd2 back.
+ * ------------------------------------------------------------------------ */
+typedef struct tpamd_solution {      /* what a solve wrote (tpamd_path_outputs); device pointers for _device */
+  const double *sd2;     /* [B][N], or NULL: sd*sd */
+  const double *sd;      /* [B][N], read only if sd2 is NULL */
+  const double *sdd;     /* [B][N] */
+  const int32_t *status; /* [B] TPAMD_PATH_*; NULL: every path is checked */
+} tpamd_solution;
+typedef struct tpamd_check_outputs {
+  int32_t *violations;   /* [B], required */
+  double *worst_excess;  /* [B], may be NULL (as the three below) */
+  int32_t *worst_sample, *worst_row, *first_sample;
+} tpamd_check_outputs;
+
+/* Conventions of the six entries: _device takes device pointers, enqueues one kernel on hip_stream
+ * (one workgroup per path) and does not synchronise; _host takes host pointers and synchronises.
+ * Neither reads nor disturbs what the engine holds of the last solve (tpamd_query_device still sees
+ * it); the check is never pipelined. Call-level errors write nothing and follow the matching solve
+ * entry: a NULL engine, struct or required input array, num_paths < 0, a NULL sol, sol->sdd, out or
+ * out->violations, or sol->sd2 and sol->sd both NULL (TPAMD_E_INVALID_ARGUMENT); num_dofs outside
+ * 1..16, num_rows outside 1..64, num_samples outside 3..8192, more than 65535 paths, or a spline
+ * that does not fit the sampling/LP kernel's LDS (TPAMD_E_UNSUPPORTED).
+ *
+ * Rows form (tpamd_optimize_rows_*, tpamd_optimize_rows_ragged_*): the rows are the caller's arrays.
+ * num_samples_per_path [B] as the ragged solve takes it, NULL: every path has num_samples.
+ * in->s_start .. in->time_start are not read and may be NULL. */
+int tpamd_check_rows_device(tpamd_engine *engine, const tpamd_rows_batch *batch, const tpamd_rows_inputs *in,
+                            const int32_t *num_samples_per_path, const tpamd_solution *sol,
+                            const tpamd_check_outputs *out, void *hip_stream);
+int tpamd_check_rows_host(tpamd_engine *engine, const tpamd_rows_batch *batch, const tpamd_rows_inputs *in,
+                          const int32_t *num_samples_per_path, const tpamd_solution *sol,
+                          const tpamd_check_outputs *out);
+/* Joint form (tpamd_time_joint_paths_*): SamplePath and ConstraintSetup as the sampling/LP kernel
+ * does them (the clamp of the parameter to the knots, the end padding with zero derivatives,
+ * B = q' * q' for the velocity rows) and the set-up kernel's limits, C = 2D. Ragged through
+ * in->num_samples_per_path, as the solve. in->sd_start, sdd_start, time_start and
+ * batch->max_solver_loops are not read.
+ * num_points_per_path [B] (NULL: every path has batch->num_points control points) checks a waypoint
+ * batch (tpamd_time_waypoint_paths_*) from its own fit outputs: knots [B][S + 3] and control_points
+ * [B][S][D] then have the slot layout tpamd_waypoint_fit_outputs writes, S = batch->num_points, path
+ * k uses the first num_points_per_path[k] entries of its slot, in->delta = delta_used and
+ * in->path_start = zeros. A path with fewer than 3 (or more than S) control points is not checked. */
+int tpamd_check_joint_paths_device(tpamd_engine *engine, const tpamd_joint_batch *batch,
+                                   const tpamd_joint_inputs *in, const int32_t *num_points_per_path,
+                                   const tpamd_solution *sol, const tpamd_check_outputs *out, void *hip_stream);
+int tpamd_check_joint_paths_host(tpamd_engine *engine, const tpamd_joint_batch *batch,
+                                 const tpamd_joint_inputs *in, const int32_t *num_points_per_path,
+                                 const tpamd_solution *sol, const tpamd_check_outputs *out);
+/* Cartesian form (tpamd_time_cartesian_paths_*, tpamd_time_cartesian_paths_ragged_*):
+ * ComputePathDerivatives with the edge rules of the forward differences at n_b - 1 and the
+ * C = 2D + 2 rows of ConstraintSetup, J q' summed over the joints in index order.
+ * num_samples_per_path and first_row may both be NULL (uniform, strided); otherwise they mean what
+ * they mean to the ragged solve, packed row tables included (num_rows: the rows the _host entry
+ * stages, read only with first_row). in->sd_start, sdd_start and time_start are not read. */
+int tpamd_check_cartesian_paths_device(tpamd_engine *engine, const tpamd_cartesian_batch *batch,
+                                       const tpamd_cartesian_inputs *in, const int32_t *num_samples_per_path,
+                                       const int32_t *first_row, const tpamd_solution *sol,
+                                       const tpamd_check_outputs *out, void *hip_stream);
+int tpamd_check_cartesian_paths_host(tpamd_engine *engine, const tpamd_cartesian_batch *batch,
+                                     const tpamd_cartesian_inputs *in, const int32_t *num_samples_per_path,
+                                     const int32_t *first_row, int64_t num_rows, const tpamd_solution *sol,
+                                     const tpamd_check_outputs *out);
+
+/* ------------------------------------------------------------------------
  * Debug/inspection: copy the boundary curve of the LAST solve to host arrays
  * [B][N] (Boundary::sd2_max, sdd_max_for_sd2_max, sdd_min_for_sd2_max,
  * sd2_max_for_sdd0, type; time_optimal_path_timing.h:225-255) and the squared

@@ -1,10 +1,16 @@
 """Randomised parity fuzzing of the engine against the oracle (run on the GPU box):
 
-    python tools/gpu_fuzz.py [seconds] [seed]
+    python tools/gpu_fuzz.py [--check] [seconds] [seed]
 
 Random joint counts, sample counts, batch sizes, limit scales, start velocities, ragged
 batches and Cartesian batches; every path of every case must match the oracle bit for bit
 (status, last extremal index, t, s, sd, sdd, q, qd, qdd). Prints one JSON summary line.
+
+--check: the uniform joint and the Cartesian cases also run the device check of the engine's own
+solution (Engine.check_joint_paths / check_cartesian_paths) and compare its violations, path by path,
+with the oracle's constraint_violations() of the same path (SolutionSatisfiesConstraints,
+time_optimal_path_timing.cc:492-518; -1 where the path has no solution). The summary then also holds
+checked_paths and ok_paths_with_violations, the number of status-OK paths with a non-zero count.
 """
 import importlib
 import json
@@ -45,9 +51,30 @@ def check(out, ref, counts=None):
     return None
 
 
+def oracle_violations(rows, s_start, s_end, sd_start, time_start):
+    """constraint_violations() of the oracle's own solve of one path (-1: no solution)."""
+    N, Cn = rows[0].shape
+    p = tpo.Profile(N, Cn)
+    p.set_max_loops(max(100, 10 * N))
+    rc = p.setup(*rows, float(s_start), float(s_end), float(sd_start), 0.0, float(time_start))
+    if rc == 0:
+        rc = p.optimize()
+    return p.constraint_violations() if rc == 0 else -1
+
+
+def check_violations(got, want, status):
+    """(field name or None, number of status-OK paths with violated rows)."""
+    got = got["violations"].cpu().numpy()
+    bad = None if np.array_equal(got, np.asarray(want, dtype=got.dtype)) else "violations"
+    return bad, int(((status == 0) & (got > 0)).sum())
+
+
 def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    argv = [a for a in sys.argv[1:] if a != "--check"]
+    do_check = len(argv) != len(sys.argv) - 1
+    budget = float(argv[0]) if len(argv) > 0 else 120.0
+    seed = int(argv[1]) if len(argv) > 1 else 1
+    checked = violated = 0
     rng = np.random.default_rng(seed)
     E = eng.Engine(0)
     t_end = time.time() + budget
@@ -115,9 +142,26 @@ def main():
             ref = tpo.time_cartesian_batch(b["ik_positions"], b["jacobians"], b["vmax"], b["amax"], b["vtrans"],
                                            b["vrot"], b["path_start"], b["delta"], nthreads=16)
             out = eng.alloc_joint_outputs(B, N, D, DEV)
-            E.time_cartesian_paths(syn.upload_cartesian_batch(b, DEV), out)
+            if do_check:
+                out["sd2"] = torch.empty(B, N, dtype=torch.float64, device=DEV)
+            inp = syn.upload_cartesian_batch(b, DEV)
+            E.time_cartesian_paths(inp, out)
             torch.cuda.synchronize()
             bad = check(out, ref)
+            if do_check and not bad:
+                want = []
+                for i in range(B):
+                    q1, q2 = tpo.cartesian_path_derivatives(b["ik_positions"][i], b["delta"][i])
+                    jq1 = np.zeros((N, 6))
+                    for d in range(D):             # J q', the joints added in index order
+                        jq1 = jq1 + b["jacobians"][i][:, :, d] * q1[:, d:d + 1]
+                    rows = tpo.cartesian_constraint_setup(q1, q2, jq1, b["vmax"][i], b["amax"][i], b["vtrans"][i],
+                                                          b["vrot"][i], b["safety"])
+                    want.append(oracle_violations(rows, b["path_start"][i], b["path_start"][i] + b["delta"][i] * (N - 1),
+                                                  0.0, 0.0))
+                bad, nz = check_violations(E.check_cartesian_paths(inp, out, safety=b["safety"]), want, ref["status"])
+                checked += B
+                violated += nz
         else:
             b = syn.make_joint_batch(B, D, N, num_waypoints=W, first_path_index=first)
             b["vmax"] = b["vmax"] * rng.uniform(0.2, 4.0, (B, 1))
@@ -153,11 +197,29 @@ def main():
                                            b["delta"], N, sd_start=b["sd_start"], time_start=b["time_start"],
                                            nthreads=16)
                 bad = check(out, ref)
+                if do_check and not bad:
+                    sd2 = torch.empty(B, N, dtype=torch.float64, device=DEV)
+                    E.time_joint_paths(inp, dict(out, sd2=sd2), N)     # the same solve, asked for sd2 as well
+                    want = []
+                    for i in range(B):
+                        _, q1, q2 = tpo.joint_sample_path(b["knots"][i], b["control_points"][i], b["path_start"][i],
+                                                          b["delta"][i], N)
+                        rows = tpo.joint_constraint_setup(q1, q2, b["vmax"][i], b["amax"][i], b["safety"])
+                        want.append(oracle_violations(rows, b["path_start"][i],
+                                                      b["path_start"][i] + b["delta"][i] * (N - 1), b["sd_start"][i],
+                                                      b["time_start"][i]))
+                    bad, nz = check_violations(E.check_joint_paths(inp, dict(out, sd2=sd2), N, safety=b["safety"]),
+                                               want, ref["status"])
+                    checked += B
+                    violated += nz
         cases += 1
         paths += B
         if bad:
             failures.append(dict(desc, field=bad))
-    print(json.dumps(dict(seconds=budget, seed=seed, cases=cases, paths=paths, failures=failures)))
+    summary = dict(seconds=budget, seed=seed, cases=cases, paths=paths, failures=failures)
+    if do_check:
+        summary.update(checked_paths=checked, ok_paths_with_violations=violated)
+    print(json.dumps(summary))
     return 1 if failures else 0
 
 

@@ -26,6 +26,7 @@
 #include "tpamd_pose_fit.h"
 #include "tpamd_joint_fit.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
+#include "tpamd_check.h"
 
 using namespace tpamd;
 
@@ -411,6 +412,7 @@ struct DeviceScope {
 // for every kernel that can ask for more than 64 KB of LDS, once per device ordinal, when the
 // first engine on that device is created (thread-safe; a failure is reported).
 constexpr int kMaxDevices = 64;
+constexpr size_t kSampleLpLdsLimitBytes = 160 * 1024;   // the LDS of one CU: the sampling/LP kernel's limit
 std::mutex g_config_mutex;
 bool g_device_configured[kMaxDevices] = {};
 
@@ -446,6 +448,9 @@ int configure_kernels_for_device(int device) {
   TPAMD_BIG_LDS(k_cartesian_lp<1, 7>);
   TPAMD_BIG_LDS(k_cartesian_lp<1, 6, true>);
   TPAMD_BIG_LDS(k_cartesian_lp<1, 7, true>);
+  // (the kernel has static LDS of its own; what a spline the solve accepts needs lies 2 * D * 64 * 8 bytes and
+  // more below the sampling/LP kernel's limit)
+  TPAMD_BIG_LDS(k_check_joint, (int)kSampleLpLdsLimitBytes - 1024);
 #undef TPAMD_BIG_LDS
   g_device_configured[device] = true;
   return 0;
@@ -713,7 +718,7 @@ int sample_lp_block(bool piped, bool ragged, int D) {
 size_t sample_lp_lds(int P, int D, int tpb) {
   return ((size_t)(P + 3) + (size_t)P * D + 2 * (size_t)(2 * D) + 2 * (size_t)D * tpb) * 8;
 }
-constexpr size_t kSampleLpLdsLimit = 160 * 1024;
+constexpr size_t kSampleLpLdsLimit = kSampleLpLdsLimitBytes;
 
 // Waypoint batches (tpamd_time_waypoint_paths_*): the splines were fitted on the device into slots
 // of p_stride control points; path k has np[k] of them, 0 if it has no waypoints.
@@ -2301,6 +2306,215 @@ int tpamd_time_waypoint_paths_host(tpamd_engine *e, const tpamd_waypoint_batch *
       HIPCHK(hipMemcpyAsync(dout.max_time_increment, out->max_time_increment, B * 8, hipMemcpyHostToDevice, st));
   }
   int rc = tpamd_time_waypoint_paths_device(e, bt, &din, &dout, &dfit, st);
+  return rc ? rc : s.download(st);
+}
+
+}  // extern "C"
+
+// ---- checking solutions against their constraint rows (tpamd_check.h) ----------------------------
+namespace {
+constexpr int kMaxCheckPaths = 65535;
+
+// What the three forms check of the solution and the outputs.
+int check_io_args(const tpamd_solution *sol, const tpamd_check_outputs *out) {
+  if (!sol || !out || !sol->sdd || (!sol->sd2 && !sol->sd) || !out->violations) return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+CheckSolution check_solution(const tpamd_solution *sol) {
+  return CheckSolution{sol->sd2, sol->sd2 ? nullptr : sol->sd, sol->sdd, sol->status};
+}
+CheckOutputs check_outputs(const tpamd_check_outputs *out) {
+  return CheckOutputs{out->violations, out->worst_excess, out->worst_sample, out->worst_row, out->first_sample};
+}
+
+// The checks of the three forms behind the null structs and num_paths <= 0: the sizes as the solve
+// entry refuses them, then the arrays the check reads.
+int check_rows_args(const tpamd_rows_batch *bt, const tpamd_rows_inputs *in) {
+  const int N = bt->num_samples, C = bt->num_rows;
+  if (C < 1 || C > 64 || N < 3 || N > 8192 || bt->num_paths > kMaxCheckPaths) return TPAMD_E_UNSUPPORTED;
+  if (!in->a || !in->b || !in->lower || !in->upper) return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+int check_joint_args(const tpamd_joint_batch *bt, const tpamd_joint_inputs *in) {
+  const int D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
+  if (D < 1 || D > 16 || N < 3 || N > 8192 || P < 3 || bt->num_paths > kMaxCheckPaths) return TPAMD_E_UNSUPPORTED;
+  if (!in->knots || !in->control_points || !in->max_velocity || !in->max_acceleration || !in->path_start ||
+      !in->delta)
+    return TPAMD_E_INVALID_ARGUMENT;
+  // the solve's limit: the sampling/LP kernel's LDS at the block size it takes for this batch
+  if (sample_lp_lds(P, D, sample_lp_block(false, in->num_samples_per_path != nullptr, D)) > kSampleLpLdsLimit)
+    return TPAMD_E_UNSUPPORTED;
+  return 0;
+}
+int check_cartesian_args(const tpamd_cartesian_batch *bt, const tpamd_cartesian_inputs *in) {
+  const int D = bt->num_dofs, N = bt->num_samples;
+  if (D < 1 || D > 16 || N < 3 || N > 8192 || bt->num_paths > kMaxCheckPaths) return TPAMD_E_UNSUPPORTED;
+  if (!in->ik_positions || !in->jacobians || !in->max_velocity || !in->max_acceleration ||
+      !in->max_translational_velocity || !in->max_rotational_velocity || !in->delta)
+    return TPAMD_E_INVALID_ARGUMENT;
+  return 0;
+}
+
+// The solution and the record arrays of a _host check in `s`.
+void stage_check_io(HostStage &s, size_t B, size_t N, const tpamd_solution *sol, const tpamd_check_outputs *out,
+                    tpamd_solution *dsol, tpamd_check_outputs *dout) {
+  s.up(&dsol->sd2, sol->sd2, B * N);
+  s.up(&dsol->sd, sol->sd2 ? nullptr : sol->sd, B * N);
+  s.up(&dsol->sdd, sol->sdd, B * N);
+  s.up(&dsol->status, sol->status, B);
+  s.down(&dout->violations, out->violations, B);
+  s.down(&dout->worst_excess, out->worst_excess, B);
+  s.down(&dout->worst_sample, out->worst_sample, B);
+  s.down(&dout->worst_row, out->worst_row, B);
+  s.down(&dout->first_sample, out->first_sample, B);
+}
+}  // namespace
+
+extern "C" {
+
+int tpamd_check_rows_device(tpamd_engine *e, const tpamd_rows_batch *bt, const tpamd_rows_inputs *in,
+                            const int32_t *num_samples_per_path, const tpamd_solution *sol,
+                            const tpamd_check_outputs *out, void *hip_stream) {
+  if (!e || !bt || !in) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_io_args(sol, out)) return rc;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_rows_args(bt, in)) return rc;
+  TPAMD_ON_DEVICE(e);
+  hipLaunchKernelGGL(k_check_rows, dim3(bt->num_paths), dim3(kCheckThreads), 0, (hipStream_t)hip_stream,
+                     bt->num_samples, bt->num_rows, in->a, in->b, in->lower, in->upper, num_samples_per_path,
+                     check_solution(sol), check_outputs(out));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_check_rows_host(tpamd_engine *e, const tpamd_rows_batch *bt, const tpamd_rows_inputs *in,
+                          const int32_t *num_samples_per_path, const tpamd_solution *sol,
+                          const tpamd_check_outputs *out) {
+  if (!e || !bt || !in) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_io_args(sol, out)) return rc;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_rows_args(bt, in)) return rc;
+  const size_t B = bt->num_paths, N = bt->num_samples, C = bt->num_rows;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_rows_inputs din{};
+  tpamd_solution dsol{};
+  tpamd_check_outputs dout{};
+  const int32_t *d_ns = nullptr;
+  HostStage s;
+  s.up(&din.a, in->a, B * N * C);
+  s.up(&din.b, in->b, B * N * C);
+  s.up(&din.lower, in->lower, B * N * C);
+  s.up(&din.upper, in->upper, B * N * C);
+  s.up(&d_ns, num_samples_per_path, B);
+  stage_check_io(s, B, N, sol, out, &dsol, &dout);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  int rc = tpamd_check_rows_device(e, bt, &din, d_ns, &dsol, &dout, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_check_joint_paths_device(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
+                                   const int32_t *num_points_per_path, const tpamd_solution *sol,
+                                   const tpamd_check_outputs *out, void *hip_stream) {
+  if (!e || !bt || !in) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_io_args(sol, out)) return rc;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_joint_args(bt, in)) return rc;
+  TPAMD_ON_DEVICE(e);
+  hipLaunchKernelGGL(k_check_joint, dim3(bt->num_paths), dim3(kCheckThreads),
+                     check_joint_lds(bt->num_points, bt->num_dofs), (hipStream_t)hip_stream, bt->num_samples,
+                     bt->num_dofs, bt->num_points, bt->constraint_safety, in->knots, in->control_points,
+                     in->max_velocity, in->max_acceleration, in->path_start, in->delta, in->num_samples_per_path,
+                     num_points_per_path, check_solution(sol), check_outputs(out));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_check_joint_paths_host(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
+                                 const int32_t *num_points_per_path, const tpamd_solution *sol,
+                                 const tpamd_check_outputs *out) {
+  if (!e || !bt || !in) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_io_args(sol, out)) return rc;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (bt->num_dofs < 1 || bt->num_samples < 1 || bt->num_points < 1) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_joint_args(bt, in)) return rc;
+  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_joint_inputs din{};
+  tpamd_solution dsol{};
+  tpamd_check_outputs dout{};
+  const int32_t *d_np = nullptr;
+  HostStage s;
+  s.up(&din.knots, in->knots, B * (P + 3));
+  s.up(&din.control_points, in->control_points, B * P * D);
+  s.up(&din.max_velocity, in->max_velocity, B * D);
+  s.up(&din.max_acceleration, in->max_acceleration, B * D);
+  s.up(&din.path_start, in->path_start, B);
+  s.up(&din.delta, in->delta, B);
+  s.up(&din.num_samples_per_path, in->num_samples_per_path, B);
+  s.up(&d_np, num_points_per_path, B);
+  stage_check_io(s, B, N, sol, out, &dsol, &dout);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  int rc = tpamd_check_joint_paths_device(e, bt, &din, d_np, &dsol, &dout, st);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_check_cartesian_paths_device(tpamd_engine *e, const tpamd_cartesian_batch *bt,
+                                       const tpamd_cartesian_inputs *in, const int32_t *num_samples_per_path,
+                                       const int32_t *first_row, const tpamd_solution *sol,
+                                       const tpamd_check_outputs *out, void *hip_stream) {
+  if (!e || !bt || !in) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_io_args(sol, out)) return rc;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_cartesian_args(bt, in)) return rc;
+  TPAMD_ON_DEVICE(e);
+  hipLaunchKernelGGL(k_check_cartesian, dim3(bt->num_paths), dim3(kCheckThreads), 0, (hipStream_t)hip_stream,
+                     bt->num_samples, bt->num_dofs, bt->constraint_safety, in->ik_positions, in->jacobians,
+                     in->max_velocity, in->max_acceleration, in->max_translational_velocity,
+                     in->max_rotational_velocity, in->delta, num_samples_per_path, first_row, check_solution(sol),
+                     check_outputs(out));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int tpamd_check_cartesian_paths_host(tpamd_engine *e, const tpamd_cartesian_batch *bt,
+                                     const tpamd_cartesian_inputs *in, const int32_t *num_samples_per_path,
+                                     const int32_t *first_row, int64_t num_rows, const tpamd_solution *sol,
+                                     const tpamd_check_outputs *out) {
+  if (!e || !bt || !in) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_io_args(sol, out)) return rc;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = check_cartesian_args(bt, in)) return rc;
+  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
+  if (first_row && (num_rows < 1 || num_rows >= ((int64_t)1 << 31))) return TPAMD_E_INVALID_ARGUMENT;
+  const size_t rows = first_row ? (size_t)num_rows : B * N;
+  // the rows of a path with a usable count must lie inside what is staged
+  if (first_row)
+    for (size_t b = 0; b < B; b++) {
+      const int64_t n = num_samples_per_path ? num_samples_per_path[b] : (int64_t)N;
+      if (n < 2 || n > (int64_t)N) continue;
+      if (first_row[b] < 0 || (int64_t)first_row[b] + n > num_rows) return TPAMD_E_INVALID_ARGUMENT;
+    }
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_cartesian_inputs din{};
+  tpamd_solution dsol{};
+  tpamd_check_outputs dout{};
+  const int32_t *d_ns = nullptr, *d_first = nullptr;
+  HostStage s;
+  s.up(&din.ik_positions, in->ik_positions, rows * D);
+  s.up(&din.jacobians, in->jacobians, rows * 6 * D);
+  s.up(&din.max_velocity, in->max_velocity, B * D);
+  s.up(&din.max_acceleration, in->max_acceleration, B * D);
+  s.up(&din.max_translational_velocity, in->max_translational_velocity, B);
+  s.up(&din.max_rotational_velocity, in->max_rotational_velocity, B);
+  s.up(&din.delta, in->delta, B);
+  s.up(&d_ns, num_samples_per_path, B);
+  s.up(&d_first, first_row, B);
+  stage_check_io(s, B, N, sol, out, &dsol, &dout);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  int rc = tpamd_check_cartesian_paths_device(e, bt, &din, d_ns, d_first, &dsol, &dout, st);
   return rc ? rc : s.download(st);
 }
 

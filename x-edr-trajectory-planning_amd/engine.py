@@ -17,7 +17,8 @@ _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # 
 _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
             "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
-            "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip", "tpamd_joint_fit.h", "tpamd_joint_fit.hip"]
+            "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip", "tpamd_joint_fit.h", "tpamd_joint_fit.hip",
+            "tpamd_check.h"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -150,6 +151,17 @@ class _WaypointFitOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("num_points", "path_end", "delta_used", "knots", "control_points")]
 
 
+class _Solution(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("sd2", "sd", "sdd", "status")]
+
+
+_CHECK_OUTPUT_KEYS = ("violations", "worst_excess", "worst_sample", "worst_row", "first_sample")
+
+
+class _CheckOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _CHECK_OUTPUT_KEYS]
+
+
 class _RowsBatch(C.Structure):
     _fields_ = [("num_paths", C.c_int32), ("num_samples", C.c_int32), ("num_rows", C.c_int32),
                 ("max_solver_loops", C.c_int32)]
@@ -248,6 +260,9 @@ ABI_SYMBOLS = [
     "tpamd_optimize_rows_ragged_device", "tpamd_optimize_rows_ragged_host",
     "tpamd_time_cartesian_paths_ragged_device", "tpamd_time_cartesian_paths_ragged_host",
     "tpamd_sample_pose_splines_device", "tpamd_sample_pose_splines_host",
+    "tpamd_check_rows_device", "tpamd_check_rows_host",
+    "tpamd_check_joint_paths_device", "tpamd_check_joint_paths_host",
+    "tpamd_check_cartesian_paths_device", "tpamd_check_cartesian_paths_host",
     "tpamd_plan_joint_windows_host",
     "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
     "tpamd_planner_set_reset", "tpamd_planner_set_plan", "tpamd_planner_set_download_trajectory",
@@ -356,6 +371,22 @@ def load_library():
     L.tpamd_time_cartesian_paths_host.argtypes = [vp, C.POINTER(_CartesianBatch),
                                                   C.POINTER(_CartesianInputs),
                                                   C.POINTER(_PathOutputs)]
+    sol, cko = C.POINTER(_Solution), C.POINTER(_CheckOutputs)
+    L.tpamd_check_rows_device.restype = i
+    L.tpamd_check_rows_device.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp, sol, cko, vp]
+    L.tpamd_check_rows_host.restype = i
+    L.tpamd_check_rows_host.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp, sol, cko]
+    L.tpamd_check_joint_paths_device.restype = i
+    L.tpamd_check_joint_paths_device.argtypes = [vp, C.POINTER(_JointBatch), C.POINTER(_JointInputs), vp, sol, cko,
+                                                 vp]
+    L.tpamd_check_joint_paths_host.restype = i
+    L.tpamd_check_joint_paths_host.argtypes = [vp, C.POINTER(_JointBatch), C.POINTER(_JointInputs), vp, sol, cko]
+    L.tpamd_check_cartesian_paths_device.restype = i
+    L.tpamd_check_cartesian_paths_device.argtypes = [vp, C.POINTER(_CartesianBatch), C.POINTER(_CartesianInputs),
+                                                     vp, vp, sol, cko, vp]
+    L.tpamd_check_cartesian_paths_host.restype = i
+    L.tpamd_check_cartesian_paths_host.argtypes = [vp, C.POINTER(_CartesianBatch), C.POINTER(_CartesianInputs),
+                                                   vp, vp, C.c_int64, sol, cko]
     L.tpamd_optimize_rows_ragged_device.restype = i
     L.tpamd_optimize_rows_ragged_device.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp,
                                                     C.POINTER(_PathOutputs), vp]
@@ -952,6 +983,125 @@ class Engine:
             _check(self._lib.tpamd_time_waypoint_paths_device(self._h, C.byref(bt), C.byref(wi), C.byref(po),
                                                               C.byref(fo), _stream_ptr(stream)),
                    "tpamd_time_waypoint_paths_device")
+        return out
+
+    # ------------------------------------------- checking solutions against their rows
+    def _check_io(self, solution, outputs, B, like, host):
+        """The tpamd_solution / tpamd_check_outputs of one check call and the dict it returns: the
+        arrays of `outputs` where it has them, new ones (on the device of `like`, or numpy arrays
+        with host=True) otherwise."""
+        out = dict(outputs) if outputs else {}
+        for k in _CHECK_OUTPUT_KEYS:
+            if k in out:
+                continue
+            real = k == "worst_excess"
+            if host:
+                out[k] = np.zeros(B, dtype=np.float64 if real else np.int32)
+            else:
+                import torch
+                out[k] = torch.zeros(B, dtype=torch.float64 if real else torch.int32, device=like.device)
+        sol = _Solution(*[_ptr(solution.get(k)) for k in ("sd2", "sd", "sdd", "status")])
+        cko = _CheckOutputs(*[_ptr(out.get(k)) for k in _CHECK_OUTPUT_KEYS])
+        return sol, cko, out
+
+    def check_rows(self, inputs, solution, outputs=None, num_samples_per_path=None, stream=None, host=False):
+        """SolutionSatisfiesConstraints for a rows batch (tpamd_check_rows_*). inputs: the dict
+        optimize_rows took (a, b, lower, upper [B][N][C] are read); solution: the outputs dict of the
+        solve (sd2 or sd, sdd [B][N], status [B] or absent). Returns a dict with violations,
+        worst_sample, worst_row, first_sample [B] int32 and worst_excess [B]: the arrays of `outputs`
+        where it has them (an entry that is None is not computed), new ones otherwise. -1 violations:
+        the path was not checked (status not ok, or a sample count the solve refuses)."""
+        a = inputs["a"]
+        B, N, Cn = a.shape
+        bt = _RowsBatch(B, N, Cn, 0)
+        ri = _RowsInputs(*[_ptr(inputs.get(k)) for k in (
+            "a", "b", "lower", "upper", "s_start", "s_end", "sd_start", "sdd_start", "time_start")])
+        ns = None if num_samples_per_path is None else _int32_array(num_samples_per_path, B, "num_samples_per_path")
+        sol, cko, out = self._check_io(solution, outputs, B, a, host)
+        if host:
+            _check(self._lib.tpamd_check_rows_host(self._h, C.byref(bt), C.byref(ri), _ptr(ns), C.byref(sol),
+                                                   C.byref(cko)), "tpamd_check_rows_host")
+        else:
+            _check(self._lib.tpamd_check_rows_device(self._h, C.byref(bt), C.byref(ri), _ptr(ns), C.byref(sol),
+                                                     C.byref(cko), _stream_ptr(stream)), "tpamd_check_rows_device")
+            self._check_keepalive = (ns,)
+        return out
+
+    def check_joint_paths(self, inputs, solution, num_samples, safety=0.8, num_points_per_path=None, outputs=None,
+                          stream=None, host=False):
+        """The same for a joint batch (tpamd_check_joint_paths_*): inputs and num_samples as
+        time_joint_paths took them, ragged through inputs["num_samples_per_path"]. With
+        num_points_per_path [B] int32 the knots [B][S + 3] and control_points [B][S][D] are slots of
+        which path k uses its first num_points_per_path[k] entries (what time_waypoint_paths
+        returns; see check_waypoint_paths)."""
+        cp = inputs["control_points"]
+        B, P, D = cp.shape
+        bt = _JointBatch(B, D, int(num_samples), P, 0, 0, float(safety))
+        ji = _JointInputs(*[_ptr(inputs.get(k)) for k in (
+            "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
+            "sd_start", "sdd_start", "time_start", "num_samples_per_path")])
+        npp = None if num_points_per_path is None else _int32_array(num_points_per_path, B, "num_points_per_path")
+        sol, cko, out = self._check_io(solution, outputs, B, cp, host)
+        if host:
+            _check(self._lib.tpamd_check_joint_paths_host(self._h, C.byref(bt), C.byref(ji), _ptr(npp),
+                                                          C.byref(sol), C.byref(cko)),
+                   "tpamd_check_joint_paths_host")
+        else:
+            _check(self._lib.tpamd_check_joint_paths_device(self._h, C.byref(bt), C.byref(ji), _ptr(npp),
+                                                            C.byref(sol), C.byref(cko), _stream_ptr(stream)),
+                   "tpamd_check_joint_paths_device")
+            self._check_keepalive = (npp,)
+        return out
+
+    def check_waypoint_paths(self, got, max_velocity, max_acceleration, num_samples, safety=0.8,
+                             num_samples_per_path=None, outputs=None, stream=None, host=False):
+        """The same for a waypoint batch, from what time_waypoint_paths returned (`got`, which must
+        hold knots and control_points: pass them in its `outputs`): the slot splines with num_points,
+        delta_used as delta, path_start 0, and got's sd2 (or sd), sdd and status as the solution.
+        A path without waypoints is not checked."""
+        for k in ("knots", "control_points", "num_points", "delta_used"):
+            if got.get(k) is None:
+                raise TpamdError("check_waypoint_paths needs got[%r] (ask time_waypoint_paths for it)" % k)
+        dl = got["delta_used"]
+        zero = np.zeros_like(dl) if isinstance(dl, np.ndarray) else dl.new_zeros(dl.shape)
+        inputs = {"knots": got["knots"], "control_points": got["control_points"], "max_velocity": max_velocity,
+                  "max_acceleration": max_acceleration, "path_start": zero, "delta": dl,
+                  "num_samples_per_path": num_samples_per_path}
+        out = self.check_joint_paths(inputs, got, num_samples, safety=safety, num_points_per_path=got["num_points"],
+                                     outputs=outputs, stream=stream, host=host)
+        if not host:
+            self._check_keepalive += (zero,)
+        return out
+
+    def check_cartesian_paths(self, inputs, solution, safety=0.8, num_samples_per_path=None, first_row=None,
+                              outputs=None, stream=None, host=False):
+        """The same for a Cartesian batch (tpamd_check_cartesian_paths_*): inputs, num_samples_per_path
+        and first_row as time_cartesian_paths took them. With first_row the inputs are packed row
+        tables, and B and the stride N are those of solution["sdd"] [B][N]."""
+        ik = inputs["ik_positions"]
+        if first_row is None:
+            B, N, D = ik.shape
+        else:
+            if len(ik.shape) != 2:
+                raise TpamdError("packed inputs: ik_positions must be [rows][D]")
+            rows, D = ik.shape
+            B, N = solution["sdd"].shape
+            if inputs["jacobians"].shape[0] != rows:
+                raise TpamdError("packed inputs: jacobians must have one [6][D] block per row")
+        ns = None if num_samples_per_path is None else _int32_array(num_samples_per_path, B, "num_samples_per_path")
+        fr = None if first_row is None else _int32_array(first_row, B, "first_row")
+        bt = _CartesianBatch(B, D, N, 0, float(safety))
+        ci = _CartesianInputs(*[_ptr(inputs.get(k)) for k in _CARTESIAN_INPUT_KEYS])
+        sol, cko, out = self._check_io(solution, outputs, B, ik, host)
+        if host:
+            _check(self._lib.tpamd_check_cartesian_paths_host(
+                self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr), int(ik.shape[0]) if fr is not None else 0,
+                C.byref(sol), C.byref(cko)), "tpamd_check_cartesian_paths_host")
+        else:
+            _check(self._lib.tpamd_check_cartesian_paths_device(
+                self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr), C.byref(sol), C.byref(cko),
+                _stream_ptr(stream)), "tpamd_check_cartesian_paths_device")
+            self._check_keepalive = (ns, fr)
         return out
 
     # ------------------------------------------------------------ path_tools

@@ -58,6 +58,7 @@ Status BatchCartesianTiming::ComputeTimingProfiles(double time_start_sec, BatchT
   r->time.resize(r->sample_offset[Bt]); r->s.resize(r->sample_offset[Bt]);
   r->sd.resize(r->sample_offset[Bt]); r->sdd.resize(r->sample_offset[Bt]);
   r->q.resize(r->joint_offset[Bt]); r->qd.resize(r->joint_offset[Bt]); r->qdd.resize(r->joint_offset[Bt]);
+  PrepareCheckResult(check_solutions_, Bt, r);
   const std::vector<int> devices = devices_.empty() ? std::vector<int>{::tpamd::default_device()} : devices_;
   const int nd = (int)devices.size();
   std::vector<int32_t> begin(nd + 1);
@@ -125,16 +126,26 @@ Status BatchCartesianTiming::ComputeBlock(int device, size_t lo, size_t hi, doub
     }
     std::vector<double> time(B * N), s(B * N), sd(B * N), sdd(B * N), qd(B * N * D), qdd(B * N * D);
     std::vector<int32_t> status(B, -1), lei(B, 0);
+    std::vector<double> sd2(check_solutions_ ? B * N : 0);
     tpamd_cartesian_batch batch{(int)B, (int)D, (int)N, 0, safety[ids[0]]};
     tpamd_cartesian_inputs in{q.data(), J.data(), vmax.data(), amax.data(), vt.data(), vr.data(),
                               ps.data(), dl.data(), sd0.data(), sdd0.data(), t0.data()};
     tpamd_path_outputs out{time.data(), s.data(), sd.data(), sdd.data(), nullptr, qd.data(), qdd.data(),
-                           lei.data(), nullptr, status.data(), nullptr};
+                           lei.data(), nullptr, status.data(), check_solutions_ ? sd2.data() : nullptr};
     {
       const int rc = tpamd_time_cartesian_paths_ragged_host(engine, &batch, &in, count.data(), first.data(),
                                                             (int64_t)rows, &out);
       ++*engine_calls;
       if (rc != 0) return InternalError(tpamd_error_string(rc));
+    }
+    if (check_solutions_) {
+      const tpamd_solution sol{sd2.data(), nullptr, sdd.data(), status.data()};
+      CheckRecords rec(B);
+      const tpamd_check_outputs cko = rec.outputs();
+      const int rc = tpamd_check_cartesian_paths_host(engine, &batch, &in, count.data(), first.data(), (int64_t)rows,
+                                                      &sol, &cko);
+      if (rc != 0) return InternalError(tpamd_error_string(rc));
+      rec.scatter(ids, r);
     }
     for (size_t g = 0; g < B; g++) {
       const size_t b = ids[g], n = (size_t)count[g];

@@ -70,7 +70,13 @@ class BatchCartesianTiming {
   // Results in the packed layout of BatchTimingResult; q holds the IK positions.
   Status ComputeTimingProfiles(double time_start_sec, BatchTimingResult *result);
   // Engine calls the last ComputeTimingProfiles made, over all devices: its number of buckets.
+  // (the check calls of CheckSolutions are not counted)
   int EngineCallsOfLastCompute() const { return engine_calls_; }
+  // On: every bucket's solve is followed by one check of its solutions against the bucket's constraint
+  // rows on the device (tpamd_check_cartesian_paths_host, the same packed rows; the solve is asked for
+  // sd2), and the result carries violations / worst_sample / worst_row / worst_excess. Off (default):
+  // the engine calls and the result are what they are without this option.
+  void CheckSolutions(bool on = true) { check_solutions_ = on; }
 
  private:
   Status ComputeBlock(int device, size_t lo, size_t hi, double time_start_sec, BatchTimingResult *r,
@@ -78,6 +84,7 @@ class BatchCartesianTiming {
   std::vector<CartesianPathSamples> paths_;
   std::vector<int> devices_;
   int engine_calls_ = 0;
+  bool check_solutions_ = false;
 };
 
 }  // namespace trajectory_planning

@@ -24,6 +24,24 @@ Status BatchPathTiming::SetPaths(const std::vector<std::shared_ptr<TimeableJoint
   return OkStatus();
 }
 
+void PrepareCheckResult(bool on, size_t num_paths, BatchTimingResult *r) {
+  r->violations.clear(); r->worst_sample.clear(); r->worst_row.clear(); r->worst_excess.clear();
+  if (!on) return;
+  r->violations.assign(num_paths, -1); r->worst_sample.assign(num_paths, -1); r->worst_row.assign(num_paths, -1);
+  r->worst_excess.assign(num_paths, std::numeric_limits<double>::quiet_NaN());
+}
+
+tpamd_check_outputs CheckRecords::outputs() {
+  return tpamd_check_outputs{violations.data(), worst_excess.data(), worst_sample.data(), worst_row.data(), nullptr};
+}
+
+void CheckRecords::scatter(const std::vector<size_t> &ids, BatchTimingResult *r) const {
+  for (size_t i = 0; i < ids.size(); i++) {
+    r->violations[ids[i]] = violations[i]; r->worst_sample[ids[i]] = worst_sample[i];
+    r->worst_row[ids[i]] = worst_row[i]; r->worst_excess[ids[i]] = worst_excess[i];
+  }
+}
+
 namespace {
 struct GroupKey {
   size_t dofs, points, bucket;
@@ -42,6 +60,7 @@ struct GroupArrays {
   std::vector<int32_t> ns;
   std::vector<double> time, s, sd, sdd, q, qd, qdd;
   std::vector<int32_t> status, lei;
+  std::vector<double> sd2;   // CheckSolutions only
 };
 }  // namespace
 
@@ -77,6 +96,8 @@ Status BatchPathTiming::ComputeTimingProfiles(double time_start_sec, BatchTiming
   r->time.resize(r->sample_offset[Bt]); r->s.resize(r->sample_offset[Bt]);
   r->sd.resize(r->sample_offset[Bt]); r->sdd.resize(r->sample_offset[Bt]);
   r->q.resize(r->joint_offset[Bt]); r->qd.resize(r->joint_offset[Bt]); r->qdd.resize(r->joint_offset[Bt]);
+
+  PrepareCheckResult(check_solutions_, Bt, r);
 
   const std::vector<int> devices = devices_.empty() ? std::vector<int>{::tpamd::default_device()} : devices_;
   const int nd = (int)devices.size();
@@ -153,6 +174,7 @@ Status BatchPathTiming::ComputeBlock(int device, size_t lo, size_t hi, double ti
     g.time.resize(B * N); g.s.resize(B * N); g.sd.resize(B * N); g.sdd.resize(B * N);
     g.q.resize(B * N * D); g.qd.resize(B * N * D); g.qdd.resize(B * N * D);
     g.status.assign(B, -1); g.lei.assign(B, 0);
+    if (check_solutions_) g.sd2.resize(B * N);
   }
   // all groups of this device in ONE call: they run side by side on the engine's lanes
   std::vector<tpamd_joint_batch> batches;
@@ -164,12 +186,23 @@ Status BatchPathTiming::ComputeBlock(int device, size_t lo, size_t hi, double ti
                                      g.dl.data(), g.sd0.data(), g.sdd0.data(), g.t0.data(),
                                      g.ragged ? g.ns.data() : nullptr});
     outs.push_back(tpamd_path_outputs{g.time.data(), g.s.data(), g.sd.data(), g.sdd.data(), g.q.data(),
-                                      g.qd.data(), g.qdd.data(), g.lei.data(), nullptr, g.status.data(), nullptr});
+                                      g.qd.data(), g.qdd.data(), g.lei.data(), nullptr, g.status.data(),
+                                      check_solutions_ ? g.sd2.data() : nullptr});
   }
   {
     const int rc = tpamd_time_joint_groups_host(engine, (int)groups.size(), batches.data(), ins.data(), outs.data());
     if (rc != 0) return InternalError(tpamd_error_string(rc));
   }
+  if (check_solutions_)
+    for (size_t k = 0; k < groups.size(); k++) {
+      const GroupArrays &g = groups[k];
+      const tpamd_solution sol{g.sd2.data(), nullptr, g.sdd.data(), g.status.data()};
+      CheckRecords rec(g.B);
+      const tpamd_check_outputs cko = rec.outputs();
+      const int rc = tpamd_check_joint_paths_host(engine, &batches[k], &ins[k], nullptr, &sol, &cko);
+      if (rc != 0) return InternalError(tpamd_error_string(rc));
+      rec.scatter(g.ids, r);
+    }
   for (const GroupArrays &g : groups) {     // padded group layout -> packed result
     const size_t N = g.N, D = g.D;
     for (size_t i = 0; i < g.B; i++) {

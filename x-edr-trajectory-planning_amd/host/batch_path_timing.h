@@ -9,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "../../include/tpamd.h"
 #include "timeable_path_joint_spline.h"
 
 namespace trajectory_planning {
@@ -25,6 +26,23 @@ struct BatchTimingResult {
   std::vector<size_t> sample_offset, joint_offset;        // [B+1]
   std::vector<double> time, s, sd, sdd;
   std::vector<double> q, qd, qdd;
+  // CheckSolutions(true) only (empty otherwise): per path what tpamd_check_*_host reports --
+  // TimeOptimalPathProfile::SolutionSatisfiesConstraints (time_optimal_path_timing.cc:492-518) as a count of
+  // violated rows (-1: not checked, the path has no solution), the row with the largest excess over its
+  // bound and that excess. status == 0 does NOT imply violations == 0.
+  std::vector<int32_t> violations, worst_sample, worst_row;  // [B]
+  std::vector<double> worst_excess;                          // [B]
+};
+
+// (shared by the three batch classes) the check result of a batch, sized or emptied; the records of one
+// group's check call and their way into the packed result
+void PrepareCheckResult(bool on, size_t num_paths, BatchTimingResult *result);
+struct CheckRecords {
+  explicit CheckRecords(size_t n) : violations(n, -1), worst_sample(n, -1), worst_row(n, -1), worst_excess(n, 0.0) {}
+  tpamd_check_outputs outputs();
+  void scatter(const std::vector<size_t> &ids, BatchTimingResult *result) const;
+  std::vector<int32_t> violations, worst_sample, worst_row;
+  std::vector<double> worst_excess;
 };
 
 class BatchPathTiming {
@@ -46,12 +64,18 @@ class BatchPathTiming {
   void SetSampleBucket(int samples) { sample_bucket_ = samples > 0 ? samples : 0; }
   // Times every path starting at path parameter 0 and time `time_start_sec`.
   Status ComputeTimingProfiles(double time_start_sec, BatchTimingResult *result);
+  // On: every engine solve of a group is followed by one check of its solutions against the group's
+  // constraint rows on the device (tpamd_check_joint_paths_host; the solve is asked for sd2), and the
+  // result carries violations / worst_sample / worst_row / worst_excess. Off (default): the engine calls
+  // and the result are what they are without this option.
+  void CheckSolutions(bool on = true) { check_solutions_ = on; }
 
  private:
   Status ComputeBlock(int device, size_t lo, size_t hi, double time_start_sec, BatchTimingResult *r) const;
   std::vector<std::shared_ptr<TimeableJointSplinePath>> paths_;
   std::vector<int> devices_;
   int sample_bucket_ = 0;
+  bool check_solutions_ = false;
 };
 
 }  // namespace trajectory_planning

@@ -51,6 +51,7 @@ Status BatchWaypointTiming::ComputeTimingProfiles(double time_start_sec, BatchTi
   r->time.resize(r->sample_offset[Bt]); r->s.resize(r->sample_offset[Bt]);
   r->sd.resize(r->sample_offset[Bt]); r->sdd.resize(r->sample_offset[Bt]);
   r->q.resize(r->joint_offset[Bt]); r->qd.resize(r->joint_offset[Bt]); r->qdd.resize(r->joint_offset[Bt]);
+  PrepareCheckResult(check_solutions_, Bt, r);
   num_points_.assign(Bt, 0); path_end_.assign(Bt, 0.0); delta_used_.assign(Bt, 0.0);
   engine_calls_ = 0;
 
@@ -81,16 +82,34 @@ Status BatchWaypointTiming::ComputeTimingProfiles(double time_start_sec, BatchTi
       std::copy(p.amax.begin(), p.amax.end(), amax.begin() + i * D);
     }
     std::vector<double> time(B * N), s(B * N), sd(B * N), sdd(B * N), q(B * N * D), qd(B * N * D), qdd(B * N * D);
+    // CheckSolutions: the fitted splines in their slots of S control points, and sd2
+    size_t S = 4;
+    for (size_t b : ids) S = std::max(S, paths_[b].W <= 1 ? (size_t)4 : 3 * paths_[b].W - 2);
+    std::vector<double> sd2(check_solutions_ ? B * N : 0), knots(check_solutions_ ? B * (S + 3) : 0),
+        cps(check_solutions_ ? B * S * D : 0);
     const tpamd_waypoint_batch bt{(int32_t)B, (int32_t)D, (int32_t)N, 0, kv.first.second};
     const tpamd_waypoint_inputs in{offsets.data(), wps.data(), rounding.data(), vmax.data(), amax.data(),
                                    ragged ? ns.data() : nullptr, cover_whole_path_ ? nullptr : delta.data(),
                                    nullptr, t0.data()};
     const tpamd_path_outputs out{time.data(), s.data(), sd.data(), sdd.data(), q.data(), qd.data(), qdd.data(),
-                                 lei.data(), nullptr, status.data(), nullptr};
-    const tpamd_waypoint_fit_outputs fit{np.data(), end.data(), used.data(), nullptr, nullptr};
+                                 lei.data(), nullptr, status.data(), check_solutions_ ? sd2.data() : nullptr};
+    const tpamd_waypoint_fit_outputs fit{np.data(), end.data(), used.data(), check_solutions_ ? knots.data() : nullptr,
+                                         check_solutions_ ? cps.data() : nullptr};
     const int rc = tpamd_time_waypoint_paths_host(engine, &bt, &in, &out, &fit);
     engine_calls_++;
     if (rc != 0) return InternalError(tpamd_error_string(rc));
+    if (check_solutions_) {
+      const std::vector<double> zero(B, 0.0);
+      const tpamd_joint_batch jb{(int32_t)B, (int32_t)D, (int32_t)N, (int32_t)S, 0, 0, kv.first.second};
+      const tpamd_joint_inputs ji{knots.data(), cps.data(), vmax.data(), amax.data(), zero.data(), used.data(),
+                                  nullptr, nullptr, nullptr, ragged ? ns.data() : nullptr};
+      const tpamd_solution sol{sd2.data(), nullptr, sdd.data(), status.data()};
+      CheckRecords rec(B);
+      const tpamd_check_outputs cko = rec.outputs();
+      const int crc = tpamd_check_joint_paths_host(engine, &jb, &ji, np.data(), &sol, &cko);
+      if (crc != 0) return InternalError(tpamd_error_string(crc));
+      rec.scatter(ids, r);
+    }
     for (size_t i = 0; i < B; i++) {     // padded group layout -> packed result
       const size_t b = ids[i], n = (size_t)ns[i];
       r->status[b] = status[i];

@@ -37,7 +37,12 @@ class BatchWaypointTiming {
   const std::vector<int32_t> &num_control_points() const { return num_points_; }
   const std::vector<double> &path_end() const { return path_end_; }
   const std::vector<double> &delta_used() const { return delta_used_; }
-  int EngineCallsOfLastCompute() const { return engine_calls_; }
+  int EngineCallsOfLastCompute() const { return engine_calls_; }   // (check calls are not counted)
+  // On: every group's solve is followed by one check of its solutions against the group's constraint rows
+  // on the device (tpamd_check_joint_paths_host on the fitted splines the solve returns; the solve is asked
+  // for them and for sd2), and the result carries violations / worst_sample / worst_row / worst_excess.
+  // Off (default): the engine calls and the result are what they are without this option.
+  void CheckSolutions(bool on = true) { check_solutions_ = on; }
 
  private:
   struct Path {
@@ -48,6 +53,7 @@ class BatchWaypointTiming {
   };
   std::vector<Path> paths_;
   bool cover_whole_path_ = false;
+  bool check_solutions_ = false;
   std::vector<int32_t> num_points_;
   std::vector<double> path_end_, delta_used_;
   int engine_calls_ = 0;
