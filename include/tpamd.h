@@ -1565,6 +1565,61 @@ int tpamd_check_cartesian_paths_host(tpamd_engine *engine, const tpamd_cartesian
                                      const tpamd_check_outputs *out);
 
 /* ------------------------------------------------------------------------
+ * Checking every window a planner set plans: the same question, asked inside
+ * tpamd_planner_set_plan / _plan_streaming / _plan_resume / _plan_device, where the windows, their
+ * path_start and (Cartesian sets) their table slots exist only until the next window iteration.
+ * Off by default; with it off a Plan call enqueues, allocates and writes exactly what it does
+ * without this feature. With it on, every window iteration runs one more kernel directly behind the
+ * sweep (one workgroup per planner, no atomics, no synchronisation): the rows are those of the
+ * window's solve, formed by the same device functions (the joint form above on the planner's
+ * resident spline and limits from the window's path_start; the Cartesian form on the window's slots
+ * of the resident IK table), and the solution is the solver's sd2 and sdd. The set then owns a
+ * [B][N] sd2 buffer and B records (counted in tpamd_planner_set_device_bytes).
+ *
+ * A planner's window is checked if the planner solved a window in that iteration and the window's
+ * status is TPAMD_PATH_OK. A planner that is idle, only erased, waits for IK rows, was stopped by
+ * the start-velocity test or by a full history, or whose window failed, is not checked in that
+ * iteration and nothing is counted for it.
+ *
+ * The record covers the windows of the planner's last Plan call, numbered from 0 in solve order (the
+ * number of windows the planner had solved in the call before this one). plan, plan_streaming and
+ * plan_device start with empty records for every planner; plan_resume continues the records and the
+ * numbering of the streaming call it resumes. Across windows the counts add, the larger excess wins
+ * and, among equal excesses, the smaller (window, sample, row); the first violated (window, sample)
+ * in solve order is kept.
+ *
+ * `violations` counts whole windows -- what SolutionSatisfiesConstraints answers for each of them. The
+ * tail of a window that is not the last, behind the sample where the next window starts, is planned
+ * again by that next window, so only the last window is in the history as a whole: hence
+ * last_window_violations, and worst_window / worst_sample tell a violation in a replaced tail from
+ * one that is executed.
+ * ------------------------------------------------------------------------ */
+typedef struct tpamd_planner_check {     /* 48 bytes; over the windows the planner's last Plan call solved */
+  int32_t windows;                 /* windows checked; 0: none */
+  int32_t violations;              /* violated rows summed over them; -1: nothing checked */
+  int32_t last_window_violations;  /* of the last checked window alone; -1 */
+  int32_t worst_window, worst_sample, worst_row;   /* -1: no row with an excess */
+  int32_t first_window, first_sample;              /* -1: no violated row */
+  double worst_excess;             /* max(lower - v, v - upper) over all checked rows; NaN: none. Negative: margin */
+  double worst_parameter;          /* the window's s at worst_sample; NaN: none */
+} tpamd_planner_check;
+/* Switches checking on or off. Switching it on allocates the sd2 buffer and the records (kept when
+ * it is switched off again) and empties the records; synchronises. */
+int tpamd_planner_set_set_checking(tpamd_planner_set *set, int on);
+int tpamd_planner_set_checking(const tpamd_planner_set *set);     /* 1 on, 0 off or NULL */
+/* out[k] = the record of planner ids[k]; ids NULL: planners 0 .. count-1. With checking off every
+ * record is the one of "nothing checked": 0, -1, -1, -1, -1, -1, -1, -1, NaN, NaN. Call-level errors
+ * write nothing: a NULL set or out, count < 0 or > B (TPAMD_E_INVALID_ARGUMENT); the host entry also
+ * refuses an id outside the set or listed twice. The host entry takes host arrays and synchronises.
+ * The _device entry takes device arrays, enqueues one kernel on hip_stream, ordered like the device
+ * readouts (behind a tpamd_planner_set_plan_device enqueued before it, on the same or on another
+ * stream), and does not synchronise; an id outside the set yields "nothing checked". */
+int tpamd_planner_set_check_results(tpamd_planner_set *set, int count, const int32_t *ids,
+                                    tpamd_planner_check *out);
+int tpamd_planner_set_check_results_device(tpamd_planner_set *set, int count, const int32_t *ids,
+                                           tpamd_planner_check *out, void *hip_stream);
+
+/* ------------------------------------------------------------------------
  * Debug/inspection: copy the boundary curve of the LAST solve to host arrays
  * [B][N] (Boundary::sd2_max, sdd_max_for_sd2_max, sdd_min_for_sd2_max,
  * sd2_max_for_sdd0, type; time_optimal_path_timing.h:225-255) and the squared

@@ -1,0 +1,406 @@
+// GPU test of planner-set checking over many windows (run by tests/test_gpu_set_check_mirror.py):
+// PathTimingTrajectorySet::SetChecking / CheckResults / CheckResultsDevice against one host
+// PathTimingTrajectory per planner with SetCheckSolutions(true), whose rows come from the path's own
+// SamplePath / ConstraintSetup on the host. For sets of 24 planners at D = 1, 7, 16, N = 64, 200 and
+// both sampling methods, over a first Plan and three replans, with one planner without a path and
+// one whose first window is refused by the start-velocity test:
+//   * a set planned through Plan and a set planned through PlanDevice + CheckResultsDevice on one
+//     non-blocking stream (nothing synchronises between the two calls) hold, after every call, the
+//     records the mirror planners hold, bit for bit;
+//   * a twin set with checking off has bit-equal statuses, summaries, trajectories and paths, and
+//     its records are the one of "nothing checked";
+//   * a planner that only erased reports 0 / -1; call-level errors write nothing.
+// Cartesian sets, through PlanStreaming (plan_streaming, then append + plan_resume for the planners
+// that wait for IK rows between two windows): the records after every call equal the mirror planners',
+// which plan the same paths window by window -- so the numbering and the record continue over a
+// suspension -- and a streaming twin with checking off plans the same.
+// Non-vacuity is counted on the mirrors' side: planners with >= 3 windows and with violations.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../../include/tpamd.h"
+#include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory.h"
+#include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
+#include "../../x-edr-trajectory-planning_amd/host/timeable_path_cartesian_spline.h"
+#include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
+
+using namespace trajectory_planning;
+using tpamd::compat::AngleAxisd;
+using tpamd::compat::FromUnixNanos;
+using tpamd::compat::Matrix6Xd;
+using tpamd::compat::Pose3d;
+using tpamd::compat::Vector3d;
+using tpamd::compat::Milliseconds;
+using tpamd::compat::Nanoseconds;
+using tpamd::compat::StatusCode;
+using tpamd::compat::ToUnixNanos;
+using Method = PathTimingTrajectoryOptions::TimeSamplingMethod;
+
+static int g_fail = 0;
+#define CHECK(cond)                                                                          \
+  do {                                                                                       \
+    if (!(cond)) {                                                                           \
+      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
+      g_fail++;                                                                              \
+    }                                                                                        \
+  } while (0)
+#define HIP_OK(expr) CHECK((expr) == hipSuccess)
+
+static const int64_t kMs = 1000000;
+static unsigned long long g_seed = 1;
+static double Rnd() {
+  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
+  return (double)(g_seed >> 11) / 9007199254740992.0;
+}
+
+static bool SameBits(const std::vector<double> &a, const std::vector<double> &b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * 8) == 0);
+}
+static bool SameRecord(const tpamd_planner_check &a, const tpamd_planner_check &b) {
+  return std::memcmp(&a, &b, sizeof a) == 0;
+}
+static bool NothingChecked(const tpamd_planner_check &r) {
+  return r.windows == 0 && r.violations == -1 && r.last_window_violations == -1 && r.worst_window == -1 &&
+         r.worst_sample == -1 && r.worst_row == -1 && r.first_window == -1 && r.first_sample == -1 &&
+         r.worst_excess != r.worst_excess && r.worst_parameter != r.worst_parameter;
+}
+static void Print(const char *what, int b, const tpamd_planner_check &r) {
+  std::printf("    %s planner %d: windows %d violations %d last %d worst (%d, %d, %d) first (%d, %d) excess %a s %a\n", what,
+              b, r.windows, r.violations, r.last_window_violations, r.worst_window, r.worst_sample, r.worst_row,
+              r.first_window, r.first_sample, r.worst_excess, r.worst_parameter);
+}
+
+static bool SameTrajectories(const std::vector<PlannedTrajectory> &a, const std::vector<PlannedTrajectory> &b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); i++)
+    if (!SameBits(a[i].time, b[i].time) || !SameBits(a[i].path_parameter, b[i].path_parameter) ||
+        !SameBits(a[i].path_parameter_derivative, b[i].path_parameter_derivative) ||
+        !SameBits(a[i].second_path_parameter_derivative, b[i].second_path_parameter_derivative) ||
+        !SameBits(a[i].positions, b[i].positions) || !SameBits(a[i].velocities, b[i].velocities) ||
+        !SameBits(a[i].accelerations, b[i].accelerations))
+      return false;
+  return true;
+}
+
+struct Totals {
+  int compared = 0, three_windows = 0, violating = 0, erased_only = 0, refused = 0;
+};
+
+static void TestJoint(hipStream_t stream, int D, int N, Method method, Totals *totals) {
+  const bool skip = method == Method::kSkipSamplesCloserThanTimeStep;
+  const int B = 24, kNoPath = B - 1, kRefused = 5, max_windows = 5;
+  // a window spans about 1.2 in the path parameter: coarse enough for OK windows with violated rows,
+  // and the paths below are several windows long
+  const double delta = 1.2 / (N - 1), rounding = 0.2;
+  g_seed = 7000 + 13 * D + N + (skip ? 1 : 0);
+  PathTimingTrajectoryOptions opt;
+  opt.SetNumDofs(D).SetNumPathSamples(N).SetTimeStep(Milliseconds(skip ? 4 : 1)).SetTimeSamplingMethod(method)
+      .SetMaxPlanningLoops(max_windows - 1);
+  PathTimingTrajectorySet sync(opt, B, 8), async(opt, B, 8), off(opt, B, 8);
+  CHECK(sync.status().ok() && async.status().ok() && off.status().ok());
+  if (!sync.status().ok() || !async.status().ok() || !off.status().ok()) return;
+  std::vector<std::unique_ptr<PathTimingTrajectory>> mirrors(B);
+  std::vector<size_t> with_path, all(B);
+  std::vector<std::vector<VectorXd>> wps;
+  std::vector<VectorXd> vmax, amax, iv;
+  for (int b = 0; b < B; b++) {
+    all[b] = b;
+    mirrors[b] = std::make_unique<PathTimingTrajectory>(opt);
+    mirrors[b]->SetCheckSolutions(true);
+    if (b == kNoPath) continue;
+    std::vector<VectorXd> w;
+    VectorXd at(D), vm(D), am(D), v0(D);
+    for (int d = 0; d < D; d++) at[d] = -1.5 + 3.0 * Rnd();
+    const int W = b % 4 == 0 ? 2 : 5;                      // short paths: one or two windows, then only erased
+    for (int i = 0; i < W; i++) {
+      if (i) for (int d = 0; d < D; d++) at[d] += (b % 4 == 0 ? 0.4 : 2.5) * (2.0 * Rnd() - 1.0) / std::sqrt((double)D);
+      w.push_back(at);
+    }
+    for (int d = 0; d < D; d++) { vm[d] = 1.0 + Rnd(); am[d] = 2.0 + 2.0 * Rnd(); v0[d] = 0.0; }
+    // the refused planner: an initial velocity across the start tangent (D = 1: against it, which the
+    // projection clips to zero)
+    if (b == kRefused) {
+      if (D == 1) v0[0] = w[1][0] > w[0][0] ? -0.5 : 0.5;
+      else { v0[0] = -(w[1][1] - w[0][1]); v0[1] = w[1][0] - w[0][0]; const double n = std::hypot(v0[0], v0[1]); v0[0] *= 0.5 / n; v0[1] *= 0.5 / n; }
+    }
+    auto path = std::make_shared<TimeableJointSplinePath>(
+        JointPathOptions().set_num_dofs(D).set_num_path_samples(N).set_delta_parameter(delta).set_rounding(rounding));
+    CHECK(path->SetWaypoints({w.data(), w.size()}).ok());
+    CHECK(path->SetMaxJointVelocity({vm.data(), vm.size()}).ok());
+    CHECK(path->SetMaxJointAcceleration({am.data(), am.size()}).ok());
+    CHECK(path->SetInitialVelocity({v0.data(), v0.size()}).ok());
+    CHECK(mirrors[b]->SetPath(path).ok());
+    with_path.push_back(b);
+    wps.push_back(w); vmax.push_back(vm); amax.push_back(am); iv.push_back(v0);
+  }
+  for (PathTimingTrajectorySet *s : {&sync, &async, &off})
+    for (const auto &st : s->SetWaypointPaths(with_path, wps, vmax, amax, iv, rounding, delta)) CHECK(st.ok());
+  CHECK(sync.SetChecking(true).ok() && async.SetChecking(true).ok());
+  CHECK(sync.Checking() && async.Checking() && !off.Checking());
+  // the enqueued-only Plan cannot grow a buffer: room for every window and trajectory of this test
+  int h0 = 0, t0 = 0;
+  CHECK(async.GetCapacity(&h0, &t0).ok() && async.Reserve(std::max(h0, 16 * N), std::max(t0, 16384)).ok());
+  int64_t *d_time = nullptr;
+  tpamd_planner_check *d_records = nullptr;
+  HIP_OK(hipMalloc((void **)&d_time, 2 * B * 8));
+  HIP_OK(hipMalloc((void **)&d_records, B * sizeof(tpamd_planner_check)));
+  std::vector<bool> diverged(B, false);
+  int reported = 0;
+  for (int round = 0; round < 4; round++) {
+    const int64_t start = (2000 + 150 * round) * kMs;
+    // the first call plans far ahead (several windows); the replans a little further each
+    const int64_t horizon = round == 0 ? 3000 * kMs : 3100 * kMs;
+    std::vector<int64_t> sh(2 * B, start);
+    std::fill(sh.begin() + B, sh.end(), horizon);
+    HIP_OK(hipMemcpy(d_time, sh.data(), 2 * B * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_records, 0x5a, B * sizeof(tpamd_planner_check)));
+    HIP_OK(hipDeviceSynchronize());
+    // enqueued back to back on one stream; the first synchronisation is FinishPlanDevice's
+    CHECK(async.PlanDevice(d_time, d_time + B, max_windows, stream).ok());
+    CHECK(async.CheckResultsDevice(B, nullptr, d_records, stream).ok());
+    const auto sa = async.FinishPlanDevice();
+    HIP_OK(hipStreamSynchronize(stream));
+    std::vector<tpamd_planner_check> from_device(B), ra, rs, ro;
+    HIP_OK(hipMemcpy(from_device.data(), d_records, B * sizeof(tpamd_planner_check), hipMemcpyDeviceToHost));
+    const auto ss = sync.Plan(FromUnixNanos(start), Nanoseconds(horizon));
+    const auto so = off.Plan(FromUnixNanos(start), Nanoseconds(horizon));
+    std::vector<PathTimingTrajectory *> batch;
+    for (int b = 0; b < B; b++) batch.push_back(mirrors[b].get());
+    const auto sm = PathTimingTrajectory::PlanBatch(batch, FromUnixNanos(start), Nanoseconds(horizon));
+    CHECK(async.CheckResults(all, &ra).ok() && sync.CheckResults(all, &rs).ok() && off.CheckResults(all, &ro).ok());
+    // checking changes no plan: the set with checking off, field by field
+    std::vector<PlannedTrajectory> ts, to, ta;
+    CHECK(sync.GetTrajectories(all, &ts).ok() && off.GetTrajectories(all, &to).ok() && async.GetTrajectories(all, &ta).ok());
+    CHECK(SameTrajectories(ts, to));
+    CHECK(SameTrajectories(ta, to));
+    for (int b = 0; b < B; b++) {
+      CHECK(ss[b].code() == so[b].code());
+      CHECK(sa[b].code() == so[b].code());
+      for (PathTimingTrajectorySet *s : {&sync, &async}) {
+        CHECK(s->GetNumTimeSamples(b) == off.GetNumTimeSamples(b) && s->WindowsOfLastPlan(b) == off.WindowsOfLastPlan(b) &&
+              ToUnixNanos(s->GetEndTime(b)) == ToUnixNanos(off.GetEndTime(b)) &&
+              ToUnixNanos(s->GetFinalDecelStart(b)) == ToUnixNanos(off.GetFinalDecelStart(b)) &&
+              s->IsTrajectoryAtEnd(b) == off.IsTrajectoryAtEnd(b));
+        std::vector<double> k1, c1, k2, c2;
+        CHECK(s->GetPath(b, &k1, &c1).ok() && off.GetPath(b, &k2, &c2).ok() && SameBits(k1, k2) && SameBits(c1, c2));
+      }
+      CHECK(NothingChecked(ro[b]));
+      CHECK(SameRecord(ra[b], from_device[b]) && SameRecord(ra[b], rs[b]));
+      if (b == kNoPath) CHECK(NothingChecked(rs[b]) && ss[b].code() == StatusCode::kFailedPrecondition);
+      if (diverged[b]) continue;
+      // the sets against the mirror planners
+      const tpamd_planner_check &m = mirrors[b]->GetCheckRecord();
+      CHECK(ss[b].code() == sm[b].code());
+      const bool same = SameRecord(rs[b], m);
+      CHECK(same);
+      if (!same && ++reported <= 6) {
+        std::printf("  D %d N %d %s round %d planner %d (status %d):\n", D, N, skip ? "skip" : "uniform", round, b,
+                    (int)ss[b].code());
+        Print("set   ", b, rs[b]);
+        Print("mirror", b, m);
+      }
+      totals->compared++;
+      if (ss[b].ok()) CHECK(rs[b].windows == sync.WindowsOfLastPlan(b));
+      totals->three_windows += m.windows >= 3;
+      totals->violating += m.violations > 0;
+      if (ss[b].ok() && sync.WindowsOfLastPlan(b) == 0 && sync.GetNumTimeSamples(b) > 0) {
+        CHECK(NothingChecked(rs[b]));                 // planned enough: only erased
+        totals->erased_only++;
+      }
+      if (b == kRefused && ss[b].code() == StatusCode::kInvalidArgument) {
+        CHECK(NothingChecked(rs[b]));                 // its window was not solved
+        totals->refused++;
+        // (a refused first window leaves the path sampled in the set, not in the mirror: DESIGN.md)
+        diverged[b] = true;
+      }
+    }
+  }
+  // call-level errors write nothing
+  {
+    std::vector<tpamd_planner_check> sentinel(B + 1), out;
+    std::memset(sentinel.data(), 0x77, sentinel.size() * sizeof(tpamd_planner_check));
+    out = sentinel;
+    tpamd_planner_set *ps = sync.native_handle();
+    const int32_t twice[2] = {3, 3}, outside[1] = {B};
+    CHECK(tpamd_planner_set_check_results(nullptr, 1, nullptr, out.data()) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results(ps, 1, nullptr, nullptr) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results(ps, -1, nullptr, out.data()) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results(ps, B + 1, nullptr, out.data()) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results(ps, 2, twice, out.data()) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results(ps, 1, outside, out.data()) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(std::memcmp(out.data(), sentinel.data(), sentinel.size() * sizeof(tpamd_planner_check)) == 0);
+    HIP_OK(hipMemset(d_records, 0x5a, B * sizeof(tpamd_planner_check)));
+    CHECK(tpamd_planner_set_check_results_device(nullptr, 1, nullptr, d_records, stream) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results_device(ps, 1, nullptr, nullptr, stream) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results_device(ps, -1, nullptr, d_records, stream) == TPAMD_E_INVALID_ARGUMENT);
+    CHECK(tpamd_planner_set_check_results_device(ps, B + 1, nullptr, d_records, stream) == TPAMD_E_INVALID_ARGUMENT);
+    HIP_OK(hipDeviceSynchronize());
+    std::vector<unsigned char> bytes(B * sizeof(tpamd_planner_check));
+    HIP_OK(hipMemcpy(bytes.data(), d_records, bytes.size(), hipMemcpyDeviceToHost));
+    CHECK(std::count(bytes.begin(), bytes.end(), (unsigned char)0x5a) == (long)bytes.size());
+    CHECK(tpamd_planner_set_set_checking(nullptr, 1) == TPAMD_E_INVALID_ARGUMENT && tpamd_planner_set_checking(nullptr) == 0);
+  }
+  HIP_OK(hipFree(d_time));
+  HIP_OK(hipFree(d_records));
+  std::printf("set check joint (D %d, N %d, %s)\n", D, N, skip ? "skip" : "uniform");
+}
+
+// ---- Cartesian sets: streaming Plan with suspensions (the paths of test_cartesian_stream_mirror_gpu.cc)
+static const int kCartesianDofs = 7, kCartesianSamples = 64;
+static Status SeededIk(const VectorXd &seed, const std::vector<Pose3d> &poses, const std::vector<VectorXd> &joints,
+                       std::vector<VectorXd> *result) {
+  result->clear();
+  for (size_t i = 0; i < poses.size(); i++) {
+    VectorXd q(kCartesianDofs);
+    for (int d = 0; d < kCartesianDofs; d++) q[d] = joints[i][d] + 1e-3 * std::sin(seed[d]);
+    result->push_back(q);
+  }
+  return tpamd::compat::OkStatus();
+}
+static Status FakeJacobian(const VectorXd &q, Matrix6Xd *J) {
+  for (int r = 0; r < 6; r++)
+    for (int d = 0; d < kCartesianDofs; d++) (*J)(r, d) = 0.2 * std::sin(q[d] * (r + 1.0) + 0.31 * d) + (r == d ? 1.0 : 0.0);
+  return tpamd::compat::OkStatus();
+}
+static Pose3d MakePose(double x, double y, double z, double ax, double ay, double az, double angle) {
+  AngleAxisd aa;
+  const double n = std::sqrt(ax * ax + ay * ay + az * az);
+  aa.axis = Vector3d(ax / n, ay / n, az / n);
+  aa.angle = angle;
+  return Pose3d(aa.toQuaternion(), Vector3d(x, y, z));
+}
+static std::shared_ptr<TimeableCartesianSplinePath> MakeCartesianPath(int shape, double frac) {
+  const int D = kCartesianDofs, N = kCartesianSamples;
+  std::vector<Pose3d> poses;
+  if (shape == 0)
+    poses = {MakePose(0.3, 0.0, 0.4, 0, 0, 1, 0.1), MakePose(0.5, 0.25, 0.6, 0, 1, 0, 0.7),
+             MakePose(0.2, 0.5, 0.3, 1, 0, 0, 0.4), MakePose(0.45, 0.1, 0.5, 0, 0, 1, 1.0)};
+  else if (shape == 1)
+    poses = {MakePose(0.1, 0.2, 0.3, 1, 1, 0, 0.3), MakePose(0.4, 0.2, 0.35, 0, 1, 1, 0.5), MakePose(0.4, 0.5, 0.6, 1, 0, 1, 0.2)};
+  else
+    poses = {MakePose(0.6, -0.1, 0.2, 0, 0, 1, 0.8), MakePose(0.3, 0.1, 0.4, 0, 1, 0, 0.2), MakePose(0.5, 0.4, 0.5, 1, 0, 0, 0.6),
+             MakePose(0.2, 0.3, 0.7, 0, 1, 1, 0.9), MakePose(0.1, 0.0, 0.4, 1, 1, 1, 0.3)};
+  std::vector<VectorXd> joints;
+  for (size_t i = 0; i < poses.size(); i++) {
+    VectorXd q(D);
+    for (int d = 0; d < 3; d++) q[d] = poses[i].translation()[d];
+    const AngleAxisd aa(poses[i].quaternion());
+    for (int d = 0; d < 3; d++) q[3 + d] = aa.axis[d] * aa.angle;
+    q[6] = 0.2 * (double)i - 0.3;
+    joints.push_back(q);
+  }
+  CartesianPathOptions probe_opt;
+  probe_opt.set_num_dofs(D).set_num_path_samples(N);
+  probe_opt.set_path_ik_func(SeededIk).set_jacobian_func(FakeJacobian);
+  TimeableCartesianSplinePath probe(probe_opt);
+  CHECK(probe.SetWaypoints({poses.data(), poses.size()}, {joints.data(), joints.size()}).ok());
+  const double delta = frac * probe.knots().back() / (N - 1);
+  CartesianPathOptions opt;
+  opt.set_num_dofs(D).set_num_path_samples(N).set_delta_parameter(delta);
+  opt.set_path_ik_func(SeededIk).set_jacobian_func(FakeJacobian);
+  auto path = std::make_shared<TimeableCartesianSplinePath>(opt);
+  const std::vector<double> vmax = {0.6, 0.5, 0.7, 1.0, 0.9, 1.1, 0.8}, amax = {1.5, 1.2, 1.8, 2.5, 2.0, 3.0, 2.2};
+  CHECK(path->SetMaxJointVelocity({vmax.data(), vmax.size()}).ok());
+  CHECK(path->SetMaxJointAcceleration({amax.data(), amax.size()}).ok());
+  CHECK(path->SetMaxCartesianVelocity(0.35 + 0.05 * shape, 0.9).ok());
+  CHECK(path->SetWaypoints({poses.data(), poses.size()}, {joints.data(), joints.size()}).ok());
+  return path;
+}
+
+static void TestCartesianStreaming(Method method, Totals *totals) {
+  const bool skip = method == Method::kSkipSamplesCloserThanTimeStep;
+  const int B = 6, D = kCartesianDofs, N = kCartesianSamples;
+  PathTimingTrajectoryOptions opt;
+  opt.SetNumDofs(D).SetNumPathSamples(N).SetTimeStep(Milliseconds(4)).SetTimeSamplingMethod(method);
+  PathTimingTrajectorySet set(opt, B, CartesianTableCapacity{(size_t)N}), off(opt, B, CartesianTableCapacity{(size_t)N});
+  CHECK(set.status().ok() && off.status().ok());
+  if (!set.status().ok() || !off.status().ok()) return;
+  std::vector<std::shared_ptr<TimeableCartesianSplinePath>> set_paths(B), off_paths(B), mirror_paths(B);
+  std::vector<std::unique_ptr<PathTimingTrajectory>> mirrors(B);
+  std::vector<size_t> all(B);
+  for (int b = 0; b < B; b++) {
+    all[b] = b;
+    const double frac = (b % 2) ? 0.25 : 0.4;
+    set_paths[b] = MakeCartesianPath(b / 2, frac);
+    off_paths[b] = MakeCartesianPath(b / 2, frac);
+    mirror_paths[b] = MakeCartesianPath(b / 2, frac);
+    mirrors[b] = std::make_unique<PathTimingTrajectory>(opt);
+    mirrors[b]->SetCheckSolutions(true);
+    CHECK(mirrors[b]->SetPath(mirror_paths[b]).ok());
+  }
+  CHECK(set.SetCartesianPaths(set_paths, /*streaming=*/true).ok() && off.SetCartesianPaths(off_paths, /*streaming=*/true).ok());
+  CHECK(set.SetChecking(true).ok());
+  std::vector<int64_t> start(B, 0);
+  int plans = 0, compared = 0, suspensions = 0, across = 0, reported = 0;
+  for (int step = 0; step < 300; step++) {
+    std::vector<Time> st(B);
+    for (int b = 0; b < B; b++) st[b] = FromUnixNanos(start[b]);
+    const std::vector<tpamd::compat::Duration> hz(B, Milliseconds(750));
+    const auto sd = set.PlanStreaming(st, hz);
+    const int suspended = set.SuspensionsOfLastPlan();
+    const auto so = off.PlanStreaming(st, hz);
+    suspensions += suspended;
+    plans++;
+    std::vector<tpamd_planner_check> rs, ro;
+    std::vector<PlannedTrajectory> ts, to;
+    CHECK(set.CheckResults(all, &rs).ok() && off.CheckResults(all, &ro).ok());
+    CHECK(set.GetTrajectories(all, &ts).ok() && off.GetTrajectories(all, &to).ok());
+    CHECK(SameTrajectories(ts, to));
+    bool all_done = true;
+    for (int b = 0; b < B; b++) {
+      const Status ms = mirrors[b]->Plan(st[b], Milliseconds(750));
+      CHECK(ms.ok() && sd[b].ok() && so[b].ok());
+      CHECK(NothingChecked(ro[b]));
+      const tpamd_planner_check &m = mirrors[b]->GetCheckRecord();
+      const bool same = SameRecord(rs[b], m);
+      CHECK(same);
+      if (!same && ++reported <= 6) {
+        std::printf("  Cartesian %s step %d planner %d:\n", skip ? "skip" : "uniform", step, b);
+        Print("set   ", b, rs[b]);
+        Print("mirror", b, m);
+      }
+      CHECK(rs[b].windows == set.WindowsOfLastPlan(b));
+      compared++;
+      totals->compared++;
+      totals->three_windows += m.windows >= 3;
+      totals->violating += m.violations > 0;
+      across += suspended > 0 && m.windows >= 2;       // (a planner that waited between two of its windows is among these)
+      if (!mirrors[b]->IsTrajectoryAtEnd()) {
+        start[b] = std::min<int64_t>(ToUnixNanos(mirrors[b]->GetEndTime()), start[b] + 200 * kMs);
+        all_done = false;
+      }
+    }
+    if (all_done) break;
+  }
+  for (int b = 0; b < B; b++) CHECK(mirrors[b]->IsTrajectoryAtEnd() && set.IsTrajectoryAtEnd(b));
+  CHECK(plans > 4 && suspensions >= B && across > 0);
+  std::printf("set check Cartesian streaming (%s): %d Plan calls, %d records compared, %d suspensions, %d records of several "
+              "windows in calls that were resumed\n", skip ? "skip" : "uniform", plans, compared, suspensions, across);
+}
+
+int main() {
+  hipStream_t stream = nullptr;
+  HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  Totals totals;
+  for (int D : {1, 7, 16})
+    for (int N : {64, 200})
+      for (Method m : {Method::kUniformlyInTime, Method::kSkipSamplesCloserThanTimeStep}) TestJoint(stream, D, N, m, &totals);
+  TestCartesianStreaming(Method::kUniformlyInTime, &totals);
+  TestCartesianStreaming(Method::kSkipSamplesCloserThanTimeStep, &totals);
+  std::printf("set check totals: %d records compared with the mirror, %d with >= 3 windows, %d with violations, %d erased only, "
+              "%d refused\n", totals.compared, totals.three_windows, totals.violating, totals.erased_only, totals.refused);
+  CHECK(totals.three_windows > 0 && totals.violating > 0 && totals.erased_only > 0 && totals.refused > 0);
+  HIP_OK(hipStreamDestroy(stream));
+  if (g_fail) {
+    std::printf("%d FAILURES\n", g_fail);
+    return 1;
+  }
+  std::printf("ALL OK\n");
+  return 0;
+}

@@ -451,6 +451,7 @@ int configure_kernels_for_device(int device) {
   // (the kernel has static LDS of its own; what a spline the solve accepts needs lies 2 * D * 64 * 8 bytes and
   // more below the sampling/LP kernel's limit)
   TPAMD_BIG_LDS(k_check_joint, (int)kSampleLpLdsLimitBytes - 1024);
+  TPAMD_BIG_LDS(k_pset_check_joint, (int)kSampleLpLdsLimitBytes - 1024);
 #undef TPAMD_BIG_LDS
   g_device_configured[device] = true;
   return 0;
@@ -2865,6 +2866,12 @@ struct tpamd_planner_set {
   std::vector<int32_t> h_need;
   int num_waiting = 0;
   bool streaming = false;
+  // tpamd_planner_set_set_checking: the solver's sd2 of the window being solved [B][N] and the
+  // per-planner records [B] (one allocation, made when checking is first switched on and kept)
+  bool checking = false;
+  DeviceBuffer check_buf;
+  double *d_sd2 = nullptr;
+  PlannerCheckDev *d_check = nullptr;
 };
 
 namespace {
@@ -3347,6 +3354,7 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   ps->rd_in.release();
   ps->rd_out.release();
   ps->stop_buf.release();
+  ps->check_buf.release();
   if (ps->fixed) (void)hipFree(ps->fixed);
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
@@ -3361,7 +3369,7 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
   return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->table_bytes + ps->sw_buf.bytes +
-                   ps->rd_in.bytes + ps->rd_out.bytes + ps->stop_buf.bytes + ps->wp_buf.bytes
+                   ps->rd_in.bytes + ps->rd_out.bytes + ps->stop_buf.bytes + ps->wp_buf.bytes + ps->check_buf.bytes
             : 0;
 }
 
@@ -3430,6 +3438,24 @@ int tpamd_planner_set_reset(tpamd_planner_set *ps, int count, const int32_t *ids
   return 0;
 }
 
+// Checking (tpamd_planner_set_set_checking; nothing of this is enqueued with checking off): a Plan
+// call that starts afresh clears the records; every window iteration checks, behind the sweep, the
+// windows it solved. P: the largest path of the set, as the solve takes it.
+static void clear_window_checks(tpamd_planner_set *ps, hipStream_t st) {
+  const int B = ps->S.B;
+  hipLaunchKernelGGL(k_pset_check_clear, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, B, ps->d_check);
+}
+static void check_windows(tpamd_planner_set *ps, int P, hipStream_t st) {
+  const PlannerSetState &S = ps->S;
+  const double safety = ps->cfg.constraint_safety;
+  if (ps->cartesian)
+    hipLaunchKernelGGL(k_pset_check_cartesian, dim3((unsigned)S.B), dim3(kCheckThreads), 0, st, ps->P, safety, ps->d_tq,
+                       ps->d_tJ, ps->table_cap, ps->d_vmax, S.amax, ps->d_vtrans, ps->d_vrot, ps->d_sd2, ps->d_check);
+  else
+    hipLaunchKernelGGL(k_pset_check_joint, dim3((unsigned)S.B), dim3(kCheckThreads), check_joint_lds(P, S.D), st, ps->P,
+                       P, ps->pcap, safety, ps->d_cp, ps->d_vmax, S.amax, ps->d_sd2, ps->d_check);
+}
+
 // Plan for every planner of a set. kPlanFresh is tpamd_planner_set_plan; kPlanStreaming is the same
 // with the streaming arrays set (a planner whose window is not resident waits); kPlanResume
 // re-enters the window loop for the planners that waited (k_pset_resume in place of the prologue,
@@ -3464,6 +3490,7 @@ static int planner_set_plan_run(tpamd_planner_set *ps, PlanKind kind, const int6
     HIPCHK(hipMemcpyAsync(ps->d_horizon, horizon_ns, B * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ps->d_loop_start, start_ns, B * 8, hipMemcpyHostToDevice, st));   // :630
     ps->last_h2d += 3 * B * 8;
+    if (ps->checking) clear_window_checks(ps, st);
     for (int *z : {ps->P.old_state, ps->P.offset, ps->P.loop, ps->P.append, ps->d_windows})
       HIPCHK(hipMemsetAsync(z, 0, B * 4, st));
     HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
@@ -3484,7 +3511,7 @@ static int planner_set_plan_run(tpamd_planner_set *ps, PlanKind kind, const int6
     tpamd_joint_inputs din{S.knots, ps->d_cp, ps->d_vmax, S.amax, S.path_start, ps->d_delta, S.path_start_velocity,
                            ps->d_sdd0, S.path_time_start, nullptr};
     tpamd_path_outputs dout{ps->w_time, ps->w_s, ps->w_sd, ps->w_sdd, ps->w_q, ps->w_qd, ps->w_qdd, ps->w_lei,
-                            ps->w_dtm, ps->w_st, nullptr};
+                            ps->w_dtm, ps->w_st, ps->checking ? ps->d_sd2 : nullptr};
     hipLaunchKernelGGL(k_plan_begin, dim3(gb), dim3(128), 0, st, ps->P, e->ws);
     int rc;
     if (ps->cartesian) {
@@ -3497,6 +3524,7 @@ static int planner_set_plan_run(tpamd_planner_set *ps, PlanKind kind, const int6
       rc = solve_joint(e, &bt, &din, &dout, st, &ps->P);
     }
     if (rc) return rc;
+    if (ps->checking) check_windows(ps, (int)P, st);
     HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
     hipLaunchKernelGGL(k_plan_end, dim3(gb), dim3(128), 0, st, ps->P);
     hipLaunchKernelGGL(k_plan_append, dim3((unsigned)((N + 127) / 128), (unsigned)B), dim3(128), 0, st, ps->P);
@@ -3629,6 +3657,7 @@ int tpamd_planner_set_plan_device(tpamd_planner_set *ps, const int64_t *start_ns
     std::fill(ps->h_wait.begin(), ps->h_wait.end(), 0);
     ps->num_waiting = 0;
   }
+  if (ps->checking) clear_window_checks(ps, st);
   HIPCHK(hipMemsetAsync(S.num_active, 0, 8, st));
   hipLaunchKernelGGL(k_pset_prologue_step, dim3(gb), dim3(128), 0, st, S, ps->P, (const long long *)start_ns,
                      (const long long *)horizon_ns, ps->d_start, ps->d_horizon, ps->d_need_cap);
@@ -3636,7 +3665,7 @@ int tpamd_planner_set_plan_device(tpamd_planner_set *ps, const int64_t *start_ns
   tpamd_joint_inputs din{S.knots, ps->d_cp, ps->d_vmax, S.amax, S.path_start, ps->d_delta, S.path_start_velocity,
                          ps->d_sdd0, S.path_time_start, nullptr};
   tpamd_path_outputs dout{ps->w_time, ps->w_s, ps->w_sd, ps->w_sdd, ps->w_q, ps->w_qd, ps->w_qdd, ps->w_lei,
-                          ps->w_dtm, ps->w_st, nullptr};
+                          ps->w_dtm, ps->w_st, ps->checking ? ps->d_sd2 : nullptr};
   int rc = 0;
   for (int w = 0; w < max_windows && !rc; w++) {
     if (ps->cartesian) {
@@ -3648,6 +3677,7 @@ int tpamd_planner_set_plan_device(tpamd_planner_set *ps, const int64_t *start_ns
       rc = solve_joint(e, &bt, &din, &dout, st, &ps->P);
     }
     if (rc) break;
+    if (ps->checking) check_windows(ps, (int)P, st);
     hipLaunchKernelGGL(k_plan_append_early, dim3((unsigned)((N + 127) / 128), (unsigned)B), dim3(128), 0, st, ps->P);
     if (w + 1 < max_windows) hipLaunchKernelGGL(k_pset_step, dim3(gb), dim3(128), 0, st, S, ps->P, ps->d_need_cap);
     else hipLaunchKernelGGL(k_pset_last_step, dim3(gb), dim3(128), 0, st, S, ps->P);
@@ -3678,6 +3708,65 @@ int tpamd_planner_set_plan_device(tpamd_planner_set *ps, const int64_t *start_ns
   if (readout_end(ps, st)) return TPAMD_E_HIP;
   HIPCHK(hipStreamWaitEvent(nullptr, ps->ev_read, 0));
   return rc;
+}
+
+int tpamd_planner_set_set_checking(tpamd_planner_set *ps, int on) {
+  static_assert(sizeof(tpamd_planner_check) == sizeof(PlannerCheckDev), "record layouts must agree");
+  if (!ps) return TPAMD_E_INVALID_ARGUMENT;
+  if (!on || ps->checking) {
+    ps->checking = on != 0;     // (switched off: the buffer stays; switched on again: the records start empty)
+    return 0;
+  }
+  TPAMD_ON_DEVICE(ps->e);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  const size_t B = ps->S.B, N = ps->S.N;
+  if (int rc = ps->check_buf.reserve(B * N * 8 + B * sizeof(PlannerCheckDev))) return rc;
+  ps->d_sd2 = (double *)ps->check_buf.p;
+  ps->d_check = (PlannerCheckDev *)(ps->d_sd2 + B * N);
+  clear_window_checks(ps, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(nullptr));
+  ps->checking = true;
+  return 0;
+}
+
+int tpamd_planner_set_checking(const tpamd_planner_set *ps) { return ps && ps->checking; }
+
+int tpamd_planner_set_check_results(tpamd_planner_set *ps, int count, const int32_t *ids, tpamd_planner_check *out) {
+  if (!ps || !out || count < 0 || count > ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (ids) {
+    std::vector<char> seen(ps->S.B, 0);
+    for (int k = 0; k < count; k++) {
+      if (ids[k] < 0 || ids[k] >= ps->S.B || seen[ids[k]]) return TPAMD_E_INVALID_ARGUMENT;
+      seen[ids[k]] = 1;
+    }
+  }
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = nullptr;
+  const int32_t *d_ids = nullptr;
+  PlannerCheckDev *d_out = nullptr;
+  HostStage in(/*packed=*/true, /*tight=*/true), res;
+  in.up(&d_ids, ids, (size_t)count);
+  res.down(&d_out, (PlannerCheckDev *)out, (size_t)count);
+  if (in.upload(ps->rd_in, st) || res.upload(ps->rd_out, st)) return TPAMD_E_HIP;
+  hipLaunchKernelGGL(k_pset_check_results, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, st, ps->S.B, count, d_ids,
+                     ps->checking ? ps->d_check : nullptr, d_out);
+  HIPCHK(hipGetLastError());
+  return res.download(st);
+}
+
+int tpamd_planner_set_check_results_device(tpamd_planner_set *ps, int count, const int32_t *ids,
+                                           tpamd_planner_check *out, void *hip_stream) {
+  if (!ps || !out || count < 0 || count > ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  hipLaunchKernelGGL(k_pset_check_results, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, st, ps->S.B, count, ids,
+                     ps->checking ? ps->d_check : nullptr, (PlannerCheckDev *)out);
+  HIPCHK(hipGetLastError());
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
 }
 
 int tpamd_planner_set_download_trajectory(tpamd_planner_set *ps, int planner, int first, int count, double *time,

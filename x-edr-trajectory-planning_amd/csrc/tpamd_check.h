@@ -30,6 +30,9 @@
 //   in the prologue); one thread per sample evaluates q', q'' and walks the 2D rows.
 //   Cartesian form: one thread per sample reads q[i], q[i+1], q[i+2] and J[i] (strided, or through
 //   first_row) and walks the 2D + 2 rows.
+// The sample loops of the joint and the Cartesian form are check_joint_path / check_cartesian_path,
+// shared with the kernels that check the windows of a planner set inside its Plan calls (at the end
+// of this file).
 #pragma once
 
 #include <limits.h>
@@ -91,8 +94,8 @@ __device__ __forceinline__ void check_store_skipped(int b, const CheckOutputs &o
   if (out.first_sample) out.first_sample[b] = -1;
 }
 
-// Workgroup reduction of the threads' records and the store of the path's five results.
-__device__ __forceinline__ void check_store(CheckAcc acc, int b, int C, const CheckOutputs &out) {
+// Workgroup reduction of the threads' records: true for thread 0, whose `acc` is then the path's.
+__device__ __forceinline__ bool check_reduce(CheckAcc &acc) {
   __shared__ double s_worst[kCheckThreads / 64];
   __shared__ int s_int[kCheckThreads / 64][3];
 #pragma unroll
@@ -105,8 +108,14 @@ __device__ __forceinline__ void check_store(CheckAcc acc, int b, int C, const Ch
     s_int[wave][0] = acc.count; s_int[wave][1] = acc.flat; s_int[wave][2] = acc.first;
   }
   __syncthreads();
-  if (threadIdx.x != 0) return;
+  if (threadIdx.x != 0) return false;
   for (int w = 1; w < kCheckThreads / 64; w++) check_merge(acc, s_int[w][0], s_worst[w], s_int[w][1], s_int[w][2]);
+  return true;
+}
+
+// The reduction and the store of the path's five results.
+__device__ __forceinline__ void check_store(CheckAcc acc, int b, int C, const CheckOutputs &out) {
+  if (!check_reduce(acc)) return;
   out.violations[b] = acc.count;
   if (out.worst_excess) out.worst_excess[b] = acc.flat >= 0 ? acc.worst : qnan();
   if (out.worst_sample) out.worst_sample[b] = acc.flat >= 0 ? acc.flat / C : -1;
@@ -149,34 +158,25 @@ k_check_rows(int N, int C, const double *a, const double *bm, const double *lo, 
   check_store(acc, b, C, out);
 }
 
-// ----------------------------------------------------------------- joint form
-// grid = B, block = kCheckThreads. Dynamic LDS: knots[P+3] | control points [P][D] | lim_lo[2D] |
-// lim_hi[2D]. knots [B][P+3], control points [B][P][D]; with np, path b uses the first np[b] + 3 and
-// np[b] entries of its slot (a count outside [3, P] is not checked).
-static __global__ void __launch_bounds__(kCheckThreads)
-k_check_joint(int N, int D, int P, double safety, const double *knots_g, const double *cps_g, const double *vmax,
-              const double *amax, const double *path_start_g, const double *delta_g, const int32_t *ns,
-              const int32_t *np, CheckSolution sol, CheckOutputs out) {
-  extern __shared__ double lds[];
+// The n samples of one joint path against its 2D rows, by the whole workgroup (every thread's own
+// record comes back). The path's Pb control points, Pb + 3 knots and D limits are the caller's;
+// `lds` is laid out for P_lds >= Pb points (check_joint_lds); the solution's samples start at row0.
+__device__ __forceinline__ CheckAcc check_joint_path(double *lds, int n, int D, int Pb, int P_lds, double safety,
+                                                     const double *knots_b, const double *cps_b,
+                                                     const double *vmax_b, const double *amax_b, double path_start,
+                                                     double delta, const CheckSolution &sol, size_t row0) {
   const int tid = threadIdx.x;
-  const int b = blockIdx.x;
   const int C = 2 * D;
-  const int Pb = np ? np[b] : P;
-  const int n = (Pb >= 3 && Pb <= P) ? check_count(sol, ns, b, N) : 0;
-  if (n == 0) {
-    check_store_skipped(b, out);
-    return;
-  }
   const int Kb = Pb + 3;
   double *s_knots = lds;
-  double *s_cp = s_knots + (P + 3);
-  double *s_lo = s_cp + (size_t)P * D;
+  double *s_cp = s_knots + (P_lds + 3);
+  double *s_lo = s_cp + (size_t)P_lds * D;
   double *s_hi = s_lo + C;
-  for (int k = tid; k < Kb; k += kCheckThreads) s_knots[k] = knots_g[(size_t)b * (P + 3) + k];
-  for (int k = tid; k < Pb * D; k += kCheckThreads) s_cp[k] = cps_g[(size_t)b * P * D + k];
+  for (int k = tid; k < Kb; k += kCheckThreads) s_knots[k] = knots_b[k];
+  for (int k = tid; k < Pb * D; k += kCheckThreads) s_cp[k] = cps_b[k];
   // the limit rows, k_setup_joint's arithmetic
   for (int d = tid; d < D; d += kCheckThreads) {
-    const double am = amax[(size_t)b * D + d], vm = vmax[(size_t)b * D + d];
+    const double am = amax_b[d], vm = vmax_b[d];
     const double al = am * safety;
     const double na = -am * safety;
     const double v = vm * safety;
@@ -187,10 +187,7 @@ k_check_joint(int N, int D, int P, double safety, const double *knots_g, const d
     s_lo[D + d] = 0.0;
   }
   __syncthreads();
-  const double path_start = path_start_g[b];
-  const double delta = delta_g[b];
   const double k0 = s_knots[0], kend = s_knots[Kb - 1];
-  const size_t row0 = (size_t)b * N;
   CheckAcc acc;
   for (int i = tid; i < n; i += kCheckThreads) {
     const double sdd = sol.sdd[row0 + i], sd2 = check_sd2(sol, row0 + i);
@@ -219,7 +216,49 @@ k_check_joint(int N, int D, int P, double safety, const double *knots_g, const d
       }
     }
   }
+  return acc;
+}
+
+// ----------------------------------------------------------------- joint form
+// grid = B, block = kCheckThreads. Dynamic LDS: knots[P+3] | control points [P][D] | lim_lo[2D] |
+// lim_hi[2D]. knots [B][P+3], control points [B][P][D]; with np, path b uses the first np[b] + 3 and
+// np[b] entries of its slot (a count outside [3, P] is not checked).
+static __global__ void __launch_bounds__(kCheckThreads)
+k_check_joint(int N, int D, int P, double safety, const double *knots_g, const double *cps_g, const double *vmax,
+              const double *amax, const double *path_start_g, const double *delta_g, const int32_t *ns,
+              const int32_t *np, CheckSolution sol, CheckOutputs out) {
+  extern __shared__ double lds[];
+  const int b = blockIdx.x;
+  const int C = 2 * D;
+  const int Pb = np ? np[b] : P;
+  const int n = (Pb >= 3 && Pb <= P) ? check_count(sol, ns, b, N) : 0;
+  if (n == 0) {
+    check_store_skipped(b, out);
+    return;
+  }
+  const CheckAcc acc = check_joint_path(lds, n, D, Pb, P, safety, knots_g + (size_t)b * (P + 3), cps_g + (size_t)b * P * D,
+                                        vmax + (size_t)b * D, amax + (size_t)b * D, path_start_g[b], delta_g[b], sol,
+                                        (size_t)b * N);
   check_store(acc, b, C, out);
+}
+
+// The n samples of one Cartesian path against its 2D + 2 rows, by the whole workgroup: its table
+// rows start at row table0 of q_g / J_g, the solution's samples at row0.
+__device__ __forceinline__ CheckAcc check_cartesian_path(int n, int D, double safety, const double *q_g,
+                                                         const double *J_g, size_t table0, const double *vmax_b,
+                                                         const double *amax_b, double vt, double vr, double delta,
+                                                         const CheckSolution &sol, size_t row0) {
+  const int C = 2 * D + 2;
+  const double inv = 1.0 / delta;
+  CheckAcc acc;
+  for (int i = threadIdx.x; i < n; i += kCheckThreads) {
+    double rec[32], ra[34], rb[34], rlo[34], rhi[34];
+    const size_t row = table0 + (size_t)i;
+    cw_rows_at(i, n, D, inv, q_g + row * D, J_g + row * 6 * D, vmax_b, amax_b, safety, vt, vr, rec, ra, rb, rlo, rhi);
+    const double sdd = sol.sdd[row0 + i], sd2 = check_sd2(sol, row0 + i);
+    for (int c = 0; c < C; c++) check_row(acc, ra[c], rb[c], rlo[c], rhi[c], sdd, sd2, i, i * C + c);
+  }
+  return acc;
 }
 
 // ------------------------------------------------------------- Cartesian form
@@ -235,22 +274,117 @@ k_check_cartesian(int N, int D, double safety, const double *q_g, const double *
     check_store_skipped(b, out);
     return;
   }
-  const size_t table0 = cw_ragged_first_row(first_row, b, N);
-  const size_t row0 = (size_t)b * N;
-  const double inv = 1.0 / delta_g[b];
-  const double vt = vtrans[b], vr = vrot[b];
-  CheckAcc acc;
-  for (int i = threadIdx.x; i < n; i += kCheckThreads) {
-    double rec[32], ra[34], rb[34], rlo[34], rhi[34];
-    const size_t row = table0 + (size_t)i;
-    cw_rows_at(i, n, D, inv, q_g + row * D, J_g + row * 6 * D, vmax + (size_t)b * D, amax + (size_t)b * D, safety, vt,
-               vr, rec, ra, rb, rlo, rhi);
-    const double sdd = sol.sdd[row0 + i], sd2 = check_sd2(sol, row0 + i);
-    for (int c = 0; c < C; c++) check_row(acc, ra[c], rb[c], rlo[c], rhi[c], sdd, sd2, i, i * C + c);
-  }
+  const CheckAcc acc =
+      check_cartesian_path(n, D, safety, q_g, J_g, cw_ragged_first_row(first_row, b, N), vmax + (size_t)b * D,
+                           amax + (size_t)b * D, vtrans[b], vrot[b], delta_g[b], sol, (size_t)b * N);
   check_store(acc, b, C, out);
 }
 
 inline size_t check_joint_lds(int P, int D) { return ((size_t)(P + 3) + (size_t)P * D + 4 * (size_t)D) * 8; }
+
+// ---------------------------------------------------------------- planner sets
+// tpamd_planner_set_set_checking (include/tpamd.h): every window a set's Plan call solves is checked
+// in the window loop, directly behind the sweep and in front of k_plan_end / k_plan_append (or
+// k_plan_append_early and the step kernel), while the window's arrays, its path_start and the
+// loop state are those of the solve. One workgroup per planner as above; a planner that solved no
+// window in this iteration (not active: idle, failed, suspended for IK rows, or skipped by the
+// start-velocity projection) or whose window is not TPAMD_PATH_OK leaves at once, uncounted.
+// Thread 0 merges the window's record into the planner's (planner_check_merge): nothing else
+// writes that record during a Plan call, so no atomics.
+struct PlannerCheckDev {                 // tpamd_planner_check
+  int32_t windows, violations, last_window_violations;
+  int32_t worst_window, worst_sample, worst_row, first_window, first_sample;
+  double worst_excess, worst_parameter;
+};
+static_assert(sizeof(PlannerCheckDev) == 48, "tpamd_planner_check is 48 bytes");
+
+__device__ __forceinline__ PlannerCheckDev planner_check_none() {
+  PlannerCheckDev r;
+  r.windows = 0;
+  r.violations = r.last_window_violations = -1;
+  r.worst_window = r.worst_sample = r.worst_row = r.first_window = r.first_sample = -1;
+  r.worst_excess = r.worst_parameter = qnan();
+  return r;
+}
+
+// Window `window`'s record (a reduced CheckAcc of C rows per sample) into the planner's. Windows
+// arrive in solve order, so an equal excess keeps the earlier window and the first violated
+// (window, sample) is set once. w_s: the window's path parameters.
+__device__ __forceinline__ void planner_check_merge(PlannerCheckDev &r, const CheckAcc &acc, int C, int window,
+                                                    const double *w_s) {
+  r.windows += 1;
+  r.violations = (r.violations < 0 ? 0 : r.violations) + acc.count;
+  r.last_window_violations = acc.count;
+  if (acc.flat >= 0 && (r.worst_window < 0 || acc.worst > r.worst_excess)) {
+    r.worst_excess = acc.worst;
+    r.worst_window = window;
+    r.worst_sample = acc.flat / C;
+    r.worst_row = acc.flat % C;
+    r.worst_parameter = w_s[r.worst_sample];
+  }
+  if (r.first_window < 0 && acc.first != INT_MAX) {
+    r.first_window = window;
+    r.first_sample = acc.first;
+  }
+}
+
+// whether planner b's window of this iteration is checked (block-uniform)
+__device__ __forceinline__ bool planner_check_takes_part(const PlanParams &p, int b) {
+  return p.active[b] && p.w_status[b] == 0;
+}
+
+static __global__ void k_pset_check_clear(int B, PlannerCheckDev *rec) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) rec[b] = planner_check_none();
+}
+
+// grid = B, block = kCheckThreads. Dynamic LDS: check_joint_lds(P_lds, D), P_lds the largest path
+// of the set. cps [B][pcap][D]; knots p.knots [B][p.K]; sd2 [B][N] is the solver's.
+static __global__ void __launch_bounds__(kCheckThreads)
+k_pset_check_joint(PlanParams p, int P_lds, int pcap, double safety, const double *cps, const double *vmax,
+                   const double *amax, const double *sd2, PlannerCheckDev *rec) {
+  extern __shared__ double lds[];
+  const int b = blockIdx.x;
+  if (!planner_check_takes_part(p, b)) return;
+  const int Pb = p.np[b];
+  if (Pb < 3 || Pb > P_lds) return;
+  const int N = p.N, D = p.D;
+  const CheckSolution sol{sd2, nullptr, p.w_sdd, nullptr};
+  CheckAcc acc = check_joint_path(lds, N, D, Pb, P_lds, safety, p.knots + (size_t)b * p.K, cps + (size_t)b * pcap * D,
+                                  vmax + (size_t)b * D, amax + (size_t)b * D, p.path_start[b], p.delta[b], sol,
+                                  (size_t)b * N);
+  if (!check_reduce(acc)) return;
+  PlannerCheckDev r = rec[b];
+  planner_check_merge(r, acc, 2 * D, p.windows[b], p.w_s + (size_t)b * N);
+  rec[b] = r;
+}
+
+// grid = B, block = kCheckThreads. The window's rows are slots p.first[b] .. + N - 1 of planner b's
+// resident table ([B][table_stride] rows), as k_cartesian_lp reads them.
+static __global__ void __launch_bounds__(kCheckThreads)
+k_pset_check_cartesian(PlanParams p, double safety, const double *q_g, const double *J_g, int table_stride,
+                       const double *vmax, const double *amax, const double *vtrans, const double *vrot,
+                       const double *sd2, PlannerCheckDev *rec) {
+  const int b = blockIdx.x;
+  if (!planner_check_takes_part(p, b)) return;
+  const int N = p.N, D = p.D;
+  const CheckSolution sol{sd2, nullptr, p.w_sdd, nullptr};
+  CheckAcc acc = check_cartesian_path(N, D, safety, q_g, J_g, (size_t)b * table_stride + p.first[b], vmax + (size_t)b * D,
+                                      amax + (size_t)b * D, vtrans[b], vrot[b], p.delta[b], sol, (size_t)b * N);
+  if (!check_reduce(acc)) return;
+  PlannerCheckDev r = rec[b];
+  planner_check_merge(r, acc, 2 * D + 2, p.windows[b], p.w_s + (size_t)b * N);
+  rec[b] = r;
+}
+
+// out[k] = the record of planner ids[k] (k, without ids); without `rec` (checking is off), or for an
+// id outside the set, the record of "nothing checked".
+static __global__ void k_pset_check_results(int B, int count, const int32_t *ids, const PlannerCheckDev *rec,
+                                            PlannerCheckDev *out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const int b = ids ? ids[k] : k;
+  out[k] = (rec && b >= 0 && b < B) ? rec[b] : planner_check_none();
+}
 
 }  // namespace tpamd

@@ -13,7 +13,9 @@
 //                    (tpamd_planner_set_plan_resume): the planners that waited for IK rows re-enter
 //                    the window loop with the loop state they had
 //   window loop      k_plan_begin / set-up / K1 / k_plan_project / sweep / k_plan_end /
-//                    k_plan_append (tpamd_kernels.h), as in tpamd_plan_joint_windows_host
+//                    k_plan_append (tpamd_kernels.h), as in tpamd_plan_joint_windows_host; with
+//                    tpamd_planner_set_set_checking on, k_pset_check_joint / k_pset_check_cartesian
+//                    (tpamd_check.h) behind the sweep: the window against its constraint rows
 //   resample         k_resample / k_resample_skip over the histories (:755-836)
 //   k_pset_epilogue  :662-684: end_time_, final_decel_start_ clamped to time-step multiples,
 //                    target_reached_

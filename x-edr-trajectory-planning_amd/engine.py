@@ -240,6 +240,18 @@ class _PlanDeviceInfo(C.Structure):
 
 PLAN_RESOURCE_EXHAUSTED = 8     # TPAMD_PLAN_RESOURCE_EXHAUSTED
 
+# tpamd_planner_check (48 bytes)
+PLANNER_CHECK_DTYPE = np.dtype([
+    ("windows", np.int32), ("violations", np.int32), ("last_window_violations", np.int32),
+    ("worst_window", np.int32), ("worst_sample", np.int32), ("worst_row", np.int32),
+    ("first_window", np.int32), ("first_sample", np.int32),
+    ("worst_excess", np.float64), ("worst_parameter", np.float64)])
+
+
+class _PlannerCheck(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in PLANNER_CHECK_DTYPE.names[:8]] +
+                [(n, C.c_double) for n in PLANNER_CHECK_DTYPE.names[8:]])
+
 _LIB = None
 
 # every symbol include/tpamd.h declares
@@ -269,6 +281,8 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_reserve", "tpamd_planner_set_capacity", "tpamd_planner_set_plan_device",
     "tpamd_planner_set_last_plan_bytes", "tpamd_planner_set_device_bytes",
     "tpamd_planner_set_stop_parameters", "tpamd_planner_set_upload_paths_ragged",
+    "tpamd_planner_set_set_checking", "tpamd_planner_set_checking",
+    "tpamd_planner_set_check_results", "tpamd_planner_set_check_results_device",
     "tpamd_planner_set_download_path", "tpamd_planner_set_switch_paths", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
     "tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
     "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device",
@@ -439,6 +453,13 @@ def load_library():
     L.tpamd_fastest_stop_host.argtypes = [vp, C.POINTER(_FastestStopArgs)]
     L.tpamd_planner_set_stop_parameters.restype = i
     L.tpamd_planner_set_stop_parameters.argtypes = [vp, i] + [vp] * 5
+    for name in ("tpamd_planner_set_set_checking", "tpamd_planner_set_checking", "tpamd_planner_set_check_results",
+                 "tpamd_planner_set_check_results_device"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_set_checking.argtypes = [vp, i]
+    L.tpamd_planner_set_checking.argtypes = [vp]
+    L.tpamd_planner_set_check_results.argtypes = [vp, i, vp, vp]
+    L.tpamd_planner_set_check_results_device.argtypes = [vp, i, vp, vp, vp]
     i64 = C.c_int64
     for name in ("tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
                  "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device"):
@@ -2088,6 +2109,42 @@ class PlannerSet:
             self._handle(), n, _ptr(ida), _ptr(t), _ptr(keep), _ptr(off), _ptr(w), float(rounding), _ptr(s), _ptr(npts),
             _ptr(st)), "tpamd_planner_set_switch_paths_rounded")
         return dict(stop_parameter=torch.from_numpy(s), num_points=torch.from_numpy(npts), status=torch.from_numpy(st))
+
+    # ------------------------------------------------------------ checking the windows
+    def set_checking(self, on=True):
+        """Check every window the Plan calls solve against its constraint rows
+        (tpamd_planner_set_set_checking; off by default)."""
+        _check(self._lib.tpamd_planner_set_set_checking(self._handle(), 1 if on else 0),
+               "tpamd_planner_set_set_checking")
+
+    @property
+    def checking(self):
+        return bool(self._lib.tpamd_planner_set_checking(self._handle()))
+
+    def check_results(self, ids=None):
+        """The tpamd_planner_check record of each listed planner (all without ids) over the windows
+        of its last Plan call: a numpy structured array of PLANNER_CHECK_DTYPE. Synchronises."""
+        ida, n = self._ids(ids)
+        out = np.zeros(max(n, 1), dtype=PLANNER_CHECK_DTYPE)
+        _check(self._lib.tpamd_planner_set_check_results(self._handle(), n, _ptr(ida), _ptr(out)),
+               "tpamd_planner_set_check_results")
+        return out[:n]
+
+    def check_results_device(self, out, ids=None, stream=None):
+        """The same records into `out`, a contiguous CUDA uint8 tensor [count][48] (view it on the host
+        with PLANNER_CHECK_DTYPE), enqueued on `stream` without synchronising: it can follow
+        plan_async on that stream. ids: CUDA int32 [count] or None for planners 0 .. count-1."""
+        import torch
+        size = PLANNER_CHECK_DTYPE.itemsize
+        if (not _is_cuda(out) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[1] != size or
+                not out.is_contiguous()):
+            raise TpamdError("out must be a contiguous CUDA uint8 tensor [count][%d]" % size)
+        n = out.shape[0]
+        idt = None if ids is None else self._cuda(ids, torch.int32, torch.device("cuda", self.device), (n,), "ids")
+        _check(self._lib.tpamd_planner_set_check_results_device(self._handle(), n, _ptr(idt), _ptr(out),
+                                                                _stream_ptr(stream)),
+               "tpamd_planner_set_check_results_device")
+        return out
 
     # ------------------------------------------------------------ readouts
     def sample_at_ticks(self, start_ns, step_ns, num_ticks, ids=None, q=None, qd=None, qdd=None, status=None,

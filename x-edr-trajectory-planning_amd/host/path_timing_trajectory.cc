@@ -461,9 +461,19 @@ void PathTimingTrajectory::SolveCartesianWindows(const std::vector<PathTimingTra
     tpamd_path_outputs out{t.data(), s.data(), sd.data(), sdd.data(), nullptr, qd.data(), qdd.data(), lei.data(),
                            dtm.data(), st.data(), sd2.data()};
     int rc;
+    bool check = false;
+    for (size_t i : g) check = check || planners[i]->check_solutions_;
+    std::vector<int32_t> c_count(B, -1), c_sample(B, -1), c_row(B, -1), c_first(B, -1);
+    std::vector<double> c_excess(B, std::numeric_limits<double>::quiet_NaN());
     {
       ::tpamd::EngineLease lease = ::tpamd::acquire_engine(planners[g[0]]->device_);
       rc = lease ? tpamd_time_cartesian_paths_host(lease.get(), &batch, &in, &out) : TPAMD_E_NO_DEVICE;
+      if (rc == 0 && check) {
+        // the same rows again, from the same inputs, against the solver's sd2 and sdd
+        tpamd_solution sol{sd2.data(), nullptr, sdd.data(), st.data()};
+        tpamd_check_outputs co{c_count.data(), c_excess.data(), c_sample.data(), c_row.data(), c_first.data()};
+        rc = tpamd_check_cartesian_paths_host(lease.get(), &batch, &in, nullptr, nullptr, 0, &sol, &co);
+      }
     }
     for (size_t k = 0; k < B; k++) {
       const size_t i = g[k];
@@ -473,6 +483,8 @@ void PathTimingTrajectory::SolveCartesianWindows(const std::vector<PathTimingTra
       pl->profile_.AdoptSolution((int)N, (int)(2 * D + 2), pl->path_start_, pl->path_horizon_, &t[k * N], &s[k * N],
                                  &sd[k * N], &sdd[k * N], &sd2[k * N], lei[k], dtm[k]);
       Window &w = (*windows)[i];
+      w.check.violations = c_count[k]; w.check.worst_excess = c_excess[k];
+      w.check.worst_sample = c_sample[k]; w.check.worst_row = c_row[k]; w.check.first_sample = c_first[k];
       std::copy_n(q.begin() + k * N * D, N * D, w.q.begin());
       std::copy_n(qd.begin() + k * N * D, N * D, w.qd.begin());
       std::copy_n(qdd.begin() + k * N * D, N * D, w.qdd.begin());
@@ -632,6 +644,7 @@ std::vector<Status> PathTimingTrajectory::PlanBatch(const std::vector<PathTiming
   for (size_t i = 0; i < P; i++) {
     if (planners[i] == nullptr) { status[i] = InvalidArgumentError("null planner"); continue; }
     bool needs = false;
+    if (planners[i]->check_solutions_) planners[i]->check_record_ = EmptyPlannerCheck();
     status[i] = planners[i]->PlanPrologue(start, time_horizon, &needs);
     // the loop condition of path_timing_trajectory.cc:632 is tested before the first window
     if (status[i].ok() && needs) { looping[i] = !planners[i]->planned_to_end_; finish[i] = 1; }
@@ -642,6 +655,7 @@ std::vector<Status> PathTimingTrajectory::PlanBatch(const std::vector<PathTiming
     std::map<std::tuple<int, size_t, size_t, size_t, double, int, double>, std::vector<size_t>> groups;
     for (size_t i = 0; i < P; i++) {
       if (!finish[i]) continue;
+      if (planners[i]->check_solutions_) continue;      // the host loop below, where the rows are
       if (auto *joint = dynamic_cast<TimeableJointSplinePath *>(planners[i]->path_.get())) {
         // (planners whose options differ in the loop limit or the start-velocity tolerance are
         // solved by separate engine calls: one value of each per call)
@@ -671,8 +685,20 @@ std::vector<Status> PathTimingTrajectory::PlanBatch(const std::vector<PathTiming
       else foreign.push_back(i);
     }
     if (!any) break;
-    for (size_t i : foreign) status[i] = planners[i]->SolveWindowOnHost(&windows[i]);
+    for (size_t i : foreign) {
+      status[i] = planners[i]->SolveWindowOnHost(&windows[i]);
+      if (status[i].ok() && planners[i]->check_solutions_)
+        windows[i].check = planners[i]->profile_.GetSolutionCheckRecord();
+    }
     if (!cartesian.empty()) SolveCartesianWindows(planners, cartesian, &windows, &status);
+    // the window's record into the planner's; loop[i] windows of this call were solved before it
+    for (size_t i = 0; i < P; i++) {
+      PathTimingTrajectory *pl = planners[i];
+      if (!looping[i] || !status[i].ok() || !pl->check_solutions_) continue;
+      const SolutionCheckRecord &c = windows[i].check;
+      MergeWindowRecord(c, loop[i], c.worst_sample >= 0 ? pl->profile_.GetPathParameter()[c.worst_sample] : 0.0,
+                        &pl->check_record_);
+    }
     // phase 3 and the loop bookkeeping of path_timing_trajectory.cc:640-660
     for (size_t i = 0; i < P; i++) {
       if (!looping[i]) continue;

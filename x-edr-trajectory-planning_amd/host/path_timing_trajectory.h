@@ -62,6 +62,15 @@ class PathTimingTrajectory : public TrajectoryPlanner {
   void SetProfileDebugVerbosity(int level) { TimeOptimalPathProfile::SetDebugVerbosity(level); }
   const PathTimingTrajectoryOptions &GetOptions() const { return options_; }
   const TimeOptimalPathProfile &GetProfile() const { return profile_; }
+  // Checks every window a Plan call solves against its constraint rows (include/tpamd.h, "Checking
+  // every window a planner set plans"; off by default). With it on, a TimeableJointSplinePath planner
+  // takes the host window loop -- rows from the path's own SamplePath / ConstraintSetup, formed on
+  // the host -- instead of the chained device windows, and a Cartesian planner's windows are checked
+  // with tpamd_check_cartesian_paths_host. GetCheckRecord: the record over the windows of the last
+  // Plan call (EmptyPlannerCheck() before the first one, with checking off or when none was solved).
+  void SetCheckSolutions(bool on) { check_solutions_ = on; check_record_ = EmptyPlannerCheck(); }
+  bool GetCheckSolutions() const { return check_solutions_; }
+  const tpamd_planner_check &GetCheckRecord() const { return check_record_; }
 
  protected:
   void ResetDerived() override;
@@ -78,6 +87,7 @@ class PathTimingTrajectory : public TrajectoryPlanner {
     std::vector<double> q, q1, q2, qd, qdd, t, s, sd, sdd, sd2;
     int32_t last_extremal_index = 0, status = -1;
     double max_time_increment = 0.0;
+    SolutionCheckRecord check;               // of this window, with check_solutions_
   };
   Status BeginWindow(Time start, Duration target_duration, Window *w);   // up to the path sampling
   Status ProjectStartVelocity(const Window &w);                          // after sampling, :360-377
@@ -117,6 +127,8 @@ class PathTimingTrajectory : public TrajectoryPlanner {
          path_start_acceleration_ = 0;
   TimeOptimalPathProfile profile_;
   bool initial_plan_ = false, planned_to_end_ = false;
+  bool check_solutions_ = false;
+  tpamd_planner_check check_record_ = EmptyPlannerCheck();
   // values at the path samples of all windows planned so far
   std::vector<double> time_at_path_samples_, path_parameter_at_path_samples_,
       path_velocity_at_path_samples_, path_acceleration_at_path_samples_;

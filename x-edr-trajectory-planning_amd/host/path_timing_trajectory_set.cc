@@ -1173,6 +1173,39 @@ size_t PathTimingTrajectorySet::LastPlanBytesOverPcie() const {
   return up + down;
 }
 
+Status PathTimingTrajectorySet::SetChecking(bool on) {
+  if (!init_status_.ok()) return init_status_;
+  if (plan_pending_) return FailedPreconditionError("a PlanDevice call is in flight (FinishPlanDevice)");
+  const int rc = tpamd_planner_set_set_checking(set_, on ? 1 : 0);
+  return rc == 0 ? OkStatus() : InternalError(tpamd_error_string(rc));
+}
+
+Status PathTimingTrajectorySet::CheckResults(const std::vector<size_t> &planners,
+                                             std::vector<tpamd_planner_check> *out) const {
+  if (!init_status_.ok()) return init_status_;
+  if (!out) return InvalidArgumentError("no output");
+  std::vector<int32_t> ids(planners.size());
+  for (size_t k = 0; k < planners.size(); k++) {
+    if (planners[k] >= num_planners_) return InvalidArgumentError("no such planner");
+    ids[k] = (int32_t)planners[k];
+  }
+  std::vector<tpamd_planner_check> records(std::max<size_t>(planners.size(), 1));
+  const int rc = tpamd_planner_set_check_results(set_, (int)ids.size(), ids.data(), records.data());
+  if (rc == TPAMD_E_INVALID_ARGUMENT) return InvalidArgumentError("more planners than the set has, or one listed twice");
+  if (rc != 0) return InternalError(tpamd_error_string(rc));
+  records.resize(planners.size());
+  out->swap(records);
+  return OkStatus();
+}
+
+Status PathTimingTrajectorySet::CheckResultsDevice(int count, const int32_t *planners_dev, tpamd_planner_check *out_dev,
+                                                   void *hip_stream) const {
+  if (!init_status_.ok()) return init_status_;
+  const int rc = tpamd_planner_set_check_results_device(set_, count, planners_dev, out_dev, hip_stream);
+  if (rc == TPAMD_E_INVALID_ARGUMENT) return InvalidArgumentError("no output, or a count outside 0 .. NumPlanners()");
+  return rc == 0 ? OkStatus() : InternalError(tpamd_error_string(rc));
+}
+
 size_t PathTimingTrajectorySet::DeviceBytes() const { return tpamd_planner_set_device_bytes(set_); }
 
 }  // namespace trajectory_planning

@@ -324,6 +324,15 @@ class PathTimingTrajectorySet {
   Status StopTrajectoriesBeforeTime(const std::vector<size_t> &planners, const std::vector<Time> &time,
                                     const std::vector<VectorXd> &max_acceleration, double time_step,
                                     std::vector<StoppingSegment> *out) const;
+  // Checks every window the set's Plan calls solve against its constraint rows, on the device
+  // (tpamd_planner_set_set_checking; off by default). CheckResults: the record of each listed planner
+  // over the windows of its last Plan call (listed once each; synchronises). CheckResultsDevice:
+  // the same into device memory (planners_dev: device ids or null for planners 0 .. count-1),
+  // enqueued on hip_stream behind a PlanDevice, no synchronisation.
+  Status SetChecking(bool on);
+  bool Checking() const { return tpamd_planner_set_checking(set_) != 0; }
+  Status CheckResults(const std::vector<size_t> &planners, std::vector<tpamd_planner_check> *out) const;
+  Status CheckResultsDevice(int count, const int32_t *planners_dev, tpamd_planner_check *out_dev, void *hip_stream) const;
   // Bytes the last Plan call moved over PCIe, both directions.
   size_t LastPlanBytesOverPcie() const;
   size_t DeviceBytes() const;

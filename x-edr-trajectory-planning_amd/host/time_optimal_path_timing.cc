@@ -153,6 +153,12 @@ Status TimeOptimalPathProfile::SolutionSatisfiesConstraints() {
   return OkStatus();
 }
 
+SolutionCheckRecord TimeOptimalPathProfile::GetSolutionCheckRecord() const {
+  if (solver_state_ != kProblemSolved || rows_a_.empty()) return SolutionCheckRecord();
+  return CheckSolutionRows(num_samples_, num_constraints_, rows_a_.data(), rows_b_.data(), rows_lo_.data(),
+                           rows_hi_.data(), sd2_.data(), sdd_.data());
+}
+
 TimeOptimalPathProfile::Scalar TimeOptimalPathProfile::GetMaxTimeIncrement() const {
   if (solver_state_ != kProblemSolved) { LogError("Error, solution not yet calculated!"); return -1; }
   return dt_max_;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "compat.h"
+#include "solution_check.h"
 
 namespace trajectory_planning {
 
@@ -92,6 +93,11 @@ class TimeOptimalPathProfile {
                          Scalar *sd2zero);
   int GetLastExtremalIndex() const { return last_extremal_index_; }
   ::tpamd::compat::Status SolutionSatisfiesConstraints();
+  // The same test as a record (solution_check.h): the count SolutionSatisfiesConstraints reports,
+  // the largest excess with its (sample, row) and the first violated sample, of the current
+  // solution on the rows SetupProblem was given. Not checked (-1 / NaN / -1 / -1 / -1) without a
+  // solution or without rows (a solution installed by AdoptSolution has none).
+  SolutionCheckRecord GetSolutionCheckRecord() const;
 
   // Engine status of the last solve (TPAMD_PATH_*), 0 when solved.
   int last_status() const { return last_status_; }
