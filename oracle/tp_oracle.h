@@ -302,6 +302,7 @@ int64_t tpo_planner_final_decel_start(const tpo_planner *p);
 int tpo_planner_target_reached(const tpo_planner *p);
 int tpo_planner_windows(const tpo_planner *p);   /* timing windows computed by the last plan */
 int tpo_planner_path_state(const tpo_planner *p);
+int tpo_planner_history_count(const tpo_planner *p);   /* samples in *_at_path_samples_ */
 
 #ifdef __cplusplus
 }

@@ -501,3 +501,4 @@ int64_t tpo_planner_final_decel_start(const tpo_planner *p) { return p->final_de
 int tpo_planner_target_reached(const tpo_planner *p) { return p->target_reached; }
 int tpo_planner_windows(const tpo_planner *p) { return p->windows; }
 int tpo_planner_path_state(const tpo_planner *p) { return p->path_state; }
+int tpo_planner_history_count(const tpo_planner *p) { return (int)p->t_ps.n; }

@@ -406,7 +406,7 @@ class Planner:
         L.tpo_planner_set_spline.argtypes = [vp, _dp, i, _dp, i, i]
         L.tpo_planner_plan.restype = i
         L.tpo_planner_plan.argtypes = [vp, i64, i64]
-        for name in ("num_samples", "target_reached", "windows", "path_state"):
+        for name in ("num_samples", "target_reached", "windows", "path_state", "history_count"):
             getattr(L, "tpo_planner_" + name).restype = i
             getattr(L, "tpo_planner_" + name).argtypes = [vp]
         for name in ("end_time", "final_decel_start"):
@@ -439,6 +439,18 @@ class Planner:
         knots, cps = _f64(knots), _f64(cps)
         self._L.tpo_planner_set_spline(self._p, knots, len(knots), cps, cps.shape[0], int(state))
 
+    def set_ik_table(self, ik_positions, jacobians, path_end, max_trans_vel, max_rot_vel, state=1):
+        """What a TimeableCartesianSplinePath holds after its IK callback ran over the whole path
+        (tpo_planner_set_ik_table): ik_positions [rows][D], row r at path parameter r * delta, the
+        Jacobians [rows][6][D] there, knots.back() and the Cartesian velocity limits."""
+        q, J = _f64(ik_positions), _f64(jacobians)
+        rows = q.shape[0]
+        assert q.shape == (rows, self.D) and J.shape == (rows, 6, self.D)
+        f = self._L.tpo_planner_set_ik_table
+        f.restype = None
+        f.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int]
+        f(self._p, q, J, rows, float(path_end), float(max_trans_vel), float(max_rot_vel), int(state))
+
     def set_initial_velocity(self, velocity):
         """TimeablePath::SetInitialVelocity: the joint velocity the next Plan of a new or modified
         path starts from."""
@@ -465,6 +477,8 @@ class Planner:
     final_decel_start = property(lambda self: self._L.tpo_planner_final_decel_start(self._p))
     target_reached = property(lambda self: bool(self._L.tpo_planner_target_reached(self._p)))
     windows = property(lambda self: self._L.tpo_planner_windows(self._p))
+    path_state = property(lambda self: self._L.tpo_planner_path_state(self._p))
+    history_count = property(lambda self: self._L.tpo_planner_history_count(self._p))
 
 
 # ------------------------------------------------------------ quaternion splines
