@@ -1565,6 +1565,92 @@ int tpamd_check_cartesian_paths_host(tpamd_engine *engine, const tpamd_cartesian
                                      const tpamd_check_outputs *out);
 
 /* ------------------------------------------------------------------------
+ * Refining violating paths on the device: solve, check, and solve the violators again at doubled
+ * sample counts, in one call and without a round trip to the host. Joint batches
+ * (tpamd_time_joint_paths_*) and waypoint batches (tpamd_time_waypoint_paths_*); Cartesian batches,
+ * explicit rows and planner sets have no refined form (a finer grid needs new rows from the caller).
+ *
+ * Round 0 is the plain call: `out` receives, bit for bit, what tpamd_time_joint_paths_* /
+ * tpamd_time_waypoint_paths_* write for the same arguments, for the paths that are refined too (their
+ * coarse solution stays available), and ref->check receives what tpamd_check_joint_paths_* writes
+ * for it. The solve is asked for sd2 internally if out->sd2 is NULL.
+ *
+ * Selection. Path b (n_b samples) needs refinement if violations[b] > 0 and worst_excess[b] >
+ * tolerance (tolerance 0 is the reference's criterion: a violated row has a positive excess). Of
+ * those, the paths with 2 n_b - 1 <= max_samples take slots 0, 1, .. in ascending path index, up to
+ * max_refined slots. The slot numbers come from a prefix count, not from atomics: the slot map is
+ * the same in every run. ref->slot[b] is
+ *   >= 0   the slot path b is refined in
+ *   -1     nothing to refine: the path is clean, within tolerance, or was not checked
+ *   -2     the path needs refinement but no slot is left
+ *   -3     the path needs refinement but 2 n_b - 1 > max_samples
+ *
+ * Rounds r = 1 .. max_rounds run on the sub-batch of max_refined slots. A slot's path is solved with
+ * n_r = 2 n_{r-1} - 1 samples and delta_r = delta_{r-1} / 2 (exact: the old samples are every second
+ * new one) on the same spline, limits, path_start, sd_start, sdd_start and time_start, into
+ * ref->refined (arrays of stride max_samples), and checked. The slot goes on to round r + 1 only if
+ * that solve still needs refinement by the rule above, r < max_rounds and 2 n_r - 1 <= max_samples;
+ * otherwise it is settled and later rounds leave its outputs alone. A finer solve that fails (status
+ * not TPAMD_PATH_OK) is not checked and therefore settles: its status is in ref->refined.status and
+ * the caller still has the coarse solution in `out`.
+ *
+ * Per slot k: slot_path[k] (the path, -1 for an unused slot), rounds[k] (solves made), num_samples[k]
+ * and delta[k] (of the last solve made; 0 for an unused slot) and refined_check (the record of that
+ * last solve; "not checked" for an unused slot). A slot's entries of ref->refined are, bit for bit,
+ * what tpamd_time_joint_paths_* writes for that path alone at (num_samples[k], delta[k]); entries
+ * behind num_samples[k], and unused slots, are not written.
+ *
+ * REFINEMENT MAY END WITH VIOLATIONS LEFT. It is a bounded loop whose outcome is reported per path,
+ * not a promise: most violators are clean after one doubling, some need two, and a few keep a
+ * violated row at every sample count tried ("Refining a batch"). Read refined_check.
+ *
+ * _device: device pointers (waypoint_offsets stays a host array); enqueues round 0 and max_rounds
+ * rounds on hip_stream and does not synchronise except where the plain entry may (workspace or
+ * scratch growth); a round with nothing left to do costs its empty launches. _host: host pointers,
+ * synchronises, and stops after the round that settles the last slot. Never pipelined. The rounds
+ * use a workspace of their own: afterwards tpamd_query_device answers as after the plain call.
+ * Call-level errors write nothing and follow the plain entry; in addition a NULL opt or ref or a
+ * NULL required array is TPAMD_E_INVALID_ARGUMENT, and options out of range (max_samples below
+ * batch->num_samples included) or more than 65535 paths are TPAMD_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------ */
+typedef struct tpamd_refine_options {
+  int32_t max_rounds;   /* 1..8 */
+  int32_t max_samples;  /* stride of the refined arrays, 3..8192, >= batch->num_samples */
+  int32_t max_refined;  /* M slots, 1..65535 */
+  int32_t reserved;
+  double tolerance;     /* >= 0 */
+} tpamd_refine_options;
+
+typedef struct tpamd_refine_outputs {
+  tpamd_check_outputs check;          /* [B] round 0; violations required */
+  int32_t *slot;                      /* [B] required */
+  int32_t *slot_path;                 /* [M] path of a slot, -1 unused; required */
+  int32_t *num_refined;               /* [1] required */
+  int32_t *rounds;                    /* [M] solves made in the slot; may be NULL */
+  int32_t *num_samples;               /* [M] of the slot's last solve; may be NULL */
+  double *delta;                      /* [M] of the slot's last solve; may be NULL */
+  tpamd_path_outputs refined;         /* [M][max_samples](..[D]); time, s, sd, sdd, status required */
+  tpamd_check_outputs refined_check;  /* [M] record of each slot's final solve; every array may be NULL */
+} tpamd_refine_outputs;
+
+int tpamd_time_joint_paths_refined_device(tpamd_engine *engine, const tpamd_joint_batch *batch,
+                                          const tpamd_joint_inputs *in, const tpamd_path_outputs *out,
+                                          const tpamd_refine_options *opt, const tpamd_refine_outputs *ref,
+                                          void *hip_stream);
+int tpamd_time_joint_paths_refined_host(tpamd_engine *engine, const tpamd_joint_batch *batch,
+                                        const tpamd_joint_inputs *in, const tpamd_path_outputs *out,
+                                        const tpamd_refine_options *opt, const tpamd_refine_outputs *ref);
+int tpamd_time_waypoint_paths_refined_device(tpamd_engine *engine, const tpamd_waypoint_batch *batch,
+                                             const tpamd_waypoint_inputs *in, const tpamd_path_outputs *out,
+                                             const tpamd_waypoint_fit_outputs *fit,
+                                             const tpamd_refine_options *opt, const tpamd_refine_outputs *ref,
+                                             void *hip_stream);
+int tpamd_time_waypoint_paths_refined_host(tpamd_engine *engine, const tpamd_waypoint_batch *batch,
+                                           const tpamd_waypoint_inputs *in, const tpamd_path_outputs *out,
+                                           const tpamd_waypoint_fit_outputs *fit,
+                                           const tpamd_refine_options *opt, const tpamd_refine_outputs *ref);
+
+/* ------------------------------------------------------------------------
  * Checking every window a planner set plans: the same question, asked inside
  * tpamd_planner_set_plan / _plan_streaming / _plan_resume / _plan_device, where the windows, their
  * path_start and (Cartesian sets) their table slots exist only until the next window iteration.

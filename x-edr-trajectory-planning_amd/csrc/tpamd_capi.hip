@@ -27,6 +27,7 @@
 #include "tpamd_joint_fit.h"
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 #include "tpamd_check.h"
+#include "tpamd_refine.h"
 
 using namespace tpamd;
 
@@ -206,6 +207,8 @@ struct tpamd_engine {
   bool pose_busy = false;
   DeviceBuffer wp_fit;         // waypoint batches (tpamd_time_waypoint_paths_*): the fitted splines, one slot of
                                // the largest control-point count per path, and what the fit knows per path
+  DeviceBuffer refine;         // refined calls (tpamd_time_*_paths_refined_*): the sub-batch of slots and their state
+  DeviceBuffer refine_ws;      // the workspace of their rounds: the current one keeps what round 0 left in it
   bool rows_for_plan = false;  // rows holds only zeros and rows written by window chaining (of any set on
                                // this engine, under its own split of the buffer: finite values, no more)
   Workspace ws{};
@@ -680,6 +683,8 @@ void tpamd_engine_destroy(tpamd_engine *e) {
   e->rows.release();
   e->pose_ints.release();
   e->wp_fit.release();
+  e->refine.release();
+  e->refine_ws.release();
   if (e->ev_pose) (void)hipEventDestroy(e->ev_pose);
   delete e;
 }
@@ -732,10 +737,13 @@ struct FittedPaths {
 // The joint-space solve; `plan` (window chaining, tpamd_plan_joint_windows_host) adds two small
 // kernels: skip marks after the set-up kernel, the start-velocity projection after K1. `fitted`
 // (waypoint batches) gives every path its own control-point count, as a planner set does, and adds
-// one small kernel behind the set-up kernel if a path has no waypoints.
+// one small kernel behind the set-up kernel if a path has no waypoints. `skip_zero_samples` (the rounds
+// of a refined call, tpamd_refine.h) adds the same kernel on the sample counts: a path whose count
+// is 0 takes no part and its outputs stay as they are.
 int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
                 const tpamd_path_outputs *out, void *hip_stream, const PlanParams *plan,
-                bool allow_pipelining = true, const FittedPaths *fitted = nullptr) {
+                bool allow_pipelining = true, const FittedPaths *fitted = nullptr,
+                bool skip_zero_samples = false) {
   if (!e || !bt || !in || !out) return TPAMD_E_INVALID_ARGUMENT;
   const int B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, P = bt->num_points;
   if (B <= 0) return B == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
@@ -792,6 +800,8 @@ int solve_joint(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_
     if (plan)
       hipLaunchKernelGGL(k_plan_mark_skipped, dim3((B + 127) / 128), dim3(128), 0, fs, *plan, ws);
     if (fitted && fitted->any_empty) launch_skip_empty_paths(B, fitted->np, ws.err_bits, fs);
+    if (skip_zero_samples && in->num_samples_per_path)
+      launch_skip_empty_paths(B, in->num_samples_per_path, ws.err_bits, fs);
     if (ordered)
       hipLaunchKernelGGL(k_order_paths, dim3(1), dim3(1024), 0, fs, B, N, in->num_samples_per_path, order);
   }
@@ -2140,6 +2150,49 @@ int waypoint_timing_args(const tpamd_engine *e, const tpamd_waypoint_batch *bt, 
   return 0;
 }
 
+// What a waypoint solve leaves on the device for the call that goes on with it (the refined entry):
+// the batch as the joint form describes it, in the engine's scratch.
+struct WaypointSolved {
+  tpamd_joint_batch jb;           // num_points = S, the slot size
+  tpamd_joint_inputs ji;          // knots [B][S + 3], control points [B][S][D]; num_samples_per_path null: uniform
+  const int32_t *np;              // [B] control points of each path
+};
+// The host arrays of a waypoint batch in `s` (both _host timing entries). S: the slot size of the fit
+// outputs. A path without waypoints, and a path's rows behind its own sample count, keep what the
+// caller's arrays hold: those go up as well then.
+void stage_waypoint(HostStage &s, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                    const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit, size_t S, bool any_empty,
+                    tpamd_waypoint_inputs *din, tpamd_path_outputs *dout, tpamd_waypoint_fit_outputs *dfit) {
+  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples;
+  din->waypoint_offsets = in->waypoint_offsets;
+  s.up(&din->waypoints, in->waypoints, (size_t)in->waypoint_offsets[B] * D);
+  s.up(&din->rounding, in->rounding, B);
+  s.up(&din->max_velocity, in->max_velocity, B * D);
+  s.up(&din->max_acceleration, in->max_acceleration, B * D);
+  s.up(&din->num_samples_per_path, in->num_samples_per_path, B);
+  s.up(&din->delta, in->delta, B);
+  s.up(&din->sd_start, in->sd_start, B);
+  s.up(&din->time_start, in->time_start, B);
+  stage_path_outputs(s, B, N, D, out, dout, /*keep=*/any_empty || in->num_samples_per_path != nullptr);
+  if (fit) {
+    s.down(&dfit->num_points, fit->num_points, B);
+    s.down(&dfit->path_end, fit->path_end, B);
+    s.down(&dfit->delta_used, fit->delta_used, B);
+    s.down(&dfit->knots, fit->knots, B * (S + 3));
+    s.down(&dfit->control_points, fit->control_points, B * S * D);
+  }
+}
+// Behind the upload: the two per-path outputs that are staged either way keep the caller's values for a
+// path without waypoints.
+int upload_kept_path_outputs(size_t B, bool any_empty, const tpamd_path_outputs *out, const tpamd_path_outputs *dout,
+                             hipStream_t st) {
+  if (!any_empty) return 0;
+  if (out->last_extremal_index)
+    HIPCHK(hipMemcpyAsync(dout->last_extremal_index, out->last_extremal_index, B * 4, hipMemcpyHostToDevice, st));
+  if (out->max_time_increment)
+    HIPCHK(hipMemcpyAsync(dout->max_time_increment, out->max_time_increment, B * 8, hipMemcpyHostToDevice, st));
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -2207,9 +2260,10 @@ int tpamd_fit_joint_waypoints_host(tpamd_engine *e, int num_paths, int num_dofs,
   return rc ? rc : s.download(st);
 }
 
-int tpamd_time_waypoint_paths_device(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
-                                     const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit,
-                                     void *hip_stream) {
+// tpamd_time_waypoint_paths_device; `solved` (may be null) receives where the batch lies afterwards.
+static int waypoint_solve(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                          const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit, void *hip_stream,
+                          WaypointSolved *solved) {
   std::vector<int32_t> np;
   int S = 0;
   bool any_empty = false;
@@ -2259,7 +2313,18 @@ int tpamd_time_waypoint_paths_device(tpamd_engine *e, const tpamd_waypoint_batch
     HIPCHK(hipMemcpyAsync(fit->knots, w.knots, (size_t)B * (S + 3) * 8, hipMemcpyDeviceToDevice, st));
   if (fit && fit->control_points)
     HIPCHK(hipMemcpyAsync(fit->control_points, w.cps, (size_t)B * S * D * 8, hipMemcpyDeviceToDevice, st));
+  if (solved) {
+    solved->jb = jb;
+    solved->ji = ji;
+    solved->np = p.num_points;
+  }
   return 0;
+}
+
+int tpamd_time_waypoint_paths_device(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                                     const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit,
+                                     void *hip_stream) {
+  return waypoint_solve(e, bt, in, out, fit, hip_stream, nullptr);
 }
 
 int tpamd_time_waypoint_paths_host(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
@@ -2279,33 +2344,9 @@ int tpamd_time_waypoint_paths_host(tpamd_engine *e, const tpamd_waypoint_batch *
   tpamd_path_outputs dout{};
   tpamd_waypoint_fit_outputs dfit{};
   HostStage s;
-  din.waypoint_offsets = in->waypoint_offsets;
-  s.up(&din.waypoints, in->waypoints, (size_t)in->waypoint_offsets[B] * D);
-  s.up(&din.rounding, in->rounding, B);
-  s.up(&din.max_velocity, in->max_velocity, B * D);
-  s.up(&din.max_acceleration, in->max_acceleration, B * D);
-  s.up(&din.num_samples_per_path, in->num_samples_per_path, B);
-  s.up(&din.delta, in->delta, B);
-  s.up(&din.sd_start, in->sd_start, B);
-  s.up(&din.time_start, in->time_start, B);
-  // a path without waypoints, and a path's rows behind its own sample count, keep what the caller's
-  // arrays hold: those go up as well then
-  stage_path_outputs(s, B, N, D, out, &dout, /*keep=*/any_empty || in->num_samples_per_path != nullptr);
-  if (fit) {
-    s.down(&dfit.num_points, fit->num_points, B);
-    s.down(&dfit.path_end, fit->path_end, B);
-    s.down(&dfit.delta_used, fit->delta_used, B);
-    s.down(&dfit.knots, fit->knots, B * (S + 3));
-    s.down(&dfit.control_points, fit->control_points, B * S * D);
-  }
+  stage_waypoint(s, bt, in, out, fit, S, any_empty, &din, &dout, &dfit);
   if (int rc = s.upload(e->stage, st)) return rc;
-  if (any_empty) {
-    // (the two per-path outputs that are staged either way)
-    if (out->last_extremal_index)
-      HIPCHK(hipMemcpyAsync(dout.last_extremal_index, out->last_extremal_index, B * 4, hipMemcpyHostToDevice, st));
-    if (out->max_time_increment)
-      HIPCHK(hipMemcpyAsync(dout.max_time_increment, out->max_time_increment, B * 8, hipMemcpyHostToDevice, st));
-  }
+  if (int rc = upload_kept_path_outputs(B, any_empty, out, &dout, st)) return rc;
   int rc = tpamd_time_waypoint_paths_device(e, bt, &din, &dout, &dfit, st);
   return rc ? rc : s.download(st);
 }
@@ -2516,6 +2557,325 @@ int tpamd_check_cartesian_paths_host(tpamd_engine *e, const tpamd_cartesian_batc
   stage_check_io(s, B, N, sol, out, &dsol, &dout);
   if (int rc = s.upload(e->stage, st)) return rc;
   int rc = tpamd_check_cartesian_paths_device(e, bt, &din, d_ns, d_first, &dsol, &dout, st);
+  return rc ? rc : s.download(st);
+}
+
+}  // extern "C"
+
+// ---- refining violating paths on the device (tpamd_refine.h) -------------------------------------
+namespace {
+
+// What both forms check of the options and the refine outputs, behind the plain entry's own checks.
+int refine_args(const tpamd_refine_options *opt, const tpamd_refine_outputs *ref, int B, int N) {
+  const tpamd_path_outputs &r = ref->refined;
+  if (!ref->check.violations || !ref->slot || !ref->slot_path || !ref->num_refined || !r.time || !r.s || !r.sd ||
+      !r.sdd || !r.status)
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (opt->max_rounds < 1 || opt->max_rounds > 8 || opt->max_samples < 3 || opt->max_samples > 8192 ||
+      opt->max_samples < N || opt->max_refined < 1 || opt->max_refined > kMaxCheckPaths ||
+      !(opt->tolerance >= 0.0) || B > kMaxCheckPaths)
+    return TPAMD_E_UNSUPPORTED;
+  return 0;
+}
+
+// The engine's scratch of a refined call: what round 0 needs beside the caller's arrays, the
+// sub-batch of M slots (splines in slots of P control points), the slots' state and the record of
+// the round just checked. Whatever the caller passes takes the place of its entry here.
+struct RefineScratch {
+  double *sd2_0, *excess_0;                  // [B][N], [B]
+  double *knots, *cps, *vmax, *amax, *path_start, *sd_start, *sdd_start, *time_start;
+  int32_t *np;                               // [M]
+  int32_t *next_samples, *rounds, *num_samples, *live;
+  double *next_delta, *delta;
+  int32_t *made_violations, *made_sample, *made_row, *made_first;
+  double *made_excess;
+  double *sd2_r;                             // [M][max_samples]
+};
+size_t carve_refine_scratch(char *base, size_t B, size_t N, size_t M, size_t NS, size_t D, size_t P, bool sd2_0,
+                            bool sd2_r, RefineScratch *w) {
+  Stage s(base);
+  w->sd2_0 = s.take<double>(sd2_0 ? B * N : 0);
+  w->excess_0 = s.take<double>(B);
+  w->knots = s.take<double>(M * (P + 3));
+  w->cps = s.take<double>(M * P * D);
+  w->vmax = s.take<double>(M * D);
+  w->amax = s.take<double>(M * D);
+  w->path_start = s.take<double>(M);
+  w->sd_start = s.take<double>(M);
+  w->sdd_start = s.take<double>(M);
+  w->time_start = s.take<double>(M);
+  w->np = s.take<int32_t>(M);
+  w->next_samples = s.take<int32_t>(M);
+  w->rounds = s.take<int32_t>(M);
+  w->num_samples = s.take<int32_t>(M);
+  w->live = s.take<int32_t>(1);
+  w->next_delta = s.take<double>(M);
+  w->delta = s.take<double>(M);
+  w->made_violations = s.take<int32_t>(M);
+  w->made_sample = s.take<int32_t>(M);
+  w->made_row = s.take<int32_t>(M);
+  w->made_first = s.take<int32_t>(M);
+  w->made_excess = s.take<double>(M);
+  w->sd2_r = s.take<double>(sd2_r ? M * NS : 0);
+  return s.off;
+}
+
+// An earlier refined call's kernels may still read the scratch (on any stream) when it has to move.
+int ensure_refine_scratch(tpamd_engine *e, int B, int N, int D, int P, const tpamd_path_outputs *out,
+                          const tpamd_refine_options *opt, const tpamd_refine_outputs *ref, RefineScratch *w) {
+  const size_t M = opt->max_refined, NS = opt->max_samples;
+  const bool sd2_0 = out->sd2 == nullptr, sd2_r = ref->refined.sd2 == nullptr;
+  const size_t need = carve_refine_scratch(nullptr, B, N, M, NS, D, P, sd2_0, sd2_r, w);
+  if (need > e->refine.bytes) {
+    HIPCHK(hipDeviceSynchronize());
+    if (e->refine.reserve(need)) return TPAMD_E_HIP;
+  }
+  carve_refine_scratch((char *)e->refine.p, B, N, M, NS, D, P, sd2_0, sd2_r, w);
+  return 0;
+}
+
+// Run `fn` with the refinement workspace in place of the engine's current one, and keep what the
+// engine remembers of its last solve (tpamd_query_device): the rounds leave round 0 as it is.
+template <class F>
+int with_refine_workspace(tpamd_engine *e, F fn) {
+  std::swap(e->ws_buf, e->refine_ws);
+  const Workspace saved = e->ws;
+  const int last_B = e->last_B, last_N = e->last_N;
+  const double *last_time = e->last_time;
+  const bool in_lane = e->in_lane;
+  e->in_lane = true;                       // not a pipelining slot: no slot bookkeeping
+  const int rc = fn();
+  e->in_lane = in_lane;
+  e->last_B = last_B; e->last_N = last_N; e->last_time = last_time;
+  e->ws = saved;
+  std::swap(e->ws_buf, e->refine_ws);
+  return rc;
+}
+
+// Everything behind round 0's solve: its check, the slot map, the sub-batch and the rounds. `jb`,
+// `ji` describe the batch on the device in the joint form (waypoint form: `np` = the control points
+// of each path in slots of jb.num_points); out0 = round 0's outputs with sd2 set. stop_early (the
+// _host entries): the count of live slots is read after every round.
+int refine_rounds(tpamd_engine *e, const tpamd_joint_batch &jb, const tpamd_joint_inputs &ji, const int32_t *np,
+                  const tpamd_path_outputs &out0, const tpamd_refine_options &opt, const tpamd_refine_outputs &ref,
+                  const RefineScratch &w, hipStream_t st, bool stop_early) {
+  const int B = jb.num_paths, D = jb.num_dofs, N = jb.num_samples, P = jb.num_points;
+  const int M = opt.max_refined, NS = opt.max_samples;
+  const tpamd_solution sol0{out0.sd2, nullptr, out0.sdd, out0.status};
+  tpamd_check_outputs chk0 = ref.check;
+  if (!chk0.worst_excess) chk0.worst_excess = w.excess_0;
+  if (int rc = tpamd_check_joint_paths_device(e, &jb, &ji, np, &sol0, &chk0, st)) return rc;
+
+  int32_t *rounds = ref.rounds ? ref.rounds : w.rounds;
+  int32_t *num_samples = ref.num_samples ? ref.num_samples : w.num_samples;
+  double *delta = ref.delta ? ref.delta : w.delta;
+  const RefineRecord record{ref.refined_check.violations, ref.refined_check.worst_excess,
+                            ref.refined_check.worst_sample, ref.refined_check.worst_row,
+                            ref.refined_check.first_sample};
+  RefineSelectParams sp{};
+  sp.B = B; sp.M = M; sp.N = N; sp.max_samples = NS; sp.tolerance = opt.tolerance;
+  sp.violations = chk0.violations; sp.worst_excess = chk0.worst_excess;
+  sp.ns = ji.num_samples_per_path; sp.delta = ji.delta;
+  sp.slot = ref.slot; sp.slot_path = ref.slot_path; sp.num_refined = ref.num_refined; sp.live = w.live;
+  sp.rounds = rounds; sp.num_samples = num_samples; sp.delta_out = delta;
+  sp.next_samples = w.next_samples; sp.next_delta = w.next_delta;
+  sp.record = record;
+  launch_refine_select(sp, st);
+
+  RefineGatherParams gp{};
+  gp.M = M; gp.D = D; gp.knots_per_path = P + 3; gp.points_per_path = P;
+  gp.slot_path = ref.slot_path;
+  gp.knots = ji.knots; gp.cps = ji.control_points; gp.vmax = ji.max_velocity; gp.amax = ji.max_acceleration;
+  gp.path_start = ji.path_start; gp.sd_start = ji.sd_start; gp.sdd_start = ji.sdd_start; gp.time_start = ji.time_start;
+  gp.np = np;
+  gp.knots_out = w.knots; gp.cps_out = w.cps; gp.vmax_out = w.vmax; gp.amax_out = w.amax;
+  gp.path_start_out = w.path_start; gp.sd_start_out = w.sd_start; gp.sdd_start_out = w.sdd_start;
+  gp.time_start_out = w.time_start;
+  gp.np_out = np ? w.np : nullptr;
+  launch_refine_gather(gp, st);
+  HIPCHK(hipGetLastError());
+
+  const tpamd_joint_batch sb{M, D, NS, P, jb.max_solver_loops, 0, jb.constraint_safety};
+  tpamd_joint_inputs si{};
+  si.knots = w.knots; si.control_points = w.cps; si.max_velocity = w.vmax; si.max_acceleration = w.amax;
+  si.path_start = w.path_start; si.delta = w.next_delta; si.sd_start = w.sd_start; si.sdd_start = w.sdd_start;
+  si.time_start = w.time_start; si.num_samples_per_path = w.next_samples;
+  tpamd_path_outputs so = ref.refined;
+  if (!so.sd2) so.sd2 = w.sd2_r;
+  const tpamd_solution sol{so.sd2, nullptr, so.sdd, so.status};
+  const tpamd_check_outputs made{w.made_violations, w.made_excess, w.made_sample, w.made_row, w.made_first};
+  const FittedPaths fitted{w.np, P, /*any_empty=*/true};
+  RefineStepParams tp{};
+  tp.M = M; tp.max_rounds = opt.max_rounds; tp.max_samples = NS; tp.tolerance = opt.tolerance;
+  tp.made = RefineRecord{w.made_violations, w.made_excess, w.made_sample, w.made_row, w.made_first};
+  tp.out = record;
+  tp.rounds = rounds; tp.num_samples = num_samples; tp.delta_out = delta;
+  tp.next_samples = w.next_samples; tp.next_delta = w.next_delta; tp.live = w.live;
+  for (int r = 1; r <= opt.max_rounds; r++) {
+    if (stop_early) {
+      int live = 0;
+      HIPCHK(hipMemcpyAsync(&live, w.live, sizeof live, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (live == 0) break;
+    }
+    // a settled or unused slot has the count 0: skipped, its outputs stay
+    const int rc = with_refine_workspace(e, [&]() {
+      return solve_joint(e, &sb, &si, &so, st, nullptr, /*allow_pipelining=*/false, np ? &fitted : nullptr,
+                         /*skip_zero_samples=*/true);
+    });
+    if (rc) return rc;
+    if (int rc2 = tpamd_check_joint_paths_device(e, &sb, &si, np ? w.np : nullptr, &sol, &made, st)) return rc2;
+    launch_refine_step(tp, st);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int joint_refined(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
+                  const tpamd_path_outputs *out, const tpamd_refine_options *opt, const tpamd_refine_outputs *ref,
+                  hipStream_t st, bool stop_early) {
+  TPAMD_ON_DEVICE(e);
+  RefineScratch w{};
+  if (int rc = ensure_refine_scratch(e, bt->num_paths, bt->num_samples, bt->num_dofs, bt->num_points, out, opt, ref, &w))
+    return rc;
+  tpamd_path_outputs out0 = *out;
+  if (!out0.sd2) out0.sd2 = w.sd2_0;
+  // round 0: the plain solve (never pipelined: its check reads the outputs directly behind it)
+  if (int rc = solve_joint(e, bt, in, &out0, st, nullptr, /*allow_pipelining=*/false)) return rc;
+  return refine_rounds(e, *bt, *in, nullptr, out0, *opt, *ref, w, st, stop_early);
+}
+
+// The refine outputs of a _host call in `s`. The refined solution travels up first: the entries a
+// round does not write (behind a slot's count, unused slots) come back as the caller had them.
+void stage_refine_outputs(HostStage &s, size_t B, size_t M, size_t NS, size_t D, const tpamd_refine_outputs *r,
+                          tpamd_refine_outputs *d) {
+  s.down(&d->check.violations, r->check.violations, B);
+  s.down(&d->check.worst_excess, r->check.worst_excess, B);
+  s.down(&d->check.worst_sample, r->check.worst_sample, B);
+  s.down(&d->check.worst_row, r->check.worst_row, B);
+  s.down(&d->check.first_sample, r->check.first_sample, B);
+  s.down(&d->slot, r->slot, B);
+  s.down(&d->slot_path, r->slot_path, M);
+  s.down(&d->num_refined, r->num_refined, 1);
+  s.down(&d->rounds, r->rounds, M);
+  s.down(&d->num_samples, r->num_samples, M);
+  s.down(&d->delta, r->delta, M);
+  const tpamd_path_outputs &o = r->refined;
+  tpamd_path_outputs &t = d->refined;
+  s.both(&t.time, o.time, M * NS);
+  s.both(&t.s, o.s, M * NS);
+  s.both(&t.sd, o.sd, M * NS);
+  s.both(&t.sdd, o.sdd, M * NS);
+  s.both(&t.q, o.q, M * NS * D);
+  s.both(&t.qd, o.qd, M * NS * D);
+  s.both(&t.qdd, o.qdd, M * NS * D);
+  s.both(&t.last_extremal_index, o.last_extremal_index, M);
+  s.both(&t.max_time_increment, o.max_time_increment, M);
+  s.both(&t.status, o.status, M);
+  s.both(&t.sd2, o.sd2, M * NS);
+  s.down(&d->refined_check.violations, r->refined_check.violations, M);
+  s.down(&d->refined_check.worst_excess, r->refined_check.worst_excess, M);
+  s.down(&d->refined_check.worst_sample, r->refined_check.worst_sample, M);
+  s.down(&d->refined_check.worst_row, r->refined_check.worst_row, M);
+  s.down(&d->refined_check.first_sample, r->refined_check.first_sample, M);
+}
+
+int waypoint_refined(tpamd_engine *e, const tpamd_waypoint_batch *bt, const tpamd_waypoint_inputs *in,
+                     const tpamd_path_outputs *out, const tpamd_waypoint_fit_outputs *fit,
+                     const tpamd_refine_options *opt, const tpamd_refine_outputs *ref, int slot_points, hipStream_t st,
+                     bool stop_early) {
+  TPAMD_ON_DEVICE(e);
+  RefineScratch w{};
+  if (int rc = ensure_refine_scratch(e, bt->num_paths, bt->num_samples, bt->num_dofs, slot_points, out, opt, ref, &w))
+    return rc;
+  tpamd_path_outputs out0 = *out;
+  if (!out0.sd2) out0.sd2 = w.sd2_0;
+  WaypointSolved solved{};
+  if (int rc = waypoint_solve(e, bt, in, &out0, fit, st, &solved)) return rc;
+  return refine_rounds(e, solved.jb, solved.ji, solved.np, out0, *opt, *ref, w, st, stop_early);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_time_joint_paths_refined_device(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
+                                          const tpamd_path_outputs *out, const tpamd_refine_options *opt,
+                                          const tpamd_refine_outputs *ref, void *hip_stream) {
+  if (!e || !bt || !in || !out || !opt || !ref) return TPAMD_E_INVALID_ARGUMENT;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = joint_args(bt, in, out)) return rc;
+  if (int rc = refine_args(opt, ref, bt->num_paths, bt->num_samples)) return rc;
+  if (sample_lp_lds(bt->num_points, bt->num_dofs, sample_lp_block(false, in->num_samples_per_path != nullptr,
+                                                                  bt->num_dofs)) > kSampleLpLdsLimit)
+    return TPAMD_E_UNSUPPORTED;
+  return joint_refined(e, bt, in, out, opt, ref, (hipStream_t)hip_stream, /*stop_early=*/false);
+}
+
+int tpamd_time_joint_paths_refined_host(tpamd_engine *e, const tpamd_joint_batch *bt, const tpamd_joint_inputs *in,
+                                        const tpamd_path_outputs *out, const tpamd_refine_options *opt,
+                                        const tpamd_refine_outputs *ref) {
+  if (!e || !bt || !in || !out || !opt || !ref) return TPAMD_E_INVALID_ARGUMENT;
+  if (bt->num_paths <= 0) return bt->num_paths == 0 ? 0 : TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = joint_host_args(bt, in, out)) return rc;
+  if (int rc = refine_args(opt, ref, bt->num_paths, bt->num_samples)) return rc;
+  if (sample_lp_lds(bt->num_points, bt->num_dofs, sample_lp_block(false, in->num_samples_per_path != nullptr,
+                                                                  bt->num_dofs)) > kSampleLpLdsLimit)
+    return TPAMD_E_UNSUPPORTED;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_joint_inputs din{};
+  tpamd_path_outputs dout{};
+  tpamd_refine_outputs dref{};
+  HostStage s;
+  stage_joint(s, bt, in, out, &din, &dout);
+  stage_refine_outputs(s, bt->num_paths, opt->max_refined, opt->max_samples, bt->num_dofs, ref, &dref);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  const int rc = joint_refined(e, bt, &din, &dout, opt, &dref, st, /*stop_early=*/true);
+  return rc ? rc : s.download(st);
+}
+
+int tpamd_time_waypoint_paths_refined_device(tpamd_engine *e, const tpamd_waypoint_batch *bt,
+                                             const tpamd_waypoint_inputs *in, const tpamd_path_outputs *out,
+                                             const tpamd_waypoint_fit_outputs *fit, const tpamd_refine_options *opt,
+                                             const tpamd_refine_outputs *ref, void *hip_stream) {
+  if (!opt || !ref) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<int32_t> np;
+  int S = 0;
+  bool any_empty = false;
+  if (int rc = waypoint_timing_args(e, bt, in, out, &np, &S, &any_empty)) return rc;
+  if (bt->num_paths == 0) return 0;
+  if (int rc = refine_args(opt, ref, bt->num_paths, bt->num_samples)) return rc;
+  return waypoint_refined(e, bt, in, out, fit, opt, ref, S, (hipStream_t)hip_stream, /*stop_early=*/false);
+}
+
+int tpamd_time_waypoint_paths_refined_host(tpamd_engine *e, const tpamd_waypoint_batch *bt,
+                                           const tpamd_waypoint_inputs *in, const tpamd_path_outputs *out,
+                                           const tpamd_waypoint_fit_outputs *fit, const tpamd_refine_options *opt,
+                                           const tpamd_refine_outputs *ref) {
+  if (!opt || !ref) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<int32_t> np;
+  int slot = 0;
+  bool any_empty = false;
+  if (int rc = waypoint_timing_args(e, bt, in, out, &np, &slot, &any_empty)) return rc;
+  const size_t B = bt->num_paths, D = bt->num_dofs, N = bt->num_samples, S = slot;
+  if (in->num_samples_per_path)
+    for (size_t k = 0; k < B; k++)
+      if (in->num_samples_per_path[k] > bt->num_samples) return TPAMD_E_INVALID_ARGUMENT;
+  if (B == 0) return 0;
+  if (int rc = refine_args(opt, ref, bt->num_paths, bt->num_samples)) return rc;
+  TPAMD_ON_DEVICE(e);
+  hipStream_t st = nullptr;
+  tpamd_waypoint_inputs din{};
+  tpamd_path_outputs dout{};
+  tpamd_waypoint_fit_outputs dfit{};
+  tpamd_refine_outputs dref{};
+  HostStage s;
+  stage_waypoint(s, bt, in, out, fit, S, any_empty, &din, &dout, &dfit);
+  stage_refine_outputs(s, B, opt->max_refined, opt->max_samples, D, ref, &dref);
+  if (int rc = s.upload(e->stage, st)) return rc;
+  if (int rc = upload_kept_path_outputs(B, any_empty, out, &dout, st)) return rc;
+  const int rc = waypoint_refined(e, bt, &din, &dout, &dfit, opt, &dref, slot, st, /*stop_early=*/true);
   return rc ? rc : s.download(st);
 }
 

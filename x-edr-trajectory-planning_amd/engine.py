@@ -18,7 +18,7 @@ _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_k
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
             "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
             "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip", "tpamd_joint_fit.h", "tpamd_joint_fit.hip",
-            "tpamd_check.h"]
+            "tpamd_check.h", "tpamd_refine.h", "tpamd_refine.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -60,7 +60,8 @@ def _compile(target, extra_flags, force, verbose):
              (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"]),
              (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"]),
              (os.path.join(objdir, "retarget.o"), ["tpamd_retarget.hip"]),
-             (os.path.join(objdir, "joint_fit.o"), ["tpamd_joint_fit.hip"])]
+             (os.path.join(objdir, "joint_fit.o"), ["tpamd_joint_fit.hip"]),
+             (os.path.join(objdir, "refine.o"), ["tpamd_refine.hip"])]
     for d, e in SWEEP_INSTANCES:
         units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
                       ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
@@ -160,6 +161,21 @@ _CHECK_OUTPUT_KEYS = ("violations", "worst_excess", "worst_sample", "worst_row",
 
 class _CheckOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _CHECK_OUTPUT_KEYS]
+
+
+class _RefineOptions(C.Structure):
+    _fields_ = [("max_rounds", C.c_int32), ("max_samples", C.c_int32), ("max_refined", C.c_int32),
+                ("reserved", C.c_int32), ("tolerance", C.c_double)]
+
+
+class _RefineOutputs(C.Structure):
+    _fields_ = [("check", _CheckOutputs), ("slot", C.c_void_p), ("slot_path", C.c_void_p),
+                ("num_refined", C.c_void_p), ("rounds", C.c_void_p), ("num_samples", C.c_void_p),
+                ("delta", C.c_void_p), ("refined", _PathOutputs), ("refined_check", _CheckOutputs)]
+
+
+# slot[b] below 0 (include/tpamd.h tpamd_refine_outputs)
+REFINE_NOTHING, REFINE_NO_SLOT, REFINE_TOO_LONG = -1, -2, -3
 
 
 class _RowsBatch(C.Structure):
@@ -275,6 +291,8 @@ ABI_SYMBOLS = [
     "tpamd_check_rows_device", "tpamd_check_rows_host",
     "tpamd_check_joint_paths_device", "tpamd_check_joint_paths_host",
     "tpamd_check_cartesian_paths_device", "tpamd_check_cartesian_paths_host",
+    "tpamd_time_joint_paths_refined_device", "tpamd_time_joint_paths_refined_host",
+    "tpamd_time_waypoint_paths_refined_device", "tpamd_time_waypoint_paths_refined_host",
     "tpamd_plan_joint_windows_host",
     "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
     "tpamd_planner_set_reset", "tpamd_planner_set_plan", "tpamd_planner_set_download_trajectory",
@@ -435,6 +453,13 @@ def load_library():
     L.tpamd_fit_joint_waypoints_device.argtypes = [vp, i, i] + [vp] * 9 + [vp]
     L.tpamd_time_waypoint_paths_host.argtypes = [vp] * 5
     L.tpamd_time_waypoint_paths_device.argtypes = [vp] * 5 + [vp]
+    for name in ("tpamd_time_joint_paths_refined_device", "tpamd_time_joint_paths_refined_host",
+                 "tpamd_time_waypoint_paths_refined_device", "tpamd_time_waypoint_paths_refined_host"):
+        getattr(L, name).restype = i
+    L.tpamd_time_joint_paths_refined_device.argtypes = [vp] * 6 + [vp]
+    L.tpamd_time_joint_paths_refined_host.argtypes = [vp] * 6
+    L.tpamd_time_waypoint_paths_refined_device.argtypes = [vp] * 7 + [vp]
+    L.tpamd_time_waypoint_paths_refined_host.argtypes = [vp] * 7
     L.tpamd_find_max_sd2_host.restype = i
     L.tpamd_find_max_sd2_host.argtypes = [vp, i, i] + [vp] * 7
     L.tpamd_query_device.restype = i
@@ -945,20 +970,10 @@ class Engine:
         out["point_offsets"] = point_offsets
         return out
 
-    def time_waypoint_paths(self, waypoints, offsets, max_velocity, max_acceleration, num_samples,
-                            num_samples_per_path=None, delta=None, rounding=None, sd_start=None, time_start=None,
-                            safety=0.8, outputs=None, stream=None, host=False):
-        """Waypoints in, trajectories out (tpamd_time_waypoint_paths_*): path k takes rows
-        offsets[k]:offsets[k + 1] of waypoints [rows][D] (offsets: host int32 [B + 1]), is fitted on the
-        device and timed from path parameter 0 with num_samples_per_path[k] samples (None: num_samples
-        each) at delta[k] (None: the samples cover exactly the whole path). max_velocity and
-        max_acceleration are [B][D]; rounding, sd_start and time_start [B] or None (0.2, 0, 0).
-        Torch CUDA tensors on `stream` (host=False; nothing synchronises unless the engine's scratch
-        grows) or numpy arrays (host=True). Returns a dict with time, s, sd, sdd [B][N], q, qd, qdd
-        [B][N][D], status, last_extremal_index, num_points [B] int32 and max_time_increment, path_end,
-        delta_used [B] -- the arrays of `outputs` where it has them (also knots [B][S + 3] and
-        control_points [B][S][D], S = max(3 max W - 2, 4), filled only if given), new ones otherwise.
-        A path without waypoints gets status 11 (PATH_STATUS) and nothing else of it is written."""
+    def _waypoint_io(self, waypoints, offsets, max_velocity, max_acceleration, num_samples, num_samples_per_path,
+                     delta, rounding, sd_start, time_start, safety, outputs, host):
+        """The C structs of one waypoint timing call (plain or refined), the dict it returns, the
+        device of the arrays (None with host=True) and what must stay alive until the call is made."""
         off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
         B = off.shape[0] - 1
         if B < 0:
@@ -969,6 +984,7 @@ class Engine:
             f = lambda x, shape, what, dt=np.float64: _host(x, dt, shape, what)
             new = lambda shape, dt=np.float64: np.zeros(shape, dtype=dt)
             i32 = np.int32
+            dev = None
         else:
             import torch
             dev = max_velocity.device
@@ -997,6 +1013,25 @@ class Engine:
             "sd2")])
         fo = _WaypointFitOutputs(*[_ptr(out.get(k)) for k in (
             "num_points", "path_end", "delta_used", "knots", "control_points")])
+        return bt, wi, po, fo, out, B, D, dev, (off, w, vm, am, ns, dl, rd, sd0, t0)
+
+    def time_waypoint_paths(self, waypoints, offsets, max_velocity, max_acceleration, num_samples,
+                            num_samples_per_path=None, delta=None, rounding=None, sd_start=None, time_start=None,
+                            safety=0.8, outputs=None, stream=None, host=False):
+        """Waypoints in, trajectories out (tpamd_time_waypoint_paths_*): path k takes rows
+        offsets[k]:offsets[k + 1] of waypoints [rows][D] (offsets: host int32 [B + 1]), is fitted on the
+        device and timed from path parameter 0 with num_samples_per_path[k] samples (None: num_samples
+        each) at delta[k] (None: the samples cover exactly the whole path). max_velocity and
+        max_acceleration are [B][D]; rounding, sd_start and time_start [B] or None (0.2, 0, 0).
+        Torch CUDA tensors on `stream` (host=False; nothing synchronises unless the engine's scratch
+        grows) or numpy arrays (host=True). Returns a dict with time, s, sd, sdd [B][N], q, qd, qdd
+        [B][N][D], status, last_extremal_index, num_points [B] int32 and max_time_increment, path_end,
+        delta_used [B] -- the arrays of `outputs` where it has them (also knots [B][S + 3] and
+        control_points [B][S][D], S = max(3 max W - 2, 4), filled only if given), new ones otherwise.
+        A path without waypoints gets status 11 (PATH_STATUS) and nothing else of it is written."""
+        bt, wi, po, fo, out, B, D, dev, keep = self._waypoint_io(
+            waypoints, offsets, max_velocity, max_acceleration, num_samples, num_samples_per_path, delta, rounding,
+            sd_start, time_start, safety, outputs, host)
         if host:
             _check(self._lib.tpamd_time_waypoint_paths_host(self._h, C.byref(bt), C.byref(wi), C.byref(po),
                                                             C.byref(fo)), "tpamd_time_waypoint_paths_host")
@@ -1005,6 +1040,106 @@ class Engine:
                                                               C.byref(fo), _stream_ptr(stream)),
                    "tpamd_time_waypoint_paths_device")
         return out
+
+    # ------------------------------------------- refining violating paths on the device
+    def _refine_io(self, B, D, max_rounds, max_samples, max_refined, tolerance, refined, device, host):
+        """The tpamd_refine_options / tpamd_refine_outputs of one refined call and the dict it
+        returns: check and refined_check (dicts of violations, worst_excess, worst_sample, worst_row,
+        first_sample, [B] and [M]), slot [B], slot_path, rounds, num_samples, delta [M], num_refined
+        [1], and refined (a dict as time_joint_paths fills, [M][max_samples](..[D]), with sd2). The
+        arrays of `refined` (the same nesting) where it has them, new zero-filled ones otherwise
+        (refined status: -1). Unused slots and the entries behind a slot's num_samples are not written:
+        read slot_path[k] >= 0 and num_samples[k] before anything of slot k."""
+        M, NS = int(max_refined), int(max_samples)
+        if host:
+            new = lambda shape, real=True: np.zeros(shape, dtype=np.float64 if real else np.int32)
+        else:
+            import torch
+            new = lambda shape, real=True: torch.zeros(shape, dtype=torch.float64 if real else torch.int32,
+                                                       device=device)
+        src = refined or {}
+        out = {k: v for k, v in src.items() if k not in ("check", "refined", "refined_check")}
+        for name, n in (("check", B), ("refined_check", M)):
+            rec = dict(src.get(name) or {})
+            for k in _CHECK_OUTPUT_KEYS:
+                rec.setdefault(k, new((n,), k == "worst_excess"))
+            out[name] = rec
+        out.setdefault("slot", new((B,), False))
+        for k in ("slot_path", "rounds", "num_samples"):
+            out.setdefault(k, new((M,), False))
+        out.setdefault("num_refined", new((1,), False))
+        out.setdefault("delta", new((M,)))
+        sol = dict(src.get("refined") or {})
+        for k in ("time", "s", "sd", "sdd", "sd2"):
+            sol.setdefault(k, new((M, NS)))
+        for k in ("q", "qd", "qdd"):
+            sol.setdefault(k, new((M, NS, D)))
+        if "status" not in sol:
+            sol["status"] = new((M,), False) - 1    # an unused slot is not written: -1, not TPAMD_PATH_OK
+        sol.setdefault("last_extremal_index", new((M,), False))
+        sol.setdefault("max_time_increment", new((M,)))
+        out["refined"] = sol
+        ro = _RefineOutputs()
+        ro.check = _CheckOutputs(*[_ptr(out["check"].get(k)) for k in _CHECK_OUTPUT_KEYS])
+        for k in ("slot", "slot_path", "num_refined", "rounds", "num_samples", "delta"):
+            setattr(ro, k, _ptr(out.get(k)))
+        ro.refined = _PathOutputs(*[_ptr(sol.get(k)) for k in (
+            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index", "max_time_increment", "status",
+            "sd2")])
+        ro.refined_check = _CheckOutputs(*[_ptr(out["refined_check"].get(k)) for k in _CHECK_OUTPUT_KEYS])
+        opt = _RefineOptions(int(max_rounds), NS, M, 0, float(tolerance))
+        return opt, ro, out
+
+    def time_joint_paths_refined(self, inputs, outputs, num_samples, max_rounds, max_samples, max_refined,
+                                 tolerance=0.0, safety=0.8, refined=None, stream=None, host=False):
+        """time_joint_paths, its check, and up to max_rounds re-timings of the violating paths at
+        doubled sample counts, in one call (tpamd_time_joint_paths_refined_*). `outputs` receives
+        exactly what time_joint_paths writes. A path with violated rows whose worst excess lies above
+        `tolerance` and whose 2 n - 1 samples fit max_samples takes one of max_refined slots, in
+        ascending path order; slot[b] is the slot, or -1 (nothing to refine), -2 (no slot left), -3
+        (too long). Returns the dict _refine_io describes. Refinement may end with violations left:
+        read refined_check."""
+        cp = inputs["control_points"]
+        B, P, D = cp.shape
+        bt = _JointBatch(B, D, int(num_samples), P, 0, 0, float(safety))
+        ji = _JointInputs(*[_ptr(inputs.get(k)) for k in (
+            "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
+            "sd_start", "sdd_start", "time_start", "num_samples_per_path")])
+        po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
+            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
+            "max_time_increment", "status", "sd2")])
+        opt, ro, out = self._refine_io(B, D, max_rounds, max_samples, max_refined, tolerance, refined,
+                                       None if host else cp.device, host)
+        if host:
+            _check(self._lib.tpamd_time_joint_paths_refined_host(self._h, C.byref(bt), C.byref(ji), C.byref(po),
+                                                                 C.byref(opt), C.byref(ro)),
+                   "tpamd_time_joint_paths_refined_host")
+        else:
+            _check(self._lib.tpamd_time_joint_paths_refined_device(self._h, C.byref(bt), C.byref(ji), C.byref(po),
+                                                                   C.byref(opt), C.byref(ro), _stream_ptr(stream)),
+                   "tpamd_time_joint_paths_refined_device")
+        return out
+
+    def time_waypoint_paths_refined(self, waypoints, offsets, max_velocity, max_acceleration, num_samples,
+                                    max_rounds, max_samples, max_refined, tolerance=0.0, num_samples_per_path=None,
+                                    delta=None, rounding=None, sd_start=None, time_start=None, safety=0.8,
+                                    outputs=None, refined=None, stream=None, host=False):
+        """time_waypoint_paths with the refinement of time_joint_paths_refined
+        (tpamd_time_waypoint_paths_refined_*). Returns (what time_waypoint_paths returns, the refine
+        outputs)."""
+        bt, wi, po, fo, out, B, D, dev, keep = self._waypoint_io(
+            waypoints, offsets, max_velocity, max_acceleration, num_samples, num_samples_per_path, delta, rounding,
+            sd_start, time_start, safety, outputs, host)
+        opt, ro, ref = self._refine_io(B, D, max_rounds, max_samples, max_refined, tolerance, refined, dev, host)
+        if host:
+            _check(self._lib.tpamd_time_waypoint_paths_refined_host(
+                self._h, C.byref(bt), C.byref(wi), C.byref(po), C.byref(fo), C.byref(opt), C.byref(ro)),
+                "tpamd_time_waypoint_paths_refined_host")
+        else:
+            _check(self._lib.tpamd_time_waypoint_paths_refined_device(
+                self._h, C.byref(bt), C.byref(wi), C.byref(po), C.byref(fo), C.byref(opt), C.byref(ro),
+                _stream_ptr(stream)), "tpamd_time_waypoint_paths_refined_device")
+        return out, ref
 
     # ------------------------------------------- checking solutions against their rows
     def _check_io(self, solution, outputs, B, like, host):

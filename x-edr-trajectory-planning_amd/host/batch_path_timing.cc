@@ -26,6 +26,7 @@ Status BatchPathTiming::SetPaths(const std::vector<std::shared_ptr<TimeableJoint
 
 void PrepareCheckResult(bool on, size_t num_paths, BatchTimingResult *r) {
   r->violations.clear(); r->worst_sample.clear(); r->worst_row.clear(); r->worst_excess.clear();
+  r->refine_rounds.clear(); r->refine_slot_code.clear();
   if (!on) return;
   r->violations.assign(num_paths, -1); r->worst_sample.assign(num_paths, -1); r->worst_row.assign(num_paths, -1);
   r->worst_excess.assign(num_paths, std::numeric_limits<double>::quiet_NaN());
@@ -39,6 +40,105 @@ void CheckRecords::scatter(const std::vector<size_t> &ids, BatchTimingResult *r)
   for (size_t i = 0; i < ids.size(); i++) {
     r->violations[ids[i]] = violations[i]; r->worst_sample[ids[i]] = worst_sample[i];
     r->worst_row[ids[i]] = worst_row[i]; r->worst_excess[ids[i]] = worst_excess[i];
+  }
+}
+
+RefinedGroup::RefinedGroup(size_t B_, size_t N_, size_t D_, const RefineOptions &o)
+    : B(B_), N(N_), D(D_), opt(o), check(B_), refined_check(0) {
+  M = o.max_refined > 0 ? (size_t)o.max_refined : B;
+  if (o.max_samples > 0) {
+    NS = (size_t)o.max_samples;
+  } else {
+    NS = N;
+    for (int r = 0; r < o.max_rounds && 2 * NS - 1 <= 8192; r++) NS = 2 * NS - 1;
+  }
+  refined_check = CheckRecords(M);
+  slot.assign(B, -1); slot_path.assign(M, -1); num_refined.assign(1, 0);
+  rounds.assign(M, 0); num_samples.assign(M, 0); status.assign(M, -1); lei.assign(M, 0);
+  delta.assign(M, 0.0);
+  time.resize(M * NS); s.resize(M * NS); sd.resize(M * NS); sdd.resize(M * NS);
+  q.resize(M * NS * D); qd.resize(M * NS * D); qdd.resize(M * NS * D);
+}
+
+tpamd_refine_options RefinedGroup::options() const {
+  return tpamd_refine_options{opt.max_rounds, (int32_t)NS, (int32_t)M, 0, opt.tolerance};
+}
+
+tpamd_refine_outputs RefinedGroup::outputs() {
+  tpamd_refine_outputs o{};
+  o.check = check.outputs();
+  o.slot = slot.data(); o.slot_path = slot_path.data(); o.num_refined = num_refined.data();
+  o.rounds = rounds.data(); o.num_samples = num_samples.data(); o.delta = delta.data();
+  o.refined = tpamd_path_outputs{time.data(), s.data(), sd.data(), sdd.data(), q.data(), qd.data(), qdd.data(),
+                                 lei.data(), nullptr, status.data(), nullptr};
+  o.refined_check = refined_check.outputs();
+  return o;
+}
+
+PathSolution RefinedGroup::Solution(size_t i, size_t samples, const tpamd_path_outputs &c,
+                                    bool keep_last_extremal_index) const {
+  PathSolution p;
+  p.dofs = (int32_t)D;
+  p.slot_code = slot[i];
+  const int k = slot[i];
+  if (k >= 0) p.rounds = rounds[k];
+  const bool refined = k >= 0 && status[k] == 0 && refined_check.violations[k] >= 0 &&
+                       refined_check.violations[k] < check.violations[i];
+  // the arrays the path carries: row `row` of arrays of stride `stride`
+  const size_t row = refined ? (size_t)k : i, stride = refined ? NS : N;
+  const size_t n = refined ? (size_t)num_samples[k] : samples;
+  const CheckRecords &rec = refined ? refined_check : check;
+  p.status = refined ? status[k] : c.status[i];
+  if (refined) p.last_extremal_index = lei[k];
+  else if (keep_last_extremal_index) p.last_extremal_index = c.last_extremal_index[i];
+  p.samples = (int32_t)n;
+  p.violations = rec.violations[row]; p.worst_sample = rec.worst_sample[row]; p.worst_row = rec.worst_row[row];
+  p.worst_excess = rec.worst_excess[row];
+  p.time.assign(n, 0.0); p.s.assign(n, 0.0); p.sd.assign(n, 0.0); p.sdd.assign(n, 0.0);
+  p.q.assign(n * D, 0.0); p.qd.assign(n * D, 0.0); p.qdd.assign(n * D, 0.0);
+  if (p.status != 0) return p;
+  const tpamd_path_outputs from = refined ? tpamd_path_outputs{const_cast<double *>(time.data()), const_cast<double *>(s.data()),
+                                                               const_cast<double *>(sd.data()), const_cast<double *>(sdd.data()),
+                                                               const_cast<double *>(q.data()), const_cast<double *>(qd.data()),
+                                                               const_cast<double *>(qdd.data()), nullptr, nullptr, nullptr, nullptr}
+                                          : c;
+  std::copy_n(from.time + row * stride, n, p.time.begin());
+  std::copy_n(from.s + row * stride, n, p.s.begin());
+  std::copy_n(from.sd + row * stride, n, p.sd.begin());
+  std::copy_n(from.sdd + row * stride, n, p.sdd.begin());
+  std::copy_n(from.q + row * stride * D, n * D, p.q.begin());
+  std::copy_n(from.qd + row * stride * D, n * D, p.qd.begin());
+  std::copy_n(from.qdd + row * stride * D, n * D, p.qdd.begin());
+  return p;
+}
+
+void PackRefinedResult(const std::vector<PathSolution> &paths, BatchTimingResult *r) {
+  const size_t Bt = paths.size();
+  r->status.resize(Bt); r->last_extremal_index.resize(Bt);
+  r->samples_per_path.resize(Bt); r->dofs_per_path.resize(Bt);
+  r->sample_offset.assign(Bt + 1, 0); r->joint_offset.assign(Bt + 1, 0);
+  r->violations.resize(Bt); r->worst_sample.resize(Bt); r->worst_row.resize(Bt); r->worst_excess.resize(Bt);
+  r->refine_rounds.resize(Bt); r->refine_slot_code.resize(Bt);
+  r->num_samples = 0; r->num_dofs = 0;
+  r->time.clear(); r->s.clear(); r->sd.clear(); r->sdd.clear(); r->q.clear(); r->qd.clear(); r->qdd.clear();
+  for (size_t b = 0; b < Bt; b++) {
+    const PathSolution &p = paths[b];
+    r->status[b] = p.status; r->last_extremal_index[b] = p.last_extremal_index;
+    r->samples_per_path[b] = p.samples; r->dofs_per_path[b] = p.dofs;
+    r->sample_offset[b + 1] = r->sample_offset[b] + (size_t)p.samples;
+    r->joint_offset[b + 1] = r->joint_offset[b] + (size_t)p.samples * (size_t)p.dofs;
+    r->num_samples = std::max(r->num_samples, (int)p.samples);
+    r->num_dofs = std::max(r->num_dofs, (int)p.dofs);
+    r->violations[b] = p.violations; r->worst_sample[b] = p.worst_sample; r->worst_row[b] = p.worst_row;
+    r->worst_excess[b] = p.worst_excess;
+    r->refine_rounds[b] = p.rounds; r->refine_slot_code[b] = p.slot_code;
+    r->time.insert(r->time.end(), p.time.begin(), p.time.end());
+    r->s.insert(r->s.end(), p.s.begin(), p.s.end());
+    r->sd.insert(r->sd.end(), p.sd.begin(), p.sd.end());
+    r->sdd.insert(r->sdd.end(), p.sdd.begin(), p.sdd.end());
+    r->q.insert(r->q.end(), p.q.begin(), p.q.end());
+    r->qd.insert(r->qd.end(), p.qd.begin(), p.qd.end());
+    r->qdd.insert(r->qdd.end(), p.qdd.begin(), p.qdd.end());
   }
 }
 
@@ -104,19 +204,23 @@ Status BatchPathTiming::ComputeTimingProfiles(double time_start_sec, BatchTiming
   std::vector<int32_t> begin(nd + 1);
   tpamd_shard_bounds_balanced((int)Bt, cost.data(), nd, begin.data());
   // one host thread per device; each block writes its own part of the (packed) result
+  // RefineSolutions: every block fills its paths' entries here, and the result is packed afterwards
+  std::vector<PathSolution> refined(refine_.enabled ? Bt : 0);
+  std::vector<PathSolution> *rp = refine_.enabled ? &refined : nullptr;
   std::vector<Status> st(nd, OkStatus());
   std::vector<std::thread> threads;
   for (int k = 1; k < nd; k++)
-    threads.emplace_back([&, k] { st[k] = ComputeBlock(devices[k], begin[k], begin[k + 1], time_start_sec, r); });
-  st[0] = ComputeBlock(devices[0], begin[0], begin[1], time_start_sec, r);
+    threads.emplace_back([&, k] { st[k] = ComputeBlock(devices[k], begin[k], begin[k + 1], time_start_sec, r, rp); });
+  st[0] = ComputeBlock(devices[0], begin[0], begin[1], time_start_sec, r, rp);
   for (auto &t : threads) t.join();
   for (const Status &s : st)
     if (!s.ok()) return s;
+  if (rp) PackRefinedResult(refined, r);
   return OkStatus();
 }
 
 Status BatchPathTiming::ComputeBlock(int device, size_t lo, size_t hi, double time_start_sec,
-                                     BatchTimingResult *r) const {
+                                     BatchTimingResult *r, std::vector<PathSolution> *refined) const {
   if (hi <= lo) return OkStatus();
   ::tpamd::EngineLease lease = ::tpamd::acquire_engine(device);
   tpamd_engine *engine = lease.get();
@@ -174,7 +278,7 @@ Status BatchPathTiming::ComputeBlock(int device, size_t lo, size_t hi, double ti
     g.time.resize(B * N); g.s.resize(B * N); g.sd.resize(B * N); g.sdd.resize(B * N);
     g.q.resize(B * N * D); g.qd.resize(B * N * D); g.qdd.resize(B * N * D);
     g.status.assign(B, -1); g.lei.assign(B, 0);
-    if (check_solutions_) g.sd2.resize(B * N);
+    if (check_solutions_ || refined) g.sd2.resize(B * N);
   }
   // all groups of this device in ONE call: they run side by side on the engine's lanes
   std::vector<tpamd_joint_batch> batches;
@@ -187,7 +291,20 @@ Status BatchPathTiming::ComputeBlock(int device, size_t lo, size_t hi, double ti
                                      g.ragged ? g.ns.data() : nullptr});
     outs.push_back(tpamd_path_outputs{g.time.data(), g.s.data(), g.sd.data(), g.sdd.data(), g.q.data(),
                                       g.qd.data(), g.qdd.data(), g.lei.data(), nullptr, g.status.data(),
-                                      check_solutions_ ? g.sd2.data() : nullptr});
+                                      g.sd2.empty() ? nullptr : g.sd2.data()});
+  }
+  if (refined) {
+    // one group at a time through the refined entry: solve, check, re-time the violators
+    for (size_t k = 0; k < groups.size(); k++) {
+      const GroupArrays &g = groups[k];
+      RefinedGroup rg(g.B, g.N, g.D, refine_);
+      const tpamd_refine_options opt = rg.options();
+      const tpamd_refine_outputs ref = rg.outputs();
+      const int rc = tpamd_time_joint_paths_refined_host(engine, &batches[k], &ins[k], &outs[k], &opt, &ref);
+      if (rc != 0) return InternalError(tpamd_error_string(rc));
+      for (size_t i = 0; i < g.B; i++) (*refined)[g.ids[i]] = rg.Solution(i, (size_t)g.ns[i], outs[k]);
+    }
+    return OkStatus();
   }
   {
     const int rc = tpamd_time_joint_groups_host(engine, (int)groups.size(), batches.data(), ins.data(), outs.data());

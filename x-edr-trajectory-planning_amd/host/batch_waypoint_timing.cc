@@ -54,6 +54,7 @@ Status BatchWaypointTiming::ComputeTimingProfiles(double time_start_sec, BatchTi
   PrepareCheckResult(check_solutions_, Bt, r);
   num_points_.assign(Bt, 0); path_end_.assign(Bt, 0.0); delta_used_.assign(Bt, 0.0);
   engine_calls_ = 0;
+  std::vector<PathSolution> refined(refine_.enabled ? Bt : 0);
 
   ::tpamd::EngineLease lease = ::tpamd::acquire_engine(::tpamd::default_device());
   tpamd_engine *engine = lease.get();
@@ -85,16 +86,30 @@ Status BatchWaypointTiming::ComputeTimingProfiles(double time_start_sec, BatchTi
     // CheckSolutions: the fitted splines in their slots of S control points, and sd2
     size_t S = 4;
     for (size_t b : ids) S = std::max(S, paths_[b].W <= 1 ? (size_t)4 : 3 * paths_[b].W - 2);
-    std::vector<double> sd2(check_solutions_ ? B * N : 0), knots(check_solutions_ ? B * (S + 3) : 0),
+    std::vector<double> sd2(check_solutions_ || refine_.enabled ? B * N : 0), knots(check_solutions_ ? B * (S + 3) : 0),
         cps(check_solutions_ ? B * S * D : 0);
     const tpamd_waypoint_batch bt{(int32_t)B, (int32_t)D, (int32_t)N, 0, kv.first.second};
     const tpamd_waypoint_inputs in{offsets.data(), wps.data(), rounding.data(), vmax.data(), amax.data(),
                                    ragged ? ns.data() : nullptr, cover_whole_path_ ? nullptr : delta.data(),
                                    nullptr, t0.data()};
     const tpamd_path_outputs out{time.data(), s.data(), sd.data(), sdd.data(), q.data(), qd.data(), qdd.data(),
-                                 lei.data(), nullptr, status.data(), check_solutions_ ? sd2.data() : nullptr};
+                                 lei.data(), nullptr, status.data(), sd2.empty() ? nullptr : sd2.data()};
     const tpamd_waypoint_fit_outputs fit{np.data(), end.data(), used.data(), check_solutions_ ? knots.data() : nullptr,
                                          check_solutions_ ? cps.data() : nullptr};
+    if (refine_.enabled) {
+      // the refined entry: solve, check, re-time the violators; the result is packed after all groups
+      RefinedGroup rg(B, N, D, refine_);
+      const tpamd_refine_options opt = rg.options();
+      const tpamd_refine_outputs ref = rg.outputs();
+      const int rrc = tpamd_time_waypoint_paths_refined_host(engine, &bt, &in, &out, &fit, &opt, &ref);
+      engine_calls_++;
+      if (rrc != 0) return InternalError(tpamd_error_string(rrc));
+      for (size_t i = 0; i < B; i++) {
+        num_points_[ids[i]] = np[i]; path_end_[ids[i]] = end[i]; delta_used_[ids[i]] = used[i];
+        refined[ids[i]] = rg.Solution(i, (size_t)ns[i], out, status[i] != TPAMD_PATH_NO_WAYPOINTS);
+      }
+      continue;
+    }
     const int rc = tpamd_time_waypoint_paths_host(engine, &bt, &in, &out, &fit);
     engine_calls_++;
     if (rc != 0) return InternalError(tpamd_error_string(rc));
@@ -126,6 +141,7 @@ Status BatchWaypointTiming::ComputeTimingProfiles(double time_start_sec, BatchTi
       std::copy_n(qdd.begin() + i * N * D, n * D, r->qdd.begin() + r->joint_offset[b]);
     }
   }
+  if (refine_.enabled) PackRefinedResult(refined, r);
   return OkStatus();
 }
 

@@ -43,6 +43,9 @@ class BatchWaypointTiming {
   // for them and for sd2), and the result carries violations / worst_sample / worst_row / worst_excess.
   // Off (default): the engine calls and the result are what they are without this option.
   void CheckSolutions(bool on = true) { check_solutions_ = on; }
+  // BatchPathTiming::RefineSolutions for waypoint paths (tpamd_time_waypoint_paths_refined_host); off by
+  // default, and with it off the engine calls and the result are what they are without this option.
+  void RefineSolutions(const RefineOptions &options) { refine_ = options; }
 
  private:
   struct Path {
@@ -54,6 +57,7 @@ class BatchWaypointTiming {
   std::vector<Path> paths_;
   bool cover_whole_path_ = false;
   bool check_solutions_ = false;
+  RefineOptions refine_{/*enabled=*/false};
   std::vector<int32_t> num_points_;
   std::vector<double> path_end_, delta_used_;
   int engine_calls_ = 0;
