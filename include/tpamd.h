@@ -1706,6 +1706,85 @@ int tpamd_planner_set_check_results_device(tpamd_planner_set *set, int count, co
                                            tpamd_planner_check *out, void *hip_stream);
 
 /* ------------------------------------------------------------------------
+ * Planner state records: a planner of a set as bytes, for another set to take.
+ *
+ * A record holds everything of one planner that a later call on its set can read: the path
+ * (spline or resident IK rows, limits, delta, initial velocity), the window history, the planner
+ * scalars, the last window's time profile and the resampled trajectory. It is versioned,
+ * position-independent and canonical (csrc/tpamd_state.h states the format): the same planner
+ * state always gives the same bytes, all padding is zero, the trajectory is stored from its first
+ * live sample (an imported planner's trajectory starts at sample 0), and export(import(r)) == r.
+ * Not in a record: per-call scratch, the check record of tpamd_planner_set_set_checking (with
+ * checking on, a planner that imports OK reports "nothing checked" until its next Plan) and
+ * anything a host mirror knows about where a path came from.
+ *
+ * A record fits a set of the same kind (joint / Cartesian), num_dofs, num_samples,
+ * sampling_method and time_step_ns whose constraint_safety and max_initial_velocity_error have
+ * the same bit patterns; num_planners and the capacities may differ.
+ *
+ * Records are packed into a blob: record k occupies bytes offsets[k] .. offsets[k + 1]); every
+ * offset is a multiple of 16 and the blob is 16-byte aligned. Per listed planner a status comes
+ * back (TPAMD_PLAN_*): OK; RESOURCE_EXHAUSTED (export: the slot is too small, only the header was
+ * written, and not even that below 192 bytes; import_state_device: the record needs more path,
+ * history, trajectory or table capacity than the set has reserved, the planner keeps its state);
+ * FAILED_PRECONDITION (the planner waits for IK rows in a suspended streaming Plan: it neither
+ * exports nor imports); INVALID_ARGUMENT (the _device entries: an id outside the set, an offset
+ * that is no multiple of 16, a record that is malformed or of another shape; the planner keeps
+ * its state). The host entries check ids (each listed once for an import), offsets and every
+ * record before anything changes and return TPAMD_E_INVALID_ARGUMENT for the whole call instead.
+ * ids NULL: planners 0 .. count-1. count == 0 returns 0 and touches nothing; count above the
+ * set's num_planners is TPAMD_E_INVALID_ARGUMENT in every entry. Bytes of the blob that no record
+ * covers (between or behind the records, behind the header of a slot that was too small) keep what
+ * they held, in both export entries.
+ *
+ * The _host entries take host arrays, grow the destination's path, history, trajectory and table
+ * capacity as the records need, and synchronise. The _device entries take device arrays (ids
+ * included), enqueue two kernels on hip_stream, ordered against the set's other work like the
+ * device readouts and tpamd_planner_set_retarget_device, and neither synchronise nor allocate
+ * once any state entry has run on the set (the first one allocates 560 bytes of scratch per
+ * planner). An import through the _device entry must list every planner once; it leaves the
+ * host's copies of the path sizes stale until they are next needed, as a device retarget does:
+ * on a Cartesian set the next host entry that reads row counts (tpamd_planner_set_ik_table_info,
+ * _append_ik_rows, _discard_ik_rows, the table downloads, a table growth) waits for the import and
+ * reads them back once.
+ * The summaries an import writes are those of tpamd_planner_set_plan with windows = 0 and the
+ * call's per-planner status.
+ * ------------------------------------------------------------------------ */
+typedef struct tpamd_planner_state_info {   /* 56 bytes */
+  int64_t bytes;                /* the planner's record, a multiple of 16 */
+  int32_t num_points;           /* control points (joint sets with a path, else 0) */
+  int32_t history_count, trajectory_count;
+  int32_t table_rows, first_row; /* Cartesian sets: path rows so far, first resident row */
+  int32_t has_path, path_state, initial_plan, planned_to_end, target_reached;
+  int32_t trajectory_first;     /* samples erased at the front of the trajectory buffer */
+  int32_t status;               /* OK, or FAILED_PRECONDITION for a planner that waits for rows */
+} tpamd_planner_state_info;
+/* The exact record size and the counts of each listed planner; host arrays, one small download,
+ * synchronises. */
+int tpamd_planner_set_state_info(tpamd_planner_set *set, int count, const int32_t *ids,
+                                 tpamd_planner_state_info *info);
+/* The largest record the set's current capacities allow. Does not synchronise. */
+size_t tpamd_planner_set_state_bytes_bound(const tpamd_planner_set *set);
+int tpamd_planner_set_export_state_host(tpamd_planner_set *set, int count, const int32_t *ids, void *blob,
+                                        const int64_t *offsets, int32_t *status);
+int tpamd_planner_set_export_state_device(tpamd_planner_set *set, int count, const int32_t *ids, void *blob,
+                                          const int64_t *offsets, int32_t *status, void *hip_stream);
+int tpamd_planner_set_import_state_host(tpamd_planner_set *set, int count, const int32_t *ids, const void *blob,
+                                        const int64_t *offsets, tpamd_planner_summary *summary, int32_t *status);
+int tpamd_planner_set_import_state_device(tpamd_planner_set *set, int count, const int32_t *ids, const void *blob,
+                                          const int64_t *offsets, tpamd_planner_summary *summary, int32_t *status,
+                                          void *hip_stream);
+/* Planner src_ids[k] of src becomes planner dst_ids[k] of dst (host id arrays, NULL: 0 .. count-1;
+ * the destination ids each listed once); synchronises. The sets must have the same shape (else
+ * TPAMD_E_INVALID_ARGUMENT) and may be the same set: the records travel through a scratch blob, so
+ * any permutation of a set's planners is legal. Sets on different devices go through host memory.
+ * If a source planner waits for IK rows nothing is copied and status says which. dst grows as
+ * import_state_host grows it. summary (may be NULL) and status are host arrays [count]. */
+int tpamd_planner_set_copy_planners(tpamd_planner_set *dst, const int32_t *dst_ids, tpamd_planner_set *src,
+                                    const int32_t *src_ids, int count, tpamd_planner_summary *summary,
+                                    int32_t *status);
+
+/* ------------------------------------------------------------------------
  * Debug/inspection: copy the boundary curve of the LAST solve to host arrays
  * [B][N] (Boundary::sd2_max, sdd_max_for_sd2_max, sdd_min_for_sd2_max,
  * sd2_max_for_sdd0, type; time_optimal_path_timing.h:225-255) and the squared

@@ -28,6 +28,7 @@
 #include "tpamd_sweep_joint.h"   // LDS layout, tile size, k_rebuild_time; the kernel instances live in tpamd_sweep_inst.hip
 #include "tpamd_check.h"
 #include "tpamd_refine.h"
+#include "tpamd_state.h"
 
 using namespace tpamd;
 
@@ -3173,7 +3174,7 @@ struct tpamd_planner_set {
   size_t fixed_bytes = 0, hist_bytes = 0, traj_bytes = 0, path_bytes = 0;
   // host copies of S.np and S.has_path: they change only through uploads, switches and resets
   std::vector<int> h_np;
-  std::vector<char> h_has;
+  mutable std::vector<char> h_has;     // (mutable: refresh_table_counts fills the cache from a const entry)
   // a device retarget's outcome is known on the device only: h_np holds an upper bound until
   // refresh_path_counts reads the planner's count back
   std::vector<char> h_stale;
@@ -3216,7 +3217,7 @@ struct tpamd_planner_set {
   void *table = nullptr;
   size_t table_bytes = 0;
   double *d_tq = nullptr, *d_tJ = nullptr;
-  std::vector<int> h_rows, h_first_row;
+  mutable std::vector<int> h_rows, h_first_row;
   double *d_vtrans = nullptr, *d_vrot = nullptr, *d_path_end = nullptr;
   int *d_rows = nullptr, *d_first = nullptr, *d_first_row = nullptr;
   // streaming Plan: the planners that wait for rows (device flags and host copy), what they lack
@@ -3230,6 +3231,10 @@ struct tpamd_planner_set {
   // per-planner records [B] (one allocation, made when checking is first switched on and kept)
   bool checking = false;
   DeviceBuffer check_buf;
+  // state records (tpamd_state.h): the host entries' staging, the layout kernel's per-planner
+  // scratch, and "a device import may have changed row counts that h_rows / h_first_row do not show"
+  DeviceBuffer state_buf, state_items;
+  mutable bool table_stale = false;
   double *d_sd2 = nullptr;
   PlannerCheckDev *d_check = nullptr;
 };
@@ -3362,7 +3367,9 @@ int ensure_pcap(tpamd_planner_set *ps, int need, hipStream_t st) {
 
 // Move the IK tables to arrays of a larger per-planner capacity (rows): the live rows (slots 0 ..
 // rows - first_row - 1 of every planner, as the host counts them) are copied, first_row stays.
+int refresh_table_counts(const tpamd_planner_set *ps);
 int grow_table(tpamd_planner_set *ps, int new_cap, hipStream_t st) {
+  if (int rc = refresh_table_counts(ps)) return rc;
   const size_t B = ps->S.B, D = ps->S.D, old_r = ps->table_cap, new_r = new_cap;
   const double *old_q = ps->d_tq, *old_J = ps->d_tJ;
   void *old_base = ps->table;
@@ -3407,6 +3414,22 @@ int refresh_path_counts(tpamd_planner_set *ps, int b) {
   ps->h_np[b] = np;
   ps->h_has[b] = (char)has;
   ps->h_stale[b] = 0;
+  return 0;
+}
+
+// The host copies of the row counts of a Cartesian set after a device import
+// (tpamd_planner_set_import_state_device), read back once that call has finished.
+int refresh_table_counts(const tpamd_planner_set *ps) {
+  if (!ps->table_stale) return 0;
+  TPAMD_ON_DEVICE(ps->e);
+  if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
+  const size_t B = ps->S.B;
+  std::vector<int> has(B);
+  HIPCHK(hipMemcpy(ps->h_rows.data(), ps->d_rows, B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ps->h_first_row.data(), ps->d_first_row, B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(has.data(), ps->S.has_path, B * 4, hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < B; b++) ps->h_has[b] = (char)has[b];
+  ps->table_stale = false;
   return 0;
 }
 
@@ -3715,6 +3738,8 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
   ps->rd_out.release();
   ps->stop_buf.release();
   ps->check_buf.release();
+  ps->state_buf.release();
+  ps->state_items.release();
   if (ps->fixed) (void)hipFree(ps->fixed);
   if (ps->hist) (void)hipFree(ps->hist);
   if (ps->traj) (void)hipFree(ps->traj);
@@ -3729,7 +3754,8 @@ void tpamd_planner_set_destroy(tpamd_planner_set *ps) {
 
 size_t tpamd_planner_set_device_bytes(const tpamd_planner_set *ps) {
   return ps ? ps->fixed_bytes + ps->hist_bytes + ps->traj_bytes + ps->path_bytes + ps->table_bytes + ps->sw_buf.bytes +
-                   ps->rd_in.bytes + ps->rd_out.bytes + ps->stop_buf.bytes + ps->wp_buf.bytes + ps->check_buf.bytes
+                   ps->rd_in.bytes + ps->rd_out.bytes + ps->stop_buf.bytes + ps->wp_buf.bytes + ps->check_buf.bytes +
+                   ps->state_buf.bytes + ps->state_items.bytes
             : 0;
 }
 
@@ -4847,6 +4873,7 @@ int ik_append_args(const tpamd_planner_set *ps, int count, const int32_t *ids, c
   if (!ps || !ps->cartesian || count < 0 || !offsets || !q || !J) return TPAMD_E_INVALID_ARGUMENT;
   const size_t B = ps->S.B;
   if ((size_t)count > B || offsets[0] != 0) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = refresh_table_counts(ps)) return rc;
   std::vector<char> seen(B, 0);
   id->resize(count);
   dst->resize(count);
@@ -4952,6 +4979,7 @@ int tpamd_planner_set_append_ik_rows_device(tpamd_planner_set *ps, int count, co
 int tpamd_planner_set_download_ik_table(tpamd_planner_set *ps, int planner, int32_t *rows, double *ik_positions,
                                         double *jacobians, int capacity) {
   if (!ps || !rows || planner < 0 || planner >= ps->S.B || !ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = refresh_table_counts(ps)) return rc;
   const int R = ps->h_has[planner] ? ps->h_rows[planner] : 0;
   *rows = R;
   if (R > 0 && ps->h_first_row[planner] > 0) return TPAMD_E_INVALID_ARGUMENT;   // rows from 0 are gone
@@ -4970,6 +4998,7 @@ int tpamd_planner_set_discard_ik_rows(tpamd_planner_set *ps, int count, const in
   if (!ps || !ps->cartesian || count < 0) return TPAMD_E_INVALID_ARGUMENT;
   const size_t B = ps->S.B, n = (size_t)count;
   if (n > B) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = refresh_table_counts(ps)) return rc;
   std::vector<char> seen(B, 0);
   std::vector<int32_t> id(n), first(n);
   for (size_t k = 0; k < n; k++) {
@@ -5010,6 +5039,7 @@ int tpamd_planner_set_discard_ik_rows(tpamd_planner_set *ps, int count, const in
 int tpamd_planner_set_ik_table_info(const tpamd_planner_set *ps, int planner, int32_t *first_row, int32_t *rows,
                                     int32_t *capacity) {
   if (!ps || planner < 0 || planner >= ps->S.B || !ps->cartesian) return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = refresh_table_counts(ps)) return rc;
   const bool has = ps->h_has[planner] && ps->h_rows[planner] > 0;
   if (first_row) *first_row = has ? ps->h_first_row[planner] : 0;
   if (rows) *rows = has ? ps->h_rows[planner] : 0;
@@ -5029,6 +5059,7 @@ int tpamd_planner_set_download_ik_rows(tpamd_planner_set *ps, int planner, int32
                                        double *ik_positions, double *jacobians, int capacity) {
   if (!ps || !first_row || !rows_live || planner < 0 || planner >= ps->S.B || !ps->cartesian)
     return TPAMD_E_INVALID_ARGUMENT;
+  if (int rc = refresh_table_counts(ps)) return rc;
   const bool has = ps->h_has[planner] && ps->h_rows[planner] > 0;
   const int R = has ? ps->h_rows[planner] - ps->h_first_row[planner] : 0;
   *first_row = has ? ps->h_first_row[planner] : 0;
@@ -5252,6 +5283,350 @@ int tpamd_planner_set_stop_trajectories_device(tpamd_planner_set *ps, int count,
   launch_stop_trajectories(ps->S.D, p, st);
   HIPCHK(hipGetLastError());
   return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- planner sets: state records
+// tpamd_planner_set_state_info / export_state_* / import_state_* / copy_planners (csrc/tpamd_state.h:
+// the record; csrc/tpamd_state.hip: the kernels).
+namespace {
+
+uint64_t double_bits(double x) {
+  uint64_t u;
+  std::memcpy(&u, &x, 8);
+  return u;
+}
+
+SetShape state_shape(const tpamd_planner_set *ps) {
+  SetShape s{};
+  s.kind = ps->cartesian ? kStateCartesian : kStateJoint;
+  s.num_dofs = ps->S.D; s.num_samples = ps->S.N; s.sampling_method = ps->S.method;
+  s.time_step_ns = ps->cfg.time_step_ns;
+  s.constraint_safety_bits = double_bits(ps->cfg.constraint_safety);
+  s.max_initial_velocity_error_bits = double_bits(ps->cfg.max_initial_velocity_error);
+  return s;
+}
+
+StateSetView state_view(const tpamd_planner_set *ps) {
+  const PlannerSetState &S = ps->S;
+  StateSetView v{};
+  v.B = S.B; v.D = S.D; v.N = S.N; v.K = S.K; v.pcap = ps->pcap; v.cap = ps->cap; v.tcap = ps->tcap;
+  v.table_cap = ps->cartesian ? ps->table_cap : 0;
+  v.shape = state_shape(ps);
+  v.knots = (double *)S.knots; v.cp = ps->d_cp; v.vmax = ps->d_vmax; v.amax = (double *)S.amax; v.iv = ps->d_iv;
+  v.delta = ps->d_delta; v.path_end = ps->d_path_end; v.vtrans = ps->d_vtrans; v.vrot = ps->d_vrot;
+  v.np = S.np; v.path_state = S.path_state; v.has_path = S.has_path; v.count = S.count;
+  v.initial_plan = S.initial_plan; v.planned_to_end = S.planned_to_end; v.target_reached = S.target_reached;
+  v.path_horizon = S.path_horizon; v.path_start = S.path_start; v.path_start_velocity = S.path_start_velocity;
+  v.path_time_start = S.path_time_start;
+  v.start_time_ns = S.start_time_ns; v.end_time_ns = S.end_time_ns; v.final_decel_start_ns = S.final_decel_start_ns;
+  v.w_time = ps->w_time; v.w_lei = ps->w_lei; v.t_first = S.t_first; v.t_count = S.t_count;
+  double *h[7] = {S.h_time, S.h_s, S.h_sd, S.h_sdd, S.h_q, S.h_qd, S.h_qdd};
+  double *t[7] = {S.t_time, S.t_s, S.t_sd, S.t_sdd, S.t_q, S.t_qd, S.t_qdd};
+  for (int i = 0; i < 7; i++) { v.h[i] = h[i]; v.t[i] = t[i]; }
+  v.tq = ps->d_tq; v.tJ = ps->d_tJ; v.rows = ps->d_rows; v.first_row = ps->d_first_row;
+  v.suspended = ps->cartesian ? ps->d_suspended : nullptr;
+  static_assert(sizeof(StateCheckDev) == sizeof(PlannerCheckDev), "check record layouts must agree");
+  v.check = ps->checking ? (StateCheckDev *)ps->d_check : nullptr;
+  return v;
+}
+
+// the largest record the set's capacities allow
+uint64_t state_bytes_bound(const tpamd_planner_set *ps) {
+  StateRecordHeader h{};
+  h.shape = state_shape(ps);
+  h.num_points = ps->cartesian ? 0 : ps->pcap;
+  h.history_count = ps->cap; h.trajectory_count = ps->tcap;
+  h.table_rows = ps->cartesian ? ps->table_cap : 0;
+  h.has_path = 1; h.initial_plan = 1;
+  return state_record_layout(h).bytes;
+}
+
+// workgroups per planner of the copy kernel (each moves 16 KiB per trip): one per 64 KiB a record
+// can have, 16 at the most
+int state_copy_blocks(const tpamd_planner_set *ps) {
+  return (int)std::min<uint64_t>(std::max<uint64_t>(state_bytes_bound(ps) >> 16, 1), 16);
+}
+
+// The layout kernel's per-planner scratch: room for every planner of the set from the first state
+// call on, so that the enqueued-only entries allocate nothing after it (no call lists more).
+int ensure_state_items(tpamd_planner_set *ps) {
+  const size_t need = (size_t)ps->S.B * sizeof(StateItem);
+  if (need <= ps->state_items.bytes) return 0;
+  if (ps->read_pending) HIPCHK(hipEventSynchronize(ps->ev_read));
+  return ps->state_items.reserve(need);
+}
+
+// ids of a host entry: in range, and each listed once where the call changes planners
+bool state_ids_ok(const tpamd_planner_set *ps, int count, const int32_t *ids, bool distinct) {
+  if (!ps || count < 0) return false;
+  const int B = ps->S.B;
+  if (count > B) return false;
+  if (!ids) return true;
+  std::vector<char> seen(distinct ? B : 0, 0);
+  for (int k = 0; k < count; k++) {
+    if (ids[k] < 0 || ids[k] >= B) return false;
+    if (distinct) {
+      if (seen[ids[k]]) return false;
+      seen[ids[k]] = 1;
+    }
+  }
+  return true;
+}
+
+// offsets[count + 1]: from a multiple of 16 on, non-decreasing, every one a multiple of 16
+bool state_offsets_ok(int count, const int64_t *offsets) {
+  if (!offsets || offsets[0] < 0) return false;
+  for (int k = 0; k <= count; k++)
+    if ((offsets[k] & 15) || (k && offsets[k] < offsets[k - 1])) return false;
+  return true;
+}
+
+// The host copies of a planner's path counts after an import that the host has seen.
+void state_bookkeeping(tpamd_planner_set *ps, int b, int num_points, int has_path, int table_rows, int first_row) {
+  if (num_points) ps->h_np[b] = num_points;
+  ps->h_has[b] = (char)has_path;
+  ps->h_stale[b] = 0;
+  ps->h_rows[b] = table_rows;
+  ps->h_first_row[b] = first_row;
+}
+
+// Capacity for records with these counts, before an import of the host kind.
+int state_grow_for(tpamd_planner_set *ps, int num_points, int history, int trajectory, int live_rows, hipStream_t st) {
+  if (num_points > ps->pcap)
+    if (int rc = ensure_pcap(ps, num_points, st)) return rc;
+  if (history > ps->cap)
+    if (int rc = grow_rows(ps, /*history=*/true, history, st)) return rc;
+  if (trajectory > ps->tcap)
+    if (int rc = grow_rows(ps, /*history=*/false, trajectory, st)) return rc;
+  if (ps->cartesian && live_rows > ps->table_cap)
+    if (int rc = ensure_table_cap(ps, live_rows, st)) return rc;
+  return 0;
+}
+
+// The sizes and counts of the listed planners (host ids, null: 0 .. count-1), on the null stream;
+// synchronises. count > 0.
+int state_info_run(tpamd_planner_set *ps, int count, const int32_t *ids, StateInfoDev *out) {
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  if (ensure_state_items(ps)) return TPAMD_E_HIP;
+  StateCall c{};
+  c.count = count;
+  c.items = (StateItem *)ps->state_items.p;
+  HostStage s;
+  s.up(&c.ids, ids, count);
+  s.down(&c.info, out, count);
+  if (int rc = s.upload(ps->state_buf, nullptr)) return rc;
+  launch_state_export(state_view(ps), c, 1, nullptr);
+  HIPCHK(hipGetLastError());
+  return s.download(nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpamd_planner_set_state_info(tpamd_planner_set *ps, int count, const int32_t *ids, tpamd_planner_state_info *info) {
+  static_assert(sizeof(tpamd_planner_state_info) == sizeof(StateInfoDev), "info layouts must agree");
+  static_assert(sizeof(tpamd_planner_summary) == sizeof(StateSummaryDev), "summary layouts must agree");
+  if (!state_ids_ok(ps, count, ids, false)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!info) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  return state_info_run(ps, count, ids, (StateInfoDev *)info);
+}
+
+size_t tpamd_planner_set_state_bytes_bound(const tpamd_planner_set *ps) {
+  return ps ? (size_t)state_bytes_bound(ps) : 0;
+}
+
+int tpamd_planner_set_export_state_device(tpamd_planner_set *ps, int count, const int32_t *ids, void *blob,
+                                          const int64_t *offsets, int32_t *status, void *hip_stream) {
+  if (!ps || count < 0 || count > ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!blob || !offsets || !status || ((uintptr_t)blob & 15)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (ensure_state_items(ps)) return TPAMD_E_HIP;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  StateCall c{};
+  c.count = count; c.ids = ids; c.blob = (unsigned char *)blob; c.offsets = (const long long *)offsets;
+  c.status = status; c.items = (StateItem *)ps->state_items.p;
+  launch_state_export(state_view(ps), c, state_copy_blocks(ps), st);
+  HIPCHK(hipGetLastError());
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+int tpamd_planner_set_export_state_host(tpamd_planner_set *ps, int count, const int32_t *ids, void *blob,
+                                        const int64_t *offsets, int32_t *status) {
+  if (!state_ids_ok(ps, count, ids, false)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!blob || !status || !state_offsets_ok(count, offsets)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  if (ensure_state_items(ps)) return TPAMD_E_HIP;
+  const size_t total = (size_t)offsets[count];
+  StateCall c{};
+  c.count = count;
+  c.items = (StateItem *)ps->state_items.p;
+  HostStage s;
+  s.up(&c.ids, ids, count);
+  s.up(&c.offsets, offsets, count + 1);
+  s.down(&c.status, status, count);
+  // the caller's bytes go up first: what no record covers comes back as it was, as the _device entry leaves it
+  if (total > 0) s.both(&c.blob, blob, total);
+  else s.scratch(&c.blob, 16);      // every slot is empty: the statuses alone
+  if (int rc = s.upload(ps->state_buf, nullptr)) return rc;
+  launch_state_export(state_view(ps), c, state_copy_blocks(ps), nullptr);
+  HIPCHK(hipGetLastError());
+  return s.download(nullptr);
+}
+
+int tpamd_planner_set_import_state_device(tpamd_planner_set *ps, int count, const int32_t *ids, const void *blob,
+                                          const int64_t *offsets, tpamd_planner_summary *summary, int32_t *status,
+                                          void *hip_stream) {
+  if (!ps || count < 0 || count > ps->S.B) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!blob || !offsets || !status || ((uintptr_t)blob & 15)) return TPAMD_E_INVALID_ARGUMENT;
+  TPAMD_ON_DEVICE(ps->e);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (ensure_state_items(ps)) return TPAMD_E_HIP;
+  if (readout_begin(ps, st)) return TPAMD_E_HIP;
+  StateCall c{};
+  c.count = count; c.ids = ids; c.blob = (unsigned char *)blob; c.offsets = (const long long *)offsets;
+  c.status = status; c.summary = (StateSummaryDev *)summary; c.items = (StateItem *)ps->state_items.p;
+  launch_state_import(state_view(ps), c, state_copy_blocks(ps), st);
+  HIPCHK(hipGetLastError());
+  // the outcome stays on the device: the host copies of the planners the call may have changed hold
+  // an upper bound (np) until they are read back (refresh_path_counts, refresh_table_counts)
+  const int B = ps->S.B;
+  for (int b = 0; b < (ids ? B : count); b++) {
+    ps->h_np[b] = std::max(ps->h_np[b], ps->pcap);
+    ps->h_stale[b] = 1;
+  }
+  if (ps->cartesian) ps->table_stale = true;
+  return readout_end(ps, st) ? TPAMD_E_HIP : 0;
+}
+
+int tpamd_planner_set_import_state_host(tpamd_planner_set *ps, int count, const int32_t *ids, const void *blob,
+                                        const int64_t *offsets, tpamd_planner_summary *summary, int32_t *status) {
+  if (!state_ids_ok(ps, count, ids, true)) return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!blob || !status || !state_offsets_ok(count, offsets)) return TPAMD_E_INVALID_ARGUMENT;
+  // every record before anything changes
+  const SetShape shape = state_shape(ps);
+  const unsigned char *bytes = (const unsigned char *)blob;
+  std::vector<StateRecordHeader> head(count);
+  int np = 0, hc = 0, tc = 0, live = 0;
+  for (int k = 0; k < count; k++) {
+    const unsigned char *rec = bytes + offsets[k];
+    if (state_record_validate(rec, (size_t)(offsets[k + 1] - offsets[k]), shape) != kStateOk)
+      return TPAMD_E_INVALID_ARGUMENT;
+    head[k] = state_record_header(rec);
+    np = std::max(np, head[k].num_points); hc = std::max(hc, head[k].history_count);
+    tc = std::max(tc, head[k].trajectory_count); live = std::max(live, head[k].table_rows - head[k].first_row);
+  }
+  TPAMD_ON_DEVICE(ps->e);
+  if (order_after_readouts(ps)) return TPAMD_E_HIP;
+  if (int rc = refresh_table_counts(ps)) return rc;
+  if (int rc = state_grow_for(ps, np, hc, tc, live, nullptr)) return rc;
+  if (ensure_state_items(ps)) return TPAMD_E_HIP;
+  const size_t total = (size_t)offsets[count];
+  std::vector<StateSummaryDev> sum(count);
+  StateCall c{};
+  c.count = count;
+  c.items = (StateItem *)ps->state_items.p;
+  HostStage s;
+  s.up(&c.ids, ids, count);
+  s.up(&c.offsets, offsets, count + 1);
+  s.down(&c.status, status, count);
+  s.down(&c.summary, sum.data(), count);
+  s.up(&c.blob, blob, total);
+  if (int rc = s.upload(ps->state_buf, nullptr)) return rc;
+  launch_state_import(state_view(ps), c, state_copy_blocks(ps), nullptr);
+  HIPCHK(hipGetLastError());
+  if (int rc = s.download(nullptr)) return rc;
+  if (summary) std::memcpy(summary, sum.data(), (size_t)count * sizeof(StateSummaryDev));
+  for (int k = 0; k < count; k++)
+    if (status[k] == TPAMD_PLAN_OK)
+      state_bookkeeping(ps, ids ? ids[k] : k, head[k].num_points, head[k].has_path, head[k].table_rows,
+                        head[k].first_row);
+  return 0;
+}
+
+int tpamd_planner_set_copy_planners(tpamd_planner_set *dst, const int32_t *dst_ids, tpamd_planner_set *src,
+                                    const int32_t *src_ids, int count, tpamd_planner_summary *summary,
+                                    int32_t *status) {
+  if (!dst || !src || !state_ids_ok(dst, count, dst_ids, true) || !state_ids_ok(src, count, src_ids, false))
+    return TPAMD_E_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (!status || !state_shape_equal(state_shape(dst), state_shape(src))) return TPAMD_E_INVALID_ARGUMENT;
+  std::vector<StateInfoDev> info(count);
+  std::vector<int64_t> offsets(count + 1, 0);
+  {
+    TPAMD_ON_DEVICE(src->e);
+    if (int rc = state_info_run(src, count, src_ids, info.data())) return rc;
+  }
+  int np = 0, hc = 0, tc = 0, live = 0;
+  for (int k = 0; k < count; k++) {
+    // a planner that refused (it waits for IK rows) gets a header's room: the import reports it
+    offsets[k + 1] = offsets[k] + (info[k].status == TPAMD_PLAN_OK ? info[k].bytes : (int64_t)sizeof(StateRecordHeader));
+    np = std::max(np, info[k].num_points); hc = std::max(hc, info[k].history_count);
+    tc = std::max(tc, info[k].trajectory_count); live = std::max(live, info[k].table_rows - info[k].first_row);
+  }
+  const size_t total = (size_t)offsets[count];
+  std::vector<int32_t> exported(count, 0);
+  if (dst->e->device != src->e->device) {
+    // the host pair: down from the source's device, up to the destination's
+    std::vector<unsigned char> blob(total);
+    if (int rc = tpamd_planner_set_export_state_host(src, count, src_ids, blob.data(), offsets.data(), exported.data()))
+      return rc;
+    for (int k = 0; k < count; k++)
+      if (exported[k] != TPAMD_PLAN_OK) {      // nothing changes unless every planner can move
+        std::memcpy(status, exported.data(), (size_t)count * 4);
+        return 0;
+      }
+    return tpamd_planner_set_import_state_host(dst, count, dst_ids, blob.data(), offsets.data(), summary, status);
+  }
+  TPAMD_ON_DEVICE(dst->e);
+  for (int k = 0; k < count; k++)
+    if (info[k].status != TPAMD_PLAN_OK) {       // nothing changes unless every planner can move
+      for (int j = 0; j < count; j++) status[j] = info[j].status;
+      return 0;
+    }
+  // through a scratch blob on the device, so that with dst == src any permutation of the ids works
+  if (order_after_readouts(dst) || order_after_readouts(src)) return TPAMD_E_HIP;
+  if (int rc = refresh_table_counts(dst)) return rc;
+  if (int rc = state_grow_for(dst, np, hc, tc, live, nullptr)) return rc;
+  if (ensure_state_items(src) || ensure_state_items(dst)) return TPAMD_E_HIP;
+  std::vector<StateSummaryDev> sum(count);
+  StateCall ex{}, im{};
+  ex.count = im.count = count;
+  ex.items = (StateItem *)src->state_items.p;
+  im.items = (StateItem *)dst->state_items.p;
+  int32_t *d_exported = nullptr;
+  HostStage s;
+  s.up(&ex.ids, src_ids, count);
+  s.up(&im.ids, dst_ids, count);
+  s.up(&ex.offsets, offsets.data(), count + 1);
+  s.down(&d_exported, exported.data(), count);
+  s.down(&im.status, status, count);
+  s.down(&im.summary, sum.data(), count);
+  s.scratch(&ex.blob, total);
+  if (int rc = s.upload(dst->state_buf, nullptr)) return rc;
+  ex.status = d_exported;
+  im.offsets = ex.offsets;
+  im.blob = ex.blob;
+  launch_state_export(state_view(src), ex, state_copy_blocks(src), nullptr);
+  launch_state_import(state_view(dst), im, state_copy_blocks(dst), nullptr);
+  HIPCHK(hipGetLastError());
+  if (int rc = s.download(nullptr)) return rc;
+  if (summary) std::memcpy(summary, sum.data(), (size_t)count * sizeof(StateSummaryDev));
+  for (int k = 0; k < count; k++)
+    if (status[k] == TPAMD_PLAN_OK)
+      state_bookkeeping(dst, dst_ids ? dst_ids[k] : k, info[k].num_points, info[k].has_path, info[k].table_rows,
+                        info[k].first_row);
+  return 0;
 }
 
 }  // extern "C"

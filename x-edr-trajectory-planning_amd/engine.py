@@ -18,7 +18,7 @@ _SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_k
             "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
             "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
             "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip", "tpamd_joint_fit.h", "tpamd_joint_fit.hip",
-            "tpamd_check.h", "tpamd_refine.h", "tpamd_refine.hip"]
+            "tpamd_check.h", "tpamd_refine.h", "tpamd_refine.hip", "tpamd_state.h", "tpamd_state.hip"]
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
@@ -61,7 +61,8 @@ def _compile(target, extra_flags, force, verbose):
              (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"]),
              (os.path.join(objdir, "retarget.o"), ["tpamd_retarget.hip"]),
              (os.path.join(objdir, "joint_fit.o"), ["tpamd_joint_fit.hip"]),
-             (os.path.join(objdir, "refine.o"), ["tpamd_refine.hip"])]
+             (os.path.join(objdir, "refine.o"), ["tpamd_refine.hip"]),
+             (os.path.join(objdir, "state.o"), ["tpamd_state.hip"])]
     for d, e in SWEEP_INSTANCES:
         units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
                       ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
@@ -256,6 +257,13 @@ class _PlanDeviceInfo(C.Structure):
 
 PLAN_RESOURCE_EXHAUSTED = 8     # TPAMD_PLAN_RESOURCE_EXHAUSTED
 
+# tpamd_planner_state_info (56 bytes)
+PLANNER_STATE_INFO_DTYPE = np.dtype([
+    ("bytes", np.int64), ("num_points", np.int32), ("history_count", np.int32), ("trajectory_count", np.int32),
+    ("table_rows", np.int32), ("first_row", np.int32), ("has_path", np.int32), ("path_state", np.int32),
+    ("initial_plan", np.int32), ("planned_to_end", np.int32), ("target_reached", np.int32),
+    ("trajectory_first", np.int32), ("status", np.int32)])
+
 # tpamd_planner_check (48 bytes)
 PLANNER_CHECK_DTYPE = np.dtype([
     ("windows", np.int32), ("violations", np.int32), ("last_window_violations", np.int32),
@@ -317,6 +325,10 @@ ABI_SYMBOLS = [
     "tpamd_planner_set_download_ik_rows", "tpamd_planner_set_ik_table_device_pointers",
     "tpamd_sample_ik_target_rows_host", "tpamd_sample_ik_target_rows_device",
     "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
+    "tpamd_planner_set_state_info", "tpamd_planner_set_state_bytes_bound",
+    "tpamd_planner_set_export_state_host", "tpamd_planner_set_export_state_device",
+    "tpamd_planner_set_import_state_host", "tpamd_planner_set_import_state_device",
+    "tpamd_planner_set_copy_planners",
     "tpamd_buffer_set_create", "tpamd_buffer_set_destroy", "tpamd_buffer_set_reserve", "tpamd_buffer_set_capacity",
     "tpamd_buffer_set_device_bytes",
     "tpamd_buffer_set_insert", "tpamd_buffer_set_insert_device",
@@ -583,6 +595,18 @@ def load_library():
     L.tpamd_compute_stopping_points_device.argtypes = [vp, i, i] + [vp] * 6 + [vp]
     L.tpamd_project_points_on_paths_host.argtypes = [vp, i, i] + [vp] * 8
     L.tpamd_project_points_on_paths_device.argtypes = [vp, i, i] + [vp] * 8 + [vp]
+    for name in ("tpamd_planner_set_state_info", "tpamd_planner_set_export_state_host",
+                 "tpamd_planner_set_export_state_device", "tpamd_planner_set_import_state_host",
+                 "tpamd_planner_set_import_state_device", "tpamd_planner_set_copy_planners"):
+        getattr(L, name).restype = i
+    L.tpamd_planner_set_state_info.argtypes = [vp, i, vp, vp]
+    L.tpamd_planner_set_state_bytes_bound.restype = C.c_size_t
+    L.tpamd_planner_set_state_bytes_bound.argtypes = [vp]
+    L.tpamd_planner_set_export_state_host.argtypes = [vp, i] + [vp] * 4
+    L.tpamd_planner_set_export_state_device.argtypes = [vp, i] + [vp] * 4 + [vp]
+    L.tpamd_planner_set_import_state_host.argtypes = [vp, i] + [vp] * 5
+    L.tpamd_planner_set_import_state_device.argtypes = [vp, i] + [vp] * 5 + [vp]
+    L.tpamd_planner_set_copy_planners.argtypes = [vp, vp, vp, vp, i, vp, vp]
     L.tpamd_planner_set_last_plan_bytes.restype = None
     L.tpamd_planner_set_last_plan_bytes.argtypes = [vp, vp, vp]
     L.tpamd_planner_set_device_bytes.restype = C.c_size_t
@@ -1645,6 +1669,7 @@ class PlannerSet:
         self._h = h
         self._num_samples = np.zeros(self.B, dtype=np.int64)    # GetNumTimeSamples after the last plan
         self._pending = None           # the PlanHandle of a plan_async whose result() has not run yet
+        self._imports = []             # device imports whose summaries have not been read yet
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1676,7 +1701,18 @@ class PlannerSet:
         if self._pending is not None:
             raise TpamdError("a plan_async call is in flight: its sample counts are on the device until "
                              "PlanHandle.result()")
+        self._settle_imports()
         return self._num_samples
+
+    def _settle_imports(self):
+        """The sample counts of planners that a device import_state changed, from the summaries
+        the call left on the device: synchronises those calls' streams, once."""
+        pending, self._imports = self._imports, []
+        for stream, summary, status, ids in pending:
+            stream.synchronize()
+            got = summary.cpu().numpy().view(PLANNER_SUMMARY_DTYPE)[:, 0]
+            ok = status.cpu().numpy() == 0
+            self._num_samples[ids[ok]] = got["num_samples"][ok]
 
     def _ids(self, ids, count=None):
         if ids is None:
@@ -2021,6 +2057,7 @@ class PlannerSet:
         """TrajectoryPlanner::Reset for the listed planners (None: all)."""
         ida, n = self._ids(ids)
         _check(self._lib.tpamd_planner_set_reset(self._handle(), n, _ptr(ida)), "tpamd_planner_set_reset")
+        self._settle_imports()
         if ida is None:
             self._num_samples[:] = 0
         else:
@@ -2098,6 +2135,7 @@ class PlannerSet:
 
     def _summary(self, out):
         import torch
+        self._imports = []             # a Plan of every planner supersedes them
         self._num_samples[:] = out["num_samples"]
         return {name: torch.from_numpy(np.ascontiguousarray(out[name]))
                 for name in PLANNER_SUMMARY_DTYPE.names if name != "reserved"}
@@ -2385,6 +2423,137 @@ class PlannerSet:
         for k in ("time", "q", "qd", "qdd"):
             out[k] = out[k][:rows]
         return out
+
+
+    # ------------------------------------------------------------ state records
+    def state_info(self, ids=None):
+        """The record size and the counts of each listed planner (all without ids)
+        (tpamd_planner_set_state_info): a numpy structured array of PLANNER_STATE_INFO_DTYPE.
+        Synchronises."""
+        ida, n = self._ids(ids)
+        out = np.zeros(max(n, 1), dtype=PLANNER_STATE_INFO_DTYPE)
+        _check(self._lib.tpamd_planner_set_state_info(self._handle(), n, _ptr(ida), _ptr(out)),
+               "tpamd_planner_set_state_info")
+        return out[:n]
+
+    @property
+    def state_bytes_bound(self):
+        """The largest state record the set's current capacities allow."""
+        return int(self._lib.tpamd_planner_set_state_bytes_bound(self._handle()))
+
+    def export_state(self, ids=None, out=None, offsets=None, stream=None):
+        """The state records of the listed planners (all without ids) packed into a CUDA uint8
+        tensor (tpamd_planner_set_export_state_device, enqueued on `stream`). Returns (blob, offsets):
+        record k is blob[offsets[k]:offsets[k + 1]], offsets a CPU int64 tensor [count + 1]; the
+        per-planner statuses are self.last_export_status (CUDA int32 [count]). Without `offsets` the records are sized exactly with state_info(), which
+        synchronises; with `offsets` (int64 [count + 1], multiples of 16, e.g. steps of
+        state_bytes_bound) nothing comes to the host and a planner whose slot is too small gets
+        PLAN_RESOURCE_EXHAUSTED. `out`: a contiguous CUDA uint8 tensor of at least offsets[-1]
+        bytes to write into."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ida, n = self._ids(ids)
+        if offsets is None:
+            sizes = self.state_info(ida)["bytes"] if ida is not None else self.state_info()["bytes"]
+            off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        else:
+            off = _host(offsets, np.int64, (n + 1,), "offsets")
+        total = int(off[-1]) if n else 0
+        if out is None:
+            out = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
+        elif (not _is_cuda(out) or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < total or
+              out.data_ptr() % 16):
+            raise TpamdError("out must be a contiguous, 16-byte aligned CUDA uint8 tensor of %d bytes" % total)
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        if st != torch.cuda.current_stream(dev):      # the fills and copies ran on the current stream
+            st.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(st):
+            idt = None if ida is None else torch.from_numpy(ida).to(dev)
+            offt = torch.from_numpy(off).to(dev)
+            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        _check(self._lib.tpamd_planner_set_export_state_device(
+            self._handle(), n, _ptr(idt), _ptr(out), _ptr(offt), _ptr(status), _stream_ptr(st)),
+            "tpamd_planner_set_export_state_device")
+        self.last_export_status = status
+        self._export_keep = (idt, offt)      # alive until the stream has read them
+        return out[:total], torch.from_numpy(off)
+
+    def import_state(self, blob, offsets, ids=None, stream=None):
+        """The listed planners (0 .. count-1 without ids, each listed once) take the states of the
+        records blob[offsets[k]:offsets[k + 1]]. A CUDA `blob` goes through
+        tpamd_planner_set_import_state_device, enqueued on `stream`: nothing is allocated, a record
+        that needs more capacity than reserve() has provided gets PLAN_RESOURCE_EXHAUSTED and its
+        planner keeps its state; returns dict status (CUDA int32 [count]) and summary (CUDA uint8
+        [count][56], PLANNER_SUMMARY_DTYPE); the host-side sample counts are refreshed from that
+        summary tensor by the first method that needs them (download_trajectories, stop_trajectories
+        without a capacity), which synchronises the import's stream then. A host `blob` (numpy uint8 or CPU tensor) goes through
+        tpamd_planner_set_import_state_host, which validates every record first, grows the set as
+        needed and synchronises; returns dict status (CPU int32) plus the summary fields of plan()."""
+        import torch
+        off = _host(offsets, np.int64, what="offsets").reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        if self._pending is not None:
+            raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
+        total = int(off[-1]) if n else 0
+        if _is_cuda(blob):
+            dev = blob.device
+            if blob.dtype != torch.uint8 or not blob.is_contiguous() or blob.numel() < total or blob.data_ptr() % 16:
+                raise TpamdError("blob must be a contiguous, 16-byte aligned CUDA uint8 tensor of %d bytes" % total)
+            st = torch.cuda.current_stream(dev) if stream is None else stream
+            if st != torch.cuda.current_stream(dev):
+                st.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(st):
+                idt = None if ida is None else torch.from_numpy(ida).to(dev)
+                offt = offsets if (_is_cuda(offsets) and offsets.dtype == torch.int64 and offsets.is_contiguous()) \
+                    else torch.from_numpy(off).to(dev)
+                status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+                summary = torch.zeros((n, PLANNER_SUMMARY_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            _check(self._lib.tpamd_planner_set_import_state_device(
+                self._handle(), n, _ptr(idt), _ptr(blob), _ptr(offt), _ptr(summary), _ptr(status), _stream_ptr(st)),
+                "tpamd_planner_set_import_state_device")
+            self._imports.append((st, summary, status, np.arange(n) if ida is None else ida.astype(np.int64)))
+            return dict(status=status, summary=summary, _keep=(idt, offt, blob))
+        b = _host(blob, np.uint8, what="blob").reshape(-1)
+        if b.shape[0] < total:
+            raise TpamdError("blob has %d bytes, offsets end at %d" % (b.shape[0], total))
+        status = np.full(n, -1, dtype=np.int32)
+        out = np.zeros(max(n, 1), dtype=PLANNER_SUMMARY_DTYPE)
+        _check(self._lib.tpamd_planner_set_import_state_host(
+            self._handle(), n, _ptr(ida), _ptr(b), _ptr(off), out.ctypes.data, _ptr(status)),
+            "tpamd_planner_set_import_state_host")
+        return self._state_result(out[:n], status, ida)
+
+    def _state_result(self, out, status, ida):
+        import torch
+        self._settle_imports()         # an earlier device import first: this call is the later one
+        sel = np.arange(out.shape[0]) if ida is None else ida
+        ok = status == 0
+        self._num_samples[sel[ok]] = out["num_samples"][ok]
+        res = {name: torch.from_numpy(np.ascontiguousarray(out[name]))
+               for name in PLANNER_SUMMARY_DTYPE.names if name != "reserved"}
+        res["status"] = torch.from_numpy(status)
+        return res
+
+    def copy_from(self, other, src_ids=None, dst_ids=None):
+        """Planner src_ids[k] of `other` becomes planner dst_ids[k] of this set
+        (tpamd_planner_set_copy_planners; None: 0 .. count-1, count from the ids given, else the
+        smaller set's size). `other` may be this set: any permutation is legal. Grows this set as
+        needed; synchronises. Returns dict status (CPU int32) plus the summary fields of plan()."""
+        if self._pending is not None or other._pending is not None:
+            raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
+        src = None if src_ids is None else _host(src_ids, np.int32, what="src_ids").reshape(-1)
+        dst = None if dst_ids is None else _host(dst_ids, np.int32, what="dst_ids").reshape(-1)
+        n = src.shape[0] if src is not None else (dst.shape[0] if dst is not None else min(self.B, other.B))
+        if (src is not None and src.shape[0] != n) or (dst is not None and dst.shape[0] != n):
+            raise TpamdError("src_ids and dst_ids must list the same number of planners")
+        status = np.full(n, -1, dtype=np.int32)
+        out = np.zeros(max(n, 1), dtype=PLANNER_SUMMARY_DTYPE)
+        _check(self._lib.tpamd_planner_set_copy_planners(
+            self._handle(), _ptr(dst), other._handle(), _ptr(src), n, out.ctypes.data, _ptr(status)),
+            "tpamd_planner_set_copy_planners")
+        return self._state_result(out[:n], status, dst)
 
 
 class PlanHandle:

@@ -35,6 +35,11 @@ class PathTimingTrajectoryOptions : public TrajectoryPlannerOptions<PathTimingTr
   TimeSamplingMethod time_sampling_method_ = TimeSamplingMethod::kUniformlyInTime;
 };
 
+class PathTimingTrajectory;
+Status PlannerStateFromHost(const PathTimingTrajectory &planner, std::vector<unsigned char> *record,
+                            double constraint_safety);
+Status PlannerStateToHost(const void *record, size_t len, PathTimingTrajectory *planner);
+
 class PathTimingTrajectory : public TrajectoryPlanner {
  public:
   explicit PathTimingTrajectory(const PathTimingTrajectoryOptions &options);
@@ -76,6 +81,10 @@ class PathTimingTrajectory : public TrajectoryPlanner {
   void ResetDerived() override;
 
  private:
+  // the planner's state as a record and back (planner_state.h)
+  friend Status PlannerStateFromHost(const PathTimingTrajectory &planner, std::vector<unsigned char> *record,
+                                     double constraint_safety);
+  friend Status PlannerStateToHost(const void *record, size_t len, PathTimingTrajectory *planner);
   void UpdatePathTrackingStatus();
   Status HandleTimeArguments(Time start);
   // One planning window (path_timing_trajectory.cc:307-475) in three phases, so that the

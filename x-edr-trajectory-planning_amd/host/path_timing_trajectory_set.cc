@@ -1,4 +1,5 @@
 #include "path_timing_trajectory_set.h"
+#include "planner_state.h"
 
 #include <chrono>
 
@@ -993,6 +994,121 @@ std::vector<Status> PathTimingTrajectorySet::RetargetWaypointPaths(
     }
   }
   return result;
+}
+
+namespace {
+Status StateStatus(int32_t st) {
+  switch (st) {
+    case TPAMD_PLAN_OK: return OkStatus();
+    case TPAMD_PLAN_FAILED_PRECONDITION: return FailedPreconditionError("the planner waits for IK rows");
+    case TPAMD_PLAN_RESOURCE_EXHAUSTED: return ::tpamd::compat::ResourceExhaustedError("the record does not fit");
+    case TPAMD_PLAN_INVALID_ARGUMENT: return InvalidArgumentError("no such planner, or not a record for this set");
+    default: return InternalError("state transfer failed");
+  }
+}
+Status StateCallStatus(int rc) {
+  return rc == TPAMD_E_INVALID_ARGUMENT ? InvalidArgumentError(tpamd_error_string(rc)) : InternalError(tpamd_error_string(rc));
+}
+}  // namespace
+
+Status PathTimingTrajectorySet::ExportPlanners(const std::vector<size_t> &planners, PlannerStateBlob *blob) {
+  if (!init_status_.ok()) return init_status_;
+  if (!blob) return InvalidArgumentError("no blob");
+  const size_t n = planners.size();
+  blob->bytes.clear();
+  blob->offsets.assign(n + 1, 0);
+  blob->status.assign(n, OkStatus());
+  if (n == 0) return OkStatus();
+  std::vector<int32_t> ids(n), st(n);
+  for (size_t k = 0; k < n; k++) {
+    if (planners[k] >= num_planners_) return InvalidArgumentError("no such planner");
+    ids[k] = (int32_t)planners[k];
+  }
+  std::vector<tpamd_planner_state_info> info(n);
+  int rc = tpamd_planner_set_state_info(set_, (int)n, ids.data(), info.data());
+  if (rc != 0) return StateCallStatus(rc);
+  // a planner that refuses (it waits for rows) gets no room: the export reports it
+  for (size_t k = 0; k < n; k++) blob->offsets[k + 1] = blob->offsets[k] + (info[k].status == TPAMD_PLAN_OK ? info[k].bytes : 0);
+  blob->bytes.assign((size_t)blob->offsets[n] + 16, 0);
+  rc = tpamd_planner_set_export_state_host(set_, (int)n, ids.data(), blob->bytes.data(), blob->offsets.data(), st.data());
+  if (rc != 0) return StateCallStatus(rc);
+  blob->bytes.resize((size_t)blob->offsets[n]);
+  for (size_t k = 0; k < n; k++) blob->status[k] = StateStatus(st[k]);
+  return OkStatus();
+}
+
+void PathTimingTrajectorySet::TakeImported(const std::vector<size_t> &planners, const std::vector<int32_t> &status,
+                                           const std::vector<tpamd_planner_summary> &summary,
+                                           std::vector<Status> *result) {
+  for (size_t k = 0; k < planners.size(); k++) {
+    (*result)[k] = StateStatus(status[k]);
+    if (status[k] != TPAMD_PLAN_OK) continue;
+    summary_[planners[k]] = summary[k];
+    ForgetStreamSource(planners[k]);
+  }
+}
+
+std::vector<Status> PathTimingTrajectorySet::ImportPlanners(const std::vector<size_t> &planners,
+                                                            const PlannerStateBlob &blob) {
+  const size_t n = planners.size();
+  if (!init_status_.ok()) return std::vector<Status>(n, init_status_);
+  std::vector<Status> result(n, OkStatus());
+  if (n == 0) return result;
+  if (blob.offsets.size() != n + 1 || blob.offsets[0] < 0 || (size_t)blob.offsets[n] > blob.bytes.size())
+    return std::vector<Status>(n, InvalidArgumentError("the blob does not hold one record per listed planner"));
+  std::vector<int32_t> ids(n), st(n, -1);
+  for (size_t k = 0; k < n; k++) ids[k] = planners[k] < num_planners_ ? (int32_t)planners[k] : -1;
+  std::vector<tpamd_planner_summary> summary(n);
+  const int rc = tpamd_planner_set_import_state_host(set_, (int)n, ids.data(), blob.bytes.data(), blob.offsets.data(),
+                                                     summary.data(), st.data());
+  if (rc != 0) return std::vector<Status>(n, StateCallStatus(rc));
+  TakeImported(planners, st, summary, &result);
+  return result;
+}
+
+std::vector<Status> PathTimingTrajectorySet::CopyPlanners(PathTimingTrajectorySet *dst,
+                                                          const std::vector<size_t> &dst_planners,
+                                                          PathTimingTrajectorySet *src,
+                                                          const std::vector<size_t> &src_planners) {
+  const size_t n = dst_planners.size();
+  if (!dst || !src || src_planners.size() != n)
+    return std::vector<Status>(n, InvalidArgumentError("two sets and as many source as destination planners"));
+  if (!dst->init_status_.ok()) return std::vector<Status>(n, dst->init_status_);
+  if (!src->init_status_.ok()) return std::vector<Status>(n, src->init_status_);
+  std::vector<Status> result(n, OkStatus());
+  if (n == 0) return result;
+  std::vector<int32_t> di(n), si(n), st(n, -1);
+  for (size_t k = 0; k < n; k++) {
+    di[k] = dst_planners[k] < dst->num_planners_ ? (int32_t)dst_planners[k] : -1;
+    si[k] = src_planners[k] < src->num_planners_ ? (int32_t)src_planners[k] : -1;
+  }
+  std::vector<tpamd_planner_summary> summary(n);
+  const int rc = tpamd_planner_set_copy_planners(dst->set_, di.data(), src->set_, si.data(), (int)n, summary.data(), st.data());
+  if (rc != 0) return std::vector<Status>(n, StateCallStatus(rc));
+  dst->TakeImported(dst_planners, st, summary, &result);
+  return result;
+}
+
+Status PathTimingTrajectorySet::AdoptPlanner(size_t slot, const PathTimingTrajectory &planner) {
+  if (!init_status_.ok()) return init_status_;
+  if (cartesian_) return FailedPreconditionError("a Cartesian set takes IK tables");
+  if (slot >= num_planners_) return InvalidArgumentError("no such planner");
+  PlannerStateBlob blob;
+  if (Status st = PlannerStateFromHost(planner, &blob.bytes, constraint_safety_); !st.ok()) return st;
+  blob.offsets = {0, (int64_t)blob.bytes.size()};
+  return ImportPlanners({slot}, blob)[0];
+}
+
+Status PathTimingTrajectorySet::ReleasePlanner(size_t slot, PathTimingTrajectory *planner) {
+  if (!init_status_.ok()) return init_status_;
+  if (cartesian_) return FailedPreconditionError("a Cartesian set's planners have no host form");
+  if (slot >= num_planners_ || !planner) return InvalidArgumentError("no such planner");
+  PlannerStateBlob blob;
+  if (Status st = ExportPlanners({slot}, &blob); !st.ok()) return st;
+  if (!blob.status[0].ok()) return blob.status[0];
+  if (Status st = PlannerStateToHost(blob.bytes.data(), blob.bytes.size(), planner); !st.ok()) return st;
+  Reset(slot);
+  return OkStatus();
 }
 
 Status PathTimingTrajectorySet::GetPath(size_t planner, std::vector<double> *knots,

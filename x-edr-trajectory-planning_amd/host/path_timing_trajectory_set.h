@@ -336,6 +336,41 @@ class PathTimingTrajectorySet {
   // Bytes the last Plan call moved over PCIe, both directions.
   size_t LastPlanBytesOverPcie() const;
   size_t DeviceBytes() const;
+  // ---- moving planners between sets (tpamd_planner_set_export_state_host / _import_state_host /
+  // _copy_planners; csrc/tpamd_state.h states the record format). A planner that was moved continues
+  // bit for bit as it would have where it was. The receiving set must have the same kind, dofs, path
+  // samples, sampling method, time step, constraint safety and initial-velocity tolerance; its
+  // number of planners and capacities may differ (it grows as needed). A planner that waits for IK
+  // rows (a suspended PlanStreaming) is refused with a failed precondition.
+  struct PlannerStateBlob {
+    std::vector<unsigned char> bytes;    // the records, packed
+    std::vector<int64_t> offsets;        // [planners + 1]: record k is bytes[offsets[k] .. offsets[k + 1])
+    std::vector<Status> status;          // [planners]: per planner, what ExportPlanners found
+  };
+  // The records of the listed planners, on the host. Synchronises.
+  Status ExportPlanners(const std::vector<size_t> &planners, PlannerStateBlob *blob);
+  // The listed planners (each listed once) take the records of `blob`, in order. Every id and record
+  // is checked before anything changes (an invalid-argument status for all of them then). The
+  // getters (GetEndTime, GetNumTimeSamples, ...) of a planner that took a record answer from it. A
+  // planner that took a record loses its stream source: where the rows of a streamed Cartesian table
+  // come from (the path object or the device fit) is this object's knowledge, not the record's, so a
+  // PlanStreaming that needs further rows for it fails until it is given a path again.
+  std::vector<Status> ImportPlanners(const std::vector<size_t> &planners, const PlannerStateBlob &blob);
+  // Planner src_planners[k] of src becomes planner dst_planners[k] of dst; dst may be src (any
+  // permutation). On one device nothing crosses PCIe but sizes and summaries; sets on different
+  // devices go through host memory. Getters and stream sources of dst as for ImportPlanners.
+  static std::vector<Status> CopyPlanners(PathTimingTrajectorySet *dst, const std::vector<size_t> &dst_planners,
+                                          PathTimingTrajectorySet *src, const std::vector<size_t> &src_planners);
+  // A planner written against the reference's API joins the set, and leaves it, without starting
+  // from rest (planner_state.h: the record of a host PathTimingTrajectory with a
+  // TimeableJointSplinePath). AdoptPlanner: planner `slot` takes the host planner's whole state
+  // (path, limits, history, scalars, trajectory) and continues bit for bit as the host planner
+  // would; the host planner is not changed. The options must agree (dofs, path samples, sampling
+  // method, time step, initial-velocity tolerance, and the path's constraint safety with the set's).
+  // ReleasePlanner: `planner` takes the state of planner `slot` (PlannerStateToHost says what a
+  // record cannot restore), and the slot is reset. Joint sets only.
+  Status AdoptPlanner(size_t slot, const PathTimingTrajectory &planner);
+  Status ReleasePlanner(size_t slot, PathTimingTrajectory *planner);
   // The C-ABI set and its engine, for objects that work on the resident trajectories in place
   // (TrajectoryBufferSet::InsertFromPlannerSet). They stay owned by this set.
   tpamd_planner_set *native_handle() const { return set_; }
@@ -374,6 +409,8 @@ class PathTimingTrajectorySet {
   Status ExtendOnDevice(const std::vector<int32_t> &need_first, const std::vector<int32_t> &need_count,
                         std::vector<Status> *failed);
   std::vector<Status> PlanStatuses() const;
+  void TakeImported(const std::vector<size_t> &planners, const std::vector<int32_t> &status,
+                    const std::vector<tpamd_planner_summary> &summary, std::vector<Status> *result);
 };
 
 }  // namespace trajectory_planning

@@ -14,6 +14,11 @@ namespace trajectory_planning {
 
 class JointPathOptions : public PathOptions<JointPathOptions> {};
 
+class PathTimingTrajectory;
+Status PlannerStateFromHost(const PathTimingTrajectory &planner, std::vector<unsigned char> *record,
+                            double constraint_safety);
+Status PlannerStateToHost(const void *record, size_t len, PathTimingTrajectory *planner);
+
 class TimeableJointSplinePath : public TimeablePath {
  public:
   explicit TimeableJointSplinePath(const JointPathOptions &options);
@@ -70,6 +75,10 @@ class TimeableJointSplinePath : public TimeablePath {
                                       std::vector<VectorXd> *control_points);
 
  private:
+  // the state record of the planner that holds this path (planner_state.h)
+  friend Status PlannerStateFromHost(const PathTimingTrajectory &planner, std::vector<unsigned char> *record,
+                                     double constraint_safety);
+  friend Status PlannerStateToHost(const void *record, size_t len, PathTimingTrajectory *planner);
   Status FitSplineToWaypoints();
   void PackControlPoints();
 
