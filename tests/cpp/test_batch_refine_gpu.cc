@@ -19,17 +19,9 @@
 #include "../../include/tpamd.h"
 #include "../../x-edr-trajectory-planning_amd/host/batch_path_timing.h"
 #include "../../x-edr-trajectory-planning_amd/host/batch_waypoint_timing.h"
+#include "test_support.h"
 
 using namespace trajectory_planning;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
 
 template <class T>
 static bool Same(const std::vector<T> &a, const std::vector<T> &b) {

@@ -47,7 +47,7 @@ static void TestDiscardFamily(Method method) {
     for (int b = 0; b < B; b++) {
       const Status ms = mirrors[b]->Plan(st[b], Milliseconds(750));
       CHECK(ms.ok() && sd[b].ok() && sw[b].ok());
-      CHECK(CompareOne(disc, b, *mirrors[b], &td[b]) == 0 && CompareOne(twin, b, *mirrors[b], &tt[b]) == 0);
+      CHECK(CompareOne(disc, b, *mirrors[b], nullptr, &td[b]) == 0 && CompareOne(twin, b, *mirrors[b], nullptr, &tt[b]) == 0);
       const bool same = disc.GetNumTimeSamples(b) == twin.GetNumTimeSamples(b) &&
                         ToUnixNanos(disc.GetEndTime(b)) == ToUnixNanos(twin.GetEndTime(b)) &&
                         ToUnixNanos(disc.GetFinalDecelStart(b)) == ToUnixNanos(twin.GetFinalDecelStart(b)) &&

@@ -15,17 +15,9 @@
 #include <vector>
 
 #include "../../x-edr-trajectory-planning_amd/csrc/tpamd_cartesian_window.h"
+#include "test_support.h"
 
 using namespace tpamd;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
 
 struct Rng {
   unsigned long long s;

@@ -14,17 +14,9 @@
 #include "../../oracle/tp_oracle.h"
 #include "../../x-edr-trajectory-planning_amd/host/batch_cartesian_timing.h"
 #include "../../x-edr-trajectory-planning_amd/host/engine_handle.h"
+#include "test_support.h"
 
 using namespace trajectory_planning;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
 
 static bool Same(const double *a, const double *b, size_t n) { return std::memcmp(a, b, n * 8) == 0; }
 

@@ -27,6 +27,9 @@
 #include "../../x-edr-trajectory-planning_amd/host/trajectory_buffer.h"
 #include "../../x-edr-trajectory-planning_amd/host/trajectory_buffer_set.h"
 
+#define TEST_SUPPORT_MIRROR
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::AngleAxisd;
 using tpamd::compat::FromUnixNanos;
@@ -38,28 +41,9 @@ using tpamd::compat::ToUnixNanos;
 using tpamd::compat::Vector3d;
 using Method = PathTimingTrajectoryOptions::TimeSamplingMethod;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
-
-static const int64_t kMs = 1000000;
 static const int D = 7, N = 400;
 static int g_ik_calls = 0;
 
-static bool SameBits(const std::vector<double> &a, const std::vector<double> &b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * 8) == 0);
-}
-static bool SameBits(const double *a, const double *b, size_t n) { return n == 0 || std::memcmp(a, b, n * 8) == 0; }
-static std::vector<double> Flatten(const std::vector<VectorXd> &v) {
-  std::vector<double> r;
-  for (const auto &x : v) r.insert(r.end(), x.begin(), x.end());
-  return r;
-}
 static int Code(const Status &s) {
   switch (s.code()) {
     case StatusCode::kOk: return TPAMD_PLAN_OK;
@@ -140,23 +124,6 @@ static std::shared_ptr<TimeableCartesianSplinePath> MakePath(int shape, double f
   CHECK(path->SetMaxCartesianVelocity(0.35 + 0.05 * shape, 0.9).ok());
   CHECK(path->SetWaypoints({poses.data(), poses.size()}, {joints.data(), joints.size()}).ok());
   return path;
-}
-
-static int CompareOne(const PathTimingTrajectorySet &set, int b, const PathTimingTrajectory &m, PlannedTrajectory *t) {
-  int bad = 0;
-  if (set.GetNumTimeSamples(b) != m.GetNumTimeSamples()) return 1;
-  bad |= (ToUnixNanos(set.GetEndTime(b)) != ToUnixNanos(m.GetEndTime())) << 1;
-  bad |= (ToUnixNanos(set.GetStartTime(b)) != ToUnixNanos(m.GetStartTime())) << 2;
-  bad |= (ToUnixNanos(set.GetFinalDecelStart(b)) != ToUnixNanos(m.GetFinalDecelStart())) << 3;
-  bad |= (set.IsTrajectoryAtEnd(b) != m.IsTrajectoryAtEnd()) << 4;
-  if (!set.GetTrajectory(b, t).ok()) return bad | (1 << 5);
-  bad |= !SameBits(t->time, m.GetTime()) << 6;
-  bad |= !SameBits(t->path_parameter, m.GetPathParameters()) << 7;
-  bad |= !SameBits(t->path_parameter_derivative, m.GetPathParameterDerivatives()) << 8;
-  bad |= !SameBits(t->positions, Flatten(m.GetPositions())) << 9;
-  bad |= !SameBits(t->velocities, Flatten(m.GetVelocities())) << 10;
-  bad |= !SameBits(t->accelerations, Flatten(m.GetAccelerations())) << 11;
-  return bad;
 }
 
 // test 7 on the set as it stands after a Plan
@@ -341,7 +308,7 @@ static void TestMirrorFamily(Method method) {
     for (int b = 0; b < B; b++) {
       const Status ms = mirrors[b]->Plan(st[b], Milliseconds(750));
       CHECK(ms.ok() && sd[b].ok());
-      const int bad = CompareOne(set, b, *mirrors[b], &tr[b]);
+      const int bad = CompareOne(set, b, *mirrors[b], nullptr, &tr[b]);
       CHECK(bad == 0);
       if (bad && ++reported <= 10) std::printf("  %s step %d planner %d: differences 0x%x\n", skip ? "skip" : "uniform", step, b, bad);
       compared++;

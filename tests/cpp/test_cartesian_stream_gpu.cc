@@ -28,18 +28,8 @@
 
 #include "../../include/tpamd.h"
 #include "../../oracle/tp_oracle.h"
+#include "test_support.h"
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
-#define HIP_OK(expr) CHECK((expr) == hipSuccess)
-
-static const int64_t kMs = 1000000;
 static const int kN = 64, kB = 32;
 static const double kSafety = 0.8, kMaxIvError = 1e-3;
 static const int kMaxIter = 10000;

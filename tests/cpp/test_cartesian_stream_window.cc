@@ -19,21 +19,7 @@
 #include <vector>
 
 #include "../../x-edr-trajectory-planning_amd/csrc/tpamd_cartesian_window.h"
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
-
-static unsigned long long g_seed = 1;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
+#include "test_support.h"
 
 // :671-674
 static int PathIkIndex(double parameter, double delta) { return (int)std::round(parameter / delta); }

@@ -23,6 +23,9 @@
 #include "../../x-edr-trajectory-planning_amd/host/engine_handle.h"
 #include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
 
+#define TEST_SUPPORT_SEED 20261018ULL
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
 using tpamd::compat::Milliseconds;
@@ -32,25 +35,9 @@ using tpamd::compat::StatusCode;
 using tpamd::compat::ToUnixNanos;
 using tpamd::compat::Vector3d;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
-
-static const int64_t kMs = 1000000;
 static const int kB = 6, kN = 64;
 static const double kDelta = 0.1, kSafety = 0.8, kMaxIvError = 1e-3;
 static const int kMaxIter = 10000;
-
-static unsigned long long g_seed = 20261018ULL;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
 
 struct Goal {
   std::vector<Pose3d> poses;
@@ -112,10 +99,6 @@ static Table HostTable(tpamd_engine *e, const Goal &g, int D, double tr, double 
     t.J.insert(t.J.end(), g.jacobian.begin(), g.jacobian.end());
   }
   return t;
-}
-
-static bool SameBits(const std::vector<double> &a, const double *b, size_t n) {
-  return a.size() == n && (n == 0 || std::memcmp(a.data(), b, n * 8) == 0);
 }
 
 static int Compare(const PathTimingTrajectorySet &set, int b, const tpo_planner *p, int D) {

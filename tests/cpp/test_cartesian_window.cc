@@ -14,21 +14,8 @@
 
 #include "../../oracle/tp_oracle.h"
 #include "../../x-edr-trajectory-planning_amd/csrc/tpamd_cartesian_window.h"
+#include "test_support.h"
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    if (!(cond)) {                                                                  \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      g_fail++;                                                                     \
-    }                                                                               \
-  } while (0)
-
-static unsigned long long g_seed = 1;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
 static bool Same(const double *a, const double *b, size_t n) { return std::memcmp(a, b, n * 8) == 0; }
 
 // tp_oracle_plan.c:308-310

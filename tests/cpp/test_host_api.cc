@@ -14,17 +14,12 @@
 #include "../../x-edr-trajectory-planning_amd/host/time_optimal_path_timing.h"
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_cartesian_spline.h"
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
+#include "test_support.h"
 
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixSeconds;
 using tpamd::compat::Milliseconds;
 using tpamd::compat::Seconds;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                          \
-  do {                                                                       \
-    if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); g_fail++; } \
-  } while (0)
 
 using Constraint = TimeOptimalPathProfile::Constraint;
 constexpr double kTiny = 2.220446049250313e-16 * 1e5;

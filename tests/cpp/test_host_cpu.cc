@@ -11,15 +11,10 @@
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_cartesian_spline.h"
 #include "../../x-edr-trajectory-planning_amd/host/time_optimal_path_timing.h"
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
+#include "test_support.h"
 
 using namespace trajectory_planning;
 using tpamd::compat::StatusCode;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                          \
-  do {                                                                       \
-    if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); g_fail++; } \
-  } while (0)
 
 static VectorXd V2(double x, double y) { VectorXd v(2); v[0] = x; v[1] = y; return v; }
 static bool Near(const VectorXd &a, const VectorXd &b, double tol) {

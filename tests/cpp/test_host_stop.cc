@@ -13,6 +13,7 @@
 #include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory.h"
 #include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
+#include "test_support.h"
 
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
@@ -20,13 +21,6 @@ using tpamd::compat::Milliseconds;
 using tpamd::compat::StatusCode;
 using Method = PathTimingTrajectoryOptions::TimeSamplingMethod;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                        \
-  do {                                                                                     \
-    if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); g_fail++; } \
-  } while (0)
-
-static const int64_t kMs = 1000000;
 static Time TimeFromSec(double s) { return FromUnixNanos((int64_t)(s * 1e9)); }
 static VectorXd V3(double x, double y, double z) { VectorXd v(3); v[0] = x; v[1] = y; v[2] = z; return v; }
 static bool SameBits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }

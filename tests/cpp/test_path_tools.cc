@@ -25,26 +25,14 @@
 #include "../../x-edr-trajectory-planning_amd/csrc/tpamd_retarget.h"
 #include "../../x-edr-trajectory-planning_amd/host/path_tools.h"
 
+#define TEST_SUPPORT_SEED 20261019ULL
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using ::tpamd::compat::StatusCode;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-
-static unsigned long long g_seed = 20261019ULL;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
 static double Uniform(double lo, double hi) { return lo + (hi - lo) * Rnd(); }
 
-static bool SameBits(const double *a, const double *b, size_t n) { return n == 0 || std::memcmp(a, b, n * 8) == 0; }
 static void Put(FILE *f, const double *v, size_t n) {
   for (size_t i = 0; i < n; i++) std::fprintf(f, " %a", v[i]);
 }

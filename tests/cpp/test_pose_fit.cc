@@ -28,15 +28,7 @@
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
 using namespace trajectory_planning;
 #endif
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
+#include "test_support.h"
 
 static const char *kFamilies[] = {"random", "identical", "tiny", "near_pi", "antipodal", "repeated_translation",
                                   "short", "empty", "golden"};
@@ -69,8 +61,6 @@ static bool ReadCases(const char *file, std::vector<Case> *cases) {
   std::fclose(f);
   return ok;
 }
-
-static bool SameBits(const double *a, const double *b, size_t n) { return n == 0 || std::memcmp(a, b, n * 8) == 0; }
 
 int main(int argc, char **argv) {
   if (argc < 2) {

@@ -19,24 +19,11 @@
 #include "../../x-edr-trajectory-planning_amd/csrc/tpamd_switch.h"
 #include "../../x-edr-trajectory-planning_amd/host/trajectory_planner.h"
 
+#define TEST_SUPPORT_SEED 20261016ULL
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::StatusCode;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-
-static unsigned long long g_seed = 20261016ULL;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
-static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
 
 static int PlanCode(const tpamd::compat::Status &s) {
   switch (s.code()) {

@@ -28,24 +28,9 @@
 
 #include "../../include/tpamd.h"
 #include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
+#include "test_support.h"
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-#define HIP_OK(expr) CHECK((expr) == hipSuccess)
-
-static const int64_t kMs = 1000000;
 static const int kN = 100;
-static unsigned long long g_seed = 1;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
 
 template <typename T>
 struct Dev {       // a device array with a host image

@@ -35,6 +35,9 @@
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
 #include "../../x-edr-trajectory-planning_amd/host/trajectory_buffer.h"
 
+#define TEST_SUPPORT_MIRROR
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
 using tpamd::compat::Milliseconds;
@@ -43,33 +46,7 @@ using tpamd::compat::StatusCode;
 using tpamd::compat::ToUnixNanos;
 using Method = PathTimingTrajectoryOptions::TimeSamplingMethod;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-#define HIP_OK(expr) CHECK((expr) == hipSuccess)
-
-static const int64_t kMs = 1000000;
-static unsigned long long g_seed = 1;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
-static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
-
-static bool SameBits(const std::vector<double> &a, const std::vector<double> &b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * 8) == 0);
-}
 static bool SameRow(const double *a, const VectorXd &b) { return std::memcmp(a, b.data(), b.size() * 8) == 0; }
-static std::vector<double> Flatten(const std::vector<VectorXd> &v) {
-  std::vector<double> r;
-  for (const auto &x : v) r.insert(r.end(), x.begin(), x.end());
-  return r;
-}
 static VectorXd RandomVec(int D, double lo, double hi) {
   VectorXd v(D);
   for (int d = 0; d < D; d++) v[d] = lo + (hi - lo) * Rnd();
@@ -91,29 +68,6 @@ static std::shared_ptr<TimeableJointSplinePath> HostPath(int D, int N, double de
   CHECK(path->SetMaxJointAcceleration({amax.data(), amax.size()}).ok());
   if (iv) CHECK(path->SetInitialVelocity({iv->data(), iv->size()}).ok());
   return path;
-}
-
-// planner b of the set against its mirror: summary, trajectory and resident spline, bit for bit
-static int CompareOne(const PathTimingTrajectorySet &set, int b, const PathTimingTrajectory &m,
-                      const TimeableJointSplinePath &path) {
-  int bad = 0;
-  if (set.GetNumTimeSamples(b) != m.GetNumTimeSamples()) return 1;
-  bad |= (ToUnixNanos(set.GetEndTime(b)) != ToUnixNanos(m.GetEndTime())) << 1;
-  bad |= (ToUnixNanos(set.GetStartTime(b)) != ToUnixNanos(m.GetStartTime())) << 2;
-  bad |= (ToUnixNanos(set.GetFinalDecelStart(b)) != ToUnixNanos(m.GetFinalDecelStart())) << 3;
-  bad |= (set.IsTrajectoryAtEnd(b) != m.IsTrajectoryAtEnd()) << 4;
-  PlannedTrajectory t;
-  if (!set.GetTrajectory(b, &t).ok()) return bad | (1 << 5);
-  bad |= !SameBits(t.time, m.GetTime()) << 6;
-  bad |= !SameBits(t.path_parameter, m.GetPathParameters()) << 7;
-  bad |= !SameBits(t.path_parameter_derivative, m.GetPathParameterDerivatives()) << 8;
-  bad |= !SameBits(t.positions, Flatten(m.GetPositions())) << 9;
-  bad |= !SameBits(t.velocities, Flatten(m.GetVelocities())) << 10;
-  bad |= !SameBits(t.accelerations, Flatten(m.GetAccelerations())) << 11;
-  std::vector<double> k, c;
-  bad |= !set.GetPath(b, &k, &c).ok() << 12;
-  bad |= (!SameBits(k, path.knots()) || !SameBits(c, path.packed_control_points())) << 13;
-  return bad;
 }
 
 // What the reference-named sequence gives one mirror planner at `time`: position, velocity, stopping
@@ -204,7 +158,7 @@ static void TestAgainstMirrors(Method method, int D) {
     }
     CHECK(first[b].ok());
     CHECK(mirrors[b]->Plan(starts[b], horizons[b]).ok());
-    CHECK(CompareOne(dev, b, *mirrors[b], *paths[b]) == 0);
+    CHECK(CompareOne(dev, b, *mirrors[b], paths[b].get()) == 0);
   }
   // 1. one retarget call: a shuffled subset (every fifth planner below kFirstAtEnd keeps its path)
   std::vector<size_t> ids;
@@ -320,7 +274,7 @@ static void TestAgainstMirrors(Method method, int D) {
       }
       const Status ms = mirrors[b]->Plan(starts[b], horizons[b]);
       CHECK(sd[b].code() == ms.code());
-      const int bad = CompareOne(dev, b, *mirrors[b], *paths[b]);
+      const int bad = CompareOne(dev, b, *mirrors[b], paths[b].get());
       CHECK(bad == 0);
       if (bad && ++reported <= 12)
         std::printf("  D %d %s round %d planner %d: differences 0x%x (status %d / mirror %d)\n", D,
@@ -395,7 +349,7 @@ static void TestAgainstMirrors(Method method, int D) {
   const auto sl = dev.Plan(starts, horizons);
   for (size_t k = 0; k < some.size(); k++) {
     const int b = (int)some[k];
-    CHECK(CompareOne(dev, b, *mirrors[b], *paths[b]) == 0);
+    CHECK(CompareOne(dev, b, *mirrors[b], paths[b].get()) == 0);
     CHECK(sl[b].ok());
   }
   CHECK(max_points >= 3 * 22 - 2);

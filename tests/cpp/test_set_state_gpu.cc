@@ -33,6 +33,9 @@
 #include "../../x-edr-trajectory-planning_amd/csrc/tpamd_state.h"
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
 
+#define TEST_SUPPORT_MIRROR
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
 using tpamd::compat::Milliseconds;
@@ -41,29 +44,6 @@ using tpamd::compat::StatusCode;
 using tpamd::compat::ToUnixNanos;
 using Method = PathTimingTrajectoryOptions::TimeSamplingMethod;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-
-static const int64_t kMs = 1000000;
-static unsigned long long g_seed = 1;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
-static bool SameBits(const std::vector<double> &a, const std::vector<double> &b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * 8) == 0);
-}
-static std::vector<double> Flatten(const std::vector<VectorXd> &v) {
-  std::vector<double> r;
-  for (const auto &x : v) r.insert(r.end(), x.begin(), x.end());
-  return r;
-}
 static VectorXd RandomVec(int D, double lo, double hi) {
   VectorXd v(D);
   for (int d = 0; d < D; d++) v[d] = lo + (hi - lo) * Rnd();

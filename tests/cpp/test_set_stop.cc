@@ -25,6 +25,7 @@
 #include "../../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
 #include "../../x-edr-trajectory-planning_amd/host/timeable_path_joint_spline.h"
 #include "../../x-edr-trajectory-planning_amd/host/trajectory_buffer.h"
+#include "test_support.h"
 
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
@@ -32,26 +33,8 @@ using tpamd::compat::Milliseconds;
 using tpamd::compat::StatusCode;
 using Method = PathTimingTrajectoryOptions::TimeSamplingMethod;
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 40) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-#define HIP_OK(expr) CHECK((expr) == hipSuccess)
-
-static const int64_t kMs = 1000000;
-static unsigned long long g_seed = 1;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
-static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
-
 // equal bytes; a NaN equals a NaN whatever its payload (host and device may make different ones)
-static bool SameBits(const double *a, const double *b, size_t n) {
+static bool SameBitsOrNaN(const double *a, const double *b, size_t n) {
   if (n == 0 || std::memcmp(a, b, n * 8) == 0) return true;
   for (size_t i = 0; i < n; i++)
     if (std::memcmp(a + i, b + i, 8) != 0 && !(std::isnan(a[i]) && std::isnan(b[i]))) return false;
@@ -128,11 +111,11 @@ static bool SameStop(const MirrorStop &m, const Rows &r, int keep, const double 
                      const double *sqdd, int seg) {
   const int D = r.D;
   if (keep < 0 || keep > r.n || seg < 0 || (size_t)(keep + seg) != m.t.size()) return false;
-  return SameBits(m.t.data(), r.t, keep) && SameBits(m.q.data(), r.q, (size_t)keep * D) &&
-         SameBits(m.qd.data(), r.qd, (size_t)keep * D) && SameBits(m.qdd.data(), r.qdd, (size_t)keep * D) &&
-         SameBits(m.t.data() + keep, st, seg) && SameBits(m.q.data() + (size_t)keep * D, sq, (size_t)seg * D) &&
-         SameBits(m.qd.data() + (size_t)keep * D, sqd, (size_t)seg * D) &&
-         SameBits(m.qdd.data() + (size_t)keep * D, sqdd, (size_t)seg * D);
+  return SameBitsOrNaN(m.t.data(), r.t, keep) && SameBitsOrNaN(m.q.data(), r.q, (size_t)keep * D) &&
+         SameBitsOrNaN(m.qd.data(), r.qd, (size_t)keep * D) && SameBitsOrNaN(m.qdd.data(), r.qdd, (size_t)keep * D) &&
+         SameBitsOrNaN(m.t.data() + keep, st, seg) && SameBitsOrNaN(m.q.data() + (size_t)keep * D, sq, (size_t)seg * D) &&
+         SameBitsOrNaN(m.qd.data() + (size_t)keep * D, sqd, (size_t)seg * D) &&
+         SameBitsOrNaN(m.qdd.data() + (size_t)keep * D, sqdd, (size_t)seg * D);
 }
 
 // A stop time for a trajectory: before it, on a sample, between two, on the last, past the end
@@ -212,9 +195,9 @@ static void TestSetAgainstMirror(Method method, int D) {
   for (int b = 0; b < B; b++) {
     PlannedTrajectory a, c;
     CHECK(set.GetTrajectory(b, &a).ok() && twin.GetTrajectory(b, &c).ok());
-    CHECK(SameBits(a.time.data(), c.time.data(), a.time.size()) && a.time.size() == c.time.size() &&
-          SameBits(a.positions.data(), c.positions.data(), a.positions.size()) &&
-          SameBits(a.velocities.data(), c.velocities.data(), a.velocities.size()));
+    CHECK(SameBitsOrNaN(a.time.data(), c.time.data(), a.time.size()) && a.time.size() == c.time.size() &&
+          SameBitsOrNaN(a.positions.data(), c.positions.data(), a.positions.size()) &&
+          SameBitsOrNaN(a.velocities.data(), c.velocities.data(), a.velocities.size()));
   }
   CHECK(cat[0] > 100 && cat[3] > 20 && cat[4] > 20 && cat[5] > 20 && cat[7] > 20);
   // errors of the call
@@ -361,9 +344,9 @@ static void TestSetCabi(Method method, int D) {
     for (int k = n; k < dn; k++) CHECK(gres[k] == TPAMD_PLAN_INVALID_ARGUMENT && gres[dn + k] == 0);
     CHECK(std::memcmp(goff.data(), hoff.data(), (n + 1) * 8) == 0 && goff[n + 1] == total && goff[n + 2] == total);
     CHECK(std::memcmp(goff2.data(), goff.data(), (dn + 1) * 8) == 0);
-    CHECK(SameBits(grows.data(), ht.data(), total) && SameBits(grows.data() + total, hq.data(), total * D) &&
-          SameBits(grows.data() + total + total * D, hqd.data(), total * D) &&
-          SameBits(grows.data() + total + 2 * total * D, hqdd.data(), total * D));
+    CHECK(SameBitsOrNaN(grows.data(), ht.data(), total) && SameBitsOrNaN(grows.data() + total, hq.data(), total * D) &&
+          SameBitsOrNaN(grows.data() + total + total * D, hqd.data(), total * D) &&
+          SameBitsOrNaN(grows.data() + total + 2 * total * D, hqdd.data(), total * D));
     bool untouched = true;
     for (double v : grows2) untouched &= v == kSentinel;
     CHECK(untouched);
@@ -510,8 +493,8 @@ static void CheckBatch(tpamd_engine *e, int B, int M, int D, const std::vector<d
   HIP_OK(hipMemcpy(gqdd.data(), doqdd, gqdd.size() * 8, hipMemcpyDeviceToHost));
   CHECK(std::memcmp(gi.data(), st.data(), B * 4) == 0 && std::memcmp(gi.data() + B, keep.data(), B * 4) == 0 &&
         std::memcmp(gi.data() + 2 * B, first.data(), B * 4) == 0 && std::memcmp(gi.data() + 3 * B, last.data(), B * 4) == 0);
-  CHECK(SameBits(got.data(), ot.data(), got.size()) && SameBits(gqd.data(), oqd.data(), gqd.size()) &&
-        SameBits(gqdd.data(), oqdd.data(), gqdd.size()));
+  CHECK(SameBitsOrNaN(got.data(), ot.data(), got.size()) && SameBitsOrNaN(gqd.data(), oqd.data(), gqd.size()) &&
+        SameBitsOrNaN(gqdd.data(), oqdd.data(), gqdd.size()));
   HIP_OK(hipFree(d));
 }
 

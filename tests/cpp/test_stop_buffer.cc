@@ -17,24 +17,11 @@
 #include "../../x-edr-trajectory-planning_amd/host/rescale_to_stop.h"
 #include "../../x-edr-trajectory-planning_amd/host/trajectory_buffer.h"
 
+#define TEST_SUPPORT_SEED 20261016ULL
+#include "test_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::StatusCode;
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                          \
-  do {                                                                                       \
-    if (!(cond)) {                                                                           \
-      if (g_fail < 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
-      g_fail++;                                                                              \
-    }                                                                                        \
-  } while (0)
-
-static unsigned long long g_seed = 20261016ULL;
-static double Rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
-static int RndInt(int lo, int hi) { return lo + (int)(Rnd() * (hi - lo + 1)) % (hi - lo + 1); }
 
 static int Code(const Status &s) {
   switch (s.code()) {
@@ -182,8 +169,6 @@ static void ReferenceCases() {
   }
   std::printf("reference cases: done\n");
 }
-
-static bool SameBits(const double *a, const double *b, size_t n) { return n == 0 || std::memcmp(a, b, n * 8) == 0; }
 
 // One seeded case: the mirror buffer against rs_stop_serial; returns the category.
 static std::string FuzzOne(int c, std::map<std::string, long> *counts) {

@@ -17,7 +17,8 @@ import zlib
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from conftest import ROOT
+from native_driver import build_driver
 import buffer_reference as br
 
 ALL_DOFS = list(range(1, 17))
@@ -25,13 +26,8 @@ ALL_DOFS = list(range(1, 17))
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("buffer_reference") / "test_buffer_reference")
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_buffer_reference.cc"),
-                           os.path.join(host, "rescale_to_stop.cc"), os.path.join(host, "trajectory_buffer.cc")],
-                          timeout=600)
-    return exe
+    return build_driver("test_buffer_reference.cc", tmp_path_factory.mktemp("buffer_reference"), opt="-O2",
+                        extra_sources=("host/rescale_to_stop.cc", "host/trajectory_buffer.cc"), timeout=600)
 
 
 def _hex(values):

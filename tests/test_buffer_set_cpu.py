@@ -5,9 +5,9 @@ compiled for the host, bit-equal to a mirror buffer after every operation of see
 operation sequences (tests/cpp/test_buffer_core.cc). No GPU needed."""
 import os
 import re
-import subprocess
 
 from conftest import ROOT, PKG_NAME
+from native_driver import build_driver, run_driver
 
 CATEGORIES = (
     "insert: empty segment", "insert: into an empty buffer", "insert: at or before the front (sequence back to 0)",
@@ -23,24 +23,13 @@ CATEGORIES = (
 )
 
 
-def _build_driver(tmp_path):
-    exe = str(tmp_path / "test_buffer_core")
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_buffer_core.cc"),
-           os.path.join(host, "rescale_to_stop.cc"), os.path.join(host, "trajectory_buffer.cc")]
-    subprocess.check_call(cmd)
-    return exe
-
-
 def test_buffer_core_matches_mirror_bit_for_bit(tmp_path):
-    exe = _build_driver(tmp_path)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-5000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "reference cases: done" in out.stdout
+    exe = build_driver("test_buffer_core.cc", tmp_path, opt="-O2",
+                       extra_sources=("host/rescale_to_stop.cc", "host/trajectory_buffer.cc"))
+    out = run_driver(exe, timeout=600, tail=5000)
+    assert "reference cases: done" in out
     counts = {}
-    for line in out.stdout.splitlines():
+    for line in out.splitlines():
         if line.startswith("category "):
             name, n = line[len("category "):].rsplit(":", 1)
             counts[name.strip()] = int(n)

@@ -8,6 +8,7 @@ import re
 import subprocess
 
 from conftest import ROOT, PKG_NAME
+from native_driver import build_driver
 
 ENTRIES = ("tpamd_planner_set_discard_ik_rows", "tpamd_planner_set_ik_table_info",
            "tpamd_planner_set_download_ik_rows", "tpamd_planner_set_ik_table_device_pointers")
@@ -37,8 +38,7 @@ def _check_counts(counts):
 
 
 def test_need_from_floor_and_compaction_schedule(tmp_path):
-    exe = str(tmp_path / "test_cartesian_discard_window")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, SRC, "-lm"])
+    exe = build_driver(SRC, tmp_path, libs=("m",), opt="-O2")
     counts, _ = _run(exe)
     _check_counts(counts)
 
@@ -46,9 +46,8 @@ def test_need_from_floor_and_compaction_schedule(tmp_path):
 def test_driver_is_clean_under_sanitizers(tmp_path):
     """The same driver as a stand-alone program with its own main, built with
     -fsanitize=address,undefined: host code only, nothing preloaded."""
-    exe = str(tmp_path / "test_cartesian_discard_window_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-o", exe, SRC, "-lm"])
+    exe = build_driver(SRC, tmp_path, libs=("m",), name="test_cartesian_discard_window_san",
+                       flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
     counts, out = _run(exe)
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
     _check_counts(counts)

@@ -10,36 +10,26 @@ import re
 import subprocess
 
 from conftest import ROOT, PKG_NAME
+from native_driver import build_driver, run_driver
 
 ENTRIES = ("tpamd_time_cartesian_paths_ragged_device", "tpamd_time_cartesian_paths_ragged_host",
            "tpamd_optimize_rows_ragged_device", "tpamd_optimize_rows_ragged_host")
 
 
 def _run(exe):
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
-    return out.stdout
+    return run_driver(exe, timeout=300, tail=3000)
 
 
 def test_ragged_row_arithmetic_matches_the_oracle_per_path(tmp_path):
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_cartesian_ragged_rows")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_cartesian_ragged_rows.cc"),
-                           "-L" + oracle, "-ltp_oracle", "-lm", "-Wl,-rpath," + oracle])
-    out = _run(exe)
+    out = _run(build_driver("test_cartesian_ragged_rows.cc", tmp_path, libs=("oracle", "m"), opt="-O2"))
     # five joint counts, two layouts, two paths of each count in {3, 4, 5, 64}
     assert "samples: %d" % (5 * 2 * 2 * (3 + 4 + 5 + 64)) in out
     assert "refused: %d" % (5 * 4 * 70) in out
 
 
 def test_mirror_buckets_on_known_length_lists(tmp_path):
-    exe = str(tmp_path / "test_cartesian_buckets")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_cartesian_buckets.cc")])
-    _run(exe)
+    _run(build_driver("test_cartesian_buckets.cc", tmp_path, fp_contract_off=False,
+                      flags=("-I" + os.path.join(ROOT, "include"),)))
 
 
 def test_ragged_entry_points_are_declared_exported_and_bound():

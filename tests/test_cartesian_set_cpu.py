@@ -9,24 +9,17 @@ import re
 import subprocess
 
 from conftest import ROOT, PKG_NAME
+from native_driver import build_driver, run_driver
 
 ENTRIES = ("tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
            "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table")
 
 
 def test_window_rule_matches_the_oracle_bit_for_bit(tmp_path):
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_cartesian_window")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_cartesian_window.cc"),
-           "-L" + oracle, "-ltp_oracle", "-lm", "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+    exe = build_driver("test_cartesian_window.cc", tmp_path, libs=("oracle", "m"), opt="-O2")
+    out = run_driver(exe, timeout=600, tail=3000)
     counts = {}
-    for line in out.stdout.splitlines():
+    for line in out.splitlines():
         if ":" in line and line.rsplit(":", 1)[1].strip().isdigit():
             counts[line.rsplit(":", 1)[0]] = int(line.rsplit(":", 1)[1])
     assert counts["in range"] > 1000 and counts["out of range"] > 100 and counts["samples"] > 50000
@@ -39,22 +32,10 @@ def test_synthetic_family_keeps_every_oracle_planner_ok(tmp_path):
     of tests/cpp/test_cartesian_set_gpu.cc (its --cpu-check mode: the oracle planners alone, no GPU
     call) every oracle planner returns OK at every Plan and ends with target_reached, the
     modified-state re-upload included."""
-    import importlib
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_cartesian_set_gpu")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_cartesian_set_gpu.cc"),
-           "-L" + csrc, "-ltpamd", "-L" + oracle, "-ltp_oracle", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           "-Wl,-rpath," + csrc, "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe, "--cpu-check"], capture_output=True, text=True, timeout=900)
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
-    assert out.stdout.count("family: D") == 6 and out.stdout.count("256 at the end") == 6
-    assert out.stdout.count("modified") == 3 and "FAILURES" not in out.stdout
+    exe = build_driver("test_cartesian_set_gpu.cc", tmp_path, libs=("engine", "oracle", "hip", "m"), flags=("-pthread",))
+    out = run_driver(exe, "--cpu-check", timeout=900, tail=3000)
+    assert out.count("family: D") == 6 and out.count("256 at the end") == 6
+    assert out.count("modified") == 3 and "FAILURES" not in out
 
 
 def test_cartesian_set_exports_are_declared():

@@ -9,6 +9,7 @@ import re
 import subprocess
 
 from conftest import ROOT, PKG_NAME
+from native_driver import build_driver
 
 ENTRIES = ("tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
            "tpamd_planner_set_plan_streaming", "tpamd_planner_set_plan_resume",
@@ -29,8 +30,7 @@ def _run(exe):
 
 
 def test_window_need_matches_the_reference_rule_and_the_state_machine(tmp_path):
-    exe = str(tmp_path / "test_cartesian_stream_window")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, SRC, "-lm"])
+    exe = build_driver(SRC, tmp_path, libs=("m",), opt="-O2")
     counts, _ = _run(exe)
     assert counts["resident"] > 1000 and counts["needs rows"] > 1000 and counts["malformed"] > 100
     for name in ("rounding ties", "negative starts", "rows = last", "rows = last + 1", "rows = last + 2"):
@@ -41,9 +41,8 @@ def test_window_need_matches_the_reference_rule_and_the_state_machine(tmp_path):
 def test_window_need_driver_is_clean_under_sanitizers(tmp_path):
     """The same driver as a stand-alone program with its own main, built with
     -fsanitize=address,undefined: host code only, nothing preloaded."""
-    exe = str(tmp_path / "test_cartesian_stream_window_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-o", exe, SRC, "-lm"])
+    exe = build_driver(SRC, tmp_path, libs=("m",), name="test_cartesian_stream_window_san",
+                       flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
     counts, out = _run(exe)
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
     assert counts["needs rows"] > 1000

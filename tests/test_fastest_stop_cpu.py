@@ -2,15 +2,13 @@
 path_timing_trajectory.cc:75-172, :235-287): a pure-Python restatement of the recurrence, checked
 bit for bit against the mirror's host function (host/fastest_stop.cc) through a small C++ driver.
 The GPU entries are checked against the same restatement in tests/test_gpu_fastest_stop.py."""
-import importlib
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from native_driver import build_driver
 
 PLAN_OK, PLAN_INVALID_ARGUMENT = 0, 3
 
@@ -127,19 +125,6 @@ def test_restatement_edge_cases():
     assert st == PLAN_OK and 0 < idx < 399 and pr[-1] == 0.0 and dur > 0.0
 
 
-def _build_driver(tmp_path):
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_fastest_stop")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_fastest_stop.cc"),
-           "-L" + host, "-ltp_host", "-L" + os.path.join(ROOT, PKG_NAME, "csrc"), "-ltpamd",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + os.path.join(ROOT, PKG_NAME, "csrc")]
-    subprocess.check_call(cmd)
-    return exe
-
-
 def test_mirror_matches_restatement_bit_for_bit(tmp_path):
     cases = stop_cases()
     inp = tmp_path / "cases.txt"
@@ -150,7 +135,7 @@ def test_mirror_matches_restatement_bit_for_bit(tmp_path):
             f.write("%d %d %s\n" % (len(time), D, float(q).hex()))
             flat = list(time) + list(s) + [x for r in qd for x in r] + [x for r in qdd for x in r] + list(amax)
             f.write(" ".join(float(x).hex() for x in flat) + "\n")
-    exe = _build_driver(tmp_path)
+    exe = build_driver("test_fastest_stop.cc", tmp_path, libs=("host", "engine"), opt="-O2")
     out = subprocess.run([exe, str(inp)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     lines = out.stdout.strip().split("\n")

@@ -2,29 +2,15 @@
 host and compared bit for bit with the mirror's TimeableJointSplinePath::SetWaypoints and the oracle's
 joint fit (tests/cpp/test_fit_waypoints.cc), and a sample of its cases with tpo.joint_fit_spline.
 No GPU needed."""
-import importlib
-import os
 import subprocess
 
 import numpy as np
 
-from conftest import ROOT, PKG_NAME
+from native_driver import build_driver
 
 
 def _build_driver(tmp_path):
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_fit_waypoints")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_fit_waypoints.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L" + oracle, "-ltp_oracle", "-lm",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc, "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd)
-    return exe
+    return build_driver("test_fit_waypoints.cc", tmp_path, libs=("host", "engine", "oracle", "m"), opt="-O2")
 
 
 def _read_cases(path):

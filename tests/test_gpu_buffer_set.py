@@ -16,13 +16,12 @@ restatement of tests/buffer_reference.py, every layout case a compaction, lists 
 capacities on and one row beside the total, ticks on and 1 ns beside the stamps."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -53,31 +52,16 @@ def _write_paths(path, D, N, per_family):
 
 
 def test_buffer_set_against_mirror(tmp_path):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
+    require_gpu()
     paths = str(tmp_path / "paths.bin")
     assert _write_paths(paths, 7, 300, 16) == 256
-    exe = str(tmp_path / "test_buffer_set_gpu")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_buffer_set_gpu.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe, paths], capture_output=True, text=True, timeout=900)
-    print(out.stdout[:4000])
-    print(out.stdout[-3000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
-    assert out.stdout.count("fuzz vs mirror") == 3
+    exe = build_driver("test_buffer_set_gpu.cc", tmp_path, libs=("host", "engine", "hip", "m"))
+    out = run_driver(exe, paths, timeout=900, head=4000, tail=3000)
+    assert out.count("fuzz vs mirror") == 3
     for part in ("planner set -> buffers", "stop in place vs stop_trajectories", "packed device outputs inserted",
                  "graph capture of insert -> discard -> sample", "TPAMD_PLAN_MORE leaves the buffer unchanged",
                  "TrajectoryBufferSet: ok"):
-        assert part in out.stdout, part
+        assert part in out, part
 
 
 def _bits(a):

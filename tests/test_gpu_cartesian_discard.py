@@ -8,14 +8,13 @@ one oracle IK-table planner per planner on the FULL table and against a streamin
 discards, bit for bit at every Plan. It also covers the appends that must not reallocate, a keep_from
 above the floor, and the refused calls. The mirror and the PyTorch route are tested here."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import pose_fit_reference as pfr
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -23,24 +22,8 @@ MS = 1_000_000
 
 
 def _build(tmp, name, host_mirror):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    exe = str(tmp / name)
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-w",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", name + ".cc")]
-    if host_mirror:
-        host = os.path.join(ROOT, PKG_NAME, "host")
-        subprocess.check_call(["make", "-C", host, "-s"])
-        cmd += ["-L" + host, "-ltp_host", "-Wl,-rpath," + host]
-    else:
-        oracle = os.path.join(ROOT, "oracle")
-        subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-        cmd += ["-L" + oracle, "-ltp_oracle", "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd + ["-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm", "-Wl,-rpath," + csrc])
-    return exe
+    require_gpu()
+    return build_driver(name + ".cc", tmp, libs=("host" if host_mirror else "oracle", "engine", "hip", "m"), flags=("-w",))
 
 
 @pytest.fixture(scope="module")
@@ -49,11 +32,7 @@ def driver(tmp_path_factory):
 
 
 def _run(exe, *args):
-    out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    print(out.stdout[-4000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout and "FAIL" not in out.stdout
-    return out.stdout
+    return run_driver(exe, *args, timeout=300, forbid_fail=True)
 
 
 @pytest.mark.parametrize("D", [5, 6, 7])

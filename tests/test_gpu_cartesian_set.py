@@ -5,48 +5,25 @@ every Plan's summaries and trajectories against one oracle IK-table planner per 
 it asserts that every oracle planner returns OK at every step and reaches its target. It also covers
 the modified-state re-upload, per-planner failures, capacity growth, the _device upload on a
 non-blocking stream, the kind checks and the PCIe bytes of a Plan."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
 
-def build_driver(tmp_path):
-    import importlib
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_cartesian_set_gpu")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_cartesian_set_gpu.cc"),
-           "-L" + csrc, "-ltpamd", "-L" + oracle, "-ltp_oracle", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           "-Wl,-rpath," + csrc, "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd)
-    return exe
-
-
 def test_cartesian_sets_against_oracle_planners(tmp_path):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    exe = build_driver(tmp_path)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=1500)
-    print(out.stdout[:6000])
-    print(out.stdout[-3000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
-    assert out.stdout.count("family: D") == 6
-    assert out.stdout.count("modified") == 3 and "modified + growth" in out.stdout
-    assert out.stdout.count("failures: internal at Plan") == 2
-    assert "device upload against host upload: 12 of 12 Plan calls equal, 64 tables equal" in out.stdout
-    assert "IK-table entries on a joint set: refused, plans unchanged" in out.stdout
-    assert "device upload with a bad delta and a bad state: statuses 0 1 1 0" in out.stdout
+    require_gpu()
+    exe = build_driver("test_cartesian_set_gpu.cc", tmp_path, libs=("engine", "oracle", "hip", "m"), flags=("-pthread",))
+    out = run_driver(exe, timeout=1500, head=6000, tail=3000)
+    assert out.count("family: D") == 6
+    assert out.count("modified") == 3 and "modified + growth" in out
+    assert out.count("failures: internal at Plan") == 2
+    assert "device upload against host upload: 12 of 12 Plan calls equal, 64 tables equal" in out
+    assert "IK-table entries on a joint set: refused, plans unchanged" in out
+    assert "device upload with a bad delta and a bad state: statuses 0 1 1 0" in out
 
 
 def test_cartesian_sets_against_mirror_planners_and_downstream(tmp_path):
@@ -54,26 +31,11 @@ def test_cartesian_sets_against_mirror_planners_and_downstream(tmp_path):
     TimeableCartesianSplinePaths equal one mirror PathTimingTrajectory per planner planning window
     by window; setpoints, packed downloads, stop parameters, stopping trajectories and the buffer-set
     insert on such a set give what the host flows give on the downloaded trajectory."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    import importlib
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_cartesian_set_mirror_gpu")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_cartesian_set_mirror_gpu.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=1200)
-    print(out.stdout[-4000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
-    assert out.stdout.count("mirror family (") == 2
-    assert "Cartesian methods on a joint set: refused" in out.stdout
+    require_gpu()
+    exe = build_driver("test_cartesian_set_mirror_gpu.cc", tmp_path, libs=("host", "engine", "hip", "m"))
+    out = run_driver(exe, timeout=1200)
+    assert out.count("mirror family (") == 2
+    assert "Cartesian methods on a joint set: refused" in out
 
 
 def _bits(a):

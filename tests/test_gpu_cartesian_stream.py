@@ -10,15 +10,14 @@ row short. It also covers the final tables, the capacity growth, tpamd_planner_s
 table, the refused calls and the dropped suspensions. The target-row sampler and the PyTorch route
 are tested here."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cartesian_paths as cp
 import pose_fit_reference as pfr
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -28,28 +27,13 @@ TPAMD_PLAN_NEEDS_ROWS = 7
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path_factory.mktemp("stream") / "test_cartesian_stream_gpu")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
-                           "-I/opt/rocm/include", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_cartesian_stream_gpu.cc"),
-                           "-L" + csrc, "-ltpamd", "-L" + oracle, "-ltp_oracle", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath," + oracle])
-    return exe
+    require_gpu()
+    return build_driver("test_cartesian_stream_gpu.cc", tmp_path_factory.mktemp("stream"),
+                        libs=("engine", "oracle", "hip", "m"))
 
 
 def _run(exe, *args):
-    out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    print(out.stdout[-4000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout and "FAIL" not in out.stdout
-    return out.stdout
+    return run_driver(exe, *args, timeout=300, forbid_fail=True)
 
 
 @pytest.mark.parametrize("D,method", [(5, 0), (5, 1), (6, 0), (6, 1), (7, 0), (7, 1)])
@@ -75,20 +59,8 @@ def test_streaming_mirror_with_a_split_dependent_ik(tmp_path):
     """tests/cpp/test_cartesian_stream_mirror_gpu.cc: SetCartesianPaths(streaming) + PlanStreaming with
     an IK seeded by the previous row equals one mirror PathTimingTrajectory per planner planning window
     by window, bit for bit; the whole-table set built with the same callback differs."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_cartesian_stream_mirror_gpu")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
-                           "-I/opt/rocm/include", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_cartesian_stream_mirror_gpu.cc"),
-                           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-                           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc])
-    out = _run(exe)
+    require_gpu()
+    out = _run(build_driver("test_cartesian_stream_mirror_gpu.cc", tmp_path, libs=("host", "engine", "hip", "m")))
     assert out.count("streaming mirror family (") == 2 and "PlanStreaming on a joint set: refused" in out
 
 
@@ -96,20 +68,8 @@ def test_streaming_mirror_through_the_device_chain(tmp_path):
     """tests/cpp/test_cartesian_stream_waypoint_gpu.cc: SetCartesianWaypointPaths(..., ik, streaming) +
     PlanStreaming (device targets for the missing rows, a device IK that receives the seed row, the
     _device append) against the non-streaming SetCartesianWaypointPaths set, bit for bit to the target."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_cartesian_stream_waypoint_gpu")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
-                           "-I/opt/rocm/include", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_cartesian_stream_waypoint_gpu.cc"),
-                           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-                           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc])
-    out = _run(exe)
+    require_gpu()
+    out = _run(build_driver("test_cartesian_stream_waypoint_gpu.cc", tmp_path, libs=("host", "engine", "hip", "m")))
     assert out.count("waypoint streaming D") == 2 and out.count("6 at the end") == 2
     assert out.count("the planner's splines are forgotten") == 2
 

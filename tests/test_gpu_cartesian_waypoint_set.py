@@ -6,14 +6,13 @@ tables equal the ones built on the host from the oracle's joint sampling and eve
 oracle's IK-table planner bit for bit."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import pose_fit_reference as pfr
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -176,27 +175,12 @@ def test_pose_waypoints_to_plan_against_the_oracle(D):
 def test_cartesian_waypoint_sets_through_the_mirror(tmp_path):
     """tests/cpp/test_cartesian_waypoint_set_gpu.cc: the same scenario through
     PathTimingTrajectorySet::SetCartesianWaypointPaths."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_cartesian_waypoint_set_gpu")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_cartesian_waypoint_set_gpu.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L" + oracle, "-ltp_oracle", "-L/opt/rocm/lib",
-           "-lamdhip64", "-lm", "-Wl,-rpath," + host, "-Wl,-rpath," + csrc, "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-4000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
+    require_gpu()
+    exe = build_driver("test_cartesian_waypoint_set_gpu.cc", tmp_path, libs=("host", "engine", "oracle", "hip", "m"),
+                       flags=("-pthread",))
+    out = run_driver(exe, timeout=600)
     for D in (6, 7):
-        assert "D %d: 6 of 6 resident tables equal the host-built ones" % D in out.stdout
-        assert "D %d: 18 of 18 plans equal the oracle planners" % D in out.stdout
-        assert "D %d: empty waypoint list: InvalidArgument, planner kept, others loaded and undisturbed" % D in out.stdout
-    assert "SetCartesianWaypointPaths on a joint set: refused" in out.stdout
+        assert "D %d: 6 of 6 resident tables equal the host-built ones" % D in out
+        assert "D %d: 18 of 18 plans equal the oracle planners" % D in out
+        assert "D %d: empty waypoint list: InvalidArgument, planner kept, others loaded and undisturbed" % D in out
+    assert "SetCartesianWaypointPaths on a joint set: refused" in out

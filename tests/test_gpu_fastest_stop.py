@@ -4,13 +4,12 @@ tests/test_fastest_stop_cpu.py, its call-level errors, and the mirror / planner-
 tests/cpp/test_host_stop.cc."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, run_driver
 from test_fastest_stop_cpu import PLAN_INVALID_ARGUMENT, fastest_stop_at_time
 
 pytestmark = pytest.mark.gpu
@@ -196,15 +195,6 @@ def test_call_level_errors(env):
 
 
 def test_mirror_and_planner_set_stop_parameters(env, tmp_path):
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_host_stop")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_host_stop.cc"),
-           "-L" + host, "-ltp_host", "-L" + os.path.join(ROOT, PKG_NAME, "csrc"), "-ltpamd",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + os.path.join(ROOT, PKG_NAME, "csrc")]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
-    print(out.stdout[-4000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
+    # the env fixture has built the engine library
+    exe = build_driver("test_host_stop.cc", tmp_path, libs=("host", "engine"), prebuilt=("engine",))
+    run_driver(exe, timeout=900)

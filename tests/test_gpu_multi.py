@@ -5,30 +5,20 @@ RCCL leg needs an 8-GPU node and stays unmeasured here; what runs is the same co
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import CPP, build_driver, run_driver
 
 
 def _build():
     eng = importlib.import_module(PKG_NAME + ".engine")
     eng.build_library()
     eng.build_multi_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "libtp_oracle.so"])
-    exe = os.path.join(ROOT, "tests", "cpp", "test_host_multi")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-o", exe, exe + ".cc", "-L" + host, "-ltp_host", "-L" + csrc,
-           "-ltpamd_multi", "-ltpamd", "-L" + os.path.join(ROOT, "oracle"), "-ltp_oracle",
-           "-L/opt/rocm/lib", "-lamdhip64", "-lm", "-Wl,-rpath," + host, "-Wl,-rpath," + csrc,
-           "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.check_call(cmd)
-    return exe
+    return build_driver("test_host_multi.cc", CPP, libs=("host", "multi", "engine", "oracle", "hip", "m"),
+                        flags=("-pthread", "-Wl,-rpath,/opt/rocm/lib"))
 
 
 def test_multi_device_pieces_build_on_cpu():
@@ -57,8 +47,4 @@ def test_shard_bounds_of_the_c_abi_match_the_python_sharding():
 
 @pytest.mark.gpu
 def test_multi_device_pieces_on_gpu():
-    exe = _build()
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-4000:])
-    print(out.stderr[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
+    run_driver(_build(), timeout=600, err_tail=3000)

@@ -5,12 +5,12 @@ rows, bit-equal to the mirror's results for the cases of tests/cpp/test_path_too
 the CPU test reads), statuses included."""
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import PKG_NAME
+from native_driver import run_driver
 from test_path_tools_cpu import build_driver, read_dump
 
 pytestmark = pytest.mark.gpu
@@ -29,8 +29,7 @@ def env(tmp_path_factory):
     d = tmp_path_factory.mktemp("path_tools_gpu")
     exe = build_driver(d)
     dump = os.path.join(str(d), "cases.txt")
-    out = subprocess.run([exe, dump], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
+    run_driver(exe, dump, timeout=600, tail=3000)
     stops, projs = read_dump(dump)
     return dict(torch=torch, eng=eng, E=eng.Engine(0), dev=torch.device("cuda", 0), stops=stops, projs=projs)
 

@@ -1,33 +1,15 @@
 """The host mirror's PathTimingTrajectorySet with the skip method at a history capacity above 32768
 samples (tests/cpp/test_set_skip_long.cc): every Plan equals one mirror PathTimingTrajectory per
 planner, bit for bit."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
 
 def test_skip_method_set_above_32768_against_mirrors(tmp_path):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    import importlib
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_set_skip_long")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_set_skip_long.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    print(out.stdout[-3000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
-    assert "9 plans bit-equal to the mirrors" in out.stdout
+    require_gpu()
+    exe = build_driver("test_set_skip_long.cc", tmp_path, libs=("host", "engine", "hip", "m"))
+    out = run_driver(exe, timeout=300, tail=3000)
+    assert "9 plans bit-equal to the mirrors" in out

@@ -3,36 +3,15 @@ PathTimingTrajectorySet::SwitchToWaypointPaths): tests/cpp/test_set_switch.cc ho
 sets at D = 3 and 7 with both sampling methods bit-equal to one mirror planner each running
 GetPathStopParameter -> SwitchToWaypointPath -> SetInitialVelocity -> Plan, follows a few of them
 with the oracle's planner, and checks the call's errors."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
 
 def test_set_switch_against_mirrors(tmp_path):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    import importlib
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    oracle = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    subprocess.check_call(["make", "-C", oracle, "-s", "libtp_oracle.so"])
-    exe = str(tmp_path / "test_set_switch")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_set_switch.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L" + oracle, "-ltp_oracle", "-lm",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc, "-Wl,-rpath," + oracle]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=1200)
-    print(out.stdout[:4000])
-    print(out.stdout[-3000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
-    assert out.stdout.count("switch vs mirrors") == 4
+    require_gpu()
+    exe = build_driver("test_set_switch.cc", tmp_path, libs=("host", "engine", "oracle", "m"))
+    out = run_driver(exe, timeout=1200, head=4000, tail=3000)
+    assert out.count("switch vs mirrors") == 4

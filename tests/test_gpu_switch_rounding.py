@@ -4,45 +4,28 @@ holds 70-planner sets at D = 3 and 7 with rounding 0, 0.05 and 1.0 bit-equal to 
 PathOptions::rounding has that value, and the entry without the argument to rounding 0.2.
 PlannerSet.switch_paths(rounding=...) is held to the same entry."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+from conftest import PKG_NAME
+from native_driver import build_driver, require_gpu, run_driver
 
 pytestmark = pytest.mark.gpu
 
 
 def test_switch_rounding_against_mirrors(tmp_path):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_switch_rounding")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_switch_rounding.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           "-Wl,-rpath," + host, "-Wl,-rpath," + csrc]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-4000:])
-    print(out.stderr[-2000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout
-    assert out.stdout.count("switch rounding") == 6
-    assert out.stdout.count("switch without the argument") == 2
+    require_gpu()
+    exe = build_driver("test_switch_rounding.cc", tmp_path, libs=("host", "engine", "hip", "m"))
+    out = run_driver(exe, timeout=600)
+    assert out.count("switch rounding") == 6
+    assert out.count("switch without the argument") == 2
 
 
 def test_python_switch_paths_takes_the_rounding():
     """PlannerSet.switch_paths: the default equals rounding=0.2 bit for bit, another radius gives
     another control polygon with the same knots."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on an MI355X")
+    require_gpu()
     eng = importlib.import_module(PKG_NAME + ".engine")
     eng.build_library()
     E = eng.Engine(0)

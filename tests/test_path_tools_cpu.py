@@ -10,8 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import native_driver
 import path_tools_reference as ref
-from conftest import ROOT, PKG_NAME
 
 # The mirror's largest relative error against the long-double restatement over the 768 moving rows
 # of the dump (3.2 epsilon, at D = 2), measured on the build this was written on, and the bound held
@@ -21,13 +21,8 @@ STOP_ERROR_BOUND = 8 * MEASURED_STOP_ERROR
 
 
 def build_driver(dirname):
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    exe = os.path.join(str(dirname), "test_path_tools")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_path_tools.cc"),
-           os.path.join(host, "path_tools.cc"), os.path.join(host, "spline_edit.cc"), "-lm"]
-    subprocess.check_call(cmd)
-    return exe
+    return native_driver.build_driver("test_path_tools.cc", dirname, libs=("m",), opt="-O2",
+                                      extra_sources=("host/path_tools.cc", "host/spline_edit.cc"))
 
 
 def read_dump(path):

@@ -16,6 +16,7 @@ import pytest
 
 import check_reference as cr
 from conftest import PKG_NAME
+from native_driver import build_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCE = os.path.join(ROOT, "tests", "cpp", "test_planner_check_record.cc")
@@ -23,9 +24,8 @@ SOURCE = os.path.join(ROOT, "tests", "cpp", "test_planner_check_record.cc")
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def driver(request, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("planner_check") / ("driver_" + request.param))
     flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if request.param == "sanitized" else []
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off"] + flags + ["-o", exe, SOURCE])
+    exe = build_driver(SOURCE, tmp_path_factory.mktemp("planner_check"), flags=flags, name="driver_" + request.param)
 
     def run(text, tmp=os.path.dirname(exe)):
         path = os.path.join(tmp, "cases.txt")

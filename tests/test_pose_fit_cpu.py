@@ -14,11 +14,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, PKG_NAME
+from native_driver import build_driver
 import pose_fit_reference as pfr
 
-CSRC = os.path.join(ROOT, PKG_NAME, "csrc")
-HOST = os.path.join(ROOT, PKG_NAME, "host")
-DRIVER = os.path.join(ROOT, "tests", "cpp", "test_pose_fit.cc")
+DRIVER = "test_pose_fit.cc"
 
 
 def _golden_cases():
@@ -40,11 +39,7 @@ def fits(tmp_path_factory):
     """The case list, and fit_pose_waypoints' result on every case as the mirror-linked driver dumps
     it (the driver's bit-for-bit comparison with the mirror runs in the same pass)."""
     tmp = tmp_path_factory.mktemp("pose_fit")
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    subprocess.check_call(["make", "-C", HOST, "-s"])
-    exe = str(tmp / "test_pose_fit")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, DRIVER, "-L" + HOST, "-ltp_host",
-                           "-L" + CSRC, "-ltpamd", "-lm", "-Wl,-rpath," + HOST, "-Wl,-rpath," + CSRC])
+    exe = build_driver(DRIVER, tmp, libs=("host", "engine", "m"), opt="-O2")
     cases = pfr.all_cases() + _golden_cases()
     case_file, dump = str(tmp / "cases.bin"), str(tmp / "fits.bin")
     pfr.write_cases(case_file, cases)
@@ -127,10 +122,9 @@ def test_reference_corner_rounding_fixtures(fits):
 def test_sanitized_standalone_driver(fits, tmp_path):
     """The same driver as a stand-alone program (own main, header only, no mirror) built with
     -fsanitize=address,undefined, on the same case list. No Python process loads sanitized code."""
-    exe = str(tmp_path / "test_pose_fit_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-DPOSE_FIT_STANDALONE",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                           "-o", exe, DRIVER, "-lm"])
+    exe = build_driver(DRIVER, tmp_path, libs=("m",), name="test_pose_fit_san",
+                       flags=("-g", "-DPOSE_FIT_STANDALONE", "-fsanitize=address,undefined",
+                              "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"))
     out = subprocess.run([exe, fits["case_file"]], capture_output=True, text=True, timeout=600)
     print(out.stdout[-1500:], out.stderr[-3000:])
     assert out.returncode == 0 and "ALL OK" in out.stdout and "standalone: mirror not linked" in out.stdout

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import PKG_NAME, ROOT
+from native_driver import build_driver
 
 import refine_cases as cases
 import refine_reference as rr
@@ -47,11 +48,8 @@ def test_exports_and_prototypes():
 # ------------------------------------------------------------------ the decisions, on the host
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("refine_logic") / "test_refine_logic")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_refine_logic.cc")])
-    return exe
+    return build_driver("test_refine_logic.cc", tmp_path_factory.mktemp("refine_logic"),
+                        flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
 
 
 def _records(B, max_samples, max_rounds, tolerance, seed):

@@ -4,26 +4,16 @@ TrajectoryPlanner::Get{Position,Velocity,Acceleration}AtTime, and the switch's s
 which takes the same bracket, with GetVelocityAtTime (tests/cpp/test_readout_interp.cc). No GPU
 needed."""
 import os
-import subprocess
 
 from conftest import ROOT, PKG_NAME
-
-
-def _build_driver(tmp_path):
-    exe = str(tmp_path / "test_readout_interp")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_readout_interp.cc")]
-    subprocess.check_call(cmd)
-    return exe
+from native_driver import build_driver, run_driver
 
 
 def test_readout_interpolation_matches_mirror_bit_for_bit(tmp_path):
-    exe = _build_driver(tmp_path)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+    exe = build_driver("test_readout_interp.cc", tmp_path, opt="-O2")
+    out = run_driver(exe, timeout=600, tail=3000)
     counts = {}
-    for line in out.stdout.splitlines():
+    for line in out.splitlines():
         if line.startswith("category "):
             name, n = line[len("category "):].rsplit(":", 1)
             counts[name.strip()] = int(n)
@@ -34,7 +24,7 @@ def test_readout_interpolation_matches_mirror_bit_for_bit(tmp_path):
                 "1 ns before the first/status 2", "1 ns after the last/status 2", "on a repeated stamp/ok",
                 "one sample/ok", "one sample/status 2", "empty/status 1"):
         assert counts.get(cat, 0) > 0, (cat, counts)
-    assert "tick times: ok" in out.stdout
+    assert "tick times: ok" in out
 
 
 def test_readout_exports_are_declared():

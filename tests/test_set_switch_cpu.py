@@ -2,33 +2,14 @@
 functions) compiled for the host and compared bit for bit with the mirror's
 TimeableJointSplinePath::SwitchToWaypointPath and TrajectoryPlanner::GetVelocityAtTime
 (tests/cpp/test_switch_edit.cc). No GPU needed."""
-import importlib
-import os
-import subprocess
-
-from conftest import ROOT, PKG_NAME
-
-
-def _build_driver(tmp_path):
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path / "test_switch_edit")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_switch_edit.cc"),
-           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-Wl,-rpath," + host, "-Wl,-rpath," + csrc]
-    subprocess.check_call(cmd)
-    return exe
+from native_driver import build_driver, run_driver
 
 
 def test_switch_edit_matches_mirror_bit_for_bit(tmp_path):
-    exe = _build_driver(tmp_path)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+    exe = build_driver("test_switch_edit.cc", tmp_path, libs=("host", "engine"), opt="-O2")
+    out = run_driver(exe, timeout=600, tail=3000)
     counts = {}
-    for line in out.stdout.splitlines():
+    for line in out.splitlines():
         if line.startswith("category "):
             name, n = line[len("category "):].rsplit(":", 1)
             counts[name.strip()] = int(n)
@@ -40,4 +21,4 @@ def test_switch_edit_matches_mirror_bit_for_bit(tmp_path):
                 "three in a row (3)/ok"):
         assert counts.get(cat, 0) > 0, (cat, counts)
     assert any(k.startswith("on a knot/") for k in counts), counts
-    assert "velocity bracket:" in out.stdout
+    assert "velocity bracket:" in out

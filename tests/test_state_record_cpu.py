@@ -11,15 +11,14 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from native_driver import build_driver
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("state_record")), "test_state_record")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_state_record.cc")])
-    return exe
+    return build_driver("test_state_record.cc", tmp_path_factory.mktemp("state_record"), fp_contract_off=False,
+                        flags=("-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                               "-fno-sanitize-recover=all"))
 
 
 def test_record_round_trips_and_rejections_under_sanitizers(program):
@@ -34,6 +33,5 @@ def test_header_is_plain_cxx(tmp_path):
     src = tmp_path / "plain.cc"
     src.write_text('#include "%s"\nint main() { return sizeof(tpamd::StateRecordHeader) == 192 ? 0 : 1; }\n'
                    % os.path.join(ROOT, "x-edr-trajectory-planning_amd", "csrc", "tpamd_state.h"))
-    exe = str(tmp_path / "plain")
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-Wextra", "-Werror", "-o", exe, str(src)])
+    exe = build_driver(src, tmp_path, opt=None, std="c++14", fp_contract_off=False, flags=("-Wall", "-Wextra", "-Werror"))
     assert subprocess.run([exe]).returncode == 0

@@ -3,29 +3,18 @@ and RescaleTrajectoryBackwardToStop (host/trajectory_buffer.cc, host/rescale_to_
 reference's test cases, and the host/device core of csrc/tpamd_rescale.h, compiled for the host,
 bit-equal to the mirror on seeded trajectories (tests/cpp/test_stop_buffer.cc). No GPU needed."""
 import os
-import subprocess
 
 from conftest import ROOT, PKG_NAME
-
-
-def _build_driver(tmp_path):
-    exe = str(tmp_path / "test_stop_buffer")
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_stop_buffer.cc"),
-           os.path.join(host, "rescale_to_stop.cc"), os.path.join(host, "trajectory_buffer.cc")]
-    subprocess.check_call(cmd)
-    return exe
+from native_driver import build_driver, run_driver
 
 
 def test_stop_core_matches_mirror_bit_for_bit(tmp_path):
-    exe = _build_driver(tmp_path)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "reference cases: done" in out.stdout
+    exe = build_driver("test_stop_buffer.cc", tmp_path, opt="-O2",
+                       extra_sources=("host/rescale_to_stop.cc", "host/trajectory_buffer.cc"))
+    out = run_driver(exe, timeout=600, tail=3000)
+    assert "reference cases: done" in out
     counts = {}
-    for line in out.stdout.splitlines():
+    for line in out.splitlines():
         if line.startswith("category "):
             name, n = line[len("category "):].rsplit(":", 1)
             counts[name.strip()] = int(n)

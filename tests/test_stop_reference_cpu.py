@@ -8,14 +8,13 @@ outputs with the recorded residuals, skip at most 1 % of the steps as ambiguous,
 forms and notice eight mutations; every outcome is reached for every D. No GPU needed."""
 import collections
 import functools
-import os
 import subprocess
 import time
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+import native_driver
 import stop_reference as sr
 
 ALL_DOFS = list(range(1, 17))
@@ -39,13 +38,8 @@ def batch_results(D):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stop_reference") / "test_stop_reference")
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_stop_reference.cc"),
-                           os.path.join(host, "rescale_to_stop.cc"), os.path.join(host, "trajectory_buffer.cc")],
-                          timeout=600)
-    return exe
+    return native_driver.build_driver("test_stop_reference.cc", tmp_path_factory.mktemp("stop_reference"), opt="-O2",
+                                      extra_sources=("host/rescale_to_stop.cc", "host/trajectory_buffer.cc"), timeout=600)
 
 
 def _hex(values):

@@ -9,8 +9,6 @@ within tolerances measured here on the restatement; every category is reached fo
 restatement, the routines and the mirror; the checkers notice mutations. No GPU needed."""
 import collections
 import functools
-import importlib
-import os
 import struct
 import subprocess
 import time
@@ -18,7 +16,7 @@ import time
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG_NAME
+import native_driver
 import switch_reference as sw
 
 ALL_DOFS = list(range(1, 17))
@@ -48,16 +46,8 @@ def checked(D):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    importlib.import_module(PKG_NAME + ".engine").build_library()
-    host = os.path.join(ROOT, PKG_NAME, "host")
-    csrc = os.path.join(ROOT, PKG_NAME, "csrc")
-    subprocess.check_call(["make", "-C", host, "-s"])
-    exe = str(tmp_path_factory.mktemp("switch_reference") / "test_switch_reference")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_switch_reference.cc"),
-                           "-L" + host, "-ltp_host", "-L" + csrc, "-ltpamd", "-Wl,-rpath," + host,
-                           "-Wl,-rpath," + csrc], timeout=600)
-    return exe
+    return native_driver.build_driver("test_switch_reference.cc", tmp_path_factory.mktemp("switch_reference"),
+                                      libs=("host", "engine"), opt="-O2", timeout=600)
 
 
 def _hex(values):

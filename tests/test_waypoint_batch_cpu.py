@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import PKG_NAME, ROOT
+from native_driver import build_driver
 
 NEW_EXPORTS = ("tpamd_fit_joint_waypoints_host", "tpamd_fit_joint_waypoints_device",
                "tpamd_time_waypoint_paths_host", "tpamd_time_waypoint_paths_device")
@@ -49,11 +50,8 @@ def test_exports_and_prototypes():
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("joint_fit") / "test_joint_fit_layout")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "test_joint_fit_layout.cc")])
-    return exe
+    return build_driver("test_joint_fit_layout.cc", tmp_path_factory.mktemp("joint_fit"),
+                        flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
 
 
 def _fit_points(W):

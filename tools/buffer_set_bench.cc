@@ -28,6 +28,10 @@
 #include "../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
 #include "../x-edr-trajectory-planning_amd/host/trajectory_buffer.h"
 
+#define BENCH_SUPPORT_SEED 20261016
+#define BENCH_SUPPORT_MIRROR
+#include "bench_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
 using tpamd::compat::Milliseconds;
@@ -38,28 +42,6 @@ static double now() {
 static double median(std::vector<double> v) {
   std::sort(v.begin(), v.end());
   return v[v.size() / 2];
-}
-
-static unsigned long long g_seed = 20261016;
-static double rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
-static std::shared_ptr<TimeableJointSplinePath> make_path(int D, int N, int W) {
-  auto p = std::make_shared<TimeableJointSplinePath>(
-      JointPathOptions().set_num_dofs(D).set_num_path_samples(N).set_delta_parameter(0.01));
-  std::vector<double> vmax(D), amax(D);
-  for (int d = 0; d < D; d++) { vmax[d] = 1.0 + rnd(); amax[d] = 2.0 + 2.0 * rnd(); }
-  p->SetMaxJointVelocity({vmax.data(), vmax.size()});
-  p->SetMaxJointAcceleration({amax.data(), amax.size()});
-  std::vector<VectorXd> w;
-  for (int i = 0; i < W; i++) {
-    VectorXd v(D);
-    for (int d = 0; d < D; d++) v[d] = 4.0 * rnd() - 2.0;
-    w.push_back(v);
-  }
-  p->SetWaypoints({w.data(), w.size()});
-  return p;
 }
 
 #define HIPCHECK(x)                                                        \

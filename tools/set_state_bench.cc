@@ -22,17 +22,15 @@
 
 #include "../include/tpamd.h"
 
+#define BENCH_SUPPORT_SEED 20261020
+#include "bench_support.h"
+
 static double now() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 static double median(std::vector<double> v) {
   std::sort(v.begin(), v.end());
   return v[v.size() / 2];
-}
-static unsigned long long g_seed = 20261020;
-static double rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
 }
 #define CHECK(expr)                                                      \
   do {                                                                   \

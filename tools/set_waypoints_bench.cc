@@ -23,6 +23,9 @@
 #include "../x-edr-trajectory-planning_amd/host/engine_handle.h"
 #include "../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
 
+#define BENCH_SUPPORT_SEED 20261016
+#include "bench_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
 using tpamd::compat::Milliseconds;
@@ -33,11 +36,6 @@ static double now() {
 static double median(std::vector<double> v) {
   std::sort(v.begin(), v.end());
   return v[v.size() / 2];
-}
-static unsigned long long g_seed = 20261016;
-static double rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
 }
 
 int main(int argc, char **argv) {

@@ -21,6 +21,9 @@
 #include "../x-edr-trajectory-planning_amd/host/path_timing_trajectory.h"
 #include "../x-edr-trajectory-planning_amd/host/path_timing_trajectory_set.h"
 
+#define BENCH_SUPPORT_SEED 20261015
+#include "bench_support.h"
+
 using namespace trajectory_planning;
 using tpamd::compat::FromUnixNanos;
 using tpamd::compat::Milliseconds;
@@ -33,11 +36,6 @@ static double median(std::vector<double> v) {
   return v[v.size() / 2];
 }
 
-static unsigned long long g_seed = 20261015;
-static double rnd() {
-  g_seed = g_seed * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (double)(g_seed >> 11) / 9007199254740992.0;
-}
 static std::vector<VectorXd> waypoints(int W, int D) {
   std::vector<VectorXd> w;
   for (int i = 0; i < W; i++) {
