@@ -30,6 +30,21 @@ def test_header_symbols_are_all_exported(eng):
         assert hasattr(lib, name), name
     assert lib.tpamd_version() == 200
     assert lib.tpamd_error_string(7).decode().startswith("could not connect")
+    # every function carries the restype and argtypes of its declaration; a struct mirror goes to
+    # its parameters by value (ctypes passes the reference) or by byref
+    protos = eng._abi.parse_prototypes(open(os.path.join(ROOT, "include", "tpamd.h")).read())
+    assert list(protos) == eng.ABI_SYMBOLS and len(protos) == 147
+    for name, (restype, argtypes) in protos.items():
+        f = getattr(lib, name)
+        assert f.restype == restype and list(f.argtypes) == argtypes, name
+    assert lib.tpamd_planner_set_sample_at_ticks.argtypes[4] is ctypes.c_int64
+    assert lib.tpamd_rebuild_time_device.argtypes[4] is ctypes.c_size_t
+    assert lib.tpamd_engine_destroy.restype is None and lib.tpamd_profile_mean_ms.restype is ctypes.c_double
+    # NULL engine: refused before anything is read, whichever way the struct goes in
+    bt = eng._JointBatch(1, 7, 100, 4, 0, 0, 0.8)
+    ji, po = eng._JointInputs.from_dict({}), eng._PathOutputs.from_dict({})
+    assert lib.tpamd_time_joint_paths_host(None, bt, ji, po) == lib.tpamd_time_joint_paths_host(
+        None, ctypes.byref(bt), ctypes.byref(ji), ctypes.byref(po)) != 0
 
 
 def test_multi_device_header_symbols_are_all_exported(eng):
@@ -66,6 +81,77 @@ def test_struct_layouts_match_header(eng):
     assert ctypes.sizeof(eng._RowsBatch) == 16
     assert ctypes.sizeof(eng._RowsInputs) == 72
     assert ctypes.sizeof(eng._ResampleArgs) == 16 + 9 * 8 + 8 + 8 + 8 * 8
+
+
+def _mirrors(eng):
+    """Every ctypes mirror the binding exports, by the name of its C struct."""
+    found = {}
+    for value in vars(eng).values():
+        if isinstance(value, type) and issubclass(value, ctypes.Structure) and getattr(value, "_c_name_", None):
+            found[value._c_name_] = value
+    return found
+
+
+def test_every_mirror_has_the_layout_the_compiler_gives_its_struct(eng, tmp_path):
+    """sizeof and every field's offsetof of each mirrored struct, printed by a C++ program that
+    includes include/tpamd.h and names the fields as the mirror does (a field the header lacks
+    does not compile), against ctypes.sizeof and the ctypes field offsets."""
+    from native_driver import build_driver, run_driver
+    mirrors = _mirrors(eng)
+    assert len(mirrors) == 20
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "tpamd.h"', 'int main() {']
+    for c_name, mirror in sorted(mirrors.items()):
+        lines.append('  std::printf("%s sizeof %%zu\\n", sizeof(%s));' % (c_name, c_name))
+        for field, _ in mirror._fields_:
+            lines.append('  std::printf("%s %s %%zu\\n", offsetof(%s, %s));' % (c_name, field, c_name, field))
+    lines += ['  std::printf("ALL OK\\n");', '  return 0;', '}']
+    source = tmp_path / "struct_layouts.cc"
+    source.write_text("\n".join(lines) + "\n")
+    exe = build_driver(str(source), tmp_path, flags=("-I" + os.path.join(ROOT, "include"),))
+    compiled = {}
+    for line in run_driver(exe, tail=0).splitlines()[:-1]:
+        c_name, what, value = line.split()
+        compiled[c_name, what] = int(value)
+    expected = {}
+    for c_name, mirror in mirrors.items():
+        expected[c_name, "sizeof"] = ctypes.sizeof(mirror)
+        for field, _ in mirror._fields_:
+            expected[c_name, field] = getattr(mirror, field).offset
+    assert compiled == expected
+    assert len(expected) > 150          # 20 structs, every field
+
+
+def test_prototype_parser_on_literal_declarations(eng):
+    from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_size_t, c_void_p
+    text = """
+    /* int tpamd_in_a_comment(int x); */
+    int tpamd_version(void);
+    const char *tpamd_error_string(int code);
+    size_t tpamd_engine_workspace_bytes(const tpamd_engine *engine);
+    void tpamd_engine_destroy(tpamd_engine *engine);
+    int tpamd_time_joint_paths_device(tpamd_engine *engine, const tpamd_joint_batch *batch,
+                                      const tpamd_joint_inputs *in,
+                                      const tpamd_path_outputs *out, void *hip_stream);
+    int tpamd_some_readout(tpamd_planner_set *set, int count, const int32_t *ids, const int64_t *start_ns,
+                           int64_t step_ns, int32_t num_ticks, double time_step, double *q, size_t bytes,
+                           tpamd_planner_check *records, tpamd_engine **out);
+    """
+    got = eng._abi.parse_prototypes(text)
+    assert got == {
+        "tpamd_version": (c_int, []),
+        "tpamd_error_string": (c_char_p, [c_int]),
+        "tpamd_engine_workspace_bytes": (c_size_t, [c_void_p]),
+        "tpamd_engine_destroy": (None, [c_void_p]),
+        "tpamd_time_joint_paths_device": (c_int, [c_void_p, POINTER(eng._JointBatch), POINTER(eng._JointInputs),
+                                                  POINTER(eng._PathOutputs), c_void_p]),
+        # a record array the call writes is an address like any other array, mirrored or not
+        "tpamd_some_readout": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p,
+                                       c_size_t, c_void_p, c_void_p]),
+    }
+    for bad in ("int tpamd_x(float gain);", "float tpamd_x(int a);", "int tpamd_x(tpamd_joint_batch by_value);",
+                "char *tpamd_x(void);", "int tpamd_x(unsigned n);"):
+        with pytest.raises(eng.TpamdError, match="no ctypes type"):
+            eng._abi.parse_prototypes(bad)
 
 
 def test_no_gpu_means_loud_failure(eng):

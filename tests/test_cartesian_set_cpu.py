@@ -44,12 +44,16 @@ def test_cartesian_set_exports_are_declared():
     hdr = open(os.path.join(ROOT, "include", "tpamd.h")).read()
     src = open(os.path.join(ROOT, PKG_NAME, "engine.py")).read()
     capi = open(os.path.join(ROOT, PKG_NAME, "csrc", "tpamd_capi.hip")).read()
+    import importlib
+    eng = importlib.import_module(PKG_NAME + ".engine")
+    eng.build_library()
+    lib = eng.load_library()
     for name in ENTRIES:
         assert "int %s(" % name in hdr, name
         assert re.search(r"^int %s\(" % name, capi, re.M), name
-        assert src.count('"%s"' % name) >= 2, name          # the export list and the restype loop
-        assert "L.%s.argtypes" % name in src, name
-    assert '"tpamd_cartesian_window.h"' in src
+        assert name in eng.ABI_SYMBOLS, name                  # the export list, read from the header
+        assert len(getattr(lib, name).argtypes) >= 4, name    # and the prototype, set from its declaration
+    assert os.path.join(ROOT, PKG_NAME, "csrc", "tpamd_cartesian_window.h") in eng._abi.library_sources()
     for method in ("def set_ik_tables(", "def download_ik_table(", "cartesian=False", "table_capacity="):
         assert method in src, method
     cls = open(os.path.join(ROOT, PKG_NAME, "host", "path_timing_trajectory_set.h")).read()

@@ -262,9 +262,7 @@ def test_bad_counts_fail_their_path_alone(env, cases, D, packed):
         out[k] = flat[k][G:G + size].view(*shape)
     ns, fr = t(counts), t(case["first"])
     bt = eng._CartesianBatch(B, D, N, 0, float(case["safety"]))
-    ci = eng._CartesianInputs(*[eng._ptr(inp.get(k)) for k in eng._CARTESIAN_INPUT_KEYS])
-    po = eng._PathOutputs(*[eng._ptr(out.get(k)) for k in (
-        "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index", "max_time_increment", "status", "sd2")])
+    ci, po = eng._CartesianInputs.from_dict(inp), eng._PathOutputs.from_dict(out)
     E = env["E"]
     rc = E._lib.tpamd_time_cartesian_paths_ragged_device(
         E._h, C.byref(bt), C.byref(ci), eng._ptr(ns), eng._ptr(fr) if packed else None, C.byref(po),

@@ -356,11 +356,7 @@ def test_call_level_errors_write_nothing(env):
         # a NULL ref, straight through the C-ABI
         cp = inp["control_points"]
         bt = eng._JointBatch(B, D, N, cp.shape[1], 0, 0, batch["safety"])
-        ji = eng._JointInputs(*[eng._ptr(inp.get(k)) for k in (
-            "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta", "sd_start",
-            "sdd_start", "time_start", "num_samples_per_path")])
-        po = eng._PathOutputs(*[eng._ptr(out.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index", "max_time_increment", "status", "sd2")])
+        ji, po = eng._JointInputs.from_dict(inp), eng._PathOutputs.from_dict(out)
         opt = eng._RefineOptions(2, cases.MAX_SAMPLES, B, 0, 0.0)
         lib = eng.load_library()
         if host:

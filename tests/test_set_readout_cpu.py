@@ -30,9 +30,12 @@ def test_readout_interpolation_matches_mirror_bit_for_bit(tmp_path):
 def test_readout_exports_are_declared():
     """The four readout entry points are in the header and registered with the binding."""
     hdr = open(os.path.join(ROOT, "include", "tpamd.h")).read()
-    src = open(os.path.join(ROOT, PKG_NAME, "engine.py")).read()
+    import importlib
+    eng = importlib.import_module(PKG_NAME + ".engine")
+    eng.build_library()
+    lib = eng.load_library()
     for name in ("tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
                  "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device"):
         assert "int %s(" % name in hdr, name
-        assert '"%s"' % name in src, name
-    assert '"tpamd_readout.h"' in src
+        assert name in eng.ABI_SYMBOLS and len(getattr(lib, name).argtypes) >= 10, name
+    assert os.path.join(ROOT, PKG_NAME, "csrc", "tpamd_readout.h") in eng._abi.library_sources()

@@ -7,22 +7,19 @@ entry point raises.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "csrc")
-_SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_CSRC, "libtpamd.so")   # override: A/B builds
-_SOURCES = ["tpamd_capi.hip", "tpamd_sweep_inst.hip", "tpamd_launch.h", "tpamd_kernels.h", "tpamd_device.h",
-            "tpamd_sweep_joint.h", "tpamd_planner_set.h", "tpamd_cartesian_window.h", "tpamd_stop.h", "tpamd_switch.h", "tpamd_readout.h",
-            "tpamd_rescale.h", "tpamd_buffer.h", "tpamd_fit.h", "tpamd_fit.hip", "tpamd_quat.h", "tpamd_pose_fit.h",
-            "tpamd_pose_fit.hip", "tpamd_retarget.h", "tpamd_retarget.hip", "tpamd_joint_fit.h", "tpamd_joint_fit.hip",
-            "tpamd_check.h", "tpamd_refine.h", "tpamd_refine.hip", "tpamd_state.h", "tpamd_state.hip"]
-_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tpamd.h")
+from . import abi as _abi
+from .abi import (  # noqa: F401  (the declarations and the build: re-exported)
+    ABI_SYMBOLS, DIAG_SO, HIPCC_FLAGS, MULTI_SO, PLAN_DEVICE_INFO_FIELDS, PLAN_RESOURCE_EXHAUSTED,
+    PLANNER_CHECK_DTYPE, PLANNER_STATE_INFO_DTYPE, PLANNER_SUMMARY_DTYPE, REFINE_NO_SLOT, REFINE_NOTHING,
+    REFINE_TOO_LONG, SWEEP_INSTANCES, TpamdError, _CartesianBatch, _CartesianInputs, _CheckOutputs,
+    _FastestStopArgs, _JointBatch, _JointInputs, _PathOutputs, _PlanDeviceInfo, _PlannerCheck, _PlannerSetConfig,
+    _RefineOptions, _RefineOutputs, _ResampleArgs, _RowsBatch, _RowsInputs, _Solution, _StopTrajectoryArgs,
+    _WaypointBatch, _WaypointFitOutputs, _WaypointInputs, _ptr)
 
-HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared",
-               "-std=c++17"]
+_SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_abi._CSRC, "libtpamd.so")   # override: A/B builds
 
 PATH_STATUS = {
     0: "ok", 2: "infeasible_bounds", 3: "s_range", 4: "sd_start_negative",
@@ -32,56 +29,8 @@ PATH_STATUS = {
 
 KERNEL_SWEEP = 4
 
-
-class TpamdError(RuntimeError):
-    pass
-
-
-# (joint count, extra rows) instances of the specialised sweep kernel: one translation unit each
-# (csrc/tpamd_launch.h TPAMD_SWEEP_INSTANCES must list the same pairs)
-SWEEP_INSTANCES = [(3, 0), (4, 0), (5, 0), (6, 0), (7, 0), (8, 0), (14, 0), (6, 2), (7, 2)]
-
-
-def _compile(target, extra_flags, force, verbose):
-    """hipcc -c every translation unit (in parallel: the sweep instances take 10-18 s each), then
-    link. Objects are kept per target under build/ so that a rebuild recompiles everything only
-    when a source changed."""
-    deps = [os.path.join(_CSRC, s) for s in _SOURCES] + [_HEADER]
-    stale = force or not os.path.exists(target) or any(
-        os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
-    if not stale:
-        return target
-    from concurrent.futures import ThreadPoolExecutor
-    objdir = os.path.join(os.path.dirname(_HERE), "build",
-                          "obj_" + os.path.splitext(os.path.basename(target))[0])
-    os.makedirs(objdir, exist_ok=True)
-    flags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags)
-    units = [(os.path.join(objdir, "capi.o"), ["tpamd_capi.hip"]),
-             (os.path.join(objdir, "fit.o"), ["tpamd_fit.hip"]),
-             (os.path.join(objdir, "pose_fit.o"), ["tpamd_pose_fit.hip"]),
-             (os.path.join(objdir, "retarget.o"), ["tpamd_retarget.hip"]),
-             (os.path.join(objdir, "joint_fit.o"), ["tpamd_joint_fit.hip"]),
-             (os.path.join(objdir, "refine.o"), ["tpamd_refine.hip"]),
-             (os.path.join(objdir, "state.o"), ["tpamd_state.hip"])]
-    for d, e in SWEEP_INSTANCES:
-        units.append((os.path.join(objdir, "sweep_%d_%d.o" % (d, e)),
-                      ["-DTPAMD_INST_D=%d" % d, "-DTPAMD_INST_E=%d" % e, "tpamd_sweep_inst.hip"]))
-
-    def one(unit):
-        obj, args = unit
-        cmd = ["hipcc"] + flags + ["-c", "-o", obj] + args[:-1] + [os.path.join(_CSRC, args[-1])]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=_CSRC)
-        return obj
-
-    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-        objs = list(pool.map(one, units))
-    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd, cwd=_CSRC)
-    return target
+# the keys of a Cartesian inputs dict, in struct order (tests fill the struct from them)
+_CARTESIAN_INPUT_KEYS = _CartesianInputs._keys_
 
 
 def build_library(force=False, verbose=False, extra_flags=(), output=None):
@@ -89,268 +38,26 @@ def build_library(force=False, verbose=False, extra_flags=(), output=None):
     global _SO
     if output is not None:
         _SO = output
-    return _compile(_SO, extra_flags, force, verbose)
-
-
-MULTI_SO = os.path.join(_CSRC, "libtpamd_multi.so")
+    return _abi._compile(_SO, extra_flags, force, verbose)
 
 
 def build_multi_library(force=False, verbose=False):
     """libtpamd_multi.so (include/tpamd_multi.h): several devices from one process, on top of
     libtpamd.so and RCCL. Host code only."""
-    src = os.path.join(_CSRC, "tpamd_multi.cc")
-    deps = [src, _HEADER, os.path.join(os.path.dirname(_HEADER), "tpamd_multi.h"), _SO]
-    if force or not os.path.exists(MULTI_SO) or any(
-            os.path.getmtime(d) > os.path.getmtime(MULTI_SO) for d in deps if os.path.exists(d)):
-        cmd = ["hipcc", "-O2", "-fPIC", "-shared", "-std=c++17", "-x", "hip", "--offload-arch=gfx950", src,
-               "-o", MULTI_SO, "-L" + _CSRC, "-ltpamd", "-L/opt/rocm/lib", "-lrccl", "-lpthread",
-               "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=_CSRC)
-    return MULTI_SO
-
-
-DIAG_SO = os.path.join(_CSRC, "libtpamd_diag.so")
+    return _abi._compile_multi(_SO, force, verbose)
 
 
 def build_diagnostic_library(force=False, verbose=False):
     """The -DTPAMD_DIAG variant: in-kernel cycle counters and the literal cross-checks of the
     sweep kernel's shortcuts (tests/test_gpu_parity.py, tools/gpu_diag.py). Not the product."""
-    return _compile(DIAG_SO, ("-DTPAMD_DIAG",), force, verbose)
+    return _abi._compile(DIAG_SO, ("-DTPAMD_DIAG",), force, verbose)
 
-
-class _JointBatch(C.Structure):
-    _fields_ = [("num_paths", C.c_int32), ("num_dofs", C.c_int32), ("num_samples", C.c_int32),
-                ("num_points", C.c_int32), ("max_solver_loops", C.c_int32),
-                ("reserved", C.c_int32), ("constraint_safety", C.c_double)]
-
-
-class _JointInputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
-        "sd_start", "sdd_start", "time_start", "num_samples_per_path")]
-
-
-class _PathOutputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-        "max_time_increment", "status", "sd2")]
-
-
-class _WaypointBatch(C.Structure):
-    _fields_ = [("num_paths", C.c_int32), ("num_dofs", C.c_int32), ("num_samples", C.c_int32),
-                ("max_solver_loops", C.c_int32), ("constraint_safety", C.c_double)]
-
-
-class _WaypointInputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "waypoint_offsets", "waypoints", "rounding", "max_velocity", "max_acceleration",
-        "num_samples_per_path", "delta", "sd_start", "time_start")]
-
-
-class _WaypointFitOutputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("num_points", "path_end", "delta_used", "knots", "control_points")]
-
-
-class _Solution(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("sd2", "sd", "sdd", "status")]
-
-
-_CHECK_OUTPUT_KEYS = ("violations", "worst_excess", "worst_sample", "worst_row", "first_sample")
-
-
-class _CheckOutputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in _CHECK_OUTPUT_KEYS]
-
-
-class _RefineOptions(C.Structure):
-    _fields_ = [("max_rounds", C.c_int32), ("max_samples", C.c_int32), ("max_refined", C.c_int32),
-                ("reserved", C.c_int32), ("tolerance", C.c_double)]
-
-
-class _RefineOutputs(C.Structure):
-    _fields_ = [("check", _CheckOutputs), ("slot", C.c_void_p), ("slot_path", C.c_void_p),
-                ("num_refined", C.c_void_p), ("rounds", C.c_void_p), ("num_samples", C.c_void_p),
-                ("delta", C.c_void_p), ("refined", _PathOutputs), ("refined_check", _CheckOutputs)]
-
-
-# slot[b] below 0 (include/tpamd.h tpamd_refine_outputs)
-REFINE_NOTHING, REFINE_NO_SLOT, REFINE_TOO_LONG = -1, -2, -3
-
-
-class _RowsBatch(C.Structure):
-    _fields_ = [("num_paths", C.c_int32), ("num_samples", C.c_int32), ("num_rows", C.c_int32),
-                ("max_solver_loops", C.c_int32)]
-
-
-class _RowsInputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "a", "b", "lower", "upper", "s_start", "s_end", "sd_start", "sdd_start", "time_start")]
-
-
-class _CartesianBatch(C.Structure):
-    _fields_ = [("num_paths", C.c_int32), ("num_dofs", C.c_int32), ("num_samples", C.c_int32),
-                ("max_solver_loops", C.c_int32), ("constraint_safety", C.c_double)]
-
-
-_CARTESIAN_INPUT_KEYS = ("ik_positions", "jacobians", "max_velocity", "max_acceleration",
-                         "max_translational_velocity", "max_rotational_velocity", "path_start",
-                         "delta", "sd_start", "sdd_start", "time_start")
-
-
-class _CartesianInputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in _CARTESIAN_INPUT_KEYS]
-
-
-class _ResampleArgs(C.Structure):
-    _fields_ = ([("num_paths", C.c_int32), ("num_samples", C.c_int32), ("num_dofs", C.c_int32),
-                 ("max_out", C.c_int32)] +
-                [(n, C.c_void_p) for n in ("time", "s", "sd", "sdd", "q", "qd", "qdd",
-                                           "max_acceleration", "start_sec")] +
-                [("time_step", C.c_double), ("status", C.c_void_p)] +
-                [(n, C.c_void_p) for n in ("out_time", "out_s", "out_sd", "out_sdd", "out_q",
-                                           "out_qd", "out_qdd", "count")])
-
-
-class _FastestStopArgs(C.Structure):
-    _fields_ = ([("num_paths", C.c_int32), ("stride", C.c_int32), ("num_dofs", C.c_int32),
-                 ("reserved", C.c_int32)] +
-                [(n, C.c_void_p) for n in ("time", "s", "qd", "qdd", "count", "max_acceleration",
-                                           "query_time", "stop_parameter", "stop_index", "duration",
-                                           "status", "profile_time", "profile_rate2",
-                                           "profile_drate2")])
-
-
-class _StopTrajectoryArgs(C.Structure):
-    _fields_ = ([("num_paths", C.c_int32), ("stride", C.c_int32), ("num_dofs", C.c_int32),
-                 ("reserved", C.c_int32)] +
-                [(n, C.c_void_p) for n in ("time", "qd", "qdd", "count", "max_acceleration")] +
-                [("time_step", C.c_double)] +
-                [(n, C.c_void_p) for n in ("stop_time", "stop_index", "status", "keep", "first", "last",
-                                           "out_time", "out_qd", "out_qdd")])
-
-
-class _PlannerSetConfig(C.Structure):
-    _fields_ = ([(n, C.c_int32) for n in (
-        "num_planners", "num_dofs", "num_samples", "num_points", "history_capacity",
-        "trajectory_capacity", "sampling_method", "max_planning_iterations")] +
-                [("constraint_safety", C.c_double), ("max_initial_velocity_error", C.c_double),
-                 ("time_step_ns", C.c_int64)])
-
-
-# tpamd_planner_summary
-PLANNER_SUMMARY_DTYPE = np.dtype([
-    ("end_time_ns", np.int64), ("final_decel_start_ns", np.int64), ("start_time_ns", np.int64),
-    ("num_samples", np.int32), ("target_reached", np.int32), ("planned_to_end", np.int32),
-    ("windows", np.int32), ("path_state", np.int32), ("history_count", np.int32),
-    ("status", np.int32), ("reserved", np.int32)])
-
-# tpamd_plan_device_info
-PLAN_DEVICE_INFO_FIELDS = ("num_ok", "num_failed", "num_exhausted", "needed_history", "needed_trajectory",
-                           "max_windows_solved")
-
-
-class _PlanDeviceInfo(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in PLAN_DEVICE_INFO_FIELDS] + [("reserved", C.c_int32 * 2)]
-
-
-PLAN_RESOURCE_EXHAUSTED = 8     # TPAMD_PLAN_RESOURCE_EXHAUSTED
-
-# tpamd_planner_state_info (56 bytes)
-PLANNER_STATE_INFO_DTYPE = np.dtype([
-    ("bytes", np.int64), ("num_points", np.int32), ("history_count", np.int32), ("trajectory_count", np.int32),
-    ("table_rows", np.int32), ("first_row", np.int32), ("has_path", np.int32), ("path_state", np.int32),
-    ("initial_plan", np.int32), ("planned_to_end", np.int32), ("target_reached", np.int32),
-    ("trajectory_first", np.int32), ("status", np.int32)])
-
-# tpamd_planner_check (48 bytes)
-PLANNER_CHECK_DTYPE = np.dtype([
-    ("windows", np.int32), ("violations", np.int32), ("last_window_violations", np.int32),
-    ("worst_window", np.int32), ("worst_sample", np.int32), ("worst_row", np.int32),
-    ("first_window", np.int32), ("first_sample", np.int32),
-    ("worst_excess", np.float64), ("worst_parameter", np.float64)])
-
-
-class _PlannerCheck(C.Structure):
-    _fields_ = ([(n, C.c_int32) for n in PLANNER_CHECK_DTYPE.names[:8]] +
-                [(n, C.c_double) for n in PLANNER_CHECK_DTYPE.names[8:]])
 
 _LIB = None
 
-# every symbol include/tpamd.h declares
-ABI_SYMBOLS = [
-    "tpamd_engine_create", "tpamd_engine_destroy", "tpamd_version", "tpamd_error_string",
-    "tpamd_device_count", "tpamd_shard_bounds", "tpamd_shard_bounds_balanced",
-    "tpamd_engine_reserve", "tpamd_engine_set_pipelining", "tpamd_engine_fence",
-    "tpamd_engine_workspace_bytes",
-    "tpamd_time_joint_paths_device",
-    "tpamd_time_joint_paths_host", "tpamd_sample_joint_paths_host",
-    "tpamd_ik_table_rows", "tpamd_fit_pose_waypoints_host", "tpamd_fit_pose_waypoints_device",
-    "tpamd_fit_joint_waypoints_host", "tpamd_fit_joint_waypoints_device",
-    "tpamd_time_waypoint_paths_host", "tpamd_time_waypoint_paths_device",
-    "tpamd_sample_ik_targets_host", "tpamd_sample_ik_targets_device",
-    "tpamd_time_joint_groups_device", "tpamd_time_joint_groups_host",
-    "tpamd_optimize_rows_device", "tpamd_optimize_rows_host",
-    "tpamd_time_cartesian_paths_device", "tpamd_time_cartesian_paths_host",
-    "tpamd_optimize_rows_ragged_device", "tpamd_optimize_rows_ragged_host",
-    "tpamd_time_cartesian_paths_ragged_device", "tpamd_time_cartesian_paths_ragged_host",
-    "tpamd_sample_pose_splines_device", "tpamd_sample_pose_splines_host",
-    "tpamd_check_rows_device", "tpamd_check_rows_host",
-    "tpamd_check_joint_paths_device", "tpamd_check_joint_paths_host",
-    "tpamd_check_cartesian_paths_device", "tpamd_check_cartesian_paths_host",
-    "tpamd_time_joint_paths_refined_device", "tpamd_time_joint_paths_refined_host",
-    "tpamd_time_waypoint_paths_refined_device", "tpamd_time_waypoint_paths_refined_host",
-    "tpamd_plan_joint_windows_host",
-    "tpamd_planner_set_create", "tpamd_planner_set_destroy", "tpamd_planner_set_upload_paths",
-    "tpamd_planner_set_reset", "tpamd_planner_set_plan", "tpamd_planner_set_download_trajectory",
-    "tpamd_planner_set_reserve", "tpamd_planner_set_capacity", "tpamd_planner_set_plan_device",
-    "tpamd_planner_set_last_plan_bytes", "tpamd_planner_set_device_bytes",
-    "tpamd_planner_set_stop_parameters", "tpamd_planner_set_upload_paths_ragged",
-    "tpamd_planner_set_set_checking", "tpamd_planner_set_checking",
-    "tpamd_planner_set_check_results", "tpamd_planner_set_check_results_device",
-    "tpamd_planner_set_download_path", "tpamd_planner_set_switch_paths", "tpamd_fastest_stop_device", "tpamd_fastest_stop_host",
-    "tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
-    "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device",
-    "tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
-    "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
-    "tpamd_planner_set_switch_paths_rounded", "tpamd_planner_set_retarget", "tpamd_planner_set_retarget_device",
-    "tpamd_compute_stopping_points_host", "tpamd_compute_stopping_points_device",
-    "tpamd_project_points_on_paths_host", "tpamd_project_points_on_paths_device",
-    "tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
-    "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table",
-    "tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
-    "tpamd_planner_set_plan_streaming", "tpamd_planner_set_plan_resume",
-    "tpamd_planner_set_discard_ik_rows", "tpamd_planner_set_ik_table_info",
-    "tpamd_planner_set_download_ik_rows", "tpamd_planner_set_ik_table_device_pointers",
-    "tpamd_sample_ik_target_rows_host", "tpamd_sample_ik_target_rows_device",
-    "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host",
-    "tpamd_planner_set_state_info", "tpamd_planner_set_state_bytes_bound",
-    "tpamd_planner_set_export_state_host", "tpamd_planner_set_export_state_device",
-    "tpamd_planner_set_import_state_host", "tpamd_planner_set_import_state_device",
-    "tpamd_planner_set_copy_planners",
-    "tpamd_buffer_set_create", "tpamd_buffer_set_destroy", "tpamd_buffer_set_reserve", "tpamd_buffer_set_capacity",
-    "tpamd_buffer_set_device_bytes",
-    "tpamd_buffer_set_insert", "tpamd_buffer_set_insert_device",
-    "tpamd_buffer_set_insert_from_planner_set", "tpamd_buffer_set_insert_from_planner_set_device",
-    "tpamd_buffer_set_append_sample", "tpamd_buffer_set_append_sample_device",
-    "tpamd_buffer_set_discard_before", "tpamd_buffer_set_discard_before_device",
-    "tpamd_buffer_set_stop_before_time", "tpamd_buffer_set_stop_before_time_device",
-    "tpamd_buffer_set_sample_at_ticks", "tpamd_buffer_set_sample_at_ticks_device",
-    "tpamd_buffer_set_add_offset", "tpamd_buffer_set_add_offset_device",
-    "tpamd_buffer_set_clear", "tpamd_buffer_set_clear_device",
-    "tpamd_buffer_set_info", "tpamd_buffer_set_info_device",
-    "tpamd_buffer_set_download", "tpamd_buffer_set_download_device",
-    "tpamd_find_max_sd2_host", "tpamd_query_device", "tpamd_resample_uniform_device",
-    "tpamd_resample_uniform_host", "tpamd_resample_skip_device", "tpamd_resample_skip_host",
-    "tpamd_debug_copy_boundary", "tpamd_debug_keep_boundary", "tpamd_debug_copy_diag", "tpamd_debug_copy_diag_ext",
-    "tpamd_debug_kernel_vgprs",
-    "tpamd_rebuild_time_device", "tpamd_profile_reset", "tpamd_profile_enable",
-    "tpamd_profile_mean_ms", "tpamd_profile_kernel_name", "tpamd_profile_num_kernels",
-]
-
 
 def load_library():
+    """libtpamd.so with the restype and argtypes of every function include/tpamd.h declares."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -365,272 +72,8 @@ def load_library():
         import torch  # noqa: F401
     except ImportError:
         pass
-    L = C.CDLL(_SO)
-    vp, i = C.c_void_p, C.c_int
-    L.tpamd_engine_create.restype = i
-    L.tpamd_engine_create.argtypes = [i, C.POINTER(vp)]
-    L.tpamd_engine_destroy.argtypes = [vp]
-    L.tpamd_version.restype = i
-    L.tpamd_error_string.restype = C.c_char_p
-    L.tpamd_error_string.argtypes = [i]
-    L.tpamd_device_count.restype = i
-    L.tpamd_shard_bounds.restype = None
-    L.tpamd_shard_bounds.argtypes = [i, i, vp]
-    L.tpamd_shard_bounds_balanced.restype = None
-    L.tpamd_shard_bounds_balanced.argtypes = [i, vp, i, vp]
-    L.tpamd_engine_reserve.restype = i
-    L.tpamd_engine_reserve.argtypes = [vp, i, i, i]
-    L.tpamd_engine_set_pipelining.restype = i
-    L.tpamd_engine_set_pipelining.argtypes = [vp, i]
-    L.tpamd_engine_fence.restype = i
-    L.tpamd_engine_fence.argtypes = [vp, vp]
-    L.tpamd_engine_workspace_bytes.restype = C.c_size_t
-    L.tpamd_engine_workspace_bytes.argtypes = [vp]
-    L.tpamd_time_joint_paths_device.restype = i
-    L.tpamd_time_joint_paths_device.argtypes = [vp, C.POINTER(_JointBatch),
-                                                C.POINTER(_JointInputs),
-                                                C.POINTER(_PathOutputs), vp]
-    L.tpamd_time_joint_paths_host.restype = i
-    L.tpamd_time_joint_paths_host.argtypes = [vp, C.POINTER(_JointBatch),
-                                              C.POINTER(_JointInputs), C.POINTER(_PathOutputs)]
-    L.tpamd_time_joint_groups_device.restype = i
-    L.tpamd_time_joint_groups_device.argtypes = [vp, i, C.POINTER(_JointBatch), C.POINTER(_JointInputs),
-                                                 C.POINTER(_PathOutputs), vp]
-    L.tpamd_time_joint_groups_host.restype = i
-    L.tpamd_time_joint_groups_host.argtypes = [vp, i, C.POINTER(_JointBatch), C.POINTER(_JointInputs),
-                                               C.POINTER(_PathOutputs)]
-    L.tpamd_sample_joint_paths_host.restype = i
-    L.tpamd_sample_joint_paths_host.argtypes = [vp, i, i, i, i] + [vp] * 7
-    L.tpamd_optimize_rows_device.restype = i
-    L.tpamd_optimize_rows_device.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs),
-                                             C.POINTER(_PathOutputs), vp]
-    L.tpamd_optimize_rows_host.restype = i
-    L.tpamd_optimize_rows_host.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs),
-                                           C.POINTER(_PathOutputs)]
-    L.tpamd_time_cartesian_paths_device.restype = i
-    L.tpamd_time_cartesian_paths_device.argtypes = [vp, C.POINTER(_CartesianBatch),
-                                                    C.POINTER(_CartesianInputs),
-                                                    C.POINTER(_PathOutputs), vp]
-    L.tpamd_time_cartesian_paths_host.restype = i
-    L.tpamd_time_cartesian_paths_host.argtypes = [vp, C.POINTER(_CartesianBatch),
-                                                  C.POINTER(_CartesianInputs),
-                                                  C.POINTER(_PathOutputs)]
-    sol, cko = C.POINTER(_Solution), C.POINTER(_CheckOutputs)
-    L.tpamd_check_rows_device.restype = i
-    L.tpamd_check_rows_device.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp, sol, cko, vp]
-    L.tpamd_check_rows_host.restype = i
-    L.tpamd_check_rows_host.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp, sol, cko]
-    L.tpamd_check_joint_paths_device.restype = i
-    L.tpamd_check_joint_paths_device.argtypes = [vp, C.POINTER(_JointBatch), C.POINTER(_JointInputs), vp, sol, cko,
-                                                 vp]
-    L.tpamd_check_joint_paths_host.restype = i
-    L.tpamd_check_joint_paths_host.argtypes = [vp, C.POINTER(_JointBatch), C.POINTER(_JointInputs), vp, sol, cko]
-    L.tpamd_check_cartesian_paths_device.restype = i
-    L.tpamd_check_cartesian_paths_device.argtypes = [vp, C.POINTER(_CartesianBatch), C.POINTER(_CartesianInputs),
-                                                     vp, vp, sol, cko, vp]
-    L.tpamd_check_cartesian_paths_host.restype = i
-    L.tpamd_check_cartesian_paths_host.argtypes = [vp, C.POINTER(_CartesianBatch), C.POINTER(_CartesianInputs),
-                                                   vp, vp, C.c_int64, sol, cko]
-    L.tpamd_optimize_rows_ragged_device.restype = i
-    L.tpamd_optimize_rows_ragged_device.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp,
-                                                    C.POINTER(_PathOutputs), vp]
-    L.tpamd_optimize_rows_ragged_host.restype = i
-    L.tpamd_optimize_rows_ragged_host.argtypes = [vp, C.POINTER(_RowsBatch), C.POINTER(_RowsInputs), vp,
-                                                  C.POINTER(_PathOutputs)]
-    L.tpamd_time_cartesian_paths_ragged_device.restype = i
-    L.tpamd_time_cartesian_paths_ragged_device.argtypes = [vp, C.POINTER(_CartesianBatch),
-                                                           C.POINTER(_CartesianInputs), vp, vp,
-                                                           C.POINTER(_PathOutputs), vp]
-    L.tpamd_time_cartesian_paths_ragged_host.restype = i
-    L.tpamd_time_cartesian_paths_ragged_host.argtypes = [vp, C.POINTER(_CartesianBatch),
-                                                         C.POINTER(_CartesianInputs), vp, vp, C.c_int64,
-                                                         C.POINTER(_PathOutputs)]
-    L.tpamd_sample_pose_splines_host.restype = i
-    L.tpamd_sample_pose_splines_host.argtypes = [vp, i, i, i] + [vp] * 6
-    L.tpamd_sample_pose_splines_device.restype = i
-    L.tpamd_sample_pose_splines_device.argtypes = [vp, i, i, i] + [vp] * 6 + [vp]
-    L.tpamd_ik_table_rows.restype = i
-    L.tpamd_ik_table_rows.argtypes = [C.c_double, C.c_double, i]
-    for name in ("tpamd_fit_pose_waypoints_host", "tpamd_fit_pose_waypoints_device",
-                 "tpamd_sample_ik_targets_host", "tpamd_sample_ik_targets_device"):
-        getattr(L, name).restype = i
-    L.tpamd_fit_pose_waypoints_host.argtypes = [vp, i, i] + [vp] * 13
-    L.tpamd_fit_pose_waypoints_device.argtypes = [vp, i, i] + [vp] * 13 + [vp]
-    L.tpamd_sample_ik_targets_host.argtypes = [vp, i, i] + [vp] * 9
-    L.tpamd_sample_ik_targets_device.argtypes = [vp, i, i] + [vp] * 9 + [vp]
-    for name in ("tpamd_fit_joint_waypoints_host", "tpamd_fit_joint_waypoints_device",
-                 "tpamd_time_waypoint_paths_host", "tpamd_time_waypoint_paths_device"):
-        getattr(L, name).restype = i
-    L.tpamd_fit_joint_waypoints_host.argtypes = [vp, i, i] + [vp] * 9
-    L.tpamd_fit_joint_waypoints_device.argtypes = [vp, i, i] + [vp] * 9 + [vp]
-    L.tpamd_time_waypoint_paths_host.argtypes = [vp] * 5
-    L.tpamd_time_waypoint_paths_device.argtypes = [vp] * 5 + [vp]
-    for name in ("tpamd_time_joint_paths_refined_device", "tpamd_time_joint_paths_refined_host",
-                 "tpamd_time_waypoint_paths_refined_device", "tpamd_time_waypoint_paths_refined_host"):
-        getattr(L, name).restype = i
-    L.tpamd_time_joint_paths_refined_device.argtypes = [vp] * 6 + [vp]
-    L.tpamd_time_joint_paths_refined_host.argtypes = [vp] * 6
-    L.tpamd_time_waypoint_paths_refined_device.argtypes = [vp] * 7 + [vp]
-    L.tpamd_time_waypoint_paths_refined_host.argtypes = [vp] * 7
-    L.tpamd_find_max_sd2_host.restype = i
-    L.tpamd_find_max_sd2_host.argtypes = [vp, i, i] + [vp] * 7
-    L.tpamd_query_device.restype = i
-    L.tpamd_query_device.argtypes = [vp, i, i, i] + [vp] * 10 + [vp]
-    L.tpamd_resample_uniform_device.restype = i
-    L.tpamd_resample_uniform_device.argtypes = [vp, C.POINTER(_ResampleArgs), vp]
-    L.tpamd_resample_uniform_host.restype = i
-    L.tpamd_resample_uniform_host.argtypes = [vp, C.POINTER(_ResampleArgs)]
-    L.tpamd_resample_skip_device.restype = i
-    L.tpamd_resample_skip_device.argtypes = [vp, C.POINTER(_ResampleArgs), vp]
-    L.tpamd_resample_skip_host.restype = i
-    L.tpamd_resample_skip_host.argtypes = [vp, C.POINTER(_ResampleArgs)]
-    L.tpamd_fastest_stop_device.restype = i
-    L.tpamd_fastest_stop_device.argtypes = [vp, C.POINTER(_FastestStopArgs), vp]
-    L.tpamd_fastest_stop_host.restype = i
-    L.tpamd_fastest_stop_host.argtypes = [vp, C.POINTER(_FastestStopArgs)]
-    L.tpamd_planner_set_stop_parameters.restype = i
-    L.tpamd_planner_set_stop_parameters.argtypes = [vp, i] + [vp] * 5
-    for name in ("tpamd_planner_set_set_checking", "tpamd_planner_set_checking", "tpamd_planner_set_check_results",
-                 "tpamd_planner_set_check_results_device"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_set_checking.argtypes = [vp, i]
-    L.tpamd_planner_set_checking.argtypes = [vp]
-    L.tpamd_planner_set_check_results.argtypes = [vp, i, vp, vp]
-    L.tpamd_planner_set_check_results_device.argtypes = [vp, i, vp, vp, vp]
-    i64 = C.c_int64
-    for name in ("tpamd_planner_set_sample_at_ticks", "tpamd_planner_set_sample_at_ticks_device",
-                 "tpamd_planner_set_download_trajectories", "tpamd_planner_set_download_trajectories_device"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_sample_at_ticks.argtypes = [vp, i, vp, vp, i64, i] + [vp] * 4
-    L.tpamd_planner_set_sample_at_ticks_device.argtypes = [vp, i, vp, vp, i64, i] + [vp] * 4 + [vp]
-    L.tpamd_planner_set_download_trajectories.argtypes = [vp, i, vp, vp, i64] + [vp] * 7
-    L.tpamd_planner_set_download_trajectories_device.argtypes = [vp, i, vp, vp, i64] + [vp] * 7 + [vp]
-    for name in ("tpamd_planner_set_stop_trajectories", "tpamd_planner_set_stop_trajectories_device",
-                 "tpamd_stop_trajectories_device", "tpamd_stop_trajectories_host"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_stop_trajectories.argtypes = [vp, i, vp, vp, vp, C.c_double, vp, vp, vp, i64] + [vp] * 4
-    L.tpamd_planner_set_stop_trajectories_device.argtypes = (
-        [vp, i, vp, vp, vp, C.c_double, vp, vp, vp, i64] + [vp] * 4 + [vp])
-    L.tpamd_stop_trajectories_device.argtypes = [vp, vp, vp]
-    dbl = C.c_double
-    for name, args in (
-            ("create", [vp, i, i, i, dbl, C.POINTER(vp)]), ("reserve", [vp, i]), ("capacity", [vp]),
-            ("insert", [vp, i] + [vp] * 7), ("insert_device", [vp, i, vp, vp, i64] + [vp] * 6),
-            ("insert_from_planner_set", [vp, vp, i, vp, vp, vp]),
-            ("insert_from_planner_set_device", [vp, vp, i, vp, vp, vp, vp]),
-            ("append_sample", [vp, i] + [vp] * 6), ("append_sample_device", [vp, i] + [vp] * 7),
-            ("discard_before", [vp, i, vp, vp, vp]), ("discard_before_device", [vp, i] + [vp] * 5),
-            ("stop_before_time", [vp, i, vp, vp, vp, vp, dbl, vp]),
-            ("stop_before_time_device", [vp, i, vp, vp, vp, vp, dbl, vp, vp]),
-            ("sample_at_ticks", [vp, i, vp, vp, i64, i] + [vp] * 4),
-            ("sample_at_ticks_device", [vp, i, vp, vp, i64, i] + [vp] * 5),
-            ("add_offset", [vp, i, vp, vp, vp]), ("add_offset_device", [vp, i] + [vp] * 5),
-            ("clear", [vp, i, vp]), ("clear_device", [vp, i, vp, vp, vp]),
-            ("info", [vp, i] + [vp] * 7), ("info_device", [vp, i] + [vp] * 8),
-            ("download", [vp, i, vp, vp, i64] + [vp] * 4), ("download_device", [vp, i, vp, vp, i64] + [vp] * 5)):
-        f = getattr(L, "tpamd_buffer_set_" + name)
-        f.restype = i
-        f.argtypes = args
-    L.tpamd_buffer_set_destroy.restype = None
-    L.tpamd_buffer_set_destroy.argtypes = [vp]
-    L.tpamd_buffer_set_device_bytes.restype = C.c_size_t
-    L.tpamd_buffer_set_device_bytes.argtypes = [vp]
-    L.tpamd_stop_trajectories_host.argtypes = [vp, vp]
-    # planner sets (PlannerSet)
-    for name in ("tpamd_planner_set_create", "tpamd_planner_set_upload_paths",
-                 "tpamd_planner_set_upload_paths_ragged", "tpamd_planner_set_download_path",
-                 "tpamd_planner_set_reset", "tpamd_planner_set_plan",
-                 "tpamd_planner_set_download_trajectory", "tpamd_planner_set_switch_paths",
-                 "tpamd_planner_set_set_waypoints", "tpamd_planner_set_set_waypoints_device",
-                 "tpamd_planner_set_create_cartesian", "tpamd_planner_set_upload_ik_tables",
-                 "tpamd_planner_set_upload_ik_tables_device", "tpamd_planner_set_download_ik_table"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_create_cartesian.argtypes = [vp, C.POINTER(_PlannerSetConfig), i, C.POINTER(vp)]
-    L.tpamd_planner_set_upload_ik_tables.argtypes = [vp, i] + [vp] * 12
-    L.tpamd_planner_set_upload_ik_tables_device.argtypes = [vp, i] + [vp] * 12 + [vp]
-    L.tpamd_planner_set_download_ik_table.argtypes = [vp, i, vp, vp, vp, i]
-    for name in ("tpamd_planner_set_append_ik_rows", "tpamd_planner_set_append_ik_rows_device",
-                 "tpamd_planner_set_plan_streaming", "tpamd_planner_set_plan_resume",
-                 "tpamd_sample_ik_target_rows_host", "tpamd_sample_ik_target_rows_device"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_append_ik_rows.argtypes = [vp, i] + [vp] * 4
-    L.tpamd_planner_set_append_ik_rows_device.argtypes = [vp, i] + [vp] * 4 + [vp]
-    L.tpamd_planner_set_plan_streaming.argtypes = [vp] + [vp] * 6
-    L.tpamd_planner_set_plan_resume.argtypes = [vp] + [vp] * 4
-    for name in ("tpamd_planner_set_discard_ik_rows", "tpamd_planner_set_ik_table_info",
-                 "tpamd_planner_set_download_ik_rows", "tpamd_planner_set_ik_table_device_pointers"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_discard_ik_rows.argtypes = [vp, i, vp, vp, vp]
-    L.tpamd_planner_set_ik_table_info.argtypes = [vp, i, vp, vp, vp]
-    L.tpamd_planner_set_download_ik_rows.argtypes = [vp, i, vp, vp, vp, vp, i]
-    L.tpamd_planner_set_ik_table_device_pointers.argtypes = [vp, vp, vp]
-    L.tpamd_sample_ik_target_rows_host.argtypes = [vp, i, i] + [vp] * 10
-    L.tpamd_sample_ik_target_rows_device.argtypes = [vp, i, i] + [vp] * 10 + [vp]
-    L.tpamd_planner_set_create.argtypes = [vp, C.POINTER(_PlannerSetConfig), C.POINTER(vp)]
-    L.tpamd_planner_set_destroy.restype = None
-    L.tpamd_planner_set_destroy.argtypes = [vp]
-    L.tpamd_planner_set_upload_paths.argtypes = [vp, i] + [vp] * 8
-    L.tpamd_planner_set_upload_paths_ragged.argtypes = [vp, i] + [vp] * 9
-    L.tpamd_planner_set_download_path.argtypes = [vp, i, vp, vp, vp, i]
-    L.tpamd_planner_set_reset.argtypes = [vp, i, vp]
-    L.tpamd_planner_set_plan.argtypes = [vp, vp, vp, vp]
-    for name in ("tpamd_planner_set_reserve", "tpamd_planner_set_capacity", "tpamd_planner_set_plan_device"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_reserve.argtypes = [vp, i, i]
-    L.tpamd_planner_set_capacity.argtypes = [vp, vp, vp]
-    L.tpamd_planner_set_plan_device.argtypes = [vp, vp, vp, i, vp, vp, vp]
-    L.tpamd_planner_set_download_trajectory.argtypes = [vp, i, i, i] + [vp] * 7
-    L.tpamd_planner_set_switch_paths.argtypes = [vp, i] + [vp] * 8
-    L.tpamd_planner_set_set_waypoints.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6
-    L.tpamd_planner_set_set_waypoints_device.argtypes = [vp, i, vp, vp, vp, C.c_double] + [vp] * 6 + [vp]
-    for name in ("tpamd_planner_set_switch_paths_rounded", "tpamd_planner_set_retarget",
-                 "tpamd_planner_set_retarget_device", "tpamd_compute_stopping_points_host",
-                 "tpamd_compute_stopping_points_device", "tpamd_project_points_on_paths_host",
-                 "tpamd_project_points_on_paths_device"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_switch_paths_rounded.argtypes = [vp, i] + [vp] * 5 + [C.c_double] + [vp] * 3
-    L.tpamd_planner_set_retarget.argtypes = [vp, i] + [vp] * 4 + [C.c_double] + [vp] * 9
-    L.tpamd_planner_set_retarget_device.argtypes = [vp, i] + [vp] * 4 + [C.c_double] + [vp] * 9 + [vp]
-    L.tpamd_compute_stopping_points_host.argtypes = [vp, i, i] + [vp] * 6
-    L.tpamd_compute_stopping_points_device.argtypes = [vp, i, i] + [vp] * 6 + [vp]
-    L.tpamd_project_points_on_paths_host.argtypes = [vp, i, i] + [vp] * 8
-    L.tpamd_project_points_on_paths_device.argtypes = [vp, i, i] + [vp] * 8 + [vp]
-    for name in ("tpamd_planner_set_state_info", "tpamd_planner_set_export_state_host",
-                 "tpamd_planner_set_export_state_device", "tpamd_planner_set_import_state_host",
-                 "tpamd_planner_set_import_state_device", "tpamd_planner_set_copy_planners"):
-        getattr(L, name).restype = i
-    L.tpamd_planner_set_state_info.argtypes = [vp, i, vp, vp]
-    L.tpamd_planner_set_state_bytes_bound.restype = C.c_size_t
-    L.tpamd_planner_set_state_bytes_bound.argtypes = [vp]
-    L.tpamd_planner_set_export_state_host.argtypes = [vp, i] + [vp] * 4
-    L.tpamd_planner_set_export_state_device.argtypes = [vp, i] + [vp] * 4 + [vp]
-    L.tpamd_planner_set_import_state_host.argtypes = [vp, i] + [vp] * 5
-    L.tpamd_planner_set_import_state_device.argtypes = [vp, i] + [vp] * 5 + [vp]
-    L.tpamd_planner_set_copy_planners.argtypes = [vp, vp, vp, vp, i, vp, vp]
-    L.tpamd_planner_set_last_plan_bytes.restype = None
-    L.tpamd_planner_set_last_plan_bytes.argtypes = [vp, vp, vp]
-    L.tpamd_planner_set_device_bytes.restype = C.c_size_t
-    L.tpamd_planner_set_device_bytes.argtypes = [vp]
-    L.tpamd_debug_copy_boundary.restype = i
-    L.tpamd_debug_copy_boundary.argtypes = [vp, i, i] + [vp] * 6
-    L.tpamd_debug_keep_boundary.argtypes = [vp, i]
-    L.tpamd_debug_copy_diag.restype = i
-    L.tpamd_debug_copy_diag.argtypes = [vp, i, vp]
-    L.tpamd_debug_copy_diag_ext.restype = i
-    L.tpamd_debug_copy_diag_ext.argtypes = [vp, i, vp]
-    L.tpamd_debug_kernel_vgprs.restype = i
-    L.tpamd_debug_kernel_vgprs.argtypes = [vp, i]
-    L.tpamd_rebuild_time_device.restype = i
-    L.tpamd_rebuild_time_device.argtypes = [vp, i, i, i, C.c_size_t, vp, vp, vp, vp, vp, vp]
-    L.tpamd_profile_reset.argtypes = [vp]
-    L.tpamd_profile_enable.argtypes = [vp, i]
-    L.tpamd_profile_mean_ms.restype = C.c_double
-    L.tpamd_profile_mean_ms.argtypes = [vp, i, C.POINTER(i)]
-    L.tpamd_profile_kernel_name.restype = C.c_char_p
-    L.tpamd_profile_kernel_name.argtypes = [i]
-    L.tpamd_profile_num_kernels.restype = i
-    _LIB = L
-    return L
+    _LIB = _abi.declare(C.CDLL(_SO))
+    return _LIB
 
 
 def _check(rc, what):
@@ -639,15 +82,193 @@ def _check(rc, what):
                                                 load_library().tpamd_error_string(rc).decode()))
 
 
-def _ptr(t):
-    """Device/host pointer of a torch tensor or numpy array (None -> NULL)."""
-    if t is None:
+def _stream_ptr(stream):
+    if stream is None:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if isinstance(stream, int):
+        return C.c_void_p(stream)
+    return C.c_void_p(stream.cuda_stream)
+
+
+def _is_cuda(t):
+    return hasattr(t, "is_cuda") and t.is_cuda
+
+
+def _host(x, dtype, shape=None, what="argument"):
+    """A C-contiguous numpy copy of a host (or CUDA) array-like; None stays None."""
+    if x is None:
         return None
-    if isinstance(t, np.ndarray):
-        assert t.flags["C_CONTIGUOUS"]
-        return t.ctypes.data
-    assert t.is_contiguous()
-    return t.data_ptr()
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(x, dtype=dtype))
+    if shape is not None and a.shape != tuple(shape):
+        raise TpamdError("%s has shape %s, expected %s" % (what, a.shape, tuple(shape)))
+    return a
+
+
+def _cpu_array(x, dtype):
+    """A C-contiguous numpy array of a CPU tensor or array (host=True arguments); None stays None."""
+    return None if x is None else np.ascontiguousarray(x.numpy() if hasattr(x, "numpy") else x, dtype=dtype)
+
+
+# ---------------------------------------------------------------- array backends
+# A method that serves host arrays through a host entry and CUDA tensors through a _device entry
+# has one body; what differs -- how an argument is coerced, how an output is made and in what type
+# results go back -- is behind one of these two.
+class _Numpy:
+    """Host arrays: C-contiguous numpy arrays, handed back as they are or as CPU tensors."""
+    host = True
+    device = None
+    float64, int32, int64 = np.float64, np.int32, np.int64
+    array = staticmethod(_host)
+
+    def __init__(self, as_torch=False):
+        self.as_torch = as_torch
+
+    def per(self, x, n, what):
+        """One float64 per entry, from [n] values or one number."""
+        return _host(np.broadcast_to(_host(x, np.float64), (n,)), np.float64, (n,), what)
+
+    def zeros(self, shape, dtype=np.float64):
+        return np.zeros(shape, dtype=dtype)
+
+    def full(self, shape, value, dtype=np.float64):
+        return np.full(shape, value, dtype=dtype)
+
+    def result(self, a):
+        if self.as_torch:
+            import torch
+            return torch.from_numpy(a)
+        return a
+
+
+class _Torch:
+    """Contiguous tensors on one CUDA device, handed back as they are."""
+    host = False
+
+    def __init__(self, device):
+        import torch
+        self.torch, self.device = torch, device
+        self.float64, self.int32, self.int64 = torch.float64, torch.int32, torch.int64
+
+    def array(self, x, dtype, shape=None, what="argument"):
+        if x is None:
+            return None
+        t = self.torch.as_tensor(x, dtype=dtype, device=self.device).contiguous()
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise TpamdError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
+        return t
+
+    def per(self, x, n, what):
+        x = x if hasattr(x, "shape") else self.torch.full((n,), float(x), dtype=self.float64)
+        return self.array(x, self.float64, (n,), what)
+
+    def zeros(self, shape, dtype=None):
+        return self.torch.zeros(shape, dtype=dtype or self.float64, device=self.device)
+
+    def full(self, shape, value, dtype=None):
+        shape = shape if isinstance(shape, tuple) else (shape,)
+        return self.torch.full(shape, value, dtype=dtype or self.float64, device=self.device)
+
+    def result(self, t):
+        return t
+
+
+_NUMPY, _NUMPY_AS_TORCH = _Numpy(), _Numpy(as_torch=True)
+
+
+def _backend(x, as_torch=False):
+    """The backend of a call whose argument x decides the side: x's device if it is a CUDA tensor."""
+    if _is_cuda(x):
+        return _Torch(x.device)
+    return _NUMPY_AS_TORCH if as_torch else _NUMPY
+
+
+def _waypoint_offsets(offsets):
+    """Host int32 waypoint offsets [B + 1] and B."""
+    off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
+    if off.shape[0] < 1:
+        raise TpamdError("waypoint offsets need at least one entry")
+    return off, off.shape[0] - 1
+
+
+def _fit_sizes(off):
+    """Control points and knots of the splines fitted to W = diff(off) waypoints each: (sum P, sum P + 3)."""
+    W = np.diff(off.astype(np.int64))
+    npts = np.where(W < 1, 0, np.where(W == 1, 4, 3 * W - 2))
+    return int(npts.sum()), int((npts + 3 * (npts > 0)).sum())
+
+
+# ---------------------------------------------------------------- the objects behind a C handle
+# what _Native._call hands to ctypes unchanged: numbers, struct mirrors (and arrays of them), byref()
+# results and stream pointers; everything else is an array or a tensor and goes in as its address
+_AS_IS = (int, float, C.Structure, C.Array, C._SimpleCData, type(C.byref(C.c_int())), np.integer, np.floating)
+_AS_IS_TYPES = frozenset([type(None), int, float, C.c_void_p, _AS_IS[5]] + list(_abi.MIRRORS.values()))   # the usual
+
+
+class _Native:
+    """What Engine, PlannerSet and BufferSet share: the C handle with its lifecycle, and the one way
+    an entry point is called."""
+    _kind = _destroy = None          # "planner set", "tpamd_planner_set_destroy"
+    _host_suffix = "_host"           # the host entry of a pair: tpamd_x_host (engine) or tpamd_x (sets)
+
+    def _adopt(self, handle):
+        self._h = handle
+        self._keepalive = {}
+
+    def _release(self):
+        """What must happen before the handle is destroyed."""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._release()
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+            self._keepalive = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise TpamdError("the %s is closed" % self._kind)
+        return self._h
+
+    def _device(self):
+        """The torch backend of this object's GPU."""
+        import torch
+        return _Torch(torch.device("cuda", self.device))
+
+    def _call(self, entry, *args, host=None, stream=None, keep=()):
+        """One C-ABI call on this object's handle; a non-zero return raises TpamdError with the
+        symbol's name. host None: `entry` is the symbol. host True / False: the symbol is the host /
+        _device entry of the pair `entry` names, and the _device entry gets `stream` as its last
+        argument. Arrays and tensors go in as they are (None: NULL), struct mirrors by reference.
+        A _device call only enqueues, so what it was handed (and `keep`: what the structs point to
+        that the caller does not own) stays referenced until the next call of the same entry."""
+        if host is None:
+            name = entry
+        elif host:
+            name = entry + self._host_suffix
+        else:
+            name = entry + "_device"
+            args += (_stream_ptr(stream),)
+        rc = getattr(self._lib, name)(self._h or self._handle(), *[
+            a if type(a) in _AS_IS_TYPES or isinstance(a, _AS_IS) else _ptr(a) for a in args])
+        if rc:
+            _check(rc, name)
+        if not (host is None or host):
+            self._keepalive[name] = args + keep if keep else args
 
 
 def _int32_array(t, n, name):
@@ -666,41 +287,32 @@ def _int32_array(t, n, name):
     return t
 
 
-class Engine:
+class Engine(_Native):
     """One engine per GPU (tpamd_engine_create/destroy)."""
+    _destroy = "tpamd_engine_destroy"
 
     def __init__(self, device=0):
         self._lib = load_library()
         h = C.c_void_p()
         _check(self._lib.tpamd_engine_create(int(device), C.byref(h)), "tpamd_engine_create")
-        self._h = h
+        self._adopt(h)
         self.device = int(device)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tpamd_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _handle(self):
+        return self._h               # closed: NULL, which every entry refuses
 
     def reserve(self, num_paths, num_samples, num_rows):
-        _check(self._lib.tpamd_engine_reserve(self._h, num_paths, num_samples, num_rows),
-               "tpamd_engine_reserve")
+        self._call("tpamd_engine_reserve", num_paths, num_samples, num_rows)
 
     def set_pipelining(self, mode=1):
         """0 off; 1: the sampling/LP kernel of a joint solve overlaps the previous solve's sweep;
         2: sweeps of consecutive solves overlap as well, outputs ordered by the next call or
         fence() (include/tpamd.h tpamd_engine_set_pipelining: inputs must be ready at call time)."""
-        _check(self._lib.tpamd_engine_set_pipelining(self._h, int(mode)),
-               "tpamd_engine_set_pipelining")
+        self._call("tpamd_engine_set_pipelining", int(mode))
 
     def fence(self, stream=None):
         """Order `stream` (default: torch's current stream) behind every solve issued so far."""
-        _check(self._lib.tpamd_engine_fence(self._h, _stream_ptr(stream)), "tpamd_engine_fence")
+        self._call("tpamd_engine_fence", _stream_ptr(stream))
 
     @property
     def workspace_bytes(self):
@@ -717,20 +329,8 @@ class Engine:
         cp = inputs["control_points"]
         B, P, D = cp.shape
         bt = _JointBatch(B, D, int(num_samples), P, int(max_solver_loops), 0, float(safety))
-        ji = _JointInputs(*[_ptr(inputs.get(k)) for k in (
-            "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
-            "sd_start", "sdd_start", "time_start", "num_samples_per_path")])
-        po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-            "max_time_increment", "status", "sd2")])
-        if host:
-            _check(self._lib.tpamd_time_joint_paths_host(self._h, C.byref(bt), C.byref(ji),
-                                                         C.byref(po)),
-                   "tpamd_time_joint_paths_host")
-        else:
-            _check(self._lib.tpamd_time_joint_paths_device(self._h, C.byref(bt), C.byref(ji),
-                                                           C.byref(po), _stream_ptr(stream)),
-                   "tpamd_time_joint_paths_device")
+        self._call("tpamd_time_joint_paths", bt, _JointInputs.from_dict(inputs), _PathOutputs.from_dict(outputs),
+                   host=host, stream=stream)
 
     def time_joint_groups(self, groups, stream=None, host=False):
         """Several joint batches side by side (tpamd_time_joint_groups_*): `groups` is a list of
@@ -743,19 +343,9 @@ class Engine:
             B, P, D = cp.shape
             bts[g] = _JointBatch(B, D, int(grp["num_samples"]), P, int(grp.get("max_solver_loops", 0)),
                                  0, float(grp.get("safety", 0.8)))
-            jis[g] = _JointInputs(*[_ptr(grp["inputs"].get(k)) for k in (
-                "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
-                "sd_start", "sdd_start", "time_start", "num_samples_per_path")])
-            pos[g] = _PathOutputs(*[_ptr(grp["outputs"].get(k)) for k in (
-                "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-                "max_time_increment", "status", "sd2")])
-        if host:
-            _check(self._lib.tpamd_time_joint_groups_host(self._h, G, bts, jis, pos),
-                   "tpamd_time_joint_groups_host")
-        else:
-            _check(self._lib.tpamd_time_joint_groups_device(self._h, G, bts, jis, pos,
-                                                            _stream_ptr(stream)),
-                   "tpamd_time_joint_groups_device")
+            jis[g] = _JointInputs.from_dict(grp["inputs"])
+            pos[g] = _PathOutputs.from_dict(grp["outputs"])
+        self._call("tpamd_time_joint_groups", G, bts, jis, pos, host=host, stream=stream)
 
     def sample_joint_paths(self, knots, control_points, path_start, delta, num_samples):
         """Host numpy arrays -> (q, q1, q2) [B][N][D]."""
@@ -765,9 +355,7 @@ class Engine:
         ps = np.ascontiguousarray(np.broadcast_to(path_start, (B,)), dtype=np.float64)
         dl = np.ascontiguousarray(np.broadcast_to(delta, (B,)), dtype=np.float64)
         out = [np.zeros((B, num_samples, D)) for _ in range(3)]
-        _check(self._lib.tpamd_sample_joint_paths_host(
-            self._h, B, D, int(num_samples), P, _ptr(kn), _ptr(cp), _ptr(ps), _ptr(dl),
-            _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), "tpamd_sample_joint_paths_host")
+        self._call("tpamd_sample_joint_paths_host", B, D, int(num_samples), P, kn, cp, ps, dl, *out)
         return tuple(out)
 
     # ------------------------------------------------------- constraint rows
@@ -779,30 +367,12 @@ class Engine:
         a = inputs["a"]
         B, N, Cn = a.shape
         bt = _RowsBatch(B, N, Cn, int(max_solver_loops))
-        ri = _RowsInputs(*[_ptr(inputs.get(k)) for k in (
-            "a", "b", "lower", "upper", "s_start", "s_end", "sd_start", "sdd_start",
-            "time_start")])
-        po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-            "max_time_increment", "status", "sd2")])
+        ri, po = _RowsInputs.from_dict(inputs), _PathOutputs.from_dict(outputs)
         if num_samples_per_path is not None:
             ns = _int32_array(num_samples_per_path, B, "num_samples_per_path")
-            if host:
-                _check(self._lib.tpamd_optimize_rows_ragged_host(self._h, C.byref(bt), C.byref(ri), _ptr(ns),
-                                                                 C.byref(po)),
-                       "tpamd_optimize_rows_ragged_host")
-            else:
-                _check(self._lib.tpamd_optimize_rows_ragged_device(self._h, C.byref(bt), C.byref(ri), _ptr(ns),
-                                                                   C.byref(po), _stream_ptr(stream)),
-                       "tpamd_optimize_rows_ragged_device")
-            return
-        if host:
-            _check(self._lib.tpamd_optimize_rows_host(self._h, C.byref(bt), C.byref(ri),
-                                                      C.byref(po)), "tpamd_optimize_rows_host")
+            self._call("tpamd_optimize_rows_ragged", bt, ri, ns, po, host=host, stream=stream)
         else:
-            _check(self._lib.tpamd_optimize_rows_device(self._h, C.byref(bt), C.byref(ri),
-                                                        C.byref(po), _stream_ptr(stream)),
-                   "tpamd_optimize_rows_device")
+            self._call("tpamd_optimize_rows", bt, ri, po, host=host, stream=stream)
 
     # ------------------------------------------------------- Cartesian paths
     def time_cartesian_paths(self, inputs, outputs, safety=0.8, max_solver_loops=0, stream=None,
@@ -820,55 +390,37 @@ class Engine:
         alone means every path has N samples. Both are device tensors, or numpy arrays with
         host=True."""
         ik = inputs["ik_positions"]
-        if num_samples_per_path is not None or first_row is not None:
-            if first_row is None:
-                B, N, D = ik.shape
-            else:
-                if len(ik.shape) != 2:
-                    raise TpamdError("packed inputs: ik_positions must be [rows][D]")
-                rows, D = ik.shape
-                B, N = outputs["time"].shape
-                if inputs["jacobians"].shape[0] != rows:
-                    raise TpamdError("packed inputs: jacobians must have one [6][D] block per row")
+        B, N, D = self._cartesian_shape(inputs, first_row, outputs["time"] if first_row is not None else None)
+        ragged = num_samples_per_path is not None or first_row is not None
+        if ragged:
             if num_samples_per_path is None:
-                if host:
-                    num_samples_per_path = np.full(B, N, dtype=np.int32)
-                else:
-                    import torch
-                    num_samples_per_path = torch.full((B,), N, dtype=torch.int32, device=ik.device)
+                xp = _NUMPY if host else _Torch(ik.device)
+                num_samples_per_path = xp.full(B, N, xp.int32)
             ns = _int32_array(num_samples_per_path, B, "num_samples_per_path")
             fr = None if first_row is None else _int32_array(first_row, B, "first_row")
-            bt = _CartesianBatch(B, D, N, int(max_solver_loops), float(safety))
-            ci = _CartesianInputs(*[_ptr(inputs.get(k)) for k in _CARTESIAN_INPUT_KEYS])
-            po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
-                "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-                "max_time_increment", "status", "sd2")])
-            if host:
-                _check(self._lib.tpamd_time_cartesian_paths_ragged_host(
-                    self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr),
-                    int(ik.shape[0]) if fr is not None else 0, C.byref(po)),
-                    "tpamd_time_cartesian_paths_ragged_host")
-            else:
-                _check(self._lib.tpamd_time_cartesian_paths_ragged_device(
-                    self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr), C.byref(po), _stream_ptr(stream)),
-                    "tpamd_time_cartesian_paths_ragged_device")
-                # the engine reads the two arrays until the stream has run the call
-                self._ragged_keepalive = (ns, fr)
-            return
-        B, N, D = ik.shape
         bt = _CartesianBatch(B, D, N, int(max_solver_loops), float(safety))
-        ci = _CartesianInputs(*[_ptr(inputs.get(k)) for k in _CARTESIAN_INPUT_KEYS])
-        po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-            "max_time_increment", "status", "sd2")])
-        if host:
-            _check(self._lib.tpamd_time_cartesian_paths_host(self._h, C.byref(bt), C.byref(ci),
-                                                             C.byref(po)),
-                   "tpamd_time_cartesian_paths_host")
+        ci, po = _CartesianInputs.from_dict(inputs), _PathOutputs.from_dict(outputs)
+        if ragged:
+            # (the host entry also takes the row count of the packed tables)
+            rows = (int(ik.shape[0]) if fr is not None else 0,) if host else ()
+            self._call("tpamd_time_cartesian_paths_ragged", bt, ci, ns, fr, *rows, po, host=host, stream=stream)
         else:
-            _check(self._lib.tpamd_time_cartesian_paths_device(self._h, C.byref(bt), C.byref(ci),
-                                                               C.byref(po), _stream_ptr(stream)),
-                   "tpamd_time_cartesian_paths_device")
+            self._call("tpamd_time_cartesian_paths", bt, ci, po, host=host, stream=stream)
+
+    @staticmethod
+    def _cartesian_shape(inputs, first_row, strided):
+        """B, N, D of a Cartesian batch: of ik_positions [B][N][D], or, with packed row tables
+        (first_row given), D of ik_positions [rows][D] and B, N of the [B][N] array `strided`."""
+        ik = inputs["ik_positions"]
+        if first_row is None:
+            return ik.shape
+        if len(ik.shape) != 2:
+            raise TpamdError("packed inputs: ik_positions must be [rows][D]")
+        rows, D = ik.shape
+        B, N = strided.shape
+        if inputs["jacobians"].shape[0] != rows:
+            raise TpamdError("packed inputs: jacobians must have one [6][D] block per row")
+        return B, N, D
 
     def sample_pose_splines(self, knots, translation_points, rotation_points, path_start, delta,
                             num_samples):
@@ -881,9 +433,7 @@ class Engine:
         ps = np.ascontiguousarray(np.broadcast_to(path_start, (B,)), dtype=np.float64)
         dl = np.ascontiguousarray(np.broadcast_to(delta, (B,)), dtype=np.float64)
         out = np.zeros((B, int(num_samples), 7))
-        _check(self._lib.tpamd_sample_pose_splines_host(self._h, B, int(num_samples), P, _ptr(kn),
-                                                        _ptr(tr), _ptr(ro), _ptr(ps), _ptr(dl),
-                                                        _ptr(out)), "tpamd_sample_pose_splines_host")
+        self._call("tpamd_sample_pose_splines_host", B, int(num_samples), P, kn, tr, ro, ps, dl, out)
         return out
 
     # ------------------------------------------------------------ Cartesian goals
@@ -897,50 +447,28 @@ class Engine:
         point_offsets [B + 1] (always a numpy array). CUDA inputs go through the _device entry on
         `stream` (default: torch's current stream) and give CUDA tensors; numpy arrays go through
         the host entry, which synchronises, and give numpy arrays."""
-        import torch
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        B = off.shape[0] - 1
-        if B < 0:
-            raise TpamdError("waypoint offsets need at least one entry")
-        W = np.diff(off.astype(np.int64))
-        npts = np.where(W < 1, 0, np.where(W == 1, 4, 3 * W - 2))
-        P, K = int(npts.sum()), int((npts + 3 * (npts > 0)).sum())
+        off, B = _waypoint_offsets(offsets)
+        P, K = _fit_sizes(off)
         rows = int(off[-1])
         point_offsets = np.zeros(B + 1, dtype=np.int32)
-        if _is_cuda(pose_waypoints):
-            dev = pose_waypoints.device
-            f = lambda x, shape, what: PlannerSet._cuda(x, torch.float64, dev, shape, what)
-            per = lambda x, what: f(x if hasattr(x, "shape") else torch.full((B,), float(x), dtype=torch.float64),
-                                    (B,), what)
-            pw = f(pose_waypoints, (rows, 7), "pose_waypoints")
-            D = int(joint_waypoints.shape[-1])
-            jw = f(joint_waypoints, (rows, D), "joint_waypoints")
-            tr, rr = per(translation_rounding, "translation_rounding"), per(rotation_rounding, "rotation_rounding")
-            new = lambda shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
-            out = dict(knots=new((K,)), translation_points=new((P, 3)), rotation_points=new((P, 4)),
-                       joint_control_points=new((P, D)), num_points=new((B,), torch.int32), path_end=new((B,)),
-                       status=torch.full((B,), -1, dtype=torch.int32, device=dev))
-            _check(self._lib.tpamd_fit_pose_waypoints_device(
-                self._h, B, D, _ptr(off), _ptr(pw), _ptr(jw), _ptr(tr), _ptr(rr), _ptr(out["knots"]),
-                _ptr(out["translation_points"]), _ptr(out["rotation_points"]), _ptr(out["joint_control_points"]),
-                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"]),
-                _stream_ptr(stream)), "tpamd_fit_pose_waypoints_device")
-        else:
-            pw = _host(pose_waypoints, np.float64, (rows, 7), "pose_waypoints")
-            jw = _host(joint_waypoints, np.float64, what="joint_waypoints")
+        xp = _backend(pose_waypoints)
+        pw = xp.array(pose_waypoints, xp.float64, (rows, 7), "pose_waypoints")
+        if xp.host:      # D is whatever the second axis holds
+            jw = xp.array(joint_waypoints, xp.float64, what="joint_waypoints")
             if jw.ndim != 2 or jw.shape[0] != rows:
                 raise TpamdError("joint_waypoints has shape %s, expected (%d, D)" % (jw.shape, rows))
             D = jw.shape[1]
-            per = lambda x, what: _host(np.broadcast_to(_host(x, np.float64), (B,)), np.float64, (B,), what)
-            tr, rr = per(translation_rounding, "translation_rounding"), per(rotation_rounding, "rotation_rounding")
-            out = dict(knots=np.zeros(K), translation_points=np.zeros((P, 3)), rotation_points=np.zeros((P, 4)),
-                       joint_control_points=np.zeros((P, D)), num_points=np.zeros(B, dtype=np.int32),
-                       path_end=np.zeros(B), status=np.full(B, -1, dtype=np.int32))
-            _check(self._lib.tpamd_fit_pose_waypoints_host(
-                self._h, B, D, _ptr(off), _ptr(pw), _ptr(jw), _ptr(tr), _ptr(rr), _ptr(out["knots"]),
-                _ptr(out["translation_points"]), _ptr(out["rotation_points"]), _ptr(out["joint_control_points"]),
-                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"])),
-                "tpamd_fit_pose_waypoints_host")
+        else:
+            D = int(joint_waypoints.shape[-1])
+            jw = xp.array(joint_waypoints, xp.float64, (rows, D), "joint_waypoints")
+        tr, rr = xp.per(translation_rounding, B, "translation_rounding"), xp.per(rotation_rounding, B,
+                                                                                 "rotation_rounding")
+        out = dict(knots=xp.zeros(K), translation_points=xp.zeros((P, 3)), rotation_points=xp.zeros((P, 4)),
+                   joint_control_points=xp.zeros((P, D)), num_points=xp.zeros(B, xp.int32), path_end=xp.zeros(B),
+                   status=xp.full(B, -1, xp.int32))
+        self._call("tpamd_fit_pose_waypoints", B, D, off, pw, jw, tr, rr, out["knots"], out["translation_points"],
+                   out["rotation_points"], out["joint_control_points"], out["num_points"], point_offsets,
+                   out["path_end"], out["status"], host=xp.host, stream=stream)
         out["point_offsets"] = point_offsets
         return out
 
@@ -953,44 +481,23 @@ class Engine:
         waypoints go through the _device entry on `stream` (default: torch's current stream) and give
         CUDA tensors; numpy arrays go through the host entry, which synchronises, and give numpy
         arrays."""
-        import torch
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        B = off.shape[0] - 1
-        if B < 0:
-            raise TpamdError("waypoint offsets need at least one entry")
-        W = np.diff(off.astype(np.int64))
-        npts = np.where(W < 1, 0, np.where(W == 1, 4, 3 * W - 2))
-        P, K = int(npts.sum()), int((npts + 3 * (npts > 0)).sum())
+        off, B = _waypoint_offsets(offsets)
+        P, K = _fit_sizes(off)
         rows = int(off[-1])
         if waypoints.ndim != 2 or waypoints.shape[0] != rows:
             raise TpamdError("waypoints has shape %s, expected (%d, D)" % (tuple(waypoints.shape), rows))
         D = int(waypoints.shape[1])
         point_offsets = np.zeros(B + 1, dtype=np.int32)
-        if _is_cuda(waypoints):
-            dev = waypoints.device
-            w = PlannerSet._cuda(waypoints, torch.float64, dev, (rows, D), "waypoints")
-            r = None
-            if rounding is not None:
-                r = PlannerSet._cuda(rounding if hasattr(rounding, "shape") and len(rounding.shape) else
-                                     torch.full((B,), float(rounding), dtype=torch.float64), torch.float64, dev, (B,),
-                                     "rounding")
-            new = lambda shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
-            out = dict(knots=new((K,)), control_points=new((P, D)), num_points=new((B,), torch.int32),
-                       path_end=new((B,)), status=torch.full((B,), -1, dtype=torch.int32, device=dev))
-            _check(self._lib.tpamd_fit_joint_waypoints_device(
-                self._h, B, D, _ptr(off), _ptr(w), _ptr(r), _ptr(out["knots"]), _ptr(out["control_points"]),
-                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"]),
-                _stream_ptr(stream)), "tpamd_fit_joint_waypoints_device")
-        else:
-            w = _host(waypoints, np.float64, (rows, D), "waypoints")
-            r = None if rounding is None else _host(np.broadcast_to(_host(rounding, np.float64), (B,)), np.float64,
-                                                    (B,), "rounding")
-            out = dict(knots=np.zeros(K), control_points=np.zeros((P, D)), num_points=np.zeros(B, dtype=np.int32),
-                       path_end=np.zeros(B), status=np.full(B, -1, dtype=np.int32))
-            _check(self._lib.tpamd_fit_joint_waypoints_host(
-                self._h, B, D, _ptr(off), _ptr(w), _ptr(r), _ptr(out["knots"]), _ptr(out["control_points"]),
-                _ptr(out["num_points"]), _ptr(point_offsets), _ptr(out["path_end"]), _ptr(out["status"])),
-                "tpamd_fit_joint_waypoints_host")
+        xp = _backend(waypoints)
+        w = xp.array(waypoints, xp.float64, (rows, D), "waypoints")
+        r = None
+        if rounding is not None:      # on the device a 0-d tensor counts as one number here
+            r = xp.per(rounding if xp.host or (hasattr(rounding, "shape") and len(rounding.shape)) else
+                       float(rounding), B, "rounding")
+        out = dict(knots=xp.zeros(K), control_points=xp.zeros((P, D)), num_points=xp.zeros(B, xp.int32),
+                   path_end=xp.zeros(B), status=xp.full(B, -1, xp.int32))
+        self._call("tpamd_fit_joint_waypoints", B, D, off, w, r, out["knots"], out["control_points"],
+                   out["num_points"], point_offsets, out["path_end"], out["status"], host=xp.host, stream=stream)
         out["point_offsets"] = point_offsets
         return out
 
@@ -998,23 +505,12 @@ class Engine:
                      delta, rounding, sd_start, time_start, safety, outputs, host):
         """The C structs of one waypoint timing call (plain or refined), the dict it returns, the
         device of the arrays (None with host=True) and what must stay alive until the call is made."""
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        B = off.shape[0] - 1
-        if B < 0:
-            raise TpamdError("waypoint offsets need at least one entry")
+        off, B = _waypoint_offsets(offsets)
         N, D = int(num_samples), int(max_velocity.shape[-1])
         out = dict(outputs) if outputs else {}
-        if host:
-            f = lambda x, shape, what, dt=np.float64: _host(x, dt, shape, what)
-            new = lambda shape, dt=np.float64: np.zeros(shape, dtype=dt)
-            i32 = np.int32
-            dev = None
-        else:
-            import torch
-            dev = max_velocity.device
-            f = lambda x, shape, what, dt=torch.float64: None if x is None else PlannerSet._cuda(x, dt, dev, shape, what)
-            new = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
-            i32 = torch.int32
+        xp = _NUMPY if host else _Torch(max_velocity.device)
+        f = lambda x, shape, what, dt=xp.float64: xp.array(x, dt, shape, what)
+        new, i32, dev = xp.zeros, xp.int32, xp.device
         rows = int(off[-1])
         w = f(waypoints, (rows, D), "waypoints")
         vm, am = f(max_velocity, (B, D), "max_velocity"), f(max_acceleration, (B, D), "max_acceleration")
@@ -1032,11 +528,7 @@ class Engine:
         bt = _WaypointBatch(B, D, N, 0, float(safety))
         wi = _WaypointInputs(_ptr(off), _ptr(w), _ptr(rd), _ptr(vm), _ptr(am), _ptr(ns), _ptr(dl), _ptr(sd0),
                              _ptr(t0))
-        po = _PathOutputs(*[_ptr(out.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index", "max_time_increment", "status",
-            "sd2")])
-        fo = _WaypointFitOutputs(*[_ptr(out.get(k)) for k in (
-            "num_points", "path_end", "delta_used", "knots", "control_points")])
+        po, fo = _PathOutputs.from_dict(out), _WaypointFitOutputs.from_dict(out)
         return bt, wi, po, fo, out, B, D, dev, (off, w, vm, am, ns, dl, rd, sd0, t0)
 
     def time_waypoint_paths(self, waypoints, offsets, max_velocity, max_acceleration, num_samples,
@@ -1056,13 +548,7 @@ class Engine:
         bt, wi, po, fo, out, B, D, dev, keep = self._waypoint_io(
             waypoints, offsets, max_velocity, max_acceleration, num_samples, num_samples_per_path, delta, rounding,
             sd_start, time_start, safety, outputs, host)
-        if host:
-            _check(self._lib.tpamd_time_waypoint_paths_host(self._h, C.byref(bt), C.byref(wi), C.byref(po),
-                                                            C.byref(fo)), "tpamd_time_waypoint_paths_host")
-        else:
-            _check(self._lib.tpamd_time_waypoint_paths_device(self._h, C.byref(bt), C.byref(wi), C.byref(po),
-                                                              C.byref(fo), _stream_ptr(stream)),
-                   "tpamd_time_waypoint_paths_device")
+        self._call("tpamd_time_waypoint_paths", bt, wi, po, fo, host=host, stream=stream, keep=keep)
         return out
 
     # ------------------------------------------- refining violating paths on the device
@@ -1075,17 +561,13 @@ class Engine:
         (refined status: -1). Unused slots and the entries behind a slot's num_samples are not written:
         read slot_path[k] >= 0 and num_samples[k] before anything of slot k."""
         M, NS = int(max_refined), int(max_samples)
-        if host:
-            new = lambda shape, real=True: np.zeros(shape, dtype=np.float64 if real else np.int32)
-        else:
-            import torch
-            new = lambda shape, real=True: torch.zeros(shape, dtype=torch.float64 if real else torch.int32,
-                                                       device=device)
+        xp = _NUMPY if host else _Torch(device)
+        new = lambda shape, real=True: xp.zeros(shape, xp.float64 if real else xp.int32)
         src = refined or {}
         out = {k: v for k, v in src.items() if k not in ("check", "refined", "refined_check")}
         for name, n in (("check", B), ("refined_check", M)):
             rec = dict(src.get(name) or {})
-            for k in _CHECK_OUTPUT_KEYS:
+            for k in _CheckOutputs._keys_:
                 rec.setdefault(k, new((n,), k == "worst_excess"))
             out[name] = rec
         out.setdefault("slot", new((B,), False))
@@ -1104,13 +586,11 @@ class Engine:
         sol.setdefault("max_time_increment", new((M,)))
         out["refined"] = sol
         ro = _RefineOutputs()
-        ro.check = _CheckOutputs(*[_ptr(out["check"].get(k)) for k in _CHECK_OUTPUT_KEYS])
+        ro.check = _CheckOutputs.from_dict(out["check"])
         for k in ("slot", "slot_path", "num_refined", "rounds", "num_samples", "delta"):
             setattr(ro, k, _ptr(out.get(k)))
-        ro.refined = _PathOutputs(*[_ptr(sol.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index", "max_time_increment", "status",
-            "sd2")])
-        ro.refined_check = _CheckOutputs(*[_ptr(out["refined_check"].get(k)) for k in _CHECK_OUTPUT_KEYS])
+        ro.refined = _PathOutputs.from_dict(sol)
+        ro.refined_check = _CheckOutputs.from_dict(out["refined_check"])
         opt = _RefineOptions(int(max_rounds), NS, M, 0, float(tolerance))
         return opt, ro, out
 
@@ -1126,22 +606,10 @@ class Engine:
         cp = inputs["control_points"]
         B, P, D = cp.shape
         bt = _JointBatch(B, D, int(num_samples), P, 0, 0, float(safety))
-        ji = _JointInputs(*[_ptr(inputs.get(k)) for k in (
-            "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
-            "sd_start", "sdd_start", "time_start", "num_samples_per_path")])
-        po = _PathOutputs(*[_ptr(outputs.get(k)) for k in (
-            "time", "s", "sd", "sdd", "q", "qd", "qdd", "last_extremal_index",
-            "max_time_increment", "status", "sd2")])
+        ji, po = _JointInputs.from_dict(inputs), _PathOutputs.from_dict(outputs)
         opt, ro, out = self._refine_io(B, D, max_rounds, max_samples, max_refined, tolerance, refined,
                                        None if host else cp.device, host)
-        if host:
-            _check(self._lib.tpamd_time_joint_paths_refined_host(self._h, C.byref(bt), C.byref(ji), C.byref(po),
-                                                                 C.byref(opt), C.byref(ro)),
-                   "tpamd_time_joint_paths_refined_host")
-        else:
-            _check(self._lib.tpamd_time_joint_paths_refined_device(self._h, C.byref(bt), C.byref(ji), C.byref(po),
-                                                                   C.byref(opt), C.byref(ro), _stream_ptr(stream)),
-                   "tpamd_time_joint_paths_refined_device")
+        self._call("tpamd_time_joint_paths_refined", bt, ji, po, opt, ro, host=host, stream=stream)
         return out
 
     def time_waypoint_paths_refined(self, waypoints, offsets, max_velocity, max_acceleration, num_samples,
@@ -1155,14 +623,7 @@ class Engine:
             waypoints, offsets, max_velocity, max_acceleration, num_samples, num_samples_per_path, delta, rounding,
             sd_start, time_start, safety, outputs, host)
         opt, ro, ref = self._refine_io(B, D, max_rounds, max_samples, max_refined, tolerance, refined, dev, host)
-        if host:
-            _check(self._lib.tpamd_time_waypoint_paths_refined_host(
-                self._h, C.byref(bt), C.byref(wi), C.byref(po), C.byref(fo), C.byref(opt), C.byref(ro)),
-                "tpamd_time_waypoint_paths_refined_host")
-        else:
-            _check(self._lib.tpamd_time_waypoint_paths_refined_device(
-                self._h, C.byref(bt), C.byref(wi), C.byref(po), C.byref(fo), C.byref(opt), C.byref(ro),
-                _stream_ptr(stream)), "tpamd_time_waypoint_paths_refined_device")
+        self._call("tpamd_time_waypoint_paths_refined", bt, wi, po, fo, opt, ro, host=host, stream=stream, keep=keep)
         return out, ref
 
     # ------------------------------------------- checking solutions against their rows
@@ -1171,18 +632,11 @@ class Engine:
         arrays of `outputs` where it has them, new ones (on the device of `like`, or numpy arrays
         with host=True) otherwise."""
         out = dict(outputs) if outputs else {}
-        for k in _CHECK_OUTPUT_KEYS:
-            if k in out:
-                continue
-            real = k == "worst_excess"
-            if host:
-                out[k] = np.zeros(B, dtype=np.float64 if real else np.int32)
-            else:
-                import torch
-                out[k] = torch.zeros(B, dtype=torch.float64 if real else torch.int32, device=like.device)
-        sol = _Solution(*[_ptr(solution.get(k)) for k in ("sd2", "sd", "sdd", "status")])
-        cko = _CheckOutputs(*[_ptr(out.get(k)) for k in _CHECK_OUTPUT_KEYS])
-        return sol, cko, out
+        xp = _NUMPY if host else _Torch(like.device)
+        for k in _CheckOutputs._keys_:
+            if k not in out:
+                out[k] = xp.zeros(B, xp.float64 if k == "worst_excess" else xp.int32)
+        return _Solution.from_dict(solution), _CheckOutputs.from_dict(out), out
 
     def check_rows(self, inputs, solution, outputs=None, num_samples_per_path=None, stream=None, host=False):
         """SolutionSatisfiesConstraints for a rows batch (tpamd_check_rows_*). inputs: the dict
@@ -1194,17 +648,10 @@ class Engine:
         a = inputs["a"]
         B, N, Cn = a.shape
         bt = _RowsBatch(B, N, Cn, 0)
-        ri = _RowsInputs(*[_ptr(inputs.get(k)) for k in (
-            "a", "b", "lower", "upper", "s_start", "s_end", "sd_start", "sdd_start", "time_start")])
+        ri = _RowsInputs.from_dict(inputs)
         ns = None if num_samples_per_path is None else _int32_array(num_samples_per_path, B, "num_samples_per_path")
         sol, cko, out = self._check_io(solution, outputs, B, a, host)
-        if host:
-            _check(self._lib.tpamd_check_rows_host(self._h, C.byref(bt), C.byref(ri), _ptr(ns), C.byref(sol),
-                                                   C.byref(cko)), "tpamd_check_rows_host")
-        else:
-            _check(self._lib.tpamd_check_rows_device(self._h, C.byref(bt), C.byref(ri), _ptr(ns), C.byref(sol),
-                                                     C.byref(cko), _stream_ptr(stream)), "tpamd_check_rows_device")
-            self._check_keepalive = (ns,)
+        self._call("tpamd_check_rows", bt, ri, ns, sol, cko, host=host, stream=stream)
         return out
 
     def check_joint_paths(self, inputs, solution, num_samples, safety=0.8, num_points_per_path=None, outputs=None,
@@ -1217,20 +664,10 @@ class Engine:
         cp = inputs["control_points"]
         B, P, D = cp.shape
         bt = _JointBatch(B, D, int(num_samples), P, 0, 0, float(safety))
-        ji = _JointInputs(*[_ptr(inputs.get(k)) for k in (
-            "knots", "control_points", "max_velocity", "max_acceleration", "path_start", "delta",
-            "sd_start", "sdd_start", "time_start", "num_samples_per_path")])
+        ji = _JointInputs.from_dict(inputs)
         npp = None if num_points_per_path is None else _int32_array(num_points_per_path, B, "num_points_per_path")
         sol, cko, out = self._check_io(solution, outputs, B, cp, host)
-        if host:
-            _check(self._lib.tpamd_check_joint_paths_host(self._h, C.byref(bt), C.byref(ji), _ptr(npp),
-                                                          C.byref(sol), C.byref(cko)),
-                   "tpamd_check_joint_paths_host")
-        else:
-            _check(self._lib.tpamd_check_joint_paths_device(self._h, C.byref(bt), C.byref(ji), _ptr(npp),
-                                                            C.byref(sol), C.byref(cko), _stream_ptr(stream)),
-                   "tpamd_check_joint_paths_device")
-            self._check_keepalive = (npp,)
+        self._call("tpamd_check_joint_paths", bt, ji, npp, sol, cko, host=host, stream=stream)
         return out
 
     def check_waypoint_paths(self, got, max_velocity, max_acceleration, num_samples, safety=0.8,
@@ -1249,8 +686,8 @@ class Engine:
                   "num_samples_per_path": num_samples_per_path}
         out = self.check_joint_paths(inputs, got, num_samples, safety=safety, num_points_per_path=got["num_points"],
                                      outputs=outputs, stream=stream, host=host)
-        if not host:
-            self._check_keepalive += (zero,)
+        if not host:      # the zeros are this method's own: they live as long as the call's other arguments
+            self._keepalive["tpamd_check_joint_paths_device"] += (zero,)
         return out
 
     def check_cartesian_paths(self, inputs, solution, safety=0.8, num_samples_per_path=None, first_row=None,
@@ -1259,29 +696,14 @@ class Engine:
         and first_row as time_cartesian_paths took them. With first_row the inputs are packed row
         tables, and B and the stride N are those of solution["sdd"] [B][N]."""
         ik = inputs["ik_positions"]
-        if first_row is None:
-            B, N, D = ik.shape
-        else:
-            if len(ik.shape) != 2:
-                raise TpamdError("packed inputs: ik_positions must be [rows][D]")
-            rows, D = ik.shape
-            B, N = solution["sdd"].shape
-            if inputs["jacobians"].shape[0] != rows:
-                raise TpamdError("packed inputs: jacobians must have one [6][D] block per row")
+        B, N, D = self._cartesian_shape(inputs, first_row, solution["sdd"] if first_row is not None else None)
         ns = None if num_samples_per_path is None else _int32_array(num_samples_per_path, B, "num_samples_per_path")
         fr = None if first_row is None else _int32_array(first_row, B, "first_row")
         bt = _CartesianBatch(B, D, N, 0, float(safety))
-        ci = _CartesianInputs(*[_ptr(inputs.get(k)) for k in _CARTESIAN_INPUT_KEYS])
+        ci = _CartesianInputs.from_dict(inputs)
         sol, cko, out = self._check_io(solution, outputs, B, ik, host)
-        if host:
-            _check(self._lib.tpamd_check_cartesian_paths_host(
-                self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr), int(ik.shape[0]) if fr is not None else 0,
-                C.byref(sol), C.byref(cko)), "tpamd_check_cartesian_paths_host")
-        else:
-            _check(self._lib.tpamd_check_cartesian_paths_device(
-                self._h, C.byref(bt), C.byref(ci), _ptr(ns), _ptr(fr), C.byref(sol), C.byref(cko),
-                _stream_ptr(stream)), "tpamd_check_cartesian_paths_device")
-            self._check_keepalive = (ns, fr)
+        rows = (int(ik.shape[0]) if fr is not None else 0,) if host else ()      # as time_cartesian_paths
+        self._call("tpamd_check_cartesian_paths", bt, ci, ns, fr, *rows, sol, cko, host=host, stream=stream)
         return out
 
     # ------------------------------------------------------------ path_tools
@@ -1294,34 +716,17 @@ class Engine:
         _device entry on `stream` (default: torch's current stream), which only enqueues, and give
         CUDA tensors; anything else goes through the host entry, which synchronises, and gives
         numpy arrays."""
-        import torch
-        if _is_cuda(position):
-            dev = position.device
-            f = lambda x, shape, what: PlannerSet._cuda(x, torch.float64, dev, shape, what)
-            pos = f(position, None, "position")
-            if pos.dim() != 2:
-                raise TpamdError("position has shape %s, expected (count, D)" % (tuple(pos.shape),))
-            n, D = pos.shape
-            vel, acc = f(velocity, (n, D), "velocity"), f(acceleration_limit, (n, D), "acceleration_limit")
-            rnd = f(corner_rounding if hasattr(corner_rounding, "shape") else
-                    torch.full((n,), float(corner_rounding), dtype=torch.float64), (n,), "corner_rounding")
-            point = torch.full((n, D), float("nan"), dtype=torch.float64, device=dev)
-            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            _check(self._lib.tpamd_compute_stopping_points_device(
-                self._h, n, D, _ptr(pos), _ptr(vel), _ptr(acc), _ptr(rnd), _ptr(point), _ptr(status),
-                _stream_ptr(stream)), "tpamd_compute_stopping_points_device")
-            return point, status
-        pos = _host(position, np.float64, what="position")
+        xp = _backend(position)
+        pos = xp.array(position, xp.float64, what="position")
         if pos.ndim != 2:
-            raise TpamdError("position has shape %s, expected (count, D)" % (pos.shape,))
+            raise TpamdError("position has shape %s, expected (count, D)" % (tuple(pos.shape),))
         n, D = pos.shape
-        vel = _host(velocity, np.float64, (n, D), "velocity")
-        acc = _host(acceleration_limit, np.float64, (n, D), "acceleration_limit")
-        rnd = _host(np.broadcast_to(_host(corner_rounding, np.float64), (n,)), np.float64, (n,), "corner_rounding")
-        point, status = np.full((n, D), np.nan), np.full(n, -1, dtype=np.int32)
-        _check(self._lib.tpamd_compute_stopping_points_host(
-            self._h, n, D, _ptr(pos), _ptr(vel), _ptr(acc), _ptr(rnd), _ptr(point), _ptr(status)),
-            "tpamd_compute_stopping_points_host")
+        vel = xp.array(velocity, xp.float64, (n, D), "velocity")
+        acc = xp.array(acceleration_limit, xp.float64, (n, D), "acceleration_limit")
+        rnd = xp.per(corner_rounding, n, "corner_rounding")
+        point, status = xp.full((n, D), float("nan")), xp.full(n, -1, xp.int32)
+        self._call("tpamd_compute_stopping_points", n, D, pos, vel, acc, rnd, point, status, host=xp.host,
+                   stream=stream)
         return point, status
 
     def project_points_on_paths(self, waypoints, offsets, point, stream=None):
@@ -1332,43 +737,24 @@ class Engine:
         offsets is a host array in both forms. CUDA waypoints go through the _device entry on
         `stream`, which only enqueues, and give CUDA tensors; anything else goes through the host
         entry, which synchronises, and gives numpy arrays."""
-        import torch
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        n = off.shape[0] - 1
-        if n < 0:
-            raise TpamdError("waypoint offsets need at least one entry")
-        if _is_cuda(point):
-            dev = point.device
-            f = lambda x, shape, what: PlannerSet._cuda(x, torch.float64, dev, shape, what)
-            pt = f(point, None, "point")
-            if pt.dim() != 2 or pt.shape[0] != n:
-                raise TpamdError("point has shape %s, expected (%d, D)" % (tuple(pt.shape), n))
-            D = pt.shape[1]
-            w = f(waypoints, (int(off[-1]), D), "waypoints")
-            out = dict(waypoint_index=torch.full((n,), -1, dtype=torch.int32, device=dev),
-                       distance_to_path=torch.full((n,), float("nan"), dtype=torch.float64, device=dev),
-                       line_parameter=torch.full((n,), float("nan"), dtype=torch.float64, device=dev),
-                       projected_point=torch.full((n, D), float("nan"), dtype=torch.float64, device=dev),
-                       status=torch.full((n,), -1, dtype=torch.int32, device=dev))
-            _check(self._lib.tpamd_project_points_on_paths_device(
-                self._h, n, D, _ptr(off), w.data_ptr() if w.numel() else None, _ptr(pt), _ptr(out["waypoint_index"]),
-                _ptr(out["distance_to_path"]), _ptr(out["line_parameter"]), _ptr(out["projected_point"]),
-                _ptr(out["status"]), _stream_ptr(stream)), "tpamd_project_points_on_paths_device")
-            return out
-        pt = _host(point, np.float64, what="point")
+        off, n = _waypoint_offsets(offsets)
+        xp, nan = _backend(point), float("nan")
+        pt = xp.array(point, xp.float64, what="point")
         if pt.ndim != 2 or pt.shape[0] != n:
-            raise TpamdError("point has shape %s, expected (%d, D)" % (pt.shape, n))
+            raise TpamdError("point has shape %s, expected (%d, D)" % (tuple(pt.shape), n))
         D = pt.shape[1]
-        w = _host(waypoints, np.float64, what="waypoints").reshape(-1, D)
-        if w.shape[0] != off[-1]:
-            raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
-        out = dict(waypoint_index=np.full(n, -1, dtype=np.int32), distance_to_path=np.full(n, np.nan),
-                   line_parameter=np.full(n, np.nan), projected_point=np.full((n, D), np.nan),
-                   status=np.full(n, -1, dtype=np.int32))
-        _check(self._lib.tpamd_project_points_on_paths_host(
-            self._h, n, D, _ptr(off), _ptr(w) if w.size else None, _ptr(pt), _ptr(out["waypoint_index"]),
-            _ptr(out["distance_to_path"]), _ptr(out["line_parameter"]), _ptr(out["projected_point"]),
-            _ptr(out["status"])), "tpamd_project_points_on_paths_host")
+        if xp.host:      # any shape that holds rows of D
+            w = xp.array(waypoints, xp.float64, what="waypoints").reshape(-1, D)
+            if w.shape[0] != off[-1]:
+                raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
+        else:
+            w = xp.array(waypoints, xp.float64, (int(off[-1]), D), "waypoints")
+        out = dict(waypoint_index=xp.full(n, -1, xp.int32), distance_to_path=xp.full(n, nan),
+                   line_parameter=xp.full(n, nan), projected_point=xp.full((n, D), nan),
+                   status=xp.full(n, -1, xp.int32))
+        self._call("tpamd_project_points_on_paths", n, D, off, w if w.shape[0] * D else None, pt, out["waypoint_index"],
+                   out["distance_to_path"], out["line_parameter"], out["projected_point"], out["status"],
+                   host=xp.host, stream=stream)
         return out
 
     def sample_ik_targets(self, fit, delta, row_offsets, stream=None, first_row=None):
@@ -1380,7 +766,6 @@ class Engine:
         rows are table rows first_row[k] .. of its path: (first_row[k] + r) * delta[k], bit-equal to
         the same rows of a whole-path call. Returns (pose_targets [rows][7], joint_targets [rows][D])
         on the side the spline arrays are on."""
-        import torch
         off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
         B = off.shape[0] - 1
         fr = None if first_row is None else _host(first_row, np.int32, (B,), "first_row")
@@ -1394,36 +779,17 @@ class Engine:
         rows = int(off[-1]) if B else 0
         jc = fit["joint_control_points"]
         D = int(jc.shape[-1])
-        if _is_cuda(jc):
-            dev = jc.device
-            f = lambda x, what: PlannerSet._cuda(x, torch.float64, dev, None, what)
-            dl = f(delta if hasattr(delta, "shape") else torch.full((B,), float(delta), dtype=torch.float64), "delta")
-            if tuple(dl.shape) != (B,):
-                raise TpamdError("delta has shape %s, expected (%d,)" % (tuple(dl.shape), B))
-            pose = torch.zeros((rows, 7), dtype=torch.float64, device=dev)
-            joint = torch.zeros((rows, D), dtype=torch.float64, device=dev)
-            splines = (_ptr(f(fit["knots"], "knots")), _ptr(f(fit["translation_points"], "translation_points")),
-                       _ptr(f(fit["rotation_points"], "rotation_points")), _ptr(f(jc, "joint_control_points")), _ptr(dl),
-                       _ptr(pose), _ptr(joint), _stream_ptr(stream))
-            if fr is not None:
-                _check(self._lib.tpamd_sample_ik_target_rows_device(self._h, B, D, _ptr(npts), _ptr(off), _ptr(fr),
-                                                                    *splines), "tpamd_sample_ik_target_rows_device")
-            else:
-                _check(self._lib.tpamd_sample_ik_targets_device(self._h, B, D, _ptr(npts), _ptr(off), *splines),
-                       "tpamd_sample_ik_targets_device")
-            return pose, joint
-        h = lambda x, what: _host(x, np.float64, what=what)
-        dl = _host(np.broadcast_to(_host(delta, np.float64), (B,)), np.float64, (B,), "delta")
-        pose, joint = np.zeros((rows, 7)), np.zeros((rows, D))
-        splines = (_ptr(h(fit["knots"], "knots")), _ptr(h(fit["translation_points"], "translation_points")),
-                   _ptr(h(fit["rotation_points"], "rotation_points")), _ptr(h(jc, "joint_control_points")), _ptr(dl),
-                   _ptr(pose), _ptr(joint))
+        xp = _backend(jc)
+        dl = xp.per(delta, B, "delta")
+        pose, joint = xp.zeros((rows, 7)), xp.zeros((rows, D))
+        splines = [xp.array(fit[k], xp.float64, what=k) for k in (
+            "knots", "translation_points", "rotation_points", "joint_control_points")]
         if fr is not None:
-            _check(self._lib.tpamd_sample_ik_target_rows_host(self._h, B, D, _ptr(npts), _ptr(off), _ptr(fr), *splines),
-                   "tpamd_sample_ik_target_rows_host")
+            self._call("tpamd_sample_ik_target_rows", B, D, npts, off, fr, *splines, dl, pose, joint, host=xp.host,
+                       stream=stream)
         else:
-            _check(self._lib.tpamd_sample_ik_targets_host(self._h, B, D, _ptr(npts), _ptr(off), *splines),
-                   "tpamd_sample_ik_targets_host")
+            self._call("tpamd_sample_ik_targets", B, D, npts, off, *splines, dl, pose, joint, host=xp.host,
+                       stream=stream)
         return pose, joint
 
     def ik_table_rows(self, path_end, delta, num_samples):
@@ -1436,9 +802,7 @@ class Engine:
                               for x in (a, b, lower, upper))
         num, Cn = a.shape
         o = [np.zeros(num) for _ in range(3)]
-        _check(self._lib.tpamd_find_max_sd2_host(self._h, num, Cn, _ptr(a), _ptr(b), _ptr(lower),
-                                                 _ptr(upper), _ptr(o[0]), _ptr(o[1]), _ptr(o[2])),
-               "tpamd_find_max_sd2_host")
+        self._call("tpamd_find_max_sd2_host", num, Cn, a, b, lower, upper, *o)
         return tuple(o)
 
     def query(self, time, s, sd, status, t_query, out_s, out_sd, out_sdd, ok=None, stream=None,
@@ -1447,10 +811,8 @@ class Engine:
         its last solve (TpamdError "stale" if time is not that solve's output)."""
         B, N = time.shape
         K = t_query.shape[1]
-        _check(self._lib.tpamd_query_device(self._h, B, N, K, _ptr(time), _ptr(s), _ptr(sd),
-                                            _ptr(sd2), _ptr(status), _ptr(t_query), _ptr(out_s),
-                                            _ptr(out_sd), _ptr(out_sdd), _ptr(ok),
-                                            _stream_ptr(stream)), "tpamd_query_device")
+        self._call("tpamd_query", B, N, K, time, s, sd, sd2, status, t_query, out_s, out_sd, out_sdd, ok,
+                   host=False, stream=stream)
 
     def resample_uniform(self, sol, max_acceleration, start_sec, time_step, out, stream=None,
                          skip=False):
@@ -1466,9 +828,7 @@ class Engine:
             _ptr(max_acceleration), _ptr(start_sec), float(time_step), _ptr(sol.get("status")),
             *[_ptr(out[k]) for k in ("out_time", "out_s", "out_sd", "out_sdd", "out_q",
                                      "out_qd", "out_qdd", "count")])
-        fn = self._lib.tpamd_resample_skip_device if skip else self._lib.tpamd_resample_uniform_device
-        _check(fn(self._h, C.byref(args), _stream_ptr(stream)),
-               "tpamd_resample_skip_device" if skip else "tpamd_resample_uniform_device")
+        self._call("tpamd_resample_skip" if skip else "tpamd_resample_uniform", args, host=False, stream=stream)
 
     def fastest_stop(self, time, s, qd, qdd, max_acceleration, query_time, count=None,
                      profile=False, stream=None, host=False):
@@ -1482,17 +842,11 @@ class Engine:
         arrays (numpy or torch), numpy outputs, synchronous."""
         B, M, D = qd.shape
         if host:
-            cv = lambda x, dt: None if x is None else np.ascontiguousarray(
-                x.numpy() if hasattr(x, "numpy") else x, dtype=dt)
             time, s, qd, qdd, max_acceleration, query_time = (
-                cv(x, np.float64) for x in (time, s, qd, qdd, max_acceleration, query_time))
-            count = cv(count, np.int32)
-            new = lambda shape, dt: np.zeros(shape, dtype=dt)
-            f64, i32 = np.float64, np.int32
-        else:
-            import torch
-            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=qd.device)
-            f64, i32 = torch.float64, torch.int32
+                _cpu_array(x, np.float64) for x in (time, s, qd, qdd, max_acceleration, query_time))
+            count = _cpu_array(count, np.int32)
+        xp = _NUMPY if host else _Torch(qd.device)
+        new, f64, i32 = xp.zeros, xp.float64, xp.int32
         out = dict(stop_parameter=new((B,), f64), stop_index=new((B,), i32),
                    duration=new((B,), f64), status=new((B,), i32))
         if profile:
@@ -1503,12 +857,7 @@ class Engine:
             _ptr(max_acceleration), _ptr(query_time),
             *[_ptr(out.get(k)) for k in ("stop_parameter", "stop_index", "duration", "status",
                                          "profile_time", "profile_rate2", "profile_drate2")])
-        if host:
-            _check(self._lib.tpamd_fastest_stop_host(self._h, C.byref(args)),
-                   "tpamd_fastest_stop_host")
-        else:
-            _check(self._lib.tpamd_fastest_stop_device(self._h, C.byref(args), _stream_ptr(stream)),
-                   "tpamd_fastest_stop_device")
+        self._call("tpamd_fastest_stop", args, host=host, stream=stream)
         return out
 
     def stop_trajectories(self, time, qd, qdd, max_acceleration, time_step, stop_time=None, stop_index=None,
@@ -1524,17 +873,11 @@ class Engine:
             raise TpamdError("give either stop_time or stop_index")
         B, M, D = qd.shape
         if host:
-            cv = lambda x, dt: None if x is None else np.ascontiguousarray(
-                x.numpy() if hasattr(x, "numpy") else x, dtype=dt)
             time, qd, qdd, max_acceleration, stop_time = (
-                cv(x, np.float64) for x in (time, qd, qdd, max_acceleration, stop_time))
-            count, stop_index = cv(count, np.int32), cv(stop_index, np.int32)
-            new = lambda shape, dt: np.zeros(shape, dtype=dt)
-            f64, i32 = np.float64, np.int32
-        else:
-            import torch
-            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=qd.device)
-            f64, i32 = torch.float64, torch.int32
+                _cpu_array(x, np.float64) for x in (time, qd, qdd, max_acceleration, stop_time))
+            count, stop_index = _cpu_array(count, np.int32), _cpu_array(stop_index, np.int32)
+        xp = _NUMPY if host else _Torch(qd.device)
+        new, f64, i32 = xp.zeros, xp.float64, xp.int32
         res = {k: new((B,), i32) for k in ("status", "keep", "first", "last")}
         for k, shape in (("out_time", (B, M)), ("out_qd", (B, M, D)), ("out_qdd", (B, M, D))):
             res[k] = out[k] if out is not None else new(shape, f64)
@@ -1544,20 +887,14 @@ class Engine:
             B, M, D, 0, _ptr(time), _ptr(qd), _ptr(qdd), _ptr(count), _ptr(max_acceleration), float(time_step),
             _ptr(stop_time), _ptr(stop_index),
             *[_ptr(res[k]) for k in ("status", "keep", "first", "last", "out_time", "out_qd", "out_qdd")])
-        if host:
-            _check(self._lib.tpamd_stop_trajectories_host(self._h, C.byref(args)), "tpamd_stop_trajectories_host")
-        else:
-            _check(self._lib.tpamd_stop_trajectories_device(self._h, C.byref(args), _stream_ptr(stream)),
-                   "tpamd_stop_trajectories_device")
+        self._call("tpamd_stop_trajectories", args, host=host, stream=stream)
         return res
 
     def debug_boundary(self, B, N):
         arr = {k: np.zeros((B, N)) for k in ("sd2_max", "sdd_max", "sdd_min", "sd2_zero", "sd2")}
         arr["type"] = np.zeros((B, N), dtype=np.uint8)
-        _check(self._lib.tpamd_debug_copy_boundary(
-            self._h, B, N, _ptr(arr["sd2_max"]), _ptr(arr["sdd_max"]), _ptr(arr["sdd_min"]),
-            _ptr(arr["sd2_zero"]), _ptr(arr["type"]), _ptr(arr["sd2"])),
-            "tpamd_debug_copy_boundary")
+        self._call("tpamd_debug_copy_boundary", B, N, arr["sd2_max"], arr["sdd_max"], arr["sdd_min"],
+                   arr["sd2_zero"], arr["type"], arr["sd2"])
         return arr
 
     def debug_keep_boundary(self, on=True):
@@ -1569,10 +906,8 @@ class Engine:
         """time [num_shards * paths_per_shard][N] from sd (tpamd_rebuild_time_device). sd, ds and
         time_start are tensors (views) that start at shard 0's data; shard r lies shard_stride
         doubles further."""
-        _check(self._lib.tpamd_rebuild_time_device(
-            self._h, num_shards, paths_per_shard, num_samples, shard_stride, _ptr(sd), _ptr(ds),
-            _ptr(time_start), _ptr(num_samples_per_path), _ptr(out), _stream_ptr(stream)),
-            "tpamd_rebuild_time_device")
+        self._call("tpamd_rebuild_time", num_shards, paths_per_shard, num_samples, shard_stride, sd, ds,
+                   time_start, num_samples_per_path, out, host=False, stream=stream)
 
     def debug_kernel_vgprs(self, which):
         """Registers per lane of the 7-joint sampling/LP kernel (0) / sweep kernel (1)."""
@@ -1582,12 +917,12 @@ class Engine:
 
     def debug_diag(self, B):
         out = np.zeros((B, 64), dtype=np.int64)
-        _check(self._lib.tpamd_debug_copy_diag(self._h, B, _ptr(out)), "tpamd_debug_copy_diag")
+        self._call("tpamd_debug_copy_diag", B, out)
         return out
 
     def debug_diag_ext(self, B):
         out = np.zeros((B, 32), dtype=np.int64)
-        _check(self._lib.tpamd_debug_copy_diag_ext(self._h, B, _ptr(out)), "tpamd_debug_copy_diag_ext")
+        self._call("tpamd_debug_copy_diag_ext", B, out)
         return out
 
     # ---------------------------------------------------------------- timing
@@ -1611,23 +946,7 @@ class Engine:
         return out
 
 
-def _is_cuda(t):
-    return hasattr(t, "is_cuda") and t.is_cuda
-
-
-def _host(x, dtype, shape=None, what="argument"):
-    """A C-contiguous numpy copy of a host (or CUDA) array-like; None stays None."""
-    if x is None:
-        return None
-    if hasattr(x, "detach"):
-        x = x.detach().cpu().numpy()
-    a = np.ascontiguousarray(np.asarray(x, dtype=dtype))
-    if shape is not None and a.shape != tuple(shape):
-        raise TpamdError("%s has shape %s, expected %s" % (what, a.shape, tuple(shape)))
-    return a
-
-
-class PlannerSet:
+class PlannerSet(_Native):
     """B receding-horizon planners with joint-space spline paths whose whole state stays on the
     device between calls (include/tpamd.h tpamd_planner_set_*). The typical loop keeps its goals,
     limits and setpoints in CUDA tensors:
@@ -1646,6 +965,8 @@ class PlannerSet:
     Cartesian path (set_ik_tables; table_capacity rows per planner to start with, it grows). The
     joint-spline calls (set_waypoints, set_paths, download_path, switch_paths, retarget) fail on such a set,
     set_ik_tables / download_ik_table on a joint set; everything else works on both kinds."""
+
+    _kind, _destroy, _host_suffix = "planner set", "tpamd_planner_set_destroy", ""
 
     def __init__(self, engine, num_planners, num_dofs, num_samples, num_points=16, time_step_ns=4_000_000,
                  sampling_method=0, max_planning_iterations=200, constraint_safety=0.8,
@@ -1666,35 +987,15 @@ class PlannerSet:
         else:
             _check(self._lib.tpamd_planner_set_create(engine._h, C.byref(cfg), C.byref(h)), "tpamd_planner_set_create")
         self._engine = engine          # the set must not outlive its engine
-        self._h = h
+        self._adopt(h)
         self._num_samples = np.zeros(self.B, dtype=np.int64)    # GetNumTimeSamples after the last plan
         self._pending = None           # the PlanHandle of a plan_async whose result() has not run yet
         self._imports = []             # device imports whose summaries have not been read yet
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self, "_pending", None) is not None:
-                self._pending._stream.synchronize()      # the call writes the handle's tensors
-                self._pending = None
-            self._lib.tpamd_planner_set_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise TpamdError("the planner set is closed")
-        return self._h
+    def _release(self):
+        if getattr(self, "_pending", None) is not None:
+            self._pending._stream.synchronize()      # the call writes the handle's tensors
+            self._pending = None
 
     def _sample_counts(self):
         """The sample counts of the last plan; they are unknown while a plan_async is in flight."""
@@ -1736,43 +1037,22 @@ class PlannerSet:
         a CUDA `waypoints` every array is taken on its device and the call only enqueues on
         `stream` (default: torch's current stream); results are CUDA tensors. Otherwise the host
         entry runs and synchronises; results are CPU tensors."""
-        import torch
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        ida, n = self._ids(ids, off.shape[0] - 1)
-        if off.shape[0] != n + 1:
-            raise TpamdError("waypoint offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        off, ida, n = self._offsets(offsets, ids, "waypoint offsets")
         D = self.D
-        if _is_cuda(waypoints):
-            dev = waypoints.device
-            f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
-            w = f(waypoints, None, "waypoints").reshape(-1, D) if waypoints.numel() else \
-                torch.zeros((0, D), dtype=torch.float64, device=dev)
-            if n and w.shape[0] != off[-1]:
-                raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
-            vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
-            dl = f(delta if hasattr(delta, "shape") else torch.full((n,), float(delta), dtype=torch.float64),
-                   (n,), "delta")
-            iv = None if initial_velocity is None else f(initial_velocity, (n, D), "initial_velocity")
-            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            num_points = torch.zeros((n,), dtype=torch.int32, device=dev)
-            _check(self._lib.tpamd_planner_set_set_waypoints_device(
-                self._handle(), n, _ptr(ida), _ptr(off), w.data_ptr() if w.numel() else None, float(rounding),
-                _ptr(vm), _ptr(am), _ptr(dl), _ptr(iv), _ptr(num_points), _ptr(status),
-                _stream_ptr(stream)), "tpamd_planner_set_set_waypoints_device")
-            return status, num_points
-        w = _host(waypoints, np.float64, what="waypoints").reshape(-1, D)
-        if w.shape[0] != off[-1]:
+        xp = _backend(waypoints, as_torch=True)
+        # (the device side takes an empty tensor of any shape, and no rows at all when nobody is listed)
+        w = xp.array(waypoints, xp.float64, what="waypoints").reshape(-1, D) if xp.host or waypoints.numel() else \
+            xp.zeros((0, D))
+        if (xp.host or n) and w.shape[0] != off[-1]:
             raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
-        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
-        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
-        dl = _host(np.broadcast_to(_host(delta, np.float64), (n,)), np.float64, (n,), "delta")
-        iv = _host(initial_velocity, np.float64, (n, D), "initial_velocity")
-        status = np.full(n, -1, dtype=np.int32)
-        num_points = np.zeros(n, dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_set_waypoints(
-            self._handle(), n, _ptr(ida), _ptr(off), _ptr(w) if w.size else None, float(rounding), _ptr(vm),
-            _ptr(am), _ptr(dl), _ptr(iv), _ptr(num_points), _ptr(status)), "tpamd_planner_set_set_waypoints")
-        return torch.from_numpy(status), torch.from_numpy(num_points)
+        vm = xp.array(max_velocity, xp.float64, (n, D), "max_velocity")
+        am = xp.array(max_acceleration, xp.float64, (n, D), "max_acceleration")
+        dl = xp.per(delta, n, "delta")
+        iv = xp.array(initial_velocity, xp.float64, (n, D), "initial_velocity")
+        status, num_points = xp.full(n, -1, xp.int32), xp.zeros(n, xp.int32)
+        self._call("tpamd_planner_set_set_waypoints", n, ida, off, w if w.shape[0] else None, float(rounding), vm, am,
+                   dl, iv, num_points, status, host=xp.host, stream=stream)
+        return xp.result(status), xp.result(num_points)
 
     def retarget(self, time_ns, waypoints, offsets, max_velocity, max_acceleration, delta, ids=None, rounding=0.2,
                  stopping_acceleration=None, stream=None):
@@ -1787,58 +1067,33 @@ class PlannerSet:
         CUDA `waypoints` (or, without waypoints, a CUDA time_ns) every array is taken on its device
         and the call only enqueues on `stream` (default: torch's current stream); results are CUDA
         tensors. Otherwise the host entry runs and synchronises; results are CPU tensors."""
-        import torch
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        ida, n = self._ids(ids, off.shape[0] - 1)
-        if off.shape[0] != n + 1:
-            raise TpamdError("waypoint offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
-        D = self.D
-        if _is_cuda(waypoints) or (_is_cuda(time_ns) and int(off[-1]) == 0):
-            dev = waypoints.device if _is_cuda(waypoints) else time_ns.device
-            f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
-            w = f(waypoints, None, "waypoints").reshape(-1, D) if int(off[-1]) else \
-                torch.zeros((0, D), dtype=torch.float64, device=dev)
-            if w.shape[0] != off[-1]:
-                raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
-            t = self._cuda(time_ns, torch.int64, dev, (n,), "time_ns")
-            vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
-            dl = f(delta if hasattr(delta, "shape") else torch.full((n,), float(delta), dtype=torch.float64),
-                   (n,), "delta")
-            sa = None if stopping_acceleration is None else f(stopping_acceleration, (n, D), "stopping_acceleration")
-            nan = lambda: torch.full((n, D), float("nan"), dtype=torch.float64, device=dev)
-            out = dict(status=torch.full((n,), -1, dtype=torch.int32, device=dev),
-                       num_points=torch.zeros((n,), dtype=torch.int32, device=dev),
-                       position=nan(), velocity=nan(), stopping_point=nan())
-            _check(self._lib.tpamd_planner_set_retarget_device(
-                self._handle(), n, _ptr(ida), _ptr(t), _ptr(off), w.data_ptr() if w.numel() else None,
-                float(rounding), _ptr(vm), _ptr(am), _ptr(dl), _ptr(sa), _ptr(out["num_points"]), _ptr(out["status"]),
-                _ptr(out["position"]), _ptr(out["velocity"]), _ptr(out["stopping_point"]), _stream_ptr(stream)),
-                "tpamd_planner_set_retarget_device")
-            return out
-        w = _host(waypoints, np.float64, what="waypoints").reshape(-1, D)
+        off, ida, n = self._offsets(offsets, ids, "waypoint offsets")
+        D, nan = self.D, float("nan")
+        xp = _backend(waypoints if _is_cuda(waypoints) or int(off[-1]) else time_ns, as_torch=True)
+        # (without waypoints the device side does not look at `waypoints`)
+        w = xp.array(waypoints, xp.float64, what="waypoints").reshape(-1, D) if xp.host or int(off[-1]) else \
+            xp.zeros((0, D))
         if w.shape[0] != off[-1]:
             raise TpamdError("waypoints has %d rows, offsets end at %d" % (w.shape[0], off[-1]))
-        t = _host(time_ns, np.int64, (n,), "time_ns")
-        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
-        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
-        dl = _host(np.broadcast_to(_host(delta, np.float64), (n,)), np.float64, (n,), "delta")
-        sa = _host(stopping_acceleration, np.float64, (n, D), "stopping_acceleration")
-        out = dict(status=np.full(n, -1, dtype=np.int32), num_points=np.zeros(n, dtype=np.int32),
-                   position=np.full((n, D), np.nan), velocity=np.full((n, D), np.nan),
-                   stopping_point=np.full((n, D), np.nan))
-        _check(self._lib.tpamd_planner_set_retarget(
-            self._handle(), n, _ptr(ida), _ptr(t), _ptr(off), _ptr(w) if w.size else None, float(rounding), _ptr(vm),
-            _ptr(am), _ptr(dl), _ptr(sa), _ptr(out["num_points"]), _ptr(out["status"]), _ptr(out["position"]),
-            _ptr(out["velocity"]), _ptr(out["stopping_point"])), "tpamd_planner_set_retarget")
-        return {k: torch.from_numpy(v) for k, v in out.items()}
+        t = xp.array(time_ns, xp.int64, (n,), "time_ns")
+        vm = xp.array(max_velocity, xp.float64, (n, D), "max_velocity")
+        am = xp.array(max_acceleration, xp.float64, (n, D), "max_acceleration")
+        dl = xp.per(delta, n, "delta")
+        sa = xp.array(stopping_acceleration, xp.float64, (n, D), "stopping_acceleration")
+        out = dict(status=xp.full(n, -1, xp.int32), num_points=xp.zeros(n, xp.int32), position=xp.full((n, D), nan),
+                   velocity=xp.full((n, D), nan), stopping_point=xp.full((n, D), nan))
+        self._call("tpamd_planner_set_retarget", n, ida, t, off, w if w.shape[0] else None, float(rounding), vm, am,
+                   dl, sa, out["num_points"], out["status"], out["position"], out["velocity"], out["stopping_point"],
+                   host=xp.host, stream=stream)
+        return {k: xp.result(v) for k, v in out.items()}
 
-    @staticmethod
-    def _cuda(x, dtype, device, shape, what):
-        import torch
-        t = torch.as_tensor(x, dtype=dtype, device=device).contiguous()
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise TpamdError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
-        return t
+    def _offsets(self, offsets, ids, what, dtype=np.int32):
+        """Host offsets [count + 1] (`what` names them in errors) with the listed ids and their count."""
+        off = _host(offsets, dtype, what=what).reshape(-1)
+        ida, n = self._ids(ids, off.shape[0] - 1)
+        if off.shape[0] != n + 1:
+            raise TpamdError("%s need count + 1 = %d entries, got %d" % (what, n + 1, off.shape[0]))
+        return off, ida, n
 
     def set_paths(self, knots, control_points, num_points, max_velocity, max_acceleration, delta,
                   initial_velocity=None, ids=None, path_state=None):
@@ -1860,9 +1115,7 @@ class PlannerSet:
         dl = _host(np.broadcast_to(_host(delta, np.float64), (n,)), np.float64, (n,), "delta")
         iv = _host(initial_velocity, np.float64, (n, D), "initial_velocity")
         ps = np.ones(n, dtype=np.int32) if path_state is None else _host(path_state, np.int32, (n,), "path_state")
-        _check(self._lib.tpamd_planner_set_upload_paths_ragged(
-            self._handle(), n, _ptr(ida), _ptr(npts), _ptr(k), _ptr(c), _ptr(vm), _ptr(am), _ptr(dl), _ptr(iv),
-            _ptr(ps)), "tpamd_planner_set_upload_paths_ragged")
+        self._call("tpamd_planner_set_upload_paths_ragged", n, ida, npts, k, c, vm, am, dl, iv, ps)
 
     def set_ik_tables(self, ik_positions, jacobians, row_offsets, path_end, max_velocity, max_acceleration,
                       max_translational_velocity, max_rotational_velocity, delta, initial_velocity=None, ids=None,
@@ -1875,42 +1128,21 @@ class PlannerSet:
         path_state [count] int32 (1 kNewPath, the default, or 2 kModifiedPath). With a CUDA
         `ik_positions` every array is taken on its device and the call only enqueues on `stream`
         (default: torch's current stream); otherwise the host entry runs and synchronises."""
-        import torch
-        off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
-        ida, n = self._ids(ids, off.shape[0] - 1)
-        if off.shape[0] != n + 1:
-            raise TpamdError("row offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        off, ida, n = self._offsets(row_offsets, ids, "row offsets")
         D = self.D
         rows = int(off[-1]) if n else 0
-        if _is_cuda(ik_positions):
-            dev = ik_positions.device
-            f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
-            per = lambda x, what: f(x if hasattr(x, "shape") else torch.full((n,), float(x), dtype=torch.float64),
-                                    (n,), what)
-            q, J = f(ik_positions, (rows, D), "ik_positions"), f(jacobians, (rows, 6, D), "jacobians")
-            pe, vt, vr, dl = (per(path_end, "path_end"), per(max_translational_velocity, "max_translational_velocity"),
-                              per(max_rotational_velocity, "max_rotational_velocity"), per(delta, "delta"))
-            vm, am = f(max_velocity, (n, D), "max_velocity"), f(max_acceleration, (n, D), "max_acceleration")
-            iv = None if initial_velocity is None else f(initial_velocity, (n, D), "initial_velocity")
-            ps = self._cuda(torch.ones(n, dtype=torch.int32) if path_state is None else path_state, torch.int32, dev,
-                            (n,), "path_state")
-            _check(self._lib.tpamd_planner_set_upload_ik_tables_device(
-                self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _ptr(pe), _ptr(vm), _ptr(am), _ptr(vt),
-                _ptr(vr), _ptr(dl), _ptr(iv), _ptr(ps), _stream_ptr(stream)),
-                "tpamd_planner_set_upload_ik_tables_device")
-            return
-        per = lambda x, what: _host(np.broadcast_to(_host(x, np.float64), (n,)), np.float64, (n,), what)
-        q = _host(ik_positions, np.float64, (rows, D), "ik_positions")
-        J = _host(jacobians, np.float64, (rows, 6, D), "jacobians")
-        pe, vt, vr, dl = (per(path_end, "path_end"), per(max_translational_velocity, "max_translational_velocity"),
-                          per(max_rotational_velocity, "max_rotational_velocity"), per(delta, "delta"))
-        vm = _host(max_velocity, np.float64, (n, D), "max_velocity")
-        am = _host(max_acceleration, np.float64, (n, D), "max_acceleration")
-        iv = _host(initial_velocity, np.float64, (n, D), "initial_velocity")
-        ps = np.ones(n, dtype=np.int32) if path_state is None else _host(path_state, np.int32, (n,), "path_state")
-        _check(self._lib.tpamd_planner_set_upload_ik_tables(
-            self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _ptr(pe), _ptr(vm), _ptr(am), _ptr(vt),
-            _ptr(vr), _ptr(dl), _ptr(iv), _ptr(ps)), "tpamd_planner_set_upload_ik_tables")
+        xp = _backend(ik_positions)
+        q = xp.array(ik_positions, xp.float64, (rows, D), "ik_positions")
+        J = xp.array(jacobians, xp.float64, (rows, 6, D), "jacobians")
+        pe, vt, vr, dl = (xp.per(path_end, n, "path_end"),
+                          xp.per(max_translational_velocity, n, "max_translational_velocity"),
+                          xp.per(max_rotational_velocity, n, "max_rotational_velocity"), xp.per(delta, n, "delta"))
+        vm = xp.array(max_velocity, xp.float64, (n, D), "max_velocity")
+        am = xp.array(max_acceleration, xp.float64, (n, D), "max_acceleration")
+        iv = xp.array(initial_velocity, xp.float64, (n, D), "initial_velocity")
+        ps = xp.full(n, 1, xp.int32) if path_state is None else xp.array(path_state, xp.int32, (n,), "path_state")
+        self._call("tpamd_planner_set_upload_ik_tables", n, ida, off, q, J, pe, vm, am, vt, vr, dl, iv, ps,
+                   host=xp.host, stream=stream)
 
     def set_pose_waypoints(self, pose_waypoints, joint_waypoints, offsets, ik, max_velocity, max_acceleration,
                            max_translational_velocity, max_rotational_velocity, delta, translation_rounding=0.05,
@@ -1937,15 +1169,12 @@ class PlannerSet:
         import torch
         if not self.cartesian:
             _check(-1, "tpamd_planner_set_upload_ik_tables_device")      # what the entry returns on a joint set
-        off = _host(offsets, np.int32, what="waypoint offsets").reshape(-1)
-        ida, n = self._ids(ids, off.shape[0] - 1)
-        if off.shape[0] != n + 1:
-            raise TpamdError("waypoint offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        off, ida, n = self._offsets(offsets, ids, "waypoint offsets")
         D = self.D
         dev = pose_waypoints.device if _is_cuda(pose_waypoints) else torch.device("cuda", self.device)
-        f = lambda x, shape, what: self._cuda(x, torch.float64, dev, shape, what)
-        per = lambda x, what: f(x if hasattr(x, "shape") else torch.full((n,), float(x), dtype=torch.float64),
-                                (n,), what)
+        xp = _Torch(dev)
+        f = lambda x, shape, what: xp.array(x, xp.float64, shape, what)
+        per = lambda x, what: xp.per(x, n, what)
         rows_w = int(off[-1]) if n else 0
         pw, jw = f(pose_waypoints, (rows_w, 7), "pose_waypoints"), f(joint_waypoints, (rows_w, D), "joint_waypoints")
         dl = per(delta, "delta")
@@ -1994,13 +1223,10 @@ class PlannerSet:
         """The resident IK table of one planner of a Cartesian set: (ik_positions [rows][D],
         jacobians [rows][6][D]) numpy; rows = 0: no table."""
         R = C.c_int32(0)
-        _check(self._lib.tpamd_planner_set_download_ik_table(self._handle(), int(planner), C.byref(R), None, None, 0),
-               "tpamd_planner_set_download_ik_table")
+        self._call("tpamd_planner_set_download_ik_table", int(planner), C.byref(R), None, None, 0)
         q, J = np.zeros((R.value, self.D)), np.zeros((R.value, 6, self.D))
         if R.value:
-            _check(self._lib.tpamd_planner_set_download_ik_table(self._handle(), int(planner), C.byref(R), _ptr(q),
-                                                                 _ptr(J), R.value),
-                   "tpamd_planner_set_download_ik_table")
+            self._call("tpamd_planner_set_download_ik_table", int(planner), C.byref(R), q, J, R.value)
         return q, J
 
     def discard_ik_rows(self, keep_from=None, ids=None):
@@ -2014,8 +1240,7 @@ class PlannerSet:
         if keep_from is not None:
             keep = _host(np.broadcast_to(_host(keep_from, np.int32), (n,)), np.int32)
         out = np.zeros(n, dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_discard_ik_rows(self._handle(), n, _ptr(ida), _ptr(keep), _ptr(out)),
-               "tpamd_planner_set_discard_ik_rows")
+        self._call("tpamd_planner_set_discard_ik_rows", n, ida, keep, out)
         return out
 
     def ik_table_info(self, planner):
@@ -2023,8 +1248,7 @@ class PlannerSet:
         (first_row, rows, capacity): the path row in slot 0, the path rows supplied so far (0: no
         table) and the table rows allocated per planner."""
         f, r, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        _check(self._lib.tpamd_planner_set_ik_table_info(self._handle(), int(planner), C.byref(f), C.byref(r), C.byref(c)),
-               "tpamd_planner_set_ik_table_info")
+        self._call("tpamd_planner_set_ik_table_info", int(planner), C.byref(f), C.byref(r), C.byref(c))
         return int(f.value), int(r.value), int(c.value)
 
     def download_ik_rows(self, planner):
@@ -2032,31 +1256,26 @@ class PlannerSet:
         (first_row, ik_positions [live][D], jacobians [live][6][D]) numpy, path rows first_row ..
         first_row + live - 1."""
         f, R = C.c_int32(0), C.c_int32(0)
-        _check(self._lib.tpamd_planner_set_download_ik_rows(self._handle(), int(planner), C.byref(f), C.byref(R), None,
-                                                            None, 0), "tpamd_planner_set_download_ik_rows")
+        self._call("tpamd_planner_set_download_ik_rows", int(planner), C.byref(f), C.byref(R), None, None, 0)
         q, J = np.zeros((R.value, self.D)), np.zeros((R.value, 6, self.D))
         if R.value:
-            _check(self._lib.tpamd_planner_set_download_ik_rows(self._handle(), int(planner), C.byref(f), C.byref(R),
-                                                                _ptr(q), _ptr(J), R.value),
-                   "tpamd_planner_set_download_ik_rows")
+            self._call("tpamd_planner_set_download_ik_rows", int(planner), C.byref(f), C.byref(R), q, J, R.value)
         return int(f.value), q, J
 
     def download_path(self, planner):
         """The resident spline of one planner: (knots [P + 3], control_points [P][D]) numpy; P = 0:
         no path."""
         P = C.c_int32(0)
-        _check(self._lib.tpamd_planner_set_download_path(self._handle(), int(planner), C.byref(P), None, None, 0),
-               "tpamd_planner_set_download_path")
+        self._call("tpamd_planner_set_download_path", int(planner), C.byref(P), None, None, 0)
         k, c = np.zeros(P.value + 3 if P.value else 0), np.zeros((P.value, self.D))
         if P.value:
-            _check(self._lib.tpamd_planner_set_download_path(self._handle(), int(planner), C.byref(P), _ptr(k),
-                                                             _ptr(c), P.value), "tpamd_planner_set_download_path")
+            self._call("tpamd_planner_set_download_path", int(planner), C.byref(P), k, c, P.value)
         return k, c
 
     def reset(self, ids=None):
         """TrajectoryPlanner::Reset for the listed planners (None: all)."""
         ida, n = self._ids(ids)
-        _check(self._lib.tpamd_planner_set_reset(self._handle(), n, _ptr(ida)), "tpamd_planner_set_reset")
+        self._call("tpamd_planner_set_reset", n, ida)
         self._settle_imports()
         if ida is None:
             self._num_samples[:] = 0
@@ -2075,8 +1294,7 @@ class PlannerSet:
         s = _host(np.broadcast_to(_host(start_ns, np.int64), (self.B,)), np.int64)
         h = _host(np.broadcast_to(_host(horizon_ns, np.int64), (self.B,)), np.int64)
         out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
-        _check(self._lib.tpamd_planner_set_plan(self._handle(), _ptr(s), _ptr(h), out.ctypes.data),
-               "tpamd_planner_set_plan")
+        self._call("tpamd_planner_set_plan", s, h, out)
         return self._summary(out)
 
     def last_plan_bytes(self):
@@ -2091,14 +1309,12 @@ class PlannerSet:
         bit) and the engine's workspace is sized for this set, so that plan_async allocates nothing."""
         if self._pending is not None:
             raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
-        _check(self._lib.tpamd_planner_set_reserve(self._handle(), int(history), int(trajectory)),
-               "tpamd_planner_set_reserve")
+        self._call("tpamd_planner_set_reserve", int(history), int(trajectory))
 
     def capacity(self):
         """(history, trajectory) samples per planner the buffers hold."""
         h, t = C.c_int32(0), C.c_int32(0)
-        _check(self._lib.tpamd_planner_set_capacity(self._handle(), C.byref(h), C.byref(t)),
-               "tpamd_planner_set_capacity")
+        self._call("tpamd_planner_set_capacity", C.byref(h), C.byref(t))
         return int(h.value), int(t.value)
 
     def plan_async(self, start_ns, horizon_ns, max_windows=2, stream=None):
@@ -2127,9 +1343,8 @@ class PlannerSet:
         info = torch.zeros(C.sizeof(_PlanDeviceInfo) // 4, dtype=torch.int32, device=dev)
         if st != torch.cuda.current_stream(dev):      # the zero fills ran on the current stream
             st.wait_stream(torch.cuda.current_stream(dev))
-        _check(self._lib.tpamd_planner_set_plan_device(self._handle(), _ptr(start_ns), _ptr(horizon_ns),
-                                                       int(max_windows), _ptr(summary), _ptr(info),
-                                                       _stream_ptr(st)), "tpamd_planner_set_plan_device")
+        self._call("tpamd_planner_set_plan", start_ns, horizon_ns, int(max_windows), summary, info, host=False,
+                   stream=st)
         self._pending = PlanHandle(self, st, summary, info, (start_ns, horizon_ns))
         return self._pending
 
@@ -2145,33 +1360,19 @@ class PlannerSet:
         (tpamd_planner_set_append_ik_rows*): listed planner k gets rows row_offsets[k]:row_offsets[k + 1]
         of ik_positions [rows][D] and jacobians [rows][6][D] behind its last row; limits, delta and
         path state stay. CUDA tensors take the _device entry and only enqueue on `stream`."""
-        import torch
-        off = _host(row_offsets, np.int32, what="row offsets").reshape(-1)
-        ida, n = self._ids(ids, off.shape[0] - 1)
-        if off.shape[0] != n + 1:
-            raise TpamdError("row offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        off, ida, n = self._offsets(row_offsets, ids, "row offsets")
         rows, D = (int(off[-1]) if n else 0), self.D
-        if _is_cuda(ik_positions):
-            dev = ik_positions.device
-            q = self._cuda(ik_positions, torch.float64, dev, (rows, D), "ik_positions")
-            J = self._cuda(jacobians, torch.float64, dev, (rows, 6, D), "jacobians")
-            _check(self._lib.tpamd_planner_set_append_ik_rows_device(
-                self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J), _stream_ptr(stream)),
-                "tpamd_planner_set_append_ik_rows_device")
-            return
-        q = _host(ik_positions, np.float64, (rows, D), "ik_positions")
-        J = _host(jacobians, np.float64, (rows, 6, D), "jacobians")
-        _check(self._lib.tpamd_planner_set_append_ik_rows(self._handle(), n, _ptr(ida), _ptr(off), _ptr(q), _ptr(J)),
-               "tpamd_planner_set_append_ik_rows")
+        xp = _backend(ik_positions)
+        q = xp.array(ik_positions, xp.float64, (rows, D), "ik_positions")
+        J = xp.array(jacobians, xp.float64, (rows, 6, D), "jacobians")
+        self._call("tpamd_planner_set_append_ik_rows", n, ida, off, q, J, host=xp.host, stream=stream)
 
     def _plan_streaming(self, start_ns, horizon_ns):
         s = _host(np.broadcast_to(_host(start_ns, np.int64), (self.B,)), np.int64)
         h = _host(np.broadcast_to(_host(horizon_ns, np.int64), (self.B,)), np.int64)
         out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
         need = np.zeros((2, self.B), dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_plan_streaming(self._handle(), _ptr(s), _ptr(h), out.ctypes.data,
-                                                          _ptr(need[0]), _ptr(need[1]), None),
-               "tpamd_planner_set_plan_streaming")
+        self._call("tpamd_planner_set_plan_streaming", s, h, out, need[0], need[1], None)
         return self._summary(out), need[0], need[1]
 
     def plan_resume(self):
@@ -2179,8 +1380,7 @@ class PlannerSet:
         Returns (summary dict as plan(), need_first [B], need_count [B] int32 numpy)."""
         out = np.zeros(self.B, dtype=PLANNER_SUMMARY_DTYPE)
         need = np.zeros((2, self.B), dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_plan_resume(self._handle(), out.ctypes.data, _ptr(need[0]), _ptr(need[1]),
-                                                       None), "tpamd_planner_set_plan_resume")
+        self._call("tpamd_planner_set_plan_resume", out, need[0], need[1], None)
         return self._summary(out), need[0], need[1]
 
     def plan_streaming(self, start_ns, horizon_ns, ik=None, lookahead_rows=0, discard=False):
@@ -2257,8 +1457,7 @@ class PlannerSet:
         if t.shape[0] != n:
             raise TpamdError("one time per listed planner")
         s, dur, st = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_stop_parameters(self._handle(), n, _ptr(ida), _ptr(t), _ptr(s), _ptr(dur),
-                                                           _ptr(st)), "tpamd_planner_set_stop_parameters")
+        self._call("tpamd_planner_set_stop_parameters", n, ida, t, s, dur, st)
         return dict(stop_parameter=torch.from_numpy(s), duration=torch.from_numpy(dur), status=torch.from_numpy(st))
 
     def switch_paths(self, time_ns, waypoints, offsets, ids=None, keep_path_until=None, rounding=0.2):
@@ -2278,17 +1477,14 @@ class PlannerSet:
             w = np.zeros((1, self.D))    # the entry takes a non-NULL array even without rows
         keep = _host(keep_path_until, np.float64, (n,), "keep_path_until")
         s, npts, st = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_switch_paths_rounded(
-            self._handle(), n, _ptr(ida), _ptr(t), _ptr(keep), _ptr(off), _ptr(w), float(rounding), _ptr(s), _ptr(npts),
-            _ptr(st)), "tpamd_planner_set_switch_paths_rounded")
+        self._call("tpamd_planner_set_switch_paths_rounded", n, ida, t, keep, off, w, float(rounding), s, npts, st)
         return dict(stop_parameter=torch.from_numpy(s), num_points=torch.from_numpy(npts), status=torch.from_numpy(st))
 
     # ------------------------------------------------------------ checking the windows
     def set_checking(self, on=True):
         """Check every window the Plan calls solve against its constraint rows
         (tpamd_planner_set_set_checking; off by default)."""
-        _check(self._lib.tpamd_planner_set_set_checking(self._handle(), 1 if on else 0),
-               "tpamd_planner_set_set_checking")
+        self._call("tpamd_planner_set_set_checking", 1 if on else 0)
 
     @property
     def checking(self):
@@ -2299,8 +1495,7 @@ class PlannerSet:
         of its last Plan call: a numpy structured array of PLANNER_CHECK_DTYPE. Synchronises."""
         ida, n = self._ids(ids)
         out = np.zeros(max(n, 1), dtype=PLANNER_CHECK_DTYPE)
-        _check(self._lib.tpamd_planner_set_check_results(self._handle(), n, _ptr(ida), _ptr(out)),
-               "tpamd_planner_set_check_results")
+        self._call("tpamd_planner_set_check_results", n, ida, out)
         return out[:n]
 
     def check_results_device(self, out, ids=None, stream=None):
@@ -2313,10 +1508,8 @@ class PlannerSet:
                 not out.is_contiguous()):
             raise TpamdError("out must be a contiguous CUDA uint8 tensor [count][%d]" % size)
         n = out.shape[0]
-        idt = None if ids is None else self._cuda(ids, torch.int32, torch.device("cuda", self.device), (n,), "ids")
-        _check(self._lib.tpamd_planner_set_check_results_device(self._handle(), n, _ptr(idt), _ptr(out),
-                                                                _stream_ptr(stream)),
-               "tpamd_planner_set_check_results_device")
+        idt = self._device().array(ids, torch.int32, (n,), "ids")
+        self._call("tpamd_planner_set_check_results", n, idt, out, host=False, stream=stream)
         return out
 
     # ------------------------------------------------------------ readouts
@@ -2331,10 +1524,11 @@ class PlannerSet:
         import torch
         T = int(num_ticks)
         if not host:
-            dev = torch.device("cuda", self.device)
-            st0 = self._cuda(start_ns, torch.int64, dev, None, "start_ns").reshape(-1)
+            xp = self._device()
+            dev = xp.device
+            st0 = xp.array(start_ns, torch.int64, what="start_ns").reshape(-1)
             n = st0.shape[0]
-            idt = None if ids is None else self._cuda(ids, torch.int32, dev, (n,), "ids")
+            idt = xp.array(ids, torch.int32, (n,), "ids")
             if ids is None and n > self.B:
                 raise TpamdError("more start times than planners")
             if q is None and qd is None and qdd is None:
@@ -2346,9 +1540,8 @@ class PlannerSet:
                     raise TpamdError("%s must be a contiguous CUDA float64 tensor [%d][%d][%d]" % (name, n, T, self.D))
             if status is None:
                 status = torch.full((n, T), -1, dtype=torch.int32, device=dev)
-            _check(self._lib.tpamd_planner_set_sample_at_ticks_device(
-                self._handle(), n, _ptr(idt), _ptr(st0), int(step_ns), T, _ptr(q), _ptr(qd), _ptr(qdd),
-                _ptr(status), _stream_ptr(stream)), "tpamd_planner_set_sample_at_ticks_device")
+            self._call("tpamd_planner_set_sample_at_ticks", n, idt, st0, int(step_ns), T, q, qd, qdd, status,
+                       host=False, stream=stream)
             return dict(q=q, qd=qd, qdd=qdd, status=status)
         st0 = _host(start_ns, np.int64).reshape(-1)
         ida, n = self._ids(ids, st0.shape[0])
@@ -2356,9 +1549,8 @@ class PlannerSet:
             raise TpamdError("one start time per listed planner")
         out = {k: np.full((n, T, self.D), np.nan) for k in ("q", "qd", "qdd")}
         out["status"] = np.full((n, T), -1, dtype=np.int32)
-        _check(self._lib.tpamd_planner_set_sample_at_ticks(
-            self._handle(), n, _ptr(ida), _ptr(st0), int(step_ns), T, _ptr(out["q"]), _ptr(out["qd"]),
-            _ptr(out["qdd"]), _ptr(out["status"])), "tpamd_planner_set_sample_at_ticks")
+        self._call("tpamd_planner_set_sample_at_ticks", n, ida, st0, int(step_ns), T, out["q"], out["qd"], out["qdd"],
+                   out["status"])
         return {k: torch.from_numpy(v) for k, v in out.items()}
 
     def download_trajectories(self, ids=None, stream=None):
@@ -2378,10 +1570,9 @@ class PlannerSet:
         for k in ("q", "qd", "qdd"):
             out[k] = torch.empty(rows, self.D, **f)
         idt = None if ida is None else torch.from_numpy(ida).to(dev)
-        _check(self._lib.tpamd_planner_set_download_trajectories_device(
-            self._handle(), n, _ptr(idt), _ptr(out["offsets"]), rows,
-            *[_ptr(out[k]) if rows else None for k in ("time", "s", "sd", "sdd", "q", "qd", "qdd")],
-            _stream_ptr(stream)), "tpamd_planner_set_download_trajectories_device")
+        self._call("tpamd_planner_set_download_trajectories", n, idt, out["offsets"], rows,
+                   *[out[k] if rows else None for k in ("time", "s", "sd", "sdd", "q", "qd", "qdd")],
+                   host=False, stream=stream)
         out["_ids"] = idt          # kept alive with the result until the stream has used it
         return out
 
@@ -2393,13 +1584,14 @@ class PlannerSet:
         `capacity` (default: the planners' sample counts plus 64 each); if the segments need more,
         the call is repeated with room for them (it changes no state)."""
         import torch
-        dev = torch.device("cuda", self.device)
-        t = self._cuda(time_ns, torch.int64, dev, None, "time_ns").reshape(-1)
+        xp = self._device()
+        dev = xp.device
+        t = xp.array(time_ns, torch.int64, what="time_ns").reshape(-1)
         n = t.shape[0]
-        idt = None if ids is None else self._cuda(ids, torch.int32, dev, (n,), "ids")
+        idt = xp.array(ids, torch.int32, (n,), "ids")
         if ids is None and n > self.B:
             raise TpamdError("more stop times than planners")
-        am = self._cuda(max_acceleration, torch.float64, dev, (n, self.D), "max_acceleration")
+        am = xp.array(max_acceleration, torch.float64, (n, self.D), "max_acceleration")
         if capacity is None:
             counts = self._sample_counts()
             sel = counts[:n] if ids is None else counts[_host(ids, np.int64).reshape(-1)]
@@ -2411,11 +1603,9 @@ class PlannerSet:
                        time=torch.empty(capacity, dtype=torch.float64, device=dev))
             for k in ("q", "qd", "qdd"):
                 out[k] = torch.empty(capacity, self.D, dtype=torch.float64, device=dev)
-            _check(self._lib.tpamd_planner_set_stop_trajectories_device(
-                self._handle(), n, _ptr(idt), _ptr(t), _ptr(am), float(time_step), _ptr(out["status"]),
-                _ptr(out["keep"]), _ptr(out["offsets"]), int(capacity),
-                *[_ptr(out[k]) if capacity else None for k in ("time", "q", "qd", "qdd")],
-                _stream_ptr(stream)), "tpamd_planner_set_stop_trajectories_device")
+            self._call("tpamd_planner_set_stop_trajectories", n, idt, t, am, float(time_step), out["status"],
+                       out["keep"], out["offsets"], int(capacity),
+                       *[out[k] if capacity else None for k in ("time", "q", "qd", "qdd")], host=False, stream=stream)
             rows = int(out["offsets"][-1].item()) if n else 0
             if rows <= capacity:
                 break
@@ -2432,8 +1622,7 @@ class PlannerSet:
         Synchronises."""
         ida, n = self._ids(ids)
         out = np.zeros(max(n, 1), dtype=PLANNER_STATE_INFO_DTYPE)
-        _check(self._lib.tpamd_planner_set_state_info(self._handle(), n, _ptr(ida), _ptr(out)),
-               "tpamd_planner_set_state_info")
+        self._call("tpamd_planner_set_state_info", n, ida, out)
         return out[:n]
 
     @property
@@ -2471,11 +1660,8 @@ class PlannerSet:
             idt = None if ida is None else torch.from_numpy(ida).to(dev)
             offt = torch.from_numpy(off).to(dev)
             status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        _check(self._lib.tpamd_planner_set_export_state_device(
-            self._handle(), n, _ptr(idt), _ptr(out), _ptr(offt), _ptr(status), _stream_ptr(st)),
-            "tpamd_planner_set_export_state_device")
+        self._call("tpamd_planner_set_export_state", n, idt, out, offt, status, host=False, stream=st)
         self.last_export_status = status
-        self._export_keep = (idt, offt)      # alive until the stream has read them
         return out[:total], torch.from_numpy(off)
 
     def import_state(self, blob, offsets, ids=None, stream=None):
@@ -2490,10 +1676,7 @@ class PlannerSet:
         tpamd_planner_set_import_state_host, which validates every record first, grows the set as
         needed and synchronises; returns dict status (CPU int32) plus the summary fields of plan()."""
         import torch
-        off = _host(offsets, np.int64, what="offsets").reshape(-1)
-        ida, n = self._ids(ids, off.shape[0] - 1)
-        if off.shape[0] != n + 1:
-            raise TpamdError("offsets need count + 1 = %d entries, got %d" % (n + 1, off.shape[0]))
+        off, ida, n = self._offsets(offsets, ids, "offsets", np.int64)
         if self._pending is not None:
             raise TpamdError("a plan_async call is in flight (PlanHandle.result())")
         total = int(off[-1]) if n else 0
@@ -2510,9 +1693,7 @@ class PlannerSet:
                     else torch.from_numpy(off).to(dev)
                 status = torch.full((n,), -1, dtype=torch.int32, device=dev)
                 summary = torch.zeros((n, PLANNER_SUMMARY_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            _check(self._lib.tpamd_planner_set_import_state_device(
-                self._handle(), n, _ptr(idt), _ptr(blob), _ptr(offt), _ptr(summary), _ptr(status), _stream_ptr(st)),
-                "tpamd_planner_set_import_state_device")
+            self._call("tpamd_planner_set_import_state", n, idt, blob, offt, summary, status, host=False, stream=st)
             self._imports.append((st, summary, status, np.arange(n) if ida is None else ida.astype(np.int64)))
             return dict(status=status, summary=summary, _keep=(idt, offt, blob))
         b = _host(blob, np.uint8, what="blob").reshape(-1)
@@ -2520,9 +1701,7 @@ class PlannerSet:
             raise TpamdError("blob has %d bytes, offsets end at %d" % (b.shape[0], total))
         status = np.full(n, -1, dtype=np.int32)
         out = np.zeros(max(n, 1), dtype=PLANNER_SUMMARY_DTYPE)
-        _check(self._lib.tpamd_planner_set_import_state_host(
-            self._handle(), n, _ptr(ida), _ptr(b), _ptr(off), out.ctypes.data, _ptr(status)),
-            "tpamd_planner_set_import_state_host")
+        self._call("tpamd_planner_set_import_state_host", n, ida, b, off, out, status)
         return self._state_result(out[:n], status, ida)
 
     def _state_result(self, out, status, ida):
@@ -2550,9 +1729,7 @@ class PlannerSet:
             raise TpamdError("src_ids and dst_ids must list the same number of planners")
         status = np.full(n, -1, dtype=np.int32)
         out = np.zeros(max(n, 1), dtype=PLANNER_SUMMARY_DTYPE)
-        _check(self._lib.tpamd_planner_set_copy_planners(
-            self._handle(), _ptr(dst), other._handle(), _ptr(src), n, out.ctypes.data, _ptr(status)),
-            "tpamd_planner_set_copy_planners")
+        self._call("tpamd_planner_set_copy_planners", dst, other._handle(), src, n, out, status)
         return self._state_result(out[:n], status, dst)
 
 
@@ -2584,7 +1761,7 @@ class PlanHandle:
         return self._result
 
 
-class BufferSet:
+class BufferSet(_Native):
     """B trajectory buffers (TrajectoryBuffer: samples of time, q, qd, qdd, a sample count and a
     sequence number each) resident on the device (include/tpamd.h tpamd_buffer_set_*). It is what
     a controller executes: after each plan the new trajectory is spliced in, consumed samples are
@@ -2602,6 +1779,8 @@ class BufferSet:
     TPAMD_PLAN_* codes in `status` (100, TPAMD_PLAN_MORE: no room, call reserve()). Errors of the
     call itself raise TpamdError."""
 
+    _kind, _destroy, _host_suffix = "buffer set", "tpamd_buffer_set_destroy", ""
+
     def __init__(self, engine, num_buffers, num_dofs, capacity=0, timestep_tolerance=1e-6):
         self._lib = load_library()
         self.B, self.D = int(num_buffers), int(num_dofs)
@@ -2610,29 +1789,7 @@ class BufferSet:
         _check(self._lib.tpamd_buffer_set_create(engine._h, self.B, self.D, int(capacity), float(timestep_tolerance),
                                                  C.byref(h)), "tpamd_buffer_set_create")
         self._engine = engine          # the set must not outlive its engine
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tpamd_buffer_set_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise TpamdError("the buffer set is closed")
-        return self._h
+        self._adopt(h)
 
     @property
     def device_bytes(self):
@@ -2644,11 +1801,10 @@ class BufferSet:
 
     def reserve(self, capacity):
         """Room for `capacity` samples per buffer (synchronises; the other calls never allocate)."""
-        _check(self._lib.tpamd_buffer_set_reserve(self._handle(), int(capacity)), "tpamd_buffer_set_reserve")
+        self._call("tpamd_buffer_set_reserve", int(capacity))
 
     def _dev(self):
-        import torch
-        return torch.device("cuda", self.device)
+        return self._device().device
 
     def _t(self, x, dtype, shape, what):
         import torch
@@ -2698,9 +1854,8 @@ class BufferSet:
         rows = tm.shape[0]
         arr = [self._t(a, torch.float64, (rows, self.D), k) for k, a in (("q", q), ("qd", qd), ("qdd", qdd))]
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_insert_device(
-            self._handle(), n, _ptr(idt), _ptr(off), rows, *[_ptr(a) if rows else None for a in [tm] + arr],
-            _ptr(st), _stream_ptr(stream)), "tpamd_buffer_set_insert_device")
+        self._call("tpamd_buffer_set_insert", n, idt, off, rows, *[a if rows else None for a in [tm] + arr], st,
+                   host=False, stream=stream)
         return dict(status=st, _keep=(idt, off, tm, arr))
 
     def insert_from(self, planner_set, ids=None, planner_ids=None, stream=None):
@@ -2712,9 +1867,8 @@ class BufferSet:
         if pid is None and ids is None:
             n = min(self.B, planner_set.B)
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_insert_from_planner_set_device(
-            self._handle(), planner_set._handle(), n, _ptr(idt), _ptr(pid), _ptr(st), _stream_ptr(stream)),
-            "tpamd_buffer_set_insert_from_planner_set_device")
+        self._call("tpamd_buffer_set_insert_from_planner_set", planner_set._handle(), n, idt, pid, st, host=False,
+                   stream=stream)
         return dict(status=st, _keep=(idt, pid))
 
     def append_sample(self, time, q, qd, qdd, ids=None, stream=None):
@@ -2724,9 +1878,7 @@ class BufferSet:
         idt, n = self._list(ids, tm.shape[0])
         arr = [self._t(a, torch.float64, (n, self.D), k) for k, a in (("q", q), ("qd", qd), ("qdd", qdd))]
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_append_sample_device(
-            self._handle(), n, _ptr(idt), _ptr(tm), *[_ptr(a) for a in arr], _ptr(st), _stream_ptr(stream)),
-            "tpamd_buffer_set_append_sample_device")
+        self._call("tpamd_buffer_set_append_sample", n, idt, tm, *arr, st, host=False, stream=stream)
         return dict(status=st, _keep=(idt, tm, arr))
 
     def discard_before(self, time_ns=None, time_sec=None, ids=None, stream=None):
@@ -2734,9 +1886,7 @@ class BufferSet:
         tn, ts, n = self._times(time_ns, time_sec)
         idt, n = self._list(ids, n)
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_discard_before_device(
-            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(ts), _ptr(st), _stream_ptr(stream)),
-            "tpamd_buffer_set_discard_before_device")
+        self._call("tpamd_buffer_set_discard_before", n, idt, tn, ts, st, host=False, stream=stream)
         return dict(status=st, _keep=(idt, tn, ts))
 
     def stop_before_time(self, max_acceleration, time_step, time_ns=None, time_sec=None, ids=None, stream=None):
@@ -2746,9 +1896,8 @@ class BufferSet:
         idt, n = self._list(ids, n)
         am = self._t(max_acceleration, torch.float64, (n, self.D), "max_acceleration")
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_stop_before_time_device(
-            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(ts), _ptr(am), float(time_step), _ptr(st),
-            _stream_ptr(stream)), "tpamd_buffer_set_stop_before_time_device")
+        self._call("tpamd_buffer_set_stop_before_time", n, idt, tn, ts, am, float(time_step), st, host=False,
+                   stream=stream)
         return dict(status=st, _keep=(idt, tn, ts, am))
 
     def sample_at_ticks(self, start_ns, step_ns, num_ticks, ids=None, stream=None):
@@ -2761,9 +1910,8 @@ class BufferSet:
         out = {k: torch.full((n, T, self.D), float("nan"), dtype=torch.float64, device=self._dev())
                for k in ("q", "qd", "qdd")}
         out["status"] = torch.full((n, T), -1, dtype=torch.int32, device=self._dev())
-        _check(self._lib.tpamd_buffer_set_sample_at_ticks_device(
-            self._handle(), n, _ptr(idt), _ptr(s0), int(step_ns), T, _ptr(out["q"]), _ptr(out["qd"]),
-            _ptr(out["qdd"]), _ptr(out["status"]), _stream_ptr(stream)), "tpamd_buffer_set_sample_at_ticks_device")
+        self._call("tpamd_buffer_set_sample_at_ticks", n, idt, s0, int(step_ns), T, out["q"], out["qd"], out["qdd"],
+                   out["status"], host=False, stream=stream)
         out["_keep"] = (idt, s0)
         return out
 
@@ -2772,16 +1920,13 @@ class BufferSet:
         tn, ts, n = self._times(offset_ns, offset_sec)
         idt, n = self._list(ids, n)
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_add_offset_device(
-            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(ts), _ptr(st), _stream_ptr(stream)),
-            "tpamd_buffer_set_add_offset_device")
+        self._call("tpamd_buffer_set_add_offset", n, idt, tn, ts, st, host=False, stream=stream)
         return dict(status=st, _keep=(idt, tn, ts))
 
     def clear(self, ids=None, stream=None):
         idt, n = self._list(ids, None)
         st = self._status(n)
-        _check(self._lib.tpamd_buffer_set_clear_device(self._handle(), n, _ptr(idt), _ptr(st), _stream_ptr(stream)),
-               "tpamd_buffer_set_clear_device")
+        self._call("tpamd_buffer_set_clear", n, idt, st, host=False, stream=stream)
         return dict(status=st, _keep=(idt,))
 
     def info(self, time_ns=None, ids=None, stream=None):
@@ -2797,10 +1942,8 @@ class BufferSet:
                    end_ns=torch.zeros(n, dtype=torch.int64, device=dev))
         if tn is not None:
             out["positions_up_to"] = torch.zeros(n, dtype=torch.int32, device=dev)
-        _check(self._lib.tpamd_buffer_set_info_device(
-            self._handle(), n, _ptr(idt), _ptr(tn), _ptr(out["num_samples"]), _ptr(out["sequence"]),
-            _ptr(out["start_ns"]), _ptr(out["end_ns"]), _ptr(out.get("positions_up_to")), _stream_ptr(stream)),
-            "tpamd_buffer_set_info_device")
+        self._call("tpamd_buffer_set_info", n, idt, tn, out["num_samples"], out["sequence"], out["start_ns"],
+                   out["end_ns"], out.get("positions_up_to"), host=False, stream=stream)
         out["_keep"] = (idt, tn)
         return out
 
@@ -2816,10 +1959,8 @@ class BufferSet:
                    time=torch.empty(rows, dtype=torch.float64, device=dev))
         for k in ("q", "qd", "qdd"):
             out[k] = torch.empty(rows, self.D, dtype=torch.float64, device=dev)
-        _check(self._lib.tpamd_buffer_set_download_device(
-            self._handle(), n, _ptr(idt), _ptr(out["offsets"]), rows,
-            *[_ptr(out[k]) if rows else None for k in ("time", "q", "qd", "qdd")], _stream_ptr(stream)),
-            "tpamd_buffer_set_download_device")
+        self._call("tpamd_buffer_set_download", n, idt, out["offsets"], rows,
+                   *[out[k] if rows else None for k in ("time", "q", "qd", "qdd")], host=False, stream=stream)
         total = int(out["offsets"][-1].item())
         if total > rows:
             raise TpamdError("the buffers hold %d rows, capacity %d" % (total, rows))
@@ -2827,15 +1968,6 @@ class BufferSet:
             out[k] = out[k][:total]
         out["_keep"] = (idt,)
         return out
-
-
-def _stream_ptr(stream):
-    if stream is None:
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if isinstance(stream, int):
-        return C.c_void_p(stream)
-    return C.c_void_p(stream.cuda_stream)
 
 
 def alloc_joint_outputs(B, N, D, device, with_q=True, with_derivs=True):
