@@ -53,6 +53,7 @@ extern "C" {
 #define TPAMD_PATH_NONZERO_END 9
 #define TPAMD_PATH_CRIT_INDEX_ZERO 10 /* reference reads sd2_max[-1] here (.cc:361,:372) */
 #define TPAMD_PATH_NO_WAYPOINTS 11 /* tpamd_time_waypoint_paths_*: a path without waypoints has no spline (timeable_path_joint_spline.cc:200-207) */
+#define TPAMD_PATH_SWEEP_POLL_EXPIRED 12 /* internal error, never expected: a bounded wait between the two waves of a sweep workgroup ran out (csrc/tpamd_sweep_joint.h, "loop queue") */
 
 typedef struct tpamd_engine tpamd_engine;
 

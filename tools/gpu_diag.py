@@ -18,7 +18,7 @@ for _ in range(3):
     E.time_joint_paths(inp, out, N)
 torch.cuda.synchronize()
 d = E.debug_diag(B).astype(np.float64)
-names = ["extremal cycles (loop)", "wait for partner (loop end)", "crit search", "tail", "chain-block cycles",
+names = ["extremal cycles (loop)", None, "crit search", "tail", "chain-block cycles",
          "first pair + loop", "chain blocks", "crit mismatches (must be 0)", "boundary-follow blocks",
          "first pair cycles", "scalar FindSdd steps", "loops", "tile fills", "fills w/o prefetch",
          "chain steps accepted", "whole kernel after set-up", "tail: sd/dt pass",
@@ -28,24 +28,34 @@ names[12] = "qd/qdd inside the loop"
 names[13] = "tail: up to the sd/dt pass"
 print("%-30s %38s | %38s" % ("B=%d D=%d N=%d" % (B, D, N), "backward wave (mean/min/max)", "forward wave (mean/min/max)"))
 for k, n in enumerate(names):
+    if n is None:
+        continue
     a, f = d[:, k], d[:, 32 + k]
     print("%-30s %12.0f %12.0f %12.0f | %12.0f %12.0f %12.0f" % (n, a.mean(), a.min(), a.max(), f.mean(), f.min(), f.max()))
 # (the literal walk of the diagnostic build runs in the forward wave since the search moved there)
 net = d[:, 32 + 15] - d[:, 32 + 18]
 print("whole kernel minus the literal walk (forward wave): mean %.0f min %.0f max %.0f" % (net.mean(), net.min(), net.max()))
 
-# The closing barrier of a switching-point loop, split by what the backward wave was doing when the
-# forward wave posted "done" (JointSweep::diagx, backward wave's slots), and the trips of emit_range.
-x = E.debug_diag_ext(B).astype(np.float64)[:, :16]
-loops = np.maximum(x[:, 0] + x[:, 1] + x[:, 2], 1)
-print("closing barrier, per path (mean): loops %.1f = backward wave still in its extremal %.1f + emission stopped %.1f + "
-      "backward wave through first %.1f" % (loops.mean(), x[:, 0].mean(), x[:, 1].mean(), x[:, 2].mean()))
-print("  emission stopped: (a) done-post -> backward wave leaves emit_range %.0f cycles (%.0f per loop), (b) its fence before the "
-      "barrier %.0f (%.0f per loop), forward wave stood at the barrier %.0f"
-      % (x[:, 3].mean(), x[:, 3].sum() / max(x[:, 1].sum(), 1), x[:, 4].mean(), x[:, 4].sum() / max(x[:, 1].sum(), 1), x[:, 5].mean()))
-print("  (c) backward wave still in its extremal: forward wave stood at the barrier %.0f cycles (%.0f per loop)"
-      % (x[:, 6].mean(), x[:, 6].sum() / max(x[:, 0].sum(), 1)))
-print("  fence cycles of all loops %.0f; emit_range trips started inside loops %.1f" % (x[:, 7].mean(), x[:, 8].mean()))
+# The loop queue (JointSweep::diagx): what the forward wave waited for, by cause, how deep the queue was
+# when the backward wave took an entry, and who was first at (sd2[icrit+1], sdd[icrit]).
+xx = E.debug_diag_ext(B).astype(np.float64)
+x, f = xx[:, :16], xx[:, 16:32]
+for k, n in enumerate(("a rare branch reads next to the switching point (hazards 1 and 2)",
+                       "marks in an earlier first-step footprint (hazard 3)", "ring full")):
+    print("forward wave waits, %-66s %9.0f cycles per path (max %9.0f), %7.3f waits per path, paths with one %d"
+          % (n, f[:, k].mean(), f[:, k].max(), f[:, 9 + k].mean(), int((f[:, 9 + k] > 0).sum())))
+print("forward wave at the final join %.0f cycles per path (max %.0f); backward wave %.0f (max %.0f)"
+      % (f[:, 4].mean(), f[:, 4].max(), x[:, 7].mean(), x[:, 7].max()))
+print("backward wave waiting for an entry %.0f cycles per path (max %.0f), %.1f waits per path"
+      % (x[:, 0].mean(), x[:, 0].max(), x[:, 9].mean()))
+taken = np.maximum(x[:, 1:5].sum(axis=1), 1)
+print("entries taken per path %.1f; queue depth at the take 1: %.2f  2: %.2f  3: %.2f  4: %.2f per path (totals %s)"
+      % (taken.mean(), x[:, 1].mean(), x[:, 2].mean(), x[:, 3].mean(), x[:, 4].mean(), [int(v) for v in x[:, 1:5].sum(axis=0)]))
+print("entries found forward first at the end of the backward first step %.2f per path (total %d; the forward wave counted %d), backward first %.2f (total %d)"
+      % (x[:, 5].mean(), int(x[:, 5].sum()), int(f[:, 5].sum()), x[:, 6].mean(), int(x[:, 6].sum())))
+print("emit_range trips started inside loops %.1f" % x[:, 8].mean())
+st = out["status"].cpu().numpy()
+print("statuses:", {int(k): int((st == k).sum()) for k in np.unique(st)})
 
 # per-path cycles of the whole kernel (the launch lasts as long as its slowest path): histogram for
 # profiles/ (DIAG_HIST=path.json)

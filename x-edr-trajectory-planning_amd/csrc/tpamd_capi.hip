@@ -592,6 +592,7 @@ const char *tpamd_error_string(int code) {
     case TPAMD_PATH_NONZERO_END: return "non-zero terminal velocity";
     case TPAMD_PATH_CRIT_INDEX_ZERO: return "critical point search degenerated to index 0";
     case TPAMD_PATH_NO_WAYPOINTS: return "path without waypoints";
+    case TPAMD_PATH_SWEEP_POLL_EXPIRED: return "internal error: a bounded wait inside the sweep kernel ran out";
     default: return "unknown";
   }
 }

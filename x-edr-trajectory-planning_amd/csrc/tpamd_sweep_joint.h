@@ -231,6 +231,26 @@ __device__ __forceinline__ long long tpamd_stamp() {
 #ifndef TPAMD_CHAIN_GUESS
 #define TPAMD_CHAIN_GUESS 0
 #endif
+// The loop queue of the two-wave kernel (k_sweep_joint, "the switching-point loop"): control words
+// among the exchange words, then a ring of kQRing entries of kQEntryWords words each.
+constexpr int kQRing = 4;
+constexpr int kQEntryWords = 16;
+constexpr int kQPosted = 6;     // control word: entries posted so far (forward wave)
+constexpr int kQDone1 = 9;      // entries whose backward extremal is past its first step (backward wave)
+constexpr int kQAbort = 10;     // nonzero: a wave gave up (error posted or poll bound hit); the other stops
+constexpr int kQStatus = 11;    // the path's status after the loops (backward wave)
+constexpr int kQPollErr = 12;   // nonzero: a bounded poll ran out
+// entry fields (words); state = 4 * number + {1 posted, 2 backward wave first, 3 forward wave first}
+constexpr int kQeState = 0, kQeCrit = 1, kQeBackHi = 2, kQeCritLo = 3, kQeKind = 4;
+constexpr int kQeDeferred = 8;  // two doubles: sd2[icrit + 1], sdd[icrit] of the forward extremal's first step
+constexpr int kQKindLoop = 0, kQKindEnd = 1, kQKindCritZero = 2;
+// Iterations (of at least one s_sleep 1 each, >= 64 cycles) after which a blocking poll gives up:
+// the longest legitimate wait is a few backward extremals of a path that fills the LDS (N < 20000
+// samples, a few hundred cycles per sample), some 1e7 cycles; this is 2.7e8 cycles or more.
+constexpr int kQPollBound = 1 << 22;
+constexpr int kStatusSweepPoll = 12;   // TPAMD_PATH_SWEEP_POLL_EXPIRED (include/tpamd.h)
+static_assert(kQPosted < 16 && kQPollErr < 16 && kQeDeferred + 4 <= kQEntryWords, "loop queue layout");
+
 constexpr int kTileSamples = 32;   // largest tile (the engine pads the records by one)
 // Samples per tile of the D-joint sweep: wide records (D > 8: 30 doubles at D = 14) take 16-sample
 // tiles, which halves the prefetch registers and the rings (the 14-joint kernel spilled 288 bytes
@@ -261,11 +281,16 @@ struct RegPack {
     if (c < LIMIT) dst[c] = v;
     rest.template store<LIMIT>(dst, c + 64);
   }
+  __device__ __forceinline__ void drop() {
+    v = f64x2{0.0, 0.0};
+    rest.drop();
+  }
 };
 template <>
 struct RegPack<0> {
   template <int LIMIT> __device__ __forceinline__ void load(const f64x2 *, int) {}
   template <int LIMIT> __device__ __forceinline__ void store(f64x2 *, int) const {}
+  __device__ __forceinline__ void drop() {}
 };
 
 // Lane layout of one FindSddMax/FindSddMin step (D joints, 2D candidates):
@@ -324,13 +349,14 @@ struct JointSweep {
   // 24 scalar-step cycles, 25 boundary-follow cycles, 26 init_carry cycles, 27 tile fills, 28 tile-fill
   // cycles, 29 init_carry calls, 30 blocks that finished their last step on the limit curve (leave_on_curve)
   long long diag[32];
-  // further slots. Backward wave, the closing barrier (C) of a switching-point loop by what the
-  // backward wave was doing when the forward wave posted "done": 0 loops in which it was still in
-  // its own extremal, 1 loops in which the post stopped its qd/qdd emission, 2 loops in which it was
-  // through with both; of the loops of case 1: 3 cycles from the post to the backward wave leaving
-  // emit_range, 4 cycles of its fence before the barrier, 5 cycles the forward wave then stood at
-  // the barrier before the backward wave reached it; 6 the same wait in the loops of case 0; 7 fence
-  // cycles of all loops; 8 trips of emit_range started inside loops.
+  // further slots: the loop queue. Forward wave, cycles it waited by cause: 0 a rare branch reads next
+  // to the switching point ("loop queue", 1 and 2), 1 marks inside an earlier first-step footprint (3),
+  // 2 ring full, 4 the join after the last loop; 5 entries whose first pair it left to the backward
+  // wave (forward first), 6 those of them that were lane 0's pair of a run on the limit curve; 9..11 how
+  // many waits of causes 0..2. Backward wave: 0 cycles waiting for an
+  // entry, 9 how many such waits; 1..4 entries taken at queue depth 1, 2, 3, 4; 5 / 6 entries found
+  // forward first / backward first at the end of its first step; 7 the join; 8 trips of emit_range
+  // started inside loops.
   mutable long long diagx[kDiagExt];
 #endif
   int N, lane;
@@ -349,6 +375,14 @@ struct JointSweep {
   const double *aml;
   uint32_t *dirty;
   int end_idx;            // sample at which the last extremal of this wave ended
+  // Loop queue of the two-wave kernel (see k_sweep_joint): the control words, the entry of the loop
+  // this wave is working on and its number.
+  int *qc, *qe;
+  int qn;
+  // forward wave: 0 nothing pending; 1 the extremal has not yet written its first (sd2[icrit+1],
+  // sdd[icrit]); 2 that pair was handed to the backward wave and may not be in the arrays yet
+  int pair_mode;
+  bool fw_first;          // backward wave: the forward wave's first pair waits in the entry
   // per-lane constants (roles are folded into data so that the hot loop has no role
   // branches): idle lanes carry lim = NaN (their candidate is NaN, hence rejected) and
   // vel_hi = +inf (their velocity check never fails).
@@ -384,6 +418,137 @@ struct JointSweep {
     __builtin_amdgcn_wave_barrier();
   }
 
+  // ---- loop queue: the pair protocol of one switching point (two-wave kernel) ---------------
+  // The forward wave runs ahead: it posts the loops in a ring in LDS and goes from one forward
+  // extremal to the next, the backward wave takes the loops in order (k_sweep_joint). In the
+  // reference's order (backward(c), then forward(c), loop by loop) the two waves could only meet at
+  // these places, h = iback_hi being c or c - 1:
+  //  (1) sd2[c+1], sdd[c]. backward(c)'s first step reads sd2[c+1] in its rare branches (negative
+  //      sd2, sdd_at_intersection) and, if h = c, writes sdd[c]; forward(c)'s first step then writes
+  //      both -- or neither if it stops at once or ends in sdd_at_intersection, see (2). Later steps of
+  //      backward(c) stay below c - 1, later steps of forward(c) read and write above c + 1, except
+  //      the forward rare branches at c + 1 and c + 2, which read sd2[c+1] again.
+  //      Who is first is settled by ONE compare-and-swap on the entry's state word: posted -> "backward
+  //      first" by the backward wave when its first step is COMPLETE and its writes are fenced
+  //      (pair_release), posted -> "forward first" by the forward wave when its first step has its
+  //      pair (pair_defer); exactly one of the two succeeds. Forward first: the pair is not written
+  //      but left in the entry, so the backward extremal's first step -- not begun, or under way --
+  //      sees exactly what the reference's sees; the backward wave finds its own transition refused,
+  //      writes the pair after its step's own sdd[c], as the reference orders them, and only then counts
+  //      the entry in kQDone1. Until then the forward wave's rare branches wait (pair_mode 2,
+  //      pair_settle); nothing else of the extremal reads sd2[c+1] -- the carried sd2 is in registers,
+  //      every look-ahead reads sd2[c+2] and above. Backward first: the step is over, the forward wave
+  //      writes the pair itself. Neither wave waits for the other here. (Claiming the entry when the
+  //      backward wave TAKES it made the forward wave wait out the backward wave's tile fill and first
+  //      step in 21 of 24 loops, 61 k cycles per path: profiles/sweep_runahead_ab.md.) An extremal that
+  //      starts with a run on the limit curve hands over lane 0's pair of that run in the same way
+  //      (follow_boundary).
+  //  (2) sd2[c-1], written by backward(c)'s first step if h = c, read by forward(c)'s first step in
+  //      its rare branches (intersection, negative sd2): these wait until kQDone1 counts the entry.
+  //  (3) The marks of the next loop, sd2[c'] and sd2[c'-1]. c' lies above the sample r >= c at which
+  //      forward(c) ended (the mid-point fall-back may give c' = r), so c' - 1 >= c, and the marks can
+  //      touch the footprint of (1) and (2) only if c' - 1 <= c + 1. Before such marks the forward wave
+  //      waits until kQDone1 counts every entry posted so far. (If c' = c, only through the fall-back
+  //      after a forward extremal that stopped at once, the marks repeat those of c with the same bits.)
+  //  Everything else is disjoint: backward extremals and the qd/qdd emission of loop c work below c,
+  //  on samples the forward wave finished before it posted c (release before the post, acquire after
+  //  the take); forward extremals, marks and the critical-point search of later loops work at c and
+  //  above; the search reads the static type bytes only.
+  static __device__ __forceinline__ void lds_store(int *p, int v) {
+    *(volatile __attribute__((address_space(3))) int *)p = v;
+  }
+  // Wait until control word `word` >= value; the time goes to diagx[CAUSE], the count to
+  // diagx[CAUSE + 9]. Bounded: false if the partner gave up or kQPollBound polls ran out (then both
+  // waves leave through the error exit with kStatusSweepPoll); callers go on, the path has failed.
+  template <int CAUSE>
+  __device__ __forceinline__ bool q_wait(int word, int value) const {
+    if (uniform_i32(lds_word(qc + word)) >= value) return true;
+#ifdef TPAMD_DIAG
+    const long long tw_ = tpamd_stamp();
+#endif
+    bool ok = false;
+    for (int n = 0;; n++) {
+      __builtin_amdgcn_s_sleep(1);
+      if (uniform_i32(lds_word(qc + word)) >= value) { ok = true; break; }
+      if (uniform_i32(lds_word(qc + kQAbort)) != 0) break;
+      if (n >= kQPollBound) {
+        if (lane == 0) { lds_store(qc + kQPollErr, 1); lds_store(qc + kQAbort, 1); }
+        break;
+      }
+    }
+#ifdef TPAMD_DIAG
+    diagx[CAUSE] += tpamd_stamp() - tw_;
+    diagx[CAUSE + 9] += 1;
+#endif
+    return ok;
+  }
+  // backward wave: the first step of the extremal of entry qn is complete
+  __device__ __forceinline__ void pair_release() {
+    // (its own writes of the step first: the pair of a forward wave that comes later lands after them)
+    __threadfence_block();
+    int old = 0;
+    if (lane == 0) {
+      int expected = 4 * qn + 1;
+      __hip_atomic_compare_exchange_strong(qe + kQeState, &expected, 4 * qn + 2, __ATOMIC_RELAXED,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      old = expected;
+    }
+    fw_first = uniform_i32(old) == 4 * qn + 3;
+    // (acquire: the pair in the entry is read after the transition was seen refused -- the fence, not
+    // only the LDS's in-order service of one wave, keeps the compiler from moving the reads up)
+    __threadfence_block();
+#ifdef TPAMD_DIAG
+    diagx[5] += fw_first;
+    diagx[6] += !fw_first;
+#endif
+    if (fw_first && lane == 0) {
+      const int c = lds_word(qe + kQeCrit);
+      const volatile __attribute__((address_space(3))) double *pd =
+          (const volatile __attribute__((address_space(3))) double *)(qe + kQeDeferred);
+      sd2[c + 1] = pd[0];
+      sdd_g[c] = pd[1];
+    }
+    __threadfence_block();
+    if (lane == 0) lds_store(qc + kQDone1, qn + 1);
+  }
+  // forward wave: the first step of the extremal of entry qn has its pair (sd2[c+1], sdd[c]) = (v, a).
+  // True: left in the entry for the backward wave to write. False: the caller writes it now.
+  __device__ __forceinline__ bool pair_defer(double v, double a) {
+    if (uniform_i32(lds_word(qc + kQDone1)) > qn) { pair_mode = 0; return false; }
+    int old = 0;
+    if (lane == 0) {
+      volatile __attribute__((address_space(3))) double *pd =
+          (volatile __attribute__((address_space(3))) double *)(qe + kQeDeferred);
+      pd[0] = v;
+      pd[1] = a;
+    }
+    __threadfence_block();
+    if (lane == 0) {
+      int expected = 4 * qn + 1;
+      __hip_atomic_compare_exchange_strong(qe + kQeState, &expected, 4 * qn + 3, __ATOMIC_RELAXED,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      old = expected;
+    }
+    old = uniform_i32(old);
+    if (old == 4 * qn + 1) {
+      TPAMD_CNTX(5);
+      pair_mode = 2;
+      return true;
+    }
+    // The backward wave's first step was complete and its writes fenced before its transition;
+    // (acquire) the caller's stores of the pair stay behind the refused transition.
+    __threadfence_block();
+    pair_mode = 0;
+    return false;
+  }
+  // forward wave, before a rare branch reads sd2 next to the switching point, and before a run on
+  // the limit curve that starts there
+  template <int CAUSE>
+  __device__ __forceinline__ void pair_settle() {
+    q_wait<CAUSE>(kQDone1, qn + 1);
+    pair_mode = 0;
+  }
+
   // ---- tile ring -----------------------------------------------------------
   // The prefetch registers live in the calling extremal (a struct-member array is not
   // promoted to registers). Loads always cover a full tile: a partial last tile reads at
@@ -397,6 +562,12 @@ struct JointSweep {
     RegPack<kChunksPerLane> r;
     double m;  // lanes 0..kTile-1: final sd2_max of sample t*kTile + lane
     int tag;   // tile index held in r (-1: none)
+    // Forget the tile: an unconditional definition, so that the registers are free up to here.
+    __device__ __forceinline__ void drop() {
+      r.drop();
+      m = 0.0;
+      tag = -1;
+    }
   };
   __device__ __forceinline__ void issue_tile_loads(int t, Prefetch &pf) const {
     const f64x2 *src = reinterpret_cast<const f64x2 *>(rec + (size_t)t * kTile * R);
@@ -497,22 +668,22 @@ struct JointSweep {
   // are software-pipelined: the loads of the next trip are issued before the arithmetic and the
   // stores of this one (emit_trips). Wave `wv` of `nwv` waves takes every nwv-th trip (one wave:
   // 0 of 1; the workgroup: tid >> 6 of 2).
-  // stop != nullptr (a word of LDS): give up as soon as *stop == stop_value, checked between trips
-  // -- the partner wave has finished and must not be kept waiting. Returns the first sample NOT
-  // written (hi + 1 if the range was completed).
+  // stop != nullptr (a word of LDS, the count of posted loops): give up as soon as *stop != go_value,
+  // checked between trips -- the forward wave has posted the next loop, whose backward extremal comes
+  // first. Returns the first sample NOT written (hi + 1 if the range was completed).
   __device__ __forceinline__ int emit_range(int lo, int hi, int wv, int nwv, const int *stop = nullptr,
-                                            int stop_value = 0) const {
-    if (qd_g != nullptr && qdd_g != nullptr) return emit_trips<true, true>(lo, hi, wv, nwv, stop, stop_value);
-    if (qd_g != nullptr) return emit_trips<true, false>(lo, hi, wv, nwv, stop, stop_value);
-    if (qdd_g != nullptr) return emit_trips<false, true>(lo, hi, wv, nwv, stop, stop_value);
+                                            int go_value = 0) const {
+    if (qd_g != nullptr && qdd_g != nullptr) return emit_trips<true, true>(lo, hi, wv, nwv, stop, go_value);
+    if (qd_g != nullptr) return emit_trips<true, false>(lo, hi, wv, nwv, stop, go_value);
+    if (qdd_g != nullptr) return emit_trips<false, true>(lo, hi, wv, nwv, stop, go_value);
     return hi + 1;
   }
   template <bool QD, bool QDD>
   __device__ __forceinline__ int emit_trips(int lo, int hi, int wv, int nwv, const int *stop,
-                                            int stop_value) const {
+                                            int go_value) const {
     int s0 = lo + 64 * wv;
     if (hi < lo || s0 > hi) return hi + 1;
-    if (stop != nullptr && uniform_i32(lds_word(stop)) == stop_value) return s0;
+    if (stop != nullptr && uniform_i32(lds_word(stop)) != go_value) return s0;
     const int step = 64 * nwv;
     const f64x2 *rec2 = reinterpret_cast<const f64x2 *>(rec);
     // (a whole trip ahead where the register budget allows it: D <= 8 stays under the 208 VGPRs
@@ -596,7 +767,7 @@ struct JointSweep {
         }
         s0 = nxt;
         if (s0 > hi) return hi + 1;
-        if (stop != nullptr && uniform_i32(lds_word(stop)) == stop_value) return s0;
+        if (stop != nullptr && uniform_i32(lds_word(stop)) != go_value) return s0;
       }
     }
   }
@@ -798,30 +969,26 @@ struct JointSweep {
   // One step of AddForwardExtremal (.cc:774-855) / AddBackwardExtremal (.cc:864-950): uses
   // the rows in `use`, stages the next step's rows into `stage`. Returns kContinue or the
   // extremal's return value. pair_signal: see add_extremal.
-  // pair_wait (two-wave kernel, first step of a forward extremal): the partner's backward
-  // extremal of the same switching point is running its first step, the only one that touches
-  // samples this extremal touches: it may write sd2[icrit-1] and sdd[icrit] and may read
-  // sd2[icrit+1] (see add_extremal). This step therefore runs up to the point where it would
-  // write (sd2[icrit+1], sdd[icrit]) or read sd2[icrit-1] (intersection, negative sd2) and takes
-  // the partner's release barrier there, not before it starts: the two first steps overlap.
+  // pair_mode (two-wave kernel, forward extremal): the partner's backward extremal of the same
+  // switching point may not have run its first step yet, the only one that touches samples this
+  // extremal touches: it may write sd2[icrit-1] and sdd[icrit] and may read sd2[icrit+1] ("loop
+  // queue" above). The first step therefore runs up to the point where it would write
+  // (sd2[icrit+1], sdd[icrit]) -- pair_defer -- or read sd2[icrit-1] (intersection, negative sd2)
+  // -- pair_settle --; later steps settle before a rare branch reads next to the switching point.
   template <bool FWD>
   __device__ __forceinline__ int extremal_step(Carry &c, const Rows &use, Rows &stage, Prefetch &pf,
-                                               int idx_start, bool &pair_signal, bool &pair_wait) {
+                                               int idx_start, bool &pair_signal) {
     constexpr int dir = FWD ? 1 : -1;
 #define TPAMD_PAIR_SIGNAL()                                   \
   do {                                                        \
     if (pair_signal) {                                        \
-      __threadfence_block();                                  \
-      __syncthreads();                                        \
+      pair_release();                                         \
       pair_signal = false;                                    \
     }                                                         \
   } while (0)
 #define TPAMD_PAIR_WAIT()                                     \
   do {                                                        \
-    if (FWD && pair_wait) {                                   \
-      __syncthreads();                                        \
-      pair_wait = false;                                      \
-    }                                                         \
+    if (FWD && pair_mode != 0) pair_settle<0>();              \
   } while (0)
     const int idx = c.idx;
     const int nidx = idx + dir;
@@ -863,8 +1030,7 @@ struct JointSweep {
                             : ((type_invalid || deriv_invalid) && !(idx_start != (N - 1)));
       if (stop) {
         end_idx = idx;
-        TPAMD_PAIR_SIGNAL();
-        TPAMD_PAIR_WAIT();
+        TPAMD_PAIR_SIGNAL();     // (a forward extremal that stops here has touched nothing)
         return idx;
       }
       sd2tmp = m_n;
@@ -881,9 +1047,10 @@ struct JointSweep {
         if (idx < N - 1) sddtmp = sd2[idx + 1] / ds; else sddtmp = 0.0;
       }
     }
-    TPAMD_PAIR_WAIT();
-    put_sd2(nidx, sd2tmp);
-    put_sdd(idx, sddtmp);
+    if (!(FWD && pair_mode == 1 && pair_defer(sd2tmp, sddtmp))) {
+      put_sd2(nidx, sd2tmp);
+      put_sdd(idx, sddtmp);
+    }
     if (!more) end_idx = nidx;
     TPAMD_PAIR_SIGNAL();
     if (!more) return FWD ? N - 1 : 0;
@@ -909,6 +1076,8 @@ struct JointSweep {
   // scalar code would treat specially (intersection with an earlier extremal, negative
   // curve value, loop end) are not eligible and fall to the scalar step. Returns the
   // number of steps taken (0..64) and advances c.idx / c.cur.
+  // (Loop queue: after a forward extremal's first step sd2[icrit+1] may still be in the queue entry,
+  // not in the array. This function reads sd2 from c.idx + 1 up, and c.idx >= icrit + 1 then: keep it so.)
   template <bool FWD>
   __device__ __forceinline__ int follow_boundary(Carry &c) {
     constexpr int dir = FWD ? 1 : -1;
@@ -935,9 +1104,19 @@ struct JointSweep {
     if (L == 0) return 0;
     const double cur_k = (lane == 0) ? c.cur : m_j;
     const double sddv = FWD ? 0.5 * (m_jn - cur_k) / ds : 0.5 * (cur_k - m_jn) / ds;
-    if (lane < L) {
+    // (a forward extremal's first run: lane 0's pair is the first pair of the extremal, "loop queue" 1)
+    const bool first = FWD && pair_mode == 1;
+    if (lane < L && !(first && lane == 0)) {
       sd2[j + dir] = m_jn;
       sdd_g[j] = sddv;
+    }
+    if (first) {
+      if (pair_defer(readlane_f64(m_jn, 0), readlane_f64(sddv, 0))) {
+        TPAMD_CNTX(6);
+      } else if (lane == 0) {
+        sd2[j + dir] = m_jn;
+        sdd_g[j] = sddv;
+      }
     }
     wave_lds_sync();
     c.idx += dir * L;
@@ -964,6 +1143,8 @@ struct JointSweep {
   // is verified (it is what the scalar step would compute) but the new sd2 exceeds the limit curve
   // (.cc:806 / :896). c.m_i / c.m_n / c.t_n then hold that step's boundary data and the caller goes
   // on with leave_on_curve instead of a scalar step that would find the same sdd again.
+  // (Loop queue: after a forward extremal's first step sd2[icrit+1] may still be in the queue entry,
+  // not in the array. This function reads sd2 from c.idx + 1 up, and c.idx >= icrit + 1 then: keep it so.)
   template <bool FWD>
   __device__ __forceinline__ int follow_chain(Carry &c, Prefetch &pf, int &next_win, bool &curve) {
     constexpr int dir = FWD ? 1 : -1;
@@ -1113,6 +1294,7 @@ struct JointSweep {
     double sd2tmp = m_n, sddtmp = sdd_bound;
     c.win = -1;
     if (sd2tmp < 0) {
+      if (FWD && pair_mode != 0) pair_settle<0>();
       sd2tmp = 0.0;
       if (FWD) {
         if (idx <= 1) sddtmp = 0.0; else sddtmp = -sd2[idx - 1] / ds;
@@ -1132,6 +1314,9 @@ struct JointSweep {
   }
 
   // (Re)start the carried state at sample idx: tiles, rows, neighbours.
+  // (Loop queue: after a forward extremal's first step sd2[icrit+1] may still be in the queue entry,
+  // not in the array. Restarts inside an extremal pass load_cur = false and read sd2[idx + 1] only,
+  // with idx >= icrit + 1: a restart that reloads sd2[idx] must settle first, see pair_settle.)
   template <bool FWD>
   __device__ __forceinline__ void init_carry(int idx, Carry &c, Rows &rows, Prefetch &pf, bool load_cur) {
     constexpr int dir = FWD ? 1 : -1;
@@ -1154,41 +1339,37 @@ struct JointSweep {
   }
 
   // AddForwardExtremal (.cc:769-857) for FWD, AddBackwardExtremal (.cc:859-952) otherwise.
-  // pair_signal (two-wave kernel, backward extremal only): release the partner wave, which
-  // runs the forward extremal of the same switching point, once this extremal's FIRST step
-  // is complete. Only that step can touch what the partner reads (sd2[icrit-1], sdd[icrit]);
-  // afterwards the two extremals work on disjoint index ranges.
+  // pair_signal (two-wave kernel, backward extremal only): tell the partner wave, which runs
+  // the forward extremal of the same switching point, that this extremal's FIRST step is
+  // complete (pair_release). Only that step can touch what the partner reads or writes
+  // (sd2[icrit-1], sd2[icrit+1], sdd[icrit]); afterwards the two extremals work on disjoint
+  // index ranges.
   // The scalar loop is unrolled by two so that the two row sets swap roles without copies.
   template <bool FWD>
   // `pf`: tile prefetch registers, possibly already holding the start tile (see the kernel).
-  // wait_pair (two-wave kernel, forward extremal only): the partner's release barrier is
-  // taken after this extremal's own set-up (tile fill, row loads), which touches nothing the
-  // partner's first step writes.
+  // wait_pair (two-wave kernel, forward extremal only): the partner's first step may still be
+  // to come (pair_mode 1). This extremal's own set-up (tile fill, row loads) touches nothing that
+  // step writes.
   __device__ __forceinline__ int add_extremal(int idx_start, Prefetch &pf, bool pair_signal = false,
                                               bool wait_pair = false) {
 #define TPAMD_PAIR_SIGNAL()                                   \
   do {                                                        \
     if (pair_signal) {                                        \
-      __threadfence_block();                                  \
-      __syncthreads();                                        \
+      pair_release();                                         \
       pair_signal = false;                                    \
     }                                                         \
   } while (0)
+    pair_mode = (FWD && wait_pair) ? 1 : 0;
     if (FWD ? !(idx_start < N - 2) : !(idx_start > 1)) {
       end_idx = idx_start;
       TPAMD_PAIR_SIGNAL();
-      if (wait_pair) __syncthreads();
       return FWD ? N - 1 : 0;
     }
     Rows rows_a, rows_b;
     Carry c;
     init_carry<FWD>(idx_start, c, rows_a, pf, true);
-    // An extremal that starts on the boundary curve writes a whole run at once: wait first. Else
-    // the first step takes the barrier itself, as late as it can (extremal_step).
-    if (wait_pair && is_tiny(c.cur - c.m_i) && (c.t_i & kBndTrajectory) && (c.t_n & kBndTrajectory)) {
-      __syncthreads();
-      wait_pair = false;
-    }
+    // (the first step settles with the partner itself, as late as it can: extremal_step, or
+    // follow_boundary for an extremal that starts with a run on the limit curve)
     bool trust = true;
     int last_win = -1;
     for (;;) {
@@ -1247,7 +1428,7 @@ struct JointSweep {
   }
       TPAMD_TRY_FOLLOW();
       TPAMD_T0(ts1_);
-      int r = extremal_step<FWD>(c, rows_a, rows_b, pf, idx_start, pair_signal, wait_pair);
+      int r = extremal_step<FWD>(c, rows_a, rows_b, pf, idx_start, pair_signal);
       TPAMD_ACC(24, ts1_);
       if (r != kContinue) return r;
       TPAMD_TRY_CHAIN();
@@ -1257,7 +1438,7 @@ struct JointSweep {
         continue;
       }
       TPAMD_T0(ts2_);
-      r = extremal_step<FWD>(c, rows_b, rows_a, pf, idx_start, pair_signal, wait_pair);
+      r = extremal_step<FWD>(c, rows_b, rows_a, pf, idx_start, pair_signal);
       TPAMD_ACC(24, ts2_);
       if (r != kContinue) return r;
       TPAMD_TRY_CHAIN();
@@ -1867,7 +2048,7 @@ __device__ __forceinline__ void boundary_passes_for_path(const JointSource &src,
 
 // Dynamic LDS of one path (bytes):
 //   sd2[N2]*8 | tile rings 2 waves x 2 slots x 32 x R*8 | type copy N (padded to 16) |
-//   exchange words 64 | dirty bitmap | zero-pair bitmap | a_max[16]*8 | reduction scratch 32
+//   exchange words 64 + loop queue 256 | dirty bitmap | zero-pair bitmap | a_max[16]*8 | reduction scratch 32
 // N2 = N rounded up to even (16-byte alignment of the rings). After the switching-point loop
 // the rings hold one chunk of dt / time values and the type copy holds the list of samples
 // whose qd/qdd are redone (see the tail).
@@ -1875,11 +2056,12 @@ template <int D, int E = 0>
 struct SweepLds {
   static constexpr int R = 2 * D + E + 2;
   static constexpr int kRingDoubles = 2 * 2 * TileCfg<D>::kSamples * R;
+  static constexpr int kXchgWords = 16 + kQRing * kQEntryWords;   // exchange words, then the loop queue
   __host__ __device__ static constexpr int n2(int N) { return (N + 1) & ~1; }
   __host__ __device__ static constexpr int words(int N) { return ((N + 31) / 32 + 1) & ~1; }
   __host__ __device__ static constexpr int type_bytes(int N) { return ((N + 15) / 16) * 16; }
   __host__ __device__ static constexpr size_t bytes(int N) {
-    return (size_t)n2(N) * 8 + (size_t)kRingDoubles * 8 + type_bytes(N) + 64 +
+    return (size_t)n2(N) * 8 + (size_t)kRingDoubles * 8 + type_bytes(N) + 4 * kXchgWords +
            2 * (size_t)words(N) * 4 + 16 * 8 + 32;
   }
 };
@@ -1938,7 +2120,7 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   S.typel = typel;
   int *xchg = reinterpret_cast<int *>(typel + LL::type_bytes(N));
   const int nw = LL::words(N);
-  uint32_t *dirty = reinterpret_cast<uint32_t *>(xchg + 16);
+  uint32_t *dirty = reinterpret_cast<uint32_t *>(xchg + LL::kXchgWords);
   uint32_t *zero = dirty + nw;
   double *aml = reinterpret_cast<double *>(zero + nw);
   double *red = aml + 16;
@@ -1951,6 +2133,8 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   S.qdd_g = qdd_out ? qdd_out + pb * D : nullptr;
   S.end_idx = 0;
   S.tag0 = -1; S.tag1 = -1;
+  S.qc = xchg; S.qe = xchg + 16; S.qn = 0;
+  S.pair_mode = 0; S.fw_first = false;
   double *sd2 = S.sd2;
   const double sd_start = ws.sd_start[b];
 #ifdef TPAMD_DIAG
@@ -1958,9 +2142,6 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   long long(&diagx)[kDiagExt] = S.diagx;
   for (int k = 0; k < 32; k++) diag[k] = 0;
   for (int k = 0; k < kDiagExt; k++) diagx[k] = 0;
-  // (closing barrier of a loop: the forward wave leaves its stamps in two spare words of the
-  // reduction scratch, which the product uses only at the kernel's end)
-  volatile long long *fw_stamp = reinterpret_cast<volatile long long *>(red + 2);   // [0] done-post, [1] at the barrier
 #define TPAMD_DIAG_PTR S.diag
 #else
 #define TPAMD_DIAG_PTR nullptr
@@ -2040,7 +2221,7 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   __syncthreads();
   if (tid == 0) {
     xchg[2] = 0;
-    xchg[6] = 0;
+    xchg[kQPosted] = 0; xchg[kQDone1] = 0; xchg[kQAbort] = 0; xchg[kQStatus] = 0; xchg[kQPollErr] = 0;
     sd2[0] = sd_start * sd_start;
     sd2[N - 1] = 0;
   }
@@ -2121,143 +2302,163 @@ k_sweep_joint(int stride, int max_loops, JointSource src, Workspace ws, double *
   const int zlast = uniform_i32(S.last_flagged_below(icrit_hi));   // icrit_hi is final from here on
   const double *m_g = ws.m + pb;
   if (max_loops <= 0) max_loops = max(100, 10 * N);   // path_timing_trajectory.cc:398-400
-  // The switching-point loop, .cc:329-397. What a loop needs before its two extremals can start --
-  // the next critical point (a scan of the type bytes above the forward extremal's end) and the
-  // limit-curve values next to it (two global loads) -- depends on nothing the backward wave
-  // produces, so the forward wave finds them right after its own extremal, while the backward wave
-  // finishes its qd/qdd trip, and posts them in LDS before the loop's closing barrier: a loop is two
-  // workgroup barriers (A, C) with nothing but the marks between C and A.
-  double *crit_m = reinterpret_cast<double *>(xchg + 10);     // [0] sd2_max[icrit], [1] sd2_max[icrit - 1]
-  auto post_next_critical_point = [&](int lo) {               // forward wave only
-    TPAMD_T0(t0);
-    int ic = uniform_i32(S.next_critical_point(lo, icrit_hi, zlast));
-    TPAMD_ACC(2, t0);
+  // The switching-point loop, .cc:329-397, as a producer and a consumer. The chain of forward
+  // extremals depends on nothing the backward wave produces: the next critical point is a scan of
+  // the static type bytes above the forward extremal's end (next_critical_point), the limit-curve
+  // values next to it are two global loads, and a forward extremal from icrit reads sd2 at icrit
+  // and above. So the forward wave goes from the end of one forward extremal straight to the marks
+  // and the forward extremal of the next loop and leaves each loop -- its number, icrit, iback_hi,
+  // icrit_lo -- in a ring of kQRing entries in LDS; the backward wave takes the entries in order:
+  // backward extremal, the `iback_lo > icrit_lo` check (status 7), then qd/qdd below icrit until the
+  // next entry is posted. Between the first pair and the join after the last loop there is no
+  // workgroup barrier; where the two waves can touch the same samples is listed at "loop queue" in
+  // JointSweep, with the wait or hand-over that keeps the reference's order there. A loop that
+  // fails ends the consumer at that entry (status 7, or status 10 posted by the producer as an
+  // entry of its own, hence seen in loop order); the producer sees kQAbort at its next entry or in
+  // any wait. At most max_loops loops are posted, then an end entry.
+  __syncthreads();     // the NaN mark above is visible
+  if (w == 1) {
+    int posted = 0, last_c = 0;
+    for (int loop = 0;; loop++) {
+      int kind = (loop >= max_loops || iforw_hi >= icrit_hi) ? kQKindEnd : kQKindLoop;
+      if (uniform_i32(lds_word(xchg + kQAbort)) != 0) break;
+      int ic = 0, bh = 0;
+      double mc = 0.0, mp = 0.0;
+      if (kind == kQKindLoop) {
+        TPAMD_CNT(11);
+        TPAMD_T0(t0);
+        ic = uniform_i32(S.next_critical_point(icrit_lo, icrit_hi, zlast));
+        TPAMD_ACC(2, t0);
 #if defined(TPAMD_DIAG) && !defined(TPAMD_DIAG_LIGHT)
-    {
-      TPAMD_T0(tl_);
-      if (ic != S.next_critical_point_literal(lo, icrit_hi)) TPAMD_CNT(7);
-      TPAMD_ACC(18, tl_);
-    }
+        {
+          TPAMD_T0(tl_);
+          if (ic != S.next_critical_point_literal(icrit_lo, icrit_hi)) TPAMD_CNT(7);
+          TPAMD_ACC(18, tl_);
+        }
 #endif
-    if (ic < 0 || ic >= N) ic = (int)(0.5 * (lo + icrit_hi));
-    const double mc = m_g[min(max(ic, 0), N - 1)], mp = m_g[min(max(ic - 1, 0), N - 1)];
-    if (ic >= 1) {
-      // the tile the next forward extremal starts in: its loads fly during the barrier
-      const int ts = ic / JS::kTile;
-      const int tag = (ts & 1) ? S.tag1 : S.tag0;
-      if (tag != ts && pf.tag != ts) S.issue_tile_loads(ts, pf);
+        if (ic < 0 || ic >= N) ic = (int)(0.5 * (icrit_lo + icrit_hi));
+        if (ic >= 1) {
+          // the tile this forward extremal starts in: its loads fly together with the two limit-curve
+          // loads below and during the marks and the post
+          const int ts = ic / JS::kTile;
+          const int tag = (ts & 1) ? S.tag1 : S.tag0;
+          if (tag != ts && pf.tag != ts) S.issue_tile_loads(ts, pf);
+        }
+        mc = uniform_f64(m_g[min(max(ic, 0), N - 1)]);
+        mp = uniform_f64(m_g[min(max(ic - 1, 0), N - 1)]);
+        if (ic < 1) kind = kQKindCritZero;
+        bh = (mp <= mc) ? ic - 1 : ic;
+      }
+      // ring full: the slot's previous entry must be past its first step (nothing of an entry is
+      // read after that)
+      if (!S.template q_wait<2>(kQDone1, posted - (kQRing - 1))) break;
+      if (kind == kQKindLoop) {
+        // marks inside the first-step footprint of the entry before ("loop queue", 3)
+        if (posted > 0 && ic - 1 <= last_c + 1 && !S.template q_wait<1>(kQDone1, posted)) break;
+        if (ic < N - 1) S.put_sd2(ic, mc);
+        if (mp <= mc) S.put_sd2(ic - 1, mp);
+      }
+      int *q = xchg + 16 + kQEntryWords * (posted & (kQRing - 1));
+      if (lane == 0) {
+        q[kQeCrit] = ic;
+        q[kQeBackHi] = bh;
+        q[kQeCritLo] = icrit_lo;
+        q[kQeKind] = kind;
+      }
+      // (release: the marks, the entry and everything earlier forward extremals wrote -- sd2 in LDS,
+      // sdd with plain global stores -- before the post)
+      __threadfence_block();
+      if (lane == 0) {
+        JS::lds_store(q + kQeState, 4 * posted + 1);
+        JS::lds_store(xchg + kQPosted, posted + 1);
+      }
+      if (kind != kQKindLoop) break;
+      S.qe = q;
+      S.qn = posted;
+      posted++;
+      last_c = ic;
+      TPAMD_T0C(t0);
+      const int r = S.template add_extremal<true>(ic, pf, false, /*wait_pair=*/true);
+      TPAMD_ACCC(0, t0);
+      iforw_hi = r;
+      icrit_lo = r;
+    }
+    if (lane == 0) xchg[3] = S.end_idx;          // where the last forward extremal ended
+  } else {
+    int taken = 0;
+    for (;;) {
+      if (!S.template q_wait<0>(kQPosted, taken + 1)) break;
+      __threadfence_block();                     // (acquire: pairs with the release before the post)
+      int *q = xchg + 16 + kQEntryWords * (taken & (kQRing - 1));
+      const int kind = uniform_i32(lds_word(q + kQeKind));
+      if (kind != kQKindLoop) {
+        if (kind == kQKindCritZero) status = 10;
+        break;
+      }
+      TPAMD_CNT(11);
+      icrit = uniform_i32(lds_word(q + kQeCrit));
+      iback_hi = uniform_i32(lds_word(q + kQeBackHi));
+      icrit_lo = uniform_i32(lds_word(q + kQeCritLo));
+#ifdef TPAMD_DIAG
+      {
+        const int depth = uniform_i32(lds_word(xchg + kQPosted)) - taken;
+        diagx[1] += depth == 1;      // (constant slots: a computed one would put the arrays in scratch memory)
+        diagx[2] += depth == 2;
+        diagx[3] += depth == 3;
+        diagx[4] += depth >= 4;
+      }
+#endif
+      {
+        const int ts = (icrit - 1) / JS::kTile;
+        const int tag = (ts & 1) ? S.tag1 : S.tag0;
+        if (tag != ts && pf.tag != ts) S.issue_tile_loads(ts, pf);
+      }
+      S.qe = q;
+      S.qn = taken;
+      TPAMD_T0C(t0);
+      const int r = S.template add_extremal<false>(iback_hi, pf, /*pair_signal=*/true);
+      TPAMD_ACCC(0, t0);
+      // (Every way out of a backward extremal's first step has released the entry: the early return
+      // of add_extremal, a run of follow_boundary, and the three exits of extremal_step -- intersection,
+      // stop on the limit curve, the written step -- each pass TPAMD_PAIR_SIGNAL; a first
+      // follow_boundary that takes no step falls through to extremal_step.)
+      taken++;
+      iback_lo = r;
+      if (iback_lo > icrit_lo) { status = 7; break; }
+      // The forward wave is at work on samples >= icrit, in this loop or a later one: write qd/qdd
+      // for everything below icrit that is new or was changed by this backward extremal (it ended at
+      // end_idx) -- until the next loop is posted: the rest waits for a later loop or the tail.
+      TPAMD_T0C(te);
+      emitted_hi = uniform_i32(S.emit_range(max(min(S.end_idx - 1, emitted_hi), 0), icrit - 1,
+                                            0, 1, xchg + kQPosted, taken));
+      TPAMD_ACCC(12, te);
+      // What the backward extremal left in the prefetch registers is the tile BELOW its end, of no use
+      // to the next one, which starts higher up: dropped, so that emit_range has those registers
+      // (with them the 7-joint kernel needs 217 VGPRs, above the 208 the pipelined modes rest on).
+      pf.drop();
     }
     if (lane == 0) {
-      xchg[9] = ic;
-      crit_m[0] = mc;
-      crit_m[1] = mp;
+      xchg[kQStatus] = status;
+      if (status != 0) JS::lds_store(xchg + kQAbort, 1);
+      xchg[4] = emitted_hi;
+      xchg[5] = upper_lo;
     }
-  };
-  __syncthreads();     // the NaN mark above is visible (the literal walk of the diagnostic build reads sd2)
-  if (w == 1 && iforw_hi < icrit_hi) post_next_critical_point(icrit_lo);
-  __threadfence_block();
-  __syncthreads();
-  for (int loop = 0; loop < max_loops; loop++) {
-    if (iforw_hi >= icrit_hi) break;
-    TPAMD_CNT(11);
-#ifdef TPAMD_DIAG
-    int bw_case = 2;
-    long long bw_left = 0;
-#endif
-    icrit = uniform_i32(xchg[9]);
-    const double m_c = uniform_f64(crit_m[0]), m_p = uniform_f64(crit_m[1]);
-    if (w == 0 && icrit >= 1) {
-      const int ts = (icrit - 1) / JS::kTile;
-      const int tag = (ts & 1) ? S.tag1 : S.tag0;
-      if (tag != ts && pf.tag != ts) S.issue_tile_loads(ts, pf);
-    }
-    // (both waves are past their extremals: nobody reads sd2 while the marks are written)
-    if (icrit > 0 && icrit < N - 1 && w == 0) S.put_sd2(icrit, m_c);
-    if (icrit < 1) { status = 10; break; }
-    if (m_p <= m_c) {
-      iback_hi = icrit - 1;
-      if (w == 0) S.put_sd2(icrit - 1, m_p);
-    } else {
-      iback_hi = icrit;
-    }
-    iforw_lo = icrit;
-    __syncthreads();                 // A: the marks are visible to the forward wave
-    {
-      TPAMD_T0C(t0);
-      if (w == 0) {
-        const int r = S.template add_extremal<false>(iback_hi, pf, /*pair_signal=*/true);   // B inside
-        if (lane == 0) xchg[0] = r;
-#ifdef TPAMD_DIAG
-        const bool fw_was_done = lds_word(xchg + 6) == loop + 1;
-#endif
-        // The forward extremal of this loop works on samples >= icrit and usually takes
-        // longer: write qd/qdd for everything below icrit that is new or was changed by this
-        // backward extremal (it ended at end_idx) while waiting for it.
-        // -- but only until that one is done (xchg[6] then holds this loop's number): the
-        // rest waits for the next loop or the tail.
-        TPAMD_T0C(te);
-        emitted_hi = uniform_i32(S.emit_range(max(min(S.end_idx - 1, emitted_hi), 0), icrit - 1,
-                                              0, 1, xchg + 6, loop + 1));
-        TPAMD_ACCC(12, te);
-#ifdef TPAMD_DIAG
-        bw_case = fw_was_done ? 0 : (lds_word(xchg + 6) == loop + 1) ? 1 : 2;
-        bw_left = tpamd_stamp();
-#endif
-      } else {
-        const int r = S.template add_extremal<true>(iforw_lo, pf, false, /*wait_pair=*/true);   // B inside
-#ifdef TPAMD_DIAG
-        { const long long t = tpamd_stamp(); if (lane == 0) fw_stamp[0] = t; }
-#endif
-        if (lane == 0) {
-          xchg[1] = r;
-          *reinterpret_cast<volatile int *>(xchg + 6) = loop + 1;
-        }
-        if (r < icrit_hi) post_next_critical_point(r);      // for the next loop, if there is one
-#ifdef TPAMD_DIAG
-        { const long long t = tpamd_stamp(); if (lane == 0) fw_stamp[1] = t; }
-#endif
-      }
-      TPAMD_ACCC(0, t0);
-    }
-    {
-      TPAMD_T0C(t0);
-      __threadfence_block();
-#ifdef TPAMD_DIAG
-      const long long fenced = tpamd_stamp();
-#endif
-      __syncthreads();               // C
-      TPAMD_ACCC(1, t0);             // time spent waiting for the partner's extremal
-#ifdef TPAMD_DIAG
-      if (w == 0) {                  // how the forward wave's wait splits up (JointSweep::diagx)
-        const long long fw_done = fw_stamp[0], fw_at_c = fw_stamp[1];
-        const long long fw_wait = (fenced > fw_at_c) ? fenced - fw_at_c : 0;
-        diagx[0] += bw_case == 0;      // (constant slots: a computed one would put the arrays in scratch memory)
-        diagx[1] += bw_case == 1;
-        diagx[2] += bw_case == 2;
-        diagx[7] += fenced - t0;
-        if (bw_case == 1) {
-          diagx[3] += bw_left - fw_done;
-          diagx[4] += fenced - t0;
-          diagx[5] += fw_wait;
-        } else if (bw_case == 0) {
-          diagx[6] += fw_wait;
-        }
-      }
-#endif
-    }
-    iback_lo = uniform_i32(xchg[0]);
-    iforw_hi = uniform_i32(xchg[1]);
-    if (iback_lo > icrit_lo) { status = 7; break; }
-    icrit_lo = iforw_hi;
   }
   TPAMD_ACCC(5, t_all);
-  if (lane == 0) {
-    if (w == 0) { xchg[4] = emitted_hi; xchg[5] = upper_lo; }
-    else xchg[3] = S.end_idx;          // where the last forward extremal ended
+  // The join. sdd_, qd, qdd were written with plain global stores; make them visible to both waves
+  {
+#ifdef TPAMD_DIAG
+    const long long tj_ = tpamd_stamp();
+#endif
+    __threadfence_block();
+    __syncthreads();
+#ifdef TPAMD_DIAG
+    if (w == 1) diagx[4] += tpamd_stamp() - tj_;
+    else diagx[7] += tpamd_stamp() - tj_;
+#endif
   }
-  // sdd_, qd, qdd were written with plain global stores; make them visible to both waves
-  __threadfence_block();
-  __syncthreads();
+  status = uniform_i32(xchg[kQStatus]);
+  if (uniform_i32(xchg[kQPollErr]) != 0) status = kStatusSweepPoll;
 
   // ---------------------------------------------------------------------------------------
   // Tail (time_optimal_path_timing.cc:398-477), shared by the two waves. `status` is uniform

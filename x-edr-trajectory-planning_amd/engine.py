@@ -24,7 +24,7 @@ _SO = os.environ.get("TPAMD_LIBRARY") or os.path.join(_abi._CSRC, "libtpamd.so")
 PATH_STATUS = {
     0: "ok", 2: "infeasible_bounds", 3: "s_range", 4: "sd_start_negative",
     5: "lower_ge_upper", 6: "too_few_samples", 7: "no_connection", 8: "nan_sd2",
-    9: "nonzero_end", 10: "crit_index_zero", 11: "no_waypoints",
+    9: "nonzero_end", 10: "crit_index_zero", 11: "no_waypoints", 12: "sweep_poll_expired",
 }
 
 KERNEL_SWEEP = 4
